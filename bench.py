@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - the hot path's headline metric on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--n 512]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--n 512] [--full] [--dump-outputs DIR]
 
 Workload (BASELINE.json: "fine-grid LUP/s + V-cycles/sec at 512^3 fp64"):
 config[2], the 512^3 vector-potential problem on ONE GPU - one STEP is one
@@ -14,7 +14,16 @@ value = fine-grid lattice-point updates per second over the WHOLE V-cycle:
         (coarse levels, residual, transfers, the convergence metric of update_u
         and the host's read-back of it are all inside the timed region and count
         as overhead, not as updates).
-Extra keys: vcycles_per_s, smoother (kernel-only, HIP events on the library
+ms_per_step = wall time of the K timed steps / K.
+
+A plain run sets up, runs W warm-up steps, times K steps, writes the outputs
+(--dump-outputs DIR: the solution u after the last timed step, all of it up to
+2^22 points, else a fixed seeded sample of 2^22 points, and the solve loop's
+returns, as .npy in float64) and prints the headline line.  N > 1 keeps its
+slab self-check and schedule trial there: they decide what is timed.
+
+Extra keys, measured after the timed steps with --full only:
+vcycle_without_metric_ms, smoother (kernel-only, HIP events on the library
 stream), roofline = the kernel that dominates the timed region (two-sweep
 Laplace launch of level 1): achieved / frac = HBM bytes the launch really moved
 (rocprofv3 counters, measured in this run) / launch time / 8 TB/s, with the
@@ -22,7 +31,8 @@ algorithmic figure (16 B/LUP x 2 sweeps) beside it as frac_algorithmic;
 roofline_general_rhs (the same launch with a right-hand side in HBM), solve
 (whole Ax solve to vc_tol=1e-10), configs (BASELINE configs 0, 1, 3 on this GPU),
 end_to_end / end_to_end_small (ndsm_vector_solve wall time, host buffers in and
-out), cpu_baseline (the reference itself on this box's host cores, same grid).
+out), cpu_baseline (the reference itself on this box's host cores, same grid);
+N > 1: same_workload_on_one_gpu.
 
 One process per GPU.  `python3 bench.py --gpus N` without a launcher starts its
 own N ranks (torch.distributed.run as a child, before anything touches a GPU)
@@ -481,6 +491,62 @@ def slab_self_check(_lib, L, dist, rank, world):
     return f"MISMATCH: {nd} points differ, max {np.abs(got - want).max():.3e} (" + tag + ")"
 
 
+DUMP_POINTS = 1 << 22     # at most this many points of the solution (32 MiB of fp64) go to --dump-outputs
+
+
+def dump_sample_index(npts):
+    """flat C-order indices of the fine-grid points --dump-outputs writes, ascending: None (every point) while
+    they fit in DUMP_POINTS, else a fixed seeded sample of DUMP_POINTS distinct points"""
+    if npts <= DUMP_POINTS:
+        return None
+    return np.sort(np.random.default_rng(2112).choice(npts, DUMP_POINTS, replace=False))
+
+
+def dump_outputs(outdir, _lib, L, S, n3, slab_mode, solved, dist, rank):
+    """What the timed path hands its caller after the last timed step: the fine-grid solution u (all of it,
+    u.npy, while it fits in DUMP_POINTS; else u_sample.npy at dump_sample_index's points) and the solve loop's
+    returns (solve_returns.npy: ierr, cycles run, du of the last cycle), all float64.  Collective in slab mode:
+    every rank reads its own planes, rank 0 writes."""
+    nx, ny, nz = n3
+    idx = dump_sample_index(nx * ny * nz)
+    if not slab_mode:
+        u = S.download(1, _lib.BUF_U).ravel()
+        parts = [(None, u if idx is None else u[idx])]
+    else:
+        mine = []
+        for i, sl in enumerate(S.slabs, start=1):
+            buf = np.empty((sl["z1"] - sl["z0"], ny, nx))
+            _lib._check(L.ndsm_hip_world_download(S.h, i, _lib.BUF_U, buf.ctypes.data_as(_lib._dp)), "world_download", L)
+            a, b = sl["z0"] * ny * nx, sl["z1"] * ny * nx
+            k = np.arange(a, b) if idx is None else idx[(idx >= a) & (idx < b)]
+            mine.append((k, buf.ravel()[k - a]))
+            del buf
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, mine)
+        parts = [p for rank_parts in parts for p in rank_parts]
+    if rank != 0:
+        return
+    total = nx * ny * nz if idx is None else idx.size
+    vals = np.full(total, np.nan)
+    filled = 0
+    for k, v in parts:
+        if k is None:
+            vals[:] = v
+            filled = total
+        else:
+            vals[k if idx is None else np.searchsorted(idx, k)] = v
+            filled += k.size
+    if filled != total:
+        raise SystemExit(f"bench.py --dump-outputs: {filled} of {total} points were read back")
+    os.makedirs(outdir, exist_ok=True)
+    if idx is None:
+        np.save(os.path.join(outdir, "u.npy"), vals.reshape(nz, ny, nx))
+    else:
+        np.save(os.path.join(outdir, "u_sample.npy"), vals)
+    ierr, du, nc, _h = solved
+    np.save(os.path.join(outdir, "solve_returns.npy"), np.array([ierr, nc, du], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -494,7 +560,15 @@ def main():
                     help="take roofline.traffic from profiles/traffic_latest.json instead of two rocprofv3 --pmc child runs")
     ap.add_argument("--slab-shape", default="1024,1024,512",
                     help="N > 1: the grid cut into z-slabs (default: BASELINE config[3]; smaller for rehearsals)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also take every other measurement (kernel timings, roofline, whole "
+                         "solves, BASELINE configs, end-to-end calls, CPU baseline); without it the run only times "
+                         "the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/*.npy (float64, at most 32 MiB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # a lone process asked for N GPUs: it becomes the launcher of N ranks (one process per GPU)
@@ -702,7 +776,7 @@ def main():
     run_cycles(args.warmup)
     barrier_sync()
     t0 = time.perf_counter()
-    run_cycles(args.steps)
+    solved = run_cycles(args.steps)
     barrier_sync()
     el = time.perf_counter() - t0
     if dist is not None:
@@ -713,6 +787,49 @@ def main():
     if timed_dog is not None:
         timed_dog.cancel()
     ms_per_step = el / args.steps * 1e3
+    if solved[2] != args.steps:
+        raise SystemExit(f"bench.py: the timed solve loop ran {solved[2]} cycles, not --steps {args.steps}")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, _lib, L, S, n3, slab_mode, solved, dist, rank)
+
+    def finish():
+        # after the result line is out: leave together, then take the communicator down (collective)
+        if dist is not None:
+            dist.barrier()
+            try:
+                _lib.dist_finalize(L)
+            except Exception as exc:  # noqa: BLE001
+                print(f"bench: dist_finalize: {exc}", file=sys.stderr, flush=True)
+
+    head = {
+        "metric": "fine-grid LUP/s (RB-GS smoother updates per second of V-cycle time, fp64)",
+        "value": 2 * ms * npts / (ms_per_step * 1e-3),
+        "unit": "LUP/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {"workload": workload, "global_points": int(npts), "parallelism": parallelism},
+        "slab_mode": slab_mode,
+        "rccl_ranks": rccl_ranks,
+        "vcycles_per_s": 1.0 / (ms_per_step * 1e-3),
+    }
+    if not args.full:
+        # a plain run: the headline line and nothing else
+        S.close()
+        del S
+        if rank == 0:
+            head["rocm_stack"] = _lib.bound_libs(L)
+            if slab_check is not None:
+                head["slab_check"] = slab_check
+            os.write(result_fd, (json.dumps(head) + "\n").encode())
+        finish()
+        return
 
     # ---- dominant kernel: the level-1 smoother launches under HIP events on the library stream ----
     nsw = 20
@@ -833,35 +950,10 @@ def main():
                      ("" if tr else "; NO counter figure for this launch: frac is null, only the algorithmic figure is given")}
         return r
 
-    def finish():
-        # after the result line is out: leave together, then take the communicator down (collective)
-        if dist is not None:
-            dist.barrier()
-            try:
-                _lib.dist_finalize(L)
-            except Exception as exc:  # noqa: BLE001
-                print(f"bench: dist_finalize: {exc}", file=sys.stderr, flush=True)
-
     if rank != 0:
         finish()
         return
-    out = {
-        "metric": "fine-grid LUP/s (RB-GS smoother updates per second of V-cycle time, fp64)",
-        "value": 2 * ms * npts / (ms_per_step * 1e-3),
-        "unit": "LUP/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": scaling,
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {"workload": workload, "global_points": int(npts), "parallelism": parallelism},
-        "slab_mode": slab_mode,
-        "rccl_ranks": rccl_ranks,
-        "vcycles_per_s": 1.0 / (ms_per_step * 1e-3),
+    out = dict(head, **{
         "vcycle_without_metric_ms": vc_only_ms,
         "smoother": ({"laplace_ms_per_sweep": lap_ms, "laplace_LUPs_per_s": npts / (lap_ms * 1e-3),
                       "general_rhs_ms_per_sweep": gen_ms,
@@ -873,7 +965,7 @@ def main():
         # the kernel that dominates the timed region (top row of profiles/*_kernel_stats.csv)
         "roofline": roofline(lap_ms, bpl, kname, traffic),
         "rocm_stack": _lib.bound_libs(L),
-    }
+    })
     if gen_ms:
         out["roofline_general_rhs"] = roofline(gen_ms, BYTES_PER_LUP,
                                                "rbgs3_fused_k<double, 2, 136, 30, 1024, 4, false, 0, true, false>", traffic_gen,

@@ -6,11 +6,11 @@ tag=${1:-rXX}
 out=gpurun_out/profiles_$tag
 rm -rf $out; mkdir -p $out
 export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o b -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-e2e \
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o b -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-e2e \
    > $out/${tag}_bench_under_rocprof.json 2> $out/bench_prof.err
 cp $out/prof/*/b_kernel_stats.csv $out/${tag}_kernel_stats.csv 2>/dev/null || cp $out/prof/b_kernel_stats.csv $out/${tag}_kernel_stats.csv
 echo "stats done"
-python3 bench.py > $out/${tag}_bench.json 2> $out/bench.err
+python3 bench.py --full > $out/${tag}_bench.json 2> $out/bench.err
 echo "bench done"
 bash scripts/collect_traffic.sh > $out/traffic.log 2>&1 || true
 cp profiles/traffic_latest.json $out/traffic_latest.json

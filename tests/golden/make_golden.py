@@ -29,8 +29,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import numpy as np  # noqa: E402
 
-from golden_inputs import (BCS3, analytic_case, manufactured_poisson, rand_field,  # noqa: E402
-                           KERNEL_SHAPES_3D, KERNEL_SHAPES_2D)
+from golden_inputs import (BCS3, BCS_RANDOM, analytic_case, digest, manufactured_poisson, quirk_case,  # noqa: E402
+                           rand_field, random_reference_cases, KERNEL_SHAPES_3D, KERNEL_SHAPES_2D)
 from oracle import Oracle, have_ref, uniform_mesh  # noqa: E402
 
 
@@ -143,6 +143,35 @@ def main():
     with open(os.path.join(HERE, "pipeline_rows.json"), "w") as fh:
         json.dump(rows, fh, indent=1)
     print("wrote pipeline_*")
+    random_and_quirks(R)
+
+
+def random_and_quirks(R):
+    """test_oracle.py's random-input and quirk checks: sha256 of the bit-identical outputs, the all-Neumann
+    sweeps (compared within 1e-14) in full, and the flags of the quirk calls"""
+    digests, nn = {}, {}
+    for ns, mesh, u, rhs in random_reference_cases():
+        tag = "x".join(str(n) for n in ns)
+        for bcs in BCS_RANDOM:
+            a = R.relax3d(u, rhs, mesh, bcs)
+            if bcs == "NNNNNN":
+                nn[f"relax_{tag}"] = a
+            else:
+                digests[f"relax_{tag}_{bcs}"] = digest(a)
+            digests[f"residual_{tag}_{bcs}"] = digest(R.residual3d(u, rhs, mesh, bcs))
+        digests[f"vcycle_{tag}_DNDDND_ms3"] = digest(R.vcycle(u, rhs, mesh, "DNDDND", ms=3))
+    with open(os.path.join(HERE, "reference_random.json"), "w") as fh:
+        json.dump(digests, fh, indent=1, sort_keys=True)
+    np.savez_compressed(os.path.join(HERE, "reference_random_NNNNNN.npz"), **nn)
+    x, y, z, b = quirk_case()
+    ierr, _, _, ioptc, _ = R.vector_potential(x, y, z, b, ncycles_max=2)
+    quirks = {"top_face_zero": {"ierr": int(ierr), "ioptc": [int(v) for v in ioptc]}}
+    x, y, z, A1, b1 = analytic_case(24)
+    ierr, _, _, ioptc, _ = R.vector_potential(x, y, z, b1, ncycles_max=2)
+    quirks["analytic"] = {"ierr": int(ierr), "ioptc": [int(v) for v in ioptc]}
+    with open(os.path.join(HERE, "reference_quirks.json"), "w") as fh:
+        json.dump(quirks, fh, indent=1)
+    print("wrote reference_random*, reference_quirks.json")
 
 
 if __name__ == "__main__":

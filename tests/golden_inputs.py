@@ -62,3 +62,33 @@ def analytic_case(n):
     A[0] = -np.cos(wn * X) * np.sin(wn * Y) * np.exp(-l * Z)
     A[1] = +np.sin(wn * X) * np.cos(wn * Y) * np.exp(-l * Z)
     return x, y, z, A, b
+
+
+# BC sets of test_oracle.py::test_live_reference_random: the three components' plus the all-Neumann,
+# all-Dirichlet and mixed corners
+BCS_RANDOM = BCS3 + ("NNNNNN", "DDDDDD", "NDNDND")
+
+
+def random_reference_cases():
+    """(ns, mesh, u, rhs) of test_oracle.py::test_live_reference_random: two odd-sized boxes, fields drawn in
+    this order from one default_rng(12345)."""
+    rng = np.random.default_rng(12345)
+    for ns in ([17, 23, 19], [40, 24, 32]):
+        shp = tuple(ns[::-1])
+        u, rhs = rng.uniform(-1, 1, shp), rng.uniform(-1, 1, shp)
+        yield ns, uniform_mesh(ns), u, rhs
+
+
+def quirk_case(n=24):
+    """analytic field with B.n = 0 on the top face: its 2-D solve (the LAST one) converges at once,
+    the 3-D solves cannot within 2 V-cycles"""
+    x, y, z, A1, b1 = analytic_case(n)
+    b = b1.copy()
+    b[2, -1, :, :] = 0.0
+    return x, y, z, b
+
+
+def digest(a):
+    """sha256 of an array's float64 bytes (C order, little-endian): equal digests <=> bit-identical arrays"""
+    import hashlib
+    return hashlib.sha256(np.ascontiguousarray(a, dtype="<f8").tobytes()).hexdigest()

@@ -2,8 +2,8 @@
 
 (a) committed golden vectors produced by the reference itself
     (tests/golden/make_golden.py), (b) the reference's own known-answer rows
-    tests/integration_test/results_test1.txt:6-7, (c) the live reference on
-    fresh random inputs when oracle/_ref is present.
+    tests/integration_test/results_test1.txt:6-7, (c) the reference's outputs on
+    fresh random inputs and on a quirk case, recorded by make_golden.py.
 
 Tolerance: the 3-D path has no order-dependent reduction, and the restatement
 keeps the reference's operand order, so 3-D results are required to be
@@ -17,8 +17,8 @@ import os
 import numpy as np
 import pytest
 
-from golden_inputs import (BCS3, KERNEL_SHAPES_2D, KERNEL_SHAPES_3D, analytic_case, manufactured_poisson,
-                           rand_field, uniform_mesh)
+from golden_inputs import (BCS3, BCS_RANDOM, KERNEL_SHAPES_2D, KERNEL_SHAPES_3D, analytic_case, digest,
+                           manufactured_poisson, quirk_case, rand_field, random_reference_cases, uniform_mesh)
 
 
 def _tag(ns):
@@ -125,41 +125,33 @@ def test_pipeline_golden(port, golden_dir, name, ns):
     assert np.abs(B - g["B"]).max() <= 1e-12 * np.abs(g["A"]).max() / h * 4
 
 
-def test_live_reference_random(port, ref):
-    """(c): fresh inputs, the reference run live (container only)."""
-    rng = np.random.default_rng(12345)
-    for ns in ([17, 23, 19], [40, 24, 32]):
-        mesh = uniform_mesh(ns)
-        shp = tuple(ns[::-1])
-        u, rhs = rng.uniform(-1, 1, shp), rng.uniform(-1, 1, shp)
-        for bcs in BCS3 + ("NNNNNN", "DDDDDD", "NDNDND"):
-            a, b = port.relax3d(u, rhs, mesh, bcs), ref.relax3d(u, rhs, mesh, bcs)
+def test_live_reference_random(port, golden_dir):
+    """(c): fresh random inputs against the reference's outputs on them (golden/reference_random.json holds the
+    sha256 of each bit-identical output, golden/reference_random_NNNNNN.npz the all-Neumann sweeps)."""
+    want = json.load(open(os.path.join(golden_dir, "reference_random.json")))
+    nn = np.load(os.path.join(golden_dir, "reference_random_NNNNNN.npz"))
+    for ns, mesh, u, rhs in random_reference_cases():
+        tag = _tag(ns)
+        for bcs in BCS_RANDOM:
+            a = port.relax3d(u, rhs, mesh, bcs)
             if bcs == "NNNNNN":
-                np.testing.assert_allclose(a, b, rtol=0, atol=1e-14)
+                np.testing.assert_allclose(a, nn[f"relax_{tag}"], rtol=0, atol=1e-14)
             else:
-                assert np.array_equal(a, b)
-            assert np.array_equal(port.residual3d(u, rhs, mesh, bcs), ref.residual3d(u, rhs, mesh, bcs))
-        assert np.array_equal(port.vcycle(u, rhs, mesh, "DNDDND", ms=3), ref.vcycle(u, rhs, mesh, "DNDDND", ms=3))
+                assert digest(a) == want[f"relax_{tag}_{bcs}"], (tag, bcs)
+            assert digest(port.residual3d(u, rhs, mesh, bcs)) == want[f"residual_{tag}_{bcs}"], (tag, bcs)
+        assert digest(port.vcycle(u, rhs, mesh, "DNDDND", ms=3)) == want[f"vcycle_{tag}_DNDDND_ms3"], tag
 
 
-def _quirk_case(n=24):
-    """analytic field with B.n = 0 on the top face: its 2-D solve (the LAST one) converges at once,
-    the 3-D solves cannot within 2 V-cycles"""
-    x, y, z, A1, b1 = analytic_case(n)
-    b = b1.copy()
-    b[2, -1, :, :] = 0.0
-    return x, y, z, b
-
-
-def test_quirk_ierr_is_the_last_face_solve(port, ref):
+def test_quirk_ierr_is_the_last_face_solve(port, golden_dir):
     """Q3': ndsm_vector_potential.f90:480 stores the flag last written at :360 (2-D face 6), because
-    `solve` (:598) keeps the 3-D flags in a local.  Checked on the live reference."""
-    x, y, z, b = _quirk_case()
-    ierr_ref, _, _, io_ref, _ = ref.vector_potential(x, y, z, b, ncycles_max=2)
+    `solve` (:598) keeps the 3-D flags in a local.  The reference's answers: golden/reference_quirks.json."""
+    want = json.load(open(os.path.join(golden_dir, "reference_quirks.json")))
+    x, y, z, b = quirk_case()
+    ierr_ref, io_ref = want["top_face_zero"]["ierr"], want["top_face_zero"]["ioptc"]
     ierr_port, _, _, io_port, _ = port.vector_potential(x, y, z, b, ncycles_max=2)
     assert ierr_ref == 0 and ierr_port == 0          # although no 3-D solve reached vc_tol
     assert io_ref[3] == io_port[3] == 0
     # sanity: with B.n != 0 on that face the same budget does return 1
     x, y, z, A1, b1 = analytic_case(24)
-    assert ref.vector_potential(x, y, z, b1, ncycles_max=2)[0] == 1
+    assert want["analytic"]["ierr"] == 1
     assert port.vector_potential(x, y, z, b1, ncycles_max=2)[0] == 1

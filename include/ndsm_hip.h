@@ -160,6 +160,43 @@ int ndsm_hip_vecpot_solve(void *handle, int ioptc[16], double ropt[16], double *
 int ndsm_hip_vecpot_solve_device(void *handle, int ioptc[16], double ropt[16], double *dA, double *dB);
 int ndsm_hip_vecpot_destroy(void *handle);
 
+/* ---- the current-carrying field on the same handle (DESIGN.md "Vector potential of a current-carrying field") ----
+ * The potential pipeline returns the potential field B_p = curl A_p of B.n.  These entries return A of the
+ * field B itself (curl B != 0: a simulation, a force-free model, a data cube), in the same Coulomb gauge and
+ * with the same tangential boundary values as A_p: the three 3-D problems get the right-hand side
+ * -(curl_h B)_c (derivq's differences) and keep their boundary letters and Dirichlet data.  Uniform spacing,
+ * as for ndsm_hip_vecpot_solve.  Options in the same slots, with the same meaning (ms, with Az's ms = 5;
+ * ncycles, nmaxex, dumax, vtol, ctol, ngrids, prec, IOPT_FLXCRL = 4).
+ * Returns 0 when every 2-D and 3-D solve reached vc_tol, 1 when at least one did not (NOT the reference's
+ * quirk Q3'), >= 9001 errors (a HIP failure such as out of memory comes back as 9001, see
+ * ndsm_hip_last_error); ioptc[IOPT_IERR] holds the same value.  ioptc[get_iopt_fail3d()]: bits 0-2 the field
+ * solves Ax, Ay, Az; bits 3-5 the potential solves of a helicity call.
+ *
+ *   ndsm_hip_vecpot_solve_field        HOST arrays (nx,ny,nz,3).  A in: initial guess, out: A.  B in: the whole
+ *                                      field (uploaded in full, 24 B/pt), out: curl A + flux-balance fields.
+ *   ndsm_hip_vecpot_solve_field_device the same on DEVICE arrays of the library's GPU.
+ *   ndsm_hip_vecpot_helicity           HOST arrays.  B in, read only.  A, Ap, Bp out: A of B, the potential
+ *                                      field's A_p and B_p (both solves start from zero; A_p, B_p are the bits
+ *                                      ndsm_hip_vecpot_solve returns for B and a zero guess).  out[8] (no 4 pi
+ *                                      or mu0 factors; trapezoid weights w, h inside and h/2 on the end planes
+ *                                      of each axis; B_rec = curl A + balance, the field solve's own output):
+ *       out[0] H_R = sum w (A + Ap).(B - Bp)   relative helicity (Finn-Antonsen)
+ *       out[1] H_J = sum w (A - Ap).(B - Bp)   helicity of the current-carrying part
+ *       out[2] E   = 1/2 sum w |B|^2           out[3] E_p = 1/2 sum w |Bp|^2
+ *       out[4] max |B_rec,c - B_c| (all c)     out[5] sqrt(sum w |B_rec - B|^2 / sum w)
+ *       out[6] max |div_h B|                   out[7] max |div_h A|
+ *                                      The sums are deterministic (fixed reduction order): the same input gives
+ *                                      the same bits.  Device memory: five fields of 24 B/pt besides the
+ *                                      hierarchy.
+ *   ndsm_hip_vecpot_helicity_device    the same on DEVICE arrays; B_rec lives in library scratch.
+ * Non-solenoidal input is not corrected: it shows in out[4], out[5] and out[6]. */
+int ndsm_hip_vecpot_solve_field(void *h, int ioptc[16], double ropt[16], double *A, double *B);
+int ndsm_hip_vecpot_solve_field_device(void *h, int ioptc[16], double ropt[16], double *dA, double *dB);
+int ndsm_hip_vecpot_helicity(void *h, int ioptc[16], double ropt[16], const double *B, double *A, double *Ap,
+                             double *Bp, double out[8]);
+int ndsm_hip_vecpot_helicity_device(void *h, int ioptc[16], double ropt[16], const double *dB, double *dA,
+                                    double *dAp, double *dBp, double out[8]);
+
 /* =====================================================================
  * PART 3 - additive exports, multi-GPU
  *

@@ -4,6 +4,7 @@ Fails loudly: a missing library raises NdsmHipError at load time and a missing
 GPU raises it at the first call that needs the device.  Nothing here computes
 on the CPU.
 """
+import collections
 import ctypes
 import os
 
@@ -229,6 +230,11 @@ class VecPot:
         self.L.ndsm_hip_vecpot_solve.argtypes = [ctypes.c_void_p, _ip, _dp, _dp, _dp]
         self.L.ndsm_hip_vecpot_solve_device.argtypes = [ctypes.c_void_p, _ip, _dp, ctypes.c_void_p, ctypes.c_void_p]
         self.L.ndsm_hip_vecpot_destroy.argtypes = [ctypes.c_void_p]
+        self.L.ndsm_hip_vecpot_solve_field.argtypes = [ctypes.c_void_p, _ip, _dp, _dp, _dp]
+        self.L.ndsm_hip_vecpot_solve_field_device.argtypes = [ctypes.c_void_p, _ip, _dp, ctypes.c_void_p, ctypes.c_void_p]
+        self.L.ndsm_hip_vecpot_helicity.argtypes = [ctypes.c_void_p, _ip, _dp, _dp, _dp, _dp, _dp, _dp]
+        self.L.ndsm_hip_vecpot_helicity_device.argtypes = [ctypes.c_void_p, _ip, _dp, ctypes.c_void_p, ctypes.c_void_p,
+                                                           ctypes.c_void_p, ctypes.c_void_p, _dp]
         self.L.ndsm_hip_device_alloc.argtypes = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
         self.L.ndsm_hip_device_free.argtypes = [ctypes.c_void_p]
         self.L.ndsm_hip_memcpy_h2d.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
@@ -292,6 +298,113 @@ class VecPot:
         self.last_ioptc, self.last_ropt = ioptc, ropt
         return ierr, A.reshape(shape), B.reshape(shape)
 
+    def _field_arg(self, b, what):
+        """b as a flat float64 copy; a shape other than (3, nz, ny, nx) is an argument error (9002)"""
+        shape = tuple(int(v) for v in self.nshape4[::-1])
+        a = np.asarray(b)
+        if a.shape != shape:
+            raise NdsmHipError(f"{what}: field of shape {a.shape}, the handle's grid needs {shape} (code 9002)")
+        return _f64(a).reshape(-1).copy()
+
+    def _on_device(self, host_arrays, call):
+        """stage host_arrays in device memory, run call(*device pointers), copy every array back"""
+        ptrs = []
+        try:
+            for a in host_arrays:
+                p = ctypes.c_void_p()
+                _check(self.L.ndsm_hip_device_alloc(a.nbytes, ctypes.byref(p)), "device_alloc", self.L)
+                ptrs.append(p)
+                _check(self.L.ndsm_hip_memcpy_h2d(p, a.ctypes.data, a.nbytes), "h2d", self.L)
+            ierr = call(*ptrs)
+            for a, p in zip(host_arrays, ptrs):
+                _check(self.L.ndsm_hip_memcpy_d2h(a.ctypes.data, p, a.nbytes), "d2h", self.L)
+        finally:
+            for p in ptrs:
+                self.L.ndsm_hip_device_free(p)
+        return ierr
+
+    def solve_field(self, b, a_init=None, niterex_max=10000, ncycles_max=1024, ex_tol=1e-13, vc_tol=1e-10, ms=5,
+                    mean=False, mixed_precision=False, flxcrl=False, device=False):
+        """Vector potential of the whole field b (3,nz,ny,nx), curl b != 0 allowed: the same gauge and tangential
+        boundary values as solve()'s potential-field A_p.  Returns (ierr, A, B_rec), B_rec = curl A + the
+        flux-balance fields; ierr 0 when every solve reached vc_tol, else 1.  device=True: the arrays are staged
+        in device memory and the device-resident entry point runs."""
+        ioptc, ropt = self._options(niterex_max, ncycles_max, ex_tol, vc_tol, ms, mean, mixed_precision, flxcrl)
+        shape = tuple(int(v) for v in self.nshape4[::-1])
+        B = self._field_arg(b, "solve_field")
+        A = np.zeros(B.size) if a_init is None else self._field_arg(a_init, "solve_field")
+        if not device:
+            ierr = self.L.ndsm_hip_vecpot_solve_field(self.h, ioptc.ctypes.data_as(_ip), _d(ropt), _d(A), _d(B))
+        else:
+            ierr = self._on_device([A, B], lambda dA, dB: self.L.ndsm_hip_vecpot_solve_field_device(
+                self.h, ioptc.ctypes.data_as(_ip), _d(ropt), dA, dB))
+        if ierr >= 9000:
+            _check(ierr, "ndsm_hip_vecpot_solve_field", self.L)
+        self.last_ioptc, self.last_ropt = ioptc, ropt
+        return ierr, A.reshape(shape), B.reshape(shape)
+
+    def helicity(self, b, niterex_max=10000, ncycles_max=1024, ex_tol=1e-13, vc_tol=1e-10, ms=5, mean=False,
+                 mixed_precision=False, flxcrl=False, device=False, return_fields=False):
+        """Relative magnetic helicity of b (3,nz,ny,nx) against the potential field of its B.n, in one call: the
+        face phase once, the potential and the field 3-D solves, one deterministic reduction on the device.
+        Returns a Helicity tuple (no 4 pi / mu0 factors; trapezoid weights): ierr, H_R (Finn-Antonsen),
+        H_J = sum w (A - A_p).(B - B_p), E, E_p, E_free = E - E_p, recon_max / recon_rms of |B_rec - b|,
+        divB_max, divA_max; with return_fields also A, A_p, B_p (else None)."""
+        ioptc, ropt = self._options(niterex_max, ncycles_max, ex_tol, vc_tol, ms, mean, mixed_precision, flxcrl)
+        shape = tuple(int(v) for v in self.nshape4[::-1])
+        B = self._field_arg(b, "helicity")
+        A, Ap, Bp = np.empty(B.size), np.empty(B.size), np.empty(B.size)
+        out = np.zeros(8)
+        if not device:
+            ierr = self.L.ndsm_hip_vecpot_helicity(self.h, ioptc.ctypes.data_as(_ip), _d(ropt), _d(B), _d(A), _d(Ap),
+                                                   _d(Bp), _d(out))
+        else:
+            ierr = self._on_device([B, A, Ap, Bp], lambda dB, dA, dAp, dBp: self.L.ndsm_hip_vecpot_helicity_device(
+                self.h, ioptc.ctypes.data_as(_ip), _d(ropt), dB, dA, dAp, dBp, _d(out)))
+        if ierr >= 9000:
+            _check(ierr, "ndsm_hip_vecpot_helicity", self.L)
+        self.last_ioptc, self.last_ropt = ioptc, ropt
+        f = (A.reshape(shape), Ap.reshape(shape), Bp.reshape(shape)) if return_fields else (None, None, None)
+        return Helicity(int(ierr), float(out[0]), float(out[1]), float(out[2]), float(out[3]), float(out[2] - out[3]),
+                        float(out[4]), float(out[5]), float(out[6]), float(out[7]), *f)
+
+
+Helicity = collections.namedtuple("Helicity", ["ierr", "H_R", "H_J", "E", "E_p", "E_free", "recon_max", "recon_rms",
+                                               "divB_max", "divA_max", "A", "A_p", "B_p"])
+
+
+def _grid_handle(x, y, z, b, ngrids, lib):
+    shape = np.shape(b)
+    want = (3, len(z), len(y), len(x))
+    if tuple(shape) != want:
+        raise NdsmHipError(f"field of shape {tuple(shape)}, the mesh needs {want} (code 9002)")
+    return VecPot(x, y, z, ngrids=ngrids, lib=lib)
+
+
+def vector_potential_field(x, y, z, b, a_init=None, niterex_max=10000, ncycles_max=1024, ex_tol=1e-13, vc_tol=1e-10,
+                           ms=5, mean=False, mixed_precision=False, flxcrl=False, ngrids=0, lib=None):
+    """Vector potential A of the whole field b (3,nz,ny,nx) - curl b != 0 allowed - in the Coulomb gauge of
+    `vector_potential`, with the same tangential boundary values as its potential-field A_p.  One-shot form of
+    VecPot.solve_field: returns (ierr, A, B_rec), B_rec = curl A + flux-balance fields.  Raises NdsmHipError on
+    device / runtime failures (>= 9001)."""
+    V = _grid_handle(x, y, z, b, ngrids, lib)
+    try:
+        return V.solve_field(b, a_init=a_init, niterex_max=niterex_max, ncycles_max=ncycles_max, ex_tol=ex_tol,
+                             vc_tol=vc_tol, ms=ms, mean=mean, mixed_precision=mixed_precision, flxcrl=flxcrl)
+    finally:
+        V.close()
+
+
+def relative_helicity(x, y, z, b, niterex_max=10000, ncycles_max=1024, ex_tol=1e-13, vc_tol=1e-10, ms=5, mean=False,
+                      mixed_precision=False, flxcrl=False, ngrids=0, return_fields=False, lib=None):
+    """Relative helicity, energies and reconstruction diagnostics of b (3,nz,ny,nx): one-shot form of
+    VecPot.helicity (returns its Helicity tuple).  Raises NdsmHipError on device / runtime failures (>= 9001)."""
+    V = _grid_handle(x, y, z, b, ngrids, lib)
+    try:
+        return V.helicity(b, niterex_max=niterex_max, ncycles_max=ncycles_max, ex_tol=ex_tol, vc_tol=vc_tol, ms=ms,
+                          mean=mean, mixed_precision=mixed_precision, flxcrl=flxcrl, return_fields=return_fields)
+    finally:
+        V.close()
 
 SLAB_FIELDS = ("rank", "z0", "z1", "g", "nloc", "k0", "ck0", "ck1", "pk0", "pk1", "cb0", "cb1")
 

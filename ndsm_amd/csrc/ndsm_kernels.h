@@ -182,6 +182,13 @@ int ndsmk_curl(const double *A, double *B, const int32_t *n3, const double *h_dq
 /* component c of B alone (needs the other two components of A only) */
 int ndsmk_curl_component(const double *A, double *B, const int32_t *n3, const double *h_dq3, int c);
 
+/* the current-carrying field (field.hip): rhs = -(curl B)_c of a device field B (nx,ny,nz,3) into a device
+ * array (nx,ny,nz) - the same bits as -ndsmk_curl_component(B)_c -, and the blocking, deterministic reduction
+ * behind ndsm_hip_vecpot_helicity (h_out8 as documented there) */
+int ndsmk_curl_rhs(const double *B, double *rhs, const int32_t *n3, const double *h_dq3, int c);
+int ndsmk_helicity_reduce(const double *A, const double *Ap, const double *B, const double *Bp, const double *Br,
+                          const int32_t *n3, const double *h_dq3, double *h_out8);
+
 /* the face phase on the device (faces.hip): packed face buffers, six faces back to back */
 int ndsmk_face_offsets(const int32_t *n3, int64_t *off6, int64_t *total);
 int ndsmk_face_extract(const double *B, const int32_t *n3, double *faces);

@@ -704,6 +704,98 @@ contains
     end if
   end function
 
+  ! ---- the current-carrying field on the same handle -------------------
+  ! A of a field B with curl B /= 0 (the 3-D problems get rhs_c = -(curl B)_c, same boundary letters and data
+  ! as the potential field), and the relative helicity of B against the potential field of its B.n.  Return
+  ! value of all four: 0 every 2-D and 3-D solve reached vc_tol, 1 at least one did not, >= 9001 errors (a
+  ! HIP failure code, e.g. out of memory, comes back as 9001; the text names it).
+
+  ! A: in initial guess, out A; B: in the whole field, out curl A + balance.  HOST arrays (nx,ny,nz,3)
+  function ndsm_hip_vecpot_solve_field(handle, ioptc, ropt, A, B) bind(c, name="ndsm_hip_vecpot_solve_field") &
+      result(ierr)
+    type(c_ptr), value :: handle, A, B
+    integer(c_int), intent(inout) :: ioptc(0:OPT_LEN - 1)
+    real(c_double), intent(inout) :: ropt(0:OPT_LEN - 1)
+    integer(c_int) :: ierr
+    real(c_double) :: out8(8)
+    ierr = vecpot_handle_field(handle, ioptc, ropt, A, B, c_null_ptr, c_null_ptr, out8, VP_FIELD, .false., &
+                               "ndsm_hip_vecpot_solve_field")
+  end function
+
+  ! the same on DEVICE arrays of the library's GPU
+  function ndsm_hip_vecpot_solve_field_device(handle, ioptc, ropt, dA, dB) &
+      bind(c, name="ndsm_hip_vecpot_solve_field_device") result(ierr)
+    type(c_ptr), value :: handle, dA, dB
+    integer(c_int), intent(inout) :: ioptc(0:OPT_LEN - 1)
+    real(c_double), intent(inout) :: ropt(0:OPT_LEN - 1)
+    integer(c_int) :: ierr
+    real(c_double) :: out8(8)
+    ierr = vecpot_handle_field(handle, ioptc, ropt, dA, dB, c_null_ptr, c_null_ptr, out8, VP_FIELD, .true., &
+                               "ndsm_hip_vecpot_solve_field_device")
+  end function
+
+  ! B: in (read only); A, Ap, Bp: out; out8: H_R, H_J, E, E_p, max|B_rec,c - B_c|, rms|B_rec - B|, max|div_h B|,
+  ! max|div_h A|.  HOST arrays (nx,ny,nz,3)
+  function ndsm_hip_vecpot_helicity(handle, ioptc, ropt, B, A, Ap, Bp, out8) bind(c, name="ndsm_hip_vecpot_helicity") &
+      result(ierr)
+    type(c_ptr), value :: handle, B, A, Ap, Bp
+    integer(c_int), intent(inout) :: ioptc(0:OPT_LEN - 1)
+    real(c_double), intent(inout) :: ropt(0:OPT_LEN - 1)
+    real(c_double), intent(out) :: out8(8)
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_field(handle, ioptc, ropt, A, B, Ap, Bp, out8, VP_HELICITY, .false., "ndsm_hip_vecpot_helicity")
+  end function
+
+  ! the same on DEVICE arrays of the library's GPU
+  function ndsm_hip_vecpot_helicity_device(handle, ioptc, ropt, dB, dA, dAp, dBp, out8) &
+      bind(c, name="ndsm_hip_vecpot_helicity_device") result(ierr)
+    type(c_ptr), value :: handle, dB, dA, dAp, dBp
+    integer(c_int), intent(inout) :: ioptc(0:OPT_LEN - 1)
+    real(c_double), intent(inout) :: ropt(0:OPT_LEN - 1)
+    real(c_double), intent(out) :: out8(8)
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_field(handle, ioptc, ropt, dA, dB, dAp, dBp, out8, VP_HELICITY, .true., &
+                               "ndsm_hip_vecpot_helicity_device")
+  end function
+
+  function vecpot_handle_field(handle, ioptc, ropt, A, B, Ap, Bp, out8, md, on_device, who) result(ierr)
+    type(c_ptr), intent(in) :: handle, A, B, Ap, Bp
+    integer(c_int), intent(inout) :: ioptc(0:OPT_LEN - 1)
+    real(c_double), intent(inout) :: ropt(0:OPT_LEN - 1)
+    real(c_double), intent(out) :: out8(8)
+    integer, intent(in) :: md
+    logical, intent(in) :: on_device
+    character(len=*), intent(in) :: who
+    integer(c_int) :: ierr
+    type(vecpot_ctx), pointer :: ctx
+    integer(ik) :: iopt(0:OPT_LEN - 1)
+    real(c_double) :: t0
+    integer(c_int) :: rc
+    out8 = 0
+    ierr = ndsmk_init(-1_c_int)                        ! without a device: 9001, whatever the arguments
+    if (ierr /= 0) return
+    ierr = NDSMK_EARG
+    if (.not. (c_associated(handle) .and. c_associated(A) .and. c_associated(B))) return
+    if (md == VP_HELICITY .and. .not. (c_associated(Ap) .and. c_associated(Bp))) return
+    call c_f_pointer(handle, ctx)
+    if (.not. ctx%live) return
+    iopt = ioptc
+    verbose = (iopt(IOPT_DEBUG) == 1)
+    t0 = wall_seconds()
+    rc = NDSMK_EARG
+    if (int(iopt(IOPT_NGRIDS)) == ctx%ngr) rc = vecpot_run(ctx, iopt, ropt, A, B, on_device, md, Ap, Bp, out8)
+    ropt(ROPT_TIM) = wall_seconds() - t0
+    ioptc = int(iopt, c_int)
+    if (rc /= 0) then
+      call report(who, rc)
+      if (rc < NDSMK_ENODEV) rc = NDSMK_ENODEV
+      ioptc(IOPT_IERR) = rc
+      ierr = rc
+    else
+      ierr = int(iopt(IOPT_IERR), c_int)
+    end if
+  end function
+
   ! ---- z-slab decomposition over GPUs (SURVEY 8e) -----------------------
 
   ! rank 0 creates the 128-byte RCCL id; the launcher hands it to every rank

@@ -507,6 +507,24 @@ module ndsmh_iface
       integer(c_int) :: rc
     end function
 
+    ! ---- the current-carrying field (field.hip) ----
+    function ndsmk_curl_rhs(B, rhs, n3, dq3, c) bind(c, name="ndsmk_curl_rhs") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_double
+      type(c_ptr), value :: B, rhs
+      integer(c_int32_t), intent(in) :: n3(3)
+      real(c_double), intent(in) :: dq3(3)
+      integer(c_int), value :: c
+      integer(c_int) :: rc
+    end function
+    function ndsmk_helicity_reduce(A, Ap, B, Bp, Br, n3, dq3, out8) bind(c, name="ndsmk_helicity_reduce") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_double
+      type(c_ptr), value :: A, Ap, B, Bp, Br
+      integer(c_int32_t), intent(in) :: n3(3)
+      real(c_double), intent(in) :: dq3(3)
+      real(c_double), intent(out) :: out8(8)
+      integer(c_int) :: rc
+    end function
+
     ! ---- the face phase on the device (faces.hip) ----
     function ndsmk_face_offsets(n3, off6, total) bind(c, name="ndsmk_face_offsets") result(rc)
       import :: c_int, c_int32_t, c_int64_t

@@ -32,6 +32,7 @@ module ndsmh_vecpot
 
   public :: vecpot_solve, poisson_solve
   public :: vecpot_ctx, vecpot_ctx_create, vecpot_ctx_destroy, vecpot_ctx_matches, vecpot_run, vecpot_cache_drop
+  public :: VP_POTENTIAL, VP_FIELD, VP_HELICITY
   ! pieces the distributed driver (ndsmh_wvecpot) shares with vecpot_solve
   public :: face_data, face_axis, face_upper, face_t1, face_t2, face_order, face_copy, vecpot_faces, say
   public :: OPT_LEN, IOPT_MS, IOPT_NCYCLES, IOPT_FACE1, IOPT_IERR, IOPT_FLXCRL, IOPT_DEBUG, IOPT_DUMAX, &
@@ -66,6 +67,12 @@ module ndsmh_vecpot
   ! (:647-650, :663-666, :679-682; later writes win on shared edges)
   integer, parameter :: face_order(4, 3) = reshape([3, 4, 5, 6, 1, 2, 5, 6, 1, 2, 3, 4], [4, 3])
 
+  ! what vecpot_run computes (DESIGN.md "Vector potential of a current-carrying field"):
+  !   VP_POTENTIAL  the reference pipeline: the potential field of B.n and its A_p (ndsm_vector_solve)
+  !   VP_FIELD      A of the whole field B: the 3-D problems get rhs_c = -(curl B)_c, same letters and data
+  !   VP_HELICITY   one face phase, then the potential and the field 3-D phases, then the helicity reduction
+  integer, parameter :: VP_POTENTIAL = 0, VP_FIELD = 1, VP_HELICITY = 2
+
   ! up to this many points the three 3-D component solves get a hierarchy each and run side by side (vecpot_run)
   integer(ik), parameter :: SIDE3D_MAX = 16_ik * 1024_ik * 1024_ik
 
@@ -87,6 +94,7 @@ module ndsmh_vecpot
     type(c_ptr) :: dA = c_null_ptr, dB = c_null_ptr, dmesh = c_null_ptr
     type(c_ptr) :: dbn = c_null_ptr, dchi = c_null_ptr, dphi = c_null_ptr   ! packed faces: B.n, chi; six fluxes
     type(c_ptr) :: hbn = c_null_ptr                                         ! pinned staging of the six faces
+    type(c_ptr) :: dF(3) = c_null_ptr       ! host-array helicity calls only: B, A_p, B_p (allocated at the first)
     integer(ik) :: foff(6) = 0, ftotal = 0
   end type
 
@@ -307,6 +315,9 @@ contains
     end do
     rc = ndsmk_free(ctx%dA); ctx%dA = c_null_ptr
     rc = ndsmk_free(ctx%dB); ctx%dB = c_null_ptr
+    do p = 1, 3
+      rc = ndsmk_free(ctx%dF(p)); ctx%dF(p) = c_null_ptr
+    end do
     rc = ndsmk_free(ctx%dmesh); ctx%dmesh = c_null_ptr
     rc = ndsmk_free(ctx%dbn); ctx%dbn = c_null_ptr
     rc = ndsmk_free(ctx%dchi); ctx%dchi = c_null_ptr
@@ -425,13 +436,26 @@ contains
   !                 16-byte convergence read-backs.
   ! Between the face upload and the downloads nothing else travels: fluxes, right-hand sides of the 2-D
   ! problems, chi, A_t and the face writes into the 3-D initial guess are device kernels (faces.hip).
+  !
+  ! mode (default VP_POTENTIAL, the above) selects what the three parts - face phase, 3-D phase, post phase
+  ! (balance + curl) - are run for:
+  !   VP_FIELD     A: initial guess in, A of the whole field out; B: the whole field in (host entry: uploaded,
+  !                3N), curl A + balance out.  The 3-D right-hand sides are -(curl B)_c (field.hip).
+  !   VP_HELICITY  B: the whole field, read only; A, Ap, Bp: out (both solves start from zero).  The face
+  !                phase once; the potential 3-D + post phase -> Ap, Bp; the field 3-D + post phase -> A and
+  !                B_rec (library scratch); the reduction of field.hip -> out8.
+  ! Both: IOPT_IERR = 0 if every 2-D and 3-D solve reached vc_tol, else 1 (no Q3'); IOPT_FAIL3D bits 0-2 the
+  ! field solves, 3-5 the potential solves of a helicity call.
   ! ------------------------------------------------------------------
-  function vecpot_run(ctx, iopt, ropt, pA, pB, on_device) result(rc)
+  function vecpot_run(ctx, iopt, ropt, pA, pB, on_device, mode, pAp, pBp, out8) result(rc)
     type(vecpot_ctx), intent(inout), target :: ctx
     integer(ik), intent(inout) :: iopt(0:OPT_LEN - 1)
     real(wp), intent(inout) :: ropt(0:OPT_LEN - 1)
     type(c_ptr), intent(in) :: pA, pB
     logical, intent(in) :: on_device
+    integer, intent(in), optional :: mode
+    type(c_ptr), intent(in), optional :: pAp, pBp
+    real(wp), intent(out), optional :: out8(8)
     integer(c_int) :: rc
 
     character(len=*), parameter :: me = "compute_vector_potential"
@@ -439,19 +463,24 @@ contains
     real(wp), target :: phi(6)
     real(wp), pointer, contiguous :: hA(:, :, :, :), hB(:, :, :, :), stage(:)
     integer(c_int32_t) :: n3(3)
-    integer :: f, c, i, ierr2d, ierr3d, ncyc, st
+    integer :: f, c, i, ierr2d, ierr3d, ncyc, st, md, shift
     integer :: ncyc6(6), ierr6(6), ncyc3(3), ierr3(3)
     real(wp) :: du6(6), du3(3)
     character(len=8) :: envbuf
     integer(ik) :: sweeps, bad, npts, cnt
     integer(c_int) :: tick_up(3), tick, zero_flag, rcb
-    logical :: use_max, resident, host_faces, late_balance, bz_done
+    logical :: use_max, resident, host_faces, late_balance, bz_done, field, any2d
     character(len=1) :: bc3(6)
-    type(c_ptr) :: dAout, dBout, u3, rhs2, u2
+    type(c_ptr) :: dAout, dBout, u3, rhs2, u2, rhs3
+    type(c_ptr) :: dBsrc, dAp, dBp, hAdst, hBdst
     integer(c_size_t) :: nb, off_y, off_z, fr, tot
     type(face_data), target :: fc(6)
 
     rc = 0
+    md = VP_POTENTIAL
+    if (present(mode)) md = mode
+    field = .false.; shift = 0; any2d = .false.
+    dBsrc = c_null_ptr; dAp = c_null_ptr; dBp = c_null_ptr
     n3 = ctx%n3
     use_max = (iopt(IOPT_DUMAX) == 1)
     iopt(IOPT_FAIL3D) = 0
@@ -468,9 +497,21 @@ contains
     call get_environment_variable("NDSM_HIP_HOST_FACES", status=st)   ! A/B testing: the host face phase (vecpot_faces)
     host_faces = (st == 0) .and. .not. on_device
     tick_up = -1
+    hAdst = c_null_ptr; hBdst = c_null_ptr                             ! host arrays the results go home to
     if (.not. on_device) then
       call c_f_pointer(pA, hA, [int(n3(1)), int(n3(2)), int(n3(3)), 3])
       call c_f_pointer(pB, hB, [int(n3(1)), int(n3(2)), int(n3(3)), 3])
+      hAdst = pA; hBdst = pB
+    end if
+
+    ! the field modes keep up to five fields next to the 3-D hierarchy (at least five level-1 arrays): a grid
+    ! the device cannot hold at all is refused before anything is allocated
+    if (md /= VP_POTENTIAL) then
+      rc = ndsmk_mem_info(fr, tot); if (rc /= 0) return
+      if (real(nb, wp) * real(merge(5, 0, .not. ctx%live3) + 3 * merge(5, 2, md == VP_HELICITY), wp) > real(tot, wp)) then
+        rc = ndsmk_note_error(NDSMK_ENODEV, "the grid needs more device memory than the device has"//c_null_char)
+        return
+      end if
     end if
 
     ! ---- device arrays of this call ----------------------------------
@@ -501,149 +542,91 @@ contains
     resident = .true.
     if (on_device) then
       dAout = pA; dBout = pB
+      if (md == VP_FIELD) dBsrc = pB                                 ! (read by the right-hand sides, then overwritten)
+      if (md == VP_HELICITY) then
+        dBsrc = pB; dAp = pAp; dBp = pBp
+        if (.not. c_associated(ctx%dB)) then                         ! B_rec
+          rc = ndsmk_alloc(ctx%dB, 3_c_size_t * nb); if (rc /= 0) return
+        end if
+      end if
     else
       if (.not. c_associated(ctx%dA)) then
         rc = ndsmk_alloc(ctx%dA, 3_c_size_t * nb); if (rc /= 0) return
       end if
       if (.not. c_associated(ctx%dB)) then
-        ! B next to the hierarchy if HBM has room for both; otherwise it takes the memory the 3-D
-        ! hierarchy returns after the solves (the peak is then A + one hierarchy, as before)
-        rc = ndsmk_mem_info(fr, tot); if (rc /= 0) return
-        resident = fr >= 3_c_size_t * nb + ishft(1_c_size_t, 31)
-        call get_environment_variable("NDSM_HIP_LEAN", status=st)      ! testing: take the small-HBM sequence
-        if (st == 0) resident = .false.
+        if (md == VP_POTENTIAL) then
+          ! B next to the hierarchy if HBM has room for both; otherwise it takes the memory the 3-D
+          ! hierarchy returns after the solves (the peak is then A + one hierarchy, as before)
+          rc = ndsmk_mem_info(fr, tot); if (rc /= 0) return
+          resident = fr >= 3_c_size_t * nb + ishft(1_c_size_t, 31)
+          call get_environment_variable("NDSM_HIP_LEAN", status=st)      ! testing: take the small-HBM sequence
+          if (st == 0) resident = .false.
+        end if
         if (resident) then
           rc = ndsmk_alloc(ctx%dB, 3_c_size_t * nb); if (rc /= 0) return
         end if
       end if
       dAout = ctx%dA; dBout = ctx%dB
+      if (md == VP_FIELD) then
+        ! the whole field goes up: the right-hand sides are its curl (dB then receives curl A + balance)
+        rc = ndsmk_h2d(ctx%dB, pB, 3_c_size_t * nb); if (rc /= 0) goto 900
+        dBsrc = ctx%dB
+      else if (md == VP_HELICITY) then
+        do i = 1, 3
+          if (.not. c_associated(ctx%dF(i))) then
+            rc = ndsmk_alloc(ctx%dF(i), 3_c_size_t * nb); if (rc /= 0) goto 900
+          end if
+        end do
+        rc = ndsmk_h2d(ctx%dF(1), pB, 3_c_size_t * nb); if (rc /= 0) goto 900
+        dBsrc = ctx%dF(1); dAp = ctx%dF(2); dBp = ctx%dF(3)
+      end if
       ! the worker thread looks at the caller's initial guess meanwhile: components that are not all zero
       ! (the reference's Python passes zeros, ndsm.py:176) go up into their slot of dA
-      do c = 1, 3
-        rc = ndsmk_bg_upload_unless_zero(c_loc(hA(1, 1, 1, c)), dptr_offset(ctx%dA, int(c - 1, c_size_t) * nb), nb, tick_up(c))
-        if (rc /= 0) goto 900
-      end do
-    end if
-
-    ! ---- 1. B.n on the faces, their fluxes -----------------------------
-    call say(me, "Allocate memory to hold boundary conditions...")
-    if (host_faces) then
-      do f = 1, 6
-        fc(f)%n1 = n3(face_t1(f)); fc(f)%n2 = n3(face_t2(f))
-        allocate (fc(f)%bn(fc(f)%n1, fc(f)%n2), fc(f)%chi(fc(f)%n1, fc(f)%n2))
-        allocate (fc(f)%at1(fc(f)%n1, fc(f)%n2), fc(f)%at2(fc(f)%n1, fc(f)%n2))
-        call face_gather(hB, n3, f, fc(f)%bn)
-      end do
-      rc = vecpot_faces(iopt, ropt, ctx%qx, ctx%qy, ctx%qz, dq, span, fc, phi, ierr2d)
-      if (rc /= 0) goto 900
-    else
-      if (on_device) then
-        rc = ndsmk_face_extract(pB, n3, ctx%dbn); if (rc /= 0) goto 900
-      else
-        call c_f_pointer(ctx%hbn, stage, [ctx%ftotal + 8])
-        do f = 1, 6
-          call face_gather_flat(hB, n3, f, stage(ctx%foff(f) + 1:ctx%foff(f) + int(n3(face_t1(f)), ik) * int(n3(face_t2(f)), ik)))
-        end do
-        rc = ndsmk_h2d_async(ctx%dbn, ctx%hbn, int(ctx%ftotal, c_size_t) * 8_c_size_t); if (rc /= 0) goto 900
-        ! everything this call reads of the caller's arrays has been read (A: by the upload jobs queued above,
-        ! B: its six faces just now); both will be overwritten completely.  Callers like numpy hand over
-        ! untouched pages: the worker touches them (4 threads) before the downloads come, which then run at
-        ! 50 GB/s instead of 13
-        rc = ndsmk_bg_first_touch(pA, 3_c_size_t * nb, tick); if (rc /= 0) goto 900
-        rc = ndsmk_bg_first_touch(pB, 3_c_size_t * nb, tick); if (rc /= 0) goto 900
-      end if
-      rc = ndsmk_face_flux(ctx%dbn, n3, dq(1) * dq(2), ctx%dphi); if (rc /= 0) goto 900     ! Q4
-      rc = ndsmk_d2h(c_loc(phi), ctx%dphi, 48_c_size_t); if (rc /= 0) goto 900
-
-      ! ---- 2. chi on every face: 2-D all-Neumann solves, right-hand side and result stay in HBM ----
-      call say(me, "Solve BVP on each boundary...")
-      ! The six problems are independent (:338-365 solves them one after the other) and each is dispatch
-      ! latency plus one host round trip per V-cycle: they run in lockstep on six streams (mg_solve_lanes;
-      ! every solve executes the kernels it would execute alone, in the same order - same bits).
-      ! NDSM_HIP_FACE_LANES=0: one after the other (A/B testing).
-      ierr2d = 0
-      do f = 1, 6
-        associate (s2 => ctx%s2(f))
-          s2%ms = int(iopt(IOPT_MS)); s2%ex_tol = ropt(ROPT_CTOL); s2%use_max = use_max
-          s2%nmax_exact = int(iopt(IOPT_NMAXEX))
-          rhs2 = mg_level_ptr(s2, 1, MG_BUF_RHS, cnt)
-          u2 = mg_level_ptr(s2, 1, MG_BUF_U, cnt)
-          rc = ndsmk_face_rhs(ctx%dbn, n3, int(f - 1, c_int), ctx%dphi, area(f), rhs2); if (rc /= 0) goto 900
-          call mg_mark_rhs_set(s2)
-          rc = ndsmk_fill0(u2, int(cnt, c_size_t) * 8_c_size_t); if (rc /= 0) goto 900
-          rc = mg_reset_info(s2); if (rc /= 0) goto 900
-        end associate
-      end do
-      call get_environment_variable("NDSM_HIP_FACE_LANES", envbuf, status=st)
-      if (st == 0 .and. envbuf(1:1) == "0") then
-        do f = 1, 6
-          rc = mg_solve(ctx%s2(f), ropt(ROPT_VTOL), int(iopt(IOPT_NCYCLES)), du6(f), ncyc6(f), ierr6(f))
+      if (md /= VP_HELICITY) then
+        do c = 1, 3
+          rc = ndsmk_bg_upload_unless_zero(c_loc(hA(1, 1, 1, c)), dptr_offset(ctx%dA, int(c - 1, c_size_t) * nb), nb, &
+                                           tick_up(c))
           if (rc /= 0) goto 900
         end do
-      else
-        rc = mg_solve_lanes(ctx%s2, ropt(ROPT_VTOL), int(iopt(IOPT_NCYCLES)), du6, ncyc6, ierr6)
-        if (rc /= 0) goto 900
       end if
-      do f = 1, 6
-        u2 = mg_level_ptr(ctx%s2(f), 1, MG_BUF_U, cnt)                  ! (the solver swaps its buffers)
-        rc = ndsmk_d2d(dptr_offset(ctx%dchi, int(ctx%foff(f), c_size_t) * 8_c_size_t), u2, int(cnt, c_size_t) * 8_c_size_t)
-        if (rc /= 0) goto 900
-        ierr2d = ierr6(f)
-        if (ierr2d /= 0) print *, "Warning: IOPT_NCYCLES exceeded. V-cycle iteration may not have converged"
-        if (mg_read_info(ctx%s2(f), sweeps, bad) == 0) then
-          if (bad > 0) print *, "Warning: IOPT_NMAXEX exceeded. Coarse-mesh solution may not have converged"
-        end if
-      end do
-      call say(me, "Compute vector potential boundary conditions...")
     end if
 
-    ! ---- 4. the three 3-D Laplace problems ----------------------------
-    call say(me, "Solve BVP 3D...")
-    if (ctx%live3x .and. iopt(IOPT_PREC) == 0) then
-      do c = 1, 3
-        rc = prep3(ctx%s3v(c), c); if (rc /= 0) goto 900
-      end do
-      rc = mg_solve_lanes(ctx%s3v, ropt(ROPT_VTOL), int(iopt(IOPT_NCYCLES)), du3, ncyc3, ierr3); if (rc /= 0) goto 900
-      do c = 1, 3
-        rc = finish3(ctx%s3v(c), c, du3(c), ncyc3(c), ierr3(c)); if (rc /= 0) goto 900
-      end do
-    else
-      do c = 1, 3
-        rc = prep3(ctx%s3v(1), c); if (rc /= 0) goto 900
-        rc = mg_solve(ctx%s3v(1), ropt(ROPT_VTOL), int(iopt(IOPT_NCYCLES)), du_last, ncyc, ierr3d)
-        if (rc /= 0) goto 900
-        rc = finish3(ctx%s3v(1), c, du_last, ncyc, ierr3d); if (rc /= 0) goto 900
-      end do
-    end if
-    if (.not. on_device .and. .not. c_associated(ctx%dB)) then      ! HBM too small for both (see above)
-      call mg_destroy(ctx%s3v(1)); ctx%live3 = .false.
-      if (ctx%live3x) then
-        call mg_destroy(ctx%s3v(2)); call mg_destroy(ctx%s3v(3)); ctx%live3x = .false.
-      end if
-      rc = ndsmk_alloc(ctx%dB, 3_c_size_t * nb); if (rc /= 0) goto 900
-      dBout = ctx%dB
-    end if
+    rc = face_phase(); if (rc /= 0) goto 900
 
-    ! ---- 5. B = curl A (and, IOPT_FLXCRL == 1, the fields afterwards) ----
-    call say(me, "Compute B = curl(B) and flux correction...")
-    if (late_balance) then
-      print *, "FLAG SET: FLXCRL"
-      rc = ndsmk_balance_curl(dAout, dBout, n3, ctx%dmesh, dptr_offset(ctx%dmesh, off_y), dptr_offset(ctx%dmesh, off_z), &
-                              phi, span, dq, 1_c_int)
-      if (rc /= 0) goto 900
+    ! ---- 4. + 5. the 3-D phase and the post phase, once or (helicity) twice ----
+    if (md == VP_HELICITY) then
+      ! the potential field of the same B.n -> Ap, Bp (FAIL3D bits 3-5) ...
+      shift = 3
+      dAout = dAp; dBout = dBp
       if (.not. on_device) then
-        rc = ndsmk_bg_download(pA, dAout, 3_c_size_t * nb, tick); if (rc /= 0) goto 900
+        hAdst = pAp; hBdst = pBp
       end if
-    else if (bz_done) then
-      rc = ndsmk_curl_component(dAout, dBout, n3, dq, 0_c_int); if (rc /= 0) goto 900
-      rc = ndsmk_curl_component(dAout, dBout, n3, dq, 1_c_int); if (rc /= 0) goto 900
+      rc = solve3_phase(); if (rc /= 0) goto 900
+      rc = post_phase(); if (rc /= 0) goto 900
+      ! ... then the whole field -> A and B_rec (library scratch: only the reduction reads it)
+      field = .true.; shift = 0; bz_done = .false.
+      if (on_device) then
+        dAout = pA
+      else
+        dAout = ctx%dA
+      end if
+      dBout = ctx%dB
+      if (.not. on_device) hAdst = pA
+      hBdst = c_null_ptr
+      rc = solve3_phase(); if (rc /= 0) goto 900
+      rc = post_phase(); if (rc /= 0) goto 900
+      call say(me, "Relative helicity...")
+      rc = ndsmk_helicity_reduce(dAout, dAp, dBsrc, dBp, dBout, n3, dq, out8); if (rc /= 0) goto 900
     else
-      rc = ndsmk_curl(dAout, dBout, n3, dq); if (rc /= 0) goto 900
+      field = (md == VP_FIELD)
+      rc = solve3_phase(); if (rc /= 0) goto 900
+      rc = post_phase(); if (rc /= 0) goto 900
     end if
-    if (.not. on_device) then
-      rc = ndsmk_bg_download(pB, dBout, merge(2_c_size_t, 3_c_size_t, bz_done) * nb, tick); if (rc /= 0) goto 900
+    if (md == VP_POTENTIAL) then
+      iopt(IOPT_IERR) = ierr2d                              ! Q3'
+    else
+      iopt(IOPT_IERR) = merge(1, 0, any2d .or. iopt(IOPT_FAIL3D) /= 0)
     end if
-    iopt(IOPT_IERR) = ierr2d                                ! Q3'
     call say(me, "Deallocate memory...")
 
 900 continue
@@ -656,7 +639,146 @@ contains
 
   contains
 
-    ! component c of the 3-D phase on solver s3: initial guess, Dirichlet data, boundary letters, options
+    ! 1.-3. B.n of the six faces, their fluxes, the six 2-D solves and chi (A_t is written per component by prep3)
+    function face_phase() result(rc)
+      integer(c_int) :: rc
+      rc = 0
+      ! ---- 1. B.n on the faces, their fluxes -----------------------------
+      call say(me, "Allocate memory to hold boundary conditions...")
+      if (host_faces) then
+        do f = 1, 6
+          fc(f)%n1 = n3(face_t1(f)); fc(f)%n2 = n3(face_t2(f))
+          allocate (fc(f)%bn(fc(f)%n1, fc(f)%n2), fc(f)%chi(fc(f)%n1, fc(f)%n2))
+          allocate (fc(f)%at1(fc(f)%n1, fc(f)%n2), fc(f)%at2(fc(f)%n1, fc(f)%n2))
+          call face_gather(hB, n3, f, fc(f)%bn)
+        end do
+        rc = vecpot_faces(iopt, ropt, ctx%qx, ctx%qy, ctx%qz, dq, span, fc, phi, ierr2d)
+        if (rc /= 0) return
+        any2d = (ierr2d /= 0)                     ! (only the last flag comes back from vecpot_faces)
+      else
+        if (on_device) then
+          rc = ndsmk_face_extract(pB, n3, ctx%dbn); if (rc /= 0) return
+        else
+          call c_f_pointer(ctx%hbn, stage, [ctx%ftotal + 8])
+          do f = 1, 6
+            call face_gather_flat(hB, n3, f, stage(ctx%foff(f) + 1:ctx%foff(f) + int(n3(face_t1(f)), ik) * int(n3(face_t2(f)), ik)))
+          end do
+          rc = ndsmk_h2d_async(ctx%dbn, ctx%hbn, int(ctx%ftotal, c_size_t) * 8_c_size_t); if (rc /= 0) return
+          ! everything this call reads of the caller's arrays has been read (A: by the upload jobs queued above,
+          ! B: its six faces just now); both will be overwritten completely.  Callers like numpy hand over
+          ! untouched pages: the worker touches them (4 threads) before the downloads come, which then run at
+          ! 50 GB/s instead of 13.  (Helicity: B is read only; A, Ap and Bp are the arrays that come home.)
+          if (md == VP_HELICITY) then
+            rc = ndsmk_bg_first_touch(pA, 3_c_size_t * nb, tick); if (rc /= 0) return
+            rc = ndsmk_bg_first_touch(pAp, 3_c_size_t * nb, tick); if (rc /= 0) return
+            rc = ndsmk_bg_first_touch(pBp, 3_c_size_t * nb, tick); if (rc /= 0) return
+          else
+            rc = ndsmk_bg_first_touch(pA, 3_c_size_t * nb, tick); if (rc /= 0) return
+            rc = ndsmk_bg_first_touch(pB, 3_c_size_t * nb, tick); if (rc /= 0) return
+          end if
+        end if
+        rc = ndsmk_face_flux(ctx%dbn, n3, dq(1) * dq(2), ctx%dphi); if (rc /= 0) return     ! Q4
+        rc = ndsmk_d2h(c_loc(phi), ctx%dphi, 48_c_size_t); if (rc /= 0) return
+
+        ! ---- 2. chi on every face: 2-D all-Neumann solves, right-hand side and result stay in HBM ----
+        call say(me, "Solve BVP on each boundary...")
+        ! The six problems are independent (:338-365 solves them one after the other) and each is dispatch
+        ! latency plus one host round trip per V-cycle: they run in lockstep on six streams (mg_solve_lanes;
+        ! every solve executes the kernels it would execute alone, in the same order - same bits).
+        ! NDSM_HIP_FACE_LANES=0: one after the other (A/B testing).
+        ierr2d = 0
+        do f = 1, 6
+          associate (s2 => ctx%s2(f))
+            s2%ms = int(iopt(IOPT_MS)); s2%ex_tol = ropt(ROPT_CTOL); s2%use_max = use_max
+            s2%nmax_exact = int(iopt(IOPT_NMAXEX))
+            rhs2 = mg_level_ptr(s2, 1, MG_BUF_RHS, cnt)
+            u2 = mg_level_ptr(s2, 1, MG_BUF_U, cnt)
+            rc = ndsmk_face_rhs(ctx%dbn, n3, int(f - 1, c_int), ctx%dphi, area(f), rhs2); if (rc /= 0) return
+            call mg_mark_rhs_set(s2)
+            rc = ndsmk_fill0(u2, int(cnt, c_size_t) * 8_c_size_t); if (rc /= 0) return
+            rc = mg_reset_info(s2); if (rc /= 0) return
+          end associate
+        end do
+        call get_environment_variable("NDSM_HIP_FACE_LANES", envbuf, status=st)
+        if (st == 0 .and. envbuf(1:1) == "0") then
+          do f = 1, 6
+            rc = mg_solve(ctx%s2(f), ropt(ROPT_VTOL), int(iopt(IOPT_NCYCLES)), du6(f), ncyc6(f), ierr6(f))
+            if (rc /= 0) return
+          end do
+        else
+          rc = mg_solve_lanes(ctx%s2, ropt(ROPT_VTOL), int(iopt(IOPT_NCYCLES)), du6, ncyc6, ierr6)
+          if (rc /= 0) return
+        end if
+        do f = 1, 6
+          u2 = mg_level_ptr(ctx%s2(f), 1, MG_BUF_U, cnt)                  ! (the solver swaps its buffers)
+          rc = ndsmk_d2d(dptr_offset(ctx%dchi, int(ctx%foff(f), c_size_t) * 8_c_size_t), u2, int(cnt, c_size_t) * 8_c_size_t)
+          if (rc /= 0) return
+          ierr2d = ierr6(f)
+          if (ierr2d /= 0) any2d = .true.
+          if (ierr2d /= 0) print *, "Warning: IOPT_NCYCLES exceeded. V-cycle iteration may not have converged"
+          if (mg_read_info(ctx%s2(f), sweeps, bad) == 0) then
+            if (bad > 0) print *, "Warning: IOPT_NMAXEX exceeded. Coarse-mesh solution may not have converged"
+          end if
+        end do
+        call say(me, "Compute vector potential boundary conditions...")
+      end if
+    end function
+
+    ! 4. the three 3-D Laplace / Poisson problems into dAout (finish3: + their flux-balance fields)
+    function solve3_phase() result(rc)
+      integer(c_int) :: rc
+      call say(me, "Solve BVP 3D...")
+      if (ctx%live3x .and. iopt(IOPT_PREC) == 0) then
+        do c = 1, 3
+          rc = prep3(ctx%s3v(c), c); if (rc /= 0) return
+        end do
+        rc = mg_solve_lanes(ctx%s3v, ropt(ROPT_VTOL), int(iopt(IOPT_NCYCLES)), du3, ncyc3, ierr3); if (rc /= 0) return
+        do c = 1, 3
+          rc = finish3(ctx%s3v(c), c, du3(c), ncyc3(c), ierr3(c)); if (rc /= 0) return
+        end do
+      else
+        do c = 1, 3
+          rc = prep3(ctx%s3v(1), c); if (rc /= 0) return
+          rc = mg_solve(ctx%s3v(1), ropt(ROPT_VTOL), int(iopt(IOPT_NCYCLES)), du_last, ncyc, ierr3d)
+          if (rc /= 0) return
+          rc = finish3(ctx%s3v(1), c, du_last, ncyc, ierr3d); if (rc /= 0) return
+        end do
+      end if
+      if (.not. on_device .and. .not. c_associated(ctx%dB)) then      ! HBM too small for both (see above)
+        call mg_destroy(ctx%s3v(1)); ctx%live3 = .false.
+        if (ctx%live3x) then
+          call mg_destroy(ctx%s3v(2)); call mg_destroy(ctx%s3v(3)); ctx%live3x = .false.
+        end if
+        rc = ndsmk_alloc(ctx%dB, 3_c_size_t * nb); if (rc /= 0) return
+        dBout = ctx%dB
+      end if
+    end function
+
+    ! 5. B = curl A (and, IOPT_FLXCRL == 1, the fields afterwards) into dBout
+    function post_phase() result(rc)
+      integer(c_int) :: rc
+      call say(me, "Compute B = curl(B) and flux correction...")
+      if (late_balance) then
+        print *, "FLAG SET: FLXCRL"
+        rc = ndsmk_balance_curl(dAout, dBout, n3, ctx%dmesh, dptr_offset(ctx%dmesh, off_y), dptr_offset(ctx%dmesh, off_z), &
+                                phi, span, dq, 1_c_int)
+        if (rc /= 0) return
+        if (c_associated(hAdst)) then
+          rc = ndsmk_bg_download(hAdst, dAout, 3_c_size_t * nb, tick); if (rc /= 0) return
+        end if
+      else if (bz_done) then
+        rc = ndsmk_curl_component(dAout, dBout, n3, dq, 0_c_int); if (rc /= 0) return
+        rc = ndsmk_curl_component(dAout, dBout, n3, dq, 1_c_int); if (rc /= 0) return
+      else
+        rc = ndsmk_curl(dAout, dBout, n3, dq); if (rc /= 0) return
+      end if
+      if (c_associated(hBdst)) then
+        rc = ndsmk_bg_download(hBdst, dBout, merge(2_c_size_t, 3_c_size_t, bz_done) * nb, tick); if (rc /= 0) return
+      end if
+    end function
+
+    ! component c of the 3-D phase on solver s3: initial guess, Dirichlet data, right-hand side, boundary
+    ! letters, options
     function prep3(s3, c) result(rc)
       type(mg_solver), intent(inout) :: s3
       integer, intent(in) :: c
@@ -666,7 +788,9 @@ contains
       s3%precision = int(iopt(IOPT_PREC))
       ! initial guess of component c -> the solver's level-1 array
       u3 = mg_level_ptr(s3, 1, MG_BUF_U, cnt)
-      if (on_device) then
+      if (md == VP_HELICITY) then
+        rc = ndsmk_fill0(u3, nb); if (rc /= 0) return
+      else if (on_device) then
         rc = ndsmk_d2d(u3, dptr_offset(pA, int(c - 1, c_size_t) * nb), nb); if (rc /= 0) return
       else
         rc = ndsmk_bg_wait(tick_up(c), zero_flag); if (rc /= 0) return
@@ -688,6 +812,15 @@ contains
           rc = ndsmk_face_write(u3, n3, ctx%dchi, int(f - 1, c_int), int(c - 1, c_int), fac); if (rc /= 0) return
         end if
       end do
+      ! its right-hand side: -(curl B)_c for the whole field, 0 for the potential field (:640-641).  The solvers
+      ! are cached: the state left by the previous call on this context is set either way.
+      if (field) then
+        rhs3 = mg_level_ptr(s3, 1, MG_BUF_RHS, cnt)
+        rc = ndsmk_curl_rhs(dBsrc, rhs3, n3, dq, int(c - 1, c_int)); if (rc /= 0) return
+        call mg_mark_rhs_set(s3)
+      else if (.not. s3%rhs1_zero) then
+        rc = mg_zero_rhs(s3); if (rc /= 0) return
+      end if
       bc3 = 'D'
       bc3(c) = 'N'; bc3(3 + c) = 'N'                        ! :655,:671,:687
       rc = mg_set_bcs(s3, bc3); if (rc /= 0) return
@@ -708,7 +841,7 @@ contains
       if (mg_read_info(s3, sweeps, bad) == 0) then
         if (bad > 0) print *, "Warning: IOPT_NMAXEX exceeded. Coarse-mesh solution may not have converged"
       end if
-      if (ierr_c /= 0) iopt(IOPT_FAIL3D) = ior(iopt(IOPT_FAIL3D), ishft(1_ik, c - 1))
+      if (ierr_c /= 0) iopt(IOPT_FAIL3D) = ior(iopt(IOPT_FAIL3D), ishft(1_ik, c - 1 + shift))
       if (ncyc_c > 1 .or. c == 1) then
         iopt(IOPT_NCYC_OUT) = ncyc_c
         ropt(ROPT_DULAST) = du_c
@@ -719,17 +852,20 @@ contains
         rc = ndsmk_balance_component(dptr_offset(dAout, int(c - 1, c_size_t) * nb), n3, int(c - 1, c_int), ctx%dmesh, &
                                      dptr_offset(ctx%dmesh, off_y), dptr_offset(ctx%dmesh, off_z), phi, span)
         if (rc /= 0) return
-        if (.not. on_device) then
-          rc = ndsmk_bg_download(c_loc(hA(1, 1, 1, c)), dptr_offset(dAout, int(c - 1, c_size_t) * nb), nb, tick)
+        if (c_associated(hAdst)) then
+          rc = ndsmk_bg_download(dptr_offset(hAdst, int(c - 1, c_size_t) * nb), dptr_offset(dAout, int(c - 1, c_size_t) * nb), &
+                                 nb, tick)
           if (rc /= 0) return
         end if
         ! B_z = d(A_y)/dx - d(A_x)/dy needs the two components that are final now: it is formed here and goes
-        ! home behind the A_z solve as well (when B's device array exists already: not on the lean path)
+        ! home behind the A_z solve as well (when B's device array exists already: not on the lean path; and not
+        ! where B_z would overwrite the field the A_z solve still takes its right-hand side from)
         call get_environment_variable("NDSM_HIP_NO_EARLY_BZ", status=st3)      ! A/B testing: one curl at the end
-        if (c == 2 .and. c_associated(dBout) .and. all(n3 >= 3) .and. st3 /= 0) then
+        if (c == 2 .and. c_associated(dBout) .and. all(n3 >= 3) .and. st3 /= 0 .and. &
+            .not. (field .and. c_associated(dBsrc, dBout))) then
           rc = ndsmk_curl_component(dAout, dBout, n3, dq, 2_c_int); if (rc /= 0) return
-          if (.not. on_device) then
-            rc = ndsmk_bg_download(c_loc(hB(1, 1, 1, 3)), dptr_offset(dBout, 2_c_size_t * nb), nb, tick)
+          if (c_associated(hBdst)) then
+            rc = ndsmk_bg_download(dptr_offset(hBdst, 2_c_size_t * nb), dptr_offset(dBout, 2_c_size_t * nb), nb, tick)
             if (rc /= 0) return
           end if
           bz_done = .true.

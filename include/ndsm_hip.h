@@ -197,6 +197,29 @@ int ndsm_hip_vecpot_helicity(void *h, int ioptc[16], double ropt[16], const doub
 int ndsm_hip_vecpot_helicity_device(void *h, int ioptc[16], double ropt[16], const double *dB, double *dA,
                                     double *dAp, double *dBp, double out[8]);
 
+/* ---- solenoidal projection (divergence cleaning) on the same handle (DESIGN.md "Solenoidal projection") ----
+ * The helicity entries assume div B = 0.  These return B' = B - G_h phi, laplace_7(phi) = div_h B - c with all
+ * six faces Neumann and c = sum w div_h B / sum w (trapezoid weights w, as above): div_h with derivq's
+ * differences, G_h phi the centred difference inside and 0 on the two end planes of each axis, so
+ *   - B.n on the six faces is left bitwise untouched: the potential field of B' is that of B, bit for bit;
+ *   - a field with div_h B = 0 (each component independent of its own coordinate, say) comes back bitwise;
+ *   - c, the uniform part (net boundary flux / volume), cannot be removed by any projection that keeps B.n:
+ *     it stays in div_h B' and is reported;
+ *   - div_h G_h is the wide stencil, not laplace_7: the projection is approximate (collocated), div_h B' is a
+ *     truncation error, O(h^2) relative to the divergence removed, not zero.
+ * The solve is the 3-D multigrid with the options in the usual slots (ms, ncycles, nmaxex, dumax, vtol, ctol,
+ * ngrids: the handle's), from phi = 0, always fp64 (IOPT_PREC is accepted and ignored).  ioptc[IOPT_IERR],
+ * ioptc[get_iopt_ncyc_out()], ropt[get_ropt_dulast()] report the solve.  The all-Neumann hierarchy is created
+ * at the first projection on a handle and kept with it.  Device callers chain ndsm_hip_vecpot_project_device
+ * -> ndsm_hip_vecpot_helicity_device on the same device arrays, nothing crosses PCIe in between.
+ * Without a GPU both return 9001 whatever the handle (a NULL handle with a GPU: 9002); on every error out[4] is
+ * cleared, and B is left untouched when the call fails before the projection runs. */
+/* B in: the field (nx,ny,nz,3); out: B - G_h phi (B.n on the six faces untouched).
+ * phi: (nx,ny,nz) out, may be NULL.  out[4]: [0] c = sum w div_h B / sum w (left in div_h B'),
+ * [1] max|div_h B| before, [2] max|div_h B'| after, [3] 1/2 sum w |G_h phi|^2.  0 / 1 / >= 9001. */
+int ndsm_hip_vecpot_project(void *h, int ioptc[16], double ropt[16], double *B, double *phi, double out[4]);
+int ndsm_hip_vecpot_project_device(void *h, int ioptc[16], double ropt[16], double *dB, double *dphi, double out[4]);
+
 /* =====================================================================
  * PART 3 - additive exports, multi-GPU
  *

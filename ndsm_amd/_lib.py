@@ -235,6 +235,10 @@ class VecPot:
         self.L.ndsm_hip_vecpot_helicity.argtypes = [ctypes.c_void_p, _ip, _dp, _dp, _dp, _dp, _dp, _dp]
         self.L.ndsm_hip_vecpot_helicity_device.argtypes = [ctypes.c_void_p, _ip, _dp, ctypes.c_void_p, ctypes.c_void_p,
                                                            ctypes.c_void_p, ctypes.c_void_p, _dp]
+        self.L.ndsm_hip_vecpot_project.argtypes = [ctypes.c_void_p, _ip, _dp, _dp, _dp, _dp]
+        self.L.ndsm_hip_vecpot_project_device.argtypes = [ctypes.c_void_p, _ip, _dp, ctypes.c_void_p, ctypes.c_void_p,
+                                                          _dp]
+        self.last_projection = None
         self.L.ndsm_hip_device_alloc.argtypes = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
         self.L.ndsm_hip_device_free.argtypes = [ctypes.c_void_p]
         self.L.ndsm_hip_memcpy_h2d.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
@@ -344,15 +348,23 @@ class VecPot:
         return ierr, A.reshape(shape), B.reshape(shape)
 
     def helicity(self, b, niterex_max=10000, ncycles_max=1024, ex_tol=1e-13, vc_tol=1e-10, ms=5, mean=False,
-                 mixed_precision=False, flxcrl=False, device=False, return_fields=False):
+                 mixed_precision=False, flxcrl=False, device=False, return_fields=False, project=False):
         """Relative magnetic helicity of b (3,nz,ny,nx) against the potential field of its B.n, in one call: the
         face phase once, the potential and the field 3-D solves, one deterministic reduction on the device.
         Returns a Helicity tuple (no 4 pi / mu0 factors; trapezoid weights): ierr, H_R (Finn-Antonsen),
         H_J = sum w (A - A_p).(B - B_p), E, E_p, E_free = E - E_p, recon_max / recon_rms of |B_rec - b|,
-        divB_max, divA_max; with return_fields also A, A_p, B_p (else None)."""
+        divB_max, divA_max; with return_fields also A, A_p, B_p (else None).
+        project=True: a copy of b is made solenoidal first (project(), same options) and the helicity is that of
+        the projected field; ierr is the larger of the two, the Projection is kept as self.last_projection."""
+        B = self._field_arg(b, "helicity")
+        ierr_p = 0
+        if project:
+            pr = self.project(B.reshape(tuple(int(v) for v in self.nshape4[::-1])), niterex_max=niterex_max,
+                              ncycles_max=ncycles_max, ex_tol=ex_tol, vc_tol=vc_tol, ms=ms, mean=mean, device=device)
+            ierr_p = pr.ierr
+            B = pr.B.reshape(-1).copy()
         ioptc, ropt = self._options(niterex_max, ncycles_max, ex_tol, vc_tol, ms, mean, mixed_precision, flxcrl)
         shape = tuple(int(v) for v in self.nshape4[::-1])
-        B = self._field_arg(b, "helicity")
         A, Ap, Bp = np.empty(B.size), np.empty(B.size), np.empty(B.size)
         out = np.zeros(8)
         if not device:
@@ -365,8 +377,43 @@ class VecPot:
             _check(ierr, "ndsm_hip_vecpot_helicity", self.L)
         self.last_ioptc, self.last_ropt = ioptc, ropt
         f = (A.reshape(shape), Ap.reshape(shape), Bp.reshape(shape)) if return_fields else (None, None, None)
-        return Helicity(int(ierr), float(out[0]), float(out[1]), float(out[2]), float(out[3]), float(out[2] - out[3]),
-                        float(out[4]), float(out[5]), float(out[6]), float(out[7]), *f)
+        return Helicity(int(max(ierr, ierr_p)), float(out[0]), float(out[1]), float(out[2]), float(out[3]),
+                        float(out[2] - out[3]), float(out[4]), float(out[5]), float(out[6]), float(out[7]), *f)
+
+    def project(self, b, niterex_max=10000, ncycles_max=1024, ex_tol=1e-13, vc_tol=1e-10, ms=5, mean=False,
+                mixed_precision=False, flxcrl=False, device=False, return_phi=False):
+        """Solenoidal projection (divergence cleaning) of b (3,nz,ny,nx): B' = b - G_h phi with laplace_7(phi) =
+        div_h b - c, all six faces Neumann, c = sum w div_h b / sum w.  B.n on the six faces is left bitwise
+        as it is, so the potential field does not change; c (net boundary flux / volume) cannot be removed by
+        such a projection and stays in div_h B'.  Approximate (collocated): div_h B' is O(h^2) relative to
+        what was removed, not zero.  Options as for solve_field; the solve is always fp64 (mixed_precision and
+        flxcrl are accepted and ignored).  Returns a Projection tuple: ierr (0 the solve reached vc_tol, else
+        1), B', phi (return_phi, else None), c, divB_before / divB_after (max |div_h|), E_removed =
+        1/2 sum w |G_h phi|^2, ncycles, du_last.  device=True: the device-resident entry point runs."""
+        shape = tuple(int(v) for v in self.nshape4[::-1])
+        B = self._field_arg(b, "project")
+        ioptc, ropt = self._options(niterex_max, ncycles_max, ex_tol, vc_tol, ms, mean, 0, False)
+        phi = np.zeros(B.size // 3) if return_phi else None
+        out = np.zeros(4)
+        if not device:
+            ierr = self.L.ndsm_hip_vecpot_project(self.h, ioptc.ctypes.data_as(_ip), _d(ropt), _d(B),
+                                                  _d(phi) if return_phi else None, _d(out))
+        else:
+            arrays = [B, phi] if return_phi else [B]
+            ierr = self._on_device(arrays, lambda dB, dphi=None: self.L.ndsm_hip_vecpot_project_device(
+                self.h, ioptc.ctypes.data_as(_ip), _d(ropt), dB, dphi, _d(out)))
+        if ierr >= 9000:
+            _check(ierr, "ndsm_hip_vecpot_project", self.L)
+        self.last_ioptc, self.last_ropt = ioptc, ropt
+        p = Projection(int(ierr), B.reshape(shape), phi.reshape(shape[1:]) if return_phi else None, float(out[0]),
+                       float(out[1]), float(out[2]), float(out[3]), int(ioptc[self.L.get_iopt_ncyc_out()]),
+                       float(ropt[self.L.get_ropt_dulast()]))
+        self.last_projection = p
+        return p
+
+
+Projection = collections.namedtuple("Projection", ["ierr", "B", "phi", "c", "divB_before", "divB_after", "E_removed",
+                                                   "ncycles", "du_last"])
 
 
 Helicity = collections.namedtuple("Helicity", ["ierr", "H_R", "H_J", "E", "E_p", "E_free", "recon_max", "recon_rms",
@@ -396,13 +443,27 @@ def vector_potential_field(x, y, z, b, a_init=None, niterex_max=10000, ncycles_m
 
 
 def relative_helicity(x, y, z, b, niterex_max=10000, ncycles_max=1024, ex_tol=1e-13, vc_tol=1e-10, ms=5, mean=False,
-                      mixed_precision=False, flxcrl=False, ngrids=0, return_fields=False, lib=None):
+                      mixed_precision=False, flxcrl=False, ngrids=0, return_fields=False, project=False, lib=None):
     """Relative helicity, energies and reconstruction diagnostics of b (3,nz,ny,nx): one-shot form of
-    VecPot.helicity (returns its Helicity tuple).  Raises NdsmHipError on device / runtime failures (>= 9001)."""
+    VecPot.helicity (returns its Helicity tuple; project=True: of the solenoidal projection of b).  Raises
+    NdsmHipError on device / runtime failures (>= 9001)."""
     V = _grid_handle(x, y, z, b, ngrids, lib)
     try:
         return V.helicity(b, niterex_max=niterex_max, ncycles_max=ncycles_max, ex_tol=ex_tol, vc_tol=vc_tol, ms=ms,
-                          mean=mean, mixed_precision=mixed_precision, flxcrl=flxcrl, return_fields=return_fields)
+                          mean=mean, mixed_precision=mixed_precision, flxcrl=flxcrl, return_fields=return_fields,
+                          project=project)
+    finally:
+        V.close()
+
+
+def solenoidal_projection(x, y, z, b, niterex_max=10000, ncycles_max=1024, ex_tol=1e-13, vc_tol=1e-10, ms=5,
+                          mean=False, mixed_precision=False, ngrids=0, return_phi=False, lib=None):
+    """Divergence cleaning of b (3,nz,ny,nx): one-shot form of VecPot.project (returns its Projection tuple).
+    Raises NdsmHipError on device / runtime failures (>= 9001)."""
+    V = _grid_handle(x, y, z, b, ngrids, lib)
+    try:
+        return V.project(b, niterex_max=niterex_max, ncycles_max=ncycles_max, ex_tol=ex_tol, vc_tol=vc_tol, ms=ms,
+                         mean=mean, mixed_precision=mixed_precision, return_phi=return_phi)
     finally:
         V.close()
 

@@ -11,6 +11,7 @@
 //              block sums a fixed set of grid rows in a fixed order, one block then sums the block
 //              partials in a fixed order; the grid size depends on the shape alone.
 #include "common.hpp"
+#include "diffq.hpp"
 
 namespace {
 
@@ -19,24 +20,8 @@ struct CurlArgs {
   double dq[3];
 };
 
-// d/dq along one axis at index q of n (stride s): post.hip's ddq, the same operand order
-__device__ __forceinline__ double ddq(const double *__restrict__ v, size_t c, int q, int n, size_t s, double h) {
-  const double half = 0.5;
-  double d = 0.0;
-  if (q == 0) {
-    d = d + v[c] * (-3 * half / h);
-    d = d + v[c + s] * (+4 * half / h);
-    d = d + v[c + 2 * s] * (-1 * half / h);
-  } else if (q == n - 1) {
-    d = d + v[c] * (+3 * half / h);
-    d = d + v[c - s] * (-4 * half / h);
-    d = d + v[c - 2 * s] * (+1 * half / h);
-  } else {
-    d = d + v[c - s] * (-1 * half / h);
-    d = d + v[c + s] * (+1 * half / h);
-  }
-  return d;
-}
+using ndsm::ddq;
+using ndsm::trap_w;
 
 template <int C>
 __global__ __launch_bounds__(256) void curl_rhs_k(const double *__restrict__ B, double *__restrict__ rhs, CurlArgs p) {
@@ -73,8 +58,6 @@ struct HelArgs {
   double dq[3];
   size_t nrows;   // ny * nz
 };
-
-__device__ __forceinline__ double trap_w(int q, int n, double h) { return (q == 0 || q == n - 1) ? 0.5 * h : h; }
 
 // block partials: v[0..5] = sums of w (A+Ap).(B-Bp), w (A-Ap).(B-Bp), w |B|^2, w |Bp|^2, w |Br-B|^2, w;
 // v[6..8] = maxima of |Br-B| (over points and components), |div_h B|, |div_h A|.  Block b walks rows b,

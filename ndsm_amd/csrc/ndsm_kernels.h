@@ -189,6 +189,14 @@ int ndsmk_curl_rhs(const double *B, double *rhs, const int32_t *n3, const double
 int ndsmk_helicity_reduce(const double *A, const double *Ap, const double *B, const double *Bp, const double *Br,
                           const int32_t *n3, const double *h_dq3, double *h_out8);
 
+/* the solenoidal projection (project.hip), all DEVICE arrays: rhs = div_h B - c into the projection solver's
+ * level-1 rhs (c = sum w div_h B / sum w stays on the device); B -= G_h phi, the normal component on the end
+ * planes of its axis untouched; then, blocking, max |div_h B'| and h_out4 = [c, max |div_h B| before, after,
+ * 1/2 sum w |G_h phi|^2].  Deterministic reductions. */
+int ndsmk_project_div_rhs(const double *B, double *rhs, const int32_t *n3, const double *h_dq3);
+int ndsmk_project_grad_sub(double *B, const double *phi, const int32_t *n3, const double *h_dq3);
+int ndsmk_project_div_max(const double *B, const int32_t *n3, const double *h_dq3, double *h_out4);
+
 /* the face phase on the device (faces.hip): packed face buffers, six faces back to back */
 int ndsmk_face_offsets(const int32_t *n3, int64_t *off6, int64_t *total);
 int ndsmk_face_extract(const double *B, const int32_t *n3, double *faces);

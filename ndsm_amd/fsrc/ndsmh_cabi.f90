@@ -796,6 +796,70 @@ contains
     end if
   end function
 
+  ! ---- solenoidal projection on the same handle ------------------------
+  ! B in: the field (nx,ny,nz,3); out: B - G_h phi, laplace_7(phi) = div_h B - c with all six faces Neumann
+  ! (B.n on the six faces untouched).  phi (nx,ny,nz) out, may be null.  out4: c = sum w div_h B / sum w (left in
+  ! div_h B'), max |div_h B| before, max |div_h B'| after, 1/2 sum w |G_h phi|^2.  Return value: 0 the solve
+  ! reached vc_tol, 1 it did not, >= 9001 errors (9002: an ngrids slot other than the handle's).
+
+  ! HOST arrays
+  function ndsm_hip_vecpot_project(handle, ioptc, ropt, B, phi, out4) bind(c, name="ndsm_hip_vecpot_project") &
+      result(ierr)
+    type(c_ptr), value :: handle, B, phi
+    integer(c_int), intent(inout) :: ioptc(0:OPT_LEN - 1)
+    real(c_double), intent(inout) :: ropt(0:OPT_LEN - 1)
+    real(c_double), intent(out) :: out4(4)
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_project(handle, ioptc, ropt, B, phi, out4, .false., "ndsm_hip_vecpot_project")
+  end function
+
+  ! the same on DEVICE arrays of the library's GPU
+  function ndsm_hip_vecpot_project_device(handle, ioptc, ropt, dB, dphi, out4) &
+      bind(c, name="ndsm_hip_vecpot_project_device") result(ierr)
+    type(c_ptr), value :: handle, dB, dphi
+    integer(c_int), intent(inout) :: ioptc(0:OPT_LEN - 1)
+    real(c_double), intent(inout) :: ropt(0:OPT_LEN - 1)
+    real(c_double), intent(out) :: out4(4)
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_project(handle, ioptc, ropt, dB, dphi, out4, .true., "ndsm_hip_vecpot_project_device")
+  end function
+
+  function vecpot_handle_project(handle, ioptc, ropt, B, phi, out4, on_device, who) result(ierr)
+    type(c_ptr), intent(in) :: handle, B, phi
+    integer(c_int), intent(inout) :: ioptc(0:OPT_LEN - 1)
+    real(c_double), intent(inout) :: ropt(0:OPT_LEN - 1)
+    real(c_double), intent(out) :: out4(4)
+    logical, intent(in) :: on_device
+    character(len=*), intent(in) :: who
+    integer(c_int) :: ierr
+    type(vecpot_ctx), pointer :: ctx
+    integer(ik) :: iopt(0:OPT_LEN - 1)
+    real(c_double) :: t0
+    integer(c_int) :: rc
+    out4 = 0
+    ierr = ndsmk_init(-1_c_int)                        ! without a device: 9001, whatever the arguments
+    if (ierr /= 0) return
+    ierr = NDSMK_EARG
+    if (.not. (c_associated(handle) .and. c_associated(B))) return
+    call c_f_pointer(handle, ctx)
+    if (.not. ctx%live) return
+    iopt = ioptc
+    verbose = (iopt(IOPT_DEBUG) == 1)
+    t0 = wall_seconds()
+    rc = NDSMK_EARG
+    if (int(iopt(IOPT_NGRIDS)) == ctx%ngr) rc = vecpot_project(ctx, iopt, ropt, B, phi, on_device, out4)
+    ropt(ROPT_TIM) = wall_seconds() - t0
+    ioptc = int(iopt, c_int)
+    if (rc /= 0) then
+      call report(who, rc)
+      if (rc < NDSMK_ENODEV) rc = NDSMK_ENODEV
+      ioptc(IOPT_IERR) = rc
+      ierr = rc
+    else
+      ierr = int(iopt(IOPT_IERR), c_int)
+    end if
+  end function
+
   ! ---- z-slab decomposition over GPUs (SURVEY 8e) -----------------------
 
   ! rank 0 creates the 128-byte RCCL id; the launcher hands it to every rank

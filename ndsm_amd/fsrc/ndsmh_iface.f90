@@ -525,6 +525,30 @@ module ndsmh_iface
       integer(c_int) :: rc
     end function
 
+    ! ---- the solenoidal projection (project.hip) ----
+    function ndsmk_project_div_rhs(B, rhs, n3, dq3) bind(c, name="ndsmk_project_div_rhs") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_double
+      type(c_ptr), value :: B, rhs
+      integer(c_int32_t), intent(in) :: n3(3)
+      real(c_double), intent(in) :: dq3(3)
+      integer(c_int) :: rc
+    end function
+    function ndsmk_project_grad_sub(B, phi, n3, dq3) bind(c, name="ndsmk_project_grad_sub") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_double
+      type(c_ptr), value :: B, phi
+      integer(c_int32_t), intent(in) :: n3(3)
+      real(c_double), intent(in) :: dq3(3)
+      integer(c_int) :: rc
+    end function
+    function ndsmk_project_div_max(B, n3, dq3, out4) bind(c, name="ndsmk_project_div_max") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_double
+      type(c_ptr), value :: B
+      integer(c_int32_t), intent(in) :: n3(3)
+      real(c_double), intent(in) :: dq3(3)
+      real(c_double), intent(out) :: out4(4)
+      integer(c_int) :: rc
+    end function
+
     ! ---- the face phase on the device (faces.hip) ----
     function ndsmk_face_offsets(n3, off6, total) bind(c, name="ndsmk_face_offsets") result(rc)
       import :: c_int, c_int32_t, c_int64_t

@@ -32,6 +32,7 @@ module ndsmh_vecpot
 
   public :: vecpot_solve, poisson_solve
   public :: vecpot_ctx, vecpot_ctx_create, vecpot_ctx_destroy, vecpot_ctx_matches, vecpot_run, vecpot_cache_drop
+  public :: vecpot_project
   public :: VP_POTENTIAL, VP_FIELD, VP_HELICITY
   ! pieces the distributed driver (ndsmh_wvecpot) shares with vecpot_solve
   public :: face_data, face_axis, face_upper, face_t1, face_t2, face_order, face_copy, vecpot_faces, say
@@ -95,6 +96,8 @@ module ndsmh_vecpot
     type(c_ptr) :: dbn = c_null_ptr, dchi = c_null_ptr, dphi = c_null_ptr   ! packed faces: B.n, chi; six fluxes
     type(c_ptr) :: hbn = c_null_ptr                                         ! pinned staging of the six faces
     type(c_ptr) :: dF(3) = c_null_ptr       ! host-array helicity calls only: B, A_p, B_p (allocated at the first)
+    type(mg_solver) :: sp                   ! the 3-D all-Neumann hierarchy of vecpot_project (created at the first)
+    logical :: livep = .false.
     integer(ik) :: foff(6) = 0, ftotal = 0
   end type
 
@@ -309,6 +312,8 @@ contains
       call mg_destroy(ctx%s3v(2)); call mg_destroy(ctx%s3v(3))
     end if
     ctx%live3 = .false.; ctx%live3x = .false.
+    if (ctx%livep) call mg_destroy(ctx%sp)
+    ctx%livep = .false.
     do p = 1, 6
       if (ctx%live2(p)) call mg_destroy(ctx%s2(p))
       ctx%live2(p) = .false.
@@ -872,6 +877,101 @@ contains
         end if
       end if
     end function
+  end function
+
+  ! ------------------------------------------------------------------
+  ! Solenoidal projection on a prepared context (DESIGN.md "Solenoidal projection"): B' = B - G_h phi,
+  ! laplace_7(phi) = div_h B - c with all six faces Neumann, c = sum w div_h B / sum w (the part no projection
+  ! that keeps B.n can remove).  pB: (nx,ny,nz,3) in and out, on the HOST or (on_device) in HBM; pphi: phi
+  ! (nx,ny,nz) out, may be null.  out4: c, max |div_h B|, max |div_h B'|, 1/2 sum w |G_h phi|^2.
+  ! The solve is the ordinary 3-D V-cycle with the usual options (ms, ncycles, nmaxex, dumax, vtol, ctol), from
+  ! phi = 0, always fp64: IOPT_PREC is ignored (the mixed-precision cycle refuses all-Neumann levels).
+  ! IOPT_IERR = 0 when the solve reached vc_tol, else 1; IOPT_NCYC_OUT, ROPT_DULAST of the solve.
+  ! The hierarchy is created at the first projection on the context and kept with it.
+  ! ------------------------------------------------------------------
+  function vecpot_project(ctx, iopt, ropt, pB, pphi, on_device, out4) result(rc)
+    type(vecpot_ctx), intent(inout), target :: ctx
+    integer(ik), intent(inout) :: iopt(0:OPT_LEN - 1)
+    real(wp), intent(inout) :: ropt(0:OPT_LEN - 1)
+    type(c_ptr), intent(in) :: pB, pphi
+    logical, intent(in) :: on_device
+    real(wp), intent(out) :: out4(4)
+    integer(c_int) :: rc
+    character(len=*), parameter :: me = "solenoidal_projection"
+    real(wp) :: dq(3), du
+    integer(c_int32_t) :: n3(3)
+    integer :: ncyc, ierr
+    integer(ik) :: cnt, sweeps, bad
+    integer(c_size_t) :: nb, fr, tot
+    character(len=1) :: bcn(6)
+    type(c_ptr) :: dB, u1, rhs1
+
+    out4 = 0
+    n3 = ctx%n3
+    if (any(n3 < 3)) then
+      rc = ndsmk_note_error(NDSMK_EARG, "the projection needs at least 3 points per axis"//c_null_char)
+      return
+    end if
+    dq = [ctx%qx(2) - ctx%qx(1), ctx%qy(2) - ctx%qy(1), ctx%qz(2) - ctx%qz(1)]
+    nb = int(product(int(n3, ik)), c_size_t) * 8_c_size_t
+    ! the hierarchy (about six level-1 arrays) next to B and phi: a grid the device cannot hold at all is refused
+    ! before anything is allocated
+    rc = ndsmk_mem_info(fr, tot); if (rc /= 0) return
+    if (real(nb, wp) * real(merge(6, 0, .not. ctx%livep) + 4, wp) > real(tot, wp)) then
+      rc = ndsmk_note_error(NDSMK_ENODEV, "the grid needs more device memory than the device has"//c_null_char)
+      return
+    end if
+    if (.not. ctx%livep) then
+      bcn = 'N'
+      rc = mg_create(ctx%sp, 3, n3, ctx%qx, ctx%qy, ctx%qz, bcn, ctx%ngr); ctx%livep = .true.
+      if (rc /= 0) return
+    end if
+    if (on_device) then
+      dB = pB
+    else
+      if (.not. c_associated(ctx%dB)) then
+        rc = ndsmk_alloc(ctx%dB, 3_c_size_t * nb); if (rc /= 0) return
+      end if
+      dB = ctx%dB
+      rc = ndsmk_h2d(dB, pB, 3_c_size_t * nb); if (rc /= 0) return
+    end if
+    associate (s => ctx%sp)
+      s%ms = int(iopt(IOPT_MS)); s%ex_tol = ropt(ROPT_CTOL); s%use_max = (iopt(IOPT_DUMAX) == 1)
+      s%nmax_exact = int(iopt(IOPT_NMAXEX))
+      s%precision = 0
+      call say(me, "Divergence...")
+      rhs1 = mg_level_ptr(s, 1, MG_BUF_RHS, cnt)
+      rc = ndsmk_project_div_rhs(dB, rhs1, n3, dq); if (rc /= 0) return
+      call mg_mark_rhs_set(s)
+      u1 = mg_level_ptr(s, 1, MG_BUF_U, cnt)
+      rc = ndsmk_fill0(u1, nb); if (rc /= 0) return
+      rc = mg_reset_info(s); if (rc /= 0) return
+      call say(me, "Solve BVP 3D (all Neumann)...")
+      rc = mg_solve(s, ropt(ROPT_VTOL), int(iopt(IOPT_NCYCLES)), du, ncyc, ierr); if (rc /= 0) return
+      if (ierr /= 0) print *, "Warning: IOPT_NCYCLES exceeded. V-cycle iteration may not have converged"
+      if (mg_read_info(s, sweeps, bad) == 0) then
+        if (bad > 0) print *, "Warning: IOPT_NMAXEX exceeded. Coarse-mesh solution may not have converged"
+      end if
+      call say(me, "Subtract grad phi...")
+      u1 = mg_level_ptr(s, 1, MG_BUF_U, cnt)                  ! (the solver swaps its buffers)
+      rc = ndsmk_project_grad_sub(dB, u1, n3, dq); if (rc /= 0) return
+      rc = ndsmk_project_div_max(dB, n3, dq, out4); if (rc /= 0) return
+      if (c_associated(pphi)) then
+        if (on_device) then
+          rc = ndsmk_d2d(pphi, u1, nb)
+        else
+          rc = ndsmk_d2h(pphi, u1, nb)
+        end if
+        if (rc /= 0) return
+      end if
+    end associate
+    if (.not. on_device) then
+      rc = ndsmk_d2h(pB, dB, 3_c_size_t * nb); if (rc /= 0) return
+    end if
+    rc = ndsmk_sync(); if (rc /= 0) return
+    iopt(IOPT_IERR) = ierr
+    iopt(IOPT_NCYC_OUT) = ncyc
+    ropt(ROPT_DULAST) = du
   end function
 
   ! B.n of face f (1..6) from the host field (extract_bn, :699-743)

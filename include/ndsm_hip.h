@@ -220,6 +220,40 @@ int ndsm_hip_vecpot_helicity_device(void *h, int ioptc[16], double ropt[16], con
 int ndsm_hip_vecpot_project(void *h, int ioptc[16], double ropt[16], double *B, double *phi, double out[4]);
 int ndsm_hip_vecpot_project_device(void *h, int ioptc[16], double ropt[16], double *dB, double *dphi, double out[4]);
 
+/* ---- DeVore-gauge vector potentials and helicity on the same handle (DESIGN.md "DeVore-gauge vector potentials") --
+ * A second, independent gauge for the helicity of ndsm_hip_vecpot_helicity: A_z = 0 (DeVore 2000), A and A_p from
+ * cumulative integrals along z, no solve (Valori, Demoulin & Pariat 2012).  H_R and H_J are gauge invariant when
+ * B.n = B_p.n on the faces and div B = 0, so the two gauges agree to the discretisation error; a larger gap
+ * points at non-solenoidal input or a poorly converged solve.  With h_x, h_y, h_z the handle's spacings (as
+ * ndsm_hip_vecpot_solve forms them), trapezoid sums in fp64 in this operand order (k = 0 is z0, k = nz-1 the top):
+ *   base plane  b_x(i,0) = 0,  b_x(i,j) = b_x(i,j-1) - (B_z(i,j-1,0) + B_z(i,j,0)) * (0.25 h_y)
+ *               b_y(0,j) = 0,  b_y(i,j) = b_y(i-1,j) + (B_z(i-1,j,0) + B_z(i,j,0)) * (0.25 h_x);  A(:,:,0) = (b_x, b_y, 0)
+ *   A, up       A_x(k) = A_x(k-1) + (B_y(k-1) + B_y(k)) * (0.5 h_z),  A_y(k) = A_y(k-1) - (B_x(k-1) + B_x(k)) * (0.5 h_z)
+ *   A_p, down   A_p(nz-1) = A(nz-1) (the same bits), then for k = nz-2 .. 0
+ *               A_p,x(k) = A_p,x(k+1) - (B_p,y(k) + B_p,y(k+1)) * (0.5 h_z)
+ *               A_p,y(k) = A_p,y(k+1) + (B_p,x(k) + B_p,x(k+1)) * (0.5 h_z)
+ *   A_z = A_p,z = 0 exactly.
+ * So curl A = B where div B = 0 (a divergent B shows as a B_z error growing with height, about -int div B dz),
+ * and curl A_p = B_p where B_p,z = B_z on the top face.  n x A_p = n x A exactly on the top face; on the side
+ * faces as far as B_p.n = B.n there (the difference on an x-face is int_z^z1 (B_p,x - B_x) dz'); on the bottom
+ * face n x (A - A_p) is a 2-D gradient, which H_R and H_J do not see.
+ * B_p is any field whose B.n matches B's: the library's potential field or the caller's own.  out[8] has the
+ * layout of ndsm_hip_vecpot_helicity with B_rec = curl_h A (derivq's differences); out[7] = max |div_h A| is
+ * the divergence of the DeVore gauge, not an error.  Deterministic.  Device memory: five fields of 24 B/pt (the
+ * host entry stages B, B_p, A, A_p in the handle's scratch; B_rec is always the handle's); no multigrid
+ * hierarchy is created.  Returns 0, or >= 9001 errors (9001 without a GPU whatever the arguments, and for a grid
+ * whose five fields do not fit in device memory, refused before any allocation; 9002 a NULL handle or array);
+ * out[8] is cleared on every failure.
+ * Device chain for a DeVore-gauge helicity with the library's potential field: copy B, run
+ * ndsm_hip_vecpot_solve_device on the copy (a zero A; the copy becomes B_p), then ndsm_hip_vecpot_devore_device
+ * on B and that B_p - nothing crosses PCIe in between.  After ndsm_hip_vecpot_project_device the same chain gives
+ * the helicity of the projected field. */
+/* B, Bp in (nx,ny,nz,3), HOST arrays; A, Ap out. */
+int ndsm_hip_vecpot_devore(void *h, const double *B, const double *Bp, double *A, double *Ap, double out[8]);
+/* the same on DEVICE arrays of the library's GPU; A, Ap distinct from each other and from B, Bp */
+int ndsm_hip_vecpot_devore_device(void *h, const double *dB, const double *dBp, double *dA, double *dAp,
+                                  double out[8]);
+
 /* =====================================================================
  * PART 3 - additive exports, multi-GPU
  *

@@ -238,6 +238,8 @@ class VecPot:
         self.L.ndsm_hip_vecpot_project.argtypes = [ctypes.c_void_p, _ip, _dp, _dp, _dp, _dp]
         self.L.ndsm_hip_vecpot_project_device.argtypes = [ctypes.c_void_p, _ip, _dp, ctypes.c_void_p, ctypes.c_void_p,
                                                           _dp]
+        self.L.ndsm_hip_vecpot_devore.argtypes = [ctypes.c_void_p, _dp, _dp, _dp, _dp, _dp]
+        self.L.ndsm_hip_vecpot_devore_device.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 4 + [_dp]
         self.last_projection = None
         self.L.ndsm_hip_device_alloc.argtypes = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
         self.L.ndsm_hip_device_free.argtypes = [ctypes.c_void_p]
@@ -348,14 +350,21 @@ class VecPot:
         return ierr, A.reshape(shape), B.reshape(shape)
 
     def helicity(self, b, niterex_max=10000, ncycles_max=1024, ex_tol=1e-13, vc_tol=1e-10, ms=5, mean=False,
-                 mixed_precision=False, flxcrl=False, device=False, return_fields=False, project=False):
+                 mixed_precision=False, flxcrl=False, device=False, return_fields=False, project=False,
+                 gauge="coulomb"):
         """Relative magnetic helicity of b (3,nz,ny,nx) against the potential field of its B.n, in one call: the
         face phase once, the potential and the field 3-D solves, one deterministic reduction on the device.
         Returns a Helicity tuple (no 4 pi / mu0 factors; trapezoid weights): ierr, H_R (Finn-Antonsen),
         H_J = sum w (A - A_p).(B - B_p), E, E_p, E_free = E - E_p, recon_max / recon_rms of |B_rec - b|,
         divB_max, divA_max; with return_fields also A, A_p, B_p (else None).
         project=True: a copy of b is made solenoidal first (project(), same options) and the helicity is that of
-        the projected field; ierr is the larger of the two, the Projection is kept as self.last_projection."""
+        the projected field; ierr is the larger of the two, the Projection is kept as self.last_projection.
+        gauge: "coulomb" (the above), "devore" (A_z = 0: b staged on the device, the potential solve on a copy
+        gives B_p - the bits of solve() -, then devore_device; no field solves; B_rec = curl_h A, divA_max the
+        gauge's divergence; ierr 1 when a solve of the potential field missed vc_tol) or "both" (helicity_device,
+        then devore_device on the same device B and B_p: one potential solve; returns (coulomb, devore))."""
+        if gauge not in ("coulomb", "devore", "both"):
+            raise ValueError(f"gauge must be 'coulomb', 'devore' or 'both', not {gauge!r}")
         B = self._field_arg(b, "helicity")
         ierr_p = 0
         if project:
@@ -364,6 +373,8 @@ class VecPot:
             ierr_p = pr.ierr
             B = pr.B.reshape(-1).copy()
         ioptc, ropt = self._options(niterex_max, ncycles_max, ex_tol, vc_tol, ms, mean, mixed_precision, flxcrl)
+        if gauge != "coulomb":
+            return self._devore_chain(B, ioptc, ropt, gauge == "both", return_fields, ierr_p)
         shape = tuple(int(v) for v in self.nshape4[::-1])
         A, Ap, Bp = np.empty(B.size), np.empty(B.size), np.empty(B.size)
         out = np.zeros(8)
@@ -377,8 +388,72 @@ class VecPot:
             _check(ierr, "ndsm_hip_vecpot_helicity", self.L)
         self.last_ioptc, self.last_ropt = ioptc, ropt
         f = (A.reshape(shape), Ap.reshape(shape), Bp.reshape(shape)) if return_fields else (None, None, None)
-        return Helicity(int(max(ierr, ierr_p)), float(out[0]), float(out[1]), float(out[2]), float(out[3]),
-                        float(out[2] - out[3]), float(out[4]), float(out[5]), float(out[6]), float(out[7]), *f)
+        return _helicity_tuple(max(ierr, ierr_p), out, *f)
+
+    def _devore_chain(self, B, ioptc, ropt, both, return_fields, ierr_p):
+        """helicity(gauge="devore" / "both") on the device: B (flat) goes up once into two arrays; the potential
+        field B_p comes from ndsm_hip_vecpot_solve_device on the copy (both: ndsm_hip_vecpot_helicity_device, the
+        same B_p) and stays there for ndsm_hip_vecpot_devore_device.  Only the results come home."""
+        L = self.L
+        shape = tuple(int(v) for v in self.nshape4[::-1])
+        names = ("B", "Bp", "A", "Ap") + (("Ac", "Apc") if both else ())
+        d = {}
+        out_c, out_d = np.zeros(8), np.zeros(8)
+        try:
+            for k in names:
+                d[k] = ctypes.c_void_p()
+                _check(L.ndsm_hip_device_alloc(B.nbytes, ctypes.byref(d[k])), "device_alloc", L)
+            _check(L.ndsm_hip_memcpy_h2d(d["B"], B.ctypes.data, B.nbytes), "h2d", L)
+            if both:
+                ierr_s = L.ndsm_hip_vecpot_helicity_device(self.h, ioptc.ctypes.data_as(_ip), _d(ropt), d["B"],
+                                                           d["Ac"], d["Apc"], d["Bp"], _d(out_c))
+                if ierr_s >= 9000:
+                    _check(ierr_s, "ndsm_hip_vecpot_helicity_device", L)
+            else:
+                # the copy of B becomes B_p; A: a zero initial guess in (its A_p out is not used)
+                _check(L.ndsm_hip_memcpy_h2d(d["Bp"], B.ctypes.data, B.nbytes), "h2d", L)
+                zero = np.zeros(B.size)
+                _check(L.ndsm_hip_memcpy_h2d(d["A"], zero.ctypes.data, zero.nbytes), "h2d", L)
+                ierr_s = L.ndsm_hip_vecpot_solve_device(self.h, ioptc.ctypes.data_as(_ip), _d(ropt), d["A"], d["Bp"])
+                if ierr_s >= 9000:
+                    _check(ierr_s, "ndsm_hip_vecpot_solve_device", L)
+                ierr_s = 1 if ierr_s != 0 or ioptc[L.get_iopt_fail3d()] != 0 else 0
+            self.last_ioptc, self.last_ropt = ioptc, ropt
+            _check(L.ndsm_hip_vecpot_devore_device(self.h, d["B"], d["Bp"], d["A"], d["Ap"], _d(out_d)),
+                   "ndsm_hip_vecpot_devore_device", L)
+            host = {}
+            for k in (names[1:] if return_fields else ()):
+                host[k] = np.empty(B.size)
+                _check(L.ndsm_hip_memcpy_d2h(host[k].ctypes.data, d[k], B.nbytes), "d2h", L)
+        finally:
+            for p in d.values():
+                L.ndsm_hip_device_free(p)
+        ierr = int(max(ierr_s, ierr_p))
+        f = {k: v.reshape(shape) for k, v in host.items()}
+        dv = _helicity_tuple(ierr, out_d, f.get("A"), f.get("Ap"), f.get("Bp"))
+        if not both:
+            return dv
+        return _helicity_tuple(ierr, out_c, f.get("Ac"), f.get("Apc"), f.get("Bp")), dv
+
+    def devore(self, b, bp, device=False):
+        """Vector potentials of b and bp (3,nz,ny,nx) in the DeVore gauge A_z = 0, and the helicity of b against
+        bp with them: no solve.  bp is any field whose B.n matches b's (solve()'s potential field, or the
+        caller's own).  A: trapezoid integral of b up from the base plane (b_x, b_y of B_z(z0)); A_p: of bp down
+        from A's top plane, so n x A_p = n x A on the top face exactly.  Returns a Helicity tuple with A, A_p
+        (always) and B_p = bp; B_rec = curl_h A, divA_max = max |div_h A| is the gauge's divergence, ierr 0.
+        device=True: the arrays are staged in device memory and the device-resident entry point runs."""
+        shape = tuple(int(v) for v in self.nshape4[::-1])
+        B = self._field_arg(b, "devore")
+        Bp = self._field_arg(bp, "devore")
+        A, Ap = np.empty(B.size), np.empty(B.size)
+        out = np.zeros(8)
+        if not device:
+            ierr = self.L.ndsm_hip_vecpot_devore(self.h, _d(B), _d(Bp), _d(A), _d(Ap), _d(out))
+        else:
+            ierr = self._on_device([B, Bp, A, Ap], lambda dB, dBp, dA, dAp: self.L.ndsm_hip_vecpot_devore_device(
+                self.h, dB, dBp, dA, dAp, _d(out)))
+        _check(ierr, "ndsm_hip_vecpot_devore", self.L)
+        return _helicity_tuple(0, out, A.reshape(shape), Ap.reshape(shape), Bp.reshape(shape))
 
     def project(self, b, niterex_max=10000, ncycles_max=1024, ex_tol=1e-13, vc_tol=1e-10, ms=5, mean=False,
                 mixed_precision=False, flxcrl=False, device=False, return_phi=False):
@@ -420,6 +495,12 @@ Helicity = collections.namedtuple("Helicity", ["ierr", "H_R", "H_J", "E", "E_p",
                                                "divB_max", "divA_max", "A", "A_p", "B_p"])
 
 
+def _helicity_tuple(ierr, out, A, Ap, Bp):
+    """a Helicity from the out[8] of the helicity / devore entries"""
+    return Helicity(int(ierr), float(out[0]), float(out[1]), float(out[2]), float(out[3]), float(out[2] - out[3]),
+                    float(out[4]), float(out[5]), float(out[6]), float(out[7]), A, Ap, Bp)
+
+
 def _grid_handle(x, y, z, b, ngrids, lib):
     shape = np.shape(b)
     want = (3, len(z), len(y), len(x))
@@ -443,15 +524,29 @@ def vector_potential_field(x, y, z, b, a_init=None, niterex_max=10000, ncycles_m
 
 
 def relative_helicity(x, y, z, b, niterex_max=10000, ncycles_max=1024, ex_tol=1e-13, vc_tol=1e-10, ms=5, mean=False,
-                      mixed_precision=False, flxcrl=False, ngrids=0, return_fields=False, project=False, lib=None):
+                      mixed_precision=False, flxcrl=False, ngrids=0, return_fields=False, project=False, lib=None,
+                      gauge="coulomb"):
     """Relative helicity, energies and reconstruction diagnostics of b (3,nz,ny,nx): one-shot form of
-    VecPot.helicity (returns its Helicity tuple; project=True: of the solenoidal projection of b).  Raises
-    NdsmHipError on device / runtime failures (>= 9001)."""
+    VecPot.helicity (returns its Helicity tuple; project=True: of the solenoidal projection of b; gauge="devore":
+    A_z = 0, "both": the (coulomb, devore) pair).  Raises NdsmHipError on device / runtime failures (>= 9001)."""
+    if gauge not in ("coulomb", "devore", "both"):
+        raise ValueError(f"gauge must be 'coulomb', 'devore' or 'both', not {gauge!r}")
     V = _grid_handle(x, y, z, b, ngrids, lib)
     try:
         return V.helicity(b, niterex_max=niterex_max, ncycles_max=ncycles_max, ex_tol=ex_tol, vc_tol=vc_tol, ms=ms,
                           mean=mean, mixed_precision=mixed_precision, flxcrl=flxcrl, return_fields=return_fields,
-                          project=project)
+                          project=project, gauge=gauge)
+    finally:
+        V.close()
+
+
+def devore_potentials(x, y, z, b, bp, lib=None):
+    """DeVore-gauge (A_z = 0) vector potentials of b and bp (3,nz,ny,nx) and the helicity with them: one-shot form
+    of VecPot.devore (returns its Helicity tuple, A and A_p filled).  No solve: bp is the caller's field with b's
+    B.n (e.g. vector_potential's B).  Raises NdsmHipError on device / runtime failures (>= 9001)."""
+    V = _grid_handle(x, y, z, b, 0, lib)
+    try:
+        return V.devore(b, bp)
     finally:
         V.close()
 

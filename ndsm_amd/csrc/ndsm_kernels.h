@@ -197,6 +197,11 @@ int ndsmk_project_div_rhs(const double *B, double *rhs, const int32_t *n3, const
 int ndsmk_project_grad_sub(double *B, const double *phi, const int32_t *n3, const double *h_dq3);
 int ndsmk_project_div_max(const double *B, const int32_t *n3, const double *h_dq3, double *h_out4);
 
+/* DeVore-gauge vector potentials (devore.hip), all DEVICE arrays (nx,ny,nz,3): A of B integrated up from the base
+ * plane b of B_z(z0), A_p of Bp integrated down from A's top plane (A_p(nz-1) = A(nz-1) bitwise), A_z = A_p,z = 0.
+ * Trapezoid cumulative sums, h/4 and h/2 formed here from h_dq3.  A, Ap distinct.  Asynchronous. */
+int ndsmk_devore(const double *B, const double *Bp, double *A, double *Ap, const int32_t *n3, const double *h_dq3);
+
 /* the face phase on the device (faces.hip): packed face buffers, six faces back to back */
 int ndsmk_face_offsets(const int32_t *n3, int64_t *off6, int64_t *total);
 int ndsmk_face_extract(const double *B, const int32_t *n3, double *faces);

@@ -860,6 +860,54 @@ contains
     end if
   end function
 
+  ! ---- DeVore-gauge vector potentials on the same handle ----------------
+  ! B, Bp in (nx,ny,nz,3): the field and any field whose B.n matches it (the library's potential field or the
+  ! caller's own); A, Ap out: A_z = 0, A of B up from the base plane, A_p of Bp down from A's top plane.  out8: the
+  ! layout of ndsm_hip_vecpot_helicity with B_rec = curl_h A (out8(8) = max |div_h A|, the gauge's divergence).
+  ! No solve runs.  Return value: 0, or >= 9001 errors (9002 a NULL array); out8 is cleared on every failure.
+
+  ! HOST arrays
+  function ndsm_hip_vecpot_devore(handle, B, Bp, A, Ap, out8) bind(c, name="ndsm_hip_vecpot_devore") result(ierr)
+    type(c_ptr), value :: handle, B, Bp, A, Ap
+    real(c_double), intent(out) :: out8(8)
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_devore(handle, B, Bp, A, Ap, out8, .false., "ndsm_hip_vecpot_devore")
+  end function
+
+  ! the same on DEVICE arrays of the library's GPU
+  function ndsm_hip_vecpot_devore_device(handle, dB, dBp, dA, dAp, out8) bind(c, name="ndsm_hip_vecpot_devore_device") &
+      result(ierr)
+    type(c_ptr), value :: handle, dB, dBp, dA, dAp
+    real(c_double), intent(out) :: out8(8)
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_devore(handle, dB, dBp, dA, dAp, out8, .true., "ndsm_hip_vecpot_devore_device")
+  end function
+
+  function vecpot_handle_devore(handle, B, Bp, A, Ap, out8, on_device, who) result(ierr)
+    type(c_ptr), intent(in) :: handle, B, Bp, A, Ap
+    real(c_double), intent(out) :: out8(8)
+    logical, intent(in) :: on_device
+    character(len=*), intent(in) :: who
+    integer(c_int) :: ierr
+    type(vecpot_ctx), pointer :: ctx
+    integer(c_int) :: rc
+    out8 = 0
+    ierr = ndsmk_init(-1_c_int)                        ! without a device: 9001, whatever the arguments
+    if (ierr /= 0) return
+    ierr = NDSMK_EARG
+    if (.not. (c_associated(handle) .and. c_associated(B) .and. c_associated(Bp) .and. c_associated(A) .and. &
+               c_associated(Ap))) return
+    call c_f_pointer(handle, ctx)
+    if (.not. ctx%live) return
+    rc = vecpot_devore(ctx, B, Bp, A, Ap, on_device, out8)
+    if (rc /= 0) then
+      call report(who, rc)
+      if (rc < NDSMK_ENODEV) rc = NDSMK_ENODEV
+      out8 = 0
+    end if
+    ierr = rc
+  end function
+
   ! ---- z-slab decomposition over GPUs (SURVEY 8e) -----------------------
 
   ! rank 0 creates the 128-byte RCCL id; the launcher hands it to every rank

@@ -549,6 +549,15 @@ module ndsmh_iface
       integer(c_int) :: rc
     end function
 
+    ! ---- DeVore-gauge vector potentials (devore.hip) ----
+    function ndsmk_devore(B, Bp, A, Ap, n3, dq3) bind(c, name="ndsmk_devore") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_double
+      type(c_ptr), value :: B, Bp, A, Ap
+      integer(c_int32_t), intent(in) :: n3(3)
+      real(c_double), intent(in) :: dq3(3)
+      integer(c_int) :: rc
+    end function
+
     ! ---- the face phase on the device (faces.hip) ----
     function ndsmk_face_offsets(n3, off6, total) bind(c, name="ndsmk_face_offsets") result(rc)
       import :: c_int, c_int32_t, c_int64_t

@@ -32,7 +32,7 @@ module ndsmh_vecpot
 
   public :: vecpot_solve, poisson_solve
   public :: vecpot_ctx, vecpot_ctx_create, vecpot_ctx_destroy, vecpot_ctx_matches, vecpot_run, vecpot_cache_drop
-  public :: vecpot_project
+  public :: vecpot_project, vecpot_devore
   public :: VP_POTENTIAL, VP_FIELD, VP_HELICITY
   ! pieces the distributed driver (ndsmh_wvecpot) shares with vecpot_solve
   public :: face_data, face_axis, face_upper, face_t1, face_t2, face_order, face_copy, vecpot_faces, say
@@ -972,6 +972,74 @@ contains
     iopt(IOPT_IERR) = ierr
     iopt(IOPT_NCYC_OUT) = ncyc
     ropt(ROPT_DULAST) = du
+  end function
+
+  ! ------------------------------------------------------------------
+  ! DeVore-gauge vector potentials and relative helicity on a prepared context (DESIGN.md "DeVore-gauge vector
+  ! potentials"): A_z = 0, A of B integrated up from the base plane of B_z(z0), A_p of B_p integrated down from
+  ! A's top plane (devore.hip), then B_rec = curl_h A into the context's scratch and the reduction of
+  ! field.hip -> out8 (out8(8) = max |div_h A|: the gauge's divergence, not an error).  pB, pBp in, pA, pAp out,
+  ! (nx,ny,nz,3) on the HOST (B and B_p go up, A and A_p come home) or (on_device) in HBM.  dq as in vecpot_run.
+  ! No solve, no hierarchy: B_p is the caller's (any field whose B.n matches B's).
+  ! ------------------------------------------------------------------
+  function vecpot_devore(ctx, pB, pBp, pA, pAp, on_device, out8) result(rc)
+    type(vecpot_ctx), intent(inout), target :: ctx
+    type(c_ptr), intent(in) :: pB, pBp, pA, pAp
+    logical, intent(in) :: on_device
+    real(wp), intent(out) :: out8(8)
+    integer(c_int) :: rc
+    character(len=*), parameter :: me = "devore_potentials"
+    real(wp) :: dq(3)
+    integer(c_int32_t) :: n3(3)
+    integer(c_size_t) :: nb, fr, tot
+    integer :: i
+    type(c_ptr) :: dB, dBp, dA, dAp
+
+    out8 = 0
+    n3 = ctx%n3
+    if (any(n3 < 3)) then
+      rc = ndsmk_note_error(NDSMK_EARG, "the DeVore gauge needs at least 3 points per axis"//c_null_char)
+      return
+    end if
+    dq = [ctx%qx(2) - ctx%qx(1), ctx%qy(2) - ctx%qy(1), ctx%qz(2) - ctx%qz(1)]      ! as vecpot_run
+    nb = int(product(int(n3, ik)), c_size_t) * 8_c_size_t
+    ! five fields of 24 B/pt (B, B_p, A, A_p, B_rec): a grid the device cannot hold is refused before anything is
+    ! allocated
+    rc = ndsmk_mem_info(fr, tot); if (rc /= 0) return
+    if (real(nb, wp) * 15.0_wp > real(tot, wp)) then
+      rc = ndsmk_note_error(NDSMK_ENODEV, "the grid needs more device memory than the device has"//c_null_char)
+      return
+    end if
+    if (.not. c_associated(ctx%dB)) then                           ! B_rec
+      rc = ndsmk_alloc(ctx%dB, 3_c_size_t * nb); if (rc /= 0) return
+    end if
+    if (on_device) then
+      dB = pB; dBp = pBp; dA = pA; dAp = pAp
+    else
+      ! the helicity entries' host staging: dF(1) B, dF(2) A_p, dF(3) B_p, dA A
+      if (.not. c_associated(ctx%dA)) then
+        rc = ndsmk_alloc(ctx%dA, 3_c_size_t * nb); if (rc /= 0) return
+      end if
+      do i = 1, 3
+        if (.not. c_associated(ctx%dF(i))) then
+          rc = ndsmk_alloc(ctx%dF(i), 3_c_size_t * nb); if (rc /= 0) return
+        end if
+      end do
+      dB = ctx%dF(1); dAp = ctx%dF(2); dBp = ctx%dF(3); dA = ctx%dA
+      rc = ndsmk_h2d(dB, pB, 3_c_size_t * nb); if (rc /= 0) return
+      rc = ndsmk_h2d(dBp, pBp, 3_c_size_t * nb); if (rc /= 0) return
+    end if
+    call say(me, "DeVore gauge: base plane, columns up (A) and down (A_p)...")
+    rc = ndsmk_devore(dB, dBp, dA, dAp, n3, dq); if (rc /= 0) return
+    call say(me, "B_rec = curl(A)...")
+    rc = ndsmk_curl(dA, ctx%dB, n3, dq); if (rc /= 0) return
+    call say(me, "Relative helicity...")
+    rc = ndsmk_helicity_reduce(dA, dAp, dB, dBp, ctx%dB, n3, dq, out8); if (rc /= 0) return
+    if (.not. on_device) then
+      rc = ndsmk_d2h(pA, dA, 3_c_size_t * nb); if (rc /= 0) return
+      rc = ndsmk_d2h(pAp, dAp, 3_c_size_t * nb); if (rc /= 0) return
+    end if
+    rc = ndsmk_sync()
   end function
 
   ! B.n of face f (1..6) from the host field (extract_bn, :699-743)

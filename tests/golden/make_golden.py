@@ -29,8 +29,9 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import numpy as np  # noqa: E402
 
-from golden_inputs import (BCS3, BCS_RANDOM, analytic_case, digest, manufactured_poisson, quirk_case,  # noqa: E402
-                           rand_field, random_reference_cases, KERNEL_SHAPES_3D, KERNEL_SHAPES_2D)
+from golden_inputs import (BCS3, BCS_ANISO, BCS_RANDOM, analytic_case, aniso_mesh, aniso_pipeline_cases,  # noqa: E402
+                           digest, manufactured_poisson, quirk_case, rand_field, random_reference_cases,
+                           ANISO_SHAPE_2D, ANISO_SHAPES_3D, KERNEL_SHAPES_3D, KERNEL_SHAPES_2D)
 from oracle import Oracle, have_ref, uniform_mesh  # noqa: E402
 
 
@@ -134,7 +135,7 @@ def main():
                         "Ea_avg": float(eA.mean()), "Eb_max": float(eB.max()), "Eb_avg": float(eB.mean())}
         if n == 22:
             np.savez(os.path.join(HERE, "pipeline_22.npz"), A=A, B=B, ioptc=ioptc)
-    # anisotropic shape, equal spacing (quirk Q4 needs dx=dy=dz)
+    # anisotropic shape, equal spacing (unequal spacings, where quirk Q4 is live: aniso() below)
     ns = [33, 22, 27]
     x, y, z, A1, b1 = analytic_case(ns)
     ierr, A, B, ioptc, ropt = R.vector_potential(x, y, z, b1)
@@ -172,6 +173,81 @@ def random_and_quirks(R):
     with open(os.path.join(HERE, "reference_quirks.json"), "w") as fh:
         json.dump(quirks, fh, indent=1)
     print("wrote reference_random*, reference_quirks.json")
+    aniso(R)
+
+
+def aniso(R):
+    """test_oracle.py's anisotropic checks (golden_inputs.aniso_mesh: a spacing of its own on every axis, no origin
+    at 0): sha256 of the bit-identical 3-D outputs and solve histories in reference_aniso.json, the 2-D outputs that
+    carry the all-Neumann mean in reference_aniso_2d.npz, and the pipeline - where quirk Q4 is live - in
+    pipeline_aniso_*.npz"""
+    want = {}
+    for ns in ANISO_SHAPES_3D:
+        tag = "x".join(str(n) for n in ns)
+        mesh = aniso_mesh(ns)
+        shp = tuple(ns[::-1])
+        u, rhs = rand_field(shp, 2112), rand_field(shp, 2113)
+        out = {}
+        shapes, meshes = R.hierarchy(ns, mesh)
+        out["level_shapes"] = shapes.tolist()
+        for l, lv in enumerate(meshes):
+            for d, m in enumerate(lv):
+                out[f"mesh_l{l+1}_d{d+1}"] = digest(m)
+        for bcs in BCS_ANISO:
+            out[f"relax_{bcs}"] = digest(R.relax3d(u, rhs, mesh, bcs))
+            out[f"residual_{bcs}"] = digest(R.residual3d(u, rhs, mesh, bcs))
+            out[f"vcycle_{bcs}"] = digest(R.vcycle(u, rhs, mesh, bcs))
+        for lvl in range(1, len(shapes)):
+            f = rand_field(tuple(int(v) for v in shapes[lvl - 1][::-1]), 3000 + lvl)
+            c = rand_field(tuple(int(v) for v in shapes[lvl][::-1]), 4000 + lvl)
+            out[f"restrict_l{lvl}"] = digest(R.restrict(f, ns, mesh, lvl))
+            out[f"interp_l{lvl}"] = digest(R.interp(c, ns, mesh, lvl))
+        want[tag] = out
+    # solve histories (the loop of main(), one V-cycle at a time) on the first shape
+    ns = ANISO_SHAPES_3D[0]
+    tag = "x".join(str(n) for n in ns)
+    mesh = aniso_mesh(ns)
+    for bcs in BCS3:
+        us, rhs = manufactured_poisson(mesh, bcs)
+        prev, dus = np.zeros_like(us), []
+        for it in range(64):
+            cur = R.vcycle(prev, rhs, mesh, bcs)
+            d = float(np.abs(cur - prev).max())
+            dus.append(d)
+            prev = cur
+            if d < 1e-10:
+                break
+        ierr, uref, du_last = R.solve_bvp(np.zeros_like(us), rhs, mesh, bcs)
+        assert ierr == 0 and np.array_equal(uref, prev) and du_last == dus[-1]
+        want[f"solve_{tag}_{bcs}"] = {"du": dus, "ncycles": len(dus), "u": digest(uref)}
+    with open(os.path.join(HERE, "reference_aniso.json"), "w") as fh:
+        json.dump(want, fh, indent=1, sort_keys=True)
+    # 2-D: the generic N-D path, as in main()
+    ns = ANISO_SHAPE_2D
+    mesh = aniso_mesh(ns)
+    shp = tuple(ns[::-1])
+    u, rhs = rand_field(shp, 2112), rand_field(shp, 2113)
+    rhs0 = rhs - rhs.mean()
+    out = {}
+    shapes, _ = R.hierarchy(ns, mesh)
+    out["level_shapes"] = shapes
+    for bcs in ("NNNN", "DNND"):
+        out[f"relax_{bcs}"] = R.relax_nd(u, rhs, mesh, bcs)
+        out[f"residual_{bcs}"] = R.residual_nd(u, rhs, mesh, bcs)
+    out["vcycle_NNNN"] = R.vcycle(u, rhs0, mesh, "NNNN")
+    ierr, us, du = R.solve_bvp(np.zeros(shp), rhs0, mesh, "NNNN")
+    out["solve_NNNN"] = us
+    out["solve_NNNN_meta"] = np.array([ierr, du])
+    for lvl in range(1, len(shapes)):
+        f = rand_field(tuple(int(v) for v in shapes[lvl - 1][::-1]), 3000 + lvl)
+        c = rand_field(tuple(int(v) for v in shapes[lvl][::-1]), 4000 + lvl)
+        out[f"restrict_l{lvl}"] = R.restrict(f, ns, mesh, lvl)
+        out[f"interp_l{lvl}"] = R.interp(c, ns, mesh, lvl)
+    np.savez_compressed(os.path.join(HERE, "reference_aniso_2d.npz"), **out)
+    for name, x, y, z, b in aniso_pipeline_cases():
+        ierr, A, B, ioptc, ropt = R.vector_potential(x, y, z, b)
+        np.savez_compressed(os.path.join(HERE, f"pipeline_aniso_{name}.npz"), A=A, B=B, ioptc=ioptc)
+    print("wrote reference_aniso*, pipeline_aniso_*")
 
 
 if __name__ == "__main__":

@@ -25,6 +25,49 @@ def uniform_mesh(nshape):
     return [x] + [np.arange(int(n)) * dx for n in nshape[1:]]
 
 
+# spacing of each axis relative to h_x = 1/(nx-1), and the first mesh point of each axis: neither ratio is 1 or a
+# power of two, and all stay close enough to 1 for point Gauss-Seidel multigrid to converge within the defaults
+ANISO_RATIOS = (1.0, 0.73, 1.37)
+ANISO_ORIGINS = (0.25, -0.4, 1.1)
+ANISO_SHAPES_3D = ([33, 22, 27], [24, 30, 20])
+ANISO_SHAPE_2D = [27, 36]
+ANISO_PIPELINE_SHAPE = [20, 17, 23]
+BCS_ANISO = BCS3 + ("DDDDDD", "NDNDND")
+
+
+def aniso_mesh(nshape):
+    """a distinct spacing on every axis and no origin at 0: q_d = o_d + arange(n_d) * r_d h_x with h_x = 1/(nx-1)
+    (ANISO_RATIOS, ANISO_ORIGINS); a 2-D shape takes the first two axes"""
+    h = 1.0 / (int(nshape[0]) - 1)
+    return [o + np.arange(int(n)) * (r * h) for n, r, o in zip(nshape, ANISO_RATIOS, ANISO_ORIGINS)]
+
+
+def analytic_field(mesh):
+    """analytic_case's current-free field and its potential at the points of `mesh` ([x, y, z], any spacings and
+    origins).  Returns A, b shaped (3, nz, ny, nx)."""
+    Z, Y, X = np.meshgrid(mesh[2], mesh[1], mesh[0], indexing="ij")
+    wn = np.pi
+    l = np.sqrt(2 * wn ** 2)
+    b = np.zeros((3,) + X.shape)
+    A = np.zeros((3,) + X.shape)
+    b[0] = +l * np.sin(wn * X) * np.cos(wn * Y) * np.exp(-l * Z)
+    b[1] = +l * np.cos(wn * X) * np.sin(wn * Y) * np.exp(-l * Z)
+    b[2] = +2 * wn * np.cos(wn * X) * np.cos(wn * Y) * np.exp(-l * Z)
+    A[0] = -np.cos(wn * X) * np.sin(wn * Y) * np.exp(-l * Z)
+    A[1] = +np.sin(wn * X) * np.cos(wn * Y) * np.exp(-l * Z)
+    return A, b
+
+
+def aniso_pipeline_cases():
+    """(name, x, y, z, b) of the anisotropic pipeline fixtures: the analytic field on aniso_mesh, and the same field
+    plus seeded noise that unbalances the face fluxes"""
+    x, y, z = aniso_mesh(ANISO_PIPELINE_SHAPE)
+    _A, b = analytic_field([x, y, z])
+    yield "analytic", x, y, z, b
+    noise = np.random.default_rng(2114).uniform(-1.0, 1.0, b.shape)
+    yield "unbalanced", x, y, z, b + 0.2 * np.abs(b).max() * noise
+
+
 def manufactured_poisson(mesh, bcs):
     """u* = prod_d (cos|sin)(pi q_d / L_d): cos on the Neumann axis, sin on
     Dirichlet axes; rhs = laplace(u*).  Returned in numpy order (nz, ny, nx)."""
@@ -77,6 +120,12 @@ def random_reference_cases():
         shp = tuple(ns[::-1])
         u, rhs = rng.uniform(-1, 1, shp), rng.uniform(-1, 1, shp)
         yield ns, uniform_mesh(ns), u, rhs
+
+
+def aniso_case(nshape):
+    """(mesh, u, rhs) of the anisotropic per-operator fixtures: aniso_mesh and the seeds of the uniform-mesh ones"""
+    shp = tuple(int(n) for n in nshape[::-1])
+    return aniso_mesh(nshape), rand_field(shp, 2112), rand_field(shp, 2113)
 
 
 def quirk_case(n=24):

@@ -12,7 +12,7 @@ import ctypes
 import numpy as np
 import pytest
 
-from golden_inputs import uniform_mesh
+from golden_inputs import aniso_mesh, uniform_mesh
 
 pytestmark = pytest.mark.gpu
 
@@ -165,10 +165,11 @@ def test_potentials_bitwise_with_unequal_spacings(hip):
 
 
 @pytest.mark.parametrize("field", sorted(FIELDS))
-@pytest.mark.parametrize("ns", ([33, 33, 33], [33, 22, 27]), ids=IDS)
-def test_reduction_against_numpy(hip, field, ns):
+@pytest.mark.parametrize("ns,meshf", [pytest.param(ns, uniform_mesh, id=IDS(ns)) for ns in ([33, 33, 33], [33, 22, 27])] +
+                         [pytest.param(ns, aniso_mesh, id="aniso-" + IDS(ns)) for ns in ([33, 22, 27], [300, 40, 60])])
+def test_reduction_against_numpy(hip, field, ns, meshf):
     import ndsm_amd
-    mesh = uniform_mesh(ns)
+    mesh = meshf(ns)
     b = FIELDS[field](mesh)
     V = ndsm_amd.VecPot(*mesh)
     h = V.helicity(b, vc_tol=VC_TOL, return_fields=True, gauge="devore")

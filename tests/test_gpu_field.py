@@ -54,7 +54,7 @@ def weights(mesh):
 
 def grad(f, mesh, axis):
     """d/dq with derivq's stencil (centred inside, 3-point one-sided on the end planes); numpy axis order"""
-    return np.gradient(f, mesh[2 - axis][1] - mesh[2 - axis][0], axis=2 - axis, edge_order=2)
+    return np.gradient(f, mesh[axis][1] - mesh[axis][0], axis=2 - axis, edge_order=2)
 
 
 def curl(v, mesh):

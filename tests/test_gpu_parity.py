@@ -22,7 +22,7 @@ import os
 import numpy as np
 import pytest
 
-from golden_inputs import (BCS3, KERNEL_SHAPES_2D, KERNEL_SHAPES_3D, analytic_case, manufactured_poisson,
+from golden_inputs import (BCS3, KERNEL_SHAPES_2D, KERNEL_SHAPES_3D, analytic_case, aniso_mesh, manufactured_poisson,
                            rand_field, uniform_mesh)
 
 pytestmark = pytest.mark.gpu
@@ -42,6 +42,13 @@ def _tag(ns):
     return "x".join(str(n) for n in ns)
 
 
+def _meshes(uniform, aniso=(), ids=_tag):
+    """(ns, mesh function) cases: the shapes on uniform_mesh under the ids they always had, and the `aniso` shapes on
+    golden_inputs.aniso_mesh (a spacing of its own on every axis, no origin at 0) under 'aniso-' ids"""
+    return ([pytest.param(ns, uniform_mesh, id=ids(ns)) for ns in uniform] +
+            [pytest.param(ns, aniso_mesh, id="aniso-" + ids(ns)) for ns in aniso])
+
+
 def _pad_r(solver, arr):
     """place a level-l array at the start of the level-1 sized residual scratch"""
     full = np.zeros(solver._npshape(1))
@@ -50,11 +57,12 @@ def _pad_r(solver, arr):
 
 
 SHAPES_3D = KERNEL_SHAPES_3D + ([17, 23, 19], [40, 24, 32], [64, 64, 64])
+ANISO_3D = ([33, 22, 27], [17, 23, 19], [40, 24, 32])       # odd and even nx
 
 
-@pytest.mark.parametrize("ns", SHAPES_3D, ids=_tag)
-def test_kernels3d_bitwise(hip, port, ns):
-    mesh = uniform_mesh(ns)
+@pytest.mark.parametrize("ns,meshf", _meshes(SHAPES_3D, ANISO_3D))
+def test_kernels3d_bitwise(hip, port, ns, meshf):
+    mesh = meshf(ns)
     shp = tuple(ns[::-1])
     u, rhs = rand_field(shp, 2112), rand_field(shp, 2113)
     for bcs in BCS3 + ("DDDDDD", "NDNDND"):
@@ -85,9 +93,9 @@ def test_kernels3d_bitwise(hip, port, ns):
         S.close()
 
 
-@pytest.mark.parametrize("ns", SHAPES_3D, ids=_tag)
-def test_transfer3d_bitwise(hip, port, ns):
-    mesh = uniform_mesh(ns)
+@pytest.mark.parametrize("ns,meshf", _meshes(SHAPES_3D, ANISO_3D))
+def test_transfer3d_bitwise(hip, port, ns, meshf):
+    mesh = meshf(ns)
     S = hip.MGSolver(ns, mesh, "NDDNDD")
     shapes, _ = port.hierarchy(ns, mesh)
     for lvl in range(1, len(shapes)):
@@ -108,12 +116,13 @@ def test_transfer3d_bitwise(hip, port, ns):
     S.close()
 
 
-@pytest.mark.parametrize("ns", ([128, 128, 128], [200, 100, 120], [256, 192, 160], [129, 128, 130], [257, 161, 158]), ids=_tag)
-def test_large_level_kernels_bitwise(hip, port, ns):
+@pytest.mark.parametrize("ns,meshf", _meshes(([128, 128, 128], [200, 100, 120], [256, 192, 160], [129, 128, 130], [257, 161, 158]),
+                                             ([200, 100, 120], [257, 161, 158])))
+def test_large_level_kernels_bitwise(hip, port, ns, meshf):
     """the kernels that only serve large levels - temporally blocked fused smoother (odd nx: its
     ghost-column variant), LDS-streamed restriction, LDS-tiled prolongation, fused residual+restriction -
     against the oracle, level 1 -> 2"""
-    mesh = uniform_mesh(ns)
+    mesh = meshf(ns)
     shp = tuple(ns[::-1])
     u, rhs = rand_field(shp, 2112), rand_field(shp, 2113)
     bcs = "DNDDND"
@@ -154,13 +163,13 @@ def test_large_level_kernels_bitwise(hip, port, ns):
     S.close()
 
 
-@pytest.mark.parametrize("ns", ([22, 22, 22], [40, 24, 32], [33, 22, 27], [64, 64, 64], [200, 100, 70], [199, 101, 70],
-                                [256, 192, 160]), ids=_tag)
-def test_sweep_plus_residual_launch_bitwise(hip, ns):
+@pytest.mark.parametrize("ns,meshf", _meshes(([22, 22, 22], [40, 24, 32], [33, 22, 27], [64, 64, 64], [200, 100, 70],
+                                              [199, 101, 70], [256, 192, 160]), ([200, 100, 70], [199, 101, 70])))
+def test_sweep_plus_residual_launch_bitwise(hip, ns, meshf):
     """the pipeline stage that evaluates r = rhs - L u behind the last sweep (op 9, forced) returns the
     bits of sweeps-then-residual.hip (which test_kernels3d_bitwise pins to the oracle): every BC set,
     odd/even sweep counts, general and declared-zero rhs"""
-    mesh = uniform_mesh(ns)
+    mesh = meshf(ns)
     shp = tuple(ns[::-1])
     u, rhs = rand_field(shp, 2112), rand_field(shp, 2113)
     for bcs in ("NDDNDD", "DNDDND", "DDNDDN", "NNNNND", "DDDDDD"):
@@ -224,9 +233,9 @@ def test_solve3d_history_golden(hip, golden_dir, ns, bcs):
         assert np.array_equal(u[:, :, ns[0] // 2], p["ix"])
 
 
-@pytest.mark.parametrize("ns", KERNEL_SHAPES_2D + ([64, 48],), ids=_tag)
-def test_kernels2d(hip, port, ns):
-    mesh = uniform_mesh(ns)
+@pytest.mark.parametrize("ns,meshf", _meshes(KERNEL_SHAPES_2D + ([64, 48],), ([27, 36],)))
+def test_kernels2d(hip, port, ns, meshf):
+    mesh = meshf(ns)
     shp = tuple(ns[::-1])
     u, rhs = rand_field(shp, 2112), rand_field(shp, 2113)
     rhs0 = rhs - rhs.mean()
@@ -488,13 +497,14 @@ def test_roundtrip_properties_large(hip):
     assert all(hist[i + 1] < 0.5 * hist[i] for i in range(len(hist) - 1))
 
 
-@pytest.mark.parametrize("ns,nranks", (([64, 64, 64], 2), ([64, 48, 96], 3), ([128, 128, 128], 4), ([128, 64, 160], 8)),
-                         ids=lambda v: str(v))
-def test_slab_world_bitwise(hip, ns, nranks):
+@pytest.mark.parametrize("ns,nranks,meshf", [pytest.param(ns, nr, uniform_mesh, id=f"{ns}-{nr}") for ns, nr in
+                                             (([64, 64, 64], 2), ([64, 48, 96], 3), ([128, 128, 128], 4), ([128, 64, 160], 8))] +
+                         [pytest.param([64, 48, 96], 3, aniso_mesh, id="aniso-[64, 48, 96]-3")])
+def test_slab_world_bitwise(hip, ns, nranks, meshf):
     """z-slab decomposition (loop-back transport: all slabs on this GPU, neighbours reached by
     device copies; production swaps those copies for RCCL send/recv): sweeps, a V-cycle and a whole
     solve must return the SAME BITS as the single-domain solver."""
-    mesh = uniform_mesh(ns)
+    mesh = meshf(ns)
     shp = tuple(ns[::-1])
     u, rhs = rand_field(shp, 2112), rand_field(shp, 2113)
     for bcs in BCS3:
@@ -558,13 +568,13 @@ def test_reference_quirks(hip, port):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("ns", ([64, 64, 64], [128, 96, 80], [256, 256, 256]), ids=_tag)
-def test_mixed_precision_solve(hip, ns):
+@pytest.mark.parametrize("ns,meshf", _meshes(([64, 64, 64], [128, 96, 80], [256, 256, 256]), ([128, 96, 80],)))
+def test_mixed_precision_solve(hip, ns, meshf):
     """BASELINE config[4] mode: fp64 residual + fp32 correction V-cycle on level 1 (csrc/mixed.hip).
     In exact arithmetic it is the reference's iteration, so: the same number of V-cycles to the same
     vc_tol, du history equal to fp32 rounding, and a final solution within a few vc_tol (the
     stopping rule's own resolution; absolute, as vc_tol is) of the all-fp64 solve."""
-    mesh = uniform_mesh(ns)
+    mesh = meshf(ns)
     for bcs in ("NDDNDD", "DNDDND", "DDDDDD"):
         us, rhs = manufactured_poisson(mesh, bcs) if bcs == "NDDNDD" else (None, rand_field(tuple(ns[::-1]), 77) * 10.0)
         u0 = np.zeros(tuple(ns[::-1]))
@@ -588,13 +598,16 @@ def test_mixed_precision_solve(hip, ns):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("ns,ms", (([256, 192, 160], 5), ([192, 192, 192], 4), ([256, 256, 256], 1), ([257, 161, 158], 5), ([193, 190, 131], 2)), ids=str)
-def test_fused_metric_bitwise(hip, ns, ms):
+@pytest.mark.parametrize("ns,ms,meshf", [pytest.param(ns, ms, uniform_mesh, id=f"{ns}-{ms}") for ns, ms in
+                                        (([256, 192, 160], 5), ([192, 192, 192], 4), ([256, 256, 256], 1), ([257, 161, 158], 5),
+                                         ([193, 190, 131], 2))] +
+                         [pytest.param([257, 161, 158], 5, aniso_mesh, id="aniso-[257, 161, 158]-5")])
+def test_fused_metric_bitwise(hip, ns, ms, meshf):
     """mg_solve on a large level 1 keeps the start-of-cycle iterate in place (three rotating buffers)
     and lets the launch of the cycle's last sweep evaluate update_u's max|u_new - u_old|
     (ndsm_multigrid_core.f90:1077-1122): same du history, same cycle count and same solution bits as
     the separate metric pass (NDSM_HIP_NO_TRACK), for ms odd, even and 1, general and declared-zero rhs."""
-    mesh = uniform_mesh(ns)
+    mesh = meshf(ns)
     shp = tuple(ns[::-1])
     u0, rhs = rand_field(shp, 11), rand_field(shp, 12) * 50.0
     for bcs in ("NDDNDD", "DDNDDN"):
@@ -621,12 +634,12 @@ def test_fused_metric_bitwise(hip, ns, ms):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("ns", ([161, 120, 115], [160, 121, 115]), ids=_tag)
-def test_tracked_solve_vs_oracle(hip, port, ns):
+@pytest.mark.parametrize("ns,meshf", _meshes(([161, 120, 115], [160, 121, 115]), ([161, 120, 115],)))
+def test_tracked_solve_vs_oracle(hip, port, ns, meshf):
     """a level 1 just large enough for every large-level path at once (fused smoother incl. its odd-nx
     ghost-column variant, sweep+residual, streamed restriction, prolongation and metric folded into the
     smoother launches) - three solve-loop cycles against the oracle: du history and solution bits"""
-    mesh = uniform_mesh(ns)
+    mesh = meshf(ns)
     shp = tuple(ns[::-1])
     u0, rhs = rand_field(shp, 21), rand_field(shp, 22) * 10.0
     for bcs, lap in (("NDDNDD", True), ("DNDDDN", False)):
@@ -689,13 +702,15 @@ def test_slab_world_laplace_variant(hip):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("ns,nranks,levels", (([64, 64, 256], 4, 2), ([128, 64, 256], 2, 3), ([64, 64, 384], 8, 2)), ids=str)
-def test_slab_world_distributed_coarse_levels(hip, ns, nranks, levels):
+@pytest.mark.parametrize("ns,nranks,levels,meshf", [pytest.param(ns, nr, lv, uniform_mesh, id=f"{ns}-{nr}-{lv}") for ns, nr, lv in
+                                                    (([64, 64, 256], 4, 2), ([128, 64, 256], 2, 3), ([64, 64, 384], 8, 2))] +
+                         [pytest.param([64, 64, 256], 4, 2, aniso_mesh, id="aniso-[64, 64, 256]-4-2")])
+def test_slab_world_distributed_coarse_levels(hip, ns, nranks, levels, meshf):
     """several distributed levels (NDSM_HIP_DIST_LEVELS; by default chosen by size): every rank
     restricts straight into its own slab of the next level's rhs and prolongs from it, only the first
     non-distributed level travels to rank 0.  Loop-back world vs the single-domain solver: V-cycles and
     a whole solve, bit for bit."""
-    mesh = uniform_mesh(ns)
+    mesh = meshf(ns)
     shp = tuple(ns[::-1])
     u, rhs = rand_field(shp, 2112), rand_field(shp, 2113)
     os.environ["NDSM_HIP_DIST_LEVELS"] = str(levels)
@@ -1360,16 +1375,16 @@ def test_vecpot_context_reuse_and_cache(hip, port):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("ns", ([64, 64, 64], [33, 22, 27], [40, 24, 32], [100, 37, 51], [128, 128, 128], [144, 144, 72],
-                                [22, 22, 22], [40, 136, 72]), ids=_tag)
-def test_tail_cycle_bitwise(hip, ns):
+@pytest.mark.parametrize("ns,meshf", _meshes(([64, 64, 64], [33, 22, 27], [40, 24, 32], [100, 37, 51], [128, 128, 128],
+                                              [144, 144, 72], [22, 22, 22], [40, 136, 72]), ([33, 22, 27],)))
+def test_tail_cycle_bitwise(hip, ns, meshf):
     """the bottom of the V-cycle as ONE single-workgroup launch (tail.hip: every level of <= 6144 points
     resident in LDS - sweeps, residual, restriction, coarsest-grid solve, interpolation) against the same
     levels run kernel by kernel (switched through the development hook): V-cycles from random data, every
     level's u and rhs afterwards, the coarsest-grid sweep counters, the du history of a solve - bit for bit;
     max and mean form of the coarsest grid's stop test, ms = 1 ... 5, an unconverged coarsest solve"""
     L = hip.load_library()
-    mesh = uniform_mesh(ns)
+    mesh = meshf(ns)
     shp = tuple(ns[::-1])
     u, rhs = rand_field(shp, 7), rand_field(shp, 8)
     ran = 0
@@ -1648,13 +1663,15 @@ def test_correction_launch_with_one_tall_chunk(hip, port):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("ns", [[136, 130, 140], [131, 140, 134]])
-def test_correction_launch_with_rhs_vs_oracle(hip, port, ns):
+@pytest.mark.parametrize("ns,meshf", [pytest.param(ns, uniform_mesh, id=f"ns{i}") for i, ns in
+                                     enumerate(([136, 130, 140], [131, 140, 134]))] +
+                         [pytest.param([136, 130, 140], aniso_mesh, id="aniso-ns0")])
+def test_correction_launch_with_rhs_vs_oracle(hip, port, ns, meshf):
     """a Poisson problem (right-hand side in HBM) takes its correction on the one-sweep launch that opens the
     post-smoothing (rbgs3_fused_k<.., S = 1, .., RHS0 = false, MODE = 3>): three solve-loop cycles, even and odd
     nx, several tiles and chunks, against the oracle - field, du history and cycle count
     (ndsm_multigrid_core.f90:593-684 coarse_to_fine followed by :672-675's sweeps)"""
-    mesh = uniform_mesh(ns)
+    mesh = meshf(ns)
     shp = tuple(ns[::-1])
     u0 = rand_field(shp, 41)
     rhs = rand_field(shp, 42) * 50.0

@@ -13,7 +13,7 @@ import ctypes
 import numpy as np
 import pytest
 
-from golden_inputs import uniform_mesh
+from golden_inputs import aniso_mesh, uniform_mesh
 
 pytestmark = pytest.mark.gpu
 
@@ -97,8 +97,8 @@ def reference(port, b, mesh, **kw):
     return dict(ierr=ierr, ncycles=nc, c=c, d=d, phi=phi, B=b - g, E=0.5 * (w * (g * g).sum(axis=0)).sum())
 
 
-def case(ns, seed=5):
-    mesh = uniform_mesh(ns)
+def case(ns, seed=5, meshf=uniform_mesh):
+    mesh = meshf(ns)
     return mesh, abc(mesh) + EPS * grad_psi(mesh) + smooth_random(mesh, seed)
 
 
@@ -124,16 +124,23 @@ def test_all_neumann_3d_solver_matches_oracle(hip, port, ns):
     assert np.abs(got - u2).max() <= 1e-13 * np.abs(u2).max(), np.abs(got - u2).max()
 
 
-@pytest.mark.parametrize("ns", SHAPES, ids=IDS)
-def test_against_numpy_and_oracle(hip, port, ns):
+def _meshes(uniform, aniso):
+    """the shapes on uniform_mesh under the ids they always had, and on golden_inputs.aniso_mesh (a spacing of its own
+    on every axis, no origin at 0) under 'aniso-' ids; [300, 40, 60]: rows longer than a block, more rows than blocks"""
+    return ([pytest.param(ns, uniform_mesh, id=IDS(ns)) for ns in uniform] +
+            [pytest.param(ns, aniso_mesh, id="aniso-" + IDS(ns)) for ns in aniso])
+
+
+@pytest.mark.parametrize("ns,meshf", _meshes(SHAPES, ([33, 22, 27], [300, 40, 60])))
+def test_against_numpy_and_oracle(hip, port, ns, meshf):
     import ndsm_amd
-    mesh, b = case(ns)
+    mesh, b = case(ns, meshf=meshf)
     V = ndsm_amd.VecPot(*mesh)
     p = V.project(b, vc_tol=VC_TOL, return_phi=True)
     V.close()
     ref = reference(port, b, mesh)
     assert p.ierr == 0 and ref["ierr"] == 0
-    h = mesh[0][1] - mesh[0][0]
+    h = min(q[1] - q[0] for q in mesh)
     scale = np.abs(b).max()
     assert np.abs(p.B - ref["B"]).max() <= 1e-12 * scale, np.abs(p.B - ref["B"]).max()
     assert abs(p.c - ref["c"]) <= 1e-14 * scale / h, (p.c, ref["c"])
@@ -148,10 +155,10 @@ def test_against_numpy_and_oracle(hip, port, ns):
     assert p.divB_after < 0.2 * p.divB_before
 
 
-@pytest.mark.parametrize("ns", ([33, 33, 33], [33, 22, 27]), ids=IDS)
-def test_invariants(hip, ns):
+@pytest.mark.parametrize("ns,meshf", _meshes(([33, 33, 33], [33, 22, 27]), ([33, 22, 27],)))
+def test_invariants(hip, ns, meshf):
     import ndsm_amd
-    mesh, b = case(ns)
+    mesh, b = case(ns, meshf=meshf)
     V = ndsm_amd.VecPot(*mesh)
     p = V.project(b, vc_tol=VC_TOL)
     for d in range(3):                   # B.n on each of the six faces: bitwise unchanged

@@ -17,7 +17,8 @@ import os
 import numpy as np
 import pytest
 
-from golden_inputs import (BCS3, BCS_RANDOM, KERNEL_SHAPES_2D, KERNEL_SHAPES_3D, analytic_case, digest,
+from golden_inputs import (ANISO_SHAPE_2D, ANISO_SHAPES_3D, BCS3, BCS_ANISO, BCS_RANDOM, KERNEL_SHAPES_2D,
+                           KERNEL_SHAPES_3D, analytic_case, aniso_case, aniso_mesh, aniso_pipeline_cases, digest,
                            manufactured_poisson, quirk_case, rand_field, random_reference_cases, uniform_mesh)
 
 
@@ -140,6 +141,81 @@ def test_live_reference_random(port, golden_dir):
                 assert digest(a) == want[f"relax_{tag}_{bcs}"], (tag, bcs)
             assert digest(port.residual3d(u, rhs, mesh, bcs)) == want[f"residual_{tag}_{bcs}"], (tag, bcs)
         assert digest(port.vcycle(u, rhs, mesh, "DNDDND", ms=3)) == want[f"vcycle_{tag}_DNDDND_ms3"], tag
+
+
+def _aniso_want(golden_dir):
+    with open(os.path.join(golden_dir, "reference_aniso.json")) as fh:
+        return json.load(fh)
+
+
+@pytest.mark.parametrize("ns", ANISO_SHAPES_3D, ids=_tag)
+def test_kernels3d_aniso_golden(port, golden_dir, ns):
+    """test_kernels3d_golden on aniso_mesh (a spacing of its own on every axis, no origin at 0), five BC sets: the
+    reference's outputs as sha256 of their bits (golden/reference_aniso.json)"""
+    want = _aniso_want(golden_dir)[_tag(ns)]
+    mesh, u, rhs = aniso_case(ns)
+    shapes, meshes = port.hierarchy(ns, mesh)
+    assert shapes.tolist() == want["level_shapes"]
+    for l, lv in enumerate(meshes):
+        for d, m in enumerate(lv):
+            assert digest(m) == want[f"mesh_l{l+1}_d{d+1}"], (l + 1, d + 1)
+    for bcs in BCS_ANISO:
+        assert digest(port.relax3d(u, rhs, mesh, bcs)) == want[f"relax_{bcs}"], bcs
+        assert digest(port.residual3d(u, rhs, mesh, bcs)) == want[f"residual_{bcs}"], bcs
+        assert digest(port.vcycle(u, rhs, mesh, bcs)) == want[f"vcycle_{bcs}"], bcs
+    for lvl in range(1, len(shapes)):
+        f = rand_field(tuple(int(v) for v in shapes[lvl - 1][::-1]), 3000 + lvl)
+        c = rand_field(tuple(int(v) for v in shapes[lvl][::-1]), 4000 + lvl)
+        assert digest(port.restrict(f, ns, mesh, lvl)) == want[f"restrict_l{lvl}"], lvl
+        assert digest(port.interp(c, ns, mesh, lvl)) == want[f"interp_l{lvl}"], lvl
+
+
+@pytest.mark.parametrize("bcs", BCS3)
+def test_solve3d_aniso_history_golden(port, golden_dir, bcs):
+    ns = ANISO_SHAPES_3D[0]
+    h = _aniso_want(golden_dir)[f"solve_{_tag(ns)}_{bcs}"]
+    mesh = aniso_mesh(ns)
+    us, rhs = manufactured_poisson(mesh, bcs)
+    ierr, u, du, hist, nc, sw = port.solve_bvp(np.zeros_like(us), rhs, mesh, bcs, hist_len=64)
+    assert ierr == 0 and nc == h["ncycles"]
+    assert list(hist) == h["du"]          # bit-identical residual history
+    assert du == h["du"][-1]
+    assert digest(u) == h["u"]
+
+
+def test_kernels2d_aniso_golden(port, golden_dir):
+    """test_kernels2d_golden on the first two axes of aniso_mesh, with its tolerances"""
+    ns = ANISO_SHAPE_2D
+    g = np.load(os.path.join(golden_dir, "reference_aniso_2d.npz"))
+    mesh, u, rhs = aniso_case(ns)
+    rhs0 = rhs - rhs.mean()
+    shapes, _ = port.hierarchy(ns, mesh)
+    assert np.array_equal(shapes, g["level_shapes"])
+    for bcs in ("NNNN", "DNND"):
+        np.testing.assert_allclose(port.relax_nd(u, rhs, mesh, bcs), g[f"relax_{bcs}"], rtol=0, atol=1e-14)
+        assert np.array_equal(port.residual_nd(u, rhs, mesh, bcs), g[f"residual_{bcs}"])
+    np.testing.assert_allclose(port.vcycle(u, rhs0, mesh, "NNNN"), g["vcycle_NNNN"], rtol=0, atol=1e-14)
+    ierr, us, du, hist, nc, sw = port.solve_bvp(np.zeros(u.shape), rhs0, mesh, "NNNN", hist_len=64)
+    assert ierr == int(g["solve_NNNN_meta"][0])
+    np.testing.assert_allclose(us, g["solve_NNNN"], rtol=0, atol=1e-13)
+    for lvl in range(1, len(shapes)):
+        f = rand_field(tuple(int(v) for v in shapes[lvl - 1][::-1]), 3000 + lvl)
+        c = rand_field(tuple(int(v) for v in shapes[lvl][::-1]), 4000 + lvl)
+        assert np.array_equal(port.restrict(f, ns, mesh, lvl), g[f"restrict_l{lvl}"])
+        assert np.array_equal(port.interp(c, ns, mesh, lvl), g[f"interp_l{lvl}"])
+
+
+@pytest.mark.parametrize("name", ("analytic", "unbalanced"))
+def test_pipeline_aniso_golden(port, golden_dir, name):
+    """test_pipeline_golden where quirk Q4 is live: fluxes with dq(1) dq(2) on every face, grad chi with the normal
+    spacing, the flux-balance fields at coordinates away from 0 (golden/pipeline_aniso_*.npz)"""
+    g = np.load(os.path.join(golden_dir, f"pipeline_aniso_{name}.npz"))
+    _name, x, y, z, b = [c for c in aniso_pipeline_cases() if c[0] == name][0]
+    ierr, A, B, ioptc, ropt = port.vector_potential(x, y, z, b)
+    assert ierr == 0 and np.array_equal(ioptc, g["ioptc"])
+    assert np.abs(A - g["A"]).max() <= 1e-12 * np.abs(g["A"]).max()
+    h = x[1] - x[0]
+    assert np.abs(B - g["B"]).max() <= 1e-12 * np.abs(g["A"]).max() / h * 4
 
 
 def test_quirk_ierr_is_the_last_face_solve(port, golden_dir):

@@ -254,6 +254,71 @@ int ndsm_hip_vecpot_devore(void *h, const double *B, const double *Bp, double *A
 int ndsm_hip_vecpot_devore_device(void *h, const double *dB, const double *dBp, double *dA, double *dAp,
                                   double out[8]);
 
+/* ---- Field lines, and line integrals along them, on the same handle (DESIGN.md "Field-line tracing and field-line
+ * helicity") -------------------------------------------------------------------------------------------------------
+ * Traces the field lines of B through nseeds seed points and integrates a second field G along them: with G = A this
+ * is the field-line helicity  int A.dl  (Yeates & Page 2018; Moraitis et al. 2019), usually with the DeVore-gauge A of
+ * ndsm_hip_vecpot_devore.  The handle supplies the mesh only (lo_d = its first point, h_d = q_d[1] - q_d[0],
+ * hi_d = lo_d + (n_d - 1) h_d per axis); no solve runs and no hierarchy is created.
+ *   B, G      (nx,ny,nz,3) as everywhere; G may be NULL (every integral is 0)
+ *   seeds     (3,nseeds): x, y, z of each seed in physical coordinates
+ *   step      > 0, in units of min(h_x,h_y,h_z): ds = step * min(h)
+ *   max_steps >= 1, finite; clamped to 2^24.  Every line ends after at most max_steps steps: a closed line costs
+ *             max_steps steps and comes back NDSM_HIP_TRACE_UNFINISHED.
+ *   direction +1 along B, -1 against B, 0 both.  nl = nseeds lines, or with 0 nl = 2 nseeds: line i (forward) and
+ *             line nseeds + i (backward) belong to seed i.
+ *   out       ends (3,nl), length (nl), integral (nl) doubles; status (nl), nsteps (nl) int32
+ * Semantics, in fp64 in this operand order (device code is built without contraction, so a restatement in the same
+ * order gives the same bits):
+ *   interpolation  trilinear in the cell c_d = clamp(floor(u_d), 0, n_d - 2), u_d = (r_d - lo_d) / h_d, with the
+ *                  unclamped f_d = u_d - c_d (a stage point outside the box extrapolates from the edge cell; a field
+ *                  linear in x, y, z is reproduced wherever it is evaluated): along x first,
+ *                  c00 = v000 + f_x (v100 - v000) ..., then y, c0 = c00 + f_y (c10 - c00), then z.
+ *   ODE            dr/ds = sgn B/|B| (sgn = +1 forward, -1 backward), dI/ds = G.B/|B|, |B| = sqrt((Bx Bx + By By)
+ *                  + Bz Bz), G.e = (Gx ex + Gy ey) + Gz ez.  The integrand carries no sgn: a backward line
+ *                  accumulates the integral of G.dl taken in the direction of B, from its end to the seed, so for
+ *                  both directions integral[i] + integral[nseeds + i] is int G.dl along the whole line through seed
+ *                  i from the foot where B enters the box to the foot where it leaves.
+ *   step           classical RK4 with fixed ds: k2 at r + (0.5 ds) k1, k3 at r + (0.5 ds) k2, k4 at r + ds k3,
+ *                  r' = r + (ds / 6) (((k1 + 2 k2) + 2 k3) + k4), the same weights for I; length is the sum of the
+ *                  ds taken.
+ *   exit           r' outside [lo, hi]: the step is not accepted.  t = the smallest (face_d - r_d) / (r'_d - r_d)
+ *                  over the axes that left (x before y before z on a tie), 0 <= t <= 1, is where the chord r -> r'
+ *                  meets a face, and the step is REDONE as a full RK4 step of length t ds from the same r (stage 1
+ *                  reused) for r and I alike; length += t ds.  Then the coordinate normal to that face is set to
+ *                  the face's value and the other two are clamped to the box: an end point lies on its face
+ *                  exactly and never outside.  status = the face.  The chord fraction is exact when the tangent's
+ *                  normal component is constant over the step; on a general field the snap leaves O(kappa ds^2) in
+ *                  the end point, kappa the line's curvature: end points are not fourth order in general.
+ *   other ends     |B| not > 0 at any stage (zero or NaN): NDSM_HIP_TRACE_NULL, the line stops at the last
+ *                  accepted point.  max_steps accepted steps: NDSM_HIP_TRACE_UNFINISHED.  A seed outside the box
+ *                  (or not finite): NDSM_HIP_TRACE_OUTSIDE, end = seed, length = integral = 0, nsteps = 0.
+ *   nsteps         the RK4 steps that moved the line: accepted steps plus the shortened exit step.
+ * Each line depends on its own seed only: the same bits whatever the number of seeds, their order, or the direction
+ * argument.  A seed on a face whose B points out of the box ends at once (one step of length 0, that face).
+ * Returns 0, or >= 9001 errors: 9001 without a GPU whatever the arguments; 9002 a NULL handle or, with nseeds > 0,
+ * a NULL B, seeds or output array; 9004 step <= 0 or not finite, max_steps < 1, a direction other than -1, 0, +1,
+ * nseeds < 0.  nseeds == 0 succeeds and touches nothing.  On failure the host entry clears the nl entries of its
+ * outputs (status 0 is no status); the device entry cannot clear device arrays without a device and leaves them.
+ * Device memory: the host entry stages B and G in the handle's scratch (24 B/pt each). */
+#define NDSM_HIP_TRACE_XLO 1        /* left through the face x = lo_x */
+#define NDSM_HIP_TRACE_XHI 2
+#define NDSM_HIP_TRACE_YLO 3
+#define NDSM_HIP_TRACE_YHI 4
+#define NDSM_HIP_TRACE_ZLO 5
+#define NDSM_HIP_TRACE_ZHI 6
+#define NDSM_HIP_TRACE_NULL 7       /* |B| not > 0 at a stage */
+#define NDSM_HIP_TRACE_UNFINISHED 8 /* max_steps steps taken */
+#define NDSM_HIP_TRACE_OUTSIDE 9    /* the seed is not in the box */
+/* HOST arrays */
+int ndsm_hip_vecpot_trace(void *h, const double *B, const double *G, int nseeds, const double *seeds, double step,
+                          int max_steps, int direction, double *ends, double *length, double *integral,
+                          int32_t *status, int32_t *nsteps);
+/* the same on DEVICE arrays of the library's GPU (seeds and the five outputs too) */
+int ndsm_hip_vecpot_trace_device(void *h, const double *dB, const double *dG, int nseeds, const double *dseeds,
+                                 double step, int max_steps, int direction, double *dends, double *dlength,
+                                 double *dintegral, int32_t *dstatus, int32_t *dnsteps);
+
 /* =====================================================================
  * PART 3 - additive exports, multi-GPU
  *

@@ -9,8 +9,9 @@ without an MI355X every call raises.
 from .ndsm import vector_potential, vector_potential_slab, get_lib_path  # noqa: F401
 from ._lib import (load_library, lib_path, MGSolver, VecPot, World, slab_plan, poisson_solve,  # noqa: F401
                    NdsmHipError, Helicity, vector_potential_field, relative_helicity, Projection,
-                   solenoidal_projection, devore_potentials)
+                   solenoidal_projection, devore_potentials, FieldLines, trace_field_lines,
+                   field_line_helicity)
 
 __all__ = ["vector_potential", "vector_potential_slab", "get_lib_path", "load_library", "lib_path", "MGSolver", "VecPot", "poisson_solve",
            "NdsmHipError", "Helicity", "vector_potential_field", "relative_helicity", "Projection", "solenoidal_projection",
-           "devore_potentials"]
+           "devore_potentials", "FieldLines", "trace_field_lines", "field_line_helicity"]

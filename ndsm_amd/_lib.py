@@ -240,6 +240,9 @@ class VecPot:
                                                           _dp]
         self.L.ndsm_hip_vecpot_devore.argtypes = [ctypes.c_void_p, _dp, _dp, _dp, _dp, _dp]
         self.L.ndsm_hip_vecpot_devore_device.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 4 + [_dp]
+        _tr = [ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5
+        self.L.ndsm_hip_vecpot_trace.argtypes = [ctypes.c_void_p] * 3 + _tr
+        self.L.ndsm_hip_vecpot_trace_device.argtypes = [ctypes.c_void_p] * 3 + _tr
         self.last_projection = None
         self.L.ndsm_hip_device_alloc.argtypes = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
         self.L.ndsm_hip_device_free.argtypes = [ctypes.c_void_p]
@@ -390,10 +393,11 @@ class VecPot:
         f = (A.reshape(shape), Ap.reshape(shape), Bp.reshape(shape)) if return_fields else (None, None, None)
         return _helicity_tuple(max(ierr, ierr_p), out, *f)
 
-    def _devore_chain(self, B, ioptc, ropt, both, return_fields, ierr_p):
+    def _devore_chain(self, B, ioptc, ropt, both, return_fields, ierr_p, after=None):
         """helicity(gauge="devore" / "both") on the device: B (flat) goes up once into two arrays; the potential
         field B_p comes from ndsm_hip_vecpot_solve_device on the copy (both: ndsm_hip_vecpot_helicity_device, the
-        same B_p) and stays there for ndsm_hip_vecpot_devore_device.  Only the results come home."""
+        same B_p) and stays there for ndsm_hip_vecpot_devore_device.  Only the results come home.  after(d): called
+        with the device arrays (B, Bp, A, Ap) while they are still resident."""
         L = self.L
         shape = tuple(int(v) for v in self.nshape4[::-1])
         names = ("B", "Bp", "A", "Ap") + (("Ac", "Apc") if both else ())
@@ -421,6 +425,8 @@ class VecPot:
             self.last_ioptc, self.last_ropt = ioptc, ropt
             _check(L.ndsm_hip_vecpot_devore_device(self.h, d["B"], d["Bp"], d["A"], d["Ap"], _d(out_d)),
                    "ndsm_hip_vecpot_devore_device", L)
+            if after is not None:
+                after(d)
             host = {}
             for k in (names[1:] if return_fields else ()):
                 host[k] = np.empty(B.size)
@@ -454,6 +460,122 @@ class VecPot:
                 self.h, dB, dBp, dA, dAp, _d(out)))
         _check(ierr, "ndsm_hip_vecpot_devore", self.L)
         return _helicity_tuple(0, out, A.reshape(shape), Ap.reshape(shape), Bp.reshape(shape))
+
+    def trace(self, b, seeds, g=None, step=0.5, max_steps=None, direction="both", device=False):
+        """Field lines of b (3,nz,ny,nx) through seeds (nseeds,3; x, y, z in physical coordinates) and the line
+        integral of g (3,nz,ny,nx; None: no integral, zeros) along them, on the device (semantics:
+        include/ndsm_hip.h, ndsm_hip_vecpot_trace).  Arc-length RK4 with the fixed step ds = step * min(h),
+        trilinear interpolation; a line ends on a face of the box (the exit step is shortened so that it ends on
+        the face), at a null of b, or after max_steps steps (None: default_max_steps(step) = ceil(4 (nx + ny +
+        nz) / step), about four box crossings; at most 2**24).  direction: "forward" (along b), "backward" or
+        "both".  Returns a FieldLines tuple: ends (ndir,nseeds,3), length, integral (ndir,nseeds), status, nsteps
+        (ndir,nseeds; int32, status one of the TRACE_* codes), flh; ndir = 2 for "both" (row 0 forward, row 1
+        backward), else 1.  A backward line's integral is that of g.dl taken in the direction of b, so flh =
+        integral[0] + integral[1] is the integral of g.dl along the whole line through each seed from the foot
+        where b enters the box to the foot where it leaves - with g = A the field-line helicity; flh is None for
+        a single direction.  device=True: the arrays are staged in device memory and the device-resident entry
+        point runs."""
+        direction, step, max_steps = self._trace_args(step, max_steps, direction)
+        B = self._field_arg(b, "trace")
+        G = None if g is None else self._field_arg(g, "trace")
+        S = self._seeds_arg(seeds)
+        out = _trace_outputs(len(S), direction)
+        if len(S) == 0:
+            return _field_lines(out, direction)
+        if not device:
+            ierr = self.L.ndsm_hip_vecpot_trace(self.h, B.ctypes.data, None if G is None else G.ctypes.data, len(S),
+                                                S.ctypes.data, step, max_steps, direction,
+                                                *[a.ctypes.data for a in out])
+        else:
+            arrays = [B, S] + out + ([G] if G is not None else [])
+            ierr = self._on_device(arrays, lambda dB, dS, d1, d2, d3, d4, d5, dG=None:
+                                   self.L.ndsm_hip_vecpot_trace_device(self.h, dB, dG, len(S), dS, step, max_steps,
+                                                                       direction, d1, d2, d3, d4, d5))
+        _check(ierr, "ndsm_hip_vecpot_trace", self.L)
+        return _field_lines(out, direction)
+
+    def default_max_steps(self, step=0.5):
+        """the max_steps that trace() uses for max_steps=None: ceil(4 (nx + ny + nz) / step)"""
+        return int(np.ceil(4.0 * float(int(self.nshape4[0]) + int(self.nshape4[1]) + int(self.nshape4[2])) / step))
+
+    def _trace_args(self, step, max_steps, direction):
+        """(direction code, step, max_steps) of trace(); ValueError before anything is launched"""
+        if direction not in _DIRECTIONS:
+            raise ValueError(f"direction must be 'forward', 'backward' or 'both', not {direction!r}")
+        step = float(step)
+        if not (step > 0.0 and np.isfinite(step)):
+            raise ValueError(f"step must be a positive finite number, not {step!r}")
+        if max_steps is None:
+            max_steps = self.default_max_steps(step)
+        if int(max_steps) != max_steps or max_steps < 1:
+            raise ValueError(f"max_steps must be an integer >= 1, not {max_steps!r}")
+        return _DIRECTIONS[direction], step, int(min(int(max_steps), TRACE_MAX_STEPS))
+
+    @staticmethod
+    def _seeds_arg(seeds):
+        S = np.asarray(seeds, dtype=np.float64)
+        if S.ndim != 2 or S.shape[1] != 3:
+            raise NdsmHipError(f"trace: seeds of shape {S.shape}, (nseeds, 3) is needed (code 9002)")
+        if len(S) > TRACE_MAX_SEEDS:
+            raise NdsmHipError(f"trace: {len(S)} seeds, at most {TRACE_MAX_SEEDS} per call (code 9002)")
+        return np.ascontiguousarray(S).copy()
+
+    def field_line_helicity(self, b, seeds, gauge="devore", a=None, step=0.5, max_steps=None, direction="both",
+                            niterex_max=10000, ncycles_max=1024, ex_tol=1e-13, vc_tol=1e-10, ms=5, mean=False,
+                            mixed_precision=False, flxcrl=False, return_fields=False):
+        """Field-line helicity of b (3,nz,ny,nx): the integral of A.dl along the field line through each seed
+        (trace() with g = A).  With a (3,nz,ny,nx) given, that A is used and no solve runs (the Helicity is None).
+        Otherwise A comes from the helicity chain of the gauge - "devore" (helicity(gauge="devore")) or "coulomb"
+        (helicity()) - ON THE DEVICE, and the lines are traced there before anything comes home: b goes up once,
+        A and b do not cross PCIe in between.  Returns (FieldLines, Helicity): the lines (flh with
+        direction="both") and the Helicity tuple of that chain, the bits helicity(gauge=gauge) returns (with
+        return_fields its A, A_p, B_p)."""
+        if gauge not in ("devore", "coulomb"):
+            raise ValueError(f"gauge must be 'devore' or 'coulomb', not {gauge!r}")
+        direction, step, max_steps = self._trace_args(step, max_steps, direction)
+        B = self._field_arg(b, "field_line_helicity")
+        S = self._seeds_arg(seeds)
+        if a is not None:
+            inv = {v: k for k, v in _DIRECTIONS.items()}
+            return self.trace(b, S, g=a, step=step, max_steps=max_steps, direction=inv[direction]), None
+        L = self.L
+        out = _trace_outputs(len(S), direction)
+
+        def lines(d):
+            """trace on the resident B and A (d: the chain's device arrays)"""
+            if len(S) == 0:
+                return
+            self._on_device([S] + out, lambda dS, d1, d2, d3, d4, d5: _check(L.ndsm_hip_vecpot_trace_device(
+                self.h, d["B"], d["A"], len(S), dS, step, max_steps, direction, d1, d2, d3, d4, d5),
+                "ndsm_hip_vecpot_trace_device", L))
+
+        ioptc, ropt = self._options(niterex_max, ncycles_max, ex_tol, vc_tol, ms, mean, mixed_precision, flxcrl)
+        if gauge == "devore":
+            hel = self._devore_chain(B, ioptc, ropt, False, return_fields, 0, after=lines)
+            return _field_lines(out, direction), hel
+        shape = tuple(int(v) for v in self.nshape4[::-1])
+        d = {}
+        o8 = np.zeros(8)
+        host = {}
+        try:
+            for k in ("B", "A", "Ap", "Bp"):
+                d[k] = ctypes.c_void_p()
+                _check(L.ndsm_hip_device_alloc(B.nbytes, ctypes.byref(d[k])), "device_alloc", L)
+            _check(L.ndsm_hip_memcpy_h2d(d["B"], B.ctypes.data, B.nbytes), "h2d", L)
+            ierr = L.ndsm_hip_vecpot_helicity_device(self.h, ioptc.ctypes.data_as(_ip), _d(ropt), d["B"], d["A"],
+                                                     d["Ap"], d["Bp"], _d(o8))
+            if ierr >= 9000:
+                _check(ierr, "ndsm_hip_vecpot_helicity_device", L)
+            self.last_ioptc, self.last_ropt = ioptc, ropt
+            lines(d)
+            for k in (("A", "Ap", "Bp") if return_fields else ()):
+                host[k] = np.empty(B.size)
+                _check(L.ndsm_hip_memcpy_d2h(host[k].ctypes.data, d[k], B.nbytes), "d2h", L)
+        finally:
+            for p in d.values():
+                L.ndsm_hip_device_free(p)
+        f = {k: v.reshape(shape) for k, v in host.items()}
+        return _field_lines(out, direction), _helicity_tuple(ierr, o8, f.get("A"), f.get("Ap"), f.get("Bp"))
 
     def project(self, b, niterex_max=10000, ncycles_max=1024, ex_tol=1e-13, vc_tol=1e-10, ms=5, mean=False,
                 mixed_precision=False, flxcrl=False, device=False, return_phi=False):
@@ -499,6 +621,27 @@ def _helicity_tuple(ierr, out, A, Ap, Bp):
     """a Helicity from the out[8] of the helicity / devore entries"""
     return Helicity(int(ierr), float(out[0]), float(out[1]), float(out[2]), float(out[3]), float(out[2] - out[3]),
                     float(out[4]), float(out[5]), float(out[6]), float(out[7]), A, Ap, Bp)
+
+
+FieldLines = collections.namedtuple("FieldLines", ["ends", "length", "integral", "status", "nsteps", "flh"])
+
+# status codes of a traced line (NDSM_HIP_TRACE_* in include/ndsm_hip.h): the face it left through, or why it stopped
+TRACE_XLO, TRACE_XHI, TRACE_YLO, TRACE_YHI, TRACE_ZLO, TRACE_ZHI, TRACE_NULL, TRACE_UNFINISHED, TRACE_OUTSIDE = \
+    range(1, 10)
+TRACE_MAX_STEPS = 2 ** 24          # the library's ceiling of max_steps
+TRACE_MAX_SEEDS = 2 ** 30 - 1      # per call (2 nseeds lines fit a C int)
+_DIRECTIONS = {"forward": 1, "backward": -1, "both": 0}
+
+
+def _trace_outputs(nseeds, direction):
+    """[ends, length, integral, status, nsteps] of ndsm_hip_vecpot_trace for nseeds seeds, zeroed"""
+    nd = 2 if direction == 0 else 1
+    return [np.zeros((nd, nseeds, 3)), np.zeros((nd, nseeds)), np.zeros((nd, nseeds)),
+            np.zeros((nd, nseeds), dtype=np.int32), np.zeros((nd, nseeds), dtype=np.int32)]
+
+
+def _field_lines(out, direction):
+    return FieldLines(*out, out[2][0] + out[2][1] if direction == 0 else None)
 
 
 def _grid_handle(x, y, z, b, ngrids, lib):
@@ -547,6 +690,35 @@ def devore_potentials(x, y, z, b, bp, lib=None):
     V = _grid_handle(x, y, z, b, 0, lib)
     try:
         return V.devore(b, bp)
+    finally:
+        V.close()
+
+
+def trace_field_lines(x, y, z, b, seeds, g=None, step=0.5, max_steps=None, direction="both", lib=None):
+    """Field lines of b (3,nz,ny,nx) through seeds (nseeds,3) and the line integral of g along them: one-shot form
+    of VecPot.trace (returns its FieldLines tuple).  Raises NdsmHipError on device / runtime failures (>= 9001)."""
+    V = _grid_handle(x, y, z, b, 0, lib)
+    try:
+        return V.trace(b, seeds, g=g, step=step, max_steps=max_steps, direction=direction)
+    finally:
+        V.close()
+
+
+def field_line_helicity(x, y, z, b, seeds, gauge="devore", a=None, step=0.5, max_steps=None, direction="both",
+                        niterex_max=10000, ncycles_max=1024, ex_tol=1e-13, vc_tol=1e-10, ms=5, mean=False,
+                        mixed_precision=False, flxcrl=False, ngrids=0, return_fields=False, lib=None):
+    """Field-line helicity of b (3,nz,ny,nx) at seeds (nseeds,3): one-shot form of VecPot.field_line_helicity.
+    Returns (FieldLines, Helicity); with a given the lines are traced with g = a and the Helicity is None, else A
+    comes from the chain of the gauge ("devore" or "coulomb") on the device.  Raises NdsmHipError on device /
+    runtime failures (>= 9001)."""
+    if gauge not in ("devore", "coulomb"):
+        raise ValueError(f"gauge must be 'devore' or 'coulomb', not {gauge!r}")
+    V = _grid_handle(x, y, z, b, ngrids, lib)
+    try:
+        return V.field_line_helicity(b, seeds, gauge=gauge, a=a, step=step, max_steps=max_steps, direction=direction,
+                                     niterex_max=niterex_max, ncycles_max=ncycles_max, ex_tol=ex_tol, vc_tol=vc_tol,
+                                     ms=ms, mean=mean, mixed_precision=mixed_precision, flxcrl=flxcrl,
+                                     return_fields=return_fields)
     finally:
         V.close()
 

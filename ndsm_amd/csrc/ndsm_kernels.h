@@ -29,7 +29,8 @@ enum {
   NDSMK_OK = 0,
   NDSMK_ENODEV = 9001,   /* no HIP device visible */
   NDSMK_EARG = 9002,     /* shape/argument check failed on the host */
-  NDSMK_ENCCL = 9003     /* RCCL call failed */
+  NDSMK_ENCCL = 9003,    /* RCCL call failed */
+  NDSMK_EVALUE = 9004    /* a scalar argument outside its range (ndsmk_trace) */
 };
 
 /* geometry + operator constants of one grid level (interoperable with the
@@ -201,6 +202,19 @@ int ndsmk_project_div_max(const double *B, const int32_t *n3, const double *h_dq
  * plane b of B_z(z0), A_p of Bp integrated down from A's top plane (A_p(nz-1) = A(nz-1) bitwise), A_z = A_p,z = 0.
  * Trapezoid cumulative sums, h/4 and h/2 formed here from h_dq3.  A, Ap distinct.  Asynchronous. */
 int ndsmk_devore(const double *B, const double *Bp, double *A, double *Ap, const int32_t *n3, const double *h_dq3);
+
+/* Field lines and line integrals (trace.hip; semantics: include/ndsm_hip.h, NDSM_HIP_TRACE_*).  B, G (G may be NULL:
+ * integrals 0) DEVICE arrays (nx,ny,nz,3); seeds (3,nseeds), ends (3,nl), length, integral, status, nsteps (nl) DEVICE
+ * arrays, nl = nseeds (direction +1 / -1) or 2 nseeds (0: the forward block, then the backward block).  lo3, h_dq3:
+ * first mesh point and spacing per axis; step in units of min(h); max_steps is clamped to 2^24.  NDSMK_EVALUE for
+ * step <= 0, max_steps < 1, another direction, nseeds < 0; nseeds == 0 launches nothing.  Asynchronous. */
+enum {
+  NDSMK_TRACE_XLO = 1, NDSMK_TRACE_XHI = 2, NDSMK_TRACE_YLO = 3, NDSMK_TRACE_YHI = 4, NDSMK_TRACE_ZLO = 5,
+  NDSMK_TRACE_ZHI = 6, NDSMK_TRACE_NULL = 7, NDSMK_TRACE_UNFINISHED = 8, NDSMK_TRACE_OUTSIDE = 9
+};
+int ndsmk_trace(const double *B, const double *G, const int32_t *n3, const double *lo3, const double *h_dq3,
+                int nseeds, const double *seeds, double step, int max_steps, int direction, double *ends,
+                double *length, double *integral, int32_t *status, int32_t *nsteps);
 
 /* the face phase on the device (faces.hip): packed face buffers, six faces back to back */
 int ndsmk_face_offsets(const int32_t *n3, int64_t *off6, int64_t *total);

@@ -908,6 +908,92 @@ contains
     ierr = rc
   end function
 
+  ! ---- field lines and line integrals on the same handle -----------------
+  ! B (nx,ny,nz,3), G the same or NULL (integrals 0), seeds (3,nseeds) in physical coordinates; step > 0 in units
+  ! of min(h), max_steps >= 1, direction +1 / -1 / 0 (both: nl = 2 nseeds lines, the forward block first; else nl =
+  ! nseeds).  Out: ends (3,nl), length, integral (nl), status, nsteps (nl, int32).  The handle supplies the mesh; no
+  ! solve runs.  Return value: 0, or >= 9001 errors (9002 a NULL handle or required array, 9004 a scalar out of
+  ! range).  The host entry clears its outputs on every failure (as far as nseeds and the pointers allow).
+
+  ! HOST arrays
+  function ndsm_hip_vecpot_trace(handle, B, G, nseeds, seeds, step, max_steps, direction, ends, length, integral, &
+                                 status, nsteps) bind(c, name="ndsm_hip_vecpot_trace") result(ierr)
+    type(c_ptr), value :: handle, B, G, seeds, ends, length, integral, status, nsteps
+    integer(c_int), value :: nseeds, max_steps, direction
+    real(c_double), value :: step
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_trace(handle, B, G, nseeds, seeds, step, max_steps, direction, ends, length, integral, &
+                               status, nsteps, .false., "ndsm_hip_vecpot_trace")
+  end function
+
+  ! the same on DEVICE arrays of the library's GPU (nothing is cleared: the outputs are not host memory)
+  function ndsm_hip_vecpot_trace_device(handle, dB, dG, nseeds, dseeds, step, max_steps, direction, dends, dlength, &
+                                        dintegral, dstatus, dnsteps) bind(c, name="ndsm_hip_vecpot_trace_device") &
+      result(ierr)
+    type(c_ptr), value :: handle, dB, dG, dseeds, dends, dlength, dintegral, dstatus, dnsteps
+    integer(c_int), value :: nseeds, max_steps, direction
+    real(c_double), value :: step
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_trace(handle, dB, dG, nseeds, dseeds, step, max_steps, direction, dends, dlength, dintegral, &
+                               dstatus, dnsteps, .true., "ndsm_hip_vecpot_trace_device")
+  end function
+
+  function vecpot_handle_trace(handle, B, G, nseeds, seeds, step, max_steps, direction, ends, length, integral, &
+                               status, nsteps, on_device, who) result(ierr)
+    type(c_ptr), intent(in) :: handle, B, G, seeds, ends, length, integral, status, nsteps
+    integer(c_int), intent(in) :: nseeds, max_steps, direction
+    real(c_double), intent(in) :: step
+    logical, intent(in) :: on_device
+    character(len=*), intent(in) :: who
+    integer(c_int) :: ierr
+    type(vecpot_ctx), pointer :: ctx
+    integer(c_int) :: rc
+    logical :: need
+    if (.not. on_device) call clear_outputs()
+    ierr = ndsmk_init(-1_c_int)                        ! without a device: 9001, whatever the arguments
+    if (ierr /= 0) return
+    ierr = NDSMK_EARG
+    if (.not. c_associated(handle)) return
+    need = nseeds > 0                                  ! no seeds: no array is looked at
+    if (need .and. .not. (c_associated(B) .and. c_associated(seeds) .and. c_associated(ends) .and. &
+                          c_associated(length) .and. c_associated(integral) .and. c_associated(status) .and. &
+                          c_associated(nsteps))) return
+    call c_f_pointer(handle, ctx)
+    if (.not. ctx%live) return
+    rc = vecpot_trace(ctx, B, G, nseeds, seeds, step, max_steps, direction, ends, length, integral, status, nsteps, &
+                      on_device)
+    if (rc /= 0) then
+      call report(who, rc)
+      if (rc < NDSMK_ENODEV) rc = NDSMK_ENODEV
+      if (.not. on_device) call clear_outputs()
+    end if
+    ierr = rc
+  contains
+    subroutine clear_outputs()
+      real(c_double), pointer :: r(:)
+      integer(c_int32_t), pointer :: k(:)
+      integer :: nl
+      if (nseeds <= 0) return
+      if (nseeds > huge(0) / 6) return
+      nl = nseeds * merge(2, 1, direction == 0)
+      if (c_associated(ends)) then
+        call c_f_pointer(ends, r, [3 * nl]); r = 0
+      end if
+      if (c_associated(length)) then
+        call c_f_pointer(length, r, [nl]); r = 0
+      end if
+      if (c_associated(integral)) then
+        call c_f_pointer(integral, r, [nl]); r = 0
+      end if
+      if (c_associated(status)) then
+        call c_f_pointer(status, k, [nl]); k = 0
+      end if
+      if (c_associated(nsteps)) then
+        call c_f_pointer(nsteps, k, [nl]); k = 0
+      end if
+    end subroutine
+  end function
+
   ! ---- z-slab decomposition over GPUs (SURVEY 8e) -----------------------
 
   ! rank 0 creates the 128-byte RCCL id; the launcher hands it to every rank

@@ -16,6 +16,7 @@ module ndsmh_iface
 
   ! error codes shared with ndsm_kernels.h
   integer(c_int), parameter :: NDSMK_OK = 0, NDSMK_ENODEV = 9001, NDSMK_EARG = 9002, NDSMK_ENCCL = 9003
+  integer(c_int), parameter :: NDSMK_EVALUE = 9004
 
   type, bind(c) :: ndsmk_grid
     integer(c_int32_t) :: ndim = 3
@@ -555,6 +556,18 @@ module ndsmh_iface
       type(c_ptr), value :: B, Bp, A, Ap
       integer(c_int32_t), intent(in) :: n3(3)
       real(c_double), intent(in) :: dq3(3)
+      integer(c_int) :: rc
+    end function
+
+    ! ---- field lines and line integrals (trace.hip) ----
+    function ndsmk_trace(B, G, n3, lo3, dq3, nseeds, seeds, step, max_steps, direction, ends, length, integral, &
+                         status, nsteps) bind(c, name="ndsmk_trace") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_double
+      type(c_ptr), value :: B, G, seeds, ends, length, integral, status, nsteps
+      integer(c_int32_t), intent(in) :: n3(3)
+      real(c_double), intent(in) :: lo3(3), dq3(3)
+      integer(c_int), value :: nseeds, max_steps, direction
+      real(c_double), value :: step
       integer(c_int) :: rc
     end function
 

@@ -32,7 +32,7 @@ module ndsmh_vecpot
 
   public :: vecpot_solve, poisson_solve
   public :: vecpot_ctx, vecpot_ctx_create, vecpot_ctx_destroy, vecpot_ctx_matches, vecpot_run, vecpot_cache_drop
-  public :: vecpot_project, vecpot_devore
+  public :: vecpot_project, vecpot_devore, vecpot_trace
   public :: VP_POTENTIAL, VP_FIELD, VP_HELICITY
   ! pieces the distributed driver (ndsmh_wvecpot) shares with vecpot_solve
   public :: face_data, face_axis, face_upper, face_t1, face_t2, face_order, face_copy, vecpot_faces, say
@@ -1040,6 +1040,79 @@ contains
       rc = ndsmk_d2h(pAp, dAp, 3_c_size_t * nb); if (rc /= 0) return
     end if
     rc = ndsmk_sync()
+  end function
+
+  ! ------------------------------------------------------------------
+  ! Field lines of B from nseeds seeds, with the line integral of G along them, on a prepared context (DESIGN.md
+  ! "Field-line tracing and field-line helicity"; semantics in include/ndsm_hip.h).  The context supplies the mesh
+  ! only: first point and spacing per axis, dq as in vecpot_run.  pB, pG (pG may be c_null_ptr: integrals 0)
+  ! (nx,ny,nz,3), pseeds (3,nseeds) in; pends (3,nl), plen, pint (nl) doubles and pstat, pnst (nl) int32 out, nl =
+  ! nseeds or (direction 0) 2 nseeds: on the HOST (B, G and the seeds go up into the helicity entries' staging
+  ! arrays and a scratch buffer, the results come home) or (on_device) in HBM.  No solve, no hierarchy.
+  ! ------------------------------------------------------------------
+  function vecpot_trace(ctx, pB, pG, nseeds, pseeds, step, max_steps, direction, pends, plen, pint, pstat, pnst, &
+                        on_device) result(rc)
+    type(vecpot_ctx), intent(inout), target :: ctx
+    type(c_ptr), intent(in) :: pB, pG, pseeds, pends, plen, pint, pstat, pnst
+    integer(c_int), intent(in) :: nseeds, max_steps, direction
+    real(wp), intent(in) :: step
+    logical, intent(in) :: on_device
+    integer(c_int) :: rc, rc2
+    character(len=*), parameter :: me = "trace_field_lines"
+    real(wp) :: dq(3), lo(3)
+    integer(c_int32_t) :: n3(3)
+    integer(c_size_t) :: nb, nl, ns
+    integer :: i
+    type(c_ptr) :: dB, dG, d(6)
+
+    n3 = ctx%n3
+    dq = [ctx%qx(2) - ctx%qx(1), ctx%qy(2) - ctx%qy(1), ctx%qz(2) - ctx%qz(1)]      ! as vecpot_run
+    lo = [ctx%qx(1), ctx%qy(1), ctx%qz(1)]
+    if (on_device .or. nseeds <= 0 .or. step <= 0.0_wp .or. max_steps < 1 .or. abs(direction) > 1) then
+      ! (the argument errors are ndsmk_trace's to name; nothing is staged for them)
+      rc = ndsmk_trace(pB, pG, n3, lo, dq, nseeds, pseeds, step, max_steps, direction, pends, plen, pint, pstat, pnst)
+      if (rc /= 0) return
+      rc = ndsmk_sync()
+      return
+    end if
+    nb = int(product(int(n3, ik)), c_size_t) * 24_c_size_t
+    ns = int(nseeds, c_size_t)
+    nl = ns * merge(2_c_size_t, 1_c_size_t, direction == 0)
+    ! the helicity entries' host staging: dF(1) B, dF(2) G
+    do i = 1, merge(1, 2, .not. c_associated(pG))
+      if (.not. c_associated(ctx%dF(i))) then
+        rc = ndsmk_alloc(ctx%dF(i), nb); if (rc /= 0) return
+      end if
+    end do
+    dB = ctx%dF(1)
+    dG = c_null_ptr
+    rc = ndsmk_h2d(dB, pB, nb); if (rc /= 0) return
+    if (c_associated(pG)) then
+      dG = ctx%dF(2)
+      rc = ndsmk_h2d(dG, pG, nb); if (rc /= 0) return
+    end if
+    ! seeds, ends, length, integral, status, nsteps
+    d = c_null_ptr
+    rc = ndsmk_alloc(d(1), 24_c_size_t * ns)
+    if (rc == 0) rc = ndsmk_alloc(d(2), 24_c_size_t * nl)
+    if (rc == 0) rc = ndsmk_alloc(d(3), 8_c_size_t * nl)
+    if (rc == 0) rc = ndsmk_alloc(d(4), 8_c_size_t * nl)
+    if (rc == 0) rc = ndsmk_alloc(d(5), 4_c_size_t * nl)
+    if (rc == 0) rc = ndsmk_alloc(d(6), 4_c_size_t * nl)
+    if (rc == 0) rc = ndsmk_h2d(d(1), pseeds, 24_c_size_t * ns)
+    if (rc == 0) then
+      call say(me, "Tracing field lines...")
+      rc = ndsmk_trace(dB, dG, n3, lo, dq, nseeds, d(1), step, max_steps, direction, d(2), d(3), d(4), d(5), d(6))
+    end if
+    if (rc == 0) rc = ndsmk_d2h(pends, d(2), 24_c_size_t * nl)
+    if (rc == 0) rc = ndsmk_d2h(plen, d(3), 8_c_size_t * nl)
+    if (rc == 0) rc = ndsmk_d2h(pint, d(4), 8_c_size_t * nl)
+    if (rc == 0) rc = ndsmk_d2h(pstat, d(5), 4_c_size_t * nl)
+    if (rc == 0) rc = ndsmk_d2h(pnst, d(6), 4_c_size_t * nl)
+    if (rc == 0) rc = ndsmk_sync()
+    do i = 1, 6
+      if (c_associated(d(i))) rc2 = ndsmk_free(d(i))
+    end do
   end function
 
   ! B.n of face f (1..6) from the host field (extract_bn, :699-743)

@@ -81,6 +81,16 @@ int get_iopt_ngrids(void);   /* -> 9  in : cap on the number of grid levels, 0 =
                                           floor(log2(nmin/2)) (ndsm_vector_potential.f90:631-632) */
 int get_iopt_ncyc_out(void); /* -> 10 out: V-cycles used by the last solve that iterated */
 int get_ropt_dulast(void);   /* -> 3  out: du of its last V-cycle */
+/* Both are written by every call, never left from an earlier one: the first 3-D solve (A_x) always writes them, a
+ * later component only if it ran more than one V-cycle.  When no solve iterated - ioptc[get_iopt_ncycles()] <= 0 -
+ * they hold 0 and the largest finite double (Fortran HUGE, 1.797...e308: "no du was measured"), every solve counts
+ * as not converged (ioptc[3] = 1, all bits of get_iopt_fail3d() set) and A keeps the initial guess with the
+ * boundary values written into it.
+ * Negative counts: ndsm_vector_solve and the ndsm_hip_vecpot_* entries take a negative ms, ncycles or nmaxex as 0,
+ * as the reference's DO loops do (the slots themselves are returned as passed).  The additive solver handles are
+ * stricter: ndsm_hip_mg_create, ndsm_hip_mg_set_ms and ndsm_hip_world_create refuse a negative ms or nmax_exact with
+ * 9002; a negative nmax of ndsm_hip_mg_solve / ndsm_hip_world_solve runs no cycle, like 0 (returns 1, *ncycles = 0,
+ * *du_last = HUGE, u untouched). */
 int get_iopt_prec(void);     /* -> 11 in : 0 fp64 throughout (reference arithmetic); 1 mixed precision for the 3-D
                                           solves: fp64 residual + fp32 correction V-cycle on level 1 (BASELINE
                                           config[4]); where level 1 is too small for the fp32 kernels the

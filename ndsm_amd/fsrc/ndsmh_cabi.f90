@@ -407,6 +407,7 @@ contains
     handle = c_null_ptr
     rc = NDSMK_EARG
     if (ndim /= 2 .and. ndim /= 3) return
+    if (ms < 0 .or. nmax_exact < 0) return       ! (sweep counts: 0 is the least; the pipeline entries clamp instead)
     n3 = 1
     n3(1:ndim) = nshape(1:ndim)
     dummy = [0.0_wp, 1.0_wp]
@@ -463,6 +464,8 @@ contains
     integer(c_int), value :: ms
     integer(c_int) :: rc
     type(mg_solver), pointer :: s
+    rc = NDSMK_EARG
+    if (ms < 0) return
     call c_f_pointer(handle, s)
     s%ms = ms
     rc = 0
@@ -1074,6 +1077,8 @@ contains
     character(len=1) :: bc(6)
     integer :: d, i
     handle = c_null_ptr
+    rc = NDSMK_EARG
+    if (ms < 0 .or. nmax_exact < 0) return       ! (as ndsm_hip_mg_create)
     n3 = nshape
     call c_f_pointer(x, qx, [n3(1)])
     call c_f_pointer(y, qy, [n3(2)])

@@ -935,8 +935,9 @@ contains
   ! solve that has not converged yet enqueues one V-cycle + its metric on its own stream, then the metrics
   ! are collected.  Small problems (the six 2-D face solves of the vector potential) are dispatch latency
   ! and one host round trip per cycle when run one after the other; side by side the device overlaps them.
-  ! Each solve runs exactly the kernels mg_solve would have run for it, in the same order: same bits, same
-  ! cycle counts.  Solvers that would take mg_solve's mixed-precision path are not accepted.
+  ! Each solve runs exactly the kernels mg_solve's plain form would have run for it, in the same order: same bits,
+  ! same cycle counts (a solver mg_solve would run in tracked form: see below).  Solvers that would take mg_solve's
+  ! mixed-precision path are not accepted.
   ! Before the call: whatever the solves read (right-hand sides, initial guesses) was enqueued on the MAIN
   ! stream; after it the main stream has waited for every lane.
   function mg_solve_lanes(ss, vc_tol, nmax, du_last, ncycles, ierr) result(rc)
@@ -957,8 +958,10 @@ contains
     rc = NDSMK_EARG
     if (nl < 1 .or. nl > 6 .or. size(du_last) < nl .or. size(ncycles) < nl .or. size(ierr) < nl) return
     ! (a solver that mg_solve would run in its tracked form - metric inside the last sweep's launch, rotating
-    ! buffers - runs the plain form here: V-cycle, then the metric pass; the same bits, and the tracked form's
-    ! metric scratch is one per process)
+    ! buffers - runs the plain form here: V-cycle, then the metric pass; the tracked form's metric scratch is one
+    ! per process.  The same bits of u, and of max|du|; the MEAN metric is added in another order by the two forms,
+    ! so du_last may differ from mg_solve's in its last bits - by at most 2 g / (1 - g) relative, g = (N-1) 2^-53 /
+    ! (1 - (N-1) 2^-53), N the level-1 point count - and, should du fall that close to vc_tol, the cycle count.)
     do l = 1, nl
       if (mg_mixed_applies(ss(l)) .or. ss(l)%slab) return
     end do
@@ -983,8 +986,12 @@ contains
     ! been read and found wanting - not after the metrics of all lanes have been collected: a lane never waits for
     ! the host to finish its round with the others (round 3: six face solves at 128^2 went from ~0.40 to ~0.3 ms per
     ! cycle each).  The lanes are independent, so the order in which the host serves them changes nothing they compute.
+    ! No cycle at all is allowed (nmax < 1; the reference's `DO i = 1, nmax`, ndsm_poisson.f90:116, runs nothing for
+    ! a zero or negative count): nothing is enqueued, every u stays as passed, du_last = huge, ierr = 1.
     itl = 0
+    if (nmax < 1) active = .false.
     do l = 1, nl
+      if (.not. active(l)) cycle
       rc = enqueue_cycle(l, 1); if (rc /= 0) goto 800
     end do
     do while (any(active(1:nl)))

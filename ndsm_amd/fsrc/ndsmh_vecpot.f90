@@ -221,8 +221,8 @@ contains
       fshape = [int(fc(f)%n1, c_int32_t), int(fc(f)%n2, c_int32_t), 1_c_int32_t]
       rc = mg_create(s2(f), 2, fshape, qa, qb, qb, bc2, int(iopt(IOPT_NGRIDS))); live2(f) = .true.
       if (rc /= 0) goto 900
-      s2(f)%ms = int(iopt(IOPT_MS)); s2(f)%ex_tol = ropt(ROPT_CTOL); s2(f)%use_max = (iopt(IOPT_DUMAX) == 1)
-      s2(f)%nmax_exact = int(iopt(IOPT_NMAXEX))
+      s2(f)%ms = max(0, int(iopt(IOPT_MS))); s2(f)%ex_tol = ropt(ROPT_CTOL); s2(f)%use_max = (iopt(IOPT_DUMAX) == 1)
+      s2(f)%nmax_exact = max(0, int(iopt(IOPT_NMAXEX)))
       fc(f)%chi = 0
       fc(f)%bn = fc(f)%bn - phi(f) / area(f)
       rc = mg_set_u(s2(f), c_loc(fc(f)%chi)); if (rc /= 0) goto 900
@@ -694,8 +694,8 @@ contains
         ierr2d = 0
         do f = 1, 6
           associate (s2 => ctx%s2(f))
-            s2%ms = int(iopt(IOPT_MS)); s2%ex_tol = ropt(ROPT_CTOL); s2%use_max = use_max
-            s2%nmax_exact = int(iopt(IOPT_NMAXEX))
+            s2%ms = max(0, int(iopt(IOPT_MS))); s2%ex_tol = ropt(ROPT_CTOL); s2%use_max = use_max
+            s2%nmax_exact = max(0, int(iopt(IOPT_NMAXEX)))
             rhs2 = mg_level_ptr(s2, 1, MG_BUF_RHS, cnt)
             u2 = mg_level_ptr(s2, 1, MG_BUF_U, cnt)
             rc = ndsmk_face_rhs(ctx%dbn, n3, int(f - 1, c_int), ctx%dphi, area(f), rhs2); if (rc /= 0) return
@@ -789,7 +789,7 @@ contains
       integer, intent(in) :: c
       integer(c_int) :: rc
       integer :: i, f
-      s3%ex_tol = ropt(ROPT_CTOL); s3%use_max = use_max; s3%nmax_exact = int(iopt(IOPT_NMAXEX))
+      s3%ex_tol = ropt(ROPT_CTOL); s3%use_max = use_max; s3%nmax_exact = max(0, int(iopt(IOPT_NMAXEX)))
       s3%precision = int(iopt(IOPT_PREC))
       ! initial guess of component c -> the solver's level-1 array
       u3 = mg_level_ptr(s3, 1, MG_BUF_U, cnt)
@@ -829,7 +829,7 @@ contains
       bc3 = 'D'
       bc3(c) = 'N'; bc3(3 + c) = 'N'                        ! :655,:671,:687
       rc = mg_set_bcs(s3, bc3); if (rc /= 0) return
-      s3%ms = merge(5, int(iopt(IOPT_MS)), c == 3)          ! Q2
+      s3%ms = merge(5, max(0, int(iopt(IOPT_MS))), c == 3)          ! Q2
       rc = mg_reset_info(s3)
     end function
 
@@ -936,8 +936,8 @@ contains
       rc = ndsmk_h2d(dB, pB, 3_c_size_t * nb); if (rc /= 0) return
     end if
     associate (s => ctx%sp)
-      s%ms = int(iopt(IOPT_MS)); s%ex_tol = ropt(ROPT_CTOL); s%use_max = (iopt(IOPT_DUMAX) == 1)
-      s%nmax_exact = int(iopt(IOPT_NMAXEX))
+      s%ms = max(0, int(iopt(IOPT_MS))); s%ex_tol = ropt(ROPT_CTOL); s%use_max = (iopt(IOPT_DUMAX) == 1)
+      s%nmax_exact = max(0, int(iopt(IOPT_NMAXEX)))
       s%precision = 0
       call say(me, "Divergence...")
       rhs1 = mg_level_ptr(s, 1, MG_BUF_RHS, cnt)

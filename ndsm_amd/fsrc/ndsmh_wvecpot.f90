@@ -217,8 +217,8 @@ contains
       bc3(c) = 'N'; bc3(3 + c) = 'N'                        ! :655,:671,:687
       rc = world_create(w, n3, qx, qy, qz, bc3, ngr, nranks, rank); livew = .true.
       if (rc /= 0) goto 900
-      call world_set_params(w, merge(5, int(iopt(IOPT_MS)), c == 3), ropt(ROPT_CTOL), iopt(IOPT_DUMAX) == 1, &
-                            int(iopt(IOPT_NMAXEX)))          ! Q2
+      call world_set_params(w, merge(5, max(0, int(iopt(IOPT_MS))), c == 3), ropt(ROPT_CTOL), iopt(IOPT_DUMAX) == 1, &
+                            max(0, int(iopt(IOPT_NMAXEX))))          ! Q2
       if (iopt(IOPT_PREC) /= 0) then                       ! fp32 correction cycle where the slabs allow it
         if (.not. world_set_precision(w, int(iopt(IOPT_PREC)))) continue
       end if

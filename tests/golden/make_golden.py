@@ -30,8 +30,11 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np  # noqa: E402
 
 from golden_inputs import (BCS3, BCS_ANISO, BCS_RANDOM, analytic_case, aniso_mesh, aniso_pipeline_cases,  # noqa: E402
-                           digest, manufactured_poisson, quirk_case, rand_field, random_reference_cases,
-                           ANISO_SHAPE_2D, ANISO_SHAPES_3D, KERNEL_SHAPES_3D, KERNEL_SHAPES_2D)
+                           digest, digest16, manufactured_poisson, negative_option_cases, noisy_case, option_matrix,
+                           pipeline_option_cases, quirk_case, rand_field, random_reference_cases, scalar_kw,
+                           scalar_option_problems, zero_field_cases,
+                           ANISO_SHAPE_2D, ANISO_SHAPES_3D, KERNEL_SHAPES_3D, KERNEL_SHAPES_2D, OPTION_PIPELINE_SHAPE,
+                           OPTION_SCALAR_3D)
 from oracle import Oracle, have_ref, uniform_mesh  # noqa: E402
 
 
@@ -248,7 +251,49 @@ def aniso(R):
         ierr, A, B, ioptc, ropt = R.vector_potential(x, y, z, b)
         np.savez_compressed(os.path.join(HERE, f"pipeline_aniso_{name}.npz"), A=A, B=B, ioptc=ioptc)
     print("wrote reference_aniso*, pipeline_aniso_*")
+    options(R)
+
+
+def options(R):
+    """test_oracle.py's option checks (edge values of ms, ncycles, nmaxex, the tolerances and the metric; negative
+    values; an all-zero field): reference_options.json holds numbers only - per case what the call returned (ierr,
+    the ioptc it left, du_last where the entry returns one) and digest16 of the arrays.  The case lists are
+    golden_inputs' (pipeline_option_cases, negative_option_cases, zero_field_cases, scalar_option_problems x
+    option_matrix), in their order."""
+    def pipe(x, y, z, b, kw):
+        ierr, A, B, ioptc, _ropt = R.vector_potential(x, y, z, b, **kw)
+        assert np.isfinite(A).all() and np.isfinite(B).all(), kw
+        return [int(ierr), [int(v) for v in ioptc], digest16(A), digest16(B)]
+
+    def scalar(u, rhs, mesh, bcs, kw):
+        ierr, us, du = R.solve_bvp(u, rhs, mesh, bcs, **kw)
+        assert np.isfinite(us).all(), (bcs, kw)
+        return [int(ierr), float(du), digest16(us)]
+
+    out = {}
+    x, y, z, b = noisy_case(OPTION_PIPELINE_SHAPE)
+    out["pipeline"] = [pipe(x, y, z, b, kw) for kw in pipeline_option_cases()]
+    out["pipeline_negative"] = [pipe(x, y, z, b, kw) for kw in negative_option_cases()]
+    out["pipeline_zero_field"] = [pipe(x, y, z, np.zeros_like(b), kw) for kw in zero_field_cases()]
+    out["scalar"] = {}
+    for name, ns, mesh, bcs, u, rhs in scalar_option_problems():
+        out["scalar"][name] = [scalar(u, rhs, mesh, bcs, scalar_kw(*t)) for t in option_matrix()]
+    name, ns, mesh, bcs, u, rhs = next(iter(scalar_option_problems()))
+    assert ns == OPTION_SCALAR_3D
+    out["scalar_negative"] = [scalar(u, rhs, mesh, bcs, kw) for kw in (
+        dict(ms=-1, nmax=3), dict(nmax=-2), dict(nmax_exact=-3, nmax=3), dict(vc_tol=-1.0, nmax=3),
+        dict(ex_tol=-1.0, nmax=3, nmax_exact=50), dict(vc_tol=float("nan"), nmax=3))]
+    z0 = np.zeros_like(u)
+    out["scalar_zero_field"] = [scalar(z0, z0, mesh, bcs, dict(vc_tol=vt, nmax=3)) for vt in (0.0, 1e-10)]
+    with open(os.path.join(HERE, "reference_options.json"), "w") as fh:
+        json.dump(out, fh, separators=(",", ":"), sort_keys=True)
+        fh.write("\n")
+    print("wrote reference_options.json")
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["options"]:         # only reference_options.json
+        assert have_ref(), "build the reference first: make -C oracle ref"
+        options(Oracle("ref"))
+    else:
+        main()

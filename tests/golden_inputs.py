@@ -141,3 +141,70 @@ def digest(a):
     """sha256 of an array's float64 bytes (C order, little-endian): equal digests <=> bit-identical arrays"""
     import hashlib
     return hashlib.sha256(np.ascontiguousarray(a, dtype="<f8").tobytes()).hexdigest()
+
+
+# ---- edge values of the solver options (tests/golden/reference_options.json, test_oracle.py, test_gpu_options.py) ----
+OPTION_PIPELINE_SHAPE = [24, 20, 18]
+OPTION_MS = (0, 1, 6, 7, 11)            # 2 ms post-smoothing sweeps: 0, 2, 12, 14, 22
+OPTION_NCYC = (0, 1, 3)
+OPTION_NEX = (0, 1, 10000)
+OPTION_SCALAR_3D = [17, 23, 19]
+OPTION_SCALAR_2D = [27, 36]
+HUGE = float(np.finfo(np.float64).max)  # du_last of a solve that ran no V-cycle (Fortran HUGE)
+
+
+def noisy_case(ns):
+    """analytic_case plus seeded noise, so that all three component solves iterate: x, y, z, b"""
+    x, y, z, _A1, b1 = analytic_case(ns)
+    return x, y, z, b1 + 0.05 * np.random.default_rng(5).standard_normal(b1.shape)
+
+
+def option_matrix():
+    """the full product (ms, ncycles, nmaxex, mean) of the edge values: 90 tuples"""
+    return [(ms, nc, nex, mean) for ms in OPTION_MS for nc in OPTION_NCYC for nex in OPTION_NEX
+            for mean in (False, True)]
+
+
+def pipeline_option_cases():
+    """keyword sets of vector_potential for the option matrix on noisy_case: the product, then zero tolerances and
+    loose ones with the mean metric (93)"""
+    kws = [dict(ms=ms, ncycles_max=nc, niterex_max=nex, mean=mean) for ms, nc, nex, mean in option_matrix()]
+    kws.append(dict(ms=5, ncycles_max=3, vc_tol=0.0))
+    kws.append(dict(ncycles_max=40, niterex_max=50, ex_tol=0.0, mean=True))
+    kws.append(dict(ms=2, ncycles_max=5, niterex_max=2, vc_tol=1e-3, ex_tol=1e-2, mean=True))
+    return kws
+
+
+def negative_option_cases():
+    """keyword sets with negative (and one NaN) option values: the reference takes a negative count as 0"""
+    return [dict(ms=-1, ncycles_max=3), dict(ncycles_max=-2), dict(niterex_max=-3, ncycles_max=3),
+            dict(vc_tol=-1.0, ncycles_max=3), dict(ex_tol=-1.0, ncycles_max=3, niterex_max=50),
+            dict(vc_tol=float("nan"), ncycles_max=3),
+            dict(ms=-1, ncycles_max=-2, niterex_max=-3, vc_tol=-1.0, ex_tol=-1.0)]
+
+
+def zero_field_cases():
+    """keyword sets for an all-zero field: du = 0 < vc_tol is strict, so vc_tol = 0 never converges"""
+    return [dict(vc_tol=0.0, ncycles_max=3), dict(vc_tol=1e-10, ncycles_max=3)]
+
+
+def scalar_option_problems():
+    """(name, ns, mesh, bcs, u, rhs) of the scalar-solve option matrix: 17x23x19 and 27x36 (2-D), uniform and
+    aniso_mesh, the three component sets plus all-Neumann (rhs made compatible by subtracting its mean)"""
+    for ns, bcsets in ((OPTION_SCALAR_3D, BCS3 + ("NNNNNN",)), (OPTION_SCALAR_2D, ("NNNN", "DNND"))):
+        shp = tuple(ns[::-1])
+        u, rhs = rand_field(shp, 2112), rand_field(shp, 2113)
+        for mname, meshf in (("uniform", uniform_mesh), ("aniso", aniso_mesh)):
+            for bcs in bcsets:
+                r = rhs - rhs.mean() if set(bcs) == {"N"} else rhs
+                yield "%s_%s_%s" % ("x".join(str(n) for n in ns), mname, bcs), ns, meshf(ns), bcs, u, r
+
+
+def scalar_kw(ms, nc, nex, mean):
+    """option_matrix tuple -> keywords of Oracle.solve_bvp"""
+    return dict(ms=ms, nmax=nc, nmax_exact=nex, du_max=not mean)
+
+
+def digest16(a):
+    """the first 16 hex digits of digest(a): 64 bits tell bit-identical arrays apart and keep the fixtures small"""
+    return digest(a)[:16]

@@ -146,6 +146,10 @@ def test_distributed_vector_potential_bitwise(hip, tmp_path, world):
         {"ns": [33, 30, 45], "noise": 5, "guess": 6, "kw": {"ms": 3, "mean": True}},
         {"ns": [64, 48, 96], "noise": 7, "kw": {"ncycles_max": 3}},
         {"ns": [64, 64, 96], "kw": {"mixed_precision": 2}},
+        # edge values of the options: no V-cycle at all, no sweeps, 14 post-smoothing sweeps
+        {"ns": [40, 36, 48], "noise": 5, "kw": {"ncycles_max": 0}},
+        {"ns": [40, 36, 48], "noise": 5, "kw": {"ms": 0, "ncycles_max": 3}},
+        {"ns": [40, 36, 48], "noise": 5, "kw": {"ms": 7, "ncycles_max": 3}},
     ]
     out = _run_world(tmp_path, world, cases, worker="multirank_vecpot_worker.py")
     for ci, c in enumerate(cases):

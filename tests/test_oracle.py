@@ -17,9 +17,11 @@ import os
 import numpy as np
 import pytest
 
-from golden_inputs import (ANISO_SHAPE_2D, ANISO_SHAPES_3D, BCS3, BCS_ANISO, BCS_RANDOM, KERNEL_SHAPES_2D,
-                           KERNEL_SHAPES_3D, analytic_case, aniso_case, aniso_mesh, aniso_pipeline_cases, digest,
-                           manufactured_poisson, quirk_case, rand_field, random_reference_cases, uniform_mesh)
+from golden_inputs import (ANISO_SHAPE_2D, ANISO_SHAPES_3D, BCS3, BCS_ANISO, BCS_RANDOM, HUGE, KERNEL_SHAPES_2D,
+                           KERNEL_SHAPES_3D, OPTION_PIPELINE_SHAPE, analytic_case, aniso_case, aniso_mesh,
+                           aniso_pipeline_cases, digest, digest16, manufactured_poisson, negative_option_cases,
+                           noisy_case, option_matrix, pipeline_option_cases, quirk_case, rand_field,
+                           random_reference_cases, scalar_kw, scalar_option_problems, uniform_mesh, zero_field_cases)
 
 
 def _tag(ns):
@@ -231,3 +233,84 @@ def test_quirk_ierr_is_the_last_face_solve(port, golden_dir):
     x, y, z, A1, b1 = analytic_case(24)
     assert want["analytic"]["ierr"] == 1
     assert port.vector_potential(x, y, z, b1, ncycles_max=2)[0] == 1
+
+
+# ---- edge values of the options: the port against what the reference returned (reference_options.json) ----
+# Exact: the reference ran on one thread, and the port adds the all-Neumann mean in that serial order on any number.
+
+@pytest.fixture(scope="module")
+def ref_options(golden_dir):
+    return json.load(open(os.path.join(golden_dir, "reference_options.json")))
+
+
+def _pipe_row(port, x, y, z, b, kw):
+    ierr, A, B, ioptc, _ropt = port.vector_potential(x, y, z, b, **kw)
+    assert np.isfinite(A).all() and np.isfinite(B).all(), kw
+    return [int(ierr), [int(v) for v in ioptc], digest16(A), digest16(B)]
+
+
+@pytest.mark.parametrize("group,cases,zero", (("pipeline", pipeline_option_cases, False),
+                                              ("pipeline_negative", negative_option_cases, False),
+                                              ("pipeline_zero_field", zero_field_cases, True)),
+                         ids=("matrix", "negative", "zero_field"))
+def test_pipeline_options_reference(port, ref_options, group, cases, zero):
+    """ndsm_vector_solve on the option matrix (ms 0 ... 11, no V-cycle, no coarsest-grid sweep, zero tolerances, both
+    metrics), with negative values and on an all-zero field: ierr, the whole ioptc and the bits of A and B"""
+    x, y, z, b = noisy_case(OPTION_PIPELINE_SHAPE)
+    if zero:
+        b = np.zeros_like(b)
+    kws = cases()
+    want = ref_options[group]
+    assert len(kws) == len(want)
+    for kw, w in zip(kws, want):
+        assert _pipe_row(port, x, y, z, b, kw) == w, kw
+    if group == "pipeline":
+        assert len(kws) == 93
+        # no cycle at all: whatever ms and the coarsest-grid count, the same A and B
+        same = {tuple(w[2:]) for kw, w in zip(kws, want) if kw.get("ncycles_max") == 0}
+        assert len(same) == 1
+    if group == "pipeline_zero_field":
+        assert [w[0] for w in want] == [1, 0]          # du = 0 < vc_tol is strict
+
+
+def _scalar_row(port, u, rhs, mesh, bcs, kw):
+    ierr, us, du, _h, nc, _sw = port.solve_bvp(u, rhs, mesh, bcs, **kw)
+    assert np.isfinite(us).all(), (bcs, kw)
+    return [int(ierr), float(du), digest16(us)], nc, us
+
+
+@pytest.mark.parametrize("case", list(scalar_option_problems()), ids=lambda c: c[0])
+def test_scalar_options_reference(port, ref_options, case):
+    """solve_poisson_bvp on the option matrix, 3-D and 2-D, uniform and unequal spacings, the component letter
+    sets and all-Neumann: ierr, du_last and the bits of u; without a V-cycle u comes back as passed"""
+    name, ns, mesh, bcs, u, rhs = case
+    want = ref_options["scalar"][name]
+    opts = option_matrix()
+    assert len(opts) == len(want) == 90
+    for t, w in zip(opts, want):
+        row, nc, us = _scalar_row(port, u, rhs, mesh, bcs, scalar_kw(*t))
+        assert row == w, (name, t)
+        assert nc <= t[1]
+        if t[1] == 0:
+            assert row[:2] == [1, HUGE] and nc == 0 and np.array_equal(us, u), (name, t)
+
+
+def test_scalar_options_reference_negative_and_zero_field(port, ref_options):
+    """negative counts behave as 0 (no sweeps, no cycles, no coarsest-grid sweeps), a negative or NaN vc_tol never
+    converges; an all-zero problem: du = 0 misses vc_tol = 0 after all three cycles, meets 1e-10 after one"""
+    name, ns, mesh, bcs, u, rhs = next(iter(scalar_option_problems()))
+    kws = (dict(ms=-1, nmax=3), dict(nmax=-2), dict(nmax_exact=-3, nmax=3), dict(vc_tol=-1.0, nmax=3),
+           dict(ex_tol=-1.0, nmax=3, nmax_exact=50), dict(vc_tol=float("nan"), nmax=3))
+    want = ref_options["scalar_negative"]
+    assert len(kws) == len(want)
+    for kw, w in zip(kws, want):
+        row, nc, us = _scalar_row(port, u, rhs, mesh, bcs, kw)
+        assert row == w, kw
+        for key, zero in (("ms", "ms"), ("nmax", "nmax"), ("nmax_exact", "nmax_exact")):
+            if kw.get(key, 0) < 0:                     # ... and is what 0 gives
+                row0, nc0, us0 = _scalar_row(port, u, rhs, mesh, bcs, dict(kw, **{key: 0}))
+                assert row0 == row and nc0 == nc, kw
+    z0 = np.zeros_like(u)
+    for vt, w, nc_want in zip((0.0, 1e-10), ref_options["scalar_zero_field"], (3, 1)):
+        row, nc, us = _scalar_row(port, z0, z0, mesh, bcs, dict(vc_tol=vt, nmax=3))
+        assert row == w and nc == nc_want and row[1] == 0.0 and row[0] == (1 if vt == 0.0 else 0), vt

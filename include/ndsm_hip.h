@@ -329,6 +329,74 @@ int ndsm_hip_vecpot_trace_device(void *h, const double *dB, const double *dG, in
                                  double step, int max_steps, int direction, double *dends, double *dlength,
                                  double *dintegral, int32_t *dstatus, int32_t *dnsteps);
 
+/* ---- Squashing factor Q and twist number along the same lines (DESIGN.md "Squashing factor and twist") -------------
+ * Q of Titov (2007) at each seed - large where the field-line mapping between the two feet of the line is strongly
+ * distorted (quasi-separatrix layers) - by the method of Scott, Pontin & Hornig (2017): two deviation vectors U, V
+ * are integrated along the line with the gradient of B, so Q at ANY point of the volume comes from the one line
+ * through it, no neighbour lines and no offset.  With G = curl B and integrand 1 the two integrals add up to 4 pi T_w,
+ * T_w = (1 / 4 pi) int (curl B).B / |B|^2 dl the twist number (Berger & Prior 2006; Liu et al. 2016).
+ * Everything not said here is as in the trace entries above: lo, h, hi, the clamped cell with unclamped fractions,
+ * the order of the interpolation, ds = step * min(h), the status codes NDSM_HIP_TRACE_*, max_steps (clamped to 2^24;
+ * every line ends after at most max_steps steps), a seed outside or not finite (NDSM_HIP_TRACE_OUTSIDE), fp64 + - * /
+ * and sqrt only, in the operand order written here, no contraction.  Always both directions (Q needs both feet):
+ * line i (forward) and line nseeds + i (backward) belong to seed i.
+ *   B, G       (nx,ny,nz,3); G may be NULL (every integral is 0)
+ *   integrand  0: dI/ds = G.B/|B| (as trace); 1: dI/ds = G.B/|B|^2 = ((Gx ex + Gy ey) + Gz ez) / |B|.
+ *              G == B (the same pointer) with integrand 1 asks for the twist map: G is then curl_h B, formed on the
+ *              device in the handle's scratch (24 B/pt) by the differences of the library's other curls (centred,
+ *              3-point one-sided on the end planes; n_d >= 3), J and B interpolated separately - exact for a linear
+ *              field.  (G = B itself would integrate 1: the length.)
+ *   out        q (nseeds); ends (3,2 nseeds), length, integral (2 nseeds) doubles; status, nsteps (2 nseeds) int32
+ * Semantics:
+ *   gradient   M_cd = dB_c/dx_d is the exact derivative of the trilinear interpolant in the clamped cell of the stage
+ *              point, from the same 8 corners per component v0 .. v7 (x fastest): with d00 = v1 - v0, d10 = v3 - v2,
+ *              d01 = v5 - v4, d11 = v7 - v6, c00 = v0 + fx d00, c10 = v2 + fx d10, c01 = v4 + fx d01,
+ *              c11 = v6 + fx d11, e0 = c10 - c00, e1 = c11 - c01, c0 = c00 + fy e0, c1 = c01 + fy e1, dz = c1 - c0
+ *              (the value is c0 + fz dz, the bits of the trace entries' interpolation):
+ *              d/dx = (dx0 + fz (dx1 - dx0)) / h_x with dx0 = d00 + fy (d10 - d00), dx1 = d01 + fy (d11 - d01);
+ *              d/dy = (e0 + fz (e1 - e0)) / h_y;  d/dz = dz / h_z.  A field linear in x, y, z gets its exact gradient.
+ *   ODE        per direction sgn = +1 / -1, state (r, U, V, I), m = |B(r)|: dr/ds = sgn B/m,
+ *              dU_c/ds = sgn (((M_c0 U_0 + M_c1 U_1) + M_c2 U_2) / m), V likewise, dI/ds = the integrand (no sgn, as
+ *              trace).  Classical RK4 with trace's weights for all ten components, the sum ((k1 + 2 k2) + 2 k3) + k4
+ *              formed in this order; U and V of a stage are advanced with that stage's own M and m.
+ *   start      e = B/m at the seed; a = the unit vector of the axis of the smallest |e_d| (x before y before z on a
+ *              tie); w = a - (a.e) e, U0 = w / sqrt((w_x w_x + w_y w_y) + w_z w_z), V0 = e x U0 =
+ *              (e_y U0_z - e_z U0_y, e_z U0_x - e_x U0_z, e_x U0_y - e_y U0_x).  Both directions start from the same
+ *              U0, V0.  A seed where |B| is not > 0 is NDSM_HIP_TRACE_NULL in both directions.
+ *   exit       as trace: the step whose end r' is outside is not accepted, the face and the chord fraction t are
+ *              found the same way and the step is REDONE from r with s = t ds (stage 1 reused).  Then two
+ *              refinements, always two: s <- s (face - r_ax) / (r'_ax - r_ax) with the r' of the redone step, and the
+ *              step is redone again with the new s; a refinement is skipped when r'_ax == r_ax (a seed on a face
+ *              whose line leaves at once has s = 0: its end is the seed, U, V are U0, V0, nsteps = 1).  Then the
+ *              normal coordinate is set to the face's value and the other two are clamped, as trace; length += the
+ *              last s.  Without the refinements the end misses the face by O(kappa ds^2) and Q of lines that end on a
+ *              side face converges at between first and second order only.  THE END POINTS THEREFORE DIFFER FROM
+ *              THOSE OF THE TRACE ENTRIES in the last digits of O(kappa ds^2), as do length and integral of the
+ *              exit step.
+ *   Q          at each end, on its face (axis ax), with B_e the interpolated B at the end point:
+ *              Ut = U - (U_ax / B_e,ax) B_e, Vt likewise, b_n = |B_e,ax|.  With F, B the forward and backward ends and
+ *              |B_s|^2 = (Bx Bx + By By) + Bz Bz of the interpolated field at the seed,
+ *              Q = (((Ut_F.Ut_F)(Vt_B.Vt_B) + (Ut_B.Ut_B)(Vt_F.Vt_F)) - 2 ((Ut_F.Vt_F)(Ut_B.Vt_B))) * b_n,F * b_n,B
+ *                  / |B_s|^2, every dot product as (x x + y y) + z z.
+ *              Not clamped to >= 2: a caller sees the integration error instead of a floor.  Q = NaN unless both
+ *              directions ended on a face, and when b_n is not > 0 at an end.  Q depends on the faces' geometry: a
+ *              uniform field gives 2 between opposite faces and |B|^2 / |B_a B_c| between faces normal to different
+ *              axes a and c.
+ * Each seed depends on itself only: the same bits whatever the number of seeds or their order.
+ * Returns 0, or >= 9001 errors: 9001 without a GPU whatever the arguments; 9002 a NULL handle or, with nseeds > 0,
+ * a NULL B, seeds or output array; 9004 step <= 0 or not finite, max_steps < 1, an integrand other than 0, 1,
+ * nseeds < 0.  nseeds == 0 succeeds and touches nothing.  On failure the host entry clears the nseeds entries of q
+ * and the 2 nseeds entries of its other outputs; the device entry leaves its device arrays.
+ * Device memory: the host entry stages B and G in the handle's scratch (24 B/pt each). */
+/* HOST arrays */
+int ndsm_hip_vecpot_squash(void *h, const double *B, const double *G, int integrand, int nseeds, const double *seeds,
+                           double step, int max_steps, double *q, double *ends, double *length, double *integral,
+                           int32_t *status, int32_t *nsteps);
+/* the same on DEVICE arrays of the library's GPU (seeds and the six outputs too) */
+int ndsm_hip_vecpot_squash_device(void *h, const double *dB, const double *dG, int integrand, int nseeds,
+                                  const double *dseeds, double step, int max_steps, double *dq, double *dends,
+                                  double *dlength, double *dintegral, int32_t *dstatus, int32_t *dnsteps);
+
 /* =====================================================================
  * PART 3 - additive exports, multi-GPU
  *

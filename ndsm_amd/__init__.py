@@ -10,8 +10,9 @@ from .ndsm import vector_potential, vector_potential_slab, get_lib_path  # noqa:
 from ._lib import (load_library, lib_path, MGSolver, VecPot, World, slab_plan, poisson_solve,  # noqa: F401
                    NdsmHipError, Helicity, vector_potential_field, relative_helicity, Projection,
                    solenoidal_projection, devore_potentials, FieldLines, trace_field_lines,
-                   field_line_helicity)
+                   field_line_helicity, QMap, squashing_factor, seed_plane)
 
 __all__ = ["vector_potential", "vector_potential_slab", "get_lib_path", "load_library", "lib_path", "MGSolver", "VecPot", "poisson_solve",
            "NdsmHipError", "Helicity", "vector_potential_field", "relative_helicity", "Projection", "solenoidal_projection",
-           "devore_potentials", "FieldLines", "trace_field_lines", "field_line_helicity"]
+           "devore_potentials", "FieldLines", "trace_field_lines", "field_line_helicity", "QMap",
+           "squashing_factor", "seed_plane"]

@@ -243,6 +243,9 @@ class VecPot:
         _tr = [ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5
         self.L.ndsm_hip_vecpot_trace.argtypes = [ctypes.c_void_p] * 3 + _tr
         self.L.ndsm_hip_vecpot_trace_device.argtypes = [ctypes.c_void_p] * 3 + _tr
+        _sq = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_int] + [ctypes.c_void_p] * 6
+        self.L.ndsm_hip_vecpot_squash.argtypes = [ctypes.c_void_p] * 3 + _sq
+        self.L.ndsm_hip_vecpot_squash_device.argtypes = [ctypes.c_void_p] * 3 + _sq
         self.last_projection = None
         self.L.ndsm_hip_device_alloc.argtypes = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
         self.L.ndsm_hip_device_free.argtypes = [ctypes.c_void_p]
@@ -520,6 +523,53 @@ class VecPot:
             raise NdsmHipError(f"trace: {len(S)} seeds, at most {TRACE_MAX_SEEDS} per call (code 9002)")
         return np.ascontiguousarray(S).copy()
 
+    def squashing(self, b, seeds, g=None, integrand=0, twist=False, step=0.5, max_steps=None, device=False):
+        """Squashing factor Q (Titov 2007) of b (3,nz,ny,nx) at seeds (nseeds,3; anywhere in the box), on the device,
+        from the one field line through each seed: two deviation vectors are integrated along it with the gradient
+        of the trilinear interpolant (Scott, Pontin & Hornig 2017; semantics: include/ndsm_hip.h,
+        ndsm_hip_vecpot_squash).  Lines, step and max_steps as trace(), always both directions; the end points differ
+        from trace()'s in the last digits (the exit step is refined twice).  g (3,nz,ny,nx; None: zeros) is integrated
+        along the lines, integrand 0: g.b/|b| (as trace), 1: g.b/|b|^2.  twist=True (not together with g): g =
+        curl_h b is formed on the device, integrand 1, and twist = (integral[0] + integral[1]) / (4 pi) is the twist
+        number T_w of the whole line.  Returns a QMap tuple: q (nseeds; NaN unless both directions ended on a face),
+        twist (nseeds, NaN where q is; None without twist=True), ends (2,nseeds,3), length, integral (2,nseeds),
+        status, nsteps (2,nseeds; int32), row 0 forward, row 1 backward.  Q is not clamped to >= 2 and depends on
+        the faces the line ends on: 2 for a uniform field between opposite faces, |b|^2 / |b_a b_c| between faces
+        normal to different axes a, c.  device=True: the arrays are staged in device memory and the device-resident
+        entry point runs."""
+        if integrand not in (0, 1) or isinstance(integrand, bool):
+            raise ValueError(f"integrand must be 0 or 1, not {integrand!r}")
+        if twist and g is not None:
+            raise ValueError("twist=True forms g = curl b itself: give g or twist, not both")
+        _d0, step, max_steps = self._trace_args(step, max_steps, "both")
+        B = self._field_arg(b, "squashing")
+        G = None if g is None else self._field_arg(g, "squashing")
+        S = self._seeds_arg(seeds)
+        out = [np.zeros(len(S))] + _trace_outputs(len(S), 0)
+        if len(S) == 0:
+            return _qmap(out, twist)
+        if twist:
+            integrand = 1
+        if not device:
+            # (the field passed as its own g with integrand 1 asks the library for g = curl b)
+            pG = B.ctypes.data if twist else (None if G is None else G.ctypes.data)
+            ierr = self.L.ndsm_hip_vecpot_squash(self.h, B.ctypes.data, pG, integrand, len(S), S.ctypes.data, step,
+                                                 max_steps, *[a.ctypes.data for a in out])
+        else:
+            arrays = [B, S] + out + ([G] if G is not None else [])
+            ierr = self._on_device(arrays, lambda dB, dS, d0, d1, d2, d3, d4, d5, dG=None:
+                                   self.L.ndsm_hip_vecpot_squash_device(self.h, dB, dB if twist else dG, integrand,
+                                                                        len(S), dS, step, max_steps, d0, d1, d2, d3,
+                                                                        d4, d5))
+        _check(ierr, "ndsm_hip_vecpot_squash", self.L)
+        return _qmap(out, twist)
+
+    def seed_plane(self, axis, value, n1, n2):
+        """the (n1 n2, 3) seeds of a mesh-aligned cut through the handle's box: coordinate `axis` (0, 1, 2 = x, y, z)
+        fixed at `value`, the other two (in the order x, y, z; the first of them fastest) n1 and n2 equally spaced
+        points from face to face"""
+        return seed_plane(self.x, self.y, self.z, axis, value, n1, n2)
+
     def field_line_helicity(self, b, seeds, gauge="devore", a=None, step=0.5, max_steps=None, direction="both",
                             niterex_max=10000, ncycles_max=1024, ex_tol=1e-13, vc_tol=1e-10, ms=5, mean=False,
                             mixed_precision=False, flxcrl=False, return_fields=False):
@@ -644,6 +694,39 @@ def _field_lines(out, direction):
     return FieldLines(*out, out[2][0] + out[2][1] if direction == 0 else None)
 
 
+QMap = collections.namedtuple("QMap", ["q", "twist", "ends", "length", "integral", "status", "nsteps"])
+
+
+def _qmap(out, twist):
+    """a QMap from [q, ends, length, integral, status, nsteps]; twist = (I_fwd + I_bwd) / 4 pi, NaN where q is"""
+    tw = None
+    if twist:
+        tw = np.where(np.isnan(out[0]), np.nan, (out[3][0] + out[3][1]) / (4.0 * np.pi))
+    return QMap(out[0], tw, *out[1:])
+
+
+def seed_plane(x, y, z, axis, value, n1, n2):
+    """the (n1 n2, 3) seeds of a cut through the box of the mesh x, y, z normal to `axis` (0, 1, 2) at `value`: n1 by
+    n2 equally spaced points from face to face along the other two axes (in the order x, y, z; the first of them
+    fastest), the box as the library forms it (lo = q[0], hi = lo + (n - 1) (q[1] - q[0]))"""
+    if axis not in (0, 1, 2) or isinstance(axis, bool):
+        raise ValueError(f"axis must be 0, 1 or 2, not {axis!r}")
+    if int(n1) != n1 or int(n2) != n2 or n1 < 1 or n2 < 1:
+        raise ValueError(f"n1 and n2 must be integers >= 1, not {n1!r}, {n2!r}")
+    q = [_f64(v) for v in (x, y, z)]
+    lo = [float(v[0]) for v in q]
+    hi = [float(v[0]) + (len(v) - 1.0) * (float(v[1]) - float(v[0])) for v in q]
+    a1, a2 = [d for d in range(3) if d != axis]
+    u1 = lo[a1] + (hi[a1] - lo[a1]) * (np.arange(int(n1)) / max(int(n1) - 1, 1))
+    u2 = lo[a2] + (hi[a2] - lo[a2]) * (np.arange(int(n2)) / max(int(n2) - 1, 1))
+    u1, u2 = np.minimum(u1, hi[a1]), np.minimum(u2, hi[a2])
+    out = np.empty((int(n2), int(n1), 3))
+    out[:, :, axis] = float(value)
+    out[:, :, a1] = u1[None, :]
+    out[:, :, a2] = u2[:, None]
+    return out.reshape(-1, 3)
+
+
 def _grid_handle(x, y, z, b, ngrids, lib):
     shape = np.shape(b)
     want = (3, len(z), len(y), len(x))
@@ -700,6 +783,19 @@ def trace_field_lines(x, y, z, b, seeds, g=None, step=0.5, max_steps=None, direc
     V = _grid_handle(x, y, z, b, 0, lib)
     try:
         return V.trace(b, seeds, g=g, step=step, max_steps=max_steps, direction=direction)
+    finally:
+        V.close()
+
+
+def squashing_factor(x, y, z, b, seeds, g=None, integrand=0, twist=False, step=0.5, max_steps=None, lib=None):
+    """Squashing factor Q of b (3,nz,ny,nx) at seeds (nseeds,3), with the twist number (twist=True) or the line
+    integral of g: one-shot form of VecPot.squashing (returns its QMap tuple).  Raises NdsmHipError on device /
+    runtime failures (>= 9001)."""
+    if twist and g is not None:
+        raise ValueError("twist=True forms g = curl b itself: give g or twist, not both")
+    V = _grid_handle(x, y, z, b, 0, lib)
+    try:
+        return V.squashing(b, seeds, g=g, integrand=integrand, twist=twist, step=step, max_steps=max_steps)
     finally:
         V.close()
 

@@ -30,7 +30,7 @@ enum {
   NDSMK_ENODEV = 9001,   /* no HIP device visible */
   NDSMK_EARG = 9002,     /* shape/argument check failed on the host */
   NDSMK_ENCCL = 9003,    /* RCCL call failed */
-  NDSMK_EVALUE = 9004    /* a scalar argument outside its range (ndsmk_trace) */
+  NDSMK_EVALUE = 9004    /* a scalar argument outside its range (ndsmk_trace, ndsmk_squash) */
 };
 
 /* geometry + operator constants of one grid level (interoperable with the
@@ -215,6 +215,15 @@ enum {
 int ndsmk_trace(const double *B, const double *G, const int32_t *n3, const double *lo3, const double *h_dq3,
                 int nseeds, const double *seeds, double step, int max_steps, int direction, double *ends,
                 double *length, double *integral, int32_t *status, int32_t *nsteps);
+
+/* Squashing factor and line integrals (squash.hip; semantics: include/ndsm_hip.h, ndsm_hip_vecpot_squash).  B, G (G may
+ * be NULL: integrals 0) DEVICE arrays (nx,ny,nz,3); integrand 0: G.B/|B|, 1: G.B/|B|^2; seeds (3,nseeds), q (nseeds),
+ * ends (3,2 nseeds), length, integral, status, nsteps (2 nseeds: the forward block, then the backward block) DEVICE
+ * arrays.  Always both directions.  NDSMK_EVALUE for step <= 0, max_steps < 1, another integrand, nseeds < 0;
+ * nseeds == 0 launches nothing.  Asynchronous. */
+int ndsmk_squash(const double *B, const double *G, int integrand, const int32_t *n3, const double *lo3,
+                 const double *h_dq3, int nseeds, const double *seeds, double step, int max_steps, double *q,
+                 double *ends, double *length, double *integral, int32_t *status, int32_t *nsteps);
 
 /* the face phase on the device (faces.hip): packed face buffers, six faces back to back */
 int ndsmk_face_offsets(const int32_t *n3, int64_t *off6, int64_t *total);

@@ -997,6 +997,94 @@ contains
     end subroutine
   end function
 
+  ! ---- squashing factor and twist on the same handle ----------------------
+  ! As the trace entries, always both directions: B, G (NULL: integrals 0), integrand 0 (G.B/|B|) or 1 (G.B/|B|^2),
+  ! seeds (3,nseeds); out q (nseeds), ends (3,2 nseeds), length, integral (2 nseeds), status, nsteps (2 nseeds,
+  ! int32), the forward block first.  Return value: 0, or >= 9001 errors (9002 a NULL handle or required array, 9004
+  ! a scalar out of range).  The host entry clears its outputs on every failure.
+
+  ! HOST arrays
+  function ndsm_hip_vecpot_squash(handle, B, G, integrand, nseeds, seeds, step, max_steps, q, ends, length, integral, &
+                                  status, nsteps) bind(c, name="ndsm_hip_vecpot_squash") result(ierr)
+    type(c_ptr), value :: handle, B, G, seeds, q, ends, length, integral, status, nsteps
+    integer(c_int), value :: integrand, nseeds, max_steps
+    real(c_double), value :: step
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_squash(handle, B, G, integrand, nseeds, seeds, step, max_steps, q, ends, length, integral, &
+                                status, nsteps, .false., "ndsm_hip_vecpot_squash")
+  end function
+
+  ! the same on DEVICE arrays of the library's GPU (nothing is cleared: the outputs are not host memory)
+  function ndsm_hip_vecpot_squash_device(handle, dB, dG, integrand, nseeds, dseeds, step, max_steps, dq, dends, &
+                                         dlength, dintegral, dstatus, dnsteps) &
+      bind(c, name="ndsm_hip_vecpot_squash_device") result(ierr)
+    type(c_ptr), value :: handle, dB, dG, dseeds, dq, dends, dlength, dintegral, dstatus, dnsteps
+    integer(c_int), value :: integrand, nseeds, max_steps
+    real(c_double), value :: step
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_squash(handle, dB, dG, integrand, nseeds, dseeds, step, max_steps, dq, dends, dlength, &
+                                dintegral, dstatus, dnsteps, .true., "ndsm_hip_vecpot_squash_device")
+  end function
+
+  function vecpot_handle_squash(handle, B, G, integrand, nseeds, seeds, step, max_steps, q, ends, length, integral, &
+                                status, nsteps, on_device, who) result(ierr)
+    type(c_ptr), intent(in) :: handle, B, G, seeds, q, ends, length, integral, status, nsteps
+    integer(c_int), intent(in) :: integrand, nseeds, max_steps
+    real(c_double), intent(in) :: step
+    logical, intent(in) :: on_device
+    character(len=*), intent(in) :: who
+    integer(c_int) :: ierr
+    type(vecpot_ctx), pointer :: ctx
+    integer(c_int) :: rc
+    logical :: need
+    if (.not. on_device) call clear_outputs()
+    ierr = ndsmk_init(-1_c_int)                        ! without a device: 9001, whatever the arguments
+    if (ierr /= 0) return
+    ierr = NDSMK_EARG
+    if (.not. c_associated(handle)) return
+    need = nseeds > 0                                  ! no seeds: no array is looked at
+    if (need .and. .not. (c_associated(B) .and. c_associated(seeds) .and. c_associated(q) .and. &
+                          c_associated(ends) .and. c_associated(length) .and. c_associated(integral) .and. &
+                          c_associated(status) .and. c_associated(nsteps))) return
+    call c_f_pointer(handle, ctx)
+    if (.not. ctx%live) return
+    rc = vecpot_squash(ctx, B, G, integrand, nseeds, seeds, step, max_steps, q, ends, length, integral, status, &
+                       nsteps, on_device)
+    if (rc /= 0) then
+      call report(who, rc)
+      if (rc < NDSMK_ENODEV) rc = NDSMK_ENODEV
+      if (.not. on_device) call clear_outputs()
+    end if
+    ierr = rc
+  contains
+    subroutine clear_outputs()
+      real(c_double), pointer :: r(:)
+      integer(c_int32_t), pointer :: k(:)
+      integer :: nl
+      if (nseeds <= 0) return
+      if (nseeds > huge(0) / 6) return
+      nl = 2 * nseeds
+      if (c_associated(q)) then
+        call c_f_pointer(q, r, [nseeds]); r = 0
+      end if
+      if (c_associated(ends)) then
+        call c_f_pointer(ends, r, [3 * nl]); r = 0
+      end if
+      if (c_associated(length)) then
+        call c_f_pointer(length, r, [nl]); r = 0
+      end if
+      if (c_associated(integral)) then
+        call c_f_pointer(integral, r, [nl]); r = 0
+      end if
+      if (c_associated(status)) then
+        call c_f_pointer(status, k, [nl]); k = 0
+      end if
+      if (c_associated(nsteps)) then
+        call c_f_pointer(nsteps, k, [nl]); k = 0
+      end if
+    end subroutine
+  end function
+
   ! ---- z-slab decomposition over GPUs (SURVEY 8e) -----------------------
 
   ! rank 0 creates the 128-byte RCCL id; the launcher hands it to every rank

@@ -571,6 +571,18 @@ module ndsmh_iface
       integer(c_int) :: rc
     end function
 
+    ! ---- squashing factor and line integrals (squash.hip) ----
+    function ndsmk_squash(B, G, integrand, n3, lo3, dq3, nseeds, seeds, step, max_steps, q, ends, length, integral, &
+                          status, nsteps) bind(c, name="ndsmk_squash") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_double
+      type(c_ptr), value :: B, G, seeds, q, ends, length, integral, status, nsteps
+      integer(c_int32_t), intent(in) :: n3(3)
+      real(c_double), intent(in) :: lo3(3), dq3(3)
+      integer(c_int), value :: integrand, nseeds, max_steps
+      real(c_double), value :: step
+      integer(c_int) :: rc
+    end function
+
     ! ---- the face phase on the device (faces.hip) ----
     function ndsmk_face_offsets(n3, off6, total) bind(c, name="ndsmk_face_offsets") result(rc)
       import :: c_int, c_int32_t, c_int64_t

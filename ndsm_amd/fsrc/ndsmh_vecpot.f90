@@ -32,7 +32,7 @@ module ndsmh_vecpot
 
   public :: vecpot_solve, poisson_solve
   public :: vecpot_ctx, vecpot_ctx_create, vecpot_ctx_destroy, vecpot_ctx_matches, vecpot_run, vecpot_cache_drop
-  public :: vecpot_project, vecpot_devore, vecpot_trace
+  public :: vecpot_project, vecpot_devore, vecpot_trace, vecpot_squash
   public :: VP_POTENTIAL, VP_FIELD, VP_HELICITY
   ! pieces the distributed driver (ndsmh_wvecpot) shares with vecpot_solve
   public :: face_data, face_axis, face_upper, face_t1, face_t2, face_order, face_copy, vecpot_faces, say
@@ -1111,6 +1111,101 @@ contains
     if (rc == 0) rc = ndsmk_d2h(pnst, d(6), 4_c_size_t * nl)
     if (rc == 0) rc = ndsmk_sync()
     do i = 1, 6
+      if (c_associated(d(i))) rc2 = ndsmk_free(d(i))
+    end do
+  end function
+
+  ! ------------------------------------------------------------------
+  ! Squashing factor Q of B at nseeds seeds, the two ends of the line through each and the line integral of G per
+  ! direction, on a prepared context (DESIGN.md "Squashing factor and twist"; semantics in include/ndsm_hip.h).
+  ! As vecpot_trace, always both directions: pq (nseeds) and pends (3,2 nseeds), plen, pint (2 nseeds) doubles,
+  ! pstat, pnst (2 nseeds) int32 out, on the HOST (the same staging arrays and a scratch buffer) or (on_device)
+  ! in HBM.  integrand 0: G.B/|B|, 1: G.B/|B|^2; pG the very pointer pB with integrand 1: G = curl_h B (ndsmk_curl
+  ! into the staging array dF(2)), the twist map.
+  ! ------------------------------------------------------------------
+  function vecpot_squash(ctx, pB, pG, integrand, nseeds, pseeds, step, max_steps, pq, pends, plen, pint, pstat, pnst, &
+                         on_device) result(rc)
+    type(vecpot_ctx), intent(inout), target :: ctx
+    type(c_ptr), intent(in) :: pB, pG, pseeds, pq, pends, plen, pint, pstat, pnst
+    integer(c_int), intent(in) :: integrand, nseeds, max_steps
+    real(wp), intent(in) :: step
+    logical, intent(in) :: on_device
+    integer(c_int) :: rc, rc2
+    character(len=*), parameter :: me = "squashing_factor"
+    real(wp) :: dq(3), lo(3)
+    integer(c_int32_t) :: n3(3)
+    integer(c_size_t) :: nb, nl, ns
+    integer :: i
+    logical :: own_curl, need(2)
+    type(c_ptr) :: dB, dG, d(7)
+
+    n3 = ctx%n3
+    dq = [ctx%qx(2) - ctx%qx(1), ctx%qy(2) - ctx%qy(1), ctx%qz(2) - ctx%qz(1)]      ! as vecpot_run
+    lo = [ctx%qx(1), ctx%qy(1), ctx%qz(1)]
+    if (nseeds <= 0 .or. step <= 0.0_wp .or. max_steps < 1 .or. integrand < 0 .or. integrand > 1) then
+      ! (the argument errors are ndsmk_squash's to name; nothing is staged for them)
+      rc = ndsmk_squash(pB, pG, integrand, n3, lo, dq, nseeds, pseeds, step, max_steps, pq, pends, plen, pint, pstat, &
+                        pnst)
+      return
+    end if
+    nb = int(product(int(n3, ik)), c_size_t) * 24_c_size_t
+    ns = int(nseeds, c_size_t)
+    nl = 2_c_size_t * ns
+    ! G given as B itself with integrand 1: the twist map, G = curl_h B formed here in the staging array dF(2)
+    own_curl = integrand == 1 .and. c_associated(pG) .and. c_associated(pG, pB)
+    ! the helicity entries' host staging: dF(1) B, dF(2) G
+    need = [.not. on_device, own_curl .or. (.not. on_device .and. c_associated(pG))]
+    do i = 1, 2
+      if (need(i) .and. .not. c_associated(ctx%dF(i))) then
+        rc = ndsmk_alloc(ctx%dF(i), nb); if (rc /= 0) return
+      end if
+    end do
+    if (on_device) then
+      dB = pB
+      dG = pG
+    else
+      dB = ctx%dF(1)
+      dG = c_null_ptr
+      rc = ndsmk_h2d(dB, pB, nb); if (rc /= 0) return
+      if (c_associated(pG) .and. .not. own_curl) then
+        dG = ctx%dF(2)
+        rc = ndsmk_h2d(dG, pG, nb); if (rc /= 0) return
+      end if
+    end if
+    if (own_curl) then
+      dG = ctx%dF(2)
+      call say(me, "G = curl(B)...")
+      rc = ndsmk_curl(dB, dG, n3, dq); if (rc /= 0) return
+    end if
+    if (on_device) then
+      rc = ndsmk_squash(dB, dG, integrand, n3, lo, dq, nseeds, pseeds, step, max_steps, pq, pends, plen, pint, pstat, &
+                        pnst)
+      if (rc /= 0) return
+      rc = ndsmk_sync()
+      return
+    end if
+    ! seeds, ends, length, integral, status, nsteps, q
+    d = c_null_ptr
+    rc = ndsmk_alloc(d(1), 24_c_size_t * ns)
+    if (rc == 0) rc = ndsmk_alloc(d(2), 24_c_size_t * nl)
+    if (rc == 0) rc = ndsmk_alloc(d(3), 8_c_size_t * nl)
+    if (rc == 0) rc = ndsmk_alloc(d(4), 8_c_size_t * nl)
+    if (rc == 0) rc = ndsmk_alloc(d(5), 4_c_size_t * nl)
+    if (rc == 0) rc = ndsmk_alloc(d(6), 4_c_size_t * nl)
+    if (rc == 0) rc = ndsmk_alloc(d(7), 8_c_size_t * ns)
+    if (rc == 0) rc = ndsmk_h2d(d(1), pseeds, 24_c_size_t * ns)
+    if (rc == 0) then
+      call say(me, "Tracing field lines with their deviation vectors...")
+      rc = ndsmk_squash(dB, dG, integrand, n3, lo, dq, nseeds, d(1), step, max_steps, d(7), d(2), d(3), d(4), d(5), d(6))
+    end if
+    if (rc == 0) rc = ndsmk_d2h(pq, d(7), 8_c_size_t * ns)
+    if (rc == 0) rc = ndsmk_d2h(pends, d(2), 24_c_size_t * nl)
+    if (rc == 0) rc = ndsmk_d2h(plen, d(3), 8_c_size_t * nl)
+    if (rc == 0) rc = ndsmk_d2h(pint, d(4), 8_c_size_t * nl)
+    if (rc == 0) rc = ndsmk_d2h(pstat, d(5), 4_c_size_t * nl)
+    if (rc == 0) rc = ndsmk_d2h(pnst, d(6), 4_c_size_t * nl)
+    if (rc == 0) rc = ndsmk_sync()
+    do i = 1, 7
       if (c_associated(d(i))) rc2 = ndsmk_free(d(i))
     end do
   end function

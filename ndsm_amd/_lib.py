@@ -80,6 +80,30 @@ def load_library(path=None):
     L.ndsm_hip_world_vcycle.argtypes = [ctypes.c_void_p, ctypes.c_int]
     L.ndsm_hip_world_set_precision.argtypes = [ctypes.c_void_p, ctypes.c_int]
     L.ndsm_hip_world_solve.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_int, _dp, _ip, _dp, ctypes.c_int]
+    L.ndsm_hip_vecpot_create.argtypes = [_ip, _dp, _dp, _dp, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
+    L.ndsm_hip_vecpot_solve.argtypes = [ctypes.c_void_p, _ip, _dp, _dp, _dp]
+    L.ndsm_hip_vecpot_solve_device.argtypes = [ctypes.c_void_p, _ip, _dp, ctypes.c_void_p, ctypes.c_void_p]
+    L.ndsm_hip_vecpot_destroy.argtypes = [ctypes.c_void_p]
+    L.ndsm_hip_vecpot_solve_field.argtypes = [ctypes.c_void_p, _ip, _dp, _dp, _dp]
+    L.ndsm_hip_vecpot_solve_field_device.argtypes = [ctypes.c_void_p, _ip, _dp, ctypes.c_void_p, ctypes.c_void_p]
+    L.ndsm_hip_vecpot_helicity.argtypes = [ctypes.c_void_p, _ip, _dp, _dp, _dp, _dp, _dp, _dp]
+    L.ndsm_hip_vecpot_helicity_device.argtypes = [ctypes.c_void_p, _ip, _dp, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_void_p, _dp]
+    L.ndsm_hip_vecpot_project.argtypes = [ctypes.c_void_p, _ip, _dp, _dp, _dp, _dp]
+    L.ndsm_hip_vecpot_project_device.argtypes = [ctypes.c_void_p, _ip, _dp, ctypes.c_void_p, ctypes.c_void_p,
+                                                 _dp]
+    L.ndsm_hip_vecpot_devore.argtypes = [ctypes.c_void_p, _dp, _dp, _dp, _dp, _dp]
+    L.ndsm_hip_vecpot_devore_device.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 4 + [_dp]
+    _tr = [ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5
+    L.ndsm_hip_vecpot_trace.argtypes = [ctypes.c_void_p] * 3 + _tr
+    L.ndsm_hip_vecpot_trace_device.argtypes = [ctypes.c_void_p] * 3 + _tr
+    _sq = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_int] + [ctypes.c_void_p] * 6
+    L.ndsm_hip_vecpot_squash.argtypes = [ctypes.c_void_p] * 3 + _sq
+    L.ndsm_hip_vecpot_squash_device.argtypes = [ctypes.c_void_p] * 3 + _sq
+    L.ndsm_hip_device_alloc.argtypes = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
+    L.ndsm_hip_device_free.argtypes = [ctypes.c_void_p]
+    L.ndsm_hip_memcpy_h2d.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
+    L.ndsm_hip_memcpy_d2h.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
     if path is None:
         _LIB = L
     return L
@@ -226,31 +250,7 @@ class VecPot:
         self.nshape4 = np.array([len(self.x), len(self.y), len(self.z), 3], dtype=np.intc)
         self.ngrids = int(ngrids)
         self.h = ctypes.c_void_p()
-        self.L.ndsm_hip_vecpot_create.argtypes = [_ip, _dp, _dp, _dp, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
-        self.L.ndsm_hip_vecpot_solve.argtypes = [ctypes.c_void_p, _ip, _dp, _dp, _dp]
-        self.L.ndsm_hip_vecpot_solve_device.argtypes = [ctypes.c_void_p, _ip, _dp, ctypes.c_void_p, ctypes.c_void_p]
-        self.L.ndsm_hip_vecpot_destroy.argtypes = [ctypes.c_void_p]
-        self.L.ndsm_hip_vecpot_solve_field.argtypes = [ctypes.c_void_p, _ip, _dp, _dp, _dp]
-        self.L.ndsm_hip_vecpot_solve_field_device.argtypes = [ctypes.c_void_p, _ip, _dp, ctypes.c_void_p, ctypes.c_void_p]
-        self.L.ndsm_hip_vecpot_helicity.argtypes = [ctypes.c_void_p, _ip, _dp, _dp, _dp, _dp, _dp, _dp]
-        self.L.ndsm_hip_vecpot_helicity_device.argtypes = [ctypes.c_void_p, _ip, _dp, ctypes.c_void_p, ctypes.c_void_p,
-                                                           ctypes.c_void_p, ctypes.c_void_p, _dp]
-        self.L.ndsm_hip_vecpot_project.argtypes = [ctypes.c_void_p, _ip, _dp, _dp, _dp, _dp]
-        self.L.ndsm_hip_vecpot_project_device.argtypes = [ctypes.c_void_p, _ip, _dp, ctypes.c_void_p, ctypes.c_void_p,
-                                                          _dp]
-        self.L.ndsm_hip_vecpot_devore.argtypes = [ctypes.c_void_p, _dp, _dp, _dp, _dp, _dp]
-        self.L.ndsm_hip_vecpot_devore_device.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 4 + [_dp]
-        _tr = [ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5
-        self.L.ndsm_hip_vecpot_trace.argtypes = [ctypes.c_void_p] * 3 + _tr
-        self.L.ndsm_hip_vecpot_trace_device.argtypes = [ctypes.c_void_p] * 3 + _tr
-        _sq = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_int] + [ctypes.c_void_p] * 6
-        self.L.ndsm_hip_vecpot_squash.argtypes = [ctypes.c_void_p] * 3 + _sq
-        self.L.ndsm_hip_vecpot_squash_device.argtypes = [ctypes.c_void_p] * 3 + _sq
         self.last_projection = None
-        self.L.ndsm_hip_device_alloc.argtypes = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
-        self.L.ndsm_hip_device_free.argtypes = [ctypes.c_void_p]
-        self.L.ndsm_hip_memcpy_h2d.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
-        self.L.ndsm_hip_memcpy_d2h.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
         rc = self.L.ndsm_hip_vecpot_create(self.nshape4.ctypes.data_as(_ip), _d(self.x), _d(self.y), _d(self.z),
                                            self.ngrids, ctypes.byref(self.h))
         _check(rc, "ndsm_hip_vecpot_create", self.L)
@@ -485,16 +485,7 @@ class VecPot:
         out = _trace_outputs(len(S), direction)
         if len(S) == 0:
             return _field_lines(out, direction)
-        if not device:
-            ierr = self.L.ndsm_hip_vecpot_trace(self.h, B.ctypes.data, None if G is None else G.ctypes.data, len(S),
-                                                S.ctypes.data, step, max_steps, direction,
-                                                *[a.ctypes.data for a in out])
-        else:
-            arrays = [B, S] + out + ([G] if G is not None else [])
-            ierr = self._on_device(arrays, lambda dB, dS, d1, d2, d3, d4, d5, dG=None:
-                                   self.L.ndsm_hip_vecpot_trace_device(self.h, dB, dG, len(S), dS, step, max_steps,
-                                                                       direction, d1, d2, d3, d4, d5))
-        _check(ierr, "ndsm_hip_vecpot_trace", self.L)
+        self._line_entry("ndsm_hip_vecpot_trace", B, G, (), S, (step, max_steps, direction), out, device)
         return _field_lines(out, direction)
 
     def default_max_steps(self, step=0.5):
@@ -523,6 +514,27 @@ class VecPot:
             raise NdsmHipError(f"trace: {len(S)} seeds, at most {TRACE_MAX_SEEDS} per call (code 9002)")
         return np.ascontiguousarray(S).copy()
 
+    def _line_entry(self, name, B, G, head, S, tail, out, device):
+        """One call of a line entry: L.<name>(h, B, G, *head, nseeds, seeds, *tail, *out) on host arrays, or (device)
+        L.<name>_device with the seeds S, the outputs and every field that is a host array staged in device memory
+        first.  B, G: flat host arrays, or with device=True pointers to arrays already there; G None: no integral;
+        G is B: the same pointer twice.  Raises NdsmHipError unless the entry returns 0."""
+        def host(a):
+            return isinstance(a, np.ndarray)
+        if not device:
+            ierr = getattr(self.L, name)(self.h, B.ctypes.data, G.ctypes.data if host(G) else None, *head, len(S),
+                                         S.ctypes.data, *tail, *[a.ctypes.data for a in out])
+        else:
+            fields = [a for a in ((B,) if G is B else (B, G)) if host(a)]
+
+            def call(dS, *ptrs):
+                rest = list(ptrs[len(out):])
+                dB = rest.pop(0) if host(B) else B
+                dG = dB if G is B else (rest.pop(0) if host(G) else G)
+                return getattr(self.L, name + "_device")(self.h, dB, dG, *head, len(S), dS, *tail, *ptrs[:len(out)])
+            ierr = self._on_device([S] + out + fields, call)
+        _check(ierr, name if host(B) else name + "_device", self.L)
+
     def squashing(self, b, seeds, g=None, integrand=0, twist=False, step=0.5, max_steps=None, device=False):
         """Squashing factor Q (Titov 2007) of b (3,nz,ny,nx) at seeds (nseeds,3; anywhere in the box), on the device,
         from the one field line through each seed: two deviation vectors are integrated along it with the gradient
@@ -550,18 +562,9 @@ class VecPot:
             return _qmap(out, twist)
         if twist:
             integrand = 1
-        if not device:
-            # (the field passed as its own g with integrand 1 asks the library for g = curl b)
-            pG = B.ctypes.data if twist else (None if G is None else G.ctypes.data)
-            ierr = self.L.ndsm_hip_vecpot_squash(self.h, B.ctypes.data, pG, integrand, len(S), S.ctypes.data, step,
-                                                 max_steps, *[a.ctypes.data for a in out])
-        else:
-            arrays = [B, S] + out + ([G] if G is not None else [])
-            ierr = self._on_device(arrays, lambda dB, dS, d0, d1, d2, d3, d4, d5, dG=None:
-                                   self.L.ndsm_hip_vecpot_squash_device(self.h, dB, dB if twist else dG, integrand,
-                                                                        len(S), dS, step, max_steps, d0, d1, d2, d3,
-                                                                        d4, d5))
-        _check(ierr, "ndsm_hip_vecpot_squash", self.L)
+        # (the field passed as its own g with integrand 1 asks the library for g = curl b)
+        self._line_entry("ndsm_hip_vecpot_squash", B, B if twist else G, (integrand,), S, (step, max_steps), out,
+                         device)
         return _qmap(out, twist)
 
     def seed_plane(self, axis, value, n1, n2):
@@ -595,9 +598,7 @@ class VecPot:
             """trace on the resident B and A (d: the chain's device arrays)"""
             if len(S) == 0:
                 return
-            self._on_device([S] + out, lambda dS, d1, d2, d3, d4, d5: _check(L.ndsm_hip_vecpot_trace_device(
-                self.h, d["B"], d["A"], len(S), dS, step, max_steps, direction, d1, d2, d3, d4, d5),
-                "ndsm_hip_vecpot_trace_device", L))
+            self._line_entry("ndsm_hip_vecpot_trace", d["B"], d["A"], (), S, (step, max_steps, direction), out, True)
 
         ioptc, ropt = self._options(niterex_max, ncycles_max, ex_tol, vc_tol, ms, mean, mixed_precision, flxcrl)
         if gauge == "devore":

@@ -3,106 +3,27 @@
 // the field, and Q at the seed follows from them at the two feet of the one line through it.  One lane per (seed,
 // direction), the two lanes of a seed next to each other in a wave; the forward lane combines the two ends.  As in
 // trace.hip the arithmetic is fixed fp64 expressions in a fixed order (-ffp-contract=off), restated in numpy by the
-// tests bit for bit (the cell, gather and lerp inlines of trace.hip are restated here: that file does not change):
+// tests bit for bit.  The cell, gather, value and gradient of the trilinear interpolant, the first-face search and the
+// snap of the exit point are line.hpp's (the specification is at the top of that file); here:
 //
-//   cell, per axis d      u = (r_d - lo_d) / h_d, c = clamp(floor(u), 0, n_d - 2), f = u - c (not clamped)
-//   per component         d00 = v100 - v000, d10 = v110 - v010, d01 = v101 - v001, d11 = v111 - v011,
-//                         c00 = v000 + fx d00, c10 = v010 + fx d10, c01 = v001 + fx d01, c11 = v011 + fx d11,
-//                         e0 = c10 - c00, e1 = c11 - c01, c0 = c00 + fy e0, c1 = c01 + fy e1, dz = c1 - c0,
-//                         value = c0 + fz dz (the bits of trace.hip's interpolation)
-//   gradient              dx0 = d00 + fy (d10 - d00), dx1 = d01 + fy (d11 - d01),
-//                         d/dx = (dx0 + fz (dx1 - dx0)) / hx, d/dy = (e0 + fz (e1 - e0)) / hy, d/dz = dz / hz
 //   stage at (p, U, V)    b = B(p), M = grad B(p), m = sqrt((bx bx + by by) + bz bz); not m > 0: "null";
 //                         e = b / m, k_r = sgn e, k_U,c = sgn (((M_c0 U_0 + M_c1 U_1) + M_c2 U_2) / m), k_V likewise,
 //                         q = (Gx ex + Gy ey) + Gz ez, divided by m for integrand 1 (no sgn)
 //   RK4 step of length s  stage 2 at y + (0.5 s) k1, 3 at y + (0.5 s) k2, 4 at y + s k3 for all of y = (r, U, V);
 //                         y' = y + (s / 6) (((k1 + 2 k2) + 2 k3) + k4), dI likewise, the sum formed as the stages
 //                         complete
-//   exit                  r' outside: face and t as in trace.hip, the step redone with s = t ds, then twice
+//   exit                  r' outside: the step is redone with s = t ds, t of the first face, then twice
 //                         s = s (face - r_ax) / (r'_ax - r_ax) (skipped when r'_ax == r_ax) and redone; snap, clamp
 // Every lane's loop is bounded by max_steps (and by four passes over a step).
-#include "common.hpp"
+#include "line.hpp"
 
 namespace {
 
-constexpr int kSqBlock = 64;             // one wave per block: 32 seeds
-constexpr int kSqMaxSteps = 1 << 24;
+using namespace ndsm;
 
-struct SqArgs {
-  int n[3];
-  double lo[3], hi[3], h[3];
-  double ds;
-  int max_steps;
-  int nseeds;
+struct SqArgs : LineArgs {
   int integrand;
 };
-
-struct SqCell {
-  size_t base;
-  double fx, fy, fz;
-};
-
-__device__ __forceinline__ SqCell sq_cell(const SqArgs &p, double x, double y, double z) {
-  const double ux = (x - p.lo[0]) / p.h[0];
-  const double uy = (y - p.lo[1]) / p.h[1];
-  const double uz = (z - p.lo[2]) / p.h[2];
-  // (the points that reach here are within one step of the box, so the conversions cannot overflow)
-  const double cx = fmin(fmax(floor(ux), 0.0), (double)(p.n[0] - 2));
-  const double cy = fmin(fmax(floor(uy), 0.0), (double)(p.n[1] - 2));
-  const double cz = fmin(fmax(floor(uz), 0.0), (double)(p.n[2] - 2));
-  SqCell c;
-  c.fx = ux - cx;
-  c.fy = uy - cy;
-  c.fz = uz - cz;
-  c.base = (size_t)(int)cx + (size_t)p.n[0] * ((size_t)(int)cy + (size_t)p.n[1] * (size_t)(int)cz);
-  return c;
-}
-
-// the 8 corners of the three components of F at cell c: all 24 loads are issued before the first use
-__device__ __forceinline__ void sq_gather(const double *__restrict__ F, size_t N, size_t sy, size_t sz, const SqCell &c,
-                                          double v[3][8]) {
-#pragma unroll
-  for (int m = 0; m < 3; ++m) {
-    const double *__restrict__ q = F + (size_t)m * N + c.base;
-    v[m][0] = q[0];
-    v[m][1] = q[1];
-    v[m][2] = q[sy];
-    v[m][3] = q[sy + 1];
-    v[m][4] = q[sz];
-    v[m][5] = q[sz + 1];
-    v[m][6] = q[sz + sy];
-    v[m][7] = q[sz + sy + 1];
-  }
-}
-
-__device__ __forceinline__ double sq_lerp3(const double v[8], const SqCell &c) {
-  const double c00 = v[0] + c.fx * (v[1] - v[0]);
-  const double c10 = v[2] + c.fx * (v[3] - v[2]);
-  const double c01 = v[4] + c.fx * (v[5] - v[4]);
-  const double c11 = v[6] + c.fx * (v[7] - v[6]);
-  const double c0 = c00 + c.fy * (c10 - c00);
-  const double c1 = c01 + c.fy * (c11 - c01);
-  return c0 + c.fz * (c1 - c0);
-}
-
-// value and gradient of the trilinear interpolant of one component (the quotients by h are formed, not products by 1 / h)
-__device__ __forceinline__ double sq_lerp3_grad(const double v[8], const SqCell &c, const SqArgs &p, double g[3]) {
-  const double d00 = v[1] - v[0], d10 = v[3] - v[2], d01 = v[5] - v[4], d11 = v[7] - v[6];
-  const double c00 = v[0] + c.fx * d00;
-  const double c10 = v[2] + c.fx * d10;
-  const double c01 = v[4] + c.fx * d01;
-  const double c11 = v[6] + c.fx * d11;
-  const double e0 = c10 - c00, e1 = c11 - c01;
-  const double c0 = c00 + c.fy * e0;
-  const double c1 = c01 + c.fy * e1;
-  const double dz = c1 - c0;
-  const double dx0 = d00 + c.fy * (d10 - d00);
-  const double dx1 = d01 + c.fy * (d11 - d01);
-  g[0] = (dx0 + c.fz * (dx1 - dx0)) / p.h[0];
-  g[1] = (e0 + c.fz * (e1 - e0)) / p.h[1];
-  g[2] = dz / p.h[2];
-  return c0 + c.fz * dz;
-}
 
 // the state of a line and its slopes: r, U, V and the integral
 struct SqVec {
@@ -114,13 +35,13 @@ template <bool kHasG>
 __device__ __forceinline__ bool sq_stage(const double *__restrict__ B, const double *__restrict__ G, const SqArgs &p,
                                          size_t N, size_t sy, size_t sz, double sgn, const double r[3],
                                          const double U[3], const double V[3], SqVec &k, double b[3], double &m2) {
-  const SqCell c = sq_cell(p, r[0], r[1], r[2]);
+  const LineCell c = line_cell(p, r[0], r[1], r[2]);
   double vb[3][8], vg[3][8];
-  sq_gather(B, N, sy, sz, c, vb);
-  if (kHasG) sq_gather(G, N, sy, sz, c, vg);
+  line_gather(B, N, sy, sz, c, vb);
+  if (kHasG) line_gather(G, N, sy, sz, c, vg);
   double M[3][3];
 #pragma unroll
-  for (int d = 0; d < 3; ++d) b[d] = sq_lerp3_grad(vb[d], c, p, M[d]);
+  for (int d = 0; d < 3; ++d) b[d] = line_lerp3_grad(vb[d], c, p, M[d]);
   m2 = (b[0] * b[0] + b[1] * b[1]) + b[2] * b[2];
   const double m = sqrt(m2);
   k.I = 0.0;
@@ -135,7 +56,7 @@ __device__ __forceinline__ bool sq_stage(const double *__restrict__ B, const dou
     k.V[d] = sgn * (((M[d][0] * V[0] + M[d][1] * V[1]) + M[d][2] * V[2]) / m);
   }
   if (kHasG) {
-    const double gx = sq_lerp3(vg[0], c), gy = sq_lerp3(vg[1], c), gz = sq_lerp3(vg[2], c);
+    const double gx = line_lerp3(vg[0], c), gy = line_lerp3(vg[1], c), gz = line_lerp3(vg[2], c);
     double q = (gx * ex + gy * ey) + gz * ez;
     if (p.integrand == 1) q = q / m;
     k.I = q;
@@ -197,12 +118,12 @@ __device__ __forceinline__ double sq_pick(const double a[3], int ax) { return ax
 // lane l: seed l / 2, direction l % 2 (0 forward, 1 backward).  Line j = direction * nseeds + seed of the outputs:
 // ends[3 j .. 3 j + 2], length[j], integral[j], status[j], nsteps[j]; q[seed] from the forward lane.
 template <bool kHasG>
-__global__ __launch_bounds__(kSqBlock) void squash_k(const double *__restrict__ B, const double *__restrict__ G,
-                                                     const double *__restrict__ seeds, double *__restrict__ qout,
-                                                     double *__restrict__ ends, double *__restrict__ length,
-                                                     double *__restrict__ integral, int32_t *__restrict__ status,
-                                                     int32_t *__restrict__ nsteps, SqArgs p) {
-  const size_t l = (size_t)blockIdx.x * kSqBlock + threadIdx.x;
+__global__ __launch_bounds__(kLineBlock) void squash_k(const double *__restrict__ B, const double *__restrict__ G,
+                                                       const double *__restrict__ seeds, double *__restrict__ qout,
+                                                       double *__restrict__ ends, double *__restrict__ length,
+                                                       double *__restrict__ integral, int32_t *__restrict__ status,
+                                                       int32_t *__restrict__ nsteps, SqArgs p) {
+  const size_t l = (size_t)blockIdx.x * kLineBlock + threadIdx.x;
   const bool live = l < 2 * (size_t)p.nseeds;
   const size_t is = live ? l >> 1 : 0;            // (a lane past the end follows seed 0 and writes nothing)
   const int back = (int)(l & 1);
@@ -226,10 +147,10 @@ __global__ __launch_bounds__(kSqBlock) void squash_k(const double *__restrict__ 
     {
       // the frame at the seed: U0 perpendicular to e = B/|B| from the axis of the smallest |e_d|, V0 = e x U0 (at a
       // null they stay 0 and the first stage below ends the line)
-      const SqCell c = sq_cell(p, y.r[0], y.r[1], y.r[2]);
+      const LineCell c = line_cell(p, y.r[0], y.r[1], y.r[2]);
       double vb[3][8];
-      sq_gather(B, N, sy, sz, c, vb);
-      const double b[3] = {sq_lerp3(vb[0], c), sq_lerp3(vb[1], c), sq_lerp3(vb[2], c)};
+      line_gather(B, N, sy, sz, c, vb);
+      const double b[3] = {line_lerp3(vb[0], c), line_lerp3(vb[1], c), line_lerp3(vb[2], c)};
       bs2 = (b[0] * b[0] + b[1] * b[1]) + b[2] * b[2];
       const double m = sqrt(bs2);
       if (m > 0.0) {
@@ -268,24 +189,8 @@ __global__ __launch_bounds__(kSqBlock) void squash_k(const double *__restrict__ 
           break;
         }
         if (pass == 0) {
-          // the first face the chord r -> rn meets, if rn is outside
-          double t = 2.0;
-#pragma unroll
-          for (int d = 0; d < 3; ++d) {
-            double td = 2.0;
-            int fd = 0;
-            if (yn.r[d] < p.lo[d]) {
-              td = (p.lo[d] - y.r[d]) / (yn.r[d] - y.r[d]);
-              fd = NDSMK_TRACE_XLO + 2 * d;
-            } else if (yn.r[d] > p.hi[d]) {
-              td = (p.hi[d] - y.r[d]) / (yn.r[d] - y.r[d]);
-              fd = NDSMK_TRACE_XLO + 2 * d + 1;
-            }
-            if (td < t) {
-              t = td;
-              face = fd;
-            }
-          }
+          double t;
+          face = line_first_face(p, y.r, yn.r, t);
           if (face == 0) break;
           ax = (face - NDSMK_TRACE_XLO) >> 1;
           fv = ((face - NDSMK_TRACE_XLO) & 1) ? sq_pick(p.hi, ax) : sq_pick(p.lo, ax);
@@ -310,8 +215,7 @@ __global__ __launch_bounds__(kSqBlock) void squash_k(const double *__restrict__ 
         len = len + p.ds;
         continue;
       }
-#pragma unroll
-      for (int d = 0; d < 3; ++d) y.r[d] = (d == ax) ? fv : fmin(fmax(yn.r[d], p.lo[d]), p.hi[d]);
+      line_snap(p, face, yn.r, y.r);
       len = len + s;
       st = face;
       break;
@@ -322,10 +226,10 @@ __global__ __launch_bounds__(kSqBlock) void squash_k(const double *__restrict__ 
   double uu = 0.0, vv = 0.0, uv = 0.0, bn = 0.0;
   if (onface) {
     const int ax = (st - NDSMK_TRACE_XLO) >> 1;
-    const SqCell c = sq_cell(p, y.r[0], y.r[1], y.r[2]);
+    const LineCell c = line_cell(p, y.r[0], y.r[1], y.r[2]);
     double vb[3][8];
-    sq_gather(B, N, sy, sz, c, vb);
-    const double be[3] = {sq_lerp3(vb[0], c), sq_lerp3(vb[1], c), sq_lerp3(vb[2], c)};
+    line_gather(B, N, sy, sz, c, vb);
+    const double be[3] = {line_lerp3(vb[0], c), line_lerp3(vb[1], c), line_lerp3(vb[2], c)};
     const double bax = sq_pick(be, ax);
     const double fu = sq_pick(y.U, ax) / bax, fw = sq_pick(y.V, ax) / bax;
     double Ut[3], Vt[3];
@@ -376,33 +280,22 @@ extern "C" int ndsmk_squash(const double *B, const double *G, int integrand, con
                             double *q, double *ends, double *length, double *integral, int32_t *status,
                             int32_t *nsteps) {
   NDSM_REQUIRE_READY();
-  if (!(step > 0.0) || !(step <= 1.0e300) || max_steps < 1 || integrand < 0 || integrand > 1 || nseeds < 0)
-    return ndsm::fail(NDSMK_EVALUE, "squash: step > 0 (finite), max_steps >= 1, integrand in 0, 1 and nseeds >= 0",
-                      __FILE__, __LINE__);
-  if (nseeds == 0) return 0;
-  NDSM_CHECK_ARG(B && seeds && q && ends && length && integral && status && nsteps);
-  NDSM_CHECK_ARG(n3[0] >= 2 && n3[1] >= 2 && n3[2] >= 2 && h_dq3[0] > 0.0 && h_dq3[1] > 0.0 && h_dq3[2] > 0.0);
   SqArgs p;
-  for (int d = 0; d < 3; ++d) {
-    p.n[d] = n3[d];
-    p.lo[d] = lo3[d];
-    p.h[d] = h_dq3[d];
-    p.hi[d] = lo3[d] + (double)(n3[d] - 1) * h_dq3[d];
-  }
-  p.ds = step * fmin(fmin(h_dq3[0], h_dq3[1]), h_dq3[2]);
-  p.max_steps = max_steps < kSqMaxSteps ? max_steps : kSqMaxSteps;
-  p.nseeds = nseeds;
   p.integrand = integrand;
+  const int rc = line_args("squash: step > 0 (finite), max_steps >= 1, integrand in 0, 1 and nseeds >= 0",
+                           integrand >= 0 && integrand <= 1,
+                           B && seeds && q && ends && length && integral && status && nsteps, n3, lo3, h_dq3, nseeds,
+                           step, max_steps, 2, p);
+  if (rc != 0 || nseeds == 0) return rc;
   const size_t nl = 2 * (size_t)nseeds;
-  NDSM_CHECK_ARG(nl <= (size_t)0x7fffffff);
-  const unsigned nb = (unsigned)((nl + kSqBlock - 1) / kSqBlock);
+  const unsigned nb = (unsigned)((nl + kLineBlock - 1) / kLineBlock);
   hipStream_t s = ndsm::stream();
   if (G)
-    hipLaunchKernelGGL(squash_k<true>, dim3(nb), dim3(kSqBlock), 0, s, B, G, seeds, q, ends, length, integral, status,
+    hipLaunchKernelGGL(squash_k<true>, dim3(nb), dim3(kLineBlock), 0, s, B, G, seeds, q, ends, length, integral, status,
                        nsteps, p);
   else
-    hipLaunchKernelGGL(squash_k<false>, dim3(nb), dim3(kSqBlock), 0, s, B, G, seeds, q, ends, length, integral, status,
-                       nsteps, p);
+    hipLaunchKernelGGL(squash_k<false>, dim3(nb), dim3(kLineBlock), 0, s, B, G, seeds, q, ends, length, integral,
+                       status, nsteps, p);
   NDSM_LAUNCH_CHECK();
   return 0;
 }

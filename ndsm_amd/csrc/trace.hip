@@ -1,97 +1,38 @@
 // Field-line tracing and line integrals on the device (DESIGN.md "Field-line tracing and field-line helicity").
 // One lane per (seed, direction): a latency-bound gather with a data-dependent trip count per lane, unlike the
 // plane-streaming kernels of the other files.  The arithmetic is fixed fp64 expressions in a fixed order (no
-// contraction: -ffp-contract=off), so a numpy restatement matches bit for bit:
+// contraction: -ffp-contract=off), so a numpy restatement matches bit for bit.  Interpolation, the first-face search
+// and the snap of the exit point are line.hpp's (the specification is at the top of that file); here:
 //
-//   interpolation, per axis d   u = (r_d - lo_d) / h_d,  c = clamp(floor(u), 0, n_d - 2),  f = u - c  (f is NOT
-//                               clamped: a stage point outside the box extrapolates from the edge cell)
-//                per component  c00 = v000 + fx (v100 - v000), c10 = v010 + fx (v110 - v010),
-//                               c01 = v001 + fx (v101 - v001), c11 = v011 + fx (v111 - v011),
-//                               c0 = c00 + fy (c10 - c00), c1 = c01 + fy (c11 - c01), v = c0 + fz (c1 - c0)
 //   stage at p                  b = B(p), m = sqrt((bx bx + by by) + bz bz); not m > 0: the line ends "null";
 //                               e = b / m, k = sgn e, q = (Gx ex + Gy ey) + Gz ez   (sgn = +1 forward, -1 backward;
 //                               q has no sgn: the integral runs in the direction of B for both directions)
 //   RK4 step of length s from r k1 = k(r), k2 = k(r + (0.5 s) k1), k3 = k(r + (0.5 s) k2), k4 = k(r + s k3),
 //                               r' = r + (s / 6) (((k1 + 2 k2) + 2 k3) + k4), dI = (s / 6) (((q1 + 2 q2) + 2 q3) + q4)
-//   exit                        r' outside [lo, hi]: per axis that left, t_d = (face_d - r_d) / (r'_d - r_d); the
-//                               smallest wins (x before y before z on a tie); the step is redone from r with
-//                               s = t ds (k1, q1 kept), then r'_axis = face and the other two are clamped.
+//   exit                        r' outside [lo, hi]: the step is redone from r with s = t ds (k1, q1 kept), t of the
+//                               first face; then the end is snapped onto that face.
 // Every lane's loop is bounded by max_steps.
-#include "common.hpp"
+#include "line.hpp"
 
 namespace {
 
-constexpr int kTrBlock = 64;             // one wave per block: a few thousand lanes spread over all CUs
-constexpr int kTrMaxSteps = 1 << 24;     // the hard ceiling of max_steps
+using namespace ndsm;
 
-struct TrArgs {
-  int n[3];
-  double lo[3], hi[3], h[3];
-  double ds;
-  int max_steps;
-  int nseeds;
+struct TrArgs : LineArgs {
   int ndir;       // 1 or 2
   int sgn0;       // direction of the first block of lanes: +1 or -1 (both: +1, the second block is -1)
 };
-
-struct TrCell {
-  size_t base;
-  double fx, fy, fz;
-};
-
-__device__ __forceinline__ TrCell tr_cell(const TrArgs &p, double x, double y, double z) {
-  const double ux = (x - p.lo[0]) / p.h[0];
-  const double uy = (y - p.lo[1]) / p.h[1];
-  const double uz = (z - p.lo[2]) / p.h[2];
-  // (the points that reach here are within one step of the box, so the conversions cannot overflow)
-  const double cx = fmin(fmax(floor(ux), 0.0), (double)(p.n[0] - 2));
-  const double cy = fmin(fmax(floor(uy), 0.0), (double)(p.n[1] - 2));
-  const double cz = fmin(fmax(floor(uz), 0.0), (double)(p.n[2] - 2));
-  TrCell c;
-  c.fx = ux - cx;
-  c.fy = uy - cy;
-  c.fz = uz - cz;
-  c.base = (size_t)(int)cx + (size_t)p.n[0] * ((size_t)(int)cy + (size_t)p.n[1] * (size_t)(int)cz);
-  return c;
-}
-
-// the 8 corners of the three components of F at cell c: all 24 loads are issued before the first use
-__device__ __forceinline__ void tr_gather(const double *__restrict__ F, size_t N, size_t sy, size_t sz, const TrCell &c,
-                                          double v[3][8]) {
-#pragma unroll
-  for (int m = 0; m < 3; ++m) {
-    const double *__restrict__ q = F + (size_t)m * N + c.base;
-    v[m][0] = q[0];
-    v[m][1] = q[1];
-    v[m][2] = q[sy];
-    v[m][3] = q[sy + 1];
-    v[m][4] = q[sz];
-    v[m][5] = q[sz + 1];
-    v[m][6] = q[sz + sy];
-    v[m][7] = q[sz + sy + 1];
-  }
-}
-
-__device__ __forceinline__ double tr_lerp3(const double v[8], const TrCell &c) {
-  const double c00 = v[0] + c.fx * (v[1] - v[0]);
-  const double c10 = v[2] + c.fx * (v[3] - v[2]);
-  const double c01 = v[4] + c.fx * (v[5] - v[4]);
-  const double c11 = v[6] + c.fx * (v[7] - v[6]);
-  const double c0 = c00 + c.fy * (c10 - c00);
-  const double c1 = c01 + c.fy * (c11 - c01);
-  return c0 + c.fz * (c1 - c0);
-}
 
 // one stage at (x,y,z): k[3] = sgn B/|B|, q = G . B/|B| (0 without G).  false: |B| is not > 0 (zero or NaN).
 template <bool kHasG>
 __device__ __forceinline__ bool tr_stage(const double *__restrict__ B, const double *__restrict__ G, const TrArgs &p,
                                          size_t N, size_t sy, size_t sz, double sgn, double x, double y, double z,
                                          double k[3], double &q) {
-  const TrCell c = tr_cell(p, x, y, z);
+  const LineCell c = line_cell(p, x, y, z);
   double vb[3][8], vg[3][8];
-  tr_gather(B, N, sy, sz, c, vb);
-  if (kHasG) tr_gather(G, N, sy, sz, c, vg);
-  const double bx = tr_lerp3(vb[0], c), by = tr_lerp3(vb[1], c), bz = tr_lerp3(vb[2], c);
+  line_gather(B, N, sy, sz, c, vb);
+  if (kHasG) line_gather(G, N, sy, sz, c, vg);
+  const double bx = line_lerp3(vb[0], c), by = line_lerp3(vb[1], c), bz = line_lerp3(vb[2], c);
   const double m = sqrt((bx * bx + by * by) + bz * bz);
   q = 0.0;
   if (!(m > 0.0)) return false;
@@ -100,7 +41,7 @@ __device__ __forceinline__ bool tr_stage(const double *__restrict__ B, const dou
   k[1] = sgn * ey;
   k[2] = sgn * ez;
   if (kHasG) {
-    const double gx = tr_lerp3(vg[0], c), gy = tr_lerp3(vg[1], c), gz = tr_lerp3(vg[2], c);
+    const double gx = line_lerp3(vg[0], c), gy = line_lerp3(vg[1], c), gz = line_lerp3(vg[2], c);
     q = (gx * ex + gy * ey) + gz * ez;
   }
   return true;
@@ -128,12 +69,12 @@ __device__ __forceinline__ bool tr_rk4(const double *__restrict__ B, const doubl
 // lane l: seed l % nseeds, direction block l / nseeds.  Outputs per lane: ends[3 l .. 3 l + 2], length[l],
 // integral[l], status[l], nsteps[l].
 template <bool kHasG>
-__global__ __launch_bounds__(kTrBlock) void trace_k(const double *__restrict__ B, const double *__restrict__ G,
-                                                    const double *__restrict__ seeds, double *__restrict__ ends,
-                                                    double *__restrict__ length, double *__restrict__ integral,
-                                                    int32_t *__restrict__ status, int32_t *__restrict__ nsteps,
-                                                    TrArgs p) {
-  const size_t l = (size_t)blockIdx.x * kTrBlock + threadIdx.x;
+__global__ __launch_bounds__(kLineBlock) void trace_k(const double *__restrict__ B, const double *__restrict__ G,
+                                                      const double *__restrict__ seeds, double *__restrict__ ends,
+                                                      double *__restrict__ length, double *__restrict__ integral,
+                                                      int32_t *__restrict__ status, int32_t *__restrict__ nsteps,
+                                                      TrArgs p) {
+  const size_t l = (size_t)blockIdx.x * kLineBlock + threadIdx.x;
   const size_t nl = (size_t)p.nseeds * (size_t)p.ndir;
   if (l >= nl) return;
   const size_t is = l % (size_t)p.nseeds;
@@ -157,25 +98,8 @@ __global__ __launch_bounds__(kTrBlock) void trace_k(const double *__restrict__ B
         st = NDSMK_TRACE_NULL;
         break;
       }
-      // the first face the chord r -> rn meets, if rn is outside
-      double t = 2.0;
-      int face = 0;
-#pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        double td = 2.0;
-        int fd = 0;
-        if (rn[d] < p.lo[d]) {
-          td = (p.lo[d] - r[d]) / (rn[d] - r[d]);
-          fd = NDSMK_TRACE_XLO + 2 * d;
-        } else if (rn[d] > p.hi[d]) {
-          td = (p.hi[d] - r[d]) / (rn[d] - r[d]);
-          fd = NDSMK_TRACE_XLO + 2 * d + 1;
-        }
-        if (td < t) {
-          t = td;
-          face = fd;
-        }
-      }
+      double t;
+      const int face = line_first_face(p, r, rn, t);
       if (face == 0) {
         r[0] = rn[0], r[1] = rn[1], r[2] = rn[2];
         len = len + p.ds;
@@ -189,12 +113,7 @@ __global__ __launch_bounds__(kTrBlock) void trace_k(const double *__restrict__ B
         st = NDSMK_TRACE_NULL;
         break;
       }
-      const int ax = (face - NDSMK_TRACE_XLO) >> 1;
-#pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        const double fv = ((face - NDSMK_TRACE_XLO) & 1) ? p.hi[d] : p.lo[d];
-        r[d] = (d == ax) ? fv : fmin(fmax(rn[d], p.lo[d]), p.hi[d]);
-      }
+      line_snap(p, face, rn, r);
       len = len + s;
       I = I + dI;
       ns = it + 1;
@@ -221,33 +140,22 @@ extern "C" int ndsmk_trace(const double *B, const double *G, const int32_t *n3, 
                            int nseeds, const double *seeds, double step, int max_steps, int direction, double *ends,
                            double *length, double *integral, int32_t *status, int32_t *nsteps) {
   NDSM_REQUIRE_READY();
-  if (!(step > 0.0) || !(step <= 1.0e300) || max_steps < 1 || direction < -1 || direction > 1 || nseeds < 0)
-    return ndsm::fail(NDSMK_EVALUE, "trace: step > 0 (finite), max_steps >= 1, direction in -1, 0, 1 and nseeds >= 0",
-                      __FILE__, __LINE__);
-  if (nseeds == 0) return 0;
-  NDSM_CHECK_ARG(B && seeds && ends && length && integral && status && nsteps);
-  NDSM_CHECK_ARG(n3[0] >= 2 && n3[1] >= 2 && n3[2] >= 2 && h_dq3[0] > 0.0 && h_dq3[1] > 0.0 && h_dq3[2] > 0.0);
   TrArgs p;
-  for (int d = 0; d < 3; ++d) {
-    p.n[d] = n3[d];
-    p.lo[d] = lo3[d];
-    p.h[d] = h_dq3[d];
-    p.hi[d] = lo3[d] + (double)(n3[d] - 1) * h_dq3[d];
-  }
-  p.ds = step * fmin(fmin(h_dq3[0], h_dq3[1]), h_dq3[2]);
-  p.max_steps = max_steps < kTrMaxSteps ? max_steps : kTrMaxSteps;
-  p.nseeds = nseeds;
   p.ndir = direction == 0 ? 2 : 1;
   p.sgn0 = direction < 0 ? -1 : 1;
+  const int rc = line_args("trace: step > 0 (finite), max_steps >= 1, direction in -1, 0, 1 and nseeds >= 0",
+                           direction >= -1 && direction <= 1,
+                           B && seeds && ends && length && integral && status && nsteps, n3, lo3, h_dq3, nseeds, step,
+                           max_steps, p.ndir, p);
+  if (rc != 0 || nseeds == 0) return rc;
   const size_t nl = (size_t)nseeds * (size_t)p.ndir;
-  NDSM_CHECK_ARG(nl <= (size_t)0x7fffffff);
-  const unsigned nb = (unsigned)((nl + kTrBlock - 1) / kTrBlock);
+  const unsigned nb = (unsigned)((nl + kLineBlock - 1) / kLineBlock);
   hipStream_t s = ndsm::stream();
   if (G)
-    hipLaunchKernelGGL(trace_k<true>, dim3(nb), dim3(kTrBlock), 0, s, B, G, seeds, ends, length, integral, status,
+    hipLaunchKernelGGL(trace_k<true>, dim3(nb), dim3(kLineBlock), 0, s, B, G, seeds, ends, length, integral, status,
                        nsteps, p);
   else
-    hipLaunchKernelGGL(trace_k<false>, dim3(nb), dim3(kTrBlock), 0, s, B, G, seeds, ends, length, integral, status,
+    hipLaunchKernelGGL(trace_k<false>, dim3(nb), dim3(kLineBlock), 0, s, B, G, seeds, ends, length, integral, status,
                        nsteps, p);
   NDSM_LAUNCH_CHECK();
   return 0;

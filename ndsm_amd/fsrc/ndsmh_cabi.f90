@@ -925,8 +925,8 @@ contains
     integer(c_int), value :: nseeds, max_steps, direction
     real(c_double), value :: step
     integer(c_int) :: ierr
-    ierr = vecpot_handle_trace(handle, B, G, nseeds, seeds, step, max_steps, direction, ends, length, integral, &
-                               status, nsteps, .false., "ndsm_hip_vecpot_trace")
+    ierr = vecpot_handle_lines(handle, .false., B, G, direction, nseeds, seeds, step, max_steps, c_null_ptr, ends, &
+                               length, integral, status, nsteps, .false., "ndsm_hip_vecpot_trace")
   end function
 
   ! the same on DEVICE arrays of the library's GPU (nothing is cleared: the outputs are not host memory)
@@ -937,64 +937,8 @@ contains
     integer(c_int), value :: nseeds, max_steps, direction
     real(c_double), value :: step
     integer(c_int) :: ierr
-    ierr = vecpot_handle_trace(handle, dB, dG, nseeds, dseeds, step, max_steps, direction, dends, dlength, dintegral, &
-                               dstatus, dnsteps, .true., "ndsm_hip_vecpot_trace_device")
-  end function
-
-  function vecpot_handle_trace(handle, B, G, nseeds, seeds, step, max_steps, direction, ends, length, integral, &
-                               status, nsteps, on_device, who) result(ierr)
-    type(c_ptr), intent(in) :: handle, B, G, seeds, ends, length, integral, status, nsteps
-    integer(c_int), intent(in) :: nseeds, max_steps, direction
-    real(c_double), intent(in) :: step
-    logical, intent(in) :: on_device
-    character(len=*), intent(in) :: who
-    integer(c_int) :: ierr
-    type(vecpot_ctx), pointer :: ctx
-    integer(c_int) :: rc
-    logical :: need
-    if (.not. on_device) call clear_outputs()
-    ierr = ndsmk_init(-1_c_int)                        ! without a device: 9001, whatever the arguments
-    if (ierr /= 0) return
-    ierr = NDSMK_EARG
-    if (.not. c_associated(handle)) return
-    need = nseeds > 0                                  ! no seeds: no array is looked at
-    if (need .and. .not. (c_associated(B) .and. c_associated(seeds) .and. c_associated(ends) .and. &
-                          c_associated(length) .and. c_associated(integral) .and. c_associated(status) .and. &
-                          c_associated(nsteps))) return
-    call c_f_pointer(handle, ctx)
-    if (.not. ctx%live) return
-    rc = vecpot_trace(ctx, B, G, nseeds, seeds, step, max_steps, direction, ends, length, integral, status, nsteps, &
-                      on_device)
-    if (rc /= 0) then
-      call report(who, rc)
-      if (rc < NDSMK_ENODEV) rc = NDSMK_ENODEV
-      if (.not. on_device) call clear_outputs()
-    end if
-    ierr = rc
-  contains
-    subroutine clear_outputs()
-      real(c_double), pointer :: r(:)
-      integer(c_int32_t), pointer :: k(:)
-      integer :: nl
-      if (nseeds <= 0) return
-      if (nseeds > huge(0) / 6) return
-      nl = nseeds * merge(2, 1, direction == 0)
-      if (c_associated(ends)) then
-        call c_f_pointer(ends, r, [3 * nl]); r = 0
-      end if
-      if (c_associated(length)) then
-        call c_f_pointer(length, r, [nl]); r = 0
-      end if
-      if (c_associated(integral)) then
-        call c_f_pointer(integral, r, [nl]); r = 0
-      end if
-      if (c_associated(status)) then
-        call c_f_pointer(status, k, [nl]); k = 0
-      end if
-      if (c_associated(nsteps)) then
-        call c_f_pointer(nsteps, k, [nl]); k = 0
-      end if
-    end subroutine
+    ierr = vecpot_handle_lines(handle, .false., dB, dG, direction, nseeds, dseeds, step, max_steps, c_null_ptr, dends, &
+                               dlength, dintegral, dstatus, dnsteps, .true., "ndsm_hip_vecpot_trace_device")
   end function
 
   ! ---- squashing factor and twist on the same handle ----------------------
@@ -1010,8 +954,8 @@ contains
     integer(c_int), value :: integrand, nseeds, max_steps
     real(c_double), value :: step
     integer(c_int) :: ierr
-    ierr = vecpot_handle_squash(handle, B, G, integrand, nseeds, seeds, step, max_steps, q, ends, length, integral, &
-                                status, nsteps, .false., "ndsm_hip_vecpot_squash")
+    ierr = vecpot_handle_lines(handle, .true., B, G, integrand, nseeds, seeds, step, max_steps, q, ends, length, &
+                               integral, status, nsteps, .false., "ndsm_hip_vecpot_squash")
   end function
 
   ! the same on DEVICE arrays of the library's GPU (nothing is cleared: the outputs are not host memory)
@@ -1022,16 +966,18 @@ contains
     integer(c_int), value :: integrand, nseeds, max_steps
     real(c_double), value :: step
     integer(c_int) :: ierr
-    ierr = vecpot_handle_squash(handle, dB, dG, integrand, nseeds, dseeds, step, max_steps, dq, dends, dlength, &
-                                dintegral, dstatus, dnsteps, .true., "ndsm_hip_vecpot_squash_device")
+    ierr = vecpot_handle_lines(handle, .true., dB, dG, integrand, nseeds, dseeds, step, max_steps, dq, dends, dlength, &
+                               dintegral, dstatus, dnsteps, .true., "ndsm_hip_vecpot_squash_device")
   end function
 
-  function vecpot_handle_squash(handle, B, G, integrand, nseeds, seeds, step, max_steps, q, ends, length, integral, &
-                                status, nsteps, on_device, who) result(ierr)
+  ! the four line entries above: squash false, sel = direction, q = c_null_ptr for trace; squash true, sel = integrand
+  ! for squash.  nl lines: 2 nseeds for squash and for both directions, else nseeds.
+  function vecpot_handle_lines(handle, squash, B, G, sel, nseeds, seeds, step, max_steps, q, ends, length, integral, &
+                               status, nsteps, on_device, who) result(ierr)
     type(c_ptr), intent(in) :: handle, B, G, seeds, q, ends, length, integral, status, nsteps
-    integer(c_int), intent(in) :: integrand, nseeds, max_steps
+    logical, intent(in) :: squash, on_device
+    integer(c_int), intent(in) :: sel, nseeds, max_steps
     real(c_double), intent(in) :: step
-    logical, intent(in) :: on_device
     character(len=*), intent(in) :: who
     integer(c_int) :: ierr
     type(vecpot_ctx), pointer :: ctx
@@ -1043,13 +989,13 @@ contains
     ierr = NDSMK_EARG
     if (.not. c_associated(handle)) return
     need = nseeds > 0                                  ! no seeds: no array is looked at
-    if (need .and. .not. (c_associated(B) .and. c_associated(seeds) .and. c_associated(q) .and. &
+    if (need .and. .not. (c_associated(B) .and. c_associated(seeds) .and. (c_associated(q) .or. .not. squash) .and. &
                           c_associated(ends) .and. c_associated(length) .and. c_associated(integral) .and. &
                           c_associated(status) .and. c_associated(nsteps))) return
     call c_f_pointer(handle, ctx)
     if (.not. ctx%live) return
-    rc = vecpot_squash(ctx, B, G, integrand, nseeds, seeds, step, max_steps, q, ends, length, integral, status, &
-                       nsteps, on_device)
+    rc = vecpot_lines(ctx, squash, B, G, sel, nseeds, seeds, step, max_steps, q, ends, length, integral, status, &
+                      nsteps, on_device)
     if (rc /= 0) then
       call report(who, rc)
       if (rc < NDSMK_ENODEV) rc = NDSMK_ENODEV
@@ -1063,7 +1009,7 @@ contains
       integer :: nl
       if (nseeds <= 0) return
       if (nseeds > huge(0) / 6) return
-      nl = 2 * nseeds
+      nl = nseeds * merge(2, 1, squash .or. sel == 0)
       if (c_associated(q)) then
         call c_f_pointer(q, r, [nseeds]); r = 0
       end if

@@ -32,7 +32,7 @@ module ndsmh_vecpot
 
   public :: vecpot_solve, poisson_solve
   public :: vecpot_ctx, vecpot_ctx_create, vecpot_ctx_destroy, vecpot_ctx_matches, vecpot_run, vecpot_cache_drop
-  public :: vecpot_project, vecpot_devore, vecpot_trace, vecpot_squash
+  public :: vecpot_project, vecpot_devore, vecpot_lines
   public :: VP_POTENTIAL, VP_FIELD, VP_HELICITY
   ! pieces the distributed driver (ndsmh_wvecpot) shares with vecpot_solve
   public :: face_data, face_axis, face_upper, face_t1, face_t2, face_order, face_copy, vecpot_faces, say
@@ -1043,95 +1043,25 @@ contains
   end function
 
   ! ------------------------------------------------------------------
-  ! Field lines of B from nseeds seeds, with the line integral of G along them, on a prepared context (DESIGN.md
-  ! "Field-line tracing and field-line helicity"; semantics in include/ndsm_hip.h).  The context supplies the mesh
-  ! only: first point and spacing per axis, dq as in vecpot_run.  pB, pG (pG may be c_null_ptr: integrals 0)
-  ! (nx,ny,nz,3), pseeds (3,nseeds) in; pends (3,nl), plen, pint (nl) doubles and pstat, pnst (nl) int32 out, nl =
-  ! nseeds or (direction 0) 2 nseeds: on the HOST (B, G and the seeds go up into the helicity entries' staging
-  ! arrays and a scratch buffer, the results come home) or (on_device) in HBM.  No solve, no hierarchy.
+  ! The line entries on a prepared context (semantics in include/ndsm_hip.h): field lines of B from nseeds seeds with
+  ! the line integral of G along them (squash false: ndsmk_trace, sel = direction; DESIGN.md "Field-line tracing and
+  ! field-line helicity"), or the squashing factor Q at the seeds with the two ends of the line through each (squash
+  ! true: ndsmk_squash, sel = integrand, always both directions; DESIGN.md "Squashing factor and twist").  The
+  ! context supplies the mesh only: first point and spacing per axis, dq as in vecpot_run.  No solve, no hierarchy.
+  ! pB, pG (pG may be c_null_ptr: integrals 0) (nx,ny,nz,3), pseeds (3,nseeds) in; pends (3,nl), plen, pint (nl)
+  ! doubles and pstat, pnst (nl) int32 out, nl = 2 nseeds (squash, direction 0) or nseeds; pq (nseeds) doubles out
+  ! for squash, not looked at for trace: on the HOST (B, G and the seeds go up into the helicity entries' staging
+  ! arrays and a scratch buffer, the results come home) or (on_device) in HBM.  Squash with integrand 1 and pG the
+  ! very pointer pB: G = curl_h B (ndsmk_curl into the staging array dF(2)), the twist map.
   ! ------------------------------------------------------------------
-  function vecpot_trace(ctx, pB, pG, nseeds, pseeds, step, max_steps, direction, pends, plen, pint, pstat, pnst, &
+  function vecpot_lines(ctx, squash, pB, pG, sel, nseeds, pseeds, step, max_steps, pq, pends, plen, pint, pstat, pnst, &
                         on_device) result(rc)
     type(vecpot_ctx), intent(inout), target :: ctx
-    type(c_ptr), intent(in) :: pB, pG, pseeds, pends, plen, pint, pstat, pnst
-    integer(c_int), intent(in) :: nseeds, max_steps, direction
-    real(wp), intent(in) :: step
-    logical, intent(in) :: on_device
-    integer(c_int) :: rc, rc2
-    character(len=*), parameter :: me = "trace_field_lines"
-    real(wp) :: dq(3), lo(3)
-    integer(c_int32_t) :: n3(3)
-    integer(c_size_t) :: nb, nl, ns
-    integer :: i
-    type(c_ptr) :: dB, dG, d(6)
-
-    n3 = ctx%n3
-    dq = [ctx%qx(2) - ctx%qx(1), ctx%qy(2) - ctx%qy(1), ctx%qz(2) - ctx%qz(1)]      ! as vecpot_run
-    lo = [ctx%qx(1), ctx%qy(1), ctx%qz(1)]
-    if (on_device .or. nseeds <= 0 .or. step <= 0.0_wp .or. max_steps < 1 .or. abs(direction) > 1) then
-      ! (the argument errors are ndsmk_trace's to name; nothing is staged for them)
-      rc = ndsmk_trace(pB, pG, n3, lo, dq, nseeds, pseeds, step, max_steps, direction, pends, plen, pint, pstat, pnst)
-      if (rc /= 0) return
-      rc = ndsmk_sync()
-      return
-    end if
-    nb = int(product(int(n3, ik)), c_size_t) * 24_c_size_t
-    ns = int(nseeds, c_size_t)
-    nl = ns * merge(2_c_size_t, 1_c_size_t, direction == 0)
-    ! the helicity entries' host staging: dF(1) B, dF(2) G
-    do i = 1, merge(1, 2, .not. c_associated(pG))
-      if (.not. c_associated(ctx%dF(i))) then
-        rc = ndsmk_alloc(ctx%dF(i), nb); if (rc /= 0) return
-      end if
-    end do
-    dB = ctx%dF(1)
-    dG = c_null_ptr
-    rc = ndsmk_h2d(dB, pB, nb); if (rc /= 0) return
-    if (c_associated(pG)) then
-      dG = ctx%dF(2)
-      rc = ndsmk_h2d(dG, pG, nb); if (rc /= 0) return
-    end if
-    ! seeds, ends, length, integral, status, nsteps
-    d = c_null_ptr
-    rc = ndsmk_alloc(d(1), 24_c_size_t * ns)
-    if (rc == 0) rc = ndsmk_alloc(d(2), 24_c_size_t * nl)
-    if (rc == 0) rc = ndsmk_alloc(d(3), 8_c_size_t * nl)
-    if (rc == 0) rc = ndsmk_alloc(d(4), 8_c_size_t * nl)
-    if (rc == 0) rc = ndsmk_alloc(d(5), 4_c_size_t * nl)
-    if (rc == 0) rc = ndsmk_alloc(d(6), 4_c_size_t * nl)
-    if (rc == 0) rc = ndsmk_h2d(d(1), pseeds, 24_c_size_t * ns)
-    if (rc == 0) then
-      call say(me, "Tracing field lines...")
-      rc = ndsmk_trace(dB, dG, n3, lo, dq, nseeds, d(1), step, max_steps, direction, d(2), d(3), d(4), d(5), d(6))
-    end if
-    if (rc == 0) rc = ndsmk_d2h(pends, d(2), 24_c_size_t * nl)
-    if (rc == 0) rc = ndsmk_d2h(plen, d(3), 8_c_size_t * nl)
-    if (rc == 0) rc = ndsmk_d2h(pint, d(4), 8_c_size_t * nl)
-    if (rc == 0) rc = ndsmk_d2h(pstat, d(5), 4_c_size_t * nl)
-    if (rc == 0) rc = ndsmk_d2h(pnst, d(6), 4_c_size_t * nl)
-    if (rc == 0) rc = ndsmk_sync()
-    do i = 1, 6
-      if (c_associated(d(i))) rc2 = ndsmk_free(d(i))
-    end do
-  end function
-
-  ! ------------------------------------------------------------------
-  ! Squashing factor Q of B at nseeds seeds, the two ends of the line through each and the line integral of G per
-  ! direction, on a prepared context (DESIGN.md "Squashing factor and twist"; semantics in include/ndsm_hip.h).
-  ! As vecpot_trace, always both directions: pq (nseeds) and pends (3,2 nseeds), plen, pint (2 nseeds) doubles,
-  ! pstat, pnst (2 nseeds) int32 out, on the HOST (the same staging arrays and a scratch buffer) or (on_device)
-  ! in HBM.  integrand 0: G.B/|B|, 1: G.B/|B|^2; pG the very pointer pB with integrand 1: G = curl_h B (ndsmk_curl
-  ! into the staging array dF(2)), the twist map.
-  ! ------------------------------------------------------------------
-  function vecpot_squash(ctx, pB, pG, integrand, nseeds, pseeds, step, max_steps, pq, pends, plen, pint, pstat, pnst, &
-                         on_device) result(rc)
-    type(vecpot_ctx), intent(inout), target :: ctx
+    logical, intent(in) :: squash, on_device
     type(c_ptr), intent(in) :: pB, pG, pseeds, pq, pends, plen, pint, pstat, pnst
-    integer(c_int), intent(in) :: integrand, nseeds, max_steps
+    integer(c_int), intent(in) :: sel, nseeds, max_steps
     real(wp), intent(in) :: step
-    logical, intent(in) :: on_device
     integer(c_int) :: rc, rc2
-    character(len=*), parameter :: me = "squashing_factor"
     real(wp) :: dq(3), lo(3)
     integer(c_int32_t) :: n3(3)
     integer(c_size_t) :: nb, nl, ns
@@ -1142,17 +1072,19 @@ contains
     n3 = ctx%n3
     dq = [ctx%qx(2) - ctx%qx(1), ctx%qy(2) - ctx%qy(1), ctx%qz(2) - ctx%qz(1)]      ! as vecpot_run
     lo = [ctx%qx(1), ctx%qy(1), ctx%qz(1)]
-    if (nseeds <= 0 .or. step <= 0.0_wp .or. max_steps < 1 .or. integrand < 0 .or. integrand > 1) then
-      ! (the argument errors are ndsmk_squash's to name; nothing is staged for them)
-      rc = ndsmk_squash(pB, pG, integrand, n3, lo, dq, nseeds, pseeds, step, max_steps, pq, pends, plen, pint, pstat, &
-                        pnst)
+    if (nseeds <= 0 .or. step <= 0.0_wp .or. max_steps < 1 .or. sel < merge(0, -1, squash) .or. sel > 1) then
+      ! (the argument errors are the kernel entry's to name; nothing is staged for them)
+      rc = launch(pB, pG, pseeds, pq, pends, plen, pint, pstat, pnst)
+      ! (trace synchronises here, squash does not: ndsmk_sync can return an earlier asynchronous error, so the call
+      ! is part of what each entry returns)
+      if (rc == 0 .and. .not. squash) rc = ndsmk_sync()
       return
     end if
     nb = int(product(int(n3, ik)), c_size_t) * 24_c_size_t
     ns = int(nseeds, c_size_t)
-    nl = 2_c_size_t * ns
+    nl = ns * merge(2_c_size_t, 1_c_size_t, squash .or. sel == 0)
     ! G given as B itself with integrand 1: the twist map, G = curl_h B formed here in the staging array dF(2)
-    own_curl = integrand == 1 .and. c_associated(pG) .and. c_associated(pG, pB)
+    own_curl = squash .and. sel == 1 .and. c_associated(pG) .and. c_associated(pG, pB)
     ! the helicity entries' host staging: dF(1) B, dF(2) G
     need = [.not. on_device, own_curl .or. (.not. on_device .and. c_associated(pG))]
     do i = 1, 2
@@ -1174,12 +1106,11 @@ contains
     end if
     if (own_curl) then
       dG = ctx%dF(2)
-      call say(me, "G = curl(B)...")
+      call say("squashing_factor", "G = curl(B)...")
       rc = ndsmk_curl(dB, dG, n3, dq); if (rc /= 0) return
     end if
     if (on_device) then
-      rc = ndsmk_squash(dB, dG, integrand, n3, lo, dq, nseeds, pseeds, step, max_steps, pq, pends, plen, pint, pstat, &
-                        pnst)
+      rc = launch(dB, dG, pseeds, pq, pends, plen, pint, pstat, pnst)
       if (rc /= 0) return
       rc = ndsmk_sync()
       return
@@ -1192,13 +1123,17 @@ contains
     if (rc == 0) rc = ndsmk_alloc(d(4), 8_c_size_t * nl)
     if (rc == 0) rc = ndsmk_alloc(d(5), 4_c_size_t * nl)
     if (rc == 0) rc = ndsmk_alloc(d(6), 4_c_size_t * nl)
-    if (rc == 0) rc = ndsmk_alloc(d(7), 8_c_size_t * ns)
+    if (rc == 0 .and. squash) rc = ndsmk_alloc(d(7), 8_c_size_t * ns)
     if (rc == 0) rc = ndsmk_h2d(d(1), pseeds, 24_c_size_t * ns)
     if (rc == 0) then
-      call say(me, "Tracing field lines with their deviation vectors...")
-      rc = ndsmk_squash(dB, dG, integrand, n3, lo, dq, nseeds, d(1), step, max_steps, d(7), d(2), d(3), d(4), d(5), d(6))
+      if (squash) then
+        call say("squashing_factor", "Tracing field lines with their deviation vectors...")
+      else
+        call say("trace_field_lines", "Tracing field lines...")
+      end if
+      rc = launch(dB, dG, d(1), d(7), d(2), d(3), d(4), d(5), d(6))
     end if
-    if (rc == 0) rc = ndsmk_d2h(pq, d(7), 8_c_size_t * ns)
+    if (rc == 0 .and. squash) rc = ndsmk_d2h(pq, d(7), 8_c_size_t * ns)
     if (rc == 0) rc = ndsmk_d2h(pends, d(2), 24_c_size_t * nl)
     if (rc == 0) rc = ndsmk_d2h(plen, d(3), 8_c_size_t * nl)
     if (rc == 0) rc = ndsmk_d2h(pint, d(4), 8_c_size_t * nl)
@@ -1208,6 +1143,18 @@ contains
     do i = 1, 7
       if (c_associated(d(i))) rc2 = ndsmk_free(d(i))
     end do
+  contains
+    ! the kernel entry of this call on the given arrays (q: looked at by squash only)
+    function launch(B, G, seeds, q, ends, length, integral, status, nsteps) result(rc)
+      type(c_ptr), intent(in) :: B, G, seeds, q, ends, length, integral, status, nsteps
+      integer(c_int) :: rc
+      if (squash) then
+        rc = ndsmk_squash(B, G, sel, n3, lo, dq, nseeds, seeds, step, max_steps, q, ends, length, integral, status, &
+                          nsteps)
+      else
+        rc = ndsmk_trace(B, G, n3, lo, dq, nseeds, seeds, step, max_steps, sel, ends, length, integral, status, nsteps)
+      end if
+    end function
   end function
 
   ! B.n of face f (1..6) from the host field (extract_bn, :699-743)

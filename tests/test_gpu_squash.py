@@ -1,10 +1,11 @@
 """GPU tests of the squashing-factor and twist maps (run with -m gpu on an MI355X): VecPot.squashing,
 squashing_factor.  The yardsticks are a numpy restatement of the semantics in include/ndsm_hip.h
-(ndsm_hip_vecpot_squash; bit for bit) and closed forms: a uniform field (Q depends on the pair of faces only), a
-hyperbolic field B = (alpha (x - xc), -alpha (y - yc), B0) (Q = 2 cosh(2 alpha Lz / B0) bottom to top, and a closed
-form for lines that leave through a side face), the helical field of the trace tests (Q = 2 and the twist number),
-the invariance of Q along a line and finite differences of the foot points VecPot.trace gives.  Every test runs on
-golden_inputs.aniso_mesh (unequal spacings, no origin at 0) and on a uniform mesh, with unequal nx, ny, nz.
+(ndsm_hip_vecpot_squash: line_model.squash_numpy; bit for bit) and closed forms: a uniform field (Q depends on the pair
+of faces only), a hyperbolic field B = (alpha (x - xc), -alpha (y - yc), B0) (Q = 2 cosh(2 alpha Lz / B0) bottom to
+top, and a closed form for lines that leave through a side face), the helical field of the trace tests (Q = 2 and the
+twist number), the invariance of Q along a line and finite differences of the foot points VecPot.trace gives.  Every
+test runs on golden_inputs.aniso_mesh (unequal spacings, no origin at 0) and on a uniform mesh, with unequal nx, ny,
+nz.
 
 The closed-form checks are functions of a `run(mesh, b, seeds, **options)` callable, so that the same checks can be
 run with squash_numpy in place of the library (model_run) on a machine without a GPU."""
@@ -12,14 +13,12 @@ import numpy as np
 import pytest
 
 from golden_inputs import aniso_mesh, uniform_mesh
-from test_gpu_trace import (abc, axis_of, box, centre, face_seeds, grids, helical, inner_seeds, lib_trace,
-                            trace_numpy)
+from line_model import (FACES, NULL, OUTSIDE, UNFINISHED, abc, axis_of, box, centre, face_seeds, grids, helical,
+                        hyperbolic, inner_seeds, patch_feet, sheared, squash_numpy, trace_numpy, uniform_b)
 
 pytestmark = pytest.mark.gpu
 
 MESHES = {"uniform": uniform_mesh, "aniso": aniso_mesh}
-FACES = range(1, 7)
-NULL, UNFINISHED, OUTSIDE = 7, 8, 9
 
 
 @pytest.fixture(scope="module")
@@ -32,6 +31,15 @@ def hip():
     return _lib
 
 
+def lib_trace(mesh, b, seeds, **kw):
+    import ndsm_amd
+    V = ndsm_amd.VecPot(*mesh)
+    try:
+        return V.trace(b, seeds, **kw)
+    finally:
+        V.close()
+
+
 def lib_run(mesh, b, seeds, **kw):
     import ndsm_amd
     V = ndsm_amd.VecPot(*mesh)
@@ -39,206 +47,6 @@ def lib_run(mesh, b, seeds, **kw):
         return V.squashing(b, seeds, **kw)
     finally:
         V.close()
-
-
-# ---------------------------------------------------------------------------------------------------------------
-# the numpy restatement of include/ndsm_hip.h (ndsm_hip_vecpot_squash), vectorised over the 2 nseeds lines
-# ---------------------------------------------------------------------------------------------------------------
-def squash_numpy(mesh, b, g, seeds, step, max_steps, integrand=0):
-    """(q, ends, length, integral, status, nsteps) with the shapes of QMap: q (ns), the others (2, ns[, 3])"""
-    lo, h, hi, n = box(mesh)
-    nx, ny = int(n[0]), int(n[1])
-    ds = step * min(h[0], h[1], h[2])
-    bf = b.reshape(3, -1)
-    gf = None if g is None else g.reshape(3, -1)
-
-    def cell(P):
-        u = (P - lo) / h
-        c = np.minimum(np.maximum(np.floor(u), 0.0), n - 2.0)
-        f = u - c
-        ci = c.astype(np.int64)
-        return ci[:, 0] + nx * (ci[:, 1] + ny * ci[:, 2]), f[:, 0], f[:, 1], f[:, 2]
-
-    def lerp(q, base, fx, fy, fz, grad):
-        v = [q[base], q[base + 1], q[base + nx], q[base + nx + 1], q[base + nx * ny], q[base + nx * ny + 1],
-             q[base + nx * ny + nx], q[base + nx * ny + nx + 1]]
-        d00, d10, d01, d11 = v[1] - v[0], v[3] - v[2], v[5] - v[4], v[7] - v[6]
-        c00 = v[0] + fx * d00
-        c10 = v[2] + fx * d10
-        c01 = v[4] + fx * d01
-        c11 = v[6] + fx * d11
-        e0, e1 = c10 - c00, c11 - c01
-        c0 = c00 + fy * e0
-        c1 = c01 + fy * e1
-        dz = c1 - c0
-        val = c0 + fz * dz
-        if not grad:
-            return val
-        dx0 = d00 + fy * (d10 - d00)
-        dx1 = d01 + fy * (d11 - d01)
-        return val, [(dx0 + fz * (dx1 - dx0)) / h[0], (e0 + fz * (e1 - e0)) / h[1], dz / h[2]]
-
-    def field(P):
-        base, fx, fy, fz = cell(P)
-        return [lerp(bf[c], base, fx, fy, fz, False) for c in range(3)]
-
-    def stage(P, U, V, sgn):
-        """ok, the ten slopes (k of r, U, V as (n,3) arrays and of I), e = B/|B| and |B|^2 at P"""
-        base, fx, fy, fz = cell(P)
-        bv, M = [], []
-        for c in range(3):
-            val, gr = lerp(bf[c], base, fx, fy, fz, True)
-            bv.append(val)
-            M.append(gr)
-        m2 = (bv[0] * bv[0] + bv[1] * bv[1]) + bv[2] * bv[2]
-        m = np.sqrt(m2)
-        ok = m > 0.0
-        ms = np.where(ok, m, 1.0)
-        e = [bv[c] / ms for c in range(3)]
-        kr = np.stack([sgn * e[c] for c in range(3)], axis=1)
-        kU = np.stack([sgn * (((M[c][0] * U[:, 0] + M[c][1] * U[:, 1]) + M[c][2] * U[:, 2]) / ms) for c in range(3)],
-                      axis=1)
-        kV = np.stack([sgn * (((M[c][0] * V[:, 0] + M[c][1] * V[:, 1]) + M[c][2] * V[:, 2]) / ms) for c in range(3)],
-                      axis=1)
-        if gf is None:
-            q = np.zeros(len(P))
-        else:
-            gv = [lerp(gf[c], base, fx, fy, fz, False) for c in range(3)]
-            q = (gv[0] * e[0] + gv[1] * e[1]) + gv[2] * e[2]
-            if integrand == 1:
-                q = q / ms
-        return ok, (kr, kU, kV, q), e, m2
-
-    def rk4(r, U, V, sgn, k1, s):
-        """stages 2-4 of a step of length s (per line) from (r, U, V) with the slopes k1; a line that met a null
-        stays where it is for the later stages (its result is not used)"""
-        hs, s6 = (0.5 * s)[:, None], (s / 6.0)[:, None]
-        sc = s[:, None]
-        ok2, k2, _e, _m = stage(r + hs * k1[0], U + hs * k1[1], V + hs * k1[2], sgn)
-        acc = [k1[i] + 2.0 * k2[i] for i in range(4)]
-        k2 = [np.where(ok2[:, None], k2[i], 0.0) for i in range(3)]
-        ok3, k3, _e, _m = stage(r + hs * k2[0], U + hs * k2[1], V + hs * k2[2], sgn)
-        acc = [acc[i] + 2.0 * k3[i] for i in range(4)]
-        ok = ok2 & ok3
-        k3 = [np.where(ok[:, None], k3[i], 0.0) for i in range(3)]
-        ok4, k4, _e, _m = stage(r + sc * k3[0], U + sc * k3[1], V + sc * k3[2], sgn)
-        acc = [acc[i] + k4[i] for i in range(4)]
-        ok = ok & ok4
-        return ok, r + s6 * acc[0], U + s6 * acc[1], V + s6 * acc[2], s6[:, 0] * acc[3]
-
-    ns = len(seeds)
-    nl = 2 * ns
-    r = np.concatenate([np.array(seeds, dtype=np.float64)] * 2)
-    sg = np.concatenate([np.full(ns, 1.0), np.full(ns, -1.0)])
-    U, V = np.zeros((nl, 3)), np.zeros((nl, 3))
-    length, integral = np.zeros(nl), np.zeros(nl)
-    status = np.full(nl, UNFINISHED, dtype=np.int32)
-    nsteps = np.zeros(nl, dtype=np.int32)
-    bs2 = np.full(nl, np.nan)
-    with np.errstate(invalid="ignore"):
-        inside = np.all((r >= lo) & (r <= hi), axis=1)
-    status[~inside] = OUTSIDE
-    act = np.nonzero(inside)[0]
-    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
-        for it in range(max_steps):
-            if len(act) == 0:
-                break
-            ra, sa = r[act], sg[act]
-            if it == 0:
-                # the frame at the seed: U0 perpendicular to e from the axis of the smallest |e_d|, V0 = e x U0
-                e = np.stack(field(ra), axis=1)
-                m2 = (e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1]) + e[:, 2] * e[:, 2]
-                mm = np.sqrt(m2)
-                okm = mm > 0.0
-                e = e / np.where(okm, mm, 1.0)[:, None]
-                ae = np.abs(e)
-                j = np.zeros(len(act), dtype=np.int64)
-                small = ae[:, 0].copy()
-                for d in (1, 2):
-                    take = ae[:, d] < small
-                    j = np.where(take, d, j)
-                    small = np.where(take, ae[:, d], small)
-                ej = e[np.arange(len(act)), j]
-                w = np.stack([np.where(j == d, 1.0, 0.0) - ej * e[:, d] for d in range(3)], axis=1)
-                wn = np.sqrt((w[:, 0] * w[:, 0] + w[:, 1] * w[:, 1]) + w[:, 2] * w[:, 2])
-                u0 = w / wn[:, None]
-                v0 = np.stack([e[:, 1] * u0[:, 2] - e[:, 2] * u0[:, 1], e[:, 2] * u0[:, 0] - e[:, 0] * u0[:, 2],
-                               e[:, 0] * u0[:, 1] - e[:, 1] * u0[:, 0]], axis=1)
-                U[act] = np.where(okm[:, None], u0, 0.0)
-                V[act] = np.where(okm[:, None], v0, 0.0)
-                bs2[act] = m2
-            Ua, Va = U[act], V[act]
-            ok1, k1, _e, _m2 = stage(ra, Ua, Va, sa)
-            k1 = [np.where(ok1[:, None], k1[i], 0.0) for i in range(3)] + [k1[3]]
-            okr, rn, Un, Vn, dI = rk4(ra, Ua, Va, sa, k1, np.full(len(act), ds))
-            ok = ok1 & okr
-            rn = np.where(ok[:, None], rn, ra)
-            t = np.full(len(act), 2.0)
-            face = np.zeros(len(act), dtype=np.int32)
-            for d in range(3):
-                below, above = rn[:, d] < lo[d], rn[:, d] > hi[d]
-                den = np.where(below | above, rn[:, d] - ra[:, d], 1.0)
-                td = np.where(below, (lo[d] - ra[:, d]) / den, np.where(above, (hi[d] - ra[:, d]) / den, 2.0))
-                fd = np.where(below, 1 + 2 * d, np.where(above, 2 + 2 * d, 0))
-                take = td < t
-                t = np.where(take, td, t)
-                face = np.where(take, fd, face).astype(np.int32)
-            leave = ok & (face != 0)
-            go = ok & ~leave
-            ia = act
-            r[ia[go]], U[ia[go]], V[ia[go]] = rn[go], Un[go], Vn[go]
-            length[ia[go]] = length[ia[go]] + ds
-            integral[ia[go]] = integral[ia[go]] + dI[go]
-            nsteps[ia[go]] = it + 1
-            status[ia[~ok]] = NULL
-            act = ia[go]
-            if not leave.any():
-                continue
-            # the exit step: redone with s = t ds, then two refinements of s, each a full step from the same state
-            il = ia[leave]
-            rl, Ul, Vl, sl = ra[leave], Ua[leave], Va[leave], sa[leave]
-            kl = [k[leave] for k in k1]
-            fl = face[leave]
-            ax = (fl - 1) >> 1
-            rows = np.arange(len(il))
-            fv = np.where((fl - 1) & 1, hi[ax], lo[ax])
-            s = t[leave] * ds
-            okx, rx, Ux, Vx, dIx = rk4(rl, Ul, Vl, sl, kl, s)
-            for _pass in range(2):
-                den = rx[rows, ax] - rl[rows, ax]
-                can = okx & (den != 0.0)
-                s = np.where(can, s * (fv - rl[rows, ax]) / np.where(can, den, 1.0), s)
-                okn, rx2, Ux2, Vx2, dIx2 = rk4(rl, Ul, Vl, sl, kl, s)
-                okx = okx & okn
-                rx, Ux, Vx, dIx = rx2, Ux2, Vx2, dIx2
-            snapped = np.minimum(np.maximum(rx, lo), hi)
-            snapped[rows, ax] = fv
-            done = okx
-            r[il[done]], U[il[done]], V[il[done]] = snapped[done], Ux[done], Vx[done]
-            length[il[done]] = length[il[done]] + s[done]
-            integral[il[done]] = integral[il[done]] + dIx[done]
-            nsteps[il[done]] = it + 1
-            status[il[done]] = fl[done]
-            status[il[~done]] = NULL
-        # the two ends of each seed: deviation vectors projected onto the face along B there
-        onface = (status >= 1) & (status <= 6)
-        ax = np.where(onface, (status - 1) >> 1, 0)
-        rows = np.arange(nl)
-        be = np.stack(field(np.where(onface[:, None], r, lo[None, :])), axis=1)
-        bax = be[rows, ax]
-        Ut = U - (U[rows, ax] / bax)[:, None] * be
-        Vt = V - (V[rows, ax] / bax)[:, None] * be
-        uu = (Ut[:, 0] * Ut[:, 0] + Ut[:, 1] * Ut[:, 1]) + Ut[:, 2] * Ut[:, 2]
-        vv = (Vt[:, 0] * Vt[:, 0] + Vt[:, 1] * Vt[:, 1]) + Vt[:, 2] * Vt[:, 2]
-        uv = (Ut[:, 0] * Vt[:, 0] + Ut[:, 1] * Vt[:, 1]) + Ut[:, 2] * Vt[:, 2]
-        bn = np.abs(bax)
-        F, B = slice(0, ns), slice(ns, nl)
-        num = (uu[F] * vv[B] + uu[B] * vv[F]) - 2.0 * (uv[F] * uv[B])
-        q = ((num * bn[F]) * bn[B]) / bs2[F]
-        good = onface[F] & onface[B] & (bn[F] > 0.0) & (bn[B] > 0.0)
-        q = np.where(good, q, np.nan)
-    return (q, r.reshape(2, ns, 3), length.reshape(2, ns), integral.reshape(2, ns), status.reshape(2, ns),
-            nsteps.reshape(2, ns))
 
 
 class _Map:
@@ -266,30 +74,6 @@ def model_run(mesh, b, seeds, g=None, integrand=0, twist=False, step=0.5, max_st
     if twist:
         tw = np.where(np.isnan(out[0]), np.nan, (out[3][0] + out[3][1]) / (4.0 * np.pi))
     return _Map(out, tw)
-
-
-# ---------------------------------------------------------------------------------------------------------------
-# fields
-# ---------------------------------------------------------------------------------------------------------------
-def uniform_b(mesh, bv=(0.3, -0.2, 0.9)):
-    X, _Y, _Z = grids(mesh)
-    return np.stack([np.full(X.shape, v) for v in bv])
-
-
-def hyperbolic(mesh, alpha, b0=1.0):
-    X, Y, _Z = grids(mesh)
-    xc, yc = axis_of(mesh)
-    return np.stack([alpha * (X - xc), -alpha * (Y - yc), np.full(X.shape, b0)])
-
-
-def sheared(mesh, alpha=0.5, beta=0.8, gamma=1.0, b0=1.0):
-    """B = (alpha x' + beta y' z' + gamma y'^2, -alpha y' + beta x' z' + gamma x'^2, B0): divergence-free, no null,
-    a foot-point mapping that is not linear in (x, y)"""
-    X, Y, Z = grids(mesh)
-    xc, yc = axis_of(mesh)
-    x, y, z = X - xc, Y - yc, Z - mesh[2][0]
-    return np.stack([alpha * x + beta * y * z + gamma * y * y, -alpha * y + beta * x * z + gamma * x * x,
-                     np.full(X.shape, b0)])
 
 
 def rel(a, b):
@@ -416,13 +200,6 @@ def numpy_tracer(mesh, b, seeds, step=0.5, max_steps=None, direction="forward"):
     fl.ends, fl.length, fl.integral = out[0][None], out[1][None], out[2][None]
     fl.status, fl.nsteps = out[3][None], out[4][None]
     return fl
-
-
-def patch_feet(mesh, n=6, span=(0.3, 0.7)):
-    lo, _h, hi, _n = box(mesh)
-    u = np.linspace(span[0], span[1], n)
-    gx, gy = np.meshgrid(lo[0] + u * (hi[0] - lo[0]), lo[1] + u * (hi[1] - lo[1]), indexing="ij")
-    return np.stack([gx.reshape(-1), gy.reshape(-1), np.full(n * n, lo[2])], axis=1)
 
 
 def along_line_spread(run, tracer, mesh, step=0.5):

@@ -1,20 +1,20 @@
 """GPU tests of field-line tracing and field-line helicity (run with -m gpu on an MI355X): VecPot.trace,
 trace_field_lines, field_line_helicity.  The yardsticks are a numpy restatement of the semantics in
-include/ndsm_hip.h (bit for bit) and closed-form fields: a uniform field (straight lines, exact integrals), a
-linear helical field B = (-eps (y - yc), eps (x - xc), B0) (trilinear interpolation is exact, only the integrator
-errs), its B0 = 0 form (closed circles), fields with zeros and NaNs, and the identity
+include/ndsm_hip.h (line_model.trace_numpy; bit for bit) and closed-form fields: a uniform field (straight lines,
+exact integrals), a linear helical field B = (-eps (y - yc), eps (x - xc), B0) (trilinear interpolation is exact, only
+the integrator errs), its B0 = 0 form (closed circles), fields with zeros and NaNs, and the identity
 sum over entering feet of flh |B.n| dS = int A.B dV.  Every mesh-dependent test runs on golden_inputs.aniso_mesh
 (unequal spacings, no origin at 0) as well as on a uniform mesh, with unequal nx, ny, nz."""
 import numpy as np
 import pytest
 
 from golden_inputs import aniso_mesh, uniform_mesh
+from line_model import (FACES, NULL, OUTSIDE, UNFINISHED, abc, axis_of, box, centre, entering_feet, face_seeds, grids,
+                        helical, inner_seeds, trace_numpy, weights1)
 
 pytestmark = pytest.mark.gpu
 
 MESHES = {"uniform": uniform_mesh, "aniso": aniso_mesh}
-FACES = range(1, 7)          # TRACE_XLO .. TRACE_ZHI
-NULL, UNFINISHED, OUTSIDE = 7, 8, 9
 
 
 @pytest.fixture(scope="module")
@@ -36,164 +36,6 @@ def lib_trace(mesh, b, seeds, g=None, step=0.5, max_steps=None, direction="both"
         V.close()
 
 
-def box(mesh):
-    """lo, h, hi per axis as the library forms them: h = q[1] - q[0], hi = lo + (n - 1) h"""
-    lo = np.array([q[0] for q in mesh])
-    h = np.array([q[1] - q[0] for q in mesh])
-    n = np.array([len(q) for q in mesh])
-    return lo, h, lo + (n - 1.0) * h, n
-
-
-def grids(mesh):
-    return np.meshgrid(mesh[2], mesh[1], mesh[0], indexing="ij")[::-1]   # X, Y, Z, each (nz, ny, nx)
-
-
-def weights1(q):
-    w = np.full(len(q), q[1] - q[0])
-    w[0] = w[-1] = 0.5 * (q[1] - q[0])
-    return w
-
-
-# ---------------------------------------------------------------------------------------------------------------
-# the numpy restatement of include/ndsm_hip.h, vectorised over the lines of one direction
-# ---------------------------------------------------------------------------------------------------------------
-def trace_numpy(mesh, b, g, seeds, step, max_steps, sgn):
-    lo, h, hi, n = box(mesh)
-    nx, ny = int(n[0]), int(n[1])
-    ds = step * min(h[0], h[1], h[2])
-    bf = b.reshape(3, -1)
-    gf = None if g is None else g.reshape(3, -1)
-
-    def interp(F, P):
-        u = (P - lo) / h
-        c = np.minimum(np.maximum(np.floor(u), 0.0), n - 2.0)
-        f = u - c
-        ci = c.astype(np.int64)
-        base = ci[:, 0] + nx * (ci[:, 1] + ny * ci[:, 2])
-        fx, fy, fz = f[:, 0], f[:, 1], f[:, 2]
-        out = []
-        for m in range(3):
-            q = F[m]
-            v = [q[base], q[base + 1], q[base + nx], q[base + nx + 1], q[base + nx * ny], q[base + nx * ny + 1],
-                 q[base + nx * ny + nx], q[base + nx * ny + nx + 1]]
-            c00 = v[0] + fx * (v[1] - v[0])
-            c10 = v[2] + fx * (v[3] - v[2])
-            c01 = v[4] + fx * (v[5] - v[4])
-            c11 = v[6] + fx * (v[7] - v[6])
-            c0 = c00 + fy * (c10 - c00)
-            c1 = c01 + fy * (c11 - c01)
-            out.append(c0 + fz * (c1 - c0))
-        return out
-
-    def stage(P):
-        bx, by, bz = interp(bf, P)
-        m = np.sqrt((bx * bx + by * by) + bz * bz)
-        ok = m > 0.0
-        ms = np.where(ok, m, 1.0)
-        ex, ey, ez = bx / ms, by / ms, bz / ms
-        k = np.stack([sgn * ex, sgn * ey, sgn * ez], axis=1)
-        if gf is None:
-            q = np.zeros(len(P))
-        else:
-            gx, gy, gz = interp(gf, P)
-            q = (gx * ex + gy * ey) + gz * ez
-        return ok, k, q
-
-    def rk4(r, k1, q1, s):
-        """stages 2-4 of a step of length s (per line); a line that met a null stays at r for the later stages"""
-        hs, s6 = (0.5 * s)[:, None], s / 6.0
-        ok2, k2, q2 = stage(r + hs * k1)
-        ok3, k3, q3 = stage(np.where(ok2[:, None], r + hs * k2, r))
-        ok = ok2 & ok3
-        ok4, k4, q4 = stage(np.where(ok[:, None], r + s[:, None] * k3, r))
-        ok = ok & ok4
-        rn = r + s6[:, None] * (((k1 + 2.0 * k2) + 2.0 * k3) + k4)
-        dI = s6 * (((q1 + 2.0 * q2) + 2.0 * q3) + q4)
-        return ok, rn, dI
-
-    ns = len(seeds)
-    r = np.array(seeds, dtype=np.float64)
-    length, integral = np.zeros(ns), np.zeros(ns)
-    status = np.full(ns, UNFINISHED, dtype=np.int32)
-    nsteps = np.zeros(ns, dtype=np.int32)
-    with np.errstate(invalid="ignore"):
-        inside = np.all((r >= lo) & (r <= hi), axis=1)
-    status[~inside] = OUTSIDE
-    act = np.nonzero(inside)[0]
-    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
-        for it in range(max_steps):
-            if len(act) == 0:
-                break
-            ra = r[act]
-            ok1, k1, q1 = stage(ra)
-            okr, rn, dI = rk4(ra, np.where(ok1[:, None], k1, 0.0), q1, np.full(len(act), ds))
-            ok = ok1 & okr
-            rn = np.where(ok[:, None], rn, ra)
-            t = np.full(len(act), 2.0)
-            face = np.zeros(len(act), dtype=np.int32)
-            for d in range(3):
-                below, above = rn[:, d] < lo[d], rn[:, d] > hi[d]
-                den = np.where(below | above, rn[:, d] - ra[:, d], 1.0)
-                td = np.where(below, (lo[d] - ra[:, d]) / den, np.where(above, (hi[d] - ra[:, d]) / den, 2.0))
-                fd = np.where(below, 1 + 2 * d, np.where(above, 2 + 2 * d, 0))
-                take = td < t
-                t = np.where(take, td, t)
-                face = np.where(take, fd, face).astype(np.int32)
-            leave = ok & (face != 0)
-            # the exit step, redone with s = t ds
-            s = np.where(leave, t * ds, ds)
-            ok2, rn2, dI2 = rk4(ra, np.where(ok1[:, None], k1, 0.0), q1, s)
-            null = ~ok | (leave & ~ok2)
-            leave = leave & ok2
-            ax = (face - 1) >> 1
-            fv = np.where(((face - 1) & 1)[:, None] == 1, hi[None, :], lo[None, :])
-            snapped = np.minimum(np.maximum(rn2, lo), hi)
-            snapped = np.where(np.arange(3)[None, :] == ax[:, None], fv, snapped)
-            go = ok & ~leave & ~null
-            ia = act
-            r[ia[go]] = rn[go]
-            length[ia[go]] = length[ia[go]] + ds
-            integral[ia[go]] = integral[ia[go]] + dI[go]
-            nsteps[ia[go]] = it + 1
-            r[ia[leave]] = snapped[leave]
-            length[ia[leave]] = length[ia[leave]] + s[leave]
-            integral[ia[leave]] = integral[ia[leave]] + dI2[leave]
-            nsteps[ia[leave]] = it + 1
-            status[ia[leave]] = face[leave]
-            status[ia[null]] = NULL
-            act = ia[go]
-    return r, length, integral, status, nsteps
-
-
-# ---------------------------------------------------------------------------------------------------------------
-# fields
-# ---------------------------------------------------------------------------------------------------------------
-def abc(mesh, k=np.pi, phase=0.0):
-    X, Y, Z = grids(mesh)
-    return np.stack([np.sin(k * Z + phase) + np.cos(k * Y), np.sin(k * X) + np.cos(k * Z + phase),
-                     np.sin(k * Y) + np.cos(k * X)])
-
-
-def centre(mesh):
-    lo, _h, hi, _n = box(mesh)
-    return 0.5 * (lo + hi)
-
-
-def helical(mesh, eps=1.5, b0=1.0, axis=(0.5, 0.5)):
-    """B = (-eps (y - yc), eps (x - xc), b0) and a vector potential of it, A = (-b0 y / 2, b0 x / 2,
-    -eps ((x - xc)^2 + (y - yc)^2) / 2); the axis (xc, yc) at the fractions `axis` of the box's x and y extent"""
-    X, Y, Z = grids(mesh)
-    xc, yc = axis_of(mesh, axis)
-    b = np.stack([-eps * (Y - yc), eps * (X - xc), np.full(X.shape, b0)])
-    a = np.stack([-0.5 * b0 * Y, 0.5 * b0 * X, -0.5 * eps * ((X - xc) ** 2 + (Y - yc) ** 2)])
-    return b, a
-
-
-def axis_of(mesh, axis=(0.5, 0.5)):
-    lo, _h, hi, _n = box(mesh)
-    return lo[0] + axis[0] * (hi[0] - lo[0]), lo[1] + axis[1] * (hi[1] - lo[1])
-
-
 # The sum-rule tests put the axis well outside the box, beyond its lower x-y corner.  (1) With this A, A.B = eps b0 / 2
 # (xc (x - xc) + yc (y - yc)), whose volume integral vanishes identically about a centred axis: nothing to compare
 # against.  (2) The projected lines are circles about the axis; a circle touches a face x = const only at y = yc and
@@ -206,49 +48,6 @@ def axis_of(mesh, axis=(0.5, 0.5)):
 # numpy restatement the signed gaps at n = 16, 32, 64 are +3.5e-3, +9.6e-4, +2.3e-4 (aniso) and +3.1e-3, +6.5e-4,
 # +1.6e-4 (uniform) for this axis; one at -0.3 of the extent changes sign between n = 32 and 64.
 OFF_CENTRE = (-1.5, -1.5)
-
-
-def face_seeds(mesh, rng, per_face):
-    """random points exactly on each of the six faces"""
-    lo, _h, hi, _n = box(mesh)
-    out = []
-    for d in range(3):
-        for v in (lo[d], hi[d]):
-            p = lo + (hi - lo) * rng.uniform(0.0, 1.0, (per_face, 3))
-            p[:, d] = v
-            out.append(p)
-    return np.concatenate(out)
-
-
-def inner_seeds(mesh, rng, count, margin=0.0):
-    lo, _h, hi, _n = box(mesh)
-    return lo + (hi - lo) * rng.uniform(margin, 1.0 - margin, (count, 3))
-
-
-def entering_feet(mesh, b):
-    """the nodes of the six faces where B points into the box: seeds (m,3) and |B.n| times the trapezoid weight of
-    the node in its face"""
-    ws = [weights1(q) for q in mesh]
-    X, Y, Z = grids(mesh)
-    P = np.stack([X, Y, Z], axis=-1)                        # (nz, ny, nx, 3)
-    W = [ws[2][:, None, None] * ws[1][None, :, None] * np.ones(len(mesh[0]))[None, None, :],
-         ws[2][:, None, None] * np.ones(len(mesh[1]))[None, :, None] * ws[0][None, None, :],
-         np.ones(len(mesh[2]))[:, None, None] * ws[1][None, :, None] * ws[0][None, None, :]]   # weight without axis d
-    lo, _h, hi, _n = box(mesh)
-    seeds, flux = [], []
-    for d in range(3):
-        for side, inward in ((0, 1.0), (-1, -1.0)):
-            sl = [slice(None)] * 3
-            sl[2 - d] = side
-            sl = tuple(sl)
-            bn = inward * b[d][sl]
-            p = P[sl].reshape(-1, 3).copy()
-            p = np.minimum(np.maximum(p, lo), hi)          # (a mesh's last point can exceed the library's hi by an ulp)
-            p[:, d] = lo[d] if side == 0 else hi[d]
-            m = bn.reshape(-1) > 0.0
-            seeds.append(p[m])
-            flux.append((bn * W[d][sl]).reshape(-1)[m])
-    return np.concatenate(seeds), np.concatenate(flux)
 
 
 def volume_sum(mesh, a, b):

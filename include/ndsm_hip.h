@@ -397,6 +397,67 @@ int ndsm_hip_vecpot_squash_device(void *h, const double *dB, const double *dG, i
                                   const double *dseeds, double step, int max_steps, double *dq, double *dends,
                                   double *dlength, double *dintegral, int32_t *dstatus, int32_t *dnsteps);
 
+/* ---- Null points of a field on the same handle (DESIGN.md "Null points") ---------------------------------------------
+ * Where B = 0 and of what type: the other half of a field's skeleton next to the squashing factor (the trace and
+ * squash entries end a line with NDSM_HIP_TRACE_NULL when it runs into one).  The field is the trilinear interpolant
+ * of the trace entries in each of the (nx-1)(ny-1)(nz-1) cells - the same corners v0 .. v7 per component (x fastest),
+ * the same operand order: along x, c00 = v0 + fx (v1 - v0) ..., then y, then z - and its gradient is the squash
+ * entries' M.  lo, h as there.  A cell is named by the linear index of its low corner, cell = i + nx (j + ny k);
+ * f = (fx, fy, fz) are the fractions within it.  fp64 + - * / and sqrt only, in the operand order written here, no
+ * contraction: a restatement in the same order gives the same bits.
+ *   B          (nx,ny,nz,3)
+ *   max_nulls  >= 0: the capacity of the record arrays; 0 counts only (no record array is looked at)
+ *   counts     int64[2], a HOST array in both entries: [0] the candidates of the screen, [1] the nulls found
+ *   out        records: cell (int64), pos (3 each), jac (9 each), det, resid doubles; sign, iters int32
+ * Semantics:
+ *   screen     a cell is a CANDIDATE unless some component's eight corner values are all > 0 or all < 0 (strict
+ *              comparisons: a zero corner never excludes a cell).  A cell with a NaN among its 24 corner values is not
+ *              a candidate.  The interpolant lies between its corner extremes, so the screen loses no null.
+ *   Newton     per candidate, in the fractions f.  NINE STARTS in this order, until one is accepted: (1/2, 1/2, 1/2),
+ *              then (1/4 or 3/4)^3 with x fastest and z slowest: start s = 1 .. 8 has fx = 3/4 if (s - 1) & 1 else 1/4,
+ *              fy by (s - 1) & 2, fz by (s - 1) & 4.  Per start AT MOST 20 ITERATIONS.  Each: b_a = B_a(f) and
+ *              J_ab = dB_a/df_b are the value and gradient expressions of the squash entries WITHOUT the quotients by h:
+ *              J_a0 = dx0 + fz (dx1 - dx0), J_a1 = e0 + fz (e1 - e0), J_a2 = dz.  The adjugate:
+ *                A00 = J11 J22 - J12 J21   A01 = J02 J21 - J01 J22   A02 = J01 J12 - J02 J11
+ *                A10 = J12 J20 - J10 J22   A11 = J00 J22 - J02 J20   A12 = J02 J10 - J00 J12
+ *                A20 = J10 J21 - J11 J20   A21 = J01 J20 - J00 J21   A22 = J00 J11 - J01 J10
+ *              det = (J00 A00 + J01 A10) + J02 A20 (cofactor expansion along the first row).  Not |det| > 0 (zero or
+ *              NaN): the start fails.  delta_d = ((A_d0 b_0 + A_d1 b_1) + A_d2 b_2) / det - three quotients, no
+ *              reciprocal - and f_d <- f_d - delta_d.  Not |f_d - 1/2| <= 2.5 on some axis (wandered off, NaN, Inf):
+ *              the start fails.  max_d |delta_d| <= 2^-40: the start has CONVERGED (tested after the update, so a start
+ *              that begins on the null uses one iteration).  A converged start is ACCEPTED when
+ *              -2^-30 <= f_d <= 1 + 2^-30 on all three axes; one converged outside fails, and the next start is tried.
+ *              At most one null per cell: the first accepted start.
+ *   record     of an accepted cell (c_x, c_y, c_z its low corner's indices):
+ *              pos_d = lo_d + (c_d + f_d) h_d, the sum formed first; jac = M_ab = dB_a/dx_b at f, row-major
+ *              (a slowest), the bits of the squash entries' gradient, quotients by h included; det = det M by the same
+ *              expansion; resid = sqrt((b_0 b_0 + b_1 b_1) + b_2 b_2) at the final f;
+ *              sign = +1 for det M < 0 (a positive null: two eigenvalues with positive real part, the fan
+ *              diverges), -1 for det M > 0, 0 otherwise; iters = 32 * (number of the start, 0 .. 8) + the iterations
+ *              it used (1 .. 20).
+ *   order      records come out in ascending cell, whatever the launch geometry, with the same bits on every run and
+ *              from both entries.  counts[1] > max_nulls: the first max_nulls records in cell order are written and
+ *              the call still returns 0 (call again with that capacity).  No result depends on the capacity of an
+ *              internal buffer: both lists are sized from exact counts.  A null on a face, edge or node shared by
+ *              cells is reported by each adjacent cell that accepts it - up to 2, 4 or 8 records; merging them is the
+ *              caller's business (ndsm_amd.VecPot.nulls does).
+ * The constants 20, 2.5, 2^-40 and 2^-30 are choices (DESIGN.md says why), not measurements.  A null of the
+ * interpolant where det J = 0 (a degenerate null, or an all-zero cell) is not found: every start stops at the singular
+ * guard.
+ * Returns 0, or >= 9001 errors: 9001 without a GPU whatever the arguments; 9002 a NULL handle, B or counts, or with
+ * max_nulls > 0 a NULL record array; 9004 max_nulls < 0.  On every failure counts is cleared; the host entry also clears
+ * the max_nulls slots of every record array (on success the slots past min(counts[1], max_nulls) are zero), the
+ * device entry leaves its device arrays (on success it writes the first min(counts[1], max_nulls) slots only).
+ * Device memory: the host entry stages B in the handle's scratch (24 B/pt); the screen keeps 1 B + 1 bit per point,
+ * the lists 8 B per candidate. */
+/* HOST arrays */
+int ndsm_hip_vecpot_nulls(void *h, const double *B, int max_nulls, int64_t *counts, int64_t *cell, double *pos,
+                          double *jac, double *det, double *resid, int32_t *sign, int32_t *iters);
+/* the same on DEVICE arrays of the library's GPU (B and the seven record arrays; counts stays on the host) */
+int ndsm_hip_vecpot_nulls_device(void *h, const double *dB, int max_nulls, int64_t *counts, int64_t *dcell,
+                                 double *dpos, double *djac, double *ddet, double *dresid, int32_t *dsign,
+                                 int32_t *diters);
+
 /* =====================================================================
  * PART 3 - additive exports, multi-GPU
  *

@@ -100,6 +100,9 @@ def load_library(path=None):
     _sq = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_int] + [ctypes.c_void_p] * 6
     L.ndsm_hip_vecpot_squash.argtypes = [ctypes.c_void_p] * 3 + _sq
     L.ndsm_hip_vecpot_squash_device.argtypes = [ctypes.c_void_p] * 3 + _sq
+    _nu = [ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 8
+    L.ndsm_hip_vecpot_nulls.argtypes = _nu
+    L.ndsm_hip_vecpot_nulls_device.argtypes = _nu
     L.ndsm_hip_device_alloc.argtypes = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
     L.ndsm_hip_device_free.argtypes = [ctypes.c_void_p]
     L.ndsm_hip_memcpy_h2d.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
@@ -567,6 +570,48 @@ class VecPot:
                          device)
         return _qmap(out, twist)
 
+    def nulls(self, b, max_nulls=4096, merge=1e-6, device=False):
+        """Null points of b (3,nz,ny,nx) and their types, on the device (semantics: include/ndsm_hip.h,
+        ndsm_hip_vecpot_nulls): every cell of the mesh is screened (a component of one strict sign over the eight
+        corners cannot vanish inside), and a Newton iteration on the trilinear interpolant runs in each remaining
+        cell.  max_nulls: the capacity of the first call; when more are found the call is repeated once with that
+        number (0: count only - ncandidates and nfound, no records).  merge (in units of min(h); None: the raw records): a null on a face, edge or node shared by cells is
+        reported by each of them - records whose positions lie within merge of one already kept are dropped, the
+        lowest cell kept.  Returns a Nulls tuple: position (n,3), cell (n; int64, i + nx (j + ny k) of the low
+        corner), jacobian (n,3,3; dB_a/dx_b), sign (n; +1: det < 0, two eigenvalues with positive real part, the fan
+        diverges; -1: det > 0; 0), spiral (n; a complex pair), eigenvalues (n,3; complex, numpy.linalg.eig of the
+        jacobian), spine (n,3; the unit eigenvector of the eigenvalue whose real part has the lone sign), fan (n,2,3;
+        the other two, complex for a spiral), det, residual (n; |b| at the position), ncandidates (the cells the
+        screen left), nfound (the records before merging).  device=True: the arrays are staged in device memory and
+        the device-resident entry point runs."""
+        if (isinstance(max_nulls, bool) or not isinstance(max_nulls, (int, float, np.integer)) or
+                not np.isfinite(max_nulls) or int(max_nulls) != max_nulls or not 0 <= max_nulls <= NULLS_MAX):
+            raise ValueError(f"max_nulls must be an integer in 0 .. {NULLS_MAX}, not {max_nulls!r}")
+        if merge is not None and not (isinstance(merge, (int, float)) and not isinstance(merge, bool) and
+                                      merge >= 0.0 and np.isfinite(merge)):
+            raise ValueError(f"merge must be None or a finite number >= 0, not {merge!r}")
+        B = self._field_arg(b, "nulls")
+        cap = int(max_nulls)
+        for _attempt in range(2):
+            counts = np.zeros(2, dtype=np.int64)
+            m = max(cap, 1)
+            out = [np.zeros(m, dtype=np.int64), np.zeros((m, 3)), np.zeros((m, 3, 3)), np.zeros(m), np.zeros(m),
+                   np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int32)]
+            if not device:
+                ierr = self.L.ndsm_hip_vecpot_nulls(self.h, B.ctypes.data, cap, counts.ctypes.data,
+                                                    *[a.ctypes.data for a in out])
+            else:
+                ierr = self._on_device([B] + out, lambda dB, *ptrs: self.L.ndsm_hip_vecpot_nulls_device(
+                    self.h, dB, cap, counts.ctypes.data, *ptrs))
+            _check(ierr, "ndsm_hip_vecpot_nulls_device" if device else "ndsm_hip_vecpot_nulls", self.L)
+            if int(counts[1]) <= cap or cap == 0:
+                break
+            cap = int(counts[1])
+        n = min(int(counts[1]), cap)
+        hmin = min(float(q[1]) - float(q[0]) for q in (self.x, self.y, self.z))
+        return _nulls_tuple([a[:n] for a in out], int(counts[0]), int(counts[1]), None if merge is None else
+                            float(merge) * hmin)
+
     def seed_plane(self, axis, value, n1, n2):
         """the (n1 n2, 3) seeds of a mesh-aligned cut through the handle's box: coordinate `axis` (0, 1, 2 = x, y, z)
         fixed at `value`, the other two (in the order x, y, z; the first of them fastest) n1 and n2 equally spaced
@@ -695,6 +740,43 @@ def _field_lines(out, direction):
     return FieldLines(*out, out[2][0] + out[2][1] if direction == 0 else None)
 
 
+NULLS_MAX = 2 ** 24               # capacity of one nulls() call: 128 B of host arrays per slot
+Nulls = collections.namedtuple("Nulls", ["position", "cell", "jacobian", "sign", "spiral", "eigenvalues", "spine", "fan",
+                                          "det", "residual", "ncandidates", "nfound"])
+
+
+def _nulls_tuple(rec, ncandidates, nfound, radius):
+    """a Nulls tuple from the records [cell, pos, jac, det, resid, sign, iters] in cell order: records within
+    `radius` of one already kept are dropped (None: none is), the types follow from numpy.linalg.eig"""
+    cell, pos, jac, det, resid, sign, _iters = rec
+    keep = np.ones(len(cell), dtype=bool)
+    if radius is not None:
+        for i in range(len(cell)):
+            if keep[i]:
+                near = np.sqrt(((pos[i + 1:] - pos[i]) ** 2).sum(axis=1)) <= radius
+                keep[i + 1:] &= ~near
+    cell, pos, jac, det, resid, sign = (a[keep].copy() for a in (cell, pos, jac, det, resid, sign))
+    n = len(cell)
+    lam, spine, fan = np.zeros((n, 3), dtype=complex), np.zeros((n, 3)), np.zeros((n, 2, 3), dtype=complex)
+    for i in range(n):
+        w, v = np.linalg.eig(jac[i])
+        # the lone sign: the real eigenvalue whose real part's sign the other two do not share (for det = 0 or a
+        # pure centre no such eigenvalue need exist: then the real eigenvalue of the largest modulus)
+        sg = np.sign(w.real)
+        lone = [k for k in range(3) if abs(w[k].imag) == 0.0 and sg[k] != 0 and np.all(np.delete(sg, k) == -sg[k])]
+        if not lone:
+            lone = sorted((k for k in range(3) if abs(w[k].imag) == 0.0), key=lambda k: -abs(w[k]))
+        k = lone[0]
+        rest = [j for j in range(3) if j != k]
+        lam[i] = w[[k] + rest]
+        spine[i] = v[:, k].real
+        fan[i] = v[:, rest].T
+    spiral = np.abs(lam.imag).max(axis=1) > 0.0 if n else np.zeros(0, dtype=bool)
+    if np.all(fan.imag == 0.0):
+        fan = fan.real
+    return Nulls(pos, cell, jac, sign, spiral, lam, spine, fan, det, resid, ncandidates, nfound)
+
+
 QMap = collections.namedtuple("QMap", ["q", "twist", "ends", "length", "integral", "status", "nsteps"])
 
 
@@ -797,6 +879,16 @@ def squashing_factor(x, y, z, b, seeds, g=None, integrand=0, twist=False, step=0
     V = _grid_handle(x, y, z, b, 0, lib)
     try:
         return V.squashing(b, seeds, g=g, integrand=integrand, twist=twist, step=step, max_steps=max_steps)
+    finally:
+        V.close()
+
+
+def find_nulls(x, y, z, b, max_nulls=4096, merge=1e-6, lib=None):
+    """Null points of b (3,nz,ny,nx) and their types: one-shot form of VecPot.nulls (returns its Nulls tuple).
+    Raises NdsmHipError on device / runtime failures (>= 9001)."""
+    V = _grid_handle(x, y, z, b, 0, lib)
+    try:
+        return V.nulls(b, max_nulls=max_nulls, merge=merge)
     finally:
         V.close()
 

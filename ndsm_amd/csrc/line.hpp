@@ -104,6 +104,26 @@ __device__ __forceinline__ double line_lerp3_grad(const double v[8], const LineC
   return c0 + c.fz * dz;
 }
 
+// the same value and the gradient with respect to the cell's fractions (fx, fy, fz): line_lerp3_grad's expressions
+// without the quotients by h (nulls.hip iterates in the fractions)
+__device__ __forceinline__ double line_lerp3_fgrad(const double v[8], const LineCell &c, double g[3]) {
+  const double d00 = v[1] - v[0], d10 = v[3] - v[2], d01 = v[5] - v[4], d11 = v[7] - v[6];
+  const double c00 = v[0] + c.fx * d00;
+  const double c10 = v[2] + c.fx * d10;
+  const double c01 = v[4] + c.fx * d01;
+  const double c11 = v[6] + c.fx * d11;
+  const double e0 = c10 - c00, e1 = c11 - c01;
+  const double c0 = c00 + c.fy * e0;
+  const double c1 = c01 + c.fy * e1;
+  const double dz = c1 - c0;
+  const double dx0 = d00 + c.fy * (d10 - d00);
+  const double dx1 = d01 + c.fy * (d11 - d01);
+  g[0] = dx0 + c.fz * (dx1 - dx0);
+  g[1] = e0 + c.fz * (e1 - e0);
+  g[2] = dz;
+  return c0 + c.fz * dz;
+}
+
 // the first face the chord r -> rn meets: its NDSMK_TRACE_* code and t, or 0 (t = 2) when rn is inside the box
 __device__ __forceinline__ int line_first_face(const LineArgs &p, const double r[3], const double rn[3], double &t) {
   int face = 0;

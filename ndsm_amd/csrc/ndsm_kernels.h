@@ -30,7 +30,7 @@ enum {
   NDSMK_ENODEV = 9001,   /* no HIP device visible */
   NDSMK_EARG = 9002,     /* shape/argument check failed on the host */
   NDSMK_ENCCL = 9003,    /* RCCL call failed */
-  NDSMK_EVALUE = 9004    /* a scalar argument outside its range (ndsmk_trace, ndsmk_squash) */
+  NDSMK_EVALUE = 9004    /* a scalar argument outside its range (ndsmk_trace, ndsmk_squash, ndsmk_nulls) */
 };
 
 /* geometry + operator constants of one grid level (interoperable with the
@@ -224,6 +224,15 @@ int ndsmk_trace(const double *B, const double *G, const int32_t *n3, const doubl
 int ndsmk_squash(const double *B, const double *G, int integrand, const int32_t *n3, const double *lo3,
                  const double *h_dq3, int nseeds, const double *seeds, double step, int max_steps, double *q,
                  double *ends, double *length, double *integral, int32_t *status, int32_t *nsteps);
+
+/* Null points (nulls.hip; semantics: include/ndsm_hip.h, ndsm_hip_vecpot_nulls).  B a DEVICE array (nx,ny,nz,3); lo3,
+ * h_dq3: first mesh point and spacing per axis.  h_counts2 (HOST, int64): the screen's candidates, the nulls found.  The
+ * first min(found, max_nulls) records in ascending cell order go into the DEVICE arrays cell (int64), pos (3 each), jac
+ * (9 each), det, resid (doubles), sign, iters (int32); with max_nulls == 0 they are not looked at.  NDSMK_EVALUE for
+ * max_nulls < 0.  Blocks for the two counts; the records are written asynchronously. */
+int ndsmk_nulls(const double *B, const int32_t *n3, const double *lo3, const double *h_dq3, int max_nulls,
+                int64_t *h_counts2, int64_t *cell, double *pos, double *jac, double *det, double *resid, int32_t *sign,
+                int32_t *iters);
 
 /* the face phase on the device (faces.hip): packed face buffers, six faces back to back */
 int ndsmk_face_offsets(const int32_t *n3, int64_t *off6, int64_t *total);

@@ -1031,6 +1031,97 @@ contains
     end subroutine
   end function
 
+  ! ---- null points on the same handle --------------------------------------
+  ! B (nx,ny,nz,3) in; max_nulls >= 0 the capacity of the record arrays; counts (2, int64, on the HOST in both
+  ! entries): the screen's candidates, the nulls found.  Out, the first min(counts(2), max_nulls) records in ascending
+  ! cell order: cell (int64), pos (3 each), jac (9 each), det, resid (doubles), sign, iters (int32).  The handle
+  ! supplies the mesh; no solve runs.  Return value: 0, or >= 9001 errors (9002 a NULL handle, B or counts, or with
+  ! max_nulls > 0 a NULL record array; 9004 max_nulls < 0).  On every failure counts is cleared, and the host entry
+  ! clears the max_nulls slots of its record arrays.
+
+  ! HOST arrays
+  function ndsm_hip_vecpot_nulls(handle, B, max_nulls, counts, cell, pos, jac, det, resid, sign, iters) &
+      bind(c, name="ndsm_hip_vecpot_nulls") result(ierr)
+    type(c_ptr), value :: handle, B, counts, cell, pos, jac, det, resid, sign, iters
+    integer(c_int), value :: max_nulls
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_nulls(handle, B, max_nulls, counts, cell, pos, jac, det, resid, sign, iters, .false., &
+                               "ndsm_hip_vecpot_nulls")
+  end function
+
+  ! the same on DEVICE arrays of the library's GPU (counts stays a host array; no record array is touched on the host)
+  function ndsm_hip_vecpot_nulls_device(handle, dB, max_nulls, counts, dcell, dpos, djac, ddet, dresid, dsign, diters) &
+      bind(c, name="ndsm_hip_vecpot_nulls_device") result(ierr)
+    type(c_ptr), value :: handle, dB, counts, dcell, dpos, djac, ddet, dresid, dsign, diters
+    integer(c_int), value :: max_nulls
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_nulls(handle, dB, max_nulls, counts, dcell, dpos, djac, ddet, dresid, dsign, diters, .true., &
+                               "ndsm_hip_vecpot_nulls_device")
+  end function
+
+  function vecpot_handle_nulls(handle, B, max_nulls, counts, cell, pos, jac, det, resid, sign, iters, on_device, who) &
+      result(ierr)
+    type(c_ptr), intent(in) :: handle, B, counts, cell, pos, jac, det, resid, sign, iters
+    integer(c_int), intent(in) :: max_nulls
+    logical, intent(in) :: on_device
+    character(len=*), intent(in) :: who
+    integer(c_int) :: ierr
+    type(vecpot_ctx), pointer :: ctx
+    integer(c_int64_t), pointer :: cnt(:)
+    integer(c_int) :: rc
+    call clear_outputs()
+    ierr = ndsmk_init(-1_c_int)                        ! without a device: 9001, whatever the arguments
+    if (ierr /= 0) return
+    ierr = NDSMK_EARG
+    if (.not. (c_associated(handle) .and. c_associated(B) .and. c_associated(counts))) return
+    if (max_nulls > 0 .and. .not. (c_associated(cell) .and. c_associated(pos) .and. c_associated(jac) .and. &
+                                   c_associated(det) .and. c_associated(resid) .and. c_associated(sign) .and. &
+                                   c_associated(iters))) return
+    call c_f_pointer(handle, ctx)
+    if (.not. ctx%live) return
+    call c_f_pointer(counts, cnt, [2])
+    rc = vecpot_nulls(ctx, B, max_nulls, cnt, cell, pos, jac, det, resid, sign, iters, on_device)
+    if (rc /= 0) then
+      call report(who, rc)
+      if (rc < NDSMK_ENODEV) rc = NDSMK_ENODEV
+      call clear_outputs()
+    end if
+    ierr = rc
+  contains
+    ! counts, and (host entry) the max_nulls slots of every record array
+    subroutine clear_outputs()
+      real(c_double), pointer :: r(:)
+      integer(c_int32_t), pointer :: k(:)
+      integer(c_int64_t), pointer :: k8(:)
+      if (c_associated(counts)) then
+        call c_f_pointer(counts, k8, [2]); k8 = 0
+      end if
+      if (on_device .or. max_nulls <= 0) return
+      if (max_nulls > huge(0) / 9) return
+      if (c_associated(cell)) then
+        call c_f_pointer(cell, k8, [max_nulls]); k8 = 0
+      end if
+      if (c_associated(pos)) then
+        call c_f_pointer(pos, r, [3 * max_nulls]); r = 0
+      end if
+      if (c_associated(jac)) then
+        call c_f_pointer(jac, r, [9 * max_nulls]); r = 0
+      end if
+      if (c_associated(det)) then
+        call c_f_pointer(det, r, [max_nulls]); r = 0
+      end if
+      if (c_associated(resid)) then
+        call c_f_pointer(resid, r, [max_nulls]); r = 0
+      end if
+      if (c_associated(sign)) then
+        call c_f_pointer(sign, k, [max_nulls]); k = 0
+      end if
+      if (c_associated(iters)) then
+        call c_f_pointer(iters, k, [max_nulls]); k = 0
+      end if
+    end subroutine
+  end function
+
   ! ---- z-slab decomposition over GPUs (SURVEY 8e) -----------------------
 
   ! rank 0 creates the 128-byte RCCL id; the launcher hands it to every rank

@@ -583,6 +583,18 @@ module ndsmh_iface
       integer(c_int) :: rc
     end function
 
+    ! ---- null points (nulls.hip) ----
+    function ndsmk_nulls(B, n3, lo3, dq3, max_nulls, counts2, cell, pos, jac, det, resid, sign, iters) &
+        bind(c, name="ndsmk_nulls") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_int64_t, c_double
+      type(c_ptr), value :: B, cell, pos, jac, det, resid, sign, iters
+      integer(c_int32_t), intent(in) :: n3(3)
+      real(c_double), intent(in) :: lo3(3), dq3(3)
+      integer(c_int), value :: max_nulls
+      integer(c_int64_t), intent(out) :: counts2(2)
+      integer(c_int) :: rc
+    end function
+
     ! ---- the face phase on the device (faces.hip) ----
     function ndsmk_face_offsets(n3, off6, total) bind(c, name="ndsmk_face_offsets") result(rc)
       import :: c_int, c_int32_t, c_int64_t

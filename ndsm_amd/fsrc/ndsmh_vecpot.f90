@@ -32,7 +32,7 @@ module ndsmh_vecpot
 
   public :: vecpot_solve, poisson_solve
   public :: vecpot_ctx, vecpot_ctx_create, vecpot_ctx_destroy, vecpot_ctx_matches, vecpot_run, vecpot_cache_drop
-  public :: vecpot_project, vecpot_devore, vecpot_lines
+  public :: vecpot_project, vecpot_devore, vecpot_lines, vecpot_nulls
   public :: VP_POTENTIAL, VP_FIELD, VP_HELICITY
   ! pieces the distributed driver (ndsmh_wvecpot) shares with vecpot_solve
   public :: face_data, face_axis, face_upper, face_t1, face_t2, face_order, face_copy, vecpot_faces, say
@@ -1155,6 +1155,70 @@ contains
         rc = ndsmk_trace(B, G, n3, lo, dq, nseeds, seeds, step, max_steps, sel, ends, length, integral, status, nsteps)
       end if
     end function
+  end function
+
+  ! ------------------------------------------------------------------
+  ! The null-point entries on a prepared context (semantics in include/ndsm_hip.h, DESIGN.md "Null points"): the
+  ! screen over every cell of B and the Newton iteration of the candidates (ndsmk_nulls).  The context supplies the
+  ! mesh only, as in vecpot_lines.  pB (nx,ny,nz,3) in; counts(2) out on the host: candidates, nulls found; the first
+  ! min(counts(2), max_nulls) records in ascending cell order out: pcell int64, ppos (3 each), pjac (9 each), pdet,
+  ! pres doubles, psign, pit int32 - on the HOST (B goes up into the staging array dF(1), the records come home from a
+  ! scratch buffer) or (on_device) in HBM.
+  ! ------------------------------------------------------------------
+  function vecpot_nulls(ctx, pB, max_nulls, counts, pcell, ppos, pjac, pdet, pres, psign, pit, on_device) result(rc)
+    type(vecpot_ctx), intent(inout), target :: ctx
+    logical, intent(in) :: on_device
+    type(c_ptr), intent(in) :: pB, pcell, ppos, pjac, pdet, pres, psign, pit
+    integer(c_int), intent(in) :: max_nulls
+    integer(c_int64_t), intent(out) :: counts(2)
+    integer(c_int) :: rc, rc_free
+    real(wp) :: dq(3), lo(3)
+    integer(c_int32_t) :: n3(3)
+    integer(c_size_t) :: nb, nm, no
+    integer :: i
+    type(c_ptr) :: buf, d(7), h(7)
+    ! bytes per record of cell, pos, jac, det, resid, sign, iters: 128 in all, the 8-byte fields first
+    integer(c_size_t), parameter :: width(7) = [8, 24, 72, 8, 8, 4, 4]
+
+    counts = 0
+    n3 = ctx%n3
+    dq = [ctx%qx(2) - ctx%qx(1), ctx%qy(2) - ctx%qy(1), ctx%qz(2) - ctx%qz(1)]      ! as vecpot_run
+    lo = [ctx%qx(1), ctx%qy(1), ctx%qz(1)]
+    if (on_device .or. max_nulls < 0) then
+      ! (the argument errors are the kernel entry's to name; nothing is staged for them)
+      rc = ndsmk_nulls(pB, n3, lo, dq, max_nulls, counts, pcell, ppos, pjac, pdet, pres, psign, pit)
+      if (rc == 0) rc = ndsmk_sync()
+      return
+    end if
+    nb = int(product(int(n3, ik)), c_size_t) * 24_c_size_t
+    if (.not. c_associated(ctx%dF(1))) then
+      rc = ndsmk_alloc(ctx%dF(1), nb); if (rc /= 0) return
+    end if
+    rc = ndsmk_h2d(ctx%dF(1), pB, nb); if (rc /= 0) return
+    ! one scratch buffer of max_nulls records, carved into the seven arrays
+    buf = c_null_ptr
+    d = c_null_ptr
+    nm = int(max_nulls, c_size_t)
+    if (nm > 0) then
+      rc = ndsmk_alloc(buf, sum(width) * nm); if (rc /= 0) return
+      no = 0
+      do i = 1, 7
+        d(i) = dptr_offset(buf, no)
+        no = no + width(i) * nm
+      end do
+    end if
+    call say("find_nulls", "Screening the cells and iterating on the candidates...")
+    rc = ndsmk_nulls(ctx%dF(1), n3, lo, dq, max_nulls, counts, d(1), d(2), d(3), d(4), d(5), d(6), d(7))
+    no = int(min(counts(2), int(max_nulls, c_int64_t)), c_size_t)
+    h = [pcell, ppos, pjac, pdet, pres, psign, pit]
+    do i = 1, 7
+      if (rc == 0 .and. no > 0) rc = ndsmk_d2h(h(i), d(i), width(i) * no)
+    end do
+    if (rc == 0) rc = ndsmk_sync()
+    if (c_associated(buf)) then
+      rc_free = ndsmk_free(buf)
+      if (rc == 0) rc = rc_free
+    end if
   end function
 
   ! B.n of face f (1..6) from the host field (extract_bn, :699-743)

@@ -174,6 +174,11 @@ def test_reduction_against_numpy(hip, field, ns, meshf):
     V = ndsm_amd.VecPot(*mesh)
     h = V.helicity(b, vc_tol=VC_TOL, return_fields=True, gauge="devore")
     V.close()
+    assert_reduction(h, b, mesh)
+
+
+def assert_reduction(h, b, mesh):
+    """the scalars of a DeVore-gauge Helicity h of b (with its A, A_p, B_p) against numpy on the returned arrays"""
     w = weights(mesh)
     db = b - h.B_p
     terms = {"H_R": w * ((h.A + h.A_p) * db).sum(axis=0), "H_J": w * ((h.A - h.A_p) * db).sum(axis=0),

@@ -329,6 +329,58 @@ int ndsm_hip_vecpot_trace_device(void *h, const double *dB, const double *dG, in
                                  double step, int max_steps, int direction, double *dends, double *dlength,
                                  double *dintegral, int32_t *dstatus, int32_t *dnsteps);
 
+/* ---- Field-line paths: the points of the same lines (DESIGN.md "Field-line paths") ---------------------------------
+ * Where a line runs, not only where it ends: every `every`-th point of each traced line, with B, G and the running
+ * integral at it - for drawing lines over a Q map, sampling a field along a loop, or following lines started near a
+ * null.  Everything not said here is exactly as in ndsm_hip_vecpot_trace above: the lanes (nl = nseeds lines, or
+ * 2 nseeds with direction 0, the forward block then the backward block), the cell, the interpolation, the RK4 step,
+ * the exit step, the snap, the status codes, max_steps, step, seeds, B and G.
+ *   trace outputs  ends, length, integral, status, nsteps are required and are bit for bit what ndsm_hip_vecpot_trace
+ *                  returns for the same arguments.
+ *   every          >= 1, the stride in steps between stored points.  With n = nsteps[l], line l stores its state after
+ *                  0, every, 2 every, ... steps for each multiple < n, and always its final state after n steps - the
+ *                  end point: on its face, the last accepted point of a NULL line, or the point after max_steps steps.
+ *                  npts(l) = 1 if n = 0, else (n - 1) / every + 2 (integer division); with every = 1 that is n + 1.
+ *   offsets, total offsets has nl + 1 int64 entries: the exclusive prefix sums of npts in lane order, offsets[nl] =
+ *                  *total.  total is one int64 on the HOST in both entries.  Both are exact and complete whatever
+ *                  max_points is.
+ *   max_points     >= 0, the capacity of the point arrays in points: points, bpt, gpt are (3,max_points) - x, y, z per
+ *                  point, as seeds -, ipt is (max_points).  The lines' points are concatenated in lane order; slot k of
+ *                  the concatenation is written if and only if k < max_points: a line cut by the capacity is written up
+ *                  to it and nothing at or beyond max_points is touched (call again with *total).  max_points = 0 is
+ *                  the counting call: the four point arrays may be NULL and no second pass is launched.  With
+ *                  max_points > 0 points is required; bpt, gpt, ipt may each be NULL and are then skipped; gpt and ipt
+ *                  are ignored (not written) when G is NULL.
+ *   per point      points: r after that many steps - point 0 carries the seed's bits, the last point those of ends.
+ *                  bpt: the trilinear B at r, the interpolation's bits - the stage-1 value of the next step; for the
+ *                  last point one extra evaluation at the final r, after the snap (on a NULL line it may be zero or
+ *                  NaN and is stored as it is).  gpt: the same for G.  ipt: the running integral after that many
+ *                  steps, 0 at point 0 and integral[l]'s bits at the last point.
+ *   OUTSIDE lines  store one point: the seed's bits as given, NaN included, bpt = gpt = 0 and ipt = 0.  Nothing is
+ *                  interpolated at a point that is not in the box.
+ * The points are written by a second pass that repeats the trace with the same expressions, at offsets[l] + j for the
+ * j-th stored point of line l; a line never writes outside [offsets[l], min(offsets[l + 1], max_points)).  The bits
+ * do not depend on the number of seeds, their order, or the launch geometry.
+ * Returns 0, or >= 9001 errors as the trace entries, and: 9004 also for every < 1 or max_points < 0; 9002 also for a
+ * NULL total, with nseeds > 0 a NULL offsets, and with max_points > 0 a NULL points.  nseeds == 0 succeeds, sets
+ * *total = 0 and touches nothing else.  On failure *total = 0, and the host entry also clears the nl entries of the
+ * trace outputs, the nl + 1 entries of offsets and exactly max_points slots of each non-NULL point array; the device
+ * entry leaves its device arrays.  On success nothing past the written slots is touched by either entry.
+ * Device memory: the host entry stages B and G in the handle's scratch (24 B/pt each) and the points it brings home,
+ * min(*total, max_points) of them (up to 80 B each). */
+/* HOST arrays */
+int ndsm_hip_vecpot_paths(void *h, const double *B, const double *G, int nseeds, const double *seeds, double step,
+                          int max_steps, int direction, int every, int64_t max_points, double *ends, double *length,
+                          double *integral, int32_t *status, int32_t *nsteps, int64_t *offsets, int64_t *total,
+                          double *points, double *bpt, double *gpt, double *ipt);
+/* the same on DEVICE arrays of the library's GPU (seeds, the five trace outputs, offsets and the four point arrays;
+ * total stays on the host) */
+int ndsm_hip_vecpot_paths_device(void *h, const double *dB, const double *dG, int nseeds, const double *dseeds,
+                                 double step, int max_steps, int direction, int every, int64_t max_points,
+                                 double *dends, double *dlength, double *dintegral, int32_t *dstatus,
+                                 int32_t *dnsteps, int64_t *doffsets, int64_t *total, double *dpoints, double *dbpt,
+                                 double *dgpt, double *dipt);
+
 /* ---- Squashing factor Q and twist number along the same lines (DESIGN.md "Squashing factor and twist") -------------
  * Q of Titov (2007) at each seed - large where the field-line mapping between the two feet of the line is strongly
  * distorted (quasi-separatrix layers) - by the method of Scott, Pontin & Hornig (2017): two deviation vectors U, V

@@ -97,6 +97,10 @@ def load_library(path=None):
     _tr = [ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5
     L.ndsm_hip_vecpot_trace.argtypes = [ctypes.c_void_p] * 3 + _tr
     L.ndsm_hip_vecpot_trace_device.argtypes = [ctypes.c_void_p] * 3 + _tr
+    _pa = ([ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64] +
+           [ctypes.c_void_p] * 11)
+    L.ndsm_hip_vecpot_paths.argtypes = [ctypes.c_void_p] * 3 + _pa
+    L.ndsm_hip_vecpot_paths_device.argtypes = [ctypes.c_void_p] * 3 + _pa
     _sq = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_int] + [ctypes.c_void_p] * 6
     L.ndsm_hip_vecpot_squash.argtypes = [ctypes.c_void_p] * 3 + _sq
     L.ndsm_hip_vecpot_squash_device.argtypes = [ctypes.c_void_p] * 3 + _sq
@@ -491,6 +495,66 @@ class VecPot:
         self._line_entry("ndsm_hip_vecpot_trace", B, G, (), S, (step, max_steps, direction), out, device)
         return _field_lines(out, direction)
 
+    def paths(self, b, seeds, g=None, step=0.5, max_steps=None, direction="both", every=1, max_points=None,
+              values=True, device=False):
+        """The field lines of trace() as polylines (semantics: include/ndsm_hip.h, ndsm_hip_vecpot_paths): every
+        `every`-th point of each line - the seed first, the end point always last - with b, g and the running integral
+        of g at each.  b, seeds, g, step, max_steps, direction as trace().  max_points: the capacity of the first
+        call; when the lines hold more points the call is repeated once with that number (None: a counting call,
+        then one call of the exact size).  values=False: the points alone.  Returns a FieldPaths tuple: lines (the
+        FieldLines of the same call, bit for bit trace()'s), offsets (nl + 1; int64: line l owns the rows offsets[l] ..
+        offsets[l + 1] - 1, lane order: the forward lines, then for "both" the backward lines), points (total,3), b, g
+        (total,3) and integral (total) at the points (b None with values=False; g and integral None without g too).
+        path_of(paths, l) cuts out one line, whole_line(paths, i) joins the two directions of seed i.  device=True:
+        the arrays are staged in device memory and the device-resident entry point runs."""
+        direction, step, max_steps = self._trace_args(step, max_steps, direction)
+        every, max_points = _paths_args(every, max_points)
+        B = self._field_arg(b, "paths")
+        G = None if g is None else self._field_arg(g, "paths")
+        S = self._seeds_arg(seeds)
+        ns = len(S)
+        nl = ns * (2 if direction == 0 else 1)
+        out = _trace_outputs(ns, direction)
+        withb, withg = bool(values), bool(values) and G is not None
+        if ns == 0:
+            return _field_paths(out, direction, np.zeros(1, dtype=np.int64), np.zeros((0, 3)),
+                                np.zeros((0, 3)) if withb else None, np.zeros((0, 3)) if withg else None,
+                                np.zeros(0) if withg else None)
+        name = "ndsm_hip_vecpot_paths_device" if device else "ndsm_hip_vecpot_paths"
+        cap = 0 if max_points is None else max_points
+        for _attempt in range(2):
+            offsets = np.zeros(nl + 1, dtype=np.int64)
+            total = np.zeros(1, dtype=np.int64)
+            m = max(cap, 1)
+            pts = [np.zeros((m, 3)), np.zeros((m, 3)) if withb else None, np.zeros((m, 3)) if withg else None,
+                   np.zeros(m) if withg else None]
+            tail = (step, max_steps, direction, every, cap)
+            if not device:
+                ierr = self.L.ndsm_hip_vecpot_paths(
+                    self.h, B.ctypes.data, None if G is None else G.ctypes.data, ns, S.ctypes.data, *tail,
+                    *[a.ctypes.data for a in out], offsets.ctypes.data, total.ctypes.data,
+                    *[None if a is None or cap == 0 else a.ctypes.data for a in pts])
+            else:
+                staged = [S] + out + [offsets] + [a for a in pts if a is not None] + [B] + ([] if G is None else [G])
+
+                def call(dS, *ptrs):
+                    ptrs = list(ptrs)
+                    head = [ptrs.pop(0) for _ in range(6)]
+                    dpts = [None if a is None else ptrs.pop(0) for a in pts]
+                    if cap == 0:
+                        dpts = [None] * 4
+                    dB = ptrs.pop(0)
+                    dG = ptrs.pop(0) if G is not None else None
+                    return self.L.ndsm_hip_vecpot_paths_device(self.h, dB, dG, ns, dS, *tail, *head, total.ctypes.data,
+                                                               *dpts)
+                ierr = self._on_device(staged, call)
+            _check(ierr, name, self.L)
+            if int(total[0]) <= cap:
+                break
+            cap = int(total[0])
+        n = min(int(total[0]), cap)
+        return _field_paths(out, direction, offsets, *[None if a is None else a[:n] for a in pts])
+
     def default_max_steps(self, step=0.5):
         """the max_steps that trace() uses for max_steps=None: ceil(4 (nx + ny + nz) / step)"""
         return int(np.ceil(4.0 * float(int(self.nshape4[0]) + int(self.nshape4[1]) + int(self.nshape4[2])) / step))
@@ -740,6 +804,55 @@ def _field_lines(out, direction):
     return FieldLines(*out, out[2][0] + out[2][1] if direction == 0 else None)
 
 
+FieldPaths = collections.namedtuple("FieldPaths", ["lines", "offsets", "points", "b", "g", "integral"])
+PATHS_MAX_POINTS = 2 ** 40         # capacity of one paths() call
+
+
+def _paths_args(every, max_points):
+    """(every, max_points) of paths(); ValueError before anything is launched"""
+    def whole(v):
+        return (not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and np.isfinite(v)
+                and int(v) == v)
+    if not whole(every) or not 1 <= every <= 2 ** 31 - 1:
+        raise ValueError(f"every must be an integer >= 1, not {every!r}")
+    if max_points is not None and (not whole(max_points) or not 0 <= max_points <= PATHS_MAX_POINTS):
+        raise ValueError(f"max_points must be None or an integer in 0 .. {PATHS_MAX_POINTS}, not {max_points!r}")
+    return int(every), None if max_points is None else int(max_points)
+
+
+def _field_paths(out, direction, offsets, points, b, g, integral):
+    return FieldPaths(_field_lines(out, direction), offsets, points, b, g, integral)
+
+
+def path_of(paths, l):
+    """the rows of line l of a FieldPaths (lane order: l = i forward, nseeds + i backward for direction "both"):
+    (points, b, g, integral), an absent array None"""
+    nl = len(paths.offsets) - 1
+    if int(l) != l or not 0 <= l < nl:
+        raise IndexError(f"line {l!r} of {nl}")
+    a, e = int(paths.offsets[int(l)]), int(paths.offsets[int(l) + 1])
+    return tuple(None if v is None else v[a:e] for v in (paths.points, paths.b, paths.g, paths.integral))
+
+
+def whole_line(paths, i):
+    """the whole line through seed i of a FieldPaths traced in both directions: the backward line reversed, then the
+    forward line, the seed once - from the foot where b enters the box to the foot where it leaves.  (points, b, g,
+    integral), each joined the same way; integral is the integral of g.dl from the entry foot up to each point (the
+    backward line's values are counted back from its total)."""
+    if paths.lines.ends.shape[0] != 2:
+        raise ValueError("whole_line needs paths traced with direction='both'")
+    ns = paths.lines.ends.shape[1]
+    if int(i) != i or not 0 <= i < ns:
+        raise IndexError(f"seed {i!r} of {ns}")
+    fwd, bwd = path_of(paths, int(i)), path_of(paths, ns + int(i))
+    joined = [None if f is None else np.concatenate([w[:0:-1], f]) for f, w in zip(fwd[:3], bwd[:3])]
+    integral = None
+    if fwd[3] is not None:
+        # a backward line accumulates g.dl in the direction of b from its points to the seed
+        integral = np.concatenate([bwd[3][-1] - bwd[3][:0:-1], bwd[3][-1] + fwd[3]])
+    return tuple(joined) + (integral,)
+
+
 NULLS_MAX = 2 ** 24               # capacity of one nulls() call: 128 B of host arrays per slot
 Nulls = collections.namedtuple("Nulls", ["position", "cell", "jacobian", "sign", "spiral", "eigenvalues", "spine", "fan",
                                           "det", "residual", "ncandidates", "nfound"])
@@ -866,6 +979,20 @@ def trace_field_lines(x, y, z, b, seeds, g=None, step=0.5, max_steps=None, direc
     V = _grid_handle(x, y, z, b, 0, lib)
     try:
         return V.trace(b, seeds, g=g, step=step, max_steps=max_steps, direction=direction)
+    finally:
+        V.close()
+
+
+def trace_paths(x, y, z, b, seeds, g=None, step=0.5, max_steps=None, direction="both", every=1, max_points=None,
+                values=True, lib=None):
+    """The field lines of b (3,nz,ny,nx) through seeds (nseeds,3) as polylines, with b, g and the running integral of
+    g at their points: one-shot form of VecPot.paths (returns its FieldPaths tuple).  Raises NdsmHipError on device /
+    runtime failures (>= 9001)."""
+    _paths_args(every, max_points)
+    V = _grid_handle(x, y, z, b, 0, lib)
+    try:
+        return V.paths(b, seeds, g=g, step=step, max_steps=max_steps, direction=direction, every=every,
+                       max_points=max_points, values=values)
     finally:
         V.close()
 

@@ -30,7 +30,7 @@ enum {
   NDSMK_ENODEV = 9001,   /* no HIP device visible */
   NDSMK_EARG = 9002,     /* shape/argument check failed on the host */
   NDSMK_ENCCL = 9003,    /* RCCL call failed */
-  NDSMK_EVALUE = 9004    /* a scalar argument outside its range (ndsmk_trace, ndsmk_squash, ndsmk_nulls) */
+  NDSMK_EVALUE = 9004    /* a scalar argument outside its range (the line entries, ndsmk_nulls) */
 };
 
 /* geometry + operator constants of one grid level (interoperable with the
@@ -233,6 +233,23 @@ int ndsmk_squash(const double *B, const double *G, int integrand, const int32_t 
 int ndsmk_nulls(const double *B, const int32_t *n3, const double *lo3, const double *h_dq3, int max_nulls,
                 int64_t *h_counts2, int64_t *cell, double *pos, double *jac, double *det, double *resid, int32_t *sign,
                 int32_t *iters);
+
+/* Field-line paths (paths.hip; semantics: include/ndsm_hip.h, ndsm_hip_vecpot_paths), in two halves with the same
+ * leading arguments, which are ndsmk_trace's.  ndsmk_paths_count: ndsmk_trace itself (ends, length, integral, status,
+ * nsteps are its outputs), then offsets (nl + 1, int64, DEVICE) = the exclusive sums of the lines' point counts for the
+ * stride every, offsets[nl] = the total, which also comes back in *h_total (HOST); blocks for it.  ndsmk_paths_fill:
+ * slot k < max_points of the concatenation into points (3 each) and, where not NULL, bpt, gpt (3 each) and ipt (gpt,
+ * ipt are not looked at without G), all DEVICE arrays; a line writes inside [offsets[l], min(offsets[l + 1],
+ * max_points)) only; max_points == 0 launches nothing; asynchronous.  NDSMK_EVALUE as ndsmk_trace, and for every < 1,
+ * max_points < 0, by both halves (the counting half takes max_points only to refuse what the filling half would: such a
+ * call launches nothing); nseeds == 0 launches nothing (*h_total = 0). */
+int ndsmk_paths_count(const double *B, const double *G, const int32_t *n3, const double *lo3, const double *h_dq3,
+                      int nseeds, const double *seeds, double step, int max_steps, int direction, int every,
+                      int64_t max_points, double *ends, double *length, double *integral, int32_t *status,
+                      int32_t *nsteps, int64_t *offsets, int64_t *h_total);
+int ndsmk_paths_fill(const double *B, const double *G, const int32_t *n3, const double *lo3, const double *h_dq3,
+                     int nseeds, const double *seeds, double step, int max_steps, int direction, int every,
+                     int64_t max_points, const int64_t *offsets, double *points, double *bpt, double *gpt, double *ipt);
 
 /* the face phase on the device (faces.hip): packed face buffers, six faces back to back */
 int ndsmk_face_offsets(const int32_t *n3, int64_t *off6, int64_t *total);

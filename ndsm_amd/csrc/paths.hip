@@ -1,0 +1,225 @@
+// Field-line paths on the device (DESIGN.md "Field-line paths"): the points of the lines that trace.hip only
+// summarises, with B, G and the running integral at each.  The semantics are written out in include/ndsm_hip.h
+// (ndsm_hip_vecpot_paths) and restated in numpy by tests/path_model.py bit for bit.  Variable-length results the way
+// nulls.hip writes them - count, scan, then a second pass that repeats the same expressions and writes at its rank:
+//
+//   count   ndsmk_trace   the trace entry itself: ends, length, integral, status and n = nsteps of every line
+//           npts_k        offsets[l] = npts(l) = 1 if n = 0, else (n - 1) / every + 2
+//           scan64_k      in place: offsets[l] = the exclusive sum, offsets[nl] = the total; one workgroup, every lane
+//                         sums a contiguous run (the int64 sibling of nulls.hip's scan_k)
+//   fill    paths_k       one lane per line, one wave per workgroup, as trace_k: the loop of trace_k with
+//                         trace_step.hpp's stage and step - the same r and I - which stores the state before step
+//                         0, every, 2 every, ... once that step is known to move the line, and the final state
+//                         with one more interpolation at it.  Point j of line l goes to slot offsets[l] + j.
+// A lane writes slot offsets[l] + j only for j < min(offsets[l + 1], max_points) - offsets[l]: its own count from the
+// first pass and the capacity bound every store, whatever the second pass computes.  No atomic append, no guessed
+// capacity, no result that depends on the launch geometry.  No vector is indexed with a run-time axis (the rule of
+// squash.hip): the state stays in registers.
+#include "trace_step.hpp"
+
+namespace {
+
+using namespace ndsm;
+
+constexpr int kNptsBlock = 256;
+constexpr int kScanBlock = 1024;
+
+typedef long long i64;
+
+__global__ __launch_bounds__(kNptsBlock) void npts_k(const int32_t *__restrict__ nsteps, size_t nl, int every,
+                                                     i64 *__restrict__ npts) {
+  const size_t l = (size_t)blockIdx.x * kNptsBlock + threadIdx.x;
+  if (l >= nl) return;
+  const int n = nsteps[l];
+  npts[l] = n <= 0 ? 1 : (i64)((n - 1) / every) + 2;
+}
+
+// in place: a[q] <- a[0] + ... + a[q - 1] for q < ng, a[ng] <- the sum of all.  One workgroup: every lane sums a
+// contiguous run and rewrites that run alone; the kScanBlock run totals are scanned in LDS.
+__global__ __launch_bounds__(kScanBlock) void scan64_k(i64 *a, size_t ng) {
+  __shared__ i64 part[kScanBlock];
+  const size_t per = (ng + kScanBlock - 1) / kScanBlock;
+  const size_t lo = threadIdx.x * per < ng ? threadIdx.x * per : ng;
+  const size_t hi = lo + per < ng ? lo + per : ng;
+  i64 s = 0;
+  for (size_t q = lo; q < hi; ++q) s += a[q];
+  part[threadIdx.x] = s;
+  __syncthreads();
+  for (int d = 1; d < kScanBlock; d <<= 1) {
+    const i64 v = (int)threadIdx.x >= d ? part[threadIdx.x - d] : 0;
+    __syncthreads();
+    part[threadIdx.x] += v;
+    __syncthreads();
+  }
+  i64 run = part[threadIdx.x] - s;
+  for (size_t q = lo; q < hi; ++q) {
+    const i64 c = a[q];
+    a[q] = run;
+    run += c;
+  }
+  if (threadIdx.x == kScanBlock - 1) a[ng] = part[kScanBlock - 1];
+}
+
+struct PathOut {
+  double *points, *bpt, *gpt, *ipt;   // bpt, gpt, ipt may be nullptr: skipped
+};
+
+// slot k of the concatenation (the caller has bounded k)
+template <bool kHasG>
+__device__ __forceinline__ void put_point(const PathOut &o, i64 k, double x, double y, double z, const double bv[3],
+                                          const double gv[3], double I) {
+  o.points[3 * k] = x;
+  o.points[3 * k + 1] = y;
+  o.points[3 * k + 2] = z;
+  if (o.bpt) {
+    o.bpt[3 * k] = bv[0];
+    o.bpt[3 * k + 1] = bv[1];
+    o.bpt[3 * k + 2] = bv[2];
+  }
+  if (kHasG) {
+    if (o.gpt) {
+      o.gpt[3 * k] = gv[0];
+      o.gpt[3 * k + 1] = gv[1];
+      o.gpt[3 * k + 2] = gv[2];
+    }
+    if (o.ipt) o.ipt[k] = I;
+  }
+}
+
+// lane l: seed l % nseeds, direction block l / nseeds, as trace_k; its points go to slots offsets[l] + j, j < room
+template <bool kHasG>
+__global__ __launch_bounds__(kLineBlock) void paths_k(const double *__restrict__ B, const double *__restrict__ G,
+                                                      const double *__restrict__ seeds,
+                                                      const i64 *__restrict__ offsets, i64 every, i64 max_points,
+                                                      PathOut o, TrArgs p) {
+  const size_t l = (size_t)blockIdx.x * kLineBlock + threadIdx.x;
+  const size_t nl = (size_t)p.nseeds * (size_t)p.ndir;
+  if (l >= nl) return;
+  const size_t is = l % (size_t)p.nseeds;
+  const double sgn = (l / (size_t)p.nseeds == 0) ? (double)p.sgn0 : -1.0;
+  const size_t sy = (size_t)p.n[0], sz = (size_t)p.n[0] * (size_t)p.n[1];
+  const size_t N = sz * (size_t)p.n[2];
+
+  // the slots of this lane: [base, min(offsets[l + 1], max_points)) and nothing else
+  const i64 base = offsets[l];
+  const i64 next_base = offsets[l + 1];
+  const i64 stop = next_base < max_points ? next_base : max_points;
+  const i64 room = (base >= 0 && stop > base) ? stop - base : 0;
+  if (room == 0) return;
+
+  double r[3] = {seeds[3 * is], seeds[3 * is + 1], seeds[3 * is + 2]};
+  double I = 0.0;
+  double bv[3] = {0.0, 0.0, 0.0}, gv[3] = {0.0, 0.0, 0.0};
+  i64 j = 0;            // points stored so far
+  i64 due = 0;          // the next step count whose state is stored
+  bool inside = true;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) inside = inside && (r[d] >= p.lo[d]) && (r[d] <= p.hi[d]);
+  if (!inside) {
+    // OUTSIDE: the seed's bits as given, nothing interpolated
+    put_point<kHasG>(o, base, r[0], r[1], r[2], bv, gv, 0.0);
+    return;
+  }
+  for (int it = 0; it < p.max_steps; ++it) {
+    double k1[3], q1, rn[3], dI;
+    if (!tr_stage<kHasG, true>(B, G, p, N, sy, sz, sgn, r[0], r[1], r[2], k1, q1, bv, gv) ||
+        !tr_rk4<kHasG>(B, G, p, N, sy, sz, sgn, r, k1, q1, p.ds, rn, dI))
+      break;                                    // NULL: the state after `it` steps is the final one
+    double t;
+    const int face = line_first_face(p, r, rn, t);
+    double s = p.ds;
+    if (face != 0) {
+      s = t * p.ds;
+      if (!tr_rk4<kHasG>(B, G, p, N, sy, sz, sgn, r, k1, q1, s, rn, dI)) break;
+    }
+    // step `it` moves the line: the state before it is a point when `it` is a multiple of every
+    if ((i64)it == due) {
+      if (j < room) put_point<kHasG>(o, base + j, r[0], r[1], r[2], bv, gv, I);
+      j = j + 1;
+      due = due + every;
+    }
+    I = I + dI;
+    if (face == 0) {
+      r[0] = rn[0], r[1] = rn[1], r[2] = rn[2];
+      continue;
+    }
+    line_snap(p, face, rn, r);
+    break;
+  }
+  // the final state, with B and G interpolated at it (after the snap)
+  if (j < room) {
+    double k1[3], q1;
+    (void)tr_stage<kHasG, true>(B, G, p, N, sy, sz, sgn, r[0], r[1], r[2], k1, q1, bv, gv);
+    put_point<kHasG>(o, base + j, r[0], r[1], r[2], bv, gv, I);
+  }
+}
+
+int path_args(const char *usage, bool own_ok, bool arrays_ok, const int32_t *n3, const double *lo3,
+              const double *h_dq3, int nseeds, double step, int max_steps, int direction, TrArgs &p) {
+  p.ndir = direction == 0 ? 2 : 1;
+  p.sgn0 = direction < 0 ? -1 : 1;
+  return line_args(usage, own_ok && direction >= -1 && direction <= 1, arrays_ok, n3, lo3, h_dq3, nseeds, step,
+                   max_steps, p.ndir, p);
+}
+
+}  // namespace
+
+// The counting half: ndsmk_trace with the same arguments (the five trace outputs are the trace entry's), then
+// offsets (nl + 1, int64, DEVICE) = the exclusive sums of the lines' point counts for the stride `every`, offsets[nl]
+// the total, which also comes back in *h_total (HOST).  max_points is the filling half's and only checked here: a call
+// that the filling half would refuse launches nothing.  Blocks for the total.
+extern "C" int ndsmk_paths_count(const double *B, const double *G, const int32_t *n3, const double *lo3,
+                                 const double *h_dq3, int nseeds, const double *seeds, double step, int max_steps,
+                                 int direction, int every, int64_t max_points, double *ends, double *length,
+                                 double *integral, int32_t *status, int32_t *nsteps, int64_t *offsets,
+                                 int64_t *h_total) {
+  NDSM_REQUIRE_READY();
+  if (h_total) *h_total = 0;
+  TrArgs p;
+  int rc = path_args("paths: step > 0 (finite), max_steps >= 1, direction in -1, 0, 1, every >= 1, max_points >= 0 and "
+                     "nseeds >= 0",
+                     every >= 1 && max_points >= 0, B && seeds && ends && length && integral && status && nsteps && offsets && h_total,
+                     n3, lo3, h_dq3, nseeds, step, max_steps, direction, p);
+  if (rc != 0 || nseeds == 0) return rc;
+  rc = ndsmk_trace(B, G, n3, lo3, h_dq3, nseeds, seeds, step, max_steps, direction, ends, length, integral, status,
+                   nsteps);
+  if (rc != 0) return rc;
+  const size_t nl = (size_t)nseeds * (size_t)p.ndir;
+  hipStream_t s = ndsm::stream();
+  hipLaunchKernelGGL(npts_k, dim3((unsigned)((nl + kNptsBlock - 1) / kNptsBlock)), dim3(kNptsBlock), 0, s, nsteps, nl,
+                     every, (i64 *)offsets);
+  NDSM_LAUNCH_CHECK();
+  hipLaunchKernelGGL(scan64_k, dim3(1), dim3(kScanBlock), 0, s, (i64 *)offsets, nl);
+  NDSM_LAUNCH_CHECK();
+  NDSM_HIP(hipMemcpyAsync(h_total, offsets + nl, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  NDSM_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+// The filling half, after ndsmk_paths_count with the same arguments and its offsets: slot k < max_points of the
+// concatenation into points (3 each) and, where given, bpt, gpt (3 each) and ipt (gpt, ipt are not looked at without
+// G).  All DEVICE arrays.  max_points == 0 launches nothing.  Asynchronous.
+extern "C" int ndsmk_paths_fill(const double *B, const double *G, const int32_t *n3, const double *lo3,
+                                const double *h_dq3, int nseeds, const double *seeds, double step, int max_steps,
+                                int direction, int every, int64_t max_points, const int64_t *offsets, double *points,
+                                double *bpt, double *gpt, double *ipt) {
+  NDSM_REQUIRE_READY();
+  TrArgs p;
+  const int rc = path_args("paths: step > 0 (finite), max_steps >= 1, direction in -1, 0, 1, every >= 1, "
+                           "max_points >= 0 and nseeds >= 0",
+                           every >= 1 && max_points >= 0, B && seeds && offsets && (max_points == 0 || points), n3,
+                           lo3, h_dq3, nseeds, step, max_steps, direction, p);
+  if (rc != 0 || nseeds == 0 || max_points == 0) return rc;
+  const size_t nl = (size_t)nseeds * (size_t)p.ndir;
+  const unsigned nb = (unsigned)((nl + kLineBlock - 1) / kLineBlock);
+  const PathOut o = {points, bpt, G ? gpt : nullptr, G ? ipt : nullptr};
+  hipStream_t s = ndsm::stream();
+  if (G)
+    hipLaunchKernelGGL(paths_k<true>, dim3(nb), dim3(kLineBlock), 0, s, B, G, seeds, (const i64 *)offsets, (i64)every,
+                       (i64)max_points, o, p);
+  else
+    hipLaunchKernelGGL(paths_k<false>, dim3(nb), dim3(kLineBlock), 0, s, B, G, seeds, (const i64 *)offsets, (i64)every,
+                       (i64)max_points, o, p);
+  NDSM_LAUNCH_CHECK();
+  return 0;
+}

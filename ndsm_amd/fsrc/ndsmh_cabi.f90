@@ -1031,6 +1031,134 @@ contains
     end subroutine
   end function
 
+  ! ---- field-line paths on the same handle ---------------------------------
+  ! As the trace entries, with the points of every line: B, G, seeds, step, max_steps, direction and the five trace
+  ! outputs as there; every >= 1 the stride in steps between stored points, max_points >= 0 the capacity of the point
+  ! arrays (0: count only).  Out: offsets (nl + 1, int64), total (one int64, on the HOST in both entries), points
+  ! (3,max_points), bpt, gpt (the same), ipt (max_points); bpt, gpt, ipt may be NULL.  Return value: 0, or >= 9001
+  ! errors (9002 a NULL handle or total, with nseeds > 0 a NULL required array, with max_points > 0 also a NULL points;
+  ! 9004 a scalar out of range).  On every failure total is cleared, and the host entry clears the nl entries of the
+  ! trace outputs, the nl + 1 of offsets and the max_points slots of its point arrays.
+
+  ! HOST arrays
+  function ndsm_hip_vecpot_paths(handle, B, G, nseeds, seeds, step, max_steps, direction, every, max_points, ends, &
+                                 length, integral, status, nsteps, offsets, total, points, bpt, gpt, ipt) &
+      bind(c, name="ndsm_hip_vecpot_paths") result(ierr)
+    type(c_ptr), value :: handle, B, G, seeds, ends, length, integral, status, nsteps, offsets, total, points, bpt, gpt, &
+                          ipt
+    integer(c_int), value :: nseeds, max_steps, direction, every
+    integer(c_int64_t), value :: max_points
+    real(c_double), value :: step
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_paths(handle, B, G, nseeds, seeds, step, max_steps, direction, every, max_points, ends, &
+                               length, integral, status, nsteps, offsets, total, points, bpt, gpt, ipt, .false., &
+                               "ndsm_hip_vecpot_paths")
+  end function
+
+  ! the same on DEVICE arrays of the library's GPU (total stays on the host; no array is touched on the host)
+  function ndsm_hip_vecpot_paths_device(handle, dB, dG, nseeds, dseeds, step, max_steps, direction, every, max_points, &
+                                        dends, dlength, dintegral, dstatus, dnsteps, doffsets, total, dpoints, dbpt, &
+                                        dgpt, dipt) bind(c, name="ndsm_hip_vecpot_paths_device") result(ierr)
+    type(c_ptr), value :: handle, dB, dG, dseeds, dends, dlength, dintegral, dstatus, dnsteps, doffsets, total, dpoints, &
+                          dbpt, dgpt, dipt
+    integer(c_int), value :: nseeds, max_steps, direction, every
+    integer(c_int64_t), value :: max_points
+    real(c_double), value :: step
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_paths(handle, dB, dG, nseeds, dseeds, step, max_steps, direction, every, max_points, dends, &
+                               dlength, dintegral, dstatus, dnsteps, doffsets, total, dpoints, dbpt, dgpt, dipt, &
+                               .true., "ndsm_hip_vecpot_paths_device")
+  end function
+
+  function vecpot_handle_paths(handle, B, G, nseeds, seeds, step, max_steps, direction, every, max_points, ends, &
+                               length, integral, status, nsteps, offsets, total, points, bpt, gpt, ipt, on_device, &
+                               who) result(ierr)
+    type(c_ptr), intent(in) :: handle, B, G, seeds, ends, length, integral, status, nsteps, offsets, total, points, bpt, &
+                               gpt, ipt
+    integer(c_int), intent(in) :: nseeds, max_steps, direction, every
+    integer(c_int64_t), intent(in) :: max_points
+    real(c_double), intent(in) :: step
+    logical, intent(in) :: on_device
+    character(len=*), intent(in) :: who
+    integer(c_int) :: ierr
+    ierr = checked()
+    if (ierr /= 0) call clear_outputs()
+  contains
+    function checked() result(rc)
+      integer(c_int) :: rc
+      type(vecpot_ctx), pointer :: ctx
+      integer(c_int64_t), pointer :: tot
+      rc = ndsmk_init(-1_c_int)                        ! without a device: 9001, whatever the arguments
+      if (rc /= 0) return
+      rc = NDSMK_EARG
+      if (.not. (c_associated(handle) .and. c_associated(total))) return
+      call c_f_pointer(total, tot)
+      tot = 0
+      ! no seeds: no array is looked at; the scalars are the kernel layer's to judge (9004) once the arrays are there
+      if (nseeds > 0) then
+        if (.not. (c_associated(B) .and. c_associated(seeds) .and. c_associated(ends) .and. c_associated(length) .and. &
+                   c_associated(integral) .and. c_associated(status) .and. c_associated(nsteps) .and. &
+                   c_associated(offsets))) return
+        if (max_points > 0 .and. .not. c_associated(points)) return
+      end if
+      call c_f_pointer(handle, ctx)
+      if (.not. ctx%live) return
+      rc = vecpot_paths(ctx, B, G, direction, nseeds, seeds, step, max_steps, every, max_points, ends, length, &
+                        integral, status, nsteps, offsets, tot, points, bpt, gpt, ipt, on_device)
+      if (rc /= 0) then
+        call report(who, rc)
+        if (rc < NDSMK_ENODEV) rc = NDSMK_ENODEV
+      end if
+    end function
+
+    ! total, and (host entry) the nl entries of the trace outputs, the nl + 1 of offsets and the max_points slots of
+    ! every point array that is there
+    subroutine clear_outputs()
+      real(c_double), pointer :: r(:)
+      integer(c_int32_t), pointer :: k(:)
+      integer(c_int64_t), pointer :: k8(:)
+      integer :: nl
+      if (c_associated(total)) then
+        call c_f_pointer(total, k8, [1]); k8 = 0
+      end if
+      if (on_device) return
+      if (nseeds > 0 .and. nseeds <= huge(0) / 6) then
+        nl = nseeds * merge(2, 1, direction == 0)
+        if (c_associated(ends)) then
+          call c_f_pointer(ends, r, [3 * nl]); r = 0
+        end if
+        if (c_associated(length)) then
+          call c_f_pointer(length, r, [nl]); r = 0
+        end if
+        if (c_associated(integral)) then
+          call c_f_pointer(integral, r, [nl]); r = 0
+        end if
+        if (c_associated(status)) then
+          call c_f_pointer(status, k, [nl]); k = 0
+        end if
+        if (c_associated(nsteps)) then
+          call c_f_pointer(nsteps, k, [nl]); k = 0
+        end if
+        if (c_associated(offsets)) then
+          call c_f_pointer(offsets, k8, [nl + 1]); k8 = 0
+        end if
+      end if
+      if (max_points <= 0 .or. max_points > huge(0_c_int64_t) / 3) return
+      if (c_associated(points)) then
+        call c_f_pointer(points, r, [3 * max_points]); r = 0
+      end if
+      if (c_associated(bpt)) then
+        call c_f_pointer(bpt, r, [3 * max_points]); r = 0
+      end if
+      if (c_associated(gpt)) then
+        call c_f_pointer(gpt, r, [3 * max_points]); r = 0
+      end if
+      if (c_associated(ipt)) then
+        call c_f_pointer(ipt, r, [max_points]); r = 0
+      end if
+    end subroutine
+  end function
+
   ! ---- null points on the same handle --------------------------------------
   ! B (nx,ny,nz,3) in; max_nulls >= 0 the capacity of the record arrays; counts (2, int64, on the HOST in both
   ! entries): the screen's candidates, the nulls found.  Out, the first min(counts(2), max_nulls) records in ascending

@@ -595,6 +595,31 @@ module ndsmh_iface
       integer(c_int) :: rc
     end function
 
+    ! ---- field-line paths (paths.hip): the counting half (blocks for total) and the filling half ----
+    function ndsmk_paths_count(B, G, n3, lo3, dq3, nseeds, seeds, step, max_steps, direction, every, max_points, ends, &
+                               length, integral, status, nsteps, offsets, total) bind(c, name="ndsmk_paths_count") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_int64_t, c_double
+      type(c_ptr), value :: B, G, seeds, ends, length, integral, status, nsteps, offsets
+      integer(c_int32_t), intent(in) :: n3(3)
+      real(c_double), intent(in) :: lo3(3), dq3(3)
+      integer(c_int), value :: nseeds, max_steps, direction, every
+      real(c_double), value :: step
+      integer(c_int64_t), value :: max_points
+      integer(c_int64_t), intent(out) :: total
+      integer(c_int) :: rc
+    end function
+    function ndsmk_paths_fill(B, G, n3, lo3, dq3, nseeds, seeds, step, max_steps, direction, every, max_points, &
+                              offsets, points, bpt, gpt, ipt) bind(c, name="ndsmk_paths_fill") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_int64_t, c_double
+      type(c_ptr), value :: B, G, seeds, offsets, points, bpt, gpt, ipt
+      integer(c_int32_t), intent(in) :: n3(3)
+      real(c_double), intent(in) :: lo3(3), dq3(3)
+      integer(c_int), value :: nseeds, max_steps, direction, every
+      real(c_double), value :: step
+      integer(c_int64_t), value :: max_points
+      integer(c_int) :: rc
+    end function
+
     ! ---- the face phase on the device (faces.hip) ----
     function ndsmk_face_offsets(n3, off6, total) bind(c, name="ndsmk_face_offsets") result(rc)
       import :: c_int, c_int32_t, c_int64_t

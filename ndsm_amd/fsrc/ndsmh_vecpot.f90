@@ -32,7 +32,7 @@ module ndsmh_vecpot
 
   public :: vecpot_solve, poisson_solve
   public :: vecpot_ctx, vecpot_ctx_create, vecpot_ctx_destroy, vecpot_ctx_matches, vecpot_run, vecpot_cache_drop
-  public :: vecpot_project, vecpot_devore, vecpot_lines, vecpot_nulls
+  public :: vecpot_project, vecpot_devore, vecpot_lines, vecpot_paths, vecpot_nulls
   public :: VP_POTENTIAL, VP_FIELD, VP_HELICITY
   ! pieces the distributed driver (ndsmh_wvecpot) shares with vecpot_solve
   public :: face_data, face_axis, face_upper, face_t1, face_t2, face_order, face_copy, vecpot_faces, say
@@ -1154,6 +1154,132 @@ contains
       else
         rc = ndsmk_trace(B, G, n3, lo, dq, nseeds, seeds, step, max_steps, sel, ends, length, integral, status, nsteps)
       end if
+    end function
+  end function
+
+  ! ------------------------------------------------------------------
+  ! The path entries on a prepared context (semantics in include/ndsm_hip.h, DESIGN.md "Field-line paths"): the
+  ! points of the lines that vecpot_lines traces, with B, G and the running integral at each.  The context supplies
+  ! the mesh only, as in vecpot_lines: no solve, no hierarchy.  pB, pG, pseeds and the five trace outputs as there
+  ! (sel = direction); every >= 1 the stride, max_points >= 0 the capacity of the point arrays; poff (nl + 1, int64)
+  ! and total out; ppts (3,max_points), pbpt, pgpt (the same; c_null_ptr: skipped), pipt (max_points; likewise) out -
+  ! on the HOST (B and G go up into the staging arrays dF(1) and dF(2), the seeds and the line outputs into a scratch
+  ! buffer; after the counting half a second buffer of min(total, max_points) points is allocated, filled, and only
+  ! what was written comes home) or (on_device) in HBM.  total is a host scalar either way.
+  ! ------------------------------------------------------------------
+  function vecpot_paths(ctx, pB, pG, sel, nseeds, pseeds, step, max_steps, every, max_points, pends, plen, pint, &
+                        pstat, pnst, poff, total, ppts, pbpt, pgpt, pipt, on_device) result(rc)
+    type(vecpot_ctx), intent(inout), target :: ctx
+    logical, intent(in) :: on_device
+    type(c_ptr), intent(in) :: pB, pG, pseeds, pends, plen, pint, pstat, pnst, poff, ppts, pbpt, pgpt, pipt
+    integer(c_int), intent(in) :: sel, nseeds, max_steps, every
+    integer(c_int64_t), intent(in) :: max_points
+    real(wp), intent(in) :: step
+    integer(c_int64_t), intent(out) :: total
+    integer(c_int) :: rc, rc_free
+    real(wp) :: dq(3), lo(3)
+    integer(c_int32_t) :: n3(3)
+    integer(c_size_t) :: nb, nl, ns, np, no
+    integer :: i
+    type(c_ptr) :: dB, dG, buf, pbuf, d(7), dp(4), hp(4), hl(5)
+    ! bytes per line of ends, length, integral, status, nsteps (the seeds and offsets are sized apart), and per point
+    ! of points, bpt, gpt, ipt
+    integer(c_size_t), parameter :: lwidth(5) = [24, 8, 8, 4, 4], pwidth(4) = [24, 24, 24, 8]
+
+    total = 0
+    n3 = ctx%n3
+    dq = [ctx%qx(2) - ctx%qx(1), ctx%qy(2) - ctx%qy(1), ctx%qz(2) - ctx%qz(1)]      ! as vecpot_run
+    lo = [ctx%qx(1), ctx%qy(1), ctx%qz(1)]
+    if (on_device .or. nseeds <= 0 .or. step <= 0.0_wp .or. max_steps < 1 .or. sel < -1 .or. sel > 1 .or. &
+        every < 1 .or. max_points < 0) then
+      ! (the argument errors are the kernel entries' to name; nothing is staged for them)
+      rc = ndsmk_paths_count(pB, pG, n3, lo, dq, nseeds, pseeds, step, max_steps, sel, every, max_points, pends, plen, &
+                             pint, pstat, pnst, poff, total)
+      if (rc == 0) rc = ndsmk_paths_fill(pB, pG, n3, lo, dq, nseeds, pseeds, step, max_steps, sel, every, max_points, &
+                                         poff, ppts, pbpt, pgpt, pipt)
+      if (rc == 0) rc = ndsmk_sync()
+      if (rc /= 0) total = 0
+      return
+    end if
+    nb = int(product(int(n3, ik)), c_size_t) * 24_c_size_t
+    ns = int(nseeds, c_size_t)
+    nl = ns * merge(2_c_size_t, 1_c_size_t, sel == 0)
+    ! the helicity entries' host staging: dF(1) B, dF(2) G
+    if (.not. c_associated(ctx%dF(1))) then
+      rc = ndsmk_alloc(ctx%dF(1), nb); if (rc /= 0) return
+    end if
+    if (c_associated(pG) .and. .not. c_associated(ctx%dF(2))) then
+      rc = ndsmk_alloc(ctx%dF(2), nb); if (rc /= 0) return
+    end if
+    dB = ctx%dF(1)
+    dG = c_null_ptr
+    rc = ndsmk_h2d(dB, pB, nb); if (rc /= 0) return
+    if (c_associated(pG)) then
+      dG = ctx%dF(2)
+      rc = ndsmk_h2d(dG, pG, nb); if (rc /= 0) return
+    end if
+    ! one scratch buffer of the lines: offsets and seeds (8-byte data first), then the five trace outputs
+    buf = c_null_ptr
+    pbuf = c_null_ptr
+    rc = ndsmk_alloc(buf, 8_c_size_t * (nl + 1) + 24_c_size_t * ns + sum(lwidth) * nl); if (rc /= 0) return
+    d(1) = buf                                                  ! offsets
+    d(2) = dptr_offset(buf, 8_c_size_t * (nl + 1))              ! seeds
+    no = 8_c_size_t * (nl + 1) + 24_c_size_t * ns
+    do i = 1, 5
+      d(2 + i) = dptr_offset(buf, no)
+      no = no + lwidth(i) * nl
+    end do
+    rc = ndsmk_h2d(d(2), pseeds, 24_c_size_t * ns)
+    if (rc == 0) then
+      call say("trace_paths", "Tracing field lines and counting their points...")
+      rc = ndsmk_paths_count(dB, dG, n3, lo, dq, nseeds, d(2), step, max_steps, sel, every, max_points, d(3), d(4), &
+                             d(5), d(6), d(7), d(1), total)
+    end if
+    ! the point arrays: min(total, max_points) slots each, carved from a second buffer
+    np = 0
+    if (rc == 0) np = int(min(total, max_points), c_size_t)
+    dp = c_null_ptr
+    hp = [ppts, pbpt, pgpt, pipt]
+    if (.not. c_associated(pG)) hp(3:4) = c_null_ptr
+    if (rc == 0 .and. np > 0) then
+      rc = ndsmk_alloc(pbuf, sum(pwidth, mask=c_associated_all(hp)) * np)
+      no = 0
+      do i = 1, 4
+        if (rc == 0 .and. c_associated(hp(i))) then
+          dp(i) = dptr_offset(pbuf, no)
+          no = no + pwidth(i) * np
+        end if
+      end do
+      if (rc == 0) then
+        call say("trace_paths", "Tracing again and storing the points...")
+        rc = ndsmk_paths_fill(dB, dG, n3, lo, dq, nseeds, d(2), step, max_steps, sel, every, int(np, c_int64_t), d(1), &
+                              dp(1), dp(2), dp(3), dp(4))
+      end if
+    end if
+    if (rc == 0) rc = ndsmk_d2h(poff, d(1), 8_c_size_t * (nl + 1))
+    hl = [pends, plen, pint, pstat, pnst]
+    do i = 1, 5
+      if (rc == 0) rc = ndsmk_d2h(hl(i), d(2 + i), lwidth(i) * nl)
+    end do
+    do i = 1, 4
+      if (rc == 0 .and. np > 0 .and. c_associated(hp(i))) rc = ndsmk_d2h(hp(i), dp(i), pwidth(i) * np)
+    end do
+    if (rc == 0) rc = ndsmk_sync()
+    if (c_associated(pbuf)) then
+      rc_free = ndsmk_free(pbuf)
+      if (rc == 0) rc = rc_free
+    end if
+    rc_free = ndsmk_free(buf)
+    if (rc == 0) rc = rc_free
+    if (rc /= 0) total = 0
+  contains
+    pure function c_associated_all(p) result(m)
+      type(c_ptr), intent(in) :: p(4)
+      logical :: m(4)
+      integer :: q
+      do q = 1, 4
+        m(q) = c_associated(p(q))
+      end do
     end function
   end function
 

@@ -510,6 +510,96 @@ int ndsm_hip_vecpot_nulls_device(void *h, const double *dB, int max_nulls, int64
                                  double *dpos, double *djac, double *ddet, double *dresid, int32_t *dsign,
                                  int32_t *diters);
 
+/* ---- Spine-fan skeleton of the nulls and null-to-null connections (DESIGN.md "Spine-fan skeleton") -------------------
+ * From the records of the nulls entries to the skeleton they anchor: the type of each null from its Jacobian, its two
+ * spine lines and a ring of fan lines, each traced AWAY from its null, and ended where it comes within a capture
+ * radius of ANOTHER null - dr/ds = B/|B| has no rest point, so a fan line that runs into a null (the lines that
+ * bracket a separator) would otherwise jitter round it for max_steps steps or drift off along its spine.  The handle
+ * supplies the mesh only; no solve runs.  Everything not said here is as in the trace and paths entries above: lo, h,
+ * hi, the clamped cell with unclamped fractions, the order of the interpolation, RK4 with ds = step * min(h), the exit
+ * step, the snap, the status codes 1 - 9, max_steps (clamped to 2^24), fp64 + - * / and sqrt only, in the operand
+ * order written here, no contraction: a restatement in the same order gives the same bits (tests/skeleton_model.py).
+ *   B          (nx,ny,nz,3)
+ *   pos, jac   nnulls records in the layout of the nulls entries: pos 3 each, jac 9 each, row-major (M_ab = dB_a/dx_b,
+ *              a slowest).  The device arrays that ndsm_hip_vecpot_nulls_device wrote can be passed straight in.
+ *              Merging duplicate records stays the caller's business.
+ *   ring       (2,nring): the coefficients (c_j, s_j) of ring seed j - the caller's cos and sin of its angle; nothing
+ *              is normalised here.  nring = 0: the spines alone (ring may be NULL).
+ *   radius     > 0, finite: the distance of the seeds from their null, rho = radius * min(h).
+ *   capture    >= 0, finite: the capture radius in units of min(h); 0 switches the capture test off.
+ *   every, max_points, offsets, total, points, bpt: exactly as in ndsm_hip_vecpot_paths (there is no G).
+ * Stage 1, the type of null m from M = jac (one lane per null):
+ *   1. det M = (M00 A00 + M01 A10) + M02 A20 with A00 = M11 M22 - M12 M21, A10 = M12 M20 - M10 M22, A20 = M10 M21 -
+ *      M11 M20 (the nulls entries' expansion).  s = +1 for det M > 0, -1 for det M < 0; otherwise (0 or NaN) the null
+ *      has NO TYPE: kind = 0.
+ *   2. N = s M (every entry times s).  The monic characteristic cubic of N is mu^3 - a mu^2 + b mu - c with
+ *      a = (N00 + N11) + N22, b = ((N00 N11 - N01 N10) + (N00 N22 - N02 N20)) + (N11 N22 - N12 N21), c = det N by the
+ *      expansion of 1 (c > 0).
+ *   3. The lone eigenvalue mu - the only one with the sign of the determinant - is the largest real root of the cubic.
+ *      Newton from mu = sqrt of the sum of the nine N_ab^2, added one by one in row-major order (the Frobenius norm: no
+ *      eigenvalue exceeds it, and to the right of its largest root the cubic is convex and increasing, so the descent
+ *      is monotone).  Per iteration, in Horner form: p = ((mu - a) mu + b) mu - c, p' = (3 mu - 2 a) mu + b,
+ *      delta = p / p', mu <- mu - delta; |delta| <= 2^-40 |mu| (the new mu): converged.  AT MOST 40 ITERATIONS; not
+ *      converged by then, or not mu > 0: kind = 0.
+ *   4. t = a - mu, the sum of the other two eigenvalues.  Not t < 0 (they do not lie on the other side: a source or
+ *      sink of data that is not solenoidal): kind = 0.
+ *   5. C = adj(N - mu I): with J = N, J_dd = N_dd - mu, the nine expressions A00 .. A22 of the nulls entries above.  C has
+ *      rank one: its columns are multiples of the spine vector v, its rows of the fan normal w.  Column j is (A0j, A1j,
+ *      A2j), row i is (Ai0, Ai1, Ai2); the sum of squares of each is (x x + y y) + z z.  v is the column with the
+ *      largest sum of squares - the lowest index on a tie -, each component divided by the sqrt of that sum, then
+ *      negated as a whole if its component of largest modulus (the lowest index on a tie) is < 0.  w the same way from
+ *      the rows.  A largest sum of squares that is not > 0: kind = 0.
+ *   6. The fan basis, by the squash entries' start rule with w in place of e: j the axis of the smallest |w_d| (x
+ *      before y before z on a tie), u_d = (1 if d = j else 0) - w_j w_d, e1 = u / sqrt((u0 u0 + u1 u1) + u2 u2),
+ *      e2 = w x e1 = (w1 e1_2 - w2 e1_1, w2 e1_0 - w0 e1_2, w0 e1_1 - w1 e1_0).
+ *   7. Out: kind = -s, so that +1 is the nulls entries' positive null (sign +1: the fan diverges), doubled to +-2
+ *      for a spiral, t t - 4 (c / mu) < 0; eig = (s mu, s t, c / mu): the spine eigenvalue of M, then the sum and the
+ *      product of its two fan eigenvalues; spine = v, normal = w.  With kind = 0 the three are zeros.
+ * Stage 2, the lines: L = 2 + nring lanes per null, lane l = m L + q, nl = nnulls L lines.
+ *   seeds      q = 0: pos_d + rho v_d; q = 1: pos_d - rho v_d; q = 2 + j: pos_d + rho (c_j e1_d + s_j e2_d).
+ *   direction  every lane runs away from its null: the spine lanes trace with sgn = s, the fan lanes with sgn = -s
+ *              (sgn as the direction of the trace entries: +1 along B).
+ *   the line   exactly the line of ndsm_hip_vecpot_paths (without G) for that seed and direction: ends, length,
+ *              status, nsteps, npts(l), offsets, *total, the stride every, the capacity max_points, the counting call
+ *              with max_points = 0, points and the optional bpt are as there.  A seed outside the box (or not finite)
+ *              is NDSM_HIP_TRACE_OUTSIDE.
+ *   capture    with (capture min(h))^2 > 0, after every accepted FULL step - not at the seed, not after the exit step -
+ *              with r the new point: for m' = 0 .. nnulls - 1 in ascending order, m' = m skipped, dx = r_0 - pos(m')_0,
+ *              dy, dz likewise, ((dx dx + dy dy) + dz dz) <= (capture min(h))^2 (the product capture min(h) formed
+ *              first, then squared).  The first m' that passes ends the line at r with status NDSM_HIP_SKEL_CAPTURED and
+ *              hit[l] = m'; that step counts in nsteps and length.  Otherwise hit[l] = -1.
+ *   no type    a null with kind = 0 gives L lines with status NDSM_HIP_SKEL_NONE: one point each with pos's bits as
+ *              given (ends too), length 0, nsteps 0, hit -1, bpt 0; nothing is interpolated.
+ * With capture = 0 every line's outputs and points are bit for bit those of ndsm_hip_vecpot_paths for that line's seed
+ * and direction; a captured line is bit for bit the first nsteps[l] steps of that line.  The bits do not depend on the
+ * number of nulls, their order (but hit names the FIRST null within reach), or the launch geometry.
+ * The constants 40 and 2^-40 are choices (DESIGN.md says why), not measurements.
+ * Returns 0, or >= 9001 errors: 9001 without a GPU whatever the arguments; 9002 a NULL handle or total, or with
+ * nnulls > 0 a NULL B, pos, jac, kind, eig, spine, normal, ends, length, status, nsteps, hit or offsets, with nring > 0 a
+ * NULL ring, with max_points > 0 a NULL points; 9004 nnulls < 0, nring < 0, every < 1, max_points < 0, a radius that is
+ * not > 0 or not finite, a capture that is < 0 or not finite, step not > 0 or not finite, max_steps < 1.  nnulls == 0
+ * succeeds, sets *total = 0 and touches nothing else.  On failure *total = 0, and the host entry also clears the nnulls
+ * entries of the per-null outputs, the nl entries of the per-line outputs, the nl + 1 entries of offsets and exactly
+ * max_points slots of each non-NULL point array; the device entry leaves its device arrays.  On success nothing past
+ * the written slots is touched by either entry.
+ * Device memory: the host entry stages B in the handle's scratch (24 B/pt) and the points it brings home,
+ * min(*total, max_points) of them (up to 48 B each); both entries keep 32 B per line of seeds between the two passes. */
+#define NDSM_HIP_SKEL_CAPTURED 10   /* came within the capture radius of another null: hit names it */
+#define NDSM_HIP_SKEL_NONE 11       /* the line's null has no type (kind = 0): nothing was traced */
+/* HOST arrays */
+int ndsm_hip_vecpot_skeleton(void *h, const double *B, int nnulls, const double *pos, const double *jac, int nring,
+                             const double *ring, double radius, double capture, double step, int max_steps, int every,
+                             int64_t max_points, int32_t *kind, double *eig, double *spine, double *normal,
+                             double *ends, double *length, int32_t *status, int32_t *nsteps, int32_t *hit,
+                             int64_t *offsets, int64_t *total, double *points, double *bpt);
+/* the same on DEVICE arrays of the library's GPU (B, pos, jac, ring and every output array; total stays on the host) */
+int ndsm_hip_vecpot_skeleton_device(void *h, const double *dB, int nnulls, const double *dpos, const double *djac,
+                                    int nring, const double *dring, double radius, double capture, double step,
+                                    int max_steps, int every, int64_t max_points, int32_t *dkind, double *deig,
+                                    double *dspine, double *dnormal, double *dends, double *dlength, int32_t *dstatus,
+                                    int32_t *dnsteps, int32_t *dhit, int64_t *doffsets, int64_t *total,
+                                    double *dpoints, double *dbpt);
+
 /* =====================================================================
  * PART 3 - additive exports, multi-GPU
  *

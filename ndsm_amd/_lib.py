@@ -107,6 +107,10 @@ def load_library(path=None):
     _nu = [ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 8
     L.ndsm_hip_vecpot_nulls.argtypes = _nu
     L.ndsm_hip_vecpot_nulls_device.argtypes = _nu
+    _sk = ([ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_int, ctypes.c_void_p] +
+           [ctypes.c_double] * 3 + [ctypes.c_int, ctypes.c_int, ctypes.c_int64] + [ctypes.c_void_p] * 13)
+    L.ndsm_hip_vecpot_skeleton.argtypes = _sk
+    L.ndsm_hip_vecpot_skeleton_device.argtypes = _sk
     L.ndsm_hip_device_alloc.argtypes = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
     L.ndsm_hip_device_free.argtypes = [ctypes.c_void_p]
     L.ndsm_hip_memcpy_h2d.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
@@ -676,6 +680,74 @@ class VecPot:
         return _nulls_tuple([a[:n] for a in out], int(counts[0]), int(counts[1]), None if merge is None else
                             float(merge) * hmin)
 
+    def skeleton(self, b, nulls=None, radius=0.5, nring=16, ring=None, capture=None, step=0.5, max_steps=None, every=1,
+                 max_points=None, values=True, device=False):
+        """The spine-fan skeleton of the nulls of b (3,nz,ny,nx), on the device (semantics: include/ndsm_hip.h,
+        ndsm_hip_vecpot_skeleton): each null is typed from its Jacobian - the spine vector, the fan normal, the
+        eigenvalues -, then its two spine lines and nring fan lines are traced away from it as paths() traces, and a
+        line that comes within `capture` of ANOTHER null ends there (status SKEL_CAPTURED, hit = that null): the fan
+        lines that bracket a separator.  nulls: a Nulls tuple (of nulls(), merged) or a (position, jacobian) pair;
+        None: self.nulls(b).  radius: the distance of the seeds from their null, capture (None: radius; 0: off) the
+        capture radius, both in units of min(h).  ring: (nring,2) coefficients (c_j, s_j) of the fan seeds pos + rho
+        (c_j e1 + s_j e2) in the fan basis; None: the angles 2 pi (j + 1/2) / nring.  step, max_steps, every,
+        max_points, values as paths().  Returns a Skeleton tuple: position (n,3), kind (n; +-1, +-2 for a spiral, the
+        sign that of Nulls.sign; 0: no type), eig (n,3: the spine eigenvalue, the sum and the product of the fan
+        eigenvalues), spine, normal (n,3), paths (a FieldPaths of the n (2 + nring) lines: lines.ends (n,L,3),
+        length, status, nsteps (n,L); no integral), hit (n,L; -1: not captured).  Line q of null m is lane m L + q:
+        q = 0, 1 the spine lines from pos +- rho spine, q = 2 + j ring seed j; spine_of, fan_of and connections
+        read the result.  device=True: the arrays are staged in device memory and the device-resident entry point
+        runs."""
+        radius, capture, ring = _skeleton_args(radius, nring, ring, capture)
+        _d0, step, max_steps = self._trace_args(step, max_steps, "forward")
+        every, max_points = _paths_args(every, max_points)
+        B = self._field_arg(b, "skeleton")
+        if nulls is None:
+            nulls = self.nulls(B.reshape(tuple(int(v) for v in self.nshape4[::-1])), device=device)
+        pos, jac = _skeleton_nulls(nulls)
+        n, nr = len(pos), len(ring)
+        L = 2 + nr
+        nl = n * L
+        if nl > TRACE_MAX_SEEDS:
+            raise NdsmHipError(f"skeleton: {nl} lines, at most {TRACE_MAX_SEEDS} per call (code 9002)")
+        withb = bool(values)
+        pernull = [np.zeros(n, dtype=np.int32), np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, 3))]
+        lines = [np.zeros((n, L, 3)), np.zeros((n, L)), np.zeros((n, L), dtype=np.int32),
+                 np.zeros((n, L), dtype=np.int32), np.zeros((n, L), dtype=np.int32)]
+        if n == 0:
+            return _skeleton_tuple(pos, nr, pernull, lines, np.zeros(1, dtype=np.int64), np.zeros((0, 3)),
+                                   np.zeros((0, 3)) if withb else None)
+        name = "ndsm_hip_vecpot_skeleton_device" if device else "ndsm_hip_vecpot_skeleton"
+        R = ring if nr else np.zeros((1, 2))
+        cap = 0 if max_points is None else max_points
+        for _attempt in range(2):
+            offsets = np.zeros(nl + 1, dtype=np.int64)
+            total = np.zeros(1, dtype=np.int64)
+            m = max(cap, 1)
+            pts = [np.zeros((m, 3)), np.zeros((m, 3)) if withb else None]
+            head = (radius, capture, step, max_steps, every, cap)
+            outs = pernull + lines + [offsets]
+            if not device:
+                ierr = self.L.ndsm_hip_vecpot_skeleton(
+                    self.h, B.ctypes.data, n, pos.ctypes.data, jac.ctypes.data, nr, R.ctypes.data if nr else None, *head,
+                    *[a.ctypes.data for a in outs], total.ctypes.data,
+                    *[None if a is None or cap == 0 else a.ctypes.data for a in pts])
+            else:
+                staged = [B, pos, jac, R] + outs + [a for a in pts if a is not None]
+
+                def call(dB, dpos, djac, dR, *ptrs):
+                    ptrs = list(ptrs)
+                    douts = [ptrs.pop(0) for _ in outs]
+                    dpts = [None if a is None or cap == 0 else ptrs.pop(0) for a in pts]
+                    return self.L.ndsm_hip_vecpot_skeleton_device(self.h, dB, n, dpos, djac, nr, dR if nr else None,
+                                                                  *head, *douts, total.ctypes.data, *dpts)
+                ierr = self._on_device(staged, call)
+            _check(ierr, name, self.L)
+            if int(total[0]) <= cap:
+                break
+            cap = int(total[0])
+        k = min(int(total[0]), cap)
+        return _skeleton_tuple(pos, nr, pernull, lines, offsets, pts[0][:k], None if pts[1] is None else pts[1][:k])
+
     def seed_plane(self, axis, value, n1, n2):
         """the (n1 n2, 3) seeds of a mesh-aligned cut through the handle's box: coordinate `axis` (0, 1, 2 = x, y, z)
         fixed at `value`, the other two (in the order x, y, z; the first of them fastest) n1 and n2 equally spaced
@@ -890,6 +962,90 @@ def _nulls_tuple(rec, ncandidates, nfound, radius):
     return Nulls(pos, cell, jac, sign, spiral, lam, spine, fan, det, resid, ncandidates, nfound)
 
 
+Skeleton = collections.namedtuple("Skeleton", ["position", "kind", "eig", "spine", "normal", "paths", "hit"])
+SKEL_CAPTURED, SKEL_NONE = 10, 11  # status codes of a skeleton line beyond TRACE_* (NDSM_HIP_SKEL_*)
+
+
+def _skeleton_ring(nring, ring):
+    """the (nring,2) coefficients (c_j, s_j) of the fan seeds: `ring` as given, or the angles 2 pi (j + 1/2) / nring"""
+    if ring is not None:
+        R = np.ascontiguousarray(np.asarray(ring, dtype=np.float64))
+        if R.ndim != 2 or R.shape[1] != 2:
+            raise ValueError(f"ring must have the shape (nring, 2), not {R.shape}")
+        return R.copy()
+    if (isinstance(nring, bool) or not isinstance(nring, (int, np.integer)) or not 0 <= nring <= 2 ** 20):
+        raise ValueError(f"nring must be an integer in 0 .. {2 ** 20}, not {nring!r}")
+    ang = 2.0 * np.pi * (np.arange(int(nring)) + 0.5) / max(int(nring), 1)
+    return np.stack([np.cos(ang), np.sin(ang)], axis=1).reshape(int(nring), 2)
+
+
+def _skeleton_args(radius, nring, ring, capture):
+    """(radius, capture, ring) of skeleton(); ValueError before anything is launched"""
+    def number(v):
+        return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and np.isfinite(v)
+    if not number(radius) or not radius > 0.0:
+        raise ValueError(f"radius must be a positive finite number, not {radius!r}")
+    if capture is None:
+        capture = radius
+    if not number(capture) or capture < 0.0:
+        raise ValueError(f"capture must be None or a finite number >= 0, not {capture!r}")
+    return float(radius), float(capture), _skeleton_ring(nring, ring)
+
+
+def _skeleton_nulls(nulls):
+    """(pos (n,3), jac (n,3,3)) of a Nulls tuple or a (position, jacobian) pair, contiguous copies"""
+    if hasattr(nulls, "position") and hasattr(nulls, "jacobian"):
+        pos, jac = nulls.position, nulls.jacobian
+    else:
+        pos, jac = nulls
+    pos = np.ascontiguousarray(np.asarray(pos, dtype=np.float64)).copy()
+    jac = np.ascontiguousarray(np.asarray(jac, dtype=np.float64)).copy()
+    if pos.ndim != 2 or pos.shape[1] != 3 or jac.shape != (len(pos), 3, 3):
+        raise NdsmHipError(f"skeleton: nulls of shapes {pos.shape}, {jac.shape}: (n, 3) and (n, 3, 3) are needed "
+                           "(code 9002)")
+    return pos, jac
+
+
+def _skeleton_tuple(pos, nring, pernull, lines, offsets, points, b):
+    """a Skeleton from [kind, eig, spine, normal], [ends, length, status, nsteps, hit] (lane order) and the points"""
+    n, L = len(pos), 2 + nring
+    ends, length, status, nsteps, hit = lines
+    fl = FieldLines(ends.reshape(n, L, 3), length.reshape(n, L), None, status.reshape(n, L), nsteps.reshape(n, L), None)
+    return Skeleton(pos, *pernull, FieldPaths(fl, offsets, points, b, None, None), hit.reshape(n, L))
+
+
+def _skeleton_null(sk, m):
+    n = len(sk.position)
+    if int(m) != m or not 0 <= m < n:
+        raise IndexError(f"null {m!r} of {n}")
+    return int(m), sk.hit.shape[1]
+
+
+def spine_of(sk, m):
+    """the two spine lines of null m of a Skeleton: [(points, b), (points, b)], from pos + rho spine and from
+    pos - rho spine, each running away from the null (b None with values=False)"""
+    m, L = _skeleton_null(sk, m)
+    return [path_of(sk.paths, m * L + q)[:2] for q in (0, 1)]
+
+
+def fan_of(sk, m):
+    """the fan lines of null m of a Skeleton, one per ring seed: [(points, b), ...]"""
+    m, L = _skeleton_null(sk, m)
+    return [path_of(sk.paths, m * L + q)[:2] for q in range(2, L)]
+
+
+def connections(sk):
+    """the null-to-null connections of a Skeleton: a list of (m, m', ring indices) - the fan lines of null m that
+    were captured by null m', ascending in m, then m'.  Neighbouring ring indices bracket a separator from m to m'."""
+    out = []
+    fan_hit = sk.hit[:, 2:]
+    captured = sk.paths.lines.status[:, 2:] == SKEL_CAPTURED
+    for m in range(len(sk.position)):
+        for other in np.unique(fan_hit[m][captured[m]]):
+            out.append((m, int(other), np.nonzero(captured[m] & (fan_hit[m] == other))[0]))
+    return out
+
+
 QMap = collections.namedtuple("QMap", ["q", "twist", "ends", "length", "integral", "status", "nsteps"])
 
 
@@ -1016,6 +1172,20 @@ def find_nulls(x, y, z, b, max_nulls=4096, merge=1e-6, lib=None):
     V = _grid_handle(x, y, z, b, 0, lib)
     try:
         return V.nulls(b, max_nulls=max_nulls, merge=merge)
+    finally:
+        V.close()
+
+
+def find_skeleton(x, y, z, b, nulls=None, radius=0.5, nring=16, ring=None, capture=None, step=0.5, max_steps=None,
+                  every=1, max_points=None, values=True, lib=None):
+    """The spine-fan skeleton of the nulls of b (3,nz,ny,nx) and the null-to-null connections: one-shot form of
+    VecPot.skeleton (returns its Skeleton tuple).  Raises NdsmHipError on device / runtime failures (>= 9001)."""
+    _skeleton_args(radius, nring, ring, capture)
+    _paths_args(every, max_points)
+    V = _grid_handle(x, y, z, b, 0, lib)
+    try:
+        return V.skeleton(b, nulls=nulls, radius=radius, nring=nring, ring=ring, capture=capture, step=step,
+                          max_steps=max_steps, every=every, max_points=max_points, values=values)
     finally:
         V.close()
 

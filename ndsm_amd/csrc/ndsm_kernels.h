@@ -251,6 +251,27 @@ int ndsmk_paths_fill(const double *B, const double *G, const int32_t *n3, const 
                      int nseeds, const double *seeds, double step, int max_steps, int direction, int every,
                      int64_t max_points, const int64_t *offsets, double *points, double *bpt, double *gpt, double *ipt);
 
+/* Spine-fan skeleton of the nulls (skeleton.hip; semantics: include/ndsm_hip.h, ndsm_hip_vecpot_skeleton), in two halves
+ * as the paths.  B a DEVICE array (nx,ny,nz,3); pos (3,nnulls), jac (9 each, row-major) the records of ndsmk_nulls, ring
+ * (2,nring) the coefficients of the fan seeds, all DEVICE arrays; radius and capture in units of min(h).  L = 2 + nring
+ * lines per null, nl = nnulls L.  ndsmk_skel_count: the type of every null - kind (nnulls), eig, spine, normal (3 each) -,
+ * the seeds and directions of its lanes into the file's own scratch, then the lines: ends (3,nl), length, status,
+ * nsteps, hit (nl) and offsets (nl + 1, int64) = the exclusive sums of the lines' point counts for the stride every,
+ * offsets[nl] = the total, which also comes back in *h_total (HOST); blocks for it.  ndsmk_skel_fill, after the counting
+ * half of the same call: slot k < max_points of the concatenation into points (3 each) and, where not NULL, bpt; a
+ * line writes inside [offsets[l], min(offsets[l + 1], max_points)) only; max_points == 0 launches nothing;
+ * asynchronous.  NDSMK_EVALUE by both halves for step <= 0, max_steps < 1, nnulls < 0, nring < 0, every < 1, max_points
+ * < 0, a radius that is not > 0 or a capture that is < 0 (or not finite); nnulls == 0 launches nothing (*h_total = 0). */
+enum { NDSMK_SKEL_CAPTURED = 10, NDSMK_SKEL_NONE = 11 };
+int ndsmk_skel_count(const double *B, const int32_t *n3, const double *lo3, const double *h_dq3, int nnulls,
+                     const double *pos, const double *jac, int nring, const double *ring, double radius,
+                     double capture, double step, int max_steps, int every, int64_t max_points, int32_t *kind,
+                     double *eig, double *spine, double *normal, double *ends, double *length, int32_t *status,
+                     int32_t *nsteps, int32_t *hit, int64_t *offsets, int64_t *h_total);
+int ndsmk_skel_fill(const double *B, const int32_t *n3, const double *lo3, const double *h_dq3, int nnulls,
+                    const double *pos, int nring, double radius, double capture, double step, int max_steps, int every,
+                    int64_t max_points, const int64_t *offsets, double *points, double *bpt);
+
 /* the face phase on the device (faces.hip): packed face buffers, six faces back to back */
 int ndsmk_face_offsets(const int32_t *n3, int64_t *off6, int64_t *total);
 int ndsmk_face_extract(const double *B, const int32_t *n3, double *faces);

@@ -6,7 +6,8 @@
 //   count   ndsmk_trace   the trace entry itself: ends, length, integral, status and n = nsteps of every line
 //           npts_k        offsets[l] = npts(l) = 1 if n = 0, else (n - 1) / every + 2
 //           scan64_k      in place: offsets[l] = the exclusive sum, offsets[nl] = the total; one workgroup, every lane
-//                         sums a contiguous run (the int64 sibling of nulls.hip's scan_k)
+//                         sums a contiguous run (scan64.hpp, shared with skeleton.hip; the int64 sibling of
+//                         nulls.hip's scan_k)
 //   fill    paths_k       one lane per line, one wave per workgroup, as trace_k: the loop of trace_k with
 //                         trace_step.hpp's stage and step - the same r and I - which stores the state before step
 //                         0, every, 2 every, ... once that step is known to move the line, and the final state
@@ -15,6 +16,7 @@
 // first pass and the capacity bound every store, whatever the second pass computes.  No atomic append, no guessed
 // capacity, no result that depends on the launch geometry.  No vector is indexed with a run-time axis (the rule of
 // squash.hip): the state stays in registers.
+#include "scan64.hpp"
 #include "trace_step.hpp"
 
 namespace {
@@ -22,9 +24,6 @@ namespace {
 using namespace ndsm;
 
 constexpr int kNptsBlock = 256;
-constexpr int kScanBlock = 1024;
-
-typedef long long i64;
 
 __global__ __launch_bounds__(kNptsBlock) void npts_k(const int32_t *__restrict__ nsteps, size_t nl, int every,
                                                      i64 *__restrict__ npts) {
@@ -32,32 +31,6 @@ __global__ __launch_bounds__(kNptsBlock) void npts_k(const int32_t *__restrict__
   if (l >= nl) return;
   const int n = nsteps[l];
   npts[l] = n <= 0 ? 1 : (i64)((n - 1) / every) + 2;
-}
-
-// in place: a[q] <- a[0] + ... + a[q - 1] for q < ng, a[ng] <- the sum of all.  One workgroup: every lane sums a
-// contiguous run and rewrites that run alone; the kScanBlock run totals are scanned in LDS.
-__global__ __launch_bounds__(kScanBlock) void scan64_k(i64 *a, size_t ng) {
-  __shared__ i64 part[kScanBlock];
-  const size_t per = (ng + kScanBlock - 1) / kScanBlock;
-  const size_t lo = threadIdx.x * per < ng ? threadIdx.x * per : ng;
-  const size_t hi = lo + per < ng ? lo + per : ng;
-  i64 s = 0;
-  for (size_t q = lo; q < hi; ++q) s += a[q];
-  part[threadIdx.x] = s;
-  __syncthreads();
-  for (int d = 1; d < kScanBlock; d <<= 1) {
-    const i64 v = (int)threadIdx.x >= d ? part[threadIdx.x - d] : 0;
-    __syncthreads();
-    part[threadIdx.x] += v;
-    __syncthreads();
-  }
-  i64 run = part[threadIdx.x] - s;
-  for (size_t q = lo; q < hi; ++q) {
-    const i64 c = a[q];
-    a[q] = run;
-    run += c;
-  }
-  if (threadIdx.x == kScanBlock - 1) a[ng] = part[kScanBlock - 1];
 }
 
 struct PathOut {

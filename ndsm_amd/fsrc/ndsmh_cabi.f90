@@ -1159,6 +1159,147 @@ contains
     end subroutine
   end function
 
+  ! ---- spine-fan skeleton of the nulls on the same handle --------------------
+  ! B (nx,ny,nz,3), pos (3,nnulls) and jac (9 each) - the nulls entries' records -, ring (2,nring), radius, capture,
+  ! step, max_steps, every, max_points in.  Out per null: kind (int32), eig, spine, normal (3 each); per line (nl =
+  ! nnulls (2 + nring)): ends (3 each), length, status, nsteps, hit (int32); offsets (nl + 1, int64), total (one int64,
+  ! on the HOST in both entries), points (3,max_points), bpt (the same; may be NULL).  Return value: 0, or >= 9001
+  ! errors (9002 a NULL handle or total, with nnulls > 0 a NULL required array, with nring > 0 a NULL ring, with
+  ! max_points > 0 a NULL points; 9004 a scalar out of range).  On every failure total is cleared, and the host entry
+  ! clears the nnulls and nl entries of its outputs, the nl + 1 of offsets and the max_points slots of its point arrays.
+
+  ! HOST arrays
+  function ndsm_hip_vecpot_skeleton(handle, B, nnulls, pos, jac, nring, ring, radius, capture, step, max_steps, every, &
+                                    max_points, kind, eig, spine, normal, ends, length, status, nsteps, hit, offsets, &
+                                    total, points, bpt) bind(c, name="ndsm_hip_vecpot_skeleton") result(ierr)
+    type(c_ptr), value :: handle, B, pos, jac, ring, kind, eig, spine, normal, ends, length, status, nsteps, hit, &
+                          offsets, total, points, bpt
+    integer(c_int), value :: nnulls, nring, max_steps, every
+    integer(c_int64_t), value :: max_points
+    real(c_double), value :: radius, capture, step
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_skeleton(handle, B, nnulls, pos, jac, nring, ring, radius, capture, step, max_steps, every, &
+                                  max_points, kind, eig, spine, normal, ends, length, status, nsteps, hit, offsets, &
+                                  total, points, bpt, .false., "ndsm_hip_vecpot_skeleton")
+  end function
+
+  ! the same on DEVICE arrays of the library's GPU (total stays on the host; no array is touched on the host)
+  function ndsm_hip_vecpot_skeleton_device(handle, dB, nnulls, dpos, djac, nring, dring, radius, capture, step, &
+                                           max_steps, every, max_points, dkind, deig, dspine, dnormal, dends, dlength, &
+                                           dstatus, dnsteps, dhit, doffsets, total, dpoints, dbpt) &
+      bind(c, name="ndsm_hip_vecpot_skeleton_device") result(ierr)
+    type(c_ptr), value :: handle, dB, dpos, djac, dring, dkind, deig, dspine, dnormal, dends, dlength, dstatus, dnsteps, &
+                          dhit, doffsets, total, dpoints, dbpt
+    integer(c_int), value :: nnulls, nring, max_steps, every
+    integer(c_int64_t), value :: max_points
+    real(c_double), value :: radius, capture, step
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_skeleton(handle, dB, nnulls, dpos, djac, nring, dring, radius, capture, step, max_steps, every, &
+                                  max_points, dkind, deig, dspine, dnormal, dends, dlength, dstatus, dnsteps, dhit, &
+                                  doffsets, total, dpoints, dbpt, .true., "ndsm_hip_vecpot_skeleton_device")
+  end function
+
+  function vecpot_handle_skeleton(handle, B, nnulls, pos, jac, nring, ring, radius, capture, step, max_steps, every, &
+                                  max_points, kind, eig, spine, normal, ends, length, status, nsteps, hit, offsets, &
+                                  total, points, bpt, on_device, who) result(ierr)
+    type(c_ptr), intent(in) :: handle, B, pos, jac, ring, kind, eig, spine, normal, ends, length, status, nsteps, hit, &
+                               offsets, total, points, bpt
+    integer(c_int), intent(in) :: nnulls, nring, max_steps, every
+    integer(c_int64_t), intent(in) :: max_points
+    real(c_double), intent(in) :: radius, capture, step
+    logical, intent(in) :: on_device
+    character(len=*), intent(in) :: who
+    integer(c_int) :: ierr
+    ierr = checked()
+    if (ierr /= 0) call clear_outputs()
+  contains
+    function checked() result(rc)
+      integer(c_int) :: rc
+      type(vecpot_ctx), pointer :: ctx
+      integer(c_int64_t), pointer :: tot
+      rc = ndsmk_init(-1_c_int)                        ! without a device: 9001, whatever the arguments
+      if (rc /= 0) return
+      rc = NDSMK_EARG
+      if (.not. (c_associated(handle) .and. c_associated(total))) return
+      call c_f_pointer(total, tot)
+      tot = 0
+      ! no nulls: no array is looked at; the scalars are the kernel layer's to judge (9004) once the arrays are there
+      if (nnulls > 0) then
+        if (.not. (c_associated(B) .and. c_associated(pos) .and. c_associated(jac) .and. c_associated(kind) .and. &
+                   c_associated(eig) .and. c_associated(spine) .and. c_associated(normal) .and. c_associated(ends) .and. &
+                   c_associated(length) .and. c_associated(status) .and. c_associated(nsteps) .and. &
+                   c_associated(hit) .and. c_associated(offsets))) return
+        if (nring > 0 .and. .not. c_associated(ring)) return
+        if (max_points > 0 .and. .not. c_associated(points)) return
+      end if
+      call c_f_pointer(handle, ctx)
+      if (.not. ctx%live) return
+      rc = vecpot_skeleton(ctx, B, nnulls, pos, jac, nring, ring, radius, capture, step, max_steps, every, max_points, &
+                           kind, eig, spine, normal, ends, length, status, nsteps, hit, offsets, tot, points, bpt, &
+                           on_device)
+      if (rc /= 0) then
+        call report(who, rc)
+        if (rc < NDSMK_ENODEV) rc = NDSMK_ENODEV
+      end if
+    end function
+
+    ! total, and (host entry) the nnulls entries of the per-null outputs, the nl entries of the per-line outputs, the
+    ! nl + 1 of offsets and the max_points slots of every point array that is there
+    subroutine clear_outputs()
+      real(c_double), pointer :: r(:)
+      integer(c_int32_t), pointer :: k(:)
+      integer(c_int64_t), pointer :: k8(:)
+      integer(c_int64_t) :: nl8
+      integer :: nl
+      if (c_associated(total)) then
+        call c_f_pointer(total, k8, [1]); k8 = 0
+      end if
+      if (on_device) return
+      nl8 = 0
+      if (nnulls > 0 .and. nring >= 0) nl8 = int(nnulls, c_int64_t) * (2_c_int64_t + int(nring, c_int64_t))
+      if (nl8 > 0 .and. nl8 <= huge(0) / 3) then
+        nl = int(nl8)
+        if (c_associated(kind)) then
+          call c_f_pointer(kind, k, [nnulls]); k = 0
+        end if
+        if (c_associated(eig)) then
+          call c_f_pointer(eig, r, [3 * nnulls]); r = 0
+        end if
+        if (c_associated(spine)) then
+          call c_f_pointer(spine, r, [3 * nnulls]); r = 0
+        end if
+        if (c_associated(normal)) then
+          call c_f_pointer(normal, r, [3 * nnulls]); r = 0
+        end if
+        if (c_associated(ends)) then
+          call c_f_pointer(ends, r, [3 * nl]); r = 0
+        end if
+        if (c_associated(length)) then
+          call c_f_pointer(length, r, [nl]); r = 0
+        end if
+        if (c_associated(status)) then
+          call c_f_pointer(status, k, [nl]); k = 0
+        end if
+        if (c_associated(nsteps)) then
+          call c_f_pointer(nsteps, k, [nl]); k = 0
+        end if
+        if (c_associated(hit)) then
+          call c_f_pointer(hit, k, [nl]); k = 0
+        end if
+        if (c_associated(offsets)) then
+          call c_f_pointer(offsets, k8, [nl + 1]); k8 = 0
+        end if
+      end if
+      if (max_points <= 0 .or. max_points > huge(0_c_int64_t) / 3) return
+      if (c_associated(points)) then
+        call c_f_pointer(points, r, [3 * max_points]); r = 0
+      end if
+      if (c_associated(bpt)) then
+        call c_f_pointer(bpt, r, [3 * max_points]); r = 0
+      end if
+    end subroutine
+  end function
+
   ! ---- null points on the same handle --------------------------------------
   ! B (nx,ny,nz,3) in; max_nulls >= 0 the capacity of the record arrays; counts (2, int64, on the HOST in both
   ! entries): the screen's candidates, the nulls found.  Out, the first min(counts(2), max_nulls) records in ascending

@@ -620,6 +620,32 @@ module ndsmh_iface
       integer(c_int) :: rc
     end function
 
+    ! ---- spine-fan skeleton of the nulls (skeleton.hip): typing and counting (blocks for total), then filling ----
+    function ndsmk_skel_count(B, n3, lo3, dq3, nnulls, pos, jac, nring, ring, radius, capture, step, max_steps, every, &
+                              max_points, kind, eig, spine, normal, ends, length, status, nsteps, hit, offsets, total) &
+        bind(c, name="ndsmk_skel_count") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_int64_t, c_double
+      type(c_ptr), value :: B, pos, jac, ring, kind, eig, spine, normal, ends, length, status, nsteps, hit, offsets
+      integer(c_int32_t), intent(in) :: n3(3)
+      real(c_double), intent(in) :: lo3(3), dq3(3)
+      integer(c_int), value :: nnulls, nring, max_steps, every
+      real(c_double), value :: radius, capture, step
+      integer(c_int64_t), value :: max_points
+      integer(c_int64_t), intent(out) :: total
+      integer(c_int) :: rc
+    end function
+    function ndsmk_skel_fill(B, n3, lo3, dq3, nnulls, pos, nring, radius, capture, step, max_steps, every, max_points, &
+                             offsets, points, bpt) bind(c, name="ndsmk_skel_fill") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_int64_t, c_double
+      type(c_ptr), value :: B, pos, offsets, points, bpt
+      integer(c_int32_t), intent(in) :: n3(3)
+      real(c_double), intent(in) :: lo3(3), dq3(3)
+      integer(c_int), value :: nnulls, nring, max_steps, every
+      real(c_double), value :: radius, capture, step
+      integer(c_int64_t), value :: max_points
+      integer(c_int) :: rc
+    end function
+
     ! ---- the face phase on the device (faces.hip) ----
     function ndsmk_face_offsets(n3, off6, total) bind(c, name="ndsmk_face_offsets") result(rc)
       import :: c_int, c_int32_t, c_int64_t

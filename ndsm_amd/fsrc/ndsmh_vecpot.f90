@@ -32,7 +32,7 @@ module ndsmh_vecpot
 
   public :: vecpot_solve, poisson_solve
   public :: vecpot_ctx, vecpot_ctx_create, vecpot_ctx_destroy, vecpot_ctx_matches, vecpot_run, vecpot_cache_drop
-  public :: vecpot_project, vecpot_devore, vecpot_lines, vecpot_paths, vecpot_nulls
+  public :: vecpot_project, vecpot_devore, vecpot_lines, vecpot_paths, vecpot_nulls, vecpot_skeleton
   public :: VP_POTENTIAL, VP_FIELD, VP_HELICITY
   ! pieces the distributed driver (ndsmh_wvecpot) shares with vecpot_solve
   public :: face_data, face_axis, face_upper, face_t1, face_t2, face_order, face_copy, vecpot_faces, say
@@ -1281,6 +1281,131 @@ contains
         m(q) = c_associated(p(q))
       end do
     end function
+  end function
+
+  ! ------------------------------------------------------------------
+  ! The skeleton entries on a prepared context (semantics in include/ndsm_hip.h, DESIGN.md "Spine-fan skeleton"): the
+  ! type of each null from its Jacobian, then its two spine lines and nring fan lines, traced away from it and ended
+  ! where they come within `capture` of another null.  The context supplies the mesh only, as in vecpot_lines: no
+  ! solve, no hierarchy.  pB (nx,ny,nz,3), ppos (3,nnulls), pjac (9 each), pring (2,nring) in; per null pkind, peig,
+  ! pspine, pnormal out; per line (nl = nnulls (2 + nring)) pends, plen, pstat, pnst, phit out; poff (nl + 1, int64),
+  ! total, ppts (3,max_points), pbpt (the same; c_null_ptr: skipped) as vecpot_paths - on the HOST (B goes up into the
+  ! staging array dF(1), the nulls, the ring and the outputs into a scratch buffer; after the counting half a second
+  ! buffer of min(total, max_points) points is allocated, filled, and only what was written comes home) or (on_device)
+  ! in HBM.  total is a host scalar either way.
+  ! ------------------------------------------------------------------
+  function vecpot_skeleton(ctx, pB, nnulls, ppos, pjac, nring, pring, radius, capture, step, max_steps, every, &
+                           max_points, pkind, peig, pspine, pnormal, pends, plen, pstat, pnst, phit, poff, total, &
+                           ppts, pbpt, on_device) result(rc)
+    type(vecpot_ctx), intent(inout), target :: ctx
+    logical, intent(in) :: on_device
+    type(c_ptr), intent(in) :: pB, ppos, pjac, pring, pkind, peig, pspine, pnormal, pends, plen, pstat, pnst, phit, poff, &
+                               ppts, pbpt
+    integer(c_int), intent(in) :: nnulls, nring, max_steps, every
+    integer(c_int64_t), intent(in) :: max_points
+    real(wp), intent(in) :: radius, capture, step
+    integer(c_int64_t), intent(out) :: total
+    integer(c_int) :: rc, rc_free
+    real(wp) :: dq(3), lo(3)
+    integer(c_int32_t) :: n3(3)
+    integer(c_size_t) :: nb, nl, nm, nr, np, no
+    integer :: i
+    type(c_ptr) :: buf, pbuf, din(3), d(10), dp(2), hp(2), ho(10)
+    ! bytes per null of pos, jac and per seed of ring; per null of kind, eig, spine, normal (the 8-byte arrays first);
+    ! per line of ends, length, status, nsteps, hit; per point of points, bpt
+    integer(c_size_t), parameter :: nwidth(4) = [24, 24, 24, 4], lwidth(5) = [24, 8, 4, 4, 4], pwidth(2) = [24, 24]
+
+    total = 0
+    n3 = ctx%n3
+    dq = [ctx%qx(2) - ctx%qx(1), ctx%qy(2) - ctx%qy(1), ctx%qz(2) - ctx%qz(1)]      ! as vecpot_run
+    lo = [ctx%qx(1), ctx%qy(1), ctx%qz(1)]
+    if (on_device .or. nnulls <= 0 .or. nring < 0 .or. step <= 0.0_wp .or. max_steps < 1 .or. every < 1 .or. &
+        max_points < 0 .or. .not. (radius > 0.0_wp) .or. .not. (capture >= 0.0_wp) .or. radius > 1.0e300_wp .or. &
+        capture > 1.0e300_wp .or. .not. (step <= 1.0e300_wp) .or. &
+        int(nnulls, c_int64_t) * (2_c_int64_t + int(nring, c_int64_t)) > 2147483647_c_int64_t) then
+      ! (the argument errors, more lines than a call takes among them, are the kernel entries' to name; nothing is
+      ! staged for them)
+      rc = ndsmk_skel_count(pB, n3, lo, dq, nnulls, ppos, pjac, nring, pring, radius, capture, step, max_steps, every, &
+                            max_points, pkind, peig, pspine, pnormal, pends, plen, pstat, pnst, phit, poff, total)
+      if (rc == 0) rc = ndsmk_skel_fill(pB, n3, lo, dq, nnulls, ppos, nring, radius, capture, step, max_steps, every, &
+                                        max_points, poff, ppts, pbpt)
+      if (rc == 0) rc = ndsmk_sync()
+      if (rc /= 0) total = 0
+      return
+    end if
+    nb = int(product(int(n3, ik)), c_size_t) * 24_c_size_t
+    nm = int(nnulls, c_size_t)
+    nr = int(nring, c_size_t)
+    nl = nm * (2_c_size_t + nr)
+    if (.not. c_associated(ctx%dF(1))) then
+      rc = ndsmk_alloc(ctx%dF(1), nb); if (rc /= 0) return
+    end if
+    rc = ndsmk_h2d(ctx%dF(1), pB, nb); if (rc /= 0) return
+    ! one scratch buffer: offsets, pos, jac, ring (8-byte data first), the per-null outputs, then the per-line outputs
+    buf = c_null_ptr
+    pbuf = c_null_ptr
+    rc = ndsmk_alloc(buf, 8_c_size_t * (nl + 1) + 96_c_size_t * nm + 16_c_size_t * max(nr, 1_c_size_t) + &
+                     sum(nwidth) * nm + sum(lwidth) * nl)
+    if (rc /= 0) return
+    no = 8_c_size_t * (nl + 1)
+    din(1) = dptr_offset(buf, no); no = no + 24_c_size_t * nm               ! pos
+    din(2) = dptr_offset(buf, no); no = no + 72_c_size_t * nm               ! jac
+    din(3) = dptr_offset(buf, no); no = no + 16_c_size_t * max(nr, 1_c_size_t)   ! ring
+    ! eig, spine, normal, kind | ends, length, status, nsteps, hit | offsets
+    do i = 1, 3
+      d(i) = dptr_offset(buf, no); no = no + nwidth(i) * nm
+    end do
+    do i = 1, 2
+      d(4 + i) = dptr_offset(buf, no); no = no + lwidth(i) * nl
+    end do
+    d(4) = dptr_offset(buf, no); no = no + nwidth(4) * nm
+    do i = 3, 5
+      d(4 + i) = dptr_offset(buf, no); no = no + lwidth(i) * nl
+    end do
+    d(10) = buf
+    rc = ndsmk_h2d(din(1), ppos, 24_c_size_t * nm)
+    if (rc == 0) rc = ndsmk_h2d(din(2), pjac, 72_c_size_t * nm)
+    if (rc == 0 .and. nr > 0) rc = ndsmk_h2d(din(3), pring, 16_c_size_t * nr)
+    if (rc == 0) then
+      call say("find_skeleton", "Typing the nulls, tracing their spines and fans and counting the points...")
+      rc = ndsmk_skel_count(ctx%dF(1), n3, lo, dq, nnulls, din(1), din(2), nring, din(3), radius, capture, step, &
+                            max_steps, every, max_points, d(4), d(1), d(2), d(3), d(5), d(6), d(7), d(8), d(9), d(10), &
+                            total)
+    end if
+    ! the point arrays: min(total, max_points) slots each, carved from a second buffer
+    np = 0
+    if (rc == 0) np = int(min(total, max_points), c_size_t)
+    dp = c_null_ptr
+    hp = [ppts, pbpt]
+    if (rc == 0 .and. np > 0) then
+      rc = ndsmk_alloc(pbuf, merge(48_c_size_t, 24_c_size_t, c_associated(pbpt)) * np)
+      if (rc == 0) then
+        dp(1) = pbuf
+        if (c_associated(pbpt)) dp(2) = dptr_offset(pbuf, 24_c_size_t * np)
+        call say("find_skeleton", "Tracing again and storing the points...")
+        rc = ndsmk_skel_fill(ctx%dF(1), n3, lo, dq, nnulls, din(1), nring, radius, capture, step, max_steps, every, &
+                             int(np, c_int64_t), d(10), dp(1), dp(2))
+      end if
+    end if
+    ho = [peig, pspine, pnormal, pkind, pends, plen, pstat, pnst, phit, poff]
+    do i = 1, 4
+      if (rc == 0) rc = ndsmk_d2h(ho(i), d(i), nwidth(i) * nm)
+    end do
+    do i = 1, 5
+      if (rc == 0) rc = ndsmk_d2h(ho(4 + i), d(4 + i), lwidth(i) * nl)
+    end do
+    if (rc == 0) rc = ndsmk_d2h(poff, d(10), 8_c_size_t * (nl + 1))
+    do i = 1, 2
+      if (rc == 0 .and. np > 0 .and. c_associated(hp(i))) rc = ndsmk_d2h(hp(i), dp(i), pwidth(i) * np)
+    end do
+    if (rc == 0) rc = ndsmk_sync()
+    if (c_associated(pbuf)) then
+      rc_free = ndsmk_free(pbuf)
+      if (rc == 0) rc = rc_free
+    end if
+    rc_free = ndsmk_free(buf)
+    if (rc == 0) rc = rc_free
+    if (rc /= 0) total = 0
   end function
 
   ! ------------------------------------------------------------------

@@ -600,6 +600,95 @@ int ndsm_hip_vecpot_skeleton_device(void *h, const double *dB, int nnulls, const
                                     int32_t *dnsteps, int32_t *dhit, int64_t *doffsets, int64_t *total,
                                     double *dpoints, double *dbpt);
 
+/* ---- Separator lines: fan brackets between null pairs, refined on the device (DESIGN.md "Separator lines") -------------
+ * The separator of two nulls of opposite sign is the field line in which their fans intersect: it leaves null m in its
+ * fan and ends at null m'.  A fan line of m diverges from it like e^(lambda t), so a ring of fan seeds does not hit it;
+ * but the fan lines on its two sides pass m' on the two sides of the fan of m' and leave along opposite spines.  A
+ * BRACKET is an arc of the fan ring of m, given by two ring coefficient pairs a = (c_a, s_a) and b = (c_b, s_b), and the
+ * null m'.  Each bracket is refined by one wave of 64 lanes: 64 directions inside the arc are traced at once, the lowest
+ * lane whose line passes m' on another side than lane 0's narrows the arc to 1/63, and this is repeated until the arc is
+ * narrower than tol.  The handle supplies the mesh only; no solve runs.  Everything not said here is as in the skeleton
+ * and paths entries above; fp64 + - * / and sqrt only, in the operand order written here, no contraction: a
+ * restatement in the same order gives the same bits (tests/separator_model.py).
+ *   B          (nx,ny,nz,3)
+ *   pos, kind, normal   nnulls entries: the pos given to, and the kind and normal written by, the skeleton entries.  The
+ *              device arrays of ndsm_hip_vecpot_skeleton_device can be passed straight in.
+ *   pair       (2,nbr) int32: the nulls (m, m') of each bracket, each in 0 .. nnulls - 1.
+ *   arc        (4,nbr): (c_a, s_a, c_b, s_b) of each bracket - ring coefficients as the skeleton's ring; nothing is
+ *              normalised on entry.
+ *   radius     > 0, finite: rho = radius * min(h), as the skeleton's.
+ *   capture    > 0, finite: the capture radius in units of min(h); it is REQUIRED here ((capture min(h))^2 > 0).
+ *   rounds     >= 1: the most rounds a bracket is given.   tol  >= 0, finite: the width at which it has converged.
+ *   every, max_points, offsets, total, points, bpt: exactly as in ndsm_hip_vecpot_paths (there is no G).
+ * Per bracket (m, m'):
+ *   1. Set-up.  w = normal(m); the fan basis e1, e2 from w by item 6 of the skeleton's stage 1, the same expressions
+ *      and so the same bits.  rho as above.  The direction of every line is sg = +1 for kind(m) > 0, -1 for kind(m) < 0
+ *      (the skeleton's fan lanes).  Unless m != m' and kind(m), kind(m') have strictly opposite signs the state is
+ *      NDSM_HIP_SEP_NONE: nothing is traced.
+ *   2. A round.  Lane i = 0 .. 63 has t = i / 63, c = (1 - t) c_a + t c_b, s = (1 - t) s_a + t s_b, n = sqrt(c c + s s),
+ *      and the direction d_i = (c / n, s / n); a lane whose n is not > 0 traces nothing and has class 0.  Lanes 0 and 63
+ *      take a and b unchanged (no division, no test of n).  The seed is pos(m)_d + rho (c e1_d + s e2_d) with the
+ *      lane's (c, s).
+ *   3. The line of a lane is the skeleton's fan line of that seed and direction with the capture test against m' ALONE.
+ *      The closest-approach test runs at the points where the capture test runs - after every accepted FULL step, not at
+ *      the seed, not after the exit step -: dx = r_0 - pos(m')_0, dy, dz likewise, d2 = (dx dx + dy dy) + dz dz.  Where
+ *      d2 < the smallest d2 of the line so far (strictly; +infinity at first), g = (w'_0 dx + w'_1 dy) + w'_2 dz is
+ *      kept, with w' = normal(m'): g belongs to the first point of the smallest d2.  Then d2 <= (capture min(h))^2 ends
+ *      the line CAPTURED.
+ *   4. The class of a lane: +1 for g >= 0, -1 for g < 0, 0 when the line has no such point (a seed outside the box, an
+ *      exit or a null of the interpolant in the first step) or g is NaN.  In the linear regime near m', w' . (r - pos')
+ *      keeps its sign along a line, so the class says along which spine of m' the line leaves.
+ *   5. Narrowing.  i* is the lowest lane >= 1 whose class differs from lane 0's.  Lane 0 of class 0: state
+ *      NDSM_HIP_SEP_GAP.  Else no such lane: NDSM_HIP_SEP_NO_CROSSING.  Else lane i* of class 0: NDSM_HIP_SEP_GAP.
+ *      Otherwise a <- d_(i* - 1), b <- d_(i*) (lanes 0 and 63: a and b as they were) and width = sqrt((c_a - c_b)
+ *      (c_a - c_b) + (s_a - s_b) (s_a - s_b)); width <= tol: converged; else another round, and when `rounds` are used
+ *      up the state is NDSM_HIP_SEP_UNRESOLVED.
+ *   6. A converged bracket is NDSM_HIP_SEP_FOUND when the lines of lanes i* - 1 and i* of its last round were both
+ *      CAPTURED by m', else NDSM_HIP_SEP_FAR: a change of side that never comes near m' - every ring has one on the side
+ *      that faces away from m'.
+ * Out, per bracket: state; nrounds, the rounds run (0 for NONE); coef, the final (c_a, s_a, c_b, s_b) (the input arc for
+ * NONE, NO_CROSSING and GAP); width, the expression of 5 on coef (0 for NONE); side, the class of lane 0 in the last
+ * round (0 for NONE); dmin, the sqrt of the smallest d2 of the lines of lanes i* - 1 and i* of the last round (lanes 0
+ * and 63 where there is no i*; +infinity for a line without a point; 0, 0 for NONE).
+ * The separator polyline of a bracket is the fan line of its a side: for FOUND, FAR and UNRESOLVED the line of 3 from
+ * the seed pos(m)_d + rho (c_a e1_d + s_a e2_d) of the final a, stored as the skeleton stores a line - ends, length,
+ * status (1 - 9, NDSM_HIP_SKEL_CAPTURED), nsteps, npts, offsets, *total, points, bpt.  NONE, NO_CROSSING and GAP give
+ * one point with pos(m)'s bits, status NDSM_HIP_SKEL_NONE, length 0, nsteps 0, bpt 0.
+ * Property: for FOUND, FAR and UNRESOLVED the line equals, bit for bit, fan line 0 (lane 2) of null 0 of
+ * ndsm_hip_vecpot_skeleton called with the two nulls (m, m'), the ring (c_a, s_a) taken from coef, and the same radius,
+ * capture, step, max_steps and every.  The bits do not depend on the number of brackets or their order.
+ * Returns 0, or >= 9001 errors: 9001 without a GPU whatever the arguments; 9002 a NULL handle or total, or with nbr > 0
+ * a NULL B, pos, kind, normal, pair, arc, state, nrounds, coef, width, side, dmin, ends, length, status, nsteps or
+ * offsets, with max_points > 0 a NULL points; 9004 nnulls < 0, nbr < 0, rounds < 1, a tol that is < 0 or not finite, a
+ * capture or a radius that is not > 0 or not finite, every < 1, max_points < 0, step not > 0 or not finite, max_steps
+ * < 1, or a pair index outside 0 .. nnulls - 1 (all pairs are checked before anything is written).  nbr == 0 succeeds,
+ * sets *total = 0 and touches nothing else.  On failure *total = 0, and the host entry also clears the nbr entries of
+ * the per-bracket outputs, the nbr + 1 entries of offsets and exactly max_points slots of each non-NULL point array; the
+ * device entry leaves its device arrays.  On success nothing past the written slots is touched by either entry.
+ * Device memory: the host entry stages B in the handle's scratch (24 B/pt) and the points it brings home; both entries
+ * keep 32 B per bracket between the two passes. */
+#define NDSM_HIP_SEP_NONE 0          /* m = m', or kind(m) kind(m') is not < 0: nothing was traced */
+#define NDSM_HIP_SEP_FOUND 1         /* converged, both bracketing lines captured by m': the separator */
+#define NDSM_HIP_SEP_FAR 2           /* converged on a change of side that does not come near m' */
+#define NDSM_HIP_SEP_NO_CROSSING 3   /* every lane passes m' on lane 0's side */
+#define NDSM_HIP_SEP_GAP 4           /* lane 0, or the first lane that differs from it, has no side */
+#define NDSM_HIP_SEP_UNRESOLVED 5    /* still wider than tol after `rounds` rounds */
+/* HOST arrays */
+int ndsm_hip_vecpot_separators(void *h, const double *B, int nnulls, const double *pos, const int32_t *kind,
+                               const double *normal, int nbr, const int32_t *pair, const double *arc, double radius,
+                               double capture, double step, int max_steps, int rounds, double tol, int every,
+                               int64_t max_points, int32_t *state, int32_t *nrounds, double *coef, double *width,
+                               int32_t *side, double *dmin, double *ends, double *length, int32_t *status,
+                               int32_t *nsteps, int64_t *offsets, int64_t *total, double *points, double *bpt);
+/* the same on DEVICE arrays of the library's GPU (every array; total stays on the host) */
+int ndsm_hip_vecpot_separators_device(void *h, const double *dB, int nnulls, const double *dpos, const int32_t *dkind,
+                                      const double *dnormal, int nbr, const int32_t *dpair, const double *darc,
+                                      double radius, double capture, double step, int max_steps, int rounds, double tol,
+                                      int every, int64_t max_points, int32_t *dstate, int32_t *dnrounds, double *dcoef,
+                                      double *dwidth, int32_t *dside, double *ddmin, double *dends, double *dlength,
+                                      int32_t *dstatus, int32_t *dnsteps, int64_t *doffsets, int64_t *total,
+                                      double *dpoints, double *dbpt);
+
 /* =====================================================================
  * PART 3 - additive exports, multi-GPU
  *

@@ -111,6 +111,11 @@ def load_library(path=None):
            [ctypes.c_double] * 3 + [ctypes.c_int, ctypes.c_int, ctypes.c_int64] + [ctypes.c_void_p] * 13)
     L.ndsm_hip_vecpot_skeleton.argtypes = _sk
     L.ndsm_hip_vecpot_skeleton_device.argtypes = _sk
+    _se = ([ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_int] + [ctypes.c_void_p] * 2 +
+           [ctypes.c_double] * 3 + [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int64] +
+           [ctypes.c_void_p] * 14)
+    L.ndsm_hip_vecpot_separators.argtypes = _se
+    L.ndsm_hip_vecpot_separators_device.argtypes = _se
     L.ndsm_hip_device_alloc.argtypes = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
     L.ndsm_hip_device_free.argtypes = [ctypes.c_void_p]
     L.ndsm_hip_memcpy_h2d.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
@@ -748,6 +753,93 @@ class VecPot:
         k = min(int(total[0]), cap)
         return _skeleton_tuple(pos, nr, pernull, lines, offsets, pts[0][:k], None if pts[1] is None else pts[1][:k])
 
+    def separators(self, b, skeleton=None, pairs=None, brackets=None, radius=0.5, capture=None, step=0.5,
+                   max_steps=None, rounds=10, tol=1e-12, every=1, ring=None, values=True, device=False):
+        """The separator lines between nulls of opposite sign of b (3,nz,ny,nx), on the device (semantics:
+        include/ndsm_hip.h, ndsm_hip_vecpot_separators): a bracket - an arc (c_a, s_a, c_b, s_b) of the fan ring of
+        null m and a null m' - is refined by one wave, 64 directions a round, until the arc round the change of the
+        side on which its fan lines pass m' is narrower than tol; the fan line of its a side is the separator.
+        skeleton: a Skeleton of b (None: self.skeleton(b, radius, capture, step, max_steps)); its position, kind and
+        normal are used.  brackets: a (pair (nbr,2), arc (nbr,4)) pair; None: for every ordered pair of typed nulls
+        with opposite signs of kind (or the caller's `pairs`, a list of (m, m')) the nring cyclically adjacent arcs
+        of the skeleton's ring (`ring`: its (nring,2) coefficients when it was not the default one) - most of them
+        end in round 1 as SEP_NO_CROSSING; more than 65536 brackets ask for `pairs`.  radius, capture (None: radius;
+        it must be > 0 here), step, max_steps, every as skeleton().  Returns a Separators tuple: pair (nbr,2), state
+        (nbr; SEP_NONE, SEP_FOUND, SEP_FAR, SEP_NO_CROSSING, SEP_GAP, SEP_UNRESOLVED), coef (nbr,4: the final arc),
+        width, side (nbr), dmin (nbr,2), paths (a FieldPaths of the nbr lines, one per bracket; one point where the
+        state has no line).  separator_of reads the result.  device=True: the arrays are staged in device memory and
+        the device-resident entry point runs."""
+        radius, capture, rounds, tol = _separator_args(radius, capture, rounds, tol)
+        _d0, step, max_steps = self._trace_args(step, max_steps, "forward")
+        every, _mp = _paths_args(every, None)
+        R = None if ring is None else _skeleton_ring(0, ring)
+        if pairs is not None:
+            pairs = np.asarray(pairs)
+            if pairs.ndim != 2 or pairs.shape[1] != 2 or pairs.dtype.kind not in "iu":
+                raise ValueError(f"pairs must be (npairs, 2) integers, not {pairs.dtype} {pairs.shape}")
+        if brackets is not None:
+            pair, arc = brackets
+            pair, arc = np.asarray(pair), np.ascontiguousarray(np.asarray(arc, dtype=np.float64)).copy()
+            if (pair.ndim != 2 or pair.shape[1] != 2 or pair.dtype.kind not in "iu" or arc.shape != (len(pair), 4) or
+                    pairs is not None):
+                raise ValueError("brackets must be a (pair (nbr, 2) integers, arc (nbr, 4)) pair, given without pairs")
+        B = self._field_arg(b, "separators")
+        if skeleton is None:
+            skeleton = self.skeleton(B.reshape(tuple(int(v) for v in self.nshape4[::-1])), radius=radius, capture=capture,
+                                     step=step, max_steps=max_steps, ring=R, values=False, device=device)
+        pos = np.ascontiguousarray(np.asarray(skeleton.position, dtype=np.float64)).copy()
+        kind = np.ascontiguousarray(np.asarray(skeleton.kind, dtype=np.int32)).copy()
+        normal = np.ascontiguousarray(np.asarray(skeleton.normal, dtype=np.float64)).copy()
+        n = len(pos)
+        if pos.shape != (n, 3) or kind.shape != (n,) or normal.shape != (n, 3):
+            raise NdsmHipError(f"separators: a skeleton of shapes {pos.shape}, {kind.shape}, {normal.shape} "
+                               "(code 9002)")
+        if brackets is None:
+            if R is None:
+                R = _skeleton_ring(int(np.asarray(skeleton.hit).shape[1]) - 2, None)
+            pair, arc = _separator_brackets(kind, R, pairs)
+        if len(pair) and (pair.min() < 0 or pair.max() >= n):
+            raise ValueError(f"a pair index outside 0 .. {n - 1}")
+        pair = np.ascontiguousarray(pair.astype(np.int32))
+        nbr = len(pair)
+        withb = bool(values)
+        per = [np.zeros(nbr, dtype=np.int32), np.zeros(nbr, dtype=np.int32), np.zeros((nbr, 4)), np.zeros(nbr),
+               np.zeros(nbr, dtype=np.int32), np.zeros((nbr, 2)), np.zeros((nbr, 3)), np.zeros(nbr),
+               np.zeros(nbr, dtype=np.int32), np.zeros(nbr, dtype=np.int32)]
+        if nbr == 0:
+            return _separators_tuple(pair, per, np.zeros(1, dtype=np.int64), np.zeros((0, 3)),
+                                     np.zeros((0, 3)) if withb else None)
+        name = "ndsm_hip_vecpot_separators_device" if device else "ndsm_hip_vecpot_separators"
+        # room for a few hundred points per line at first; the call is repeated once when the lines are longer
+        cap = int(min(nbr * min(-(-max_steps // every) + 2, 512), 2 ** 22))
+        for _attempt in range(2):
+            offsets = np.zeros(nbr + 1, dtype=np.int64)
+            total = np.zeros(1, dtype=np.int64)
+            pts = [np.zeros((cap, 3)), np.zeros((cap, 3)) if withb else None]
+            head = (radius, capture, step, max_steps, rounds, tol, every, cap)
+            outs = per + [offsets]
+            if not device:
+                ierr = self.L.ndsm_hip_vecpot_separators(
+                    self.h, B.ctypes.data, n, pos.ctypes.data, kind.ctypes.data, normal.ctypes.data, nbr,
+                    pair.ctypes.data, arc.ctypes.data, *head, *[a.ctypes.data for a in outs], total.ctypes.data,
+                    *[None if a is None else a.ctypes.data for a in pts])
+            else:
+                staged = [B, pos, kind, normal, pair, arc] + outs + [a for a in pts if a is not None]
+
+                def call(dB, dpos, dkind, dnormal, dpair, darc, *ptrs):
+                    ptrs = list(ptrs)
+                    douts = [ptrs.pop(0) for _ in outs]
+                    dpts = [None if a is None else ptrs.pop(0) for a in pts]
+                    return self.L.ndsm_hip_vecpot_separators_device(self.h, dB, n, dpos, dkind, dnormal, nbr, dpair, darc,
+                                                                    *head, *douts, total.ctypes.data, *dpts)
+                ierr = self._on_device(staged, call)
+            _check(ierr, name, self.L)
+            if int(total[0]) <= cap:
+                break
+            cap = int(total[0])
+        k = min(int(total[0]), cap)
+        return _separators_tuple(pair, per, offsets, pts[0][:k], None if pts[1] is None else pts[1][:k])
+
     def seed_plane(self, axis, value, n1, n2):
         """the (n1 n2, 3) seeds of a mesh-aligned cut through the handle's box: coordinate `axis` (0, 1, 2 = x, y, z)
         fixed at `value`, the other two (in the order x, y, z; the first of them fastest) n1 and n2 equally spaced
@@ -1046,6 +1138,66 @@ def connections(sk):
     return out
 
 
+Separators = collections.namedtuple("Separators", ["pair", "state", "coef", "width", "side", "dmin", "paths"])
+# states of a bracket (NDSM_HIP_SEP_*)
+SEP_NONE, SEP_FOUND, SEP_FAR, SEP_NO_CROSSING, SEP_GAP, SEP_UNRESOLVED = range(6)
+SEP_MAX_BRACKETS = 65536           # default brackets of one separators() call
+
+
+def _separator_args(radius, capture, rounds, tol):
+    """(radius, capture, rounds, tol) of separators(); ValueError before anything is launched"""
+    def number(v):
+        return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and np.isfinite(v)
+    if not number(radius) or not radius > 0.0:
+        raise ValueError(f"radius must be a positive finite number, not {radius!r}")
+    if capture is None:
+        capture = radius
+    if not number(capture) or not capture > 0.0:
+        raise ValueError(f"capture must be None or a positive finite number, not {capture!r}")
+    if not number(rounds) or int(rounds) != rounds or not 1 <= rounds <= 2 ** 31 - 1:
+        raise ValueError(f"rounds must be an integer >= 1, not {rounds!r}")
+    if not number(tol) or tol < 0.0:
+        raise ValueError(f"tol must be a finite number >= 0, not {tol!r}")
+    return float(radius), float(capture), int(rounds), float(tol)
+
+
+def _separator_brackets(kind, ring, pairs=None):
+    """the default brackets: for every ordered pair (m, m') of typed nulls with opposite signs of kind (or `pairs`) the
+    nring arcs (ring_j, ring_(j+1) cyclically), pair by pair, j ascending: pair (nbr,2) int32, arc (nbr,4)"""
+    kind = np.asarray(kind)
+    nr = len(ring)
+    if pairs is None:
+        plus, minus = np.nonzero(kind > 0)[0], np.nonzero(kind < 0)[0]
+        if 2 * len(plus) * len(minus) * nr > SEP_MAX_BRACKETS:
+            raise ValueError(f"{2 * len(plus) * len(minus)} pairs of nulls with {nr} arcs each are more than "
+                             f"{SEP_MAX_BRACKETS} brackets: name the pairs to refine with pairs=")
+        pairs = sorted([(int(m), int(o)) for m in plus for o in minus] + [(int(o), int(m)) for m in plus for o in minus])
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    if len(pairs) * nr > SEP_MAX_BRACKETS:
+        raise ValueError(f"{len(pairs)} pairs with {nr} arcs each are more than {SEP_MAX_BRACKETS} brackets: name fewer "
+                         "pairs")
+    arcs = np.concatenate([ring, np.roll(ring, -1, axis=0)], axis=1).reshape(nr, 4)
+    pair = np.repeat(pairs, nr, axis=0).astype(np.int32).reshape(-1, 2)
+    return np.ascontiguousarray(pair), np.ascontiguousarray(np.tile(arcs, (len(pairs), 1))).reshape(-1, 4)
+
+
+def _separators_tuple(pair, per, offsets, points, b):
+    """a Separators from [state, nrounds, coef, width, side, dmin, ends, length, status, nsteps] and the points"""
+    state, _nrounds, coef, width, side, dmin, ends, length, status, nsteps = per
+    fl = FieldLines(ends, length, None, status, nsteps, None)
+    return Separators(pair, state, coef, width, side, dmin, FieldPaths(fl, offsets, points, b, None, None))
+
+
+def separator_of(result, m, m2):
+    """the separators from null m to null m2 of a Separators: [(points, b), ...], one per SEP_FOUND bracket of that
+    pair, each running from m to within the capture radius of m2 (b None with values=False)"""
+    for v in (m, m2):
+        if int(v) != v or v < 0:
+            raise IndexError(f"null {v!r}")
+    rows = np.nonzero((result.pair[:, 0] == m) & (result.pair[:, 1] == m2) & (result.state == SEP_FOUND))[0]
+    return [path_of(result.paths, int(l))[:2] for l in rows]
+
+
 QMap = collections.namedtuple("QMap", ["q", "twist", "ends", "length", "integral", "status", "nsteps"])
 
 
@@ -1186,6 +1338,20 @@ def find_skeleton(x, y, z, b, nulls=None, radius=0.5, nring=16, ring=None, captu
     try:
         return V.skeleton(b, nulls=nulls, radius=radius, nring=nring, ring=ring, capture=capture, step=step,
                           max_steps=max_steps, every=every, max_points=max_points, values=values)
+    finally:
+        V.close()
+
+
+def find_separators(x, y, z, b, skeleton=None, pairs=None, brackets=None, radius=0.5, capture=None, step=0.5,
+                    max_steps=None, rounds=10, tol=1e-12, every=1, ring=None, values=True, lib=None):
+    """The separator lines between the nulls of b (3,nz,ny,nx): one-shot form of VecPot.separators (returns its
+    Separators tuple).  Raises NdsmHipError on device / runtime failures (>= 9001)."""
+    _separator_args(radius, capture, rounds, tol)
+    _paths_args(every, None)
+    V = _grid_handle(x, y, z, b, 0, lib)
+    try:
+        return V.separators(b, skeleton=skeleton, pairs=pairs, brackets=brackets, radius=radius, capture=capture,
+                            step=step, max_steps=max_steps, rounds=rounds, tol=tol, every=every, ring=ring, values=values)
     finally:
         V.close()
 

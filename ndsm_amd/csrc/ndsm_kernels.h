@@ -272,6 +272,31 @@ int ndsmk_skel_fill(const double *B, const int32_t *n3, const double *lo3, const
                     const double *pos, int nring, double radius, double capture, double step, int max_steps, int every,
                     int64_t max_points, const int64_t *offsets, double *points, double *bpt);
 
+/* Separator lines (separators.hip; semantics: include/ndsm_hip.h, ndsm_hip_vecpot_separators), in two halves as the
+ * skeleton.  B a DEVICE array (nx,ny,nz,3); pos (3,nnulls), kind (nnulls), normal (3,nnulls) the skeleton's arrays of the
+ * nulls, pair (2,nbr; int32) the nulls (m, m') and arc (4,nbr) the ring coefficients (c_a, s_a, c_b, s_b) of every
+ * bracket, all DEVICE arrays; radius and capture in units of min(h).  ndsmk_sep_count: the pair indices are checked on the
+ * device (blocks for the answer), then one wave per bracket refines it in up to `rounds` rounds - state, nrounds, side
+ * (nbr; int32), coef (4,nbr), width (nbr), dmin (2,nbr) -, the seed and direction of each bracket's line go into the file's
+ * own scratch, then the lines: ends (3,nbr), length, status, nsteps (nbr) and offsets (nbr + 1, int64) = the exclusive
+ * sums of the lines' point counts for the stride every, offsets[nbr] = the total, which also comes back in *h_total
+ * (HOST); blocks for it.  ndsmk_sep_fill, after the counting half of the same call: slot k < max_points of the
+ * concatenation into points (3 each) and, where not NULL, bpt; a line writes inside [offsets[l], min(offsets[l + 1],
+ * max_points)) only; max_points == 0 launches nothing; asynchronous.  NDSMK_EVALUE by both halves for step <= 0,
+ * max_steps < 1, nnulls < 0, nbr < 0, rounds < 1, every < 1, max_points < 0, a radius or a capture that is not > 0, a tol
+ * that is < 0 (or not finite), and by the counting half for a pair index outside 0 .. nnulls - 1 (nothing is written);
+ * nbr == 0 launches nothing (*h_total = 0). */
+int ndsmk_sep_count(const double *B, const int32_t *n3, const double *lo3, const double *h_dq3, int nnulls,
+                    const double *pos, const int32_t *kind, const double *normal, int nbr, const int32_t *pair,
+                    const double *arc, double radius, double capture, double step, int max_steps, int rounds,
+                    double tol, int every, int64_t max_points, int32_t *state, int32_t *nrounds, double *coef,
+                    double *width, int32_t *side, double *dmin, double *ends, double *length, int32_t *status,
+                    int32_t *nsteps, int64_t *offsets, int64_t *h_total);
+int ndsmk_sep_fill(const double *B, const int32_t *n3, const double *lo3, const double *h_dq3, int nnulls,
+                   const double *pos, int nbr, const int32_t *pair, double radius, double capture, double step,
+                   int max_steps, int rounds, double tol, int every, int64_t max_points, const int64_t *offsets,
+                   double *points, double *bpt);
+
 /* the face phase on the device (faces.hip): packed face buffers, six faces back to back */
 int ndsmk_face_offsets(const int32_t *n3, int64_t *off6, int64_t *total);
 int ndsmk_face_extract(const double *B, const int32_t *n3, double *faces);

@@ -1300,6 +1300,133 @@ contains
     end subroutine
   end function
 
+  ! ---- separator lines on the same handle ------------------------------------
+  ! B (nx,ny,nz,3), pos (3,nnulls), kind (nnulls; int32), normal (3,nnulls) - the skeleton entries' arrays of the nulls -,
+  ! pair (2,nbr; int32), arc (4,nbr), radius, capture, step, max_steps, rounds, tol, every, max_points in.  Out per
+  ! bracket: state, nrounds (int32), coef (4 each), width, side (int32), dmin (2 each), ends (3 each), length, status,
+  ! nsteps (int32); offsets (nbr + 1, int64), total (one int64, on the HOST in both entries), points (3,max_points), bpt
+  ! (the same; may be NULL).  Return value: 0, or >= 9001 errors (9002 a NULL handle or total, with nbr > 0 a NULL
+  ! required array, with max_points > 0 a NULL points; 9004 a scalar out of range or a pair index outside 0 .. nnulls - 1).
+  ! On every failure total is cleared, and the host entry clears the nbr entries of its outputs, the nbr + 1 of offsets
+  ! and the max_points slots of its point arrays.
+
+  ! HOST arrays
+  function ndsm_hip_vecpot_separators(handle, B, nnulls, pos, kind, normal, nbr, pair, arc, radius, capture, step, &
+                                      max_steps, rounds, tol, every, max_points, state, nrounds, coef, width, side, &
+                                      dmin, ends, length, status, nsteps, offsets, total, points, bpt) &
+      bind(c, name="ndsm_hip_vecpot_separators") result(ierr)
+    type(c_ptr), value :: handle, B, pos, kind, normal, pair, arc, state, nrounds, coef, width, side, dmin, ends, length, &
+                          status, nsteps, offsets, total, points, bpt
+    integer(c_int), value :: nnulls, nbr, max_steps, rounds, every
+    integer(c_int64_t), value :: max_points
+    real(c_double), value :: radius, capture, step, tol
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_separators(handle, B, nnulls, pos, kind, normal, nbr, pair, arc, radius, capture, step, &
+                                    max_steps, rounds, tol, every, max_points, state, nrounds, coef, width, side, dmin, &
+                                    ends, length, status, nsteps, offsets, total, points, bpt, .false., &
+                                    "ndsm_hip_vecpot_separators")
+  end function
+
+  ! the same on DEVICE arrays of the library's GPU (total stays on the host; no array is touched on the host)
+  function ndsm_hip_vecpot_separators_device(handle, dB, nnulls, dpos, dkind, dnormal, nbr, dpair, darc, radius, capture, &
+                                             step, max_steps, rounds, tol, every, max_points, dstate, dnrounds, dcoef, &
+                                             dwidth, dside, ddmin, dends, dlength, dstatus, dnsteps, doffsets, total, &
+                                             dpoints, dbpt) bind(c, name="ndsm_hip_vecpot_separators_device") result(ierr)
+    type(c_ptr), value :: handle, dB, dpos, dkind, dnormal, dpair, darc, dstate, dnrounds, dcoef, dwidth, dside, ddmin, &
+                          dends, dlength, dstatus, dnsteps, doffsets, total, dpoints, dbpt
+    integer(c_int), value :: nnulls, nbr, max_steps, rounds, every
+    integer(c_int64_t), value :: max_points
+    real(c_double), value :: radius, capture, step, tol
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_separators(handle, dB, nnulls, dpos, dkind, dnormal, nbr, dpair, darc, radius, capture, step, &
+                                    max_steps, rounds, tol, every, max_points, dstate, dnrounds, dcoef, dwidth, dside, &
+                                    ddmin, dends, dlength, dstatus, dnsteps, doffsets, total, dpoints, dbpt, .true., &
+                                    "ndsm_hip_vecpot_separators_device")
+  end function
+
+  function vecpot_handle_separators(handle, B, nnulls, pos, kind, normal, nbr, pair, arc, radius, capture, step, &
+                                    max_steps, rounds, tol, every, max_points, state, nrounds, coef, width, side, dmin, &
+                                    ends, length, status, nsteps, offsets, total, points, bpt, on_device, who) &
+      result(ierr)
+    type(c_ptr), intent(in) :: handle, B, pos, kind, normal, pair, arc, state, nrounds, coef, width, side, dmin, ends, &
+                               length, status, nsteps, offsets, total, points, bpt
+    integer(c_int), intent(in) :: nnulls, nbr, max_steps, rounds, every
+    integer(c_int64_t), intent(in) :: max_points
+    real(c_double), intent(in) :: radius, capture, step, tol
+    logical, intent(in) :: on_device
+    character(len=*), intent(in) :: who
+    integer(c_int) :: ierr
+    ierr = checked()
+    if (ierr /= 0) call clear_outputs()
+  contains
+    function checked() result(rc)
+      integer(c_int) :: rc
+      type(vecpot_ctx), pointer :: ctx
+      integer(c_int64_t), pointer :: tot
+      rc = ndsmk_init(-1_c_int)                        ! without a device: 9001, whatever the arguments
+      if (rc /= 0) return
+      rc = NDSMK_EARG
+      if (.not. (c_associated(handle) .and. c_associated(total))) return
+      call c_f_pointer(total, tot)
+      tot = 0
+      ! no brackets: no array is looked at; the scalars are the kernel layer's to judge (9004) once the arrays are there
+      if (nbr > 0) then
+        if (.not. (c_associated(B) .and. c_associated(pos) .and. c_associated(kind) .and. c_associated(normal) .and. &
+                   c_associated(pair) .and. c_associated(arc) .and. c_associated(state) .and. &
+                   c_associated(nrounds) .and. c_associated(coef) .and. c_associated(width) .and. &
+                   c_associated(side) .and. c_associated(dmin) .and. c_associated(ends) .and. c_associated(length) .and. &
+                   c_associated(status) .and. c_associated(nsteps) .and. c_associated(offsets))) return
+        if (max_points > 0 .and. .not. c_associated(points)) return
+      end if
+      call c_f_pointer(handle, ctx)
+      if (.not. ctx%live) return
+      rc = vecpot_separators(ctx, B, nnulls, pos, kind, normal, nbr, pair, arc, radius, capture, step, max_steps, rounds, &
+                             tol, every, max_points, state, nrounds, coef, width, side, dmin, ends, length, status, nsteps, &
+                             offsets, tot, points, bpt, on_device)
+      if (rc /= 0) then
+        call report(who, rc)
+        if (rc < NDSMK_ENODEV) rc = NDSMK_ENODEV
+      end if
+    end function
+
+    ! total, and (host entry) the nbr entries of the per-bracket outputs, the nbr + 1 of offsets and the max_points
+    ! slots of every point array that is there
+    subroutine clear_outputs()
+      real(c_double), pointer :: r(:)
+      integer(c_int32_t), pointer :: k(:)
+      integer(c_int64_t), pointer :: k8(:)
+      type(c_ptr) :: pr(5), pk(5)
+      integer :: i
+      integer, parameter :: per(5) = [4, 1, 2, 3, 1]
+      if (c_associated(total)) then
+        call c_f_pointer(total, k8, [1]); k8 = 0
+      end if
+      if (on_device) return
+      if (nbr > 0 .and. nbr <= huge(0) / 4) then
+        pr = [coef, width, dmin, ends, length]
+        pk = [state, nrounds, side, status, nsteps]
+        do i = 1, 5
+          if (c_associated(pr(i))) then
+            call c_f_pointer(pr(i), r, [per(i) * nbr]); r = 0
+          end if
+          if (c_associated(pk(i))) then
+            call c_f_pointer(pk(i), k, [nbr]); k = 0
+          end if
+        end do
+        if (c_associated(offsets)) then
+          call c_f_pointer(offsets, k8, [nbr + 1]); k8 = 0
+        end if
+      end if
+      if (max_points <= 0 .or. max_points > huge(0_c_int64_t) / 3) return
+      if (c_associated(points)) then
+        call c_f_pointer(points, r, [3 * max_points]); r = 0
+      end if
+      if (c_associated(bpt)) then
+        call c_f_pointer(bpt, r, [3 * max_points]); r = 0
+      end if
+    end subroutine
+  end function
+
   ! ---- null points on the same handle --------------------------------------
   ! B (nx,ny,nz,3) in; max_nulls >= 0 the capacity of the record arrays; counts (2, int64, on the HOST in both
   ! entries): the screen's candidates, the nulls found.  Out, the first min(counts(2), max_nulls) records in ascending

@@ -646,6 +646,33 @@ module ndsmh_iface
       integer(c_int) :: rc
     end function
 
+    ! ---- separator lines (separators.hip): check, refinement and counting (blocks for total), then filling ----
+    function ndsmk_sep_count(B, n3, lo3, dq3, nnulls, pos, kind, normal, nbr, pair, arc, radius, capture, step, &
+                             max_steps, rounds, tol, every, max_points, state, nrounds, coef, width, side, dmin, ends, &
+                             length, status, nsteps, offsets, total) bind(c, name="ndsmk_sep_count") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_int64_t, c_double
+      type(c_ptr), value :: B, pos, kind, normal, pair, arc, state, nrounds, coef, width, side, dmin, ends, length, &
+                            status, nsteps, offsets
+      integer(c_int32_t), intent(in) :: n3(3)
+      real(c_double), intent(in) :: lo3(3), dq3(3)
+      integer(c_int), value :: nnulls, nbr, max_steps, rounds, every
+      real(c_double), value :: radius, capture, step, tol
+      integer(c_int64_t), value :: max_points
+      integer(c_int64_t), intent(out) :: total
+      integer(c_int) :: rc
+    end function
+    function ndsmk_sep_fill(B, n3, lo3, dq3, nnulls, pos, nbr, pair, radius, capture, step, max_steps, rounds, tol, &
+                            every, max_points, offsets, points, bpt) bind(c, name="ndsmk_sep_fill") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_int64_t, c_double
+      type(c_ptr), value :: B, pos, pair, offsets, points, bpt
+      integer(c_int32_t), intent(in) :: n3(3)
+      real(c_double), intent(in) :: lo3(3), dq3(3)
+      integer(c_int), value :: nnulls, nbr, max_steps, rounds, every
+      real(c_double), value :: radius, capture, step, tol
+      integer(c_int64_t), value :: max_points
+      integer(c_int) :: rc
+    end function
+
     ! ---- the face phase on the device (faces.hip) ----
     function ndsmk_face_offsets(n3, off6, total) bind(c, name="ndsmk_face_offsets") result(rc)
       import :: c_int, c_int32_t, c_int64_t

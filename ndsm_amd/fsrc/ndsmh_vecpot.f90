@@ -32,7 +32,7 @@ module ndsmh_vecpot
 
   public :: vecpot_solve, poisson_solve
   public :: vecpot_ctx, vecpot_ctx_create, vecpot_ctx_destroy, vecpot_ctx_matches, vecpot_run, vecpot_cache_drop
-  public :: vecpot_project, vecpot_devore, vecpot_lines, vecpot_paths, vecpot_nulls, vecpot_skeleton
+  public :: vecpot_project, vecpot_devore, vecpot_lines, vecpot_paths, vecpot_nulls, vecpot_skeleton, vecpot_separators
   public :: VP_POTENTIAL, VP_FIELD, VP_HELICITY
   ! pieces the distributed driver (ndsmh_wvecpot) shares with vecpot_solve
   public :: face_data, face_axis, face_upper, face_t1, face_t2, face_order, face_copy, vecpot_faces, say
@@ -1397,6 +1397,124 @@ contains
     if (rc == 0) rc = ndsmk_d2h(poff, d(10), 8_c_size_t * (nl + 1))
     do i = 1, 2
       if (rc == 0 .and. np > 0 .and. c_associated(hp(i))) rc = ndsmk_d2h(hp(i), dp(i), pwidth(i) * np)
+    end do
+    if (rc == 0) rc = ndsmk_sync()
+    if (c_associated(pbuf)) then
+      rc_free = ndsmk_free(pbuf)
+      if (rc == 0) rc = rc_free
+    end if
+    rc_free = ndsmk_free(buf)
+    if (rc == 0) rc = rc_free
+    if (rc /= 0) total = 0
+  end function
+
+  ! ------------------------------------------------------------------
+  ! The separator entries on a prepared context (semantics in include/ndsm_hip.h, DESIGN.md "Separator lines"): each
+  ! bracket - an arc (a, b) of the fan ring of null m and a null m' of the other sign - is refined by one wave until the
+  ! arc is narrower than tol, and the fan line of its a side is stored as the skeleton stores a line.  The context
+  ! supplies the mesh only, as in vecpot_skeleton.  pB (nx,ny,nz,3), ppos (3,nnulls), pkind (nnulls; int32), pnormal
+  ! (3,nnulls), ppair (2,nbr; int32), parc (4,nbr) in; per bracket pstate, pnrounds, pside (int32), pcoef (4), pwidth,
+  ! pdmin (2), pends (3), plen, pstat, pnst out; poff (nbr + 1, int64), total, ppts (3,max_points), pbpt (the same;
+  ! c_null_ptr: skipped) as vecpot_skeleton - on the HOST (staged as there) or (on_device) in HBM.  total is a host scalar
+  ! either way.
+  ! ------------------------------------------------------------------
+  function vecpot_separators(ctx, pB, nnulls, ppos, pkind, pnormal, nbr, ppair, parc, radius, capture, step, max_steps, &
+                             rounds, tol, every, max_points, pstate, pnrounds, pcoef, pwidth, pside, pdmin, pends, plen, &
+                             pstat, pnst, poff, total, ppts, pbpt, on_device) result(rc)
+    type(vecpot_ctx), intent(inout), target :: ctx
+    logical, intent(in) :: on_device
+    type(c_ptr), intent(in) :: pB, ppos, pkind, pnormal, ppair, parc, pstate, pnrounds, pcoef, pwidth, pside, pdmin, &
+                               pends, plen, pstat, pnst, poff, ppts, pbpt
+    integer(c_int), intent(in) :: nnulls, nbr, max_steps, rounds, every
+    integer(c_int64_t), intent(in) :: max_points
+    real(wp), intent(in) :: radius, capture, step, tol
+    integer(c_int64_t), intent(out) :: total
+    integer(c_int) :: rc, rc_free
+    real(wp) :: dq(3), lo(3)
+    integer(c_int32_t) :: n3(3)
+    integer(c_size_t) :: nb, nm, nq, np, no
+    integer :: i
+    type(c_ptr) :: buf, pbuf, din(5), d(11), dp(2), hp(2), hi(5), ho(11)
+    ! bytes per null of pos, normal, kind and per bracket of arc, pair (the 8-byte arrays first); per bracket of coef,
+    ! width, dmin, ends, length, then state, nrounds, side, status, nsteps; per point of points, bpt
+    integer(c_size_t), parameter :: iwidth(5) = [24, 24, 32, 4, 8], owidth(10) = [32, 8, 16, 24, 8, 4, 4, 4, 4, 4], &
+                                    ptwidth(2) = [24, 24]
+    integer(c_size_t) :: icount(5)
+
+    total = 0
+    n3 = ctx%n3
+    dq = [ctx%qx(2) - ctx%qx(1), ctx%qy(2) - ctx%qy(1), ctx%qz(2) - ctx%qz(1)]      ! as vecpot_run
+    lo = [ctx%qx(1), ctx%qy(1), ctx%qz(1)]
+    if (on_device .or. nbr <= 0 .or. nnulls <= 0 .or. step <= 0.0_wp .or. max_steps < 1 .or. every < 1 .or. &
+        rounds < 1 .or. max_points < 0 .or. .not. (radius > 0.0_wp) .or. .not. (capture > 0.0_wp) .or. &
+        radius > 1.0e300_wp .or. capture > 1.0e300_wp .or. .not. (step <= 1.0e300_wp) .or. .not. (tol >= 0.0_wp) .or. &
+        tol > 1.0e300_wp .or. int(nbr, c_int64_t) * 64_c_int64_t > 2147483647_c_int64_t) then
+      ! (the argument errors, more brackets than a call takes among them, are the kernel entries' to name; nothing is
+      ! staged for them)
+      rc = ndsmk_sep_count(pB, n3, lo, dq, nnulls, ppos, pkind, pnormal, nbr, ppair, parc, radius, capture, step, &
+                           max_steps, rounds, tol, every, max_points, pstate, pnrounds, pcoef, pwidth, pside, pdmin, &
+                           pends, plen, pstat, pnst, poff, total)
+      if (rc == 0) rc = ndsmk_sep_fill(pB, n3, lo, dq, nnulls, ppos, nbr, ppair, radius, capture, step, max_steps, rounds, &
+                                       tol, every, max_points, poff, ppts, pbpt)
+      if (rc == 0) rc = ndsmk_sync()
+      if (rc /= 0) total = 0
+      return
+    end if
+    nb = int(product(int(n3, ik)), c_size_t) * 24_c_size_t
+    nm = int(nnulls, c_size_t)
+    nq = int(nbr, c_size_t)
+    if (.not. c_associated(ctx%dF(1))) then
+      rc = ndsmk_alloc(ctx%dF(1), nb); if (rc /= 0) return
+    end if
+    rc = ndsmk_h2d(ctx%dF(1), pB, nb); if (rc /= 0) return
+    ! one scratch buffer: offsets, then the inputs pos, normal, arc, pair (a whole number of 8-byte words), kind, then
+    ! the outputs in the order of owidth
+    icount = [nm, nm, nq, nm + mod(nm, 2_c_size_t), nq]
+    buf = c_null_ptr
+    pbuf = c_null_ptr
+    rc = ndsmk_alloc(buf, 8_c_size_t * (nq + 1) + sum(iwidth * icount) + sum(owidth) * nq)
+    if (rc /= 0) return
+    d(11) = buf
+    no = 8_c_size_t * (nq + 1)
+    do i = 1, 5
+      din(i) = dptr_offset(buf, no); no = no + iwidth(i) * icount(i)
+    end do
+    do i = 1, 10
+      d(i) = dptr_offset(buf, no); no = no + owidth(i) * nq
+    end do
+    hi = [ppos, pnormal, parc, pkind, ppair]
+    icount(4) = nm
+    do i = 1, 5
+      if (rc == 0) rc = ndsmk_h2d(din(i), hi(i), iwidth(i) * icount(i))
+    end do
+    if (rc == 0) then
+      call say("find_separators", "Refining the brackets, tracing the separators and counting the points...")
+      rc = ndsmk_sep_count(ctx%dF(1), n3, lo, dq, nnulls, din(1), din(4), din(2), nbr, din(5), din(3), radius, capture, &
+                           step, max_steps, rounds, tol, every, max_points, d(6), d(7), d(1), d(2), d(8), d(3), d(4), &
+                           d(5), d(9), d(10), d(11), total)
+    end if
+    ! the point arrays: min(total, max_points) slots each, carved from a second buffer
+    np = 0
+    if (rc == 0) np = int(min(total, max_points), c_size_t)
+    dp = c_null_ptr
+    hp = [ppts, pbpt]
+    if (rc == 0 .and. np > 0) then
+      rc = ndsmk_alloc(pbuf, merge(48_c_size_t, 24_c_size_t, c_associated(pbpt)) * np)
+      if (rc == 0) then
+        dp(1) = pbuf
+        if (c_associated(pbpt)) dp(2) = dptr_offset(pbuf, 24_c_size_t * np)
+        call say("find_separators", "Tracing again and storing the points...")
+        rc = ndsmk_sep_fill(ctx%dF(1), n3, lo, dq, nnulls, din(1), nbr, din(5), radius, capture, step, max_steps, rounds, &
+                            tol, every, int(np, c_int64_t), d(11), dp(1), dp(2))
+      end if
+    end if
+    ho = [pcoef, pwidth, pdmin, pends, plen, pstate, pnrounds, pside, pstat, pnst, poff]
+    do i = 1, 10
+      if (rc == 0) rc = ndsmk_d2h(ho(i), d(i), owidth(i) * nq)
+    end do
+    if (rc == 0) rc = ndsmk_d2h(poff, d(11), 8_c_size_t * (nq + 1))
+    do i = 1, 2
+      if (rc == 0 .and. np > 0 .and. c_associated(hp(i))) rc = ndsmk_d2h(hp(i), dp(i), ptwidth(i) * np)
     end do
     if (rc == 0) rc = ndsmk_sync()
     if (c_associated(pbuf)) then

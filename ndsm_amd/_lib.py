@@ -351,6 +351,27 @@ class VecPot:
                 self.L.ndsm_hip_device_free(p)
         return ierr
 
+    def _entry(self, name, args, device, who=None):
+        """One call of an entry that takes arrays: L.<name>(h, *args) on host arrays, or (device) L.<name>_device with
+        the arrays staged in device memory first and copied back.  args in the order of the C prototype: a numpy
+        array is passed by its address (host) or staged (device) - the same array twice is staged once -, anything
+        else (a scalar, None, an address that holds in both modes, a pointer to an array already on the device) goes
+        through as it is.  Raises NdsmHipError unless the entry returns 0, under the name of the entry that ran or
+        `who`."""
+        def host(a):
+            return isinstance(a, np.ndarray)
+        if not device:
+            ierr = getattr(self.L, name)(self.h, *[a.ctypes.data if host(a) else a for a in args])
+        else:
+            name += "_device"
+            staged = list({id(a): a for a in args if host(a)}.values())
+
+            def call(*ptrs):
+                dev = {id(a): p for a, p in zip(staged, ptrs)}
+                return getattr(self.L, name)(self.h, *[dev[id(a)] if host(a) else a for a in args])
+            ierr = self._on_device(staged, call)
+        _check(ierr, who or name, self.L)
+
     def solve_field(self, b, a_init=None, niterex_max=10000, ncycles_max=1024, ex_tol=1e-13, vc_tol=1e-10, ms=5,
                     mean=False, mixed_precision=False, flxcrl=False, device=False):
         """Vector potential of the whole field b (3,nz,ny,nx), curl b != 0 allowed: the same gauge and tangential
@@ -501,7 +522,9 @@ class VecPot:
         out = _trace_outputs(len(S), direction)
         if len(S) == 0:
             return _field_lines(out, direction)
-        self._line_entry("ndsm_hip_vecpot_trace", B, G, (), S, (step, max_steps, direction), out, device)
+        # (an error of the device entry has always been reported under the host entry's name here)
+        self._entry("ndsm_hip_vecpot_trace", [B, G, len(S), S, step, max_steps, direction, *out], device,
+                    who="ndsm_hip_vecpot_trace")
         return _field_lines(out, direction)
 
     def paths(self, b, seeds, g=None, step=0.5, max_steps=None, direction="both", every=1, max_points=None,
@@ -529,39 +552,15 @@ class VecPot:
             return _field_paths(out, direction, np.zeros(1, dtype=np.int64), np.zeros((0, 3)),
                                 np.zeros((0, 3)) if withb else None, np.zeros((0, 3)) if withg else None,
                                 np.zeros(0) if withg else None)
-        name = "ndsm_hip_vecpot_paths_device" if device else "ndsm_hip_vecpot_paths"
-        cap = 0 if max_points is None else max_points
-        for _attempt in range(2):
-            offsets = np.zeros(nl + 1, dtype=np.int64)
-            total = np.zeros(1, dtype=np.int64)
+        def run(cap):
+            offsets, total = np.zeros(nl + 1, dtype=np.int64), np.zeros(1, dtype=np.int64)
             m = max(cap, 1)
             pts = [np.zeros((m, 3)), np.zeros((m, 3)) if withb else None, np.zeros((m, 3)) if withg else None,
                    np.zeros(m) if withg else None]
-            tail = (step, max_steps, direction, every, cap)
-            if not device:
-                ierr = self.L.ndsm_hip_vecpot_paths(
-                    self.h, B.ctypes.data, None if G is None else G.ctypes.data, ns, S.ctypes.data, *tail,
-                    *[a.ctypes.data for a in out], offsets.ctypes.data, total.ctypes.data,
-                    *[None if a is None or cap == 0 else a.ctypes.data for a in pts])
-            else:
-                staged = [S] + out + [offsets] + [a for a in pts if a is not None] + [B] + ([] if G is None else [G])
-
-                def call(dS, *ptrs):
-                    ptrs = list(ptrs)
-                    head = [ptrs.pop(0) for _ in range(6)]
-                    dpts = [None if a is None else ptrs.pop(0) for a in pts]
-                    if cap == 0:
-                        dpts = [None] * 4
-                    dB = ptrs.pop(0)
-                    dG = ptrs.pop(0) if G is not None else None
-                    return self.L.ndsm_hip_vecpot_paths_device(self.h, dB, dG, ns, dS, *tail, *head, total.ctypes.data,
-                                                               *dpts)
-                ierr = self._on_device(staged, call)
-            _check(ierr, name, self.L)
-            if int(total[0]) <= cap:
-                break
-            cap = int(total[0])
-        n = min(int(total[0]), cap)
+            self._entry("ndsm_hip_vecpot_paths", [B, G, ns, S, step, max_steps, direction, every, cap, *out, offsets,
+                                                  total.ctypes.data, *[a if cap else None for a in pts]], device)
+            return int(total[0]), (offsets, pts)
+        n, (offsets, pts) = _with_capacity(run, 0 if max_points is None else max_points)
         return _field_paths(out, direction, offsets, *[None if a is None else a[:n] for a in pts])
 
     def default_max_steps(self, step=0.5):
@@ -589,27 +588,6 @@ class VecPot:
         if len(S) > TRACE_MAX_SEEDS:
             raise NdsmHipError(f"trace: {len(S)} seeds, at most {TRACE_MAX_SEEDS} per call (code 9002)")
         return np.ascontiguousarray(S).copy()
-
-    def _line_entry(self, name, B, G, head, S, tail, out, device):
-        """One call of a line entry: L.<name>(h, B, G, *head, nseeds, seeds, *tail, *out) on host arrays, or (device)
-        L.<name>_device with the seeds S, the outputs and every field that is a host array staged in device memory
-        first.  B, G: flat host arrays, or with device=True pointers to arrays already there; G None: no integral;
-        G is B: the same pointer twice.  Raises NdsmHipError unless the entry returns 0."""
-        def host(a):
-            return isinstance(a, np.ndarray)
-        if not device:
-            ierr = getattr(self.L, name)(self.h, B.ctypes.data, G.ctypes.data if host(G) else None, *head, len(S),
-                                         S.ctypes.data, *tail, *[a.ctypes.data for a in out])
-        else:
-            fields = [a for a in ((B,) if G is B else (B, G)) if host(a)]
-
-            def call(dS, *ptrs):
-                rest = list(ptrs[len(out):])
-                dB = rest.pop(0) if host(B) else B
-                dG = dB if G is B else (rest.pop(0) if host(G) else G)
-                return getattr(self.L, name + "_device")(self.h, dB, dG, *head, len(S), dS, *tail, *ptrs[:len(out)])
-            ierr = self._on_device([S] + out + fields, call)
-        _check(ierr, name if host(B) else name + "_device", self.L)
 
     def squashing(self, b, seeds, g=None, integrand=0, twist=False, step=0.5, max_steps=None, device=False):
         """Squashing factor Q (Titov 2007) of b (3,nz,ny,nx) at seeds (nseeds,3; anywhere in the box), on the device,
@@ -639,8 +617,8 @@ class VecPot:
         if twist:
             integrand = 1
         # (the field passed as its own g with integrand 1 asks the library for g = curl b)
-        self._line_entry("ndsm_hip_vecpot_squash", B, B if twist else G, (integrand,), S, (step, max_steps), out,
-                         device)
+        self._entry("ndsm_hip_vecpot_squash", [B, B if twist else G, integrand, len(S), S, step, max_steps, *out],
+                    device, who="ndsm_hip_vecpot_squash")
         return _qmap(out, twist)
 
     def nulls(self, b, max_nulls=4096, merge=1e-6, device=False):
@@ -664,23 +642,14 @@ class VecPot:
                                       merge >= 0.0 and np.isfinite(merge)):
             raise ValueError(f"merge must be None or a finite number >= 0, not {merge!r}")
         B = self._field_arg(b, "nulls")
-        cap = int(max_nulls)
-        for _attempt in range(2):
+        def run(cap):
             counts = np.zeros(2, dtype=np.int64)
             m = max(cap, 1)
             out = [np.zeros(m, dtype=np.int64), np.zeros((m, 3)), np.zeros((m, 3, 3)), np.zeros(m), np.zeros(m),
                    np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int32)]
-            if not device:
-                ierr = self.L.ndsm_hip_vecpot_nulls(self.h, B.ctypes.data, cap, counts.ctypes.data,
-                                                    *[a.ctypes.data for a in out])
-            else:
-                ierr = self._on_device([B] + out, lambda dB, *ptrs: self.L.ndsm_hip_vecpot_nulls_device(
-                    self.h, dB, cap, counts.ctypes.data, *ptrs))
-            _check(ierr, "ndsm_hip_vecpot_nulls_device" if device else "ndsm_hip_vecpot_nulls", self.L)
-            if int(counts[1]) <= cap or cap == 0:
-                break
-            cap = int(counts[1])
-        n = min(int(counts[1]), cap)
+            self._entry("ndsm_hip_vecpot_nulls", [B, cap, counts.ctypes.data, *out], device)
+            return int(counts[1]), (counts, out)
+        n, (counts, out) = _with_capacity(run, int(max_nulls), count_only=True)
         hmin = min(float(q[1]) - float(q[0]) for q in (self.x, self.y, self.z))
         return _nulls_tuple([a[:n] for a in out], int(counts[0]), int(counts[1]), None if merge is None else
                             float(merge) * hmin)
@@ -721,36 +690,15 @@ class VecPot:
         if n == 0:
             return _skeleton_tuple(pos, nr, pernull, lines, np.zeros(1, dtype=np.int64), np.zeros((0, 3)),
                                    np.zeros((0, 3)) if withb else None)
-        name = "ndsm_hip_vecpot_skeleton_device" if device else "ndsm_hip_vecpot_skeleton"
-        R = ring if nr else np.zeros((1, 2))
-        cap = 0 if max_points is None else max_points
-        for _attempt in range(2):
-            offsets = np.zeros(nl + 1, dtype=np.int64)
-            total = np.zeros(1, dtype=np.int64)
+        def run(cap):
+            offsets, total = np.zeros(nl + 1, dtype=np.int64), np.zeros(1, dtype=np.int64)
             m = max(cap, 1)
             pts = [np.zeros((m, 3)), np.zeros((m, 3)) if withb else None]
-            head = (radius, capture, step, max_steps, every, cap)
-            outs = pernull + lines + [offsets]
-            if not device:
-                ierr = self.L.ndsm_hip_vecpot_skeleton(
-                    self.h, B.ctypes.data, n, pos.ctypes.data, jac.ctypes.data, nr, R.ctypes.data if nr else None, *head,
-                    *[a.ctypes.data for a in outs], total.ctypes.data,
-                    *[None if a is None or cap == 0 else a.ctypes.data for a in pts])
-            else:
-                staged = [B, pos, jac, R] + outs + [a for a in pts if a is not None]
-
-                def call(dB, dpos, djac, dR, *ptrs):
-                    ptrs = list(ptrs)
-                    douts = [ptrs.pop(0) for _ in outs]
-                    dpts = [None if a is None or cap == 0 else ptrs.pop(0) for a in pts]
-                    return self.L.ndsm_hip_vecpot_skeleton_device(self.h, dB, n, dpos, djac, nr, dR if nr else None,
-                                                                  *head, *douts, total.ctypes.data, *dpts)
-                ierr = self._on_device(staged, call)
-            _check(ierr, name, self.L)
-            if int(total[0]) <= cap:
-                break
-            cap = int(total[0])
-        k = min(int(total[0]), cap)
+            self._entry("ndsm_hip_vecpot_skeleton",
+                        [B, n, pos, jac, nr, ring if nr else None, radius, capture, step, max_steps, every, cap, *pernull,
+                         *lines, offsets, total.ctypes.data, *[a if cap else None for a in pts]], device)
+            return int(total[0]), (offsets, pts)
+        k, (offsets, pts) = _with_capacity(run, 0 if max_points is None else max_points)
         return _skeleton_tuple(pos, nr, pernull, lines, offsets, pts[0][:k], None if pts[1] is None else pts[1][:k])
 
     def separators(self, b, skeleton=None, pairs=None, brackets=None, radius=0.5, capture=None, step=0.5,
@@ -809,35 +757,15 @@ class VecPot:
         if nbr == 0:
             return _separators_tuple(pair, per, np.zeros(1, dtype=np.int64), np.zeros((0, 3)),
                                      np.zeros((0, 3)) if withb else None)
-        name = "ndsm_hip_vecpot_separators_device" if device else "ndsm_hip_vecpot_separators"
-        # room for a few hundred points per line at first; the call is repeated once when the lines are longer
-        cap = int(min(nbr * min(-(-max_steps // every) + 2, 512), 2 ** 22))
-        for _attempt in range(2):
-            offsets = np.zeros(nbr + 1, dtype=np.int64)
-            total = np.zeros(1, dtype=np.int64)
+        def run(cap):
+            offsets, total = np.zeros(nbr + 1, dtype=np.int64), np.zeros(1, dtype=np.int64)
             pts = [np.zeros((cap, 3)), np.zeros((cap, 3)) if withb else None]
-            head = (radius, capture, step, max_steps, rounds, tol, every, cap)
-            outs = per + [offsets]
-            if not device:
-                ierr = self.L.ndsm_hip_vecpot_separators(
-                    self.h, B.ctypes.data, n, pos.ctypes.data, kind.ctypes.data, normal.ctypes.data, nbr,
-                    pair.ctypes.data, arc.ctypes.data, *head, *[a.ctypes.data for a in outs], total.ctypes.data,
-                    *[None if a is None else a.ctypes.data for a in pts])
-            else:
-                staged = [B, pos, kind, normal, pair, arc] + outs + [a for a in pts if a is not None]
-
-                def call(dB, dpos, dkind, dnormal, dpair, darc, *ptrs):
-                    ptrs = list(ptrs)
-                    douts = [ptrs.pop(0) for _ in outs]
-                    dpts = [None if a is None else ptrs.pop(0) for a in pts]
-                    return self.L.ndsm_hip_vecpot_separators_device(self.h, dB, n, dpos, dkind, dnormal, nbr, dpair, darc,
-                                                                    *head, *douts, total.ctypes.data, *dpts)
-                ierr = self._on_device(staged, call)
-            _check(ierr, name, self.L)
-            if int(total[0]) <= cap:
-                break
-            cap = int(total[0])
-        k = min(int(total[0]), cap)
+            self._entry("ndsm_hip_vecpot_separators", [B, n, pos, kind, normal, nbr, pair, arc, radius, capture, step,
+                                                       max_steps, rounds, tol, every, cap, *per, offsets,
+                                                       total.ctypes.data, *pts], device)
+            return int(total[0]), (offsets, pts)
+        # room for a few hundred points per line at first; the call is repeated once when the lines are longer
+        k, (offsets, pts) = _with_capacity(run, int(min(nbr * min(-(-max_steps // every) + 2, 512), 2 ** 22)))
         return _separators_tuple(pair, per, offsets, pts[0][:k], None if pts[1] is None else pts[1][:k])
 
     def seed_plane(self, axis, value, n1, n2):
@@ -871,7 +799,7 @@ class VecPot:
             """trace on the resident B and A (d: the chain's device arrays)"""
             if len(S) == 0:
                 return
-            self._line_entry("ndsm_hip_vecpot_trace", d["B"], d["A"], (), S, (step, max_steps, direction), out, True)
+            self._entry("ndsm_hip_vecpot_trace", [d["B"], d["A"], len(S), S, step, max_steps, direction, *out], True)
 
         ioptc, ropt = self._options(niterex_max, ncycles_max, ex_tol, vc_tol, ms, mean, mixed_precision, flxcrl)
         if gauge == "devore":
@@ -939,6 +867,18 @@ Projection = collections.namedtuple("Projection", ["ierr", "B", "phi", "c", "div
 
 Helicity = collections.namedtuple("Helicity", ["ierr", "H_R", "H_J", "E", "E_p", "E_free", "recon_max", "recon_rms",
                                                "divB_max", "divA_max", "A", "A_p", "B_p"])
+
+
+def _with_capacity(run, cap, count_only=False):
+    """The two-attempt capacity rule of the entries with results of unknown length: run(cap) makes the call with room
+    for cap records and returns (the number there are, its arrays); when that number is more than cap the call is made
+    once more with that number (count_only: not from cap 0, which asks for the count alone).  Returns (the number of
+    records the last call stored, its arrays)."""
+    total, arrays = run(cap)
+    if total > cap and not (count_only and cap == 0):
+        cap = total
+        total, arrays = run(cap)
+    return min(total, cap), arrays
 
 
 def _helicity_tuple(ierr, out, A, Ap, Bp):

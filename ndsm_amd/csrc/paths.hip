@@ -6,8 +6,8 @@
 //   count   ndsmk_trace   the trace entry itself: ends, length, integral, status and n = nsteps of every line
 //           npts_k        offsets[l] = npts(l) = 1 if n = 0, else (n - 1) / every + 2
 //           scan64_k      in place: offsets[l] = the exclusive sum, offsets[nl] = the total; one workgroup, every lane
-//                         sums a contiguous run (scan64.hpp, shared with skeleton.hip; the int64 sibling of
-//                         nulls.hip's scan_k)
+//                         sums a contiguous run (scan64.hpp's scan64_total, shared with skeleton.hip and
+//                         separators.hip; the int64 sibling of nulls.hip's scan_k)
 //   fill    paths_k       one lane per line, one wave per workgroup, as trace_k: the loop of trace_k with
 //                         trace_step.hpp's stage and step - the same r and I - which stores the state before step
 //                         0, every, 2 every, ... once that step is known to move the line, and the final state
@@ -162,11 +162,7 @@ extern "C" int ndsmk_paths_count(const double *B, const double *G, const int32_t
   hipLaunchKernelGGL(npts_k, dim3((unsigned)((nl + kNptsBlock - 1) / kNptsBlock)), dim3(kNptsBlock), 0, s, nsteps, nl,
                      every, (i64 *)offsets);
   NDSM_LAUNCH_CHECK();
-  hipLaunchKernelGGL(scan64_k, dim3(1), dim3(kScanBlock), 0, s, (i64 *)offsets, nl);
-  NDSM_LAUNCH_CHECK();
-  NDSM_HIP(hipMemcpyAsync(h_total, offsets + nl, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  NDSM_HIP(hipStreamSynchronize(s));
-  return 0;
+  return scan64_total(offsets, nl, h_total, s);
 }
 
 // The filling half, after ndsmk_paths_count with the same arguments and its offsets: slot k < max_points of the

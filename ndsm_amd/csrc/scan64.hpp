@@ -1,5 +1,5 @@
-// The in-place int64 exclusive scan of one workgroup, shared by paths.hip and skeleton.hip (count, scan, fill: the
-// offsets of variable-length results come from their counts).
+// The in-place int64 exclusive scan of one workgroup and the tail of a counting half built on it, shared by paths.hip,
+// skeleton.hip and separators.hip (count, scan, fill: the offsets of variable-length results come from their counts).
 #pragma once
 
 #include "common.hpp"
@@ -35,6 +35,16 @@ __global__ __launch_bounds__(kScanBlock) void scan64_k(i64 *a, size_t ng) {
     run += c;
   }
   if (threadIdx.x == kScanBlock - 1) a[ng] = part[kScanBlock - 1];
+}
+
+// the tail of a counting half: offsets (ng counts, DEVICE) scanned in place, the total offsets[ng] into *h_total
+// (HOST).  Blocks for the total.
+int scan64_total(int64_t *offsets, size_t ng, int64_t *h_total, hipStream_t s) {
+  hipLaunchKernelGGL(scan64_k, dim3(1), dim3(kScanBlock), 0, s, (i64 *)offsets, ng);
+  NDSM_LAUNCH_CHECK();
+  NDSM_HIP(hipMemcpyAsync(h_total, offsets + ng, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  NDSM_HIP(hipStreamSynchronize(s));
+  return 0;
 }
 
 }  // namespace

@@ -14,11 +14,14 @@
 //                            bracket's line, go to scratch.
 //   count   sep_line_k<0>    one lane per bracket, as skel_line_k with the capture test against m' alone: ends, length,
 //                            status, nsteps, and offsets[l] = npts(l)
-//           scan64_k         in place, as paths.hip
+//           scan64_total     scan64.hpp: the scan in place and the total, as paths.hip
 //   fill    sep_line_k<1>    the same loop - the same expressions, so the same bits - which stores the points
+// The flag of the check, the seeds and the directions live in g_sep, a line_scratch.hpp LineScratch with one leading
+// slot.
 // A lane writes slot offsets[l] + j only for j < min(offsets[l + 1], max_points) - offsets[l].  No wave ever leaves
 // sep_refine_k's round loop with part of its lanes: the exits are decided from ballots and lane 0's values, which every
 // lane holds.
+#include "line_scratch.hpp"
 #include "scan64.hpp"
 #include "trace_step.hpp"
 
@@ -304,42 +307,10 @@ __global__ __launch_bounds__(kLineBlock) void sep_line_k(const double *__restric
   }
 }
 
-// scratch of the call, kept between calls and grown on demand (no result depends on its size): the flag of the check
-// (one 8-byte slot), then the seed (3 doubles) and the direction (1 double) of every bracket's line, written by the
-// counting half and read again by the filling half
-struct SepScratch {
-  double *buf = nullptr;
-  size_t cap = 0;              // brackets the buffer holds
-  size_t nbr = 0;              // brackets the last counting half wrote
-  bool registered = false;     // sep_release is queued for the next reset
-};
-SepScratch g_sep;
-
-void sep_release() {
-  if (g_sep.buf) (void)hipFree(g_sep.buf);
-  g_sep = SepScratch();
-}
-
-int sep_grow(size_t nbr) {
-  if (!g_sep.registered) {
-    ndsm::at_reset(sep_release);
-    g_sep.registered = true;
-  }
-  g_sep.nbr = 0;
-  if (nbr <= g_sep.cap) return 0;
-  if (g_sep.buf) {
-    const int rc = ndsmk_free(g_sep.buf);      // (drains the streams first)
-    g_sep.buf = nullptr;
-    g_sep.cap = 0;
-    if (rc != 0) return rc;
-  }
-  void *q = nullptr;
-  const int rc = ndsmk_alloc(&q, sizeof(double) * (1 + 4 * nbr));
-  if (rc != 0) return rc;
-  g_sep.buf = (double *)q;
-  g_sep.cap = nbr;
-  return 0;
-}
+// (the leading slot is the flag of the check)
+void sep_release();
+LineScratch g_sep = {1, sep_release};
+void sep_release() { g_sep.release(); }
 
 const char *kSepUsage = "separators: step > 0 (finite), max_steps >= 1, radius > 0 (finite), capture > 0 (finite), "
                         "rounds >= 1, tol >= 0 (finite), every >= 1, max_points >= 0, nnulls >= 0, nbr >= 0 and every "
@@ -386,10 +357,10 @@ extern "C" int ndsmk_sep_count(const double *B, const int32_t *n3, const double 
                     rho, cap2);
   if (rc != 0 || nbr == 0) return rc;
   const size_t nb = (size_t)nbr;
-  rc = sep_grow(nb);
+  rc = g_sep.grow(nb);
   if (rc != 0) return rc;
   int32_t *flag = (int32_t *)g_sep.buf;
-  double *seeds = g_sep.buf + 1, *sgns = g_sep.buf + 1 + 3 * nb;
+  double *seeds = g_sep.seeds(), *sgns = g_sep.sgns(nb);
   hipStream_t s = ndsm::stream();
   // no pair index is used before all of them are known to be in range
   int32_t bad = 0;
@@ -408,11 +379,9 @@ extern "C" int ndsmk_sep_count(const double *B, const int32_t *n3, const double 
   hipLaunchKernelGGL(sep_line_k<false>, dim3((unsigned)((nb + kLineBlock - 1) / kLineBlock)), dim3(kLineBlock), 0, s, B,
                      seeds, sgns, pos, pair, cap2, (const i64 *)nullptr, (i64)every, (i64)max_points, o, p);
   NDSM_LAUNCH_CHECK();
-  hipLaunchKernelGGL(scan64_k, dim3(1), dim3(kScanBlock), 0, s, (i64 *)offsets, nb);
-  NDSM_LAUNCH_CHECK();
-  NDSM_HIP(hipMemcpyAsync(h_total, offsets + nb, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  NDSM_HIP(hipStreamSynchronize(s));
-  g_sep.nbr = nb;
+  rc = scan64_total(offsets, nb, h_total, s);
+  if (rc != 0) return rc;
+  g_sep.lanes = nb;
   return 0;
 }
 
@@ -429,8 +398,8 @@ extern "C" int ndsmk_sep_fill(const double *B, const int32_t *n3, const double *
   if (rc != 0 || nbr == 0 || max_points == 0) return rc;
   const size_t nb = (size_t)nbr;
   // (the seeds and directions are those the counting half of this call left in the scratch; it checked the pairs)
-  NDSM_CHECK_ARG(g_sep.buf && g_sep.nbr == nb);
-  const double *seeds = g_sep.buf + 1, *sgns = g_sep.buf + 1 + 3 * nb;
+  NDSM_CHECK_ARG(g_sep.buf && g_sep.lanes == nb);
+  const double *seeds = g_sep.seeds(), *sgns = g_sep.sgns(nb);
   const SepLineOut o = {nullptr, nullptr, nullptr, nullptr, nullptr, points, bpt};
   hipStream_t s = ndsm::stream();
   hipLaunchKernelGGL(sep_line_k<true>, dim3((unsigned)((nb + kLineBlock - 1) / kLineBlock)), dim3(kLineBlock), 0, s, B,

@@ -11,13 +11,15 @@
 //   count   skel_line_k<0>   one lane per line, one wave per workgroup, as trace_k: trace_step.hpp's stage and step
 //                            with the lane's own direction, the capture test after every accepted full step; ends,
 //                            length, status, nsteps, hit, and offsets[l] = npts(l)
-//           scan64_k         in place, as paths.hip
+//           scan64_total     scan64.hpp: the scan in place and the total, as paths.hip
 //   fill    skel_line_k<1>   the same loop - the same expressions, so the same bits - which stores the points as
 //                            paths_k does: point j of line l goes to slot offsets[l] + j
+// The seeds and directions pass from the counting to the filling half in g_skel, a line_scratch.hpp LineScratch.
 // A lane writes slot offsets[l] + j only for j < min(offsets[l + 1], max_points) - offsets[l].  No atomic append, no
 // guessed capacity, no vector indexed with a run-time axis.  In the capture loop every lane reads the same null
 // positions in the same order: plain global loads at a lane-independent address, served by the caches (DESIGN.md
 // says why they are not staged in LDS).
+#include "line_scratch.hpp"
 #include "scan64.hpp"
 #include "trace_step.hpp"
 
@@ -332,41 +334,9 @@ __global__ __launch_bounds__(kLineBlock) void skel_line_k(const double *__restri
   }
 }
 
-// scratch of the call, kept between calls and grown on demand (no result depends on its size): the seeds (3 doubles)
-// and the direction (1 double) of every lane, written by the counting half and read again by the filling half
-struct SkelScratch {
-  double *buf = nullptr;
-  size_t cap = 0;              // lanes the buffer holds
-  size_t nl = 0;               // lanes the last counting half wrote
-  bool registered = false;     // skel_release is queued for the next reset
-};
-SkelScratch g_skel;
-
-void skel_release() {
-  if (g_skel.buf) (void)hipFree(g_skel.buf);
-  g_skel = SkelScratch();
-}
-
-int skel_grow(size_t nl) {
-  if (!g_skel.registered) {
-    ndsm::at_reset(skel_release);
-    g_skel.registered = true;
-  }
-  g_skel.nl = 0;
-  if (nl <= g_skel.cap) return 0;
-  if (g_skel.buf) {
-    const int rc = ndsmk_free(g_skel.buf);      // (drains the streams first)
-    g_skel.buf = nullptr;
-    g_skel.cap = 0;
-    if (rc != 0) return rc;
-  }
-  void *q = nullptr;
-  const int rc = ndsmk_alloc(&q, 4 * sizeof(double) * nl);
-  if (rc != 0) return rc;
-  g_skel.buf = (double *)q;
-  g_skel.cap = nl;
-  return 0;
-}
+void skel_release();
+LineScratch g_skel = {0, skel_release};
+void skel_release() { g_skel.release(); }
 
 const char *kSkelUsage = "skeleton: step > 0 (finite), max_steps >= 1, radius > 0 (finite), capture >= 0 (finite), "
                          "every >= 1, max_points >= 0, nring >= 0 and nnulls >= 0";
@@ -409,9 +379,9 @@ extern "C" int ndsmk_skel_count(const double *B, const int32_t *n3, const double
   if (rc != 0 || nnulls == 0) return rc;
   const size_t L = 2 + (size_t)nring;
   const size_t nl = (size_t)nnulls * L;
-  rc = skel_grow(nl);
+  rc = g_skel.grow(nl);
   if (rc != 0) return rc;
-  double *seeds = g_skel.buf, *sgns = g_skel.buf + 3 * nl;
+  double *seeds = g_skel.seeds(), *sgns = g_skel.sgns(nl);
   hipStream_t s = ndsm::stream();
   const SkelTypeOut to = {kind, eig, spine, normal, seeds, sgns};
   hipLaunchKernelGGL(skel_type_k, dim3((unsigned)((nnulls + kTypeBlock - 1) / kTypeBlock)), dim3(kTypeBlock), 0, s, pos,
@@ -421,11 +391,9 @@ extern "C" int ndsmk_skel_count(const double *B, const int32_t *n3, const double
   hipLaunchKernelGGL(skel_line_k<false>, dim3((unsigned)((nl + kLineBlock - 1) / kLineBlock)), dim3(kLineBlock), 0, s, B,
                      seeds, sgns, pos, L, cap2, (const i64 *)nullptr, (i64)every, (i64)max_points, o, p);
   NDSM_LAUNCH_CHECK();
-  hipLaunchKernelGGL(scan64_k, dim3(1), dim3(kScanBlock), 0, s, (i64 *)offsets, nl);
-  NDSM_LAUNCH_CHECK();
-  NDSM_HIP(hipMemcpyAsync(h_total, offsets + nl, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  NDSM_HIP(hipStreamSynchronize(s));
-  g_skel.nl = nl;
+  rc = scan64_total(offsets, nl, h_total, s);
+  if (rc != 0) return rc;
+  g_skel.lanes = nl;
   return 0;
 }
 
@@ -443,8 +411,8 @@ extern "C" int ndsmk_skel_fill(const double *B, const int32_t *n3, const double 
   const size_t L = 2 + (size_t)nring;
   const size_t nl = (size_t)nnulls * L;
   // (the seeds and directions are those the counting half of this call left in the scratch)
-  NDSM_CHECK_ARG(g_skel.buf && g_skel.nl == nl);
-  const double *seeds = g_skel.buf, *sgns = g_skel.buf + 3 * nl;
+  NDSM_CHECK_ARG(g_skel.buf && g_skel.lanes == nl);
+  const double *seeds = g_skel.seeds(), *sgns = g_skel.sgns(nl);
   const SkelLineOut o = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, points, bpt};
   hipStream_t s = ndsm::stream();
   hipLaunchKernelGGL(skel_line_k<true>, dim3((unsigned)((nl + kLineBlock - 1) / kLineBlock)), dim3(kLineBlock), 0, s, B,

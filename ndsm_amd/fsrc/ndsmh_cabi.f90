@@ -65,6 +65,16 @@ module ndsmh_cabi
     end function
   end interface
 
+  interface
+    function c_memset(p, c, n) bind(c, name="memset") result(q)
+      import :: c_ptr, c_int, c_size_t
+      type(c_ptr), value :: p
+      integer(c_int), value :: c
+      integer(c_size_t), value :: n
+      type(c_ptr) :: q
+    end function
+  end interface
+
 contains
 
   ! wall clock in seconds (the reference uses OMP_GET_WTIME, ndsm_root.f90:521-536)
@@ -970,6 +980,46 @@ contains
                                dintegral, dstatus, dnsteps, .true., "ndsm_hip_vecpot_squash_device")
   end function
 
+  ! ---- shared by the handle entries of the line and null calls below ----------
+  ! the prologue: the runtime is up (without a device: 9001, whatever the arguments), and handle is that of a live
+  ! context, which comes back in ctx; else 9002
+  function live_ctx(handle, ctx) result(rc)
+    type(c_ptr), intent(in) :: handle
+    type(vecpot_ctx), pointer, intent(out) :: ctx
+    integer(c_int) :: rc
+    nullify (ctx)
+    rc = ndsmk_init(-1_c_int)
+    if (rc /= 0) return
+    rc = NDSMK_EARG
+    if (.not. c_associated(handle)) return
+    call c_f_pointer(handle, ctx)
+    if (ctx%live) rc = 0
+  end function
+
+  ! the epilogue: an error of the driver is reported and comes back as 9001 at least
+  function reported(who, rc) result(ierr)
+    character(len=*), intent(in) :: who
+    integer(c_int), intent(in) :: rc
+    integer(c_int) :: ierr
+    ierr = rc
+    if (rc == 0) return
+    call report(who, rc)
+    if (ierr < NDSMK_ENODEV) ierr = NDSMK_ENODEV
+  end function
+
+  ! zeroes on the host: count entries of width bytes at every p that is not NULL
+  subroutine clear_host(p, width, count)
+    type(c_ptr), intent(in) :: p(:)
+    integer, intent(in) :: width(:)
+    integer(c_int64_t), intent(in) :: count(:)
+    type(c_ptr) :: q
+    integer :: i
+    do i = 1, size(p)
+      if (c_associated(p(i)) .and. count(i) > 0) &
+        q = c_memset(p(i), 0_c_int, int(int(width(i), c_int64_t) * count(i), c_size_t))
+    end do
+  end subroutine
+
   ! the four line entries above: squash false, sel = direction, q = c_null_ptr for trace; squash true, sel = integrand
   ! for squash.  nl lines: 2 nseeds for squash and for both directions, else nseeds.
   function vecpot_handle_lines(handle, squash, B, G, sel, nseeds, seeds, step, max_steps, q, ends, length, integral, &
@@ -981,53 +1031,25 @@ contains
     character(len=*), intent(in) :: who
     integer(c_int) :: ierr
     type(vecpot_ctx), pointer :: ctx
-    integer(c_int) :: rc
-    logical :: need
     if (.not. on_device) call clear_outputs()
-    ierr = ndsmk_init(-1_c_int)                        ! without a device: 9001, whatever the arguments
+    ierr = live_ctx(handle, ctx)
     if (ierr /= 0) return
     ierr = NDSMK_EARG
-    if (.not. c_associated(handle)) return
-    need = nseeds > 0                                  ! no seeds: no array is looked at
-    if (need .and. .not. (c_associated(B) .and. c_associated(seeds) .and. (c_associated(q) .or. .not. squash) .and. &
-                          c_associated(ends) .and. c_associated(length) .and. c_associated(integral) .and. &
-                          c_associated(status) .and. c_associated(nsteps))) return
-    call c_f_pointer(handle, ctx)
-    if (.not. ctx%live) return
-    rc = vecpot_lines(ctx, squash, B, G, sel, nseeds, seeds, step, max_steps, q, ends, length, integral, status, &
-                      nsteps, on_device)
-    if (rc /= 0) then
-      call report(who, rc)
-      if (rc < NDSMK_ENODEV) rc = NDSMK_ENODEV
-      if (.not. on_device) call clear_outputs()
-    end if
-    ierr = rc
+    ! no seeds: no array is looked at
+    if (nseeds > 0 .and. .not. (c_associated(B) .and. c_associated(seeds) .and. (c_associated(q) .or. .not. squash) .and. &
+                                c_associated(ends) .and. c_associated(length) .and. c_associated(integral) .and. &
+                                c_associated(status) .and. c_associated(nsteps))) return
+    ierr = reported(who, vecpot_lines(ctx, squash, B, G, sel, nseeds, seeds, step, max_steps, q, ends, length, integral, &
+                                      status, nsteps, on_device))
+    if (ierr /= 0 .and. .not. on_device) call clear_outputs()
   contains
     subroutine clear_outputs()
-      real(c_double), pointer :: r(:)
-      integer(c_int32_t), pointer :: k(:)
-      integer :: nl
+      integer(c_int64_t) :: ns, nl
       if (nseeds <= 0) return
       if (nseeds > huge(0) / 6) return
-      nl = nseeds * merge(2, 1, squash .or. sel == 0)
-      if (c_associated(q)) then
-        call c_f_pointer(q, r, [nseeds]); r = 0
-      end if
-      if (c_associated(ends)) then
-        call c_f_pointer(ends, r, [3 * nl]); r = 0
-      end if
-      if (c_associated(length)) then
-        call c_f_pointer(length, r, [nl]); r = 0
-      end if
-      if (c_associated(integral)) then
-        call c_f_pointer(integral, r, [nl]); r = 0
-      end if
-      if (c_associated(status)) then
-        call c_f_pointer(status, k, [nl]); k = 0
-      end if
-      if (c_associated(nsteps)) then
-        call c_f_pointer(nsteps, k, [nl]); k = 0
-      end if
+      ns = nseeds
+      nl = ns * merge(2, 1, squash .or. sel == 0)
+      call clear_host([q, ends, length, integral, status, nsteps], [8, 24, 8, 8, 4, 4], [ns, nl, nl, nl, nl, nl])
     end subroutine
   end function
 
@@ -1088,10 +1110,10 @@ contains
       integer(c_int) :: rc
       type(vecpot_ctx), pointer :: ctx
       integer(c_int64_t), pointer :: tot
-      rc = ndsmk_init(-1_c_int)                        ! without a device: 9001, whatever the arguments
+      rc = live_ctx(handle, ctx)
       if (rc /= 0) return
       rc = NDSMK_EARG
-      if (.not. (c_associated(handle) .and. c_associated(total))) return
+      if (.not. c_associated(total)) return
       call c_f_pointer(total, tot)
       tot = 0
       ! no seeds: no array is looked at; the scalars are the kernel layer's to judge (9004) once the arrays are there
@@ -1101,61 +1123,26 @@ contains
                    c_associated(offsets))) return
         if (max_points > 0 .and. .not. c_associated(points)) return
       end if
-      call c_f_pointer(handle, ctx)
-      if (.not. ctx%live) return
-      rc = vecpot_paths(ctx, B, G, direction, nseeds, seeds, step, max_steps, every, max_points, ends, length, &
-                        integral, status, nsteps, offsets, tot, points, bpt, gpt, ipt, on_device)
-      if (rc /= 0) then
-        call report(who, rc)
-        if (rc < NDSMK_ENODEV) rc = NDSMK_ENODEV
-      end if
+      rc = reported(who, vecpot_paths(ctx, B, G, direction, nseeds, seeds, step, max_steps, every, max_points, ends, &
+                                      length, integral, status, nsteps, offsets, tot, points, bpt, gpt, ipt, on_device))
     end function
 
     ! total, and (host entry) the nl entries of the trace outputs, the nl + 1 of offsets and the max_points slots of
     ! every point array that is there
     subroutine clear_outputs()
-      real(c_double), pointer :: r(:)
-      integer(c_int32_t), pointer :: k(:)
-      integer(c_int64_t), pointer :: k8(:)
-      integer :: nl
-      if (c_associated(total)) then
-        call c_f_pointer(total, k8, [1]); k8 = 0
-      end if
+      integer(c_int64_t) :: nl, np
+      call clear_host([total], [8], [1_c_int64_t])
       if (on_device) return
+      ! (no lines: no line array is touched)
       if (nseeds > 0 .and. nseeds <= huge(0) / 6) then
-        nl = nseeds * merge(2, 1, direction == 0)
-        if (c_associated(ends)) then
-          call c_f_pointer(ends, r, [3 * nl]); r = 0
-        end if
-        if (c_associated(length)) then
-          call c_f_pointer(length, r, [nl]); r = 0
-        end if
-        if (c_associated(integral)) then
-          call c_f_pointer(integral, r, [nl]); r = 0
-        end if
-        if (c_associated(status)) then
-          call c_f_pointer(status, k, [nl]); k = 0
-        end if
-        if (c_associated(nsteps)) then
-          call c_f_pointer(nsteps, k, [nl]); k = 0
-        end if
-        if (c_associated(offsets)) then
-          call c_f_pointer(offsets, k8, [nl + 1]); k8 = 0
-        end if
+        nl = int(nseeds, c_int64_t) * merge(2, 1, direction == 0)
+        call clear_host([ends, length, integral, status, nsteps, offsets], [24, 8, 8, 4, 4, 8], &
+                        [nl, nl, nl, nl, nl, nl + 1])
       end if
+      ! (no capacity: no point array is touched)
       if (max_points <= 0 .or. max_points > huge(0_c_int64_t) / 3) return
-      if (c_associated(points)) then
-        call c_f_pointer(points, r, [3 * max_points]); r = 0
-      end if
-      if (c_associated(bpt)) then
-        call c_f_pointer(bpt, r, [3 * max_points]); r = 0
-      end if
-      if (c_associated(gpt)) then
-        call c_f_pointer(gpt, r, [3 * max_points]); r = 0
-      end if
-      if (c_associated(ipt)) then
-        call c_f_pointer(ipt, r, [max_points]); r = 0
-      end if
+      np = max_points
+      call clear_host([points, bpt, gpt, ipt], [24, 24, 24, 8], [np, np, np, np])
     end subroutine
   end function
 
@@ -1217,10 +1204,10 @@ contains
       integer(c_int) :: rc
       type(vecpot_ctx), pointer :: ctx
       integer(c_int64_t), pointer :: tot
-      rc = ndsmk_init(-1_c_int)                        ! without a device: 9001, whatever the arguments
+      rc = live_ctx(handle, ctx)
       if (rc /= 0) return
       rc = NDSMK_EARG
-      if (.not. (c_associated(handle) .and. c_associated(total))) return
+      if (.not. c_associated(total)) return
       call c_f_pointer(total, tot)
       tot = 0
       ! no nulls: no array is looked at; the scalars are the kernel layer's to judge (9004) once the arrays are there
@@ -1232,71 +1219,29 @@ contains
         if (nring > 0 .and. .not. c_associated(ring)) return
         if (max_points > 0 .and. .not. c_associated(points)) return
       end if
-      call c_f_pointer(handle, ctx)
-      if (.not. ctx%live) return
-      rc = vecpot_skeleton(ctx, B, nnulls, pos, jac, nring, ring, radius, capture, step, max_steps, every, max_points, &
-                           kind, eig, spine, normal, ends, length, status, nsteps, hit, offsets, tot, points, bpt, &
-                           on_device)
-      if (rc /= 0) then
-        call report(who, rc)
-        if (rc < NDSMK_ENODEV) rc = NDSMK_ENODEV
-      end if
+      rc = reported(who, vecpot_skeleton(ctx, B, nnulls, pos, jac, nring, ring, radius, capture, step, max_steps, every, &
+                                         max_points, kind, eig, spine, normal, ends, length, status, nsteps, hit, &
+                                         offsets, tot, points, bpt, on_device))
     end function
 
     ! total, and (host entry) the nnulls entries of the per-null outputs, the nl entries of the per-line outputs, the
     ! nl + 1 of offsets and the max_points slots of every point array that is there
     subroutine clear_outputs()
-      real(c_double), pointer :: r(:)
-      integer(c_int32_t), pointer :: k(:)
-      integer(c_int64_t), pointer :: k8(:)
-      integer(c_int64_t) :: nl8
-      integer :: nl
-      if (c_associated(total)) then
-        call c_f_pointer(total, k8, [1]); k8 = 0
-      end if
+      integer(c_int64_t) :: nm, nl, np
+      call clear_host([total], [8], [1_c_int64_t])
       if (on_device) return
-      nl8 = 0
-      if (nnulls > 0 .and. nring >= 0) nl8 = int(nnulls, c_int64_t) * (2_c_int64_t + int(nring, c_int64_t))
-      if (nl8 > 0 .and. nl8 <= huge(0) / 3) then
-        nl = int(nl8)
-        if (c_associated(kind)) then
-          call c_f_pointer(kind, k, [nnulls]); k = 0
-        end if
-        if (c_associated(eig)) then
-          call c_f_pointer(eig, r, [3 * nnulls]); r = 0
-        end if
-        if (c_associated(spine)) then
-          call c_f_pointer(spine, r, [3 * nnulls]); r = 0
-        end if
-        if (c_associated(normal)) then
-          call c_f_pointer(normal, r, [3 * nnulls]); r = 0
-        end if
-        if (c_associated(ends)) then
-          call c_f_pointer(ends, r, [3 * nl]); r = 0
-        end if
-        if (c_associated(length)) then
-          call c_f_pointer(length, r, [nl]); r = 0
-        end if
-        if (c_associated(status)) then
-          call c_f_pointer(status, k, [nl]); k = 0
-        end if
-        if (c_associated(nsteps)) then
-          call c_f_pointer(nsteps, k, [nl]); k = 0
-        end if
-        if (c_associated(hit)) then
-          call c_f_pointer(hit, k, [nl]); k = 0
-        end if
-        if (c_associated(offsets)) then
-          call c_f_pointer(offsets, k8, [nl + 1]); k8 = 0
-        end if
+      nl = 0
+      if (nnulls > 0 .and. nring >= 0) nl = int(nnulls, c_int64_t) * (2_c_int64_t + int(nring, c_int64_t))
+      ! (no lines: no line array is touched)
+      if (nl > 0 .and. nl <= huge(0) / 3) then
+        nm = nnulls
+        call clear_host([kind, eig, spine, normal, ends, length, status, nsteps, hit, offsets], &
+                        [4, 24, 24, 24, 24, 8, 4, 4, 4, 8], [nm, nm, nm, nm, nl, nl, nl, nl, nl, nl + 1])
       end if
+      ! (no capacity: no point array is touched)
       if (max_points <= 0 .or. max_points > huge(0_c_int64_t) / 3) return
-      if (c_associated(points)) then
-        call c_f_pointer(points, r, [3 * max_points]); r = 0
-      end if
-      if (c_associated(bpt)) then
-        call c_f_pointer(bpt, r, [3 * max_points]); r = 0
-      end if
+      np = max_points
+      call clear_host([points, bpt], [24, 24], [np, np])
     end subroutine
   end function
 
@@ -1363,10 +1308,10 @@ contains
       integer(c_int) :: rc
       type(vecpot_ctx), pointer :: ctx
       integer(c_int64_t), pointer :: tot
-      rc = ndsmk_init(-1_c_int)                        ! without a device: 9001, whatever the arguments
+      rc = live_ctx(handle, ctx)
       if (rc /= 0) return
       rc = NDSMK_EARG
-      if (.not. (c_associated(handle) .and. c_associated(total))) return
+      if (.not. c_associated(total)) return
       call c_f_pointer(total, tot)
       tot = 0
       ! no brackets: no array is looked at; the scalars are the kernel layer's to judge (9004) once the arrays are there
@@ -1378,52 +1323,27 @@ contains
                    c_associated(status) .and. c_associated(nsteps) .and. c_associated(offsets))) return
         if (max_points > 0 .and. .not. c_associated(points)) return
       end if
-      call c_f_pointer(handle, ctx)
-      if (.not. ctx%live) return
-      rc = vecpot_separators(ctx, B, nnulls, pos, kind, normal, nbr, pair, arc, radius, capture, step, max_steps, rounds, &
-                             tol, every, max_points, state, nrounds, coef, width, side, dmin, ends, length, status, nsteps, &
-                             offsets, tot, points, bpt, on_device)
-      if (rc /= 0) then
-        call report(who, rc)
-        if (rc < NDSMK_ENODEV) rc = NDSMK_ENODEV
-      end if
+      rc = reported(who, vecpot_separators(ctx, B, nnulls, pos, kind, normal, nbr, pair, arc, radius, capture, step, &
+                                           max_steps, rounds, tol, every, max_points, state, nrounds, coef, width, side, &
+                                           dmin, ends, length, status, nsteps, offsets, tot, points, bpt, on_device))
     end function
 
     ! total, and (host entry) the nbr entries of the per-bracket outputs, the nbr + 1 of offsets and the max_points
     ! slots of every point array that is there
     subroutine clear_outputs()
-      real(c_double), pointer :: r(:)
-      integer(c_int32_t), pointer :: k(:)
-      integer(c_int64_t), pointer :: k8(:)
-      type(c_ptr) :: pr(5), pk(5)
-      integer :: i
-      integer, parameter :: per(5) = [4, 1, 2, 3, 1]
-      if (c_associated(total)) then
-        call c_f_pointer(total, k8, [1]); k8 = 0
-      end if
+      integer(c_int64_t) :: nq, np
+      call clear_host([total], [8], [1_c_int64_t])
       if (on_device) return
+      ! (no lines: no line array is touched)
       if (nbr > 0 .and. nbr <= huge(0) / 4) then
-        pr = [coef, width, dmin, ends, length]
-        pk = [state, nrounds, side, status, nsteps]
-        do i = 1, 5
-          if (c_associated(pr(i))) then
-            call c_f_pointer(pr(i), r, [per(i) * nbr]); r = 0
-          end if
-          if (c_associated(pk(i))) then
-            call c_f_pointer(pk(i), k, [nbr]); k = 0
-          end if
-        end do
-        if (c_associated(offsets)) then
-          call c_f_pointer(offsets, k8, [nbr + 1]); k8 = 0
-        end if
+        nq = nbr
+        call clear_host([state, nrounds, coef, width, side, dmin, ends, length, status, nsteps, offsets], &
+                        [4, 4, 32, 8, 4, 16, 24, 8, 4, 4, 8], [nq, nq, nq, nq, nq, nq, nq, nq, nq, nq, nq + 1])
       end if
+      ! (no capacity: no point array is touched)
       if (max_points <= 0 .or. max_points > huge(0_c_int64_t) / 3) return
-      if (c_associated(points)) then
-        call c_f_pointer(points, r, [3 * max_points]); r = 0
-      end if
-      if (c_associated(bpt)) then
-        call c_f_pointer(bpt, r, [3 * max_points]); r = 0
-      end if
+      np = max_points
+      call clear_host([points, bpt], [24, 24], [np, np])
     end subroutine
   end function
 
@@ -1464,57 +1384,26 @@ contains
     integer(c_int) :: ierr
     type(vecpot_ctx), pointer :: ctx
     integer(c_int64_t), pointer :: cnt(:)
-    integer(c_int) :: rc
     call clear_outputs()
-    ierr = ndsmk_init(-1_c_int)                        ! without a device: 9001, whatever the arguments
+    ierr = live_ctx(handle, ctx)
     if (ierr /= 0) return
     ierr = NDSMK_EARG
-    if (.not. (c_associated(handle) .and. c_associated(B) .and. c_associated(counts))) return
+    if (.not. (c_associated(B) .and. c_associated(counts))) return
     if (max_nulls > 0 .and. .not. (c_associated(cell) .and. c_associated(pos) .and. c_associated(jac) .and. &
                                    c_associated(det) .and. c_associated(resid) .and. c_associated(sign) .and. &
                                    c_associated(iters))) return
-    call c_f_pointer(handle, ctx)
-    if (.not. ctx%live) return
     call c_f_pointer(counts, cnt, [2])
-    rc = vecpot_nulls(ctx, B, max_nulls, cnt, cell, pos, jac, det, resid, sign, iters, on_device)
-    if (rc /= 0) then
-      call report(who, rc)
-      if (rc < NDSMK_ENODEV) rc = NDSMK_ENODEV
-      call clear_outputs()
-    end if
-    ierr = rc
+    ierr = reported(who, vecpot_nulls(ctx, B, max_nulls, cnt, cell, pos, jac, det, resid, sign, iters, on_device))
+    if (ierr /= 0) call clear_outputs()
   contains
     ! counts, and (host entry) the max_nulls slots of every record array
     subroutine clear_outputs()
-      real(c_double), pointer :: r(:)
-      integer(c_int32_t), pointer :: k(:)
-      integer(c_int64_t), pointer :: k8(:)
-      if (c_associated(counts)) then
-        call c_f_pointer(counts, k8, [2]); k8 = 0
-      end if
+      integer(c_int64_t) :: nm
+      call clear_host([counts], [8], [2_c_int64_t])
       if (on_device .or. max_nulls <= 0) return
       if (max_nulls > huge(0) / 9) return
-      if (c_associated(cell)) then
-        call c_f_pointer(cell, k8, [max_nulls]); k8 = 0
-      end if
-      if (c_associated(pos)) then
-        call c_f_pointer(pos, r, [3 * max_nulls]); r = 0
-      end if
-      if (c_associated(jac)) then
-        call c_f_pointer(jac, r, [9 * max_nulls]); r = 0
-      end if
-      if (c_associated(det)) then
-        call c_f_pointer(det, r, [max_nulls]); r = 0
-      end if
-      if (c_associated(resid)) then
-        call c_f_pointer(resid, r, [max_nulls]); r = 0
-      end if
-      if (c_associated(sign)) then
-        call c_f_pointer(sign, k, [max_nulls]); k = 0
-      end if
-      if (c_associated(iters)) then
-        call c_f_pointer(iters, k, [max_nulls]); k = 0
-      end if
+      nm = max_nulls
+      call clear_host([cell, pos, jac, det, resid, sign, iters], [8, 24, 72, 8, 8, 4, 4], [nm, nm, nm, nm, nm, nm, nm])
     end subroutine
   end function
 

@@ -101,6 +101,15 @@ module ndsmh_vecpot
     integer(ik) :: foff(6) = 0, ftotal = 0
   end type
 
+  ! one array of a host-array line entry in its staging buffer (carve, fetch)
+  type :: slice
+    type(c_ptr) :: host                     ! the caller's array; c_null_ptr: absent, dev stays c_null_ptr
+    integer(c_size_t) :: width, count       ! bytes per entry, entries
+    logical :: home                         ! COMES_HOME: an output; GOES_UP: an input
+    type(c_ptr) :: dev = c_null_ptr         ! its place on the device
+  end type
+  logical, parameter :: GOES_UP = .false., COMES_HOME = .true.
+
   type(vecpot_ctx), save, target :: cache
   logical, save :: cache_busy = .false.     ! ndsm_vector_solve is running on the cached context
 
@@ -1043,6 +1052,95 @@ contains
   end function
 
   ! ------------------------------------------------------------------
+  ! Staging of the host-array line entries below.  Each of them names its arrays once, as a list of slices in the order
+  ! of the kernel entry's arguments; carve gives every slice its place in one device buffer and sends the inputs up,
+  ! fetch brings the outputs home, unstage frees.
+  ! ------------------------------------------------------------------
+
+  ! first point, spacing and shape of the context's mesh (dq as in vecpot_run)
+  subroutine ctx_mesh(ctx, n3, lo, dq)
+    type(vecpot_ctx), intent(in) :: ctx
+    integer(c_int32_t), intent(out) :: n3(3)
+    real(wp), intent(out) :: lo(3), dq(3)
+    n3 = ctx%n3
+    dq = [ctx%qx(2) - ctx%qx(1), ctx%qy(2) - ctx%qy(1), ctx%qz(2) - ctx%qz(1)]
+    lo = [ctx%qx(1), ctx%qy(1), ctx%qz(1)]
+  end subroutine
+
+  ! the helicity entries' staging array dF(i), allocated at the first use; host (nx,ny,nz,3) goes up into it
+  ! (c_null_ptr: nothing goes up)
+  function stage_field(ctx, i, host) result(rc)
+    type(vecpot_ctx), intent(inout) :: ctx
+    integer, intent(in) :: i
+    type(c_ptr), intent(in) :: host
+    integer(c_int) :: rc
+    integer(c_size_t) :: nb
+    rc = 0
+    nb = int(product(int(ctx%n3, ik)), c_size_t) * 24_c_size_t
+    if (.not. c_associated(ctx%dF(i))) rc = ndsmk_alloc(ctx%dF(i), nb)
+    if (rc == 0 .and. c_associated(host)) rc = ndsmk_h2d(ctx%dF(i), host, nb)
+  end function
+
+  ! buf: one device buffer of all slices of s that have a host array and a count > 0, each rounded up to a whole number
+  ! of 8-byte words (so any order of the slices keeps 8-byte data aligned); the others get c_null_ptr.  The inputs go
+  ! up.  Nothing to hold: no buffer.  On an error of a copy the buffer stays allocated for unstage.
+  function carve(buf, s) result(rc)
+    type(c_ptr), intent(out) :: buf
+    type(slice), intent(inout) :: s(:)
+    integer(c_int) :: rc
+    integer(c_size_t) :: no, bytes(size(s))
+    integer :: i
+    rc = 0
+    buf = c_null_ptr
+    do i = 1, size(s)
+      s(i)%dev = c_null_ptr
+      bytes(i) = 0
+      if (c_associated(s(i)%host)) bytes(i) = (s(i)%width * s(i)%count + 7_c_size_t) / 8_c_size_t * 8_c_size_t
+    end do
+    if (sum(bytes) == 0) return
+    rc = ndsmk_alloc(buf, sum(bytes)); if (rc /= 0) return
+    no = 0
+    do i = 1, size(s)
+      if (bytes(i) == 0) cycle
+      s(i)%dev = dptr_offset(buf, no)
+      no = no + bytes(i)
+      if (rc == 0 .and. .not. s(i)%home) rc = ndsmk_h2d(s(i)%dev, s(i)%host, s(i)%width * s(i)%count)
+    end do
+  end function
+
+  ! the outputs among the slices of s come home (rows given: that many entries of each instead of its count)
+  function fetch(s, rows) result(rc)
+    type(slice), intent(in) :: s(:)
+    integer(c_size_t), intent(in), optional :: rows
+    integer(c_int) :: rc
+    integer(c_size_t) :: n
+    integer :: i
+    rc = 0
+    do i = 1, size(s)
+      n = s(i)%count
+      if (present(rows)) n = rows
+      if (rc == 0 .and. s(i)%home .and. c_associated(s(i)%dev) .and. n > 0) &
+        rc = ndsmk_d2h(s(i)%host, s(i)%dev, s(i)%width * n)
+    end do
+  end function
+
+  ! the buffers of carve are freed in the order given; the first error wins, and any error zeroes total
+  subroutine unstage(rc, bufs, total)
+    integer(c_int), intent(inout) :: rc
+    type(c_ptr), intent(in) :: bufs(:)
+    integer(c_int64_t), intent(inout), optional :: total
+    integer(c_int) :: rc_free
+    integer :: i
+    do i = 1, size(bufs)
+      if (c_associated(bufs(i))) then
+        rc_free = ndsmk_free(bufs(i))
+        if (rc == 0) rc = rc_free
+      end if
+    end do
+    if (present(total) .and. rc /= 0) total = 0
+  end subroutine
+
+  ! ------------------------------------------------------------------
   ! The line entries on a prepared context (semantics in include/ndsm_hip.h): field lines of B from nseeds seeds with
   ! the line integral of G along them (squash false: ndsmk_trace, sel = direction; DESIGN.md "Field-line tracing and
   ! field-line helicity"), or the squashing factor Q at the seeds with the two ends of the line through each (squash
@@ -1061,17 +1159,15 @@ contains
     type(c_ptr), intent(in) :: pB, pG, pseeds, pq, pends, plen, pint, pstat, pnst
     integer(c_int), intent(in) :: sel, nseeds, max_steps
     real(wp), intent(in) :: step
-    integer(c_int) :: rc, rc2
+    integer(c_int) :: rc, rc_free
     real(wp) :: dq(3), lo(3)
     integer(c_int32_t) :: n3(3)
-    integer(c_size_t) :: nb, nl, ns
-    integer :: i
-    logical :: own_curl, need(2)
-    type(c_ptr) :: dB, dG, d(7)
+    integer(c_size_t) :: nl, ns
+    logical :: own_curl
+    type(c_ptr) :: dB, dG, buf
+    type(slice) :: s(7)
 
-    n3 = ctx%n3
-    dq = [ctx%qx(2) - ctx%qx(1), ctx%qy(2) - ctx%qy(1), ctx%qz(2) - ctx%qz(1)]      ! as vecpot_run
-    lo = [ctx%qx(1), ctx%qy(1), ctx%qz(1)]
+    call ctx_mesh(ctx, n3, lo, dq)
     if (nseeds <= 0 .or. step <= 0.0_wp .or. max_steps < 1 .or. sel < merge(0, -1, squash) .or. sel > 1) then
       ! (the argument errors are the kernel entry's to name; nothing is staged for them)
       rc = launch(pB, pG, pseeds, pq, pends, plen, pint, pstat, pnst)
@@ -1080,31 +1176,23 @@ contains
       if (rc == 0 .and. .not. squash) rc = ndsmk_sync()
       return
     end if
-    nb = int(product(int(n3, ik)), c_size_t) * 24_c_size_t
     ns = int(nseeds, c_size_t)
     nl = ns * merge(2_c_size_t, 1_c_size_t, squash .or. sel == 0)
     ! G given as B itself with integrand 1: the twist map, G = curl_h B formed here in the staging array dF(2)
     own_curl = squash .and. sel == 1 .and. c_associated(pG) .and. c_associated(pG, pB)
     ! the helicity entries' host staging: dF(1) B, dF(2) G
-    need = [.not. on_device, own_curl .or. (.not. on_device .and. c_associated(pG))]
-    do i = 1, 2
-      if (need(i) .and. .not. c_associated(ctx%dF(i))) then
-        rc = ndsmk_alloc(ctx%dF(i), nb); if (rc /= 0) return
-      end if
-    end do
-    if (on_device) then
-      dB = pB
-      dG = pG
-    else
+    dB = pB
+    dG = pG
+    if (.not. on_device) then
+      rc = stage_field(ctx, 1, pB); if (rc /= 0) return
       dB = ctx%dF(1)
-      dG = c_null_ptr
-      rc = ndsmk_h2d(dB, pB, nb); if (rc /= 0) return
       if (c_associated(pG) .and. .not. own_curl) then
+        rc = stage_field(ctx, 2, pG); if (rc /= 0) return
         dG = ctx%dF(2)
-        rc = ndsmk_h2d(dG, pG, nb); if (rc /= 0) return
       end if
     end if
     if (own_curl) then
+      rc = stage_field(ctx, 2, c_null_ptr); if (rc /= 0) return
       dG = ctx%dF(2)
       call say("squashing_factor", "G = curl(B)...")
       rc = ndsmk_curl(dB, dG, n3, dq); if (rc /= 0) return
@@ -1115,34 +1203,22 @@ contains
       rc = ndsmk_sync()
       return
     end if
-    ! seeds, ends, length, integral, status, nsteps, q
-    d = c_null_ptr
-    rc = ndsmk_alloc(d(1), 24_c_size_t * ns)
-    if (rc == 0) rc = ndsmk_alloc(d(2), 24_c_size_t * nl)
-    if (rc == 0) rc = ndsmk_alloc(d(3), 8_c_size_t * nl)
-    if (rc == 0) rc = ndsmk_alloc(d(4), 8_c_size_t * nl)
-    if (rc == 0) rc = ndsmk_alloc(d(5), 4_c_size_t * nl)
-    if (rc == 0) rc = ndsmk_alloc(d(6), 4_c_size_t * nl)
-    if (rc == 0 .and. squash) rc = ndsmk_alloc(d(7), 8_c_size_t * ns)
-    if (rc == 0) rc = ndsmk_h2d(d(1), pseeds, 24_c_size_t * ns)
+    s = [slice(pseeds, 24, ns, GOES_UP), slice(merge(pq, c_null_ptr, squash), 8, ns, COMES_HOME), &
+         slice(pends, 24, nl, COMES_HOME), slice(plen, 8, nl, COMES_HOME), slice(pint, 8, nl, COMES_HOME), &
+         slice(pstat, 4, nl, COMES_HOME), slice(pnst, 4, nl, COMES_HOME)]
+    rc = carve(buf, s)
     if (rc == 0) then
       if (squash) then
         call say("squashing_factor", "Tracing field lines with their deviation vectors...")
       else
         call say("trace_field_lines", "Tracing field lines...")
       end if
-      rc = launch(dB, dG, d(1), d(7), d(2), d(3), d(4), d(5), d(6))
+      rc = launch(dB, dG, s(1)%dev, s(2)%dev, s(3)%dev, s(4)%dev, s(5)%dev, s(6)%dev, s(7)%dev)
     end if
-    if (rc == 0 .and. squash) rc = ndsmk_d2h(pq, d(7), 8_c_size_t * ns)
-    if (rc == 0) rc = ndsmk_d2h(pends, d(2), 24_c_size_t * nl)
-    if (rc == 0) rc = ndsmk_d2h(plen, d(3), 8_c_size_t * nl)
-    if (rc == 0) rc = ndsmk_d2h(pint, d(4), 8_c_size_t * nl)
-    if (rc == 0) rc = ndsmk_d2h(pstat, d(5), 4_c_size_t * nl)
-    if (rc == 0) rc = ndsmk_d2h(pnst, d(6), 4_c_size_t * nl)
+    if (rc == 0) rc = fetch(s)
     if (rc == 0) rc = ndsmk_sync()
-    do i = 1, 7
-      if (c_associated(d(i))) rc2 = ndsmk_free(d(i))
-    end do
+    rc_free = rc                                       ! (an error of the free is not returned here, unlike below)
+    call unstage(rc_free, [buf])
   contains
     ! the kernel entry of this call on the given arrays (q: looked at by squash only)
     function launch(B, G, seeds, q, ends, length, integral, status, nsteps) result(rc)
@@ -1176,20 +1252,15 @@ contains
     integer(c_int64_t), intent(in) :: max_points
     real(wp), intent(in) :: step
     integer(c_int64_t), intent(out) :: total
-    integer(c_int) :: rc, rc_free
+    integer(c_int) :: rc
     real(wp) :: dq(3), lo(3)
     integer(c_int32_t) :: n3(3)
-    integer(c_size_t) :: nb, nl, ns, np, no
-    integer :: i
-    type(c_ptr) :: dB, dG, buf, pbuf, d(7), dp(4), hp(4), hl(5)
-    ! bytes per line of ends, length, integral, status, nsteps (the seeds and offsets are sized apart), and per point
-    ! of points, bpt, gpt, ipt
-    integer(c_size_t), parameter :: lwidth(5) = [24, 8, 8, 4, 4], pwidth(4) = [24, 24, 24, 8]
+    integer(c_size_t) :: nl, ns, np
+    type(c_ptr) :: dG, buf, pbuf
+    type(slice) :: s(7), pt(4)
 
     total = 0
-    n3 = ctx%n3
-    dq = [ctx%qx(2) - ctx%qx(1), ctx%qy(2) - ctx%qy(1), ctx%qz(2) - ctx%qz(1)]      ! as vecpot_run
-    lo = [ctx%qx(1), ctx%qy(1), ctx%qz(1)]
+    call ctx_mesh(ctx, n3, lo, dq)
     if (on_device .or. nseeds <= 0 .or. step <= 0.0_wp .or. max_steps < 1 .or. sel < -1 .or. sel > 1 .or. &
         every < 1 .or. max_points < 0) then
       ! (the argument errors are the kernel entries' to name; nothing is staged for them)
@@ -1201,86 +1272,43 @@ contains
       if (rc /= 0) total = 0
       return
     end if
-    nb = int(product(int(n3, ik)), c_size_t) * 24_c_size_t
     ns = int(nseeds, c_size_t)
     nl = ns * merge(2_c_size_t, 1_c_size_t, sel == 0)
     ! the helicity entries' host staging: dF(1) B, dF(2) G
-    if (.not. c_associated(ctx%dF(1))) then
-      rc = ndsmk_alloc(ctx%dF(1), nb); if (rc /= 0) return
-    end if
-    if (c_associated(pG) .and. .not. c_associated(ctx%dF(2))) then
-      rc = ndsmk_alloc(ctx%dF(2), nb); if (rc /= 0) return
-    end if
-    dB = ctx%dF(1)
+    rc = stage_field(ctx, 1, pB); if (rc /= 0) return
     dG = c_null_ptr
-    rc = ndsmk_h2d(dB, pB, nb); if (rc /= 0) return
     if (c_associated(pG)) then
+      rc = stage_field(ctx, 2, pG); if (rc /= 0) return
       dG = ctx%dF(2)
-      rc = ndsmk_h2d(dG, pG, nb); if (rc /= 0) return
     end if
-    ! one scratch buffer of the lines: offsets and seeds (8-byte data first), then the five trace outputs
-    buf = c_null_ptr
     pbuf = c_null_ptr
-    rc = ndsmk_alloc(buf, 8_c_size_t * (nl + 1) + 24_c_size_t * ns + sum(lwidth) * nl); if (rc /= 0) return
-    d(1) = buf                                                  ! offsets
-    d(2) = dptr_offset(buf, 8_c_size_t * (nl + 1))              ! seeds
-    no = 8_c_size_t * (nl + 1) + 24_c_size_t * ns
-    do i = 1, 5
-      d(2 + i) = dptr_offset(buf, no)
-      no = no + lwidth(i) * nl
-    end do
-    rc = ndsmk_h2d(d(2), pseeds, 24_c_size_t * ns)
+    s = [slice(pseeds, 24, ns, GOES_UP), slice(pends, 24, nl, COMES_HOME), slice(plen, 8, nl, COMES_HOME), &
+         slice(pint, 8, nl, COMES_HOME), slice(pstat, 4, nl, COMES_HOME), slice(pnst, 4, nl, COMES_HOME), &
+         slice(poff, 8, nl + 1, COMES_HOME)]
+    rc = carve(buf, s)
     if (rc == 0) then
       call say("trace_paths", "Tracing field lines and counting their points...")
-      rc = ndsmk_paths_count(dB, dG, n3, lo, dq, nseeds, d(2), step, max_steps, sel, every, max_points, d(3), d(4), &
-                             d(5), d(6), d(7), d(1), total)
+      rc = ndsmk_paths_count(ctx%dF(1), dG, n3, lo, dq, nseeds, s(1)%dev, step, max_steps, sel, every, max_points, &
+                             s(2)%dev, s(3)%dev, s(4)%dev, s(5)%dev, s(6)%dev, s(7)%dev, total)
     end if
-    ! the point arrays: min(total, max_points) slots each, carved from a second buffer
+    ! the point arrays: min(total, max_points) slots each, carved from a second buffer (gpt, ipt: with G only)
     np = 0
     if (rc == 0) np = int(min(total, max_points), c_size_t)
-    dp = c_null_ptr
-    hp = [ppts, pbpt, pgpt, pipt]
-    if (.not. c_associated(pG)) hp(3:4) = c_null_ptr
     if (rc == 0 .and. np > 0) then
-      rc = ndsmk_alloc(pbuf, sum(pwidth, mask=c_associated_all(hp)) * np)
-      no = 0
-      do i = 1, 4
-        if (rc == 0 .and. c_associated(hp(i))) then
-          dp(i) = dptr_offset(pbuf, no)
-          no = no + pwidth(i) * np
-        end if
-      end do
+      pt = [slice(ppts, 24, np, COMES_HOME), slice(pbpt, 24, np, COMES_HOME), &
+            slice(merge(pgpt, c_null_ptr, c_associated(pG)), 24, np, COMES_HOME), &
+            slice(merge(pipt, c_null_ptr, c_associated(pG)), 8, np, COMES_HOME)]
+      rc = carve(pbuf, pt)
       if (rc == 0) then
         call say("trace_paths", "Tracing again and storing the points...")
-        rc = ndsmk_paths_fill(dB, dG, n3, lo, dq, nseeds, d(2), step, max_steps, sel, every, int(np, c_int64_t), d(1), &
-                              dp(1), dp(2), dp(3), dp(4))
+        rc = ndsmk_paths_fill(ctx%dF(1), dG, n3, lo, dq, nseeds, s(1)%dev, step, max_steps, sel, every, &
+                              int(np, c_int64_t), s(7)%dev, pt(1)%dev, pt(2)%dev, pt(3)%dev, pt(4)%dev)
       end if
     end if
-    if (rc == 0) rc = ndsmk_d2h(poff, d(1), 8_c_size_t * (nl + 1))
-    hl = [pends, plen, pint, pstat, pnst]
-    do i = 1, 5
-      if (rc == 0) rc = ndsmk_d2h(hl(i), d(2 + i), lwidth(i) * nl)
-    end do
-    do i = 1, 4
-      if (rc == 0 .and. np > 0 .and. c_associated(hp(i))) rc = ndsmk_d2h(hp(i), dp(i), pwidth(i) * np)
-    end do
+    if (rc == 0) rc = fetch(s)
+    if (rc == 0 .and. np > 0) rc = fetch(pt)
     if (rc == 0) rc = ndsmk_sync()
-    if (c_associated(pbuf)) then
-      rc_free = ndsmk_free(pbuf)
-      if (rc == 0) rc = rc_free
-    end if
-    rc_free = ndsmk_free(buf)
-    if (rc == 0) rc = rc_free
-    if (rc /= 0) total = 0
-  contains
-    pure function c_associated_all(p) result(m)
-      type(c_ptr), intent(in) :: p(4)
-      logical :: m(4)
-      integer :: q
-      do q = 1, 4
-        m(q) = c_associated(p(q))
-      end do
-    end function
+    call unstage(rc, [pbuf, buf], total)
   end function
 
   ! ------------------------------------------------------------------
@@ -1305,20 +1333,15 @@ contains
     integer(c_int64_t), intent(in) :: max_points
     real(wp), intent(in) :: radius, capture, step
     integer(c_int64_t), intent(out) :: total
-    integer(c_int) :: rc, rc_free
+    integer(c_int) :: rc
     real(wp) :: dq(3), lo(3)
     integer(c_int32_t) :: n3(3)
-    integer(c_size_t) :: nb, nl, nm, nr, np, no
-    integer :: i
-    type(c_ptr) :: buf, pbuf, din(3), d(10), dp(2), hp(2), ho(10)
-    ! bytes per null of pos, jac and per seed of ring; per null of kind, eig, spine, normal (the 8-byte arrays first);
-    ! per line of ends, length, status, nsteps, hit; per point of points, bpt
-    integer(c_size_t), parameter :: nwidth(4) = [24, 24, 24, 4], lwidth(5) = [24, 8, 4, 4, 4], pwidth(2) = [24, 24]
+    integer(c_size_t) :: nl, nm, nr, np
+    type(c_ptr) :: buf, pbuf
+    type(slice) :: s(13), pt(2)
 
     total = 0
-    n3 = ctx%n3
-    dq = [ctx%qx(2) - ctx%qx(1), ctx%qy(2) - ctx%qy(1), ctx%qz(2) - ctx%qz(1)]      ! as vecpot_run
-    lo = [ctx%qx(1), ctx%qy(1), ctx%qz(1)]
+    call ctx_mesh(ctx, n3, lo, dq)
     if (on_device .or. nnulls <= 0 .or. nring < 0 .or. step <= 0.0_wp .or. max_steps < 1 .or. every < 1 .or. &
         max_points < 0 .or. .not. (radius > 0.0_wp) .or. .not. (capture >= 0.0_wp) .or. radius > 1.0e300_wp .or. &
         capture > 1.0e300_wp .or. .not. (step <= 1.0e300_wp) .or. &
@@ -1333,79 +1356,40 @@ contains
       if (rc /= 0) total = 0
       return
     end if
-    nb = int(product(int(n3, ik)), c_size_t) * 24_c_size_t
     nm = int(nnulls, c_size_t)
     nr = int(nring, c_size_t)
     nl = nm * (2_c_size_t + nr)
-    if (.not. c_associated(ctx%dF(1))) then
-      rc = ndsmk_alloc(ctx%dF(1), nb); if (rc /= 0) return
-    end if
-    rc = ndsmk_h2d(ctx%dF(1), pB, nb); if (rc /= 0) return
-    ! one scratch buffer: offsets, pos, jac, ring (8-byte data first), the per-null outputs, then the per-line outputs
-    buf = c_null_ptr
+    rc = stage_field(ctx, 1, pB); if (rc /= 0) return
     pbuf = c_null_ptr
-    rc = ndsmk_alloc(buf, 8_c_size_t * (nl + 1) + 96_c_size_t * nm + 16_c_size_t * max(nr, 1_c_size_t) + &
-                     sum(nwidth) * nm + sum(lwidth) * nl)
-    if (rc /= 0) return
-    no = 8_c_size_t * (nl + 1)
-    din(1) = dptr_offset(buf, no); no = no + 24_c_size_t * nm               ! pos
-    din(2) = dptr_offset(buf, no); no = no + 72_c_size_t * nm               ! jac
-    din(3) = dptr_offset(buf, no); no = no + 16_c_size_t * max(nr, 1_c_size_t)   ! ring
-    ! eig, spine, normal, kind | ends, length, status, nsteps, hit | offsets
-    do i = 1, 3
-      d(i) = dptr_offset(buf, no); no = no + nwidth(i) * nm
-    end do
-    do i = 1, 2
-      d(4 + i) = dptr_offset(buf, no); no = no + lwidth(i) * nl
-    end do
-    d(4) = dptr_offset(buf, no); no = no + nwidth(4) * nm
-    do i = 3, 5
-      d(4 + i) = dptr_offset(buf, no); no = no + lwidth(i) * nl
-    end do
-    d(10) = buf
-    rc = ndsmk_h2d(din(1), ppos, 24_c_size_t * nm)
-    if (rc == 0) rc = ndsmk_h2d(din(2), pjac, 72_c_size_t * nm)
-    if (rc == 0 .and. nr > 0) rc = ndsmk_h2d(din(3), pring, 16_c_size_t * nr)
+    ! (nring = 0: an empty slice, so the kernel entry gets c_null_ptr for ring, which it takes when nring <= 0)
+    s = [slice(ppos, 24, nm, GOES_UP), slice(pjac, 72, nm, GOES_UP), slice(pring, 16, nr, GOES_UP), &
+         slice(pkind, 4, nm, COMES_HOME), slice(peig, 24, nm, COMES_HOME), slice(pspine, 24, nm, COMES_HOME), &
+         slice(pnormal, 24, nm, COMES_HOME), slice(pends, 24, nl, COMES_HOME), slice(plen, 8, nl, COMES_HOME), &
+         slice(pstat, 4, nl, COMES_HOME), slice(pnst, 4, nl, COMES_HOME), slice(phit, 4, nl, COMES_HOME), &
+         slice(poff, 8, nl + 1, COMES_HOME)]
+    rc = carve(buf, s)
     if (rc == 0) then
       call say("find_skeleton", "Typing the nulls, tracing their spines and fans and counting the points...")
-      rc = ndsmk_skel_count(ctx%dF(1), n3, lo, dq, nnulls, din(1), din(2), nring, din(3), radius, capture, step, &
-                            max_steps, every, max_points, d(4), d(1), d(2), d(3), d(5), d(6), d(7), d(8), d(9), d(10), &
-                            total)
+      rc = ndsmk_skel_count(ctx%dF(1), n3, lo, dq, nnulls, s(1)%dev, s(2)%dev, nring, s(3)%dev, radius, capture, step, &
+                            max_steps, every, max_points, s(4)%dev, s(5)%dev, s(6)%dev, s(7)%dev, s(8)%dev, s(9)%dev, &
+                            s(10)%dev, s(11)%dev, s(12)%dev, s(13)%dev, total)
     end if
     ! the point arrays: min(total, max_points) slots each, carved from a second buffer
     np = 0
     if (rc == 0) np = int(min(total, max_points), c_size_t)
-    dp = c_null_ptr
-    hp = [ppts, pbpt]
     if (rc == 0 .and. np > 0) then
-      rc = ndsmk_alloc(pbuf, merge(48_c_size_t, 24_c_size_t, c_associated(pbpt)) * np)
+      pt = [slice(ppts, 24, np, COMES_HOME), slice(pbpt, 24, np, COMES_HOME)]
+      rc = carve(pbuf, pt)
       if (rc == 0) then
-        dp(1) = pbuf
-        if (c_associated(pbpt)) dp(2) = dptr_offset(pbuf, 24_c_size_t * np)
         call say("find_skeleton", "Tracing again and storing the points...")
-        rc = ndsmk_skel_fill(ctx%dF(1), n3, lo, dq, nnulls, din(1), nring, radius, capture, step, max_steps, every, &
-                             int(np, c_int64_t), d(10), dp(1), dp(2))
+        rc = ndsmk_skel_fill(ctx%dF(1), n3, lo, dq, nnulls, s(1)%dev, nring, radius, capture, step, max_steps, every, &
+                             int(np, c_int64_t), s(13)%dev, pt(1)%dev, pt(2)%dev)
       end if
     end if
-    ho = [peig, pspine, pnormal, pkind, pends, plen, pstat, pnst, phit, poff]
-    do i = 1, 4
-      if (rc == 0) rc = ndsmk_d2h(ho(i), d(i), nwidth(i) * nm)
-    end do
-    do i = 1, 5
-      if (rc == 0) rc = ndsmk_d2h(ho(4 + i), d(4 + i), lwidth(i) * nl)
-    end do
-    if (rc == 0) rc = ndsmk_d2h(poff, d(10), 8_c_size_t * (nl + 1))
-    do i = 1, 2
-      if (rc == 0 .and. np > 0 .and. c_associated(hp(i))) rc = ndsmk_d2h(hp(i), dp(i), pwidth(i) * np)
-    end do
+    if (rc == 0) rc = fetch(s)
+    if (rc == 0 .and. np > 0) rc = fetch(pt)
     if (rc == 0) rc = ndsmk_sync()
-    if (c_associated(pbuf)) then
-      rc_free = ndsmk_free(pbuf)
-      if (rc == 0) rc = rc_free
-    end if
-    rc_free = ndsmk_free(buf)
-    if (rc == 0) rc = rc_free
-    if (rc /= 0) total = 0
+    call unstage(rc, [pbuf, buf], total)
   end function
 
   ! ------------------------------------------------------------------
@@ -1429,22 +1413,15 @@ contains
     integer(c_int64_t), intent(in) :: max_points
     real(wp), intent(in) :: radius, capture, step, tol
     integer(c_int64_t), intent(out) :: total
-    integer(c_int) :: rc, rc_free
+    integer(c_int) :: rc
     real(wp) :: dq(3), lo(3)
     integer(c_int32_t) :: n3(3)
-    integer(c_size_t) :: nb, nm, nq, np, no
-    integer :: i
-    type(c_ptr) :: buf, pbuf, din(5), d(11), dp(2), hp(2), hi(5), ho(11)
-    ! bytes per null of pos, normal, kind and per bracket of arc, pair (the 8-byte arrays first); per bracket of coef,
-    ! width, dmin, ends, length, then state, nrounds, side, status, nsteps; per point of points, bpt
-    integer(c_size_t), parameter :: iwidth(5) = [24, 24, 32, 4, 8], owidth(10) = [32, 8, 16, 24, 8, 4, 4, 4, 4, 4], &
-                                    ptwidth(2) = [24, 24]
-    integer(c_size_t) :: icount(5)
+    integer(c_size_t) :: nm, nq, np
+    type(c_ptr) :: buf, pbuf
+    type(slice) :: s(16), pt(2)
 
     total = 0
-    n3 = ctx%n3
-    dq = [ctx%qx(2) - ctx%qx(1), ctx%qy(2) - ctx%qy(1), ctx%qz(2) - ctx%qz(1)]      ! as vecpot_run
-    lo = [ctx%qx(1), ctx%qy(1), ctx%qz(1)]
+    call ctx_mesh(ctx, n3, lo, dq)
     if (on_device .or. nbr <= 0 .or. nnulls <= 0 .or. step <= 0.0_wp .or. max_steps < 1 .or. every < 1 .or. &
         rounds < 1 .or. max_points < 0 .or. .not. (radius > 0.0_wp) .or. .not. (capture > 0.0_wp) .or. &
         radius > 1.0e300_wp .or. capture > 1.0e300_wp .or. .not. (step <= 1.0e300_wp) .or. .not. (tol >= 0.0_wp) .or. &
@@ -1460,70 +1437,39 @@ contains
       if (rc /= 0) total = 0
       return
     end if
-    nb = int(product(int(n3, ik)), c_size_t) * 24_c_size_t
     nm = int(nnulls, c_size_t)
     nq = int(nbr, c_size_t)
-    if (.not. c_associated(ctx%dF(1))) then
-      rc = ndsmk_alloc(ctx%dF(1), nb); if (rc /= 0) return
-    end if
-    rc = ndsmk_h2d(ctx%dF(1), pB, nb); if (rc /= 0) return
-    ! one scratch buffer: offsets, then the inputs pos, normal, arc, pair (a whole number of 8-byte words), kind, then
-    ! the outputs in the order of owidth
-    icount = [nm, nm, nq, nm + mod(nm, 2_c_size_t), nq]
-    buf = c_null_ptr
+    rc = stage_field(ctx, 1, pB); if (rc /= 0) return
     pbuf = c_null_ptr
-    rc = ndsmk_alloc(buf, 8_c_size_t * (nq + 1) + sum(iwidth * icount) + sum(owidth) * nq)
-    if (rc /= 0) return
-    d(11) = buf
-    no = 8_c_size_t * (nq + 1)
-    do i = 1, 5
-      din(i) = dptr_offset(buf, no); no = no + iwidth(i) * icount(i)
-    end do
-    do i = 1, 10
-      d(i) = dptr_offset(buf, no); no = no + owidth(i) * nq
-    end do
-    hi = [ppos, pnormal, parc, pkind, ppair]
-    icount(4) = nm
-    do i = 1, 5
-      if (rc == 0) rc = ndsmk_h2d(din(i), hi(i), iwidth(i) * icount(i))
-    end do
+    s = [slice(ppos, 24, nm, GOES_UP), slice(pkind, 4, nm, GOES_UP), slice(pnormal, 24, nm, GOES_UP), &
+         slice(ppair, 8, nq, GOES_UP), slice(parc, 32, nq, GOES_UP), &
+         slice(pstate, 4, nq, COMES_HOME), slice(pnrounds, 4, nq, COMES_HOME), slice(pcoef, 32, nq, COMES_HOME), &
+         slice(pwidth, 8, nq, COMES_HOME), slice(pside, 4, nq, COMES_HOME), slice(pdmin, 16, nq, COMES_HOME), &
+         slice(pends, 24, nq, COMES_HOME), slice(plen, 8, nq, COMES_HOME), slice(pstat, 4, nq, COMES_HOME), &
+         slice(pnst, 4, nq, COMES_HOME), slice(poff, 8, nq + 1, COMES_HOME)]
+    rc = carve(buf, s)
     if (rc == 0) then
       call say("find_separators", "Refining the brackets, tracing the separators and counting the points...")
-      rc = ndsmk_sep_count(ctx%dF(1), n3, lo, dq, nnulls, din(1), din(4), din(2), nbr, din(5), din(3), radius, capture, &
-                           step, max_steps, rounds, tol, every, max_points, d(6), d(7), d(1), d(2), d(8), d(3), d(4), &
-                           d(5), d(9), d(10), d(11), total)
+      rc = ndsmk_sep_count(ctx%dF(1), n3, lo, dq, nnulls, s(1)%dev, s(2)%dev, s(3)%dev, nbr, s(4)%dev, s(5)%dev, radius, &
+                           capture, step, max_steps, rounds, tol, every, max_points, s(6)%dev, s(7)%dev, s(8)%dev, &
+                           s(9)%dev, s(10)%dev, s(11)%dev, s(12)%dev, s(13)%dev, s(14)%dev, s(15)%dev, s(16)%dev, total)
     end if
     ! the point arrays: min(total, max_points) slots each, carved from a second buffer
     np = 0
     if (rc == 0) np = int(min(total, max_points), c_size_t)
-    dp = c_null_ptr
-    hp = [ppts, pbpt]
     if (rc == 0 .and. np > 0) then
-      rc = ndsmk_alloc(pbuf, merge(48_c_size_t, 24_c_size_t, c_associated(pbpt)) * np)
+      pt = [slice(ppts, 24, np, COMES_HOME), slice(pbpt, 24, np, COMES_HOME)]
+      rc = carve(pbuf, pt)
       if (rc == 0) then
-        dp(1) = pbuf
-        if (c_associated(pbpt)) dp(2) = dptr_offset(pbuf, 24_c_size_t * np)
         call say("find_separators", "Tracing again and storing the points...")
-        rc = ndsmk_sep_fill(ctx%dF(1), n3, lo, dq, nnulls, din(1), nbr, din(5), radius, capture, step, max_steps, rounds, &
-                            tol, every, int(np, c_int64_t), d(11), dp(1), dp(2))
+        rc = ndsmk_sep_fill(ctx%dF(1), n3, lo, dq, nnulls, s(1)%dev, nbr, s(4)%dev, radius, capture, step, max_steps, &
+                            rounds, tol, every, int(np, c_int64_t), s(16)%dev, pt(1)%dev, pt(2)%dev)
       end if
     end if
-    ho = [pcoef, pwidth, pdmin, pends, plen, pstate, pnrounds, pside, pstat, pnst, poff]
-    do i = 1, 10
-      if (rc == 0) rc = ndsmk_d2h(ho(i), d(i), owidth(i) * nq)
-    end do
-    if (rc == 0) rc = ndsmk_d2h(poff, d(11), 8_c_size_t * (nq + 1))
-    do i = 1, 2
-      if (rc == 0 .and. np > 0 .and. c_associated(hp(i))) rc = ndsmk_d2h(hp(i), dp(i), ptwidth(i) * np)
-    end do
+    if (rc == 0) rc = fetch(s)
+    if (rc == 0 .and. np > 0) rc = fetch(pt)
     if (rc == 0) rc = ndsmk_sync()
-    if (c_associated(pbuf)) then
-      rc_free = ndsmk_free(pbuf)
-      if (rc == 0) rc = rc_free
-    end if
-    rc_free = ndsmk_free(buf)
-    if (rc == 0) rc = rc_free
-    if (rc /= 0) total = 0
+    call unstage(rc, [pbuf, buf], total)
   end function
 
   ! ------------------------------------------------------------------
@@ -1540,54 +1486,34 @@ contains
     type(c_ptr), intent(in) :: pB, pcell, ppos, pjac, pdet, pres, psign, pit
     integer(c_int), intent(in) :: max_nulls
     integer(c_int64_t), intent(out) :: counts(2)
-    integer(c_int) :: rc, rc_free
+    integer(c_int) :: rc
     real(wp) :: dq(3), lo(3)
     integer(c_int32_t) :: n3(3)
-    integer(c_size_t) :: nb, nm, no
-    integer :: i
-    type(c_ptr) :: buf, d(7), h(7)
-    ! bytes per record of cell, pos, jac, det, resid, sign, iters: 128 in all, the 8-byte fields first
-    integer(c_size_t), parameter :: width(7) = [8, 24, 72, 8, 8, 4, 4]
+    integer(c_size_t) :: nm
+    type(c_ptr) :: buf
+    type(slice) :: s(7)
 
     counts = 0
-    n3 = ctx%n3
-    dq = [ctx%qx(2) - ctx%qx(1), ctx%qy(2) - ctx%qy(1), ctx%qz(2) - ctx%qz(1)]      ! as vecpot_run
-    lo = [ctx%qx(1), ctx%qy(1), ctx%qz(1)]
+    call ctx_mesh(ctx, n3, lo, dq)
     if (on_device .or. max_nulls < 0) then
       ! (the argument errors are the kernel entry's to name; nothing is staged for them)
       rc = ndsmk_nulls(pB, n3, lo, dq, max_nulls, counts, pcell, ppos, pjac, pdet, pres, psign, pit)
       if (rc == 0) rc = ndsmk_sync()
       return
     end if
-    nb = int(product(int(n3, ik)), c_size_t) * 24_c_size_t
-    if (.not. c_associated(ctx%dF(1))) then
-      rc = ndsmk_alloc(ctx%dF(1), nb); if (rc /= 0) return
-    end if
-    rc = ndsmk_h2d(ctx%dF(1), pB, nb); if (rc /= 0) return
-    ! one scratch buffer of max_nulls records, carved into the seven arrays
-    buf = c_null_ptr
-    d = c_null_ptr
+    rc = stage_field(ctx, 1, pB); if (rc /= 0) return
+    ! one scratch buffer of max_nulls records (none for max_nulls = 0: the arrays are c_null_ptr)
     nm = int(max_nulls, c_size_t)
-    if (nm > 0) then
-      rc = ndsmk_alloc(buf, sum(width) * nm); if (rc /= 0) return
-      no = 0
-      do i = 1, 7
-        d(i) = dptr_offset(buf, no)
-        no = no + width(i) * nm
-      end do
-    end if
+    s = [slice(pcell, 8, nm, COMES_HOME), slice(ppos, 24, nm, COMES_HOME), slice(pjac, 72, nm, COMES_HOME), &
+         slice(pdet, 8, nm, COMES_HOME), slice(pres, 8, nm, COMES_HOME), slice(psign, 4, nm, COMES_HOME), &
+         slice(pit, 4, nm, COMES_HOME)]
+    rc = carve(buf, s); if (rc /= 0) return
     call say("find_nulls", "Screening the cells and iterating on the candidates...")
-    rc = ndsmk_nulls(ctx%dF(1), n3, lo, dq, max_nulls, counts, d(1), d(2), d(3), d(4), d(5), d(6), d(7))
-    no = int(min(counts(2), int(max_nulls, c_int64_t)), c_size_t)
-    h = [pcell, ppos, pjac, pdet, pres, psign, pit]
-    do i = 1, 7
-      if (rc == 0 .and. no > 0) rc = ndsmk_d2h(h(i), d(i), width(i) * no)
-    end do
+    rc = ndsmk_nulls(ctx%dF(1), n3, lo, dq, max_nulls, counts, s(1)%dev, s(2)%dev, s(3)%dev, s(4)%dev, s(5)%dev, &
+                     s(6)%dev, s(7)%dev)
+    if (rc == 0) rc = fetch(s, rows=int(min(counts(2), int(max_nulls, c_int64_t)), c_size_t))
     if (rc == 0) rc = ndsmk_sync()
-    if (c_associated(buf)) then
-      rc_free = ndsmk_free(buf)
-      if (rc == 0) rc = rc_free
-    end if
+    call unstage(rc, [buf])
   end function
 
   ! B.n of face f (1..6) from the host field (extract_bn, :699-743)

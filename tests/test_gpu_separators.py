@@ -205,7 +205,7 @@ def test_noise_nulls_match_the_restatement_bitwise(hip, handles, mname, ns, narc
 @pytest.mark.parametrize("mname", list(MESHES))
 def test_bracket_counts_rounds_tol_every(hip, handles, mname):
     """1, 2, 64 and 65 brackets (one lane of the line kernel; one workgroup of it; a workgroup plus one), rounds 1 and
-    10, tol 0 and 1e-12, every 1, 3 and 1000"""
+    10, tol 0 and 1e-12, every 1, 3 and 1000; 1, 2 and 65 brackets through the host entry as well; 3 nulls"""
     mesh, b, pos, _jac, kind, normal, pair, arc, want = noise_case(mname, [5, 5, 5], 4)
     # brackets that carry a line first, so that the small calls trace something
     order = np.argsort(~np.isin(want.state, (1, 2, 5)), kind="stable")
@@ -224,7 +224,21 @@ def test_bracket_counts_rounds_tol_every(hip, handles, mname):
         seen |= set(got.state.tolist())
         if tol == 0.0 or rounds == 1:
             assert not np.any(np.isin(got.state, (1, 2))) and UNRESOLVED in got.state
+        if (rounds, tol, every) == (10, 1e-12, 1) and nbr in (1, 2, 65):
+            # the host entry: an odd and an even number of 4-byte entries in front of 8-byte data in its staging buffer
+            host, n = sep_call(hip, V, b, pos, kind, normal, pair[idx], arc[idx], opt, int(w.offsets[-1]), device=False)
+            same_sep(host, w, "%s nbr %d, host entry" % (mname, nbr))
     assert FOUND in seen
+    # an odd number of nulls (the 4-byte kind in front of 8-byte data): the arrays of the nulls cut to 3, the brackets
+    # among them, the restatement on the same cut arrays
+    idx = np.nonzero(np.all(pair < 3, axis=1))[0]
+    assert len(pos) > 3 and len(idx) >= 1
+    w = separators_numpy(mesh, b, pos[:3], kind[:3], normal[:3], pair[idx], arc[idx], **NOISE_OPT)
+    for device in (True, False):
+        got, n = sep_call(hip, V, b, pos[:3], kind[:3], normal[:3], pair[idx], arc[idx], NOISE_OPT, int(w.offsets[-1]),
+                          device=device)
+        assert n == int(w.offsets[-1])
+        same_sep(got, w, "%s 3 nulls, %d brackets, device %s" % (mname, len(idx), device))
 
 
 # ---------------------------------------------------------------------------------------------------------------

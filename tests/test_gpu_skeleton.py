@@ -196,6 +196,29 @@ def test_skeleton_matches_the_restatement_bitwise(hip, runner, mname, ns):
     same_skel(runner(mesh, b, P, J, ring, RADIUS, 0.5, STEP, MAX_STEPS, 3), want, "%s %s counted first" % (mname, ns))
 
 
+@pytest.mark.parametrize("mname", list(MESHES))
+def test_odd_and_even_counts_on_both_entries(hip, runner, mname):
+    """1 and 3 nulls with 0 and 1 ring seeds - 2, 3, 6 and 9 lines, so the 4-byte arrays of the host entry's staging
+    buffer hold an odd and an even number of entries in front of 8-byte data -, bpt present and NULL, both entries"""
+    mesh, b, pos, jac = noise_case(mname, [5, 5, 5])
+    V = runner.handle(mesh)
+    for count in (1, 3):
+        for nring in (0, 1):
+            P, J = first_nulls(pos, jac, count)
+            ring = default_ring(nring)
+            want = skeleton_numpy(mesh, b, P, J, ring, RADIUS, 0.5, STEP, MAX_STEPS, 1)
+            assert len(want.status) == count * (2 + nring)
+            total = int(want.offsets[-1])
+            nob = want._replace(bpt=np.zeros_like(want.bpt))
+            for device in (True, False):
+                for with_bpt in (True, False):
+                    got, n = skel_call(hip, V, b, P, J, ring, RADIUS, 0.5, STEP, MAX_STEPS, 1, total, with_bpt=with_bpt,
+                                       device=device)
+                    assert n == total
+                    same_skel(got, want if with_bpt else nob,
+                              "%s %d nulls, nring %d, device %s bpt %s" % (mname, count, nring, device, with_bpt))
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # 2. capacity
 # ---------------------------------------------------------------------------------------------------------------

@@ -449,6 +449,36 @@ int ndsm_hip_vecpot_squash_device(void *h, const double *dB, const double *dG, i
                                   const double *dseeds, double step, int max_steps, double *dq, double *dends,
                                   double *dlength, double *dintegral, int32_t *dstatus, int32_t *dnsteps);
 
+/* ---- Perpendicular squashing factor on the same handle (DESIGN.md "Perpendicular squashing factor") ------------------
+ * Q-perp of Titov (2007) next to Q: the squashing factor of the mapping between the planes PERPENDICULAR TO THE FIELD
+ * at the two feet of the line, which does not depend on the faces the line happens to end on (a uniform field gives 2
+ * for every pair of faces).  It is the quantity to look at in a cut through the volume, where the lines of one
+ * structure leave through the top and through side faces.  Everything is as in the squash entries above - arguments,
+ * lines, ODE, start, exit, integrals, G == B for the twist map, status codes, independence of the seeds -, and q,
+ * ends, length, integral, status and nsteps of this entry are the bits of ndsm_hip_vecpot_squash on the same
+ * arguments.  Only the projection at the two ends and the normalisation differ:
+ *   out        qperp (nseeds) doubles, after q
+ *   Q-perp     at each end, from the same U, V and the same B_e (the interpolated B at the end point) as Q:
+ *              me = sqrt((Bx Bx + By By) + Bz Bz) of B_e, e = B_e / me (three divisions);
+ *              du = (U_x e_x + U_y e_y) + U_z e_z, dv likewise with V;  Up = U - du e, Vp = V - dv e;
+ *              puu = Up.Up, pvv = Vp.Vp, puv = Up.Vp, every dot product as (x x + y y) + z z.
+ *              With F, B the forward and backward ends and |B_s|^2 of the seed as for Q,
+ *              Q-perp = (((puu_F pvv_B + puu_B pvv_F) - 2 (puv_F puv_B)) * me_F) * me_B / |B_s|^2.
+ *              Not clamped to >= 2, as Q is not.  Q-perp = NaN unless both directions ended on a face and me > 0 at
+ *              both ends.  It does NOT need b_n > 0: a line that arrives tangent to its face has a Q-perp but no Q.
+ * Returns and failures as the squash entries (9002 also for a NULL qperp with nseeds > 0); on failure the host entry
+ * clears the nseeds entries of q and of qperp and the 2 nseeds entries of its other outputs.  nseeds == 0 succeeds and
+ * touches nothing.  Device memory as the squash entries. */
+/* HOST arrays */
+int ndsm_hip_vecpot_squash_perp(void *h, const double *B, const double *G, int integrand, int nseeds,
+                                const double *seeds, double step, int max_steps, double *q, double *qperp,
+                                double *ends, double *length, double *integral, int32_t *status, int32_t *nsteps);
+/* the same on DEVICE arrays of the library's GPU (seeds and the seven outputs too) */
+int ndsm_hip_vecpot_squash_perp_device(void *h, const double *dB, const double *dG, int integrand, int nseeds,
+                                       const double *dseeds, double step, int max_steps, double *dq, double *dqperp,
+                                       double *dends, double *dlength, double *dintegral, int32_t *dstatus,
+                                       int32_t *dnsteps);
+
 /* ---- Null points of a field on the same handle (DESIGN.md "Null points") ---------------------------------------------
  * Where B = 0 and of what type: the other half of a field's skeleton next to the squashing factor (the trace and
  * squash entries end a line with NDSM_HIP_TRACE_NULL when it runs into one).  The field is the trilinear interpolant

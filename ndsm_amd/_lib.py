@@ -104,6 +104,8 @@ def load_library(path=None):
     _sq = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_int] + [ctypes.c_void_p] * 6
     L.ndsm_hip_vecpot_squash.argtypes = [ctypes.c_void_p] * 3 + _sq
     L.ndsm_hip_vecpot_squash_device.argtypes = [ctypes.c_void_p] * 3 + _sq
+    L.ndsm_hip_vecpot_squash_perp.argtypes = [ctypes.c_void_p] * 3 + _sq + [ctypes.c_void_p]
+    L.ndsm_hip_vecpot_squash_perp_device.argtypes = [ctypes.c_void_p] * 3 + _sq + [ctypes.c_void_p]
     _nu = [ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 8
     L.ndsm_hip_vecpot_nulls.argtypes = _nu
     L.ndsm_hip_vecpot_nulls_device.argtypes = _nu
@@ -621,6 +623,34 @@ class VecPot:
                     device, who="ndsm_hip_vecpot_squash")
         return _qmap(out, twist)
 
+    def squashing_perp(self, b, seeds, g=None, integrand=0, twist=False, step=0.5, max_steps=None, device=False):
+        """Perpendicular squashing factor Q-perp (Titov 2007) of b next to Q, on the device (semantics:
+        include/ndsm_hip.h, ndsm_hip_vecpot_squash_perp): squashing() with the deviation vectors at the two feet
+        projected onto the planes perpendicular to b there instead of onto the faces, and |b| at the feet in place of
+        |b_n|.  Q-perp does not depend on the faces a line ends on - a uniform field gives 2 for every pair - and is
+        the quantity for cuts through the volume (seed_cut).  Arguments as squashing().  Returns a QPerpMap tuple: q
+        (the bits of squashing()), q_perp (nseeds; NaN unless both directions ended on a face; a line that arrives
+        tangent to its face has a q_perp but no q), twist (NaN where q_perp is: the twist of a line exists whenever
+        both feet do; None without twist=True), ends, length, integral, status, nsteps as squashing(), bit for bit.
+        Not clamped to >= 2."""
+        if integrand not in (0, 1) or isinstance(integrand, bool):
+            raise ValueError(f"integrand must be 0 or 1, not {integrand!r}")
+        if twist and g is not None:
+            raise ValueError("twist=True forms g = curl b itself: give g or twist, not both")
+        _d0, step, max_steps = self._trace_args(step, max_steps, "both")
+        B = self._field_arg(b, "squashing_perp")
+        G = None if g is None else self._field_arg(g, "squashing_perp")
+        S = self._seeds_arg(seeds)
+        q, qperp, lines = np.zeros(len(S)), np.zeros(len(S)), _trace_outputs(len(S), 0)
+        if len(S) == 0:
+            return _qperpmap(q, qperp, lines, twist)
+        if twist:
+            integrand = 1
+        # (the field passed as its own g with integrand 1 asks the library for g = curl b)
+        self._entry("ndsm_hip_vecpot_squash_perp", [B, B if twist else G, integrand, len(S), S, step, max_steps, q,
+                                                    qperp, *lines], device)
+        return _qperpmap(q, qperp, lines, twist)
+
     def nulls(self, b, max_nulls=4096, merge=1e-6, device=False):
         """Null points of b (3,nz,ny,nx) and their types, on the device (semantics: include/ndsm_hip.h,
         ndsm_hip_vecpot_nulls): every cell of the mesh is screened (a component of one strict sign over the eight
@@ -773,6 +803,10 @@ class VecPot:
         fixed at `value`, the other two (in the order x, y, z; the first of them fastest) n1 and n2 equally spaced
         points from face to face"""
         return seed_plane(self.x, self.y, self.z, axis, value, n1, n2)
+
+    def seed_cut(self, origin, e1, e2, n1, n2):
+        """the (n1 n2, 3) seeds origin + s e1 + t e2 of an oblique cut (see the module's seed_cut)"""
+        return seed_cut(self.x, self.y, self.z, origin, e1, e2, n1, n2)
 
     def field_line_helicity(self, b, seeds, gauge="devore", a=None, step=0.5, max_steps=None, direction="both",
                             niterex_max=10000, ncycles_max=1024, ex_tol=1e-13, vc_tol=1e-10, ms=5, mean=False,
@@ -1171,6 +1205,41 @@ def seed_plane(x, y, z, axis, value, n1, n2):
     return out.reshape(-1, 3)
 
 
+QPerpMap = collections.namedtuple("QPerpMap", ["q", "q_perp", "twist", "ends", "length", "integral", "status",
+                                              "nsteps"])
+
+
+def _qperpmap(q, qperp, lines, twist):
+    """a QPerpMap from q, q_perp and [ends, length, integral, status, nsteps]; twist = (I_fwd + I_bwd) / 4 pi, NaN
+    where q_perp is"""
+    tw = None
+    if twist:
+        tw = np.where(np.isnan(qperp), np.nan, (lines[2][0] + lines[2][1]) / (4.0 * np.pi))
+    return QPerpMap(q, qperp, tw, *lines)
+
+
+def seed_cut(x, y, z, origin, e1, e2, n1, n2):
+    """the (n1 n2, 3) seeds origin + s e1 + t e2 of an oblique cut through the mesh x, y, z: s and t n1 and n2 equally
+    spaced values in [0, 1] (a single one: 0), s fastest - the ordering of seed_plane, whose mesh-aligned cuts this
+    complements.  origin, e1, e2: three finite numbers each, in physical coordinates.  Points outside the box are
+    allowed: their lines come back with TRACE_OUTSIDE.  (The mesh takes no part: the cut is the caller's.)"""
+    if int(n1) != n1 or int(n2) != n2 or n1 < 1 or n2 < 1:
+        raise ValueError(f"n1 and n2 must be integers >= 1, not {n1!r}, {n2!r}")
+    vec = []
+    for name, v in (("origin", origin), ("e1", e1), ("e2", e2)):
+        try:
+            a = np.asarray(v, dtype=np.float64)
+        except (TypeError, ValueError):
+            a = None
+        if a is None or a.shape != (3,) or not np.all(np.isfinite(a)):
+            raise ValueError(f"{name} must be three finite numbers, not {v!r}")
+        vec.append(a)
+    s = np.arange(int(n1)) / max(int(n1) - 1, 1)
+    t = np.arange(int(n2)) / max(int(n2) - 1, 1)
+    out = vec[0][None, None, :] + s[None, :, None] * vec[1][None, None, :] + t[:, None, None] * vec[2][None, None, :]
+    return out.reshape(-1, 3)
+
+
 def _grid_handle(x, y, z, b, ngrids, lib):
     shape = np.shape(b)
     want = (3, len(z), len(y), len(x))
@@ -1254,6 +1323,19 @@ def squashing_factor(x, y, z, b, seeds, g=None, integrand=0, twist=False, step=0
     V = _grid_handle(x, y, z, b, 0, lib)
     try:
         return V.squashing(b, seeds, g=g, integrand=integrand, twist=twist, step=step, max_steps=max_steps)
+    finally:
+        V.close()
+
+
+def perpendicular_squashing(x, y, z, b, seeds, g=None, integrand=0, twist=False, step=0.5, max_steps=None, lib=None):
+    """Perpendicular squashing factor Q-perp of b (3,nz,ny,nx) at seeds (nseeds,3) next to Q, with the twist number
+    (twist=True) or the line integral of g: one-shot form of VecPot.squashing_perp (returns its QPerpMap tuple).
+    Raises NdsmHipError on device / runtime failures (>= 9001)."""
+    if twist and g is not None:
+        raise ValueError("twist=True forms g = curl b itself: give g or twist, not both")
+    V = _grid_handle(x, y, z, b, 0, lib)
+    try:
+        return V.squashing_perp(b, seeds, g=g, integrand=integrand, twist=twist, step=step, max_steps=max_steps)
     finally:
         V.close()
 

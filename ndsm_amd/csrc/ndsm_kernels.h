@@ -225,6 +225,13 @@ int ndsmk_squash(const double *B, const double *G, int integrand, const int32_t 
                  const double *h_dq3, int nseeds, const double *seeds, double step, int max_steps, double *q,
                  double *ends, double *length, double *integral, int32_t *status, int32_t *nsteps);
 
+/* The same with the perpendicular squashing factor (semantics: include/ndsm_hip.h, ndsm_hip_vecpot_squash_perp): qperp
+ * (nseeds) a DEVICE array after q; every other argument, check and output as ndsmk_squash, whose bits q, ends, length,
+ * integral, status and nsteps hold.  Asynchronous. */
+int ndsmk_squash_perp(const double *B, const double *G, int integrand, const int32_t *n3, const double *lo3,
+                      const double *h_dq3, int nseeds, const double *seeds, double step, int max_steps, double *q,
+                      double *qperp, double *ends, double *length, double *integral, int32_t *status, int32_t *nsteps);
+
 /* Null points (nulls.hip; semantics: include/ndsm_hip.h, ndsm_hip_vecpot_nulls).  B a DEVICE array (nx,ny,nz,3); lo3,
  * h_dq3: first mesh point and spacing per axis.  h_counts2 (HOST, int64): the screen's candidates, the nulls found.  The
  * first min(found, max_nulls) records in ascending cell order go into the DEVICE arrays cell (int64), pos (3 each), jac

@@ -15,6 +15,13 @@
 //   exit                  r' outside: the step is redone with s = t ds, t of the first face, then twice
 //                         s = s (face - r_ax) / (r'_ax - r_ax) (skipped when r'_ax == r_ax) and redone; snap, clamp
 // Every lane's loop is bounded by max_steps (and by four passes over a step).
+//
+// The perpendicular squashing factor (DESIGN.md "Perpendicular squashing factor"; kPerp) differs in the epilogue only:
+// the same U, V at the same two ends are projected onto the plane perpendicular to B at the end instead of onto the
+// face along B, and |B| at the two ends takes the place of |B_n|:
+//   end                   me = sqrt((Bx Bx + By By) + Bz Bz) of B at the end, e = B / me; du = (U_x e_x + U_y e_y) +
+//                         U_z e_z, dv likewise; Up = U - du e, Vp = V - dv e; puu, pvv, puv their dot products
+//   seed                  Qperp = (((puu_F pvv_B + puu_B pvv_F) - 2 (puv_F puv_B)) me_F) me_B / |B_s|^2
 #include "line.hpp"
 
 namespace {
@@ -116,13 +123,15 @@ __device__ __forceinline__ bool sq_rk4(const double *__restrict__ B, const doubl
 __device__ __forceinline__ double sq_pick(const double a[3], int ax) { return ax == 0 ? a[0] : (ax == 1 ? a[1] : a[2]); }
 
 // lane l: seed l / 2, direction l % 2 (0 forward, 1 backward).  Line j = direction * nseeds + seed of the outputs:
-// ends[3 j .. 3 j + 2], length[j], integral[j], status[j], nsteps[j]; q[seed] from the forward lane.
-template <bool kHasG>
+// ends[3 j .. 3 j + 2], length[j], integral[j], status[j], nsteps[j]; q[seed] (kPerp: and qperp[seed]) from the forward
+// lane.  kPerp false: qperp is not looked at.
+template <bool kHasG, bool kPerp>
 __global__ __launch_bounds__(kLineBlock) void squash_k(const double *__restrict__ B, const double *__restrict__ G,
                                                        const double *__restrict__ seeds, double *__restrict__ qout,
                                                        double *__restrict__ ends, double *__restrict__ length,
                                                        double *__restrict__ integral, int32_t *__restrict__ status,
-                                                       int32_t *__restrict__ nsteps, SqArgs p) {
+                                                       int32_t *__restrict__ nsteps, SqArgs p,
+                                                       double *__restrict__ qperp) {
   const size_t l = (size_t)blockIdx.x * kLineBlock + threadIdx.x;
   const bool live = l < 2 * (size_t)p.nseeds;
   const size_t is = live ? l >> 1 : 0;            // (a lane past the end follows seed 0 and writes nothing)
@@ -224,6 +233,7 @@ __global__ __launch_bounds__(kLineBlock) void squash_k(const double *__restrict_
   // this end's part of Q: the deviation vectors projected onto the face along B there
   const bool onface = st >= NDSMK_TRACE_XLO && st <= NDSMK_TRACE_ZHI;
   double uu = 0.0, vv = 0.0, uv = 0.0, bn = 0.0;
+  double puu = 0.0, pvv = 0.0, puv = 0.0, me = 0.0;
   if (onface) {
     const int ax = (st - NDSMK_TRACE_XLO) >> 1;
     const LineCell c = line_cell(p, y.r[0], y.r[1], y.r[2]);
@@ -242,11 +252,29 @@ __global__ __launch_bounds__(kLineBlock) void squash_k(const double *__restrict_
     vv = (Vt[0] * Vt[0] + Vt[1] * Vt[1]) + Vt[2] * Vt[2];
     uv = (Ut[0] * Vt[0] + Ut[1] * Vt[1]) + Ut[2] * Vt[2];
     bn = fabs(bax);
+    if (kPerp) {
+      // and of Qperp: the same vectors projected onto the plane perpendicular to B there
+      me = sqrt((be[0] * be[0] + be[1] * be[1]) + be[2] * be[2]);
+      const double e[3] = {be[0] / me, be[1] / me, be[2] / me};
+      const double du = (y.U[0] * e[0] + y.U[1] * e[1]) + y.U[2] * e[2];
+      const double dv = (y.V[0] * e[0] + y.V[1] * e[1]) + y.V[2] * e[2];
+      double Up[3], Vp[3];
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        Up[d] = y.U[d] - du * e[d];
+        Vp[d] = y.V[d] - dv * e[d];
+      }
+      puu = (Up[0] * Up[0] + Up[1] * Up[1]) + Up[2] * Up[2];
+      pvv = (Vp[0] * Vp[0] + Vp[1] * Vp[1]) + Vp[2] * Vp[2];
+      puv = (Up[0] * Vp[0] + Up[1] * Vp[1]) + Up[2] * Vp[2];
+    }
   }
   // the partner lane (the other direction of the same seed) is the neighbour in the wave: every lane of the wave
   // arrives here, whatever its line did
   const double uuo = __shfl_xor(uu, 1), vvo = __shfl_xor(vv, 1), uvo = __shfl_xor(uv, 1), bno = __shfl_xor(bn, 1);
   const int sto = __shfl_xor(st, 1);
+  double puuo = 0.0, pvvo = 0.0, puvo = 0.0, meo = 0.0;
+  if (kPerp) puuo = __shfl_xor(puu, 1), pvvo = __shfl_xor(pvv, 1), puvo = __shfl_xor(puv, 1), meo = __shfl_xor(me, 1);
   if (!live) return;
   const size_t j = (size_t)back * (size_t)p.nseeds + is;
   ends[3 * j] = y.r[0];
@@ -265,6 +293,15 @@ __global__ __launch_bounds__(kLineBlock) void squash_k(const double *__restrict_
       q = ((num * bn) * bno) / bs2;
     }
     qout[is] = q;
+    if (kPerp) {
+      // (no b_n > 0 here: a line that arrives tangent to its face has a Qperp but no Q)
+      double qp = __builtin_nan("");
+      if (onface && oface && me > 0.0 && meo > 0.0) {
+        const double num = (puu * pvvo + puuo * pvv) - 2.0 * (puv * puvo);
+        qp = ((num * me) * meo) / bs2;
+      }
+      qperp[is] = qp;
+    }
   }
 }
 
@@ -290,12 +327,40 @@ extern "C" int ndsmk_squash(const double *B, const double *G, int integrand, con
   const size_t nl = 2 * (size_t)nseeds;
   const unsigned nb = (unsigned)((nl + kLineBlock - 1) / kLineBlock);
   hipStream_t s = ndsm::stream();
+  double *const none = nullptr;
   if (G)
-    hipLaunchKernelGGL(squash_k<true>, dim3(nb), dim3(kLineBlock), 0, s, B, G, seeds, q, ends, length, integral, status,
-                       nsteps, p);
+    hipLaunchKernelGGL((squash_k<true, false>), dim3(nb), dim3(kLineBlock), 0, s, B, G, seeds, q, ends, length,
+                       integral, status, nsteps, p, none);
   else
-    hipLaunchKernelGGL(squash_k<false>, dim3(nb), dim3(kLineBlock), 0, s, B, G, seeds, q, ends, length, integral,
-                       status, nsteps, p);
+    hipLaunchKernelGGL((squash_k<false, false>), dim3(nb), dim3(kLineBlock), 0, s, B, G, seeds, q, ends, length,
+                       integral, status, nsteps, p, none);
+  NDSM_LAUNCH_CHECK();
+  return 0;
+}
+
+// The same with the perpendicular squashing factor Qperp (qperp: nseeds values, DEVICE) next to Q; every other output
+// holds ndsmk_squash's bits.  The same checks and launch shape.  Asynchronous.
+extern "C" int ndsmk_squash_perp(const double *B, const double *G, int integrand, const int32_t *n3, const double *lo3,
+                                 const double *h_dq3, int nseeds, const double *seeds, double step, int max_steps,
+                                 double *q, double *qperp, double *ends, double *length, double *integral,
+                                 int32_t *status, int32_t *nsteps) {
+  NDSM_REQUIRE_READY();
+  SqArgs p;
+  p.integrand = integrand;
+  const int rc = line_args("squash_perp: step > 0 (finite), max_steps >= 1, integrand in 0, 1 and nseeds >= 0",
+                           integrand >= 0 && integrand <= 1,
+                           B && seeds && q && qperp && ends && length && integral && status && nsteps, n3, lo3, h_dq3,
+                           nseeds, step, max_steps, 2, p);
+  if (rc != 0 || nseeds == 0) return rc;
+  const size_t nl = 2 * (size_t)nseeds;
+  const unsigned nb = (unsigned)((nl + kLineBlock - 1) / kLineBlock);
+  hipStream_t s = ndsm::stream();
+  if (G)
+    hipLaunchKernelGGL((squash_k<true, true>), dim3(nb), dim3(kLineBlock), 0, s, B, G, seeds, q, ends, length,
+                       integral, status, nsteps, p, qperp);
+  else
+    hipLaunchKernelGGL((squash_k<false, true>), dim3(nb), dim3(kLineBlock), 0, s, B, G, seeds, q, ends, length,
+                       integral, status, nsteps, p, qperp);
   NDSM_LAUNCH_CHECK();
   return 0;
 }

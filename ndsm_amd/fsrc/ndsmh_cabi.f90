@@ -980,6 +980,35 @@ contains
                                dintegral, dstatus, dnsteps, .true., "ndsm_hip_vecpot_squash_device")
   end function
 
+  ! ---- perpendicular squashing factor on the same handle -------------------
+  ! As the squash entries, with qperp (nseeds) after q: Titov's Q-perp, from the same deviation vectors at the same two
+  ! ends projected onto the planes perpendicular to B there (semantics: include/ndsm_hip.h).  q, ends, length, integral,
+  ! status and nsteps hold the bits of the squash entry on the same arguments.  Return value and clearing as there
+  ! (qperp: nseeds entries, required with nseeds > 0).
+
+  ! HOST arrays
+  function ndsm_hip_vecpot_squash_perp(handle, B, G, integrand, nseeds, seeds, step, max_steps, q, qperp, ends, length, &
+                                       integral, status, nsteps) bind(c, name="ndsm_hip_vecpot_squash_perp") result(ierr)
+    type(c_ptr), value :: handle, B, G, seeds, q, qperp, ends, length, integral, status, nsteps
+    integer(c_int), value :: integrand, nseeds, max_steps
+    real(c_double), value :: step
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_lines(handle, .true., B, G, integrand, nseeds, seeds, step, max_steps, q, ends, length, &
+                               integral, status, nsteps, .false., "ndsm_hip_vecpot_squash_perp", qperp)
+  end function
+
+  ! the same on DEVICE arrays of the library's GPU (nothing is cleared: the outputs are not host memory)
+  function ndsm_hip_vecpot_squash_perp_device(handle, dB, dG, integrand, nseeds, dseeds, step, max_steps, dq, dqperp, &
+                                              dends, dlength, dintegral, dstatus, dnsteps) &
+      bind(c, name="ndsm_hip_vecpot_squash_perp_device") result(ierr)
+    type(c_ptr), value :: handle, dB, dG, dseeds, dq, dqperp, dends, dlength, dintegral, dstatus, dnsteps
+    integer(c_int), value :: integrand, nseeds, max_steps
+    real(c_double), value :: step
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_lines(handle, .true., dB, dG, integrand, nseeds, dseeds, step, max_steps, dq, dends, dlength, &
+                               dintegral, dstatus, dnsteps, .true., "ndsm_hip_vecpot_squash_perp_device", dqperp)
+  end function
+
   ! ---- shared by the handle entries of the line and null calls below ----------
   ! the prologue: the runtime is up (without a device: 9001, whatever the arguments), and handle is that of a live
   ! context, which comes back in ctx; else 9002
@@ -1020,11 +1049,12 @@ contains
     end do
   end subroutine
 
-  ! the four line entries above: squash false, sel = direction, q = c_null_ptr for trace; squash true, sel = integrand
-  ! for squash.  nl lines: 2 nseeds for squash and for both directions, else nseeds.
+  ! the six line entries above: squash false, sel = direction, q = c_null_ptr for trace; squash true, sel = integrand
+  ! for squash, and qperp given for squash_perp.  nl lines: 2 nseeds for squash and for both directions, else nseeds.
   function vecpot_handle_lines(handle, squash, B, G, sel, nseeds, seeds, step, max_steps, q, ends, length, integral, &
-                               status, nsteps, on_device, who) result(ierr)
+                               status, nsteps, on_device, who, qperp) result(ierr)
     type(c_ptr), intent(in) :: handle, B, G, seeds, q, ends, length, integral, status, nsteps
+    type(c_ptr), intent(in), optional :: qperp
     logical, intent(in) :: squash, on_device
     integer(c_int), intent(in) :: sel, nseeds, max_steps
     real(c_double), intent(in) :: step
@@ -1039,8 +1069,11 @@ contains
     if (nseeds > 0 .and. .not. (c_associated(B) .and. c_associated(seeds) .and. (c_associated(q) .or. .not. squash) .and. &
                                 c_associated(ends) .and. c_associated(length) .and. c_associated(integral) .and. &
                                 c_associated(status) .and. c_associated(nsteps))) return
+    if (nseeds > 0 .and. present(qperp)) then
+      if (.not. c_associated(qperp)) return
+    end if
     ierr = reported(who, vecpot_lines(ctx, squash, B, G, sel, nseeds, seeds, step, max_steps, q, ends, length, integral, &
-                                      status, nsteps, on_device))
+                                      status, nsteps, on_device, qperp))
     if (ierr /= 0 .and. .not. on_device) call clear_outputs()
   contains
     subroutine clear_outputs()
@@ -1050,6 +1083,7 @@ contains
       ns = nseeds
       nl = ns * merge(2, 1, squash .or. sel == 0)
       call clear_host([q, ends, length, integral, status, nsteps], [8, 24, 8, 8, 4, 4], [ns, nl, nl, nl, nl, nl])
+      if (present(qperp)) call clear_host([qperp], [8], [ns])
     end subroutine
   end function
 

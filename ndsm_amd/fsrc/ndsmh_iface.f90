@@ -583,6 +583,18 @@ module ndsmh_iface
       integer(c_int) :: rc
     end function
 
+    ! the same with the perpendicular squashing factor qperp (nseeds) after q
+    function ndsmk_squash_perp(B, G, integrand, n3, lo3, dq3, nseeds, seeds, step, max_steps, q, qperp, ends, length, &
+                               integral, status, nsteps) bind(c, name="ndsmk_squash_perp") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_double
+      type(c_ptr), value :: B, G, seeds, q, qperp, ends, length, integral, status, nsteps
+      integer(c_int32_t), intent(in) :: n3(3)
+      real(c_double), intent(in) :: lo3(3), dq3(3)
+      integer(c_int), value :: integrand, nseeds, max_steps
+      real(c_double), value :: step
+      integer(c_int) :: rc
+    end function
+
     ! ---- null points (nulls.hip) ----
     function ndsmk_nulls(B, n3, lo3, dq3, max_nulls, counts2, cell, pos, jac, det, resid, sign, iters) &
         bind(c, name="ndsmk_nulls") result(rc)

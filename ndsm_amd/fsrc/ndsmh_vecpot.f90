@@ -1150,27 +1150,33 @@ contains
   ! doubles and pstat, pnst (nl) int32 out, nl = 2 nseeds (squash, direction 0) or nseeds; pq (nseeds) doubles out
   ! for squash, not looked at for trace: on the HOST (B, G and the seeds go up into the helicity entries' staging
   ! arrays and a scratch buffer, the results come home) or (on_device) in HBM.  Squash with integrand 1 and pG the
-  ! very pointer pB: G = curl_h B (ndsmk_curl into the staging array dF(2)), the twist map.
+  ! very pointer pB: G = curl_h B (ndsmk_curl into the staging array dF(2)), the twist map.  Squash with pqperp given
+  ! (nseeds doubles out, where pq is): ndsmk_squash_perp, the perpendicular squashing factor next to Q (DESIGN.md
+  ! "Perpendicular squashing factor").
   ! ------------------------------------------------------------------
   function vecpot_lines(ctx, squash, pB, pG, sel, nseeds, pseeds, step, max_steps, pq, pends, plen, pint, pstat, pnst, &
-                        on_device) result(rc)
+                        on_device, pqperp) result(rc)
     type(vecpot_ctx), intent(inout), target :: ctx
     logical, intent(in) :: squash, on_device
     type(c_ptr), intent(in) :: pB, pG, pseeds, pq, pends, plen, pint, pstat, pnst
+    type(c_ptr), intent(in), optional :: pqperp
     integer(c_int), intent(in) :: sel, nseeds, max_steps
     real(wp), intent(in) :: step
     integer(c_int) :: rc, rc_free
     real(wp) :: dq(3), lo(3)
     integer(c_int32_t) :: n3(3)
     integer(c_size_t) :: nl, ns
-    logical :: own_curl
-    type(c_ptr) :: dB, dG, buf
-    type(slice) :: s(7)
+    logical :: own_curl, perp
+    type(c_ptr) :: dB, dG, buf, pqp
+    type(slice) :: s(8)
 
     call ctx_mesh(ctx, n3, lo, dq)
+    perp = squash .and. present(pqperp)
+    pqp = c_null_ptr
+    if (perp) pqp = pqperp
     if (nseeds <= 0 .or. step <= 0.0_wp .or. max_steps < 1 .or. sel < merge(0, -1, squash) .or. sel > 1) then
       ! (the argument errors are the kernel entry's to name; nothing is staged for them)
-      rc = launch(pB, pG, pseeds, pq, pends, plen, pint, pstat, pnst)
+      rc = launch(pB, pG, pseeds, pq, pqp, pends, plen, pint, pstat, pnst)
       ! (trace synchronises here, squash does not: ndsmk_sync can return an earlier asynchronous error, so the call
       ! is part of what each entry returns)
       if (rc == 0 .and. .not. squash) rc = ndsmk_sync()
@@ -1198,14 +1204,14 @@ contains
       rc = ndsmk_curl(dB, dG, n3, dq); if (rc /= 0) return
     end if
     if (on_device) then
-      rc = launch(dB, dG, pseeds, pq, pends, plen, pint, pstat, pnst)
+      rc = launch(dB, dG, pseeds, pq, pqp, pends, plen, pint, pstat, pnst)
       if (rc /= 0) return
       rc = ndsmk_sync()
       return
     end if
     s = [slice(pseeds, 24, ns, GOES_UP), slice(merge(pq, c_null_ptr, squash), 8, ns, COMES_HOME), &
          slice(pends, 24, nl, COMES_HOME), slice(plen, 8, nl, COMES_HOME), slice(pint, 8, nl, COMES_HOME), &
-         slice(pstat, 4, nl, COMES_HOME), slice(pnst, 4, nl, COMES_HOME)]
+         slice(pstat, 4, nl, COMES_HOME), slice(pnst, 4, nl, COMES_HOME), slice(pqp, 8, ns, COMES_HOME)]
     rc = carve(buf, s)
     if (rc == 0) then
       if (squash) then
@@ -1213,18 +1219,21 @@ contains
       else
         call say("trace_field_lines", "Tracing field lines...")
       end if
-      rc = launch(dB, dG, s(1)%dev, s(2)%dev, s(3)%dev, s(4)%dev, s(5)%dev, s(6)%dev, s(7)%dev)
+      rc = launch(dB, dG, s(1)%dev, s(2)%dev, s(8)%dev, s(3)%dev, s(4)%dev, s(5)%dev, s(6)%dev, s(7)%dev)
     end if
     if (rc == 0) rc = fetch(s)
     if (rc == 0) rc = ndsmk_sync()
     rc_free = rc                                       ! (an error of the free is not returned here, unlike below)
     call unstage(rc_free, [buf])
   contains
-    ! the kernel entry of this call on the given arrays (q: looked at by squash only)
-    function launch(B, G, seeds, q, ends, length, integral, status, nsteps) result(rc)
-      type(c_ptr), intent(in) :: B, G, seeds, q, ends, length, integral, status, nsteps
+    ! the kernel entry of this call on the given arrays (q: looked at by squash only, qperp by squash with pqperp)
+    function launch(B, G, seeds, q, qperp, ends, length, integral, status, nsteps) result(rc)
+      type(c_ptr), intent(in) :: B, G, seeds, q, qperp, ends, length, integral, status, nsteps
       integer(c_int) :: rc
-      if (squash) then
+      if (perp) then
+        rc = ndsmk_squash_perp(B, G, sel, n3, lo, dq, nseeds, seeds, step, max_steps, q, qperp, ends, length, integral, &
+                               status, nsteps)
+      else if (squash) then
         rc = ndsmk_squash(B, G, sel, n3, lo, dq, nseeds, seeds, step, max_steps, q, ends, length, integral, status, &
                           nsteps)
       else

@@ -11,6 +11,7 @@
 //   rbgs3_color   : two launches per sweep, half-line utilisation -> baseline
 //                   and fallback for tiny / oddly shaped levels
 //   rbgs3_fused   : one launch per sweep (see smooth_fused.hip)
+//   rbgs3_block_k : two sweeps per launch on the cache-resident levels in between (see smooth_block.hip)
 #include "common.hpp"
 
 namespace ndsm {
@@ -18,6 +19,9 @@ void fused_metric_accumulate(bool on);
 int launch_rbgs3_fused(const ndsmk_grid &g, const double *u, double *uout, const double *rhs, int max_sweeps,
                        bool force, int *sweeps_done, double *rout, int *res_done, const double *prev, int *met_done,
                        const ndsmk_xfer *px, const double *uc);
+int launch_rbgs3_block(const ndsmk_grid &g, const double *u, double *uout, const double *rhs, int max_sweeps,
+                       int *sweeps_done);
+int64_t block_smoother_first_below();
 int fetch_fused_metric(double *h_out2);
 int launch_mean_shift(double *u, int64_t n);
 }
@@ -263,7 +267,7 @@ __global__ __launch_bounds__(256) void rbgs2_color(double *__restrict__ u, const
 
 }  // namespace
 
-// The sweeps of one relax call.  bufs[0] holds u on entry; the out-of-place fused passes write to
+// The sweeps of one relax call.  bufs[0] holds u on entry; the out-of-place fused and block passes write to
 // whichever of bufs[0..2] is neither the current one nor `keep` (bufs[2] may be null: plain
 // ping-pong); *where tells which buffer holds the result.  keep: a buffer that must survive (the
 // iterate the V-cycle started from, which the convergence metric is taken against); prev: evaluate
@@ -344,9 +348,19 @@ static int relax_impl(const ndsmk_grid *gp, double *const bufs[3], const double 
           }
         // all-Neumann levels shift the mean after EVERY sweep: one sweep per pass there
         int ndone = 0;
+        // the block-resident launch (two sweeps, or a last single one) takes the whole, not all-Neumann levels
+        // above the single-workgroup limit that the fused launcher declines - up to 512 K points: measured per five
+        // sweeps at 32^3 / 64^3 / 96^3 / 128^3, block 19 / 28 / 65 / 123 us, colour passes 28 / 38 / 56 / 107 us,
+        // fused 62 / 65 / 67 / 73 us (scripts/time_small_levels.py, profiles/block_levels.txt; the lines cross near 600 K)
+        const int64_t blk_first_below = ndsm::block_smoother_first_below();   // (development knob: default 0)
+        const bool blk = variant == 0 && dst >= 0 && !g.all_neumann && npts > 4096 && g.k0 == 0 && g.zown0 == 0 &&
+                         g.zown1 == g.n[2] && (npts < (int64_t)512 * 1024 || npts < blk_first_below);
+        const bool blk_first = blk && npts < blk_first_below;
         if (prol_pending) {  // first pass: try the launch that interpolates while it loads
-          int rc = ndsm::launch_rbgs3_fused(g, u, dst >= 0 ? bufs[dst] : nullptr, rhs, g.all_neumann ? 1 : nsweeps - sw,
-                                            variant == 2, &ndone, nullptr, nullptr, nullptr, nullptr, px, uc);
+          int rc = blk_first ? 0
+                             : ndsm::launch_rbgs3_fused(g, u, dst >= 0 ? bufs[dst] : nullptr, rhs,
+                                                        g.all_neumann ? 1 : nsweeps - sw, variant == 2, &ndone, nullptr,
+                                                        nullptr, nullptr, nullptr, px, uc);
           if (rc) return rc;
           if (ndone == 0) {  // not that launch: interpolate in place, then sweep as usual
             NDSM_CHECK_ARG(in_place_ok());
@@ -356,12 +370,17 @@ static int relax_impl(const ndsmk_grid *gp, double *const bufs[3], const double 
           prol_pending = false;
         }
         // the residual rides on the last sweep (not on all-Neumann levels: the mean shift comes in between)
-        int rc = ndone > 0 ? 0
-                           : ndsm::launch_rbgs3_fused(g, u, dst >= 0 ? bufs[dst] : nullptr, rhs,
-                                                      g.all_neumann ? 1 : nsweeps - sw, variant == 2, &ndone,
-                                                      g.all_neumann ? nullptr : rout, res_done,
-                                                      g.all_neumann ? nullptr : prev, met_done, nullptr, nullptr);
+        int rc = ndone > 0 || blk_first
+                     ? 0
+                     : ndsm::launch_rbgs3_fused(g, u, dst >= 0 ? bufs[dst] : nullptr, rhs,
+                                                g.all_neumann ? 1 : nsweeps - sw, variant == 2, &ndone,
+                                                g.all_neumann ? nullptr : rout, res_done,
+                                                g.all_neumann ? nullptr : prev, met_done, nullptr, nullptr);
         if (rc) return rc;
+        if (ndone == 0 && blk) {
+          rc = ndsm::launch_rbgs3_block(g, u, bufs[dst], rhs, nsweeps - sw, &ndone);
+          if (rc) return rc;
+        }
         done = ndone > 0;
         if (done) {  // the sweeps landed in the other array
           sw += ndone - 1;

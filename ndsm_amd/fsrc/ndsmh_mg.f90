@@ -360,7 +360,10 @@ contains
   !     stream would end the recording half way);
   !   * every array must be where it was when the next cycle starts: the in-place kernels keep them; the
   !     out-of-place fused smoother swaps a level's array with its partner once per pass, and only level 1
-  !     makes an even number of passes per cycle (ceil(ms/2) down and up) - so no level below it may use it;
+  !     makes an even number of passes per cycle (ceil(ms/2) down and up) - so no level below it may use it.
+  !     (The block-resident smoother of the mid-size levels is out of place as well: ceil(ms/2) launches down and
+  !     ms up, even for ms = 1, 4, 5; where the sum is odd the recording itself finds the arrays swapped and the
+  !     cycle is enqueued kernel by kernel - enqueue_cycle in mg_solve_lanes);
   !   * it must pay: 2-D levels from ~180^2 points on (below, a cycle is a handful of launches - sweeps of a
   !     whole level and the tail are one each - and a replay costs more than it saves: 64^3 calls measured 12-13
   !     ms without, 14.5 ms with), 3-D solves up to 16 M points (dispatch latency, not bandwidth).

@@ -631,6 +631,11 @@ __global__ __launch_bounds__(NT, WPS) void rbgs3_fused_k(const T *__restrict__ u
   double met_mx = 0.0, met_sm = 0.0;
   // z range in which a stage plane is an ordinary one: inside the update bounds and off the mirror faces
   const int zin0 = max(g.lb[2], 1 - g.k0), zin1 = min(g.ub[2], g.nzg - 2 - g.k0);
+  // stage t is needed from step kn0 + 2t on (stages, below); the steps in which every stage is needed AND ordinary
+  // take the steady-state form; zw0 / zw1: the planes a stage may write (update bounds, inside the array)
+  const int kn0 = zs - NSTG + 1;
+  const int kfull0 = max(kn0 + 2 * (NST - 1), zin0 + NST - 1), kfull1 = min(klast, zin1);
+  const int zw0 = max(g.lb[2], 0), zw1 = min(g.ub[2], nz - 1);
   // One plane-step.  The copy C of the step serves the iterations k = C (mod NCOPY): plane k-d sits in LDS buffer
   // (C - d) mod NB, every stage updates class C & 1.
   static_assert(NB == NSTG, "one LDS plane per pipeline stage");
@@ -698,39 +703,48 @@ __global__ __launch_bounds__(NT, WPS) void rbgs3_fused_k(const T *__restrict__ u
       zback[s] = cL[s][HK];
       if (RHS0) asm volatile("" : "+v"(zback[s]));   // (the kernels with an rhs window have no register to spare for it)
     }
+    // The ZB form is also the EDGE form: every stage sits under a wave-uniform test and runs only where a stored
+    // plane depends on it.  Stage t reads planes p +- 1 as stage t-1 left them, so the planes [zs, ze) after their
+    // last stage depend on stage t of plane p only for zs - (NSTG-1-t) <= p <= ze-1 + (NSTG-1-t): in step k
+    // (p = k - t) that is kn0 + 2t <= k <= klast.  Below that cone - the chunk's warm-up steps, which need 0, 1, 1,
+    // 2, 2, ... of their stages, and the steps GROUPS adds at either end - a stage would produce a value no needed
+    // stage ever reads (the argument of the halo rings, above), and a stage whose plane is outside the z update
+    // bounds writes nothing at all: both skip their arithmetic and LDS traffic.  A needed stage finds every
+    // operand where it did before: stage t needed in step k implies stage t-1 needed in steps k and k-1.
     auto stages = [&](auto ZBT) __attribute__((always_inline)) {
       constexpr bool ZB = decltype(ZBT)::value;
 #pragma unroll
       for (int t = 0; t < NST; ++t) {
         const int bB = NDSM_BO(t), bZ = NDSM_BO(t + 1);
-        T oth[NS], xn[NS], yhv[NS], ylv[NS], zm[NS];
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-          if (t > 0) zp[s] = LDSD((RHS0 ? zback[s] : cL[s][HK]) + NDSM_BO(t - 1));
-          oth[s] = LDSD(cL[s][1 - HK] + bB);
-          xn[s] = LDSD(cX[s][HK] + bB);
-          yhv[s] = LDSD(cYH[s][HK] + bB);
-          ylv[s] = LDSD(cYL[s][HK] + bB);
-          // plane k-t-1: its LDS copy, or (last stage) the saved final point
-          zm[s] = (t < NSTG - 1) ? LDSD(cL[s][HK] + bZ) : mLe[RES ? 0 : s];
-        }
         const int pg = k - t + g.k0;
-        const bool wr = !ZB || (k - t >= g.lb[2] && k - t <= g.ub[2]);
+        if (!ZB || (k >= kn0 + 2 * t && k <= klast && k - t >= zw0 && k - t <= zw1)) {
+          T oth[NS], xn[NS], yhv[NS], ylv[NS], zm[NS];
 #pragma unroll
-        for (int s = 0; s < NS; ++s) {
-          const T xs = oth[s] + xn[s];  // u(xh) + u(xl)
-          const T ys = yhv[s] + ylv[s];
-          const T zhv = (ZB && pg == g.nzg - 1) ? zm[s] : zp[s];
-          const T zlv = (ZB && pg == 0) ? zp[s] : zm[s];
-          const T zsum = zhv + zlv;
-          const T rr = RHS0 ? (T)0 : (HK ? rw[RHS0 ? 0 : s][RHS0 ? 0 : t].y : rw[RHS0 ? 0 : s][RHS0 ? 0 : t].x);
-          const T unew = xs * gw0 + ys * gw1 + zsum * gw2 - rr;
-          const T nw = gw1i * unew;
-          if (wr && __builtin_amdgcn_inverse_ballot_w64(mU[s][HK])) LDSD(cL[s][HK] + bB) = nw;
+          for (int s = 0; s < NS; ++s) {
+            if (t > 0) zp[s] = LDSD((RHS0 ? zback[s] : cL[s][HK]) + NDSM_BO(t - 1));
+            oth[s] = LDSD(cL[s][1 - HK] + bB);
+            xn[s] = LDSD(cX[s][HK] + bB);
+            yhv[s] = LDSD(cYH[s][HK] + bB);
+            ylv[s] = LDSD(cYL[s][HK] + bB);
+            // plane k-t-1: its LDS copy, or (last stage) the saved final point
+            zm[s] = (t < NSTG - 1) ? LDSD(cL[s][HK] + bZ) : mLe[RES ? 0 : s];
+          }
+#pragma unroll
+          for (int s = 0; s < NS; ++s) {
+            const T xs = oth[s] + xn[s];  // u(xh) + u(xl)
+            const T ys = yhv[s] + ylv[s];
+            const T zhv = (ZB && pg == g.nzg - 1) ? zm[s] : zp[s];
+            const T zlv = (ZB && pg == 0) ? zp[s] : zm[s];
+            const T zsum = zhv + zlv;
+            const T rr = RHS0 ? (T)0 : (HK ? rw[RHS0 ? 0 : s][RHS0 ? 0 : t].y : rw[RHS0 ? 0 : s][RHS0 ? 0 : t].x);
+            const T unew = xs * gw0 + ys * gw1 + zsum * gw2 - rr;
+            const T nw = gw1i * unew;
+            if (__builtin_amdgcn_inverse_ballot_w64(mU[s][HK])) LDSD(cL[s][HK] + bB) = nw;
+          }
         }
       }
     };
-    if (pf >= zin0 && k <= zin1)
+    if (k >= kfull0 && k <= kfull1)
       stages(std::false_type());
     else
       stages(std::true_type());
@@ -1011,7 +1025,7 @@ int launch_cfg(const ndsmk_grid &g, const T *u, T *uout, const T *rhs, int targe
     nzc = (target_wgs + tiles - 1) / tiles;
     if (nzc < 1) nzc = 1;
     int zc = (nzo + nzc - 1) / nzc;
-    if (zc < 16) zc = 16 < nzo ? 16 : nzo;
+    if (zc < NST) zc = NST < nzo ? NST : nzo;   // (down to the pipeline depth: what the chunk-count timings force)
     nzc = (nzo + zc - 1) / zc;
   } else {
     const int64_t slots = (int64_t)ndsm::cu_count() * wgs_per_cu[v];

@@ -329,6 +329,87 @@ int ndsm_hip_vecpot_trace_device(void *h, const double *dB, const double *dG, in
                                  double step, int max_steps, int direction, double *dends, double *dlength,
                                  double *dintegral, int32_t *dstatus, int32_t *dnsteps);
 
+/* ---- Nonlinear force-free field: the Grad-Rubin iteration on the same handle (DESIGN.md "Nonlinear force-free
+ * field") ------------------------------------------------------------------------------------------------------------
+ * A vector magnetogram gives B.n on the faces and, on the lower face, alpha0 = (curl B)_z / B_z.  The field that uses
+ * both is the nonlinear force-free field, curl B = alpha B with B.grad alpha = 0 (Grad & Rubin 1958; Amari et al.
+ * 1999, 2006; Wheatland 2006).  One pass k of the iteration:
+ *   1. alpha^k: alpha0 carried from the lower face along the field lines of B^k to every node (the alpha map);
+ *   2. J = alpha^k B^k;
+ *   3. laplace(A_c) = -J_c, c = x, y, z, with the potential field's gauge, boundary letters and tangential data,
+ *      warm-started from A^k, and B^{k+1} = curl A^{k+1} + the flux-balance fields.
+ * Uniform spacing, the handle's mesh (lo_d, h_d, hi_d as for ndsm_hip_vecpot_trace).  Three pairs of entries:
+ *
+ * The alpha map (step 1 alone; no solve, no hierarchy: the handle supplies the mesh only)
+ *   B         (nx,ny,nz,3)
+ *   alpha0    (nx,ny), x fastest: the function on the face z = lo_z
+ *   polarity  +1: the line of each node is followed against B (alpha0 is taken where B_z > 0 brings the current in);
+ *             -1: along B.  Either way the line runs back to where its current entered the box.
+ *   step, max_steps   as ndsm_hip_vecpot_trace
+ *   out       alpha (nx,ny,nz) doubles; status (nx,ny,nz) int32, may be NULL
+ *   One line per node, x fastest; there is no seed array: the seed of node (i,j,k) is r_d = lo_d + (double) i_d h_d,
+ *   on the last node hi_d's own expression, so every node is inside the box, and the number of nodes is bounded by
+ *   the launch (2^37), not by 2^31 - 1 lines.  The line, its end point and its status are bit for bit those of
+ *   ndsm_hip_vecpot_trace from that seed with direction = -polarity (G = NULL).  Then
+ *     status == NDSM_HIP_TRACE_ZLO   alpha = the bilinear interpolant of alpha0 at the end point's (x, y): the cell
+ *                                    c_d = clamp(floor(u_d), 0, n_d - 2), the unclamped f_d = u_d - c_d, and
+ *                                    c0 = v00 + f_x (v10 - v00), c1 = v01 + f_x (v11 - v01), alpha = c0 + f_y (c1 - c0)
+ *     any other status               alpha = +0.0: a line that leaves through a side face or the top, ends at a null
+ *                                    or does not finish within max_steps carries no current.
+ *   Each node depends on its own line only.  9004: step <= 0 or not finite, max_steps < 1, polarity not +1 / -1.
+ *
+ * The solve for a prescribed current (steps 2-3 with the caller's J)
+ *   J         (nx,ny,nz,3): the right-hand sides are rhs_c = -J_c
+ *   A         in: the initial guess; out: the solution
+ *   B         in: the field whose B.n on the six faces is kept (only its faces are read); out: curl A + balance
+ *   Options in the usual slots, return value, ioptc[IOPT_IERR], ioptc[get_iopt_fail3d()] bits 0-2 and the refusal of
+ *   a grid that cannot fit as ndsm_hip_vecpot_solve_field; J = 0 gives the potential field.
+ *
+ * The iteration
+ *   B         in: supplies B.n on the six faces; out: the last pass's field
+ *   alpha0, polarity, step, max_steps   as the alpha map
+ *   start     0: B^0 is the potential field of that B.n and A^0 its A (the bits ndsm_hip_vecpot_solve_device gives
+ *             from a zero guess); 1: B^0 = B and A^0 = the caller's A
+ *   niter_max >= 1 passes at most; tol >= 0: the loop stops after the pass whose hist[k][0] < tol
+ *   A         in (start 1): A^0; out: the last pass's A.  alpha, status (may be NULL): the last pass's alpha map
+ *   hist      (niter_max rows of 4 doubles, on the HOST in both entries), row k of the passes run:
+ *       [0] max over components and points of |B^{k+1} - B^k|
+ *       [1] 1/2 sum w |B^{k+1}|^2 (trapezoid weights, as ndsm_hip_vecpot_helicity)
+ *       [2] the current-weighted sine: sum w |J x B| / |B| over sum w |J|, J = curl_h B^{k+1} (derivq's differences);
+ *           points where |B| is not > 0 are skipped; 0 when the denominator is 0
+ *       [3] the number of nodes whose status is NDSM_HIP_TRACE_ZLO
+ *       deterministic sums: the same input gives the same bits
+ *   niter_out (one int, on the HOST in both entries): the passes run
+ *   The face phase (B.n, the fluxes, the six 2-D solves) runs once per call, from the input B, never from an iterate.
+ *   A pass is exactly the alpha map of B^k followed by the solve for J = alpha^k B^k (rhs_c = -(alpha B_c): one
+ *   rounding and a sign) from the guess A^k with the input's B.n: the same kernels in the same order, the same bits.
+ *   Returns 0, 1 when any 2-D or 3-D solve of any pass missed vc_tol, >= 9001 errors.  9004: polarity not +1 / -1,
+ *   start not 0 / 1, niter_max < 1, tol < 0 or not finite, step <= 0 or not finite, max_steps < 1.
+ *   Device memory besides the hierarchy: A, two fields B (the caller's and the handle's) and alpha, plus 4 B/pt of
+ *   status; the host entry stages all of them.  A grid that cannot fit is refused (9001) before any allocation.
+ *
+ * All six: 9001 without a GPU whatever the arguments, 9002 a NULL handle or required array.  On failure the host
+ * entries clear their outputs (with a live handle, whose grid gives their sizes; hist and niter_out always). */
+/* HOST arrays */
+int ndsm_hip_vecpot_alpha_map(void *h, const double *B, const double *alpha0, int polarity, double step,
+                              int max_steps, double *alpha, int32_t *status);
+/* the same on DEVICE arrays of the library's GPU */
+int ndsm_hip_vecpot_alpha_map_device(void *h, const double *dB, const double *dalpha0, int polarity, double step,
+                                     int max_steps, double *dalpha, int32_t *dstatus);
+/* HOST arrays */
+int ndsm_hip_vecpot_solve_current(void *h, int ioptc[16], double ropt[16], const double *J, double *A, double *B);
+/* the same on DEVICE arrays of the library's GPU */
+int ndsm_hip_vecpot_solve_current_device(void *h, int ioptc[16], double ropt[16], const double *dJ, double *dA,
+                                         double *dB);
+/* HOST arrays */
+int ndsm_hip_vecpot_nlfff(void *h, int ioptc[16], double ropt[16], double *B, const double *alpha0, int polarity,
+                          int start, int niter_max, double tol, double step, int max_steps, double *A, double *alpha,
+                          int32_t *status, double *hist, int *niter_out);
+/* the same on DEVICE arrays of the library's GPU (hist and niter_out stay on the host) */
+int ndsm_hip_vecpot_nlfff_device(void *h, int ioptc[16], double ropt[16], double *dB, const double *dalpha0,
+                                 int polarity, int start, int niter_max, double tol, double step, int max_steps,
+                                 double *dA, double *dalpha, int32_t *dstatus, double *hist, int *niter_out);
+
 /* ---- Field-line paths: the points of the same lines (DESIGN.md "Field-line paths") ---------------------------------
  * Where a line runs, not only where it ends: every `every`-th point of each traced line, with B, G and the running
  * integral at it - for drawing lines over a Q map, sampling a field along a loop, or following lines started near a

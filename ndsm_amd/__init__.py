@@ -12,11 +12,13 @@ from ._lib import (load_library, lib_path, MGSolver, VecPot, World, slab_plan, p
                    solenoidal_projection, devore_potentials, FieldLines, trace_field_lines,
                    field_line_helicity, QMap, squashing_factor, seed_plane, Nulls, find_nulls, FieldPaths, trace_paths,
                    path_of, whole_line, Skeleton, find_skeleton, spine_of, fan_of, connections, Separators,
-                   find_separators, separator_of, QPerpMap, perpendicular_squashing, seed_cut)
+                   find_separators, separator_of, QPerpMap, perpendicular_squashing, seed_cut, boundary_alpha,
+                   map_alpha, vector_potential_current, force_free_field)
 
 __all__ = ["vector_potential", "vector_potential_slab", "get_lib_path", "load_library", "lib_path", "MGSolver", "VecPot", "poisson_solve",
            "NdsmHipError", "Helicity", "vector_potential_field", "relative_helicity", "Projection", "solenoidal_projection",
            "devore_potentials", "FieldLines", "trace_field_lines", "field_line_helicity", "QMap",
            "squashing_factor", "seed_plane", "Nulls", "find_nulls", "FieldPaths", "trace_paths", "path_of", "whole_line",
            "Skeleton", "find_skeleton", "spine_of", "fan_of", "connections", "Separators", "find_separators",
-           "separator_of", "QPerpMap", "perpendicular_squashing", "seed_cut"]
+           "separator_of", "QPerpMap", "perpendicular_squashing", "seed_cut", "boundary_alpha", "map_alpha",
+           "vector_potential_current", "force_free_field"]

@@ -97,6 +97,15 @@ def load_library(path=None):
     _tr = [ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5
     L.ndsm_hip_vecpot_trace.argtypes = [ctypes.c_void_p] * 3 + _tr
     L.ndsm_hip_vecpot_trace_device.argtypes = [ctypes.c_void_p] * 3 + _tr
+    _am = [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_double, ctypes.c_int] + [ctypes.c_void_p] * 2
+    L.ndsm_hip_vecpot_alpha_map.argtypes = _am
+    L.ndsm_hip_vecpot_alpha_map_device.argtypes = _am
+    L.ndsm_hip_vecpot_solve_current.argtypes = [ctypes.c_void_p, _ip, _dp, _dp, _dp, _dp]
+    L.ndsm_hip_vecpot_solve_current_device.argtypes = [ctypes.c_void_p, _ip, _dp] + [ctypes.c_void_p] * 3
+    _nl = ([ctypes.c_void_p, _ip, _dp] + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 3 + [ctypes.c_double] * 2 +
+           [ctypes.c_int] + [ctypes.c_void_p] * 3 + [_dp, _ip])
+    L.ndsm_hip_vecpot_nlfff.argtypes = _nl
+    L.ndsm_hip_vecpot_nlfff_device.argtypes = _nl
     _pa = ([ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64] +
            [ctypes.c_void_p] * 11)
     L.ndsm_hip_vecpot_paths.argtypes = [ctypes.c_void_p] * 3 + _pa
@@ -528,6 +537,92 @@ class VecPot:
         self._entry("ndsm_hip_vecpot_trace", [B, G, len(S), S, step, max_steps, direction, *out], device,
                     who="ndsm_hip_vecpot_trace")
         return _field_lines(out, direction)
+
+    def _alpha0_arg(self, alpha0, what):
+        """alpha0 as a flat float64 copy; a shape other than (ny, nx) is an argument error (9002)"""
+        shape = (int(self.nshape4[1]), int(self.nshape4[0]))
+        a = np.asarray(alpha0)
+        if a.shape != shape:
+            raise NdsmHipError(f"{what}: alpha0 of shape {a.shape}, the handle's lower face needs {shape} (code 9002)")
+        return _f64(a).reshape(-1).copy()
+
+    def alpha_map(self, b, alpha0, polarity=1, step=0.5, max_steps=None, device=False):
+        """alpha0 (ny,nx), a function on the lower face z = z[0], carried along the field lines of b (3,nz,ny,nx) to
+        every grid node, on the device (semantics: include/ndsm_hip.h, ndsm_hip_vecpot_alpha_map): the line of each
+        node is followed against b (polarity +1) or along it (-1) with trace()'s step rules; where it ends on the
+        lower face alpha is the bilinear interpolant of alpha0 there, everywhere else 0.  Returns (alpha, status):
+        (nz,ny,nx) float64 and int32 (the TRACE_* code of each node's line).  step, max_steps as trace().
+        device=True: the arrays are staged in device memory and the device-resident entry point runs."""
+        _direction, step, max_steps = self._trace_args(step, max_steps, "both")
+        shape = tuple(int(v) for v in self.nshape4[2::-1])
+        B = self._field_arg(b, "alpha_map")
+        a0 = self._alpha0_arg(alpha0, "alpha_map")
+        alpha = np.zeros(int(np.prod(shape)))
+        status = np.zeros(alpha.size, dtype=np.int32)
+        self._entry("ndsm_hip_vecpot_alpha_map", [B, a0, int(polarity), step, max_steps, alpha, status], device)
+        return alpha.reshape(shape), status.reshape(shape)
+
+    def solve_current(self, b, j, a_init=None, niterex_max=10000, ncycles_max=1024, ex_tol=1e-13, vc_tol=1e-10, ms=5,
+                      mean=False, mixed_precision=False, flxcrl=False, device=False):
+        """Vector potential of a prescribed current j (3,nz,ny,nx): laplace(A_c) = -j_c with the gauge, boundary
+        letters and tangential boundary values of solve()'s potential field for the B.n of b (3,nz,ny,nx; only its
+        six faces are read).  Returns (ierr, A, B), B = curl A + the flux-balance fields; ierr 0 when every solve
+        reached vc_tol, else 1.  j = 0 gives the potential field.  device=True: the arrays are staged in device
+        memory and the device-resident entry point runs."""
+        ioptc, ropt = self._options(niterex_max, ncycles_max, ex_tol, vc_tol, ms, mean, mixed_precision, flxcrl)
+        shape = tuple(int(v) for v in self.nshape4[::-1])
+        B = self._field_arg(b, "solve_current")
+        J = self._field_arg(j, "solve_current")
+        A = np.zeros(B.size) if a_init is None else self._field_arg(a_init, "solve_current")
+        if not device:
+            ierr = self.L.ndsm_hip_vecpot_solve_current(self.h, ioptc.ctypes.data_as(_ip), _d(ropt), _d(J), _d(A), _d(B))
+        else:
+            ierr = self._on_device([J, A, B], lambda dJ, dA, dB: self.L.ndsm_hip_vecpot_solve_current_device(
+                self.h, ioptc.ctypes.data_as(_ip), _d(ropt), dJ, dA, dB))
+        if ierr >= 9000:
+            _check(ierr, "ndsm_hip_vecpot_solve_current", self.L)
+        self.last_ioptc, self.last_ropt = ioptc, ropt
+        return ierr, A.reshape(shape), B.reshape(shape)
+
+    def force_free(self, b, alpha0, polarity=1, start="potential", a_init=None, niter_max=20, tol=0.0, step=0.5,
+                   max_steps=None, niterex_max=10000, ncycles_max=1024, ex_tol=1e-13, vc_tol=1e-10, ms=5, mean=False,
+                   mixed_precision=False, flxcrl=False, device=False):
+        """Nonlinear force-free field, curl B = alpha B, from the B.n of b (3,nz,ny,nx) on the six faces and alpha0
+        (ny,nx) on the lower face, by the Grad-Rubin iteration on the device (semantics: include/ndsm_hip.h,
+        ndsm_hip_vecpot_nlfff).  Each pass is alpha_map() of the current field followed by solve_current() for
+        j = alpha * B, warm-started from the last A, always with the B.n of the input b.  start: "potential" (the
+        first field is solve()'s potential field of b) or "given" (it is b itself, with a_init - None: zeros - as
+        its A).  At most niter_max passes; the loop stops after the pass whose max |B_new - B_old| < tol.  polarity,
+        step, max_steps as alpha_map().  Returns (ierr, A, B, alpha, status, hist): the last pass's fields and alpha
+        map, and hist (npasses, 4): max |B_new - B_old|, the energy 1/2 sum w |B|^2, the current-weighted sine of
+        the angle between curl_h B and B, and the number of nodes whose line reaches the lower face.  ierr 0 when
+        every solve of every pass reached vc_tol, else 1.  device=True: the arrays are staged in device memory and
+        the device-resident entry point runs."""
+        if start not in ("potential", "given"):
+            raise ValueError(f"start must be 'potential' or 'given', not {start!r}")
+        _direction, step, max_steps = self._trace_args(step, max_steps, "both")
+        shape = tuple(int(v) for v in self.nshape4[::-1])
+        B = self._field_arg(b, "force_free")
+        a0 = self._alpha0_arg(alpha0, "force_free")
+        A = np.zeros(B.size) if a_init is None else self._field_arg(a_init, "force_free")
+        ioptc, ropt = self._options(niterex_max, ncycles_max, ex_tol, vc_tol, ms, mean, mixed_precision, flxcrl)
+        alpha = np.zeros(B.size // 3)
+        status = np.zeros(alpha.size, dtype=np.int32)
+        hist = np.zeros((max(int(niter_max), 1), 4))
+        niter = ctypes.c_int(0)
+        args = (int(polarity), 0 if start == "potential" else 1, int(niter_max), float(tol), step, max_steps)
+        if not device:
+            ierr = self.L.ndsm_hip_vecpot_nlfff(self.h, ioptc.ctypes.data_as(_ip), _d(ropt), B.ctypes.data, a0.ctypes.data,
+                                                *args, A.ctypes.data, alpha.ctypes.data, status.ctypes.data, _d(hist),
+                                                ctypes.byref(niter))
+        else:
+            ierr = self._on_device([B, a0, A, alpha, status], lambda dB, da0, dA, dal, dst: self.L.ndsm_hip_vecpot_nlfff_device(
+                self.h, ioptc.ctypes.data_as(_ip), _d(ropt), dB, da0, *args, dA, dal, dst, _d(hist), ctypes.byref(niter)))
+        if ierr >= 9000:
+            _check(ierr, "ndsm_hip_vecpot_nlfff", self.L)
+        self.last_ioptc, self.last_ropt = ioptc, ropt
+        return (ierr, A.reshape(shape), B.reshape(shape), alpha.reshape(shape[1:]), status.reshape(shape[1:]),
+                hist[:niter.value].copy())
 
     def paths(self, b, seeds, g=None, step=0.5, max_steps=None, direction="both", every=1, max_points=None,
               values=True, device=False):
@@ -1296,6 +1391,55 @@ def trace_field_lines(x, y, z, b, seeds, g=None, step=0.5, max_steps=None, direc
     V = _grid_handle(x, y, z, b, 0, lib)
     try:
         return V.trace(b, seeds, g=g, step=step, max_steps=max_steps, direction=direction)
+    finally:
+        V.close()
+
+
+def boundary_alpha(x, y, b, bz_min):
+    """alpha0 (ny,nx) of a field b (3,nz,ny,nx) on its lower face k = 0: (d_x B_y - d_y B_x) / B_z with numpy's
+    second-order differences (np.gradient, edge_order=2) on the mesh vectors x, y; 0 where |B_z| < bz_min.  Plain
+    numpy: the input of force_free() and map_alpha()."""
+    b = np.asarray(b, dtype=np.float64)
+    bx, by, bz = b[0, 0], b[1, 0], b[2, 0]
+    jz = np.gradient(by, _f64(x), axis=1, edge_order=2) - np.gradient(bx, _f64(y), axis=0, edge_order=2)
+    weak = np.abs(bz) < bz_min
+    return np.where(weak, 0.0, jz / np.where(weak, 1.0, bz))
+
+
+def map_alpha(x, y, z, b, alpha0, polarity=1, step=0.5, max_steps=None, lib=None):
+    """alpha0 (ny,nx) on the lower face carried along the field lines of b (3,nz,ny,nx) to every node: one-shot form
+    of VecPot.alpha_map (returns its (alpha, status)).  Raises NdsmHipError on device / runtime failures (>= 9001)."""
+    V = _grid_handle(x, y, z, b, 0, lib)
+    try:
+        return V.alpha_map(b, alpha0, polarity=polarity, step=step, max_steps=max_steps)
+    finally:
+        V.close()
+
+
+def vector_potential_current(x, y, z, b, j, a_init=None, niterex_max=10000, ncycles_max=1024, ex_tol=1e-13,
+                             vc_tol=1e-10, ms=5, mean=False, mixed_precision=False, flxcrl=False, ngrids=0, lib=None):
+    """Vector potential of a prescribed current j (3,nz,ny,nx) with the B.n of b on the six faces: one-shot form of
+    VecPot.solve_current (returns its (ierr, A, B)).  Raises NdsmHipError on device / runtime failures (>= 9001)."""
+    V = _grid_handle(x, y, z, b, ngrids, lib)
+    try:
+        return V.solve_current(b, j, a_init=a_init, niterex_max=niterex_max, ncycles_max=ncycles_max, ex_tol=ex_tol,
+                               vc_tol=vc_tol, ms=ms, mean=mean, mixed_precision=mixed_precision, flxcrl=flxcrl)
+    finally:
+        V.close()
+
+
+def force_free_field(x, y, z, b, alpha0, polarity=1, start="potential", a_init=None, niter_max=20, tol=0.0, step=0.5,
+                     max_steps=None, niterex_max=10000, ncycles_max=1024, ex_tol=1e-13, vc_tol=1e-10, ms=5, mean=False,
+                     mixed_precision=False, flxcrl=False, ngrids=0, lib=None):
+    """Nonlinear force-free field from the B.n of b (3,nz,ny,nx) and alpha0 (ny,nx) on the lower face (e.g.
+    boundary_alpha's) by the Grad-Rubin iteration: one-shot form of VecPot.force_free (returns its (ierr, A, B, alpha,
+    status, hist)).  Raises NdsmHipError on device / runtime failures (>= 9001)."""
+    V = _grid_handle(x, y, z, b, ngrids, lib)
+    try:
+        return V.force_free(b, alpha0, polarity=polarity, start=start, a_init=a_init, niter_max=niter_max, tol=tol,
+                            step=step, max_steps=max_steps, niterex_max=niterex_max, ncycles_max=ncycles_max,
+                            ex_tol=ex_tol, vc_tol=vc_tol, ms=ms, mean=mean, mixed_precision=mixed_precision,
+                            flxcrl=flxcrl)
     finally:
         V.close()
 

@@ -157,6 +157,19 @@ __device__ __forceinline__ void line_snap(const LineArgs &p, int face, const dou
   }
 }
 
+// the mesh, the box and the step of a call into p (the shape and the spacings have been checked)
+inline void line_mesh(const int32_t *n3, const double *lo3, const double *h_dq3, double step, int max_steps,
+                      LineArgs &p) {
+  for (int d = 0; d < 3; ++d) {
+    p.n[d] = n3[d];
+    p.lo[d] = lo3[d];
+    p.h[d] = h_dq3[d];
+    p.hi[d] = lo3[d] + (double)(n3[d] - 1) * h_dq3[d];
+  }
+  p.ds = step * fmin(fmin(h_dq3[0], h_dq3[1]), h_dq3[2]);
+  p.max_steps = max_steps < kLineMaxSteps ? max_steps : kLineMaxSteps;
+}
+
 // The checks and the set-up common to the line entries, after NDSM_REQUIRE_READY: `usage` names the entry and its
 // scalar ranges (own_ok: the entry's own scalar is in range), arrays_ok: every required array is there (looked at
 // only with seeds), per_seed: lines per seed.  0 with p filled, or with nseeds == 0 (nothing to launch); else the
@@ -169,14 +182,7 @@ inline int line_args(const char *usage, bool own_ok, bool arrays_ok, const int32
   NDSM_CHECK_ARG(arrays_ok);
   NDSM_CHECK_ARG(n3[0] >= 2 && n3[1] >= 2 && n3[2] >= 2 && h_dq3[0] > 0.0 && h_dq3[1] > 0.0 && h_dq3[2] > 0.0);
   NDSM_CHECK_ARG((size_t)nseeds * (size_t)per_seed <= (size_t)0x7fffffff);
-  for (int d = 0; d < 3; ++d) {
-    p.n[d] = n3[d];
-    p.lo[d] = lo3[d];
-    p.h[d] = h_dq3[d];
-    p.hi[d] = lo3[d] + (double)(n3[d] - 1) * h_dq3[d];
-  }
-  p.ds = step * fmin(fmin(h_dq3[0], h_dq3[1]), h_dq3[2]);
-  p.max_steps = max_steps < kLineMaxSteps ? max_steps : kLineMaxSteps;
+  line_mesh(n3, lo3, h_dq3, step, max_steps, p);
   p.nseeds = nseeds;
   return 0;
 }

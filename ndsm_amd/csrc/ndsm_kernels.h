@@ -190,6 +190,15 @@ int ndsmk_curl_rhs(const double *B, double *rhs, const int32_t *n3, const double
 int ndsmk_helicity_reduce(const double *A, const double *Ap, const double *B, const double *Bp, const double *Br,
                           const int32_t *n3, const double *h_dq3, double *h_out8);
 
+/* the nonlinear force-free field (field.hip; semantics: include/ndsm_hip.h, ndsm_hip_vecpot_nlfff).  current_rhs: rhs
+ * = -F_c (alpha NULL: F a prescribed current J) or rhs = -(alpha F_c) (F = B, the Grad-Rubin pass: the bits of numpy's
+ * -(alpha * b)), F (nx,ny,nz,3), alpha, rhs (nx,ny,nz) DEVICE arrays; asynchronous.  nlfff_metrics: blocking,
+ * deterministic; h_out4 = [max |B_c - Bold_c|, 1/2 sum w |B|^2, sum w |J x B| / |B| over sum w |J| with J = curl_h B,
+ * the number of ZLO entries of status (nx,ny,nz; int32)]. */
+int ndsmk_current_rhs(const double *F, const double *alpha, double *rhs, const int32_t *n3, int c);
+int ndsmk_nlfff_metrics(const double *B, const double *Bold, const int32_t *status, const int32_t *n3,
+                        const double *h_dq3, double *h_out4);
+
 /* the solenoidal projection (project.hip), all DEVICE arrays: rhs = div_h B - c into the projection solver's
  * level-1 rhs (c = sum w div_h B / sum w stays on the device); B -= G_h phi, the normal component on the end
  * planes of its axis untouched; then, blocking, max |div_h B'| and h_out4 = [c, max |div_h B| before, after,
@@ -215,6 +224,14 @@ enum {
 int ndsmk_trace(const double *B, const double *G, const int32_t *n3, const double *lo3, const double *h_dq3,
                 int nseeds, const double *seeds, double step, int max_steps, int direction, double *ends,
                 double *length, double *integral, int32_t *status, int32_t *nsteps);
+
+/* The alpha map (alphamap.hip; semantics: include/ndsm_hip.h, ndsm_hip_vecpot_alpha_map): alpha0 (nx,ny) on the lower
+ * face carried along the lines of B (nx,ny,nz,3) to every node, alpha (nx,ny,nz) and status (nx,ny,nz; int32, may be
+ * NULL), all DEVICE arrays.  One lane per node (a size_t index: no 2^31 - 1 cap on the nodes), the node is the seed,
+ * the line runs against B (polarity +1) or along it (-1) with ndsmk_trace's step rules.  NDSMK_EVALUE for step <= 0,
+ * max_steps < 1, a polarity other than +1 / -1.  Asynchronous. */
+int ndsmk_alpha_map(const double *B, const int32_t *n3, const double *lo3, const double *h_dq3, const double *alpha0,
+                    int polarity, double step, int max_steps, double *alpha, int32_t *status);
 
 /* Squashing factor and line integrals (squash.hip; semantics: include/ndsm_hip.h, ndsm_hip_vecpot_squash).  B, G (G may
  * be NULL: integrals 0) DEVICE arrays (nx,ny,nz,3); integrand 0: G.B/|B|, 1: G.B/|B|^2; seeds (3,nseeds), q (nseeds),

@@ -1009,6 +1009,197 @@ contains
                                dintegral, dstatus, dnsteps, .true., "ndsm_hip_vecpot_squash_perp_device", dqperp)
   end function
 
+  ! ---- nonlinear force-free field (Grad-Rubin) on the same handle ------------
+  ! Semantics: include/ndsm_hip.h.  Return values of all six: 0, 1 (the solving entries: a 2-D or 3-D solve missed
+  ! vc_tol), or >= 9001 errors (9001 without a GPU whatever the arguments, 9002 a NULL handle or required array, 9004
+  ! a scalar out of range).  The host entries clear their outputs on every failure.
+
+  ! alpha0 (nx,ny) carried along the lines of B (nx,ny,nz,3) to every node: alpha (nx,ny,nz), status (nx,ny,nz; int32,
+  ! may be NULL).  HOST arrays
+  function ndsm_hip_vecpot_alpha_map(handle, B, alpha0, polarity, step, max_steps, alpha, status) &
+      bind(c, name="ndsm_hip_vecpot_alpha_map") result(ierr)
+    type(c_ptr), value :: handle, B, alpha0, alpha, status
+    integer(c_int), value :: polarity, max_steps
+    real(c_double), value :: step
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_alpha_map(handle, B, alpha0, polarity, step, max_steps, alpha, status, .false., &
+                                   "ndsm_hip_vecpot_alpha_map")
+  end function
+
+  ! the same on DEVICE arrays of the library's GPU (nothing is cleared: the outputs are not host memory)
+  function ndsm_hip_vecpot_alpha_map_device(handle, dB, dalpha0, polarity, step, max_steps, dalpha, dstatus) &
+      bind(c, name="ndsm_hip_vecpot_alpha_map_device") result(ierr)
+    type(c_ptr), value :: handle, dB, dalpha0, dalpha, dstatus
+    integer(c_int), value :: polarity, max_steps
+    real(c_double), value :: step
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_alpha_map(handle, dB, dalpha0, polarity, step, max_steps, dalpha, dstatus, .true., &
+                                   "ndsm_hip_vecpot_alpha_map_device")
+  end function
+
+  ! the grid of ctx can size a clearing: live_ctx has given a live context
+  function usable(ctx) result(yes)
+    type(vecpot_ctx), pointer, intent(in) :: ctx
+    logical :: yes
+    yes = associated(ctx)
+    if (yes) yes = ctx%live
+  end function
+
+  function vecpot_handle_alpha_map(handle, B, alpha0, polarity, step, max_steps, alpha, status, on_device, who) &
+      result(ierr)
+    type(c_ptr), intent(in) :: handle, B, alpha0, alpha, status
+    integer(c_int), intent(in) :: polarity, max_steps
+    real(c_double), intent(in) :: step
+    logical, intent(in) :: on_device
+    character(len=*), intent(in) :: who
+    integer(c_int) :: ierr
+    type(vecpot_ctx), pointer :: ctx
+    ierr = live_ctx(handle, ctx)
+    if (ierr == 0 .and. .not. (c_associated(B) .and. c_associated(alpha0) .and. c_associated(alpha))) ierr = NDSMK_EARG
+    if (ierr == 0) ierr = reported(who, vecpot_alpha_map(ctx, B, alpha0, polarity, step, max_steps, alpha, status, &
+                                                         on_device))
+    if (ierr /= 0 .and. .not. on_device .and. usable(ctx)) &
+      call clear_host([alpha, status], [8, 4], spread(product(int(ctx%n3, c_int64_t)), 1, 2))
+  end function
+
+  ! A for a prescribed current J (nx,ny,nz,3): laplace(A_c) = -J_c with the potential field's gauge, boundary letters
+  ! and tangential data.  A: in initial guess, out A; B: in the field whose B.n is kept, out curl A + balance.  HOST
+  ! arrays; options and IOPT_FAIL3D as ndsm_hip_vecpot_solve_field
+  function ndsm_hip_vecpot_solve_current(handle, ioptc, ropt, J, A, B) bind(c, name="ndsm_hip_vecpot_solve_current") &
+      result(ierr)
+    type(c_ptr), value :: handle, J, A, B
+    integer(c_int), intent(inout) :: ioptc(0:OPT_LEN - 1)
+    real(c_double), intent(inout) :: ropt(0:OPT_LEN - 1)
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_current(handle, ioptc, ropt, J, A, B, .false., "ndsm_hip_vecpot_solve_current")
+  end function
+
+  ! the same on DEVICE arrays of the library's GPU
+  function ndsm_hip_vecpot_solve_current_device(handle, ioptc, ropt, dJ, dA, dB) &
+      bind(c, name="ndsm_hip_vecpot_solve_current_device") result(ierr)
+    type(c_ptr), value :: handle, dJ, dA, dB
+    integer(c_int), intent(inout) :: ioptc(0:OPT_LEN - 1)
+    real(c_double), intent(inout) :: ropt(0:OPT_LEN - 1)
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_current(handle, ioptc, ropt, dJ, dA, dB, .true., "ndsm_hip_vecpot_solve_current_device")
+  end function
+
+  function vecpot_handle_current(handle, ioptc, ropt, J, A, B, on_device, who) result(ierr)
+    type(c_ptr), intent(in) :: handle, J, A, B
+    integer(c_int), intent(inout) :: ioptc(0:OPT_LEN - 1)
+    real(c_double), intent(inout) :: ropt(0:OPT_LEN - 1)
+    logical, intent(in) :: on_device
+    character(len=*), intent(in) :: who
+    integer(c_int) :: ierr
+    type(vecpot_ctx), pointer :: ctx
+    integer(ik) :: iopt(0:OPT_LEN - 1)
+    real(c_double) :: t0
+    integer(c_int) :: rc
+    ierr = live_ctx(handle, ctx)
+    if (ierr == 0 .and. .not. (c_associated(J) .and. c_associated(A) .and. c_associated(B))) ierr = NDSMK_EARG
+    if (ierr == 0) then
+      iopt = ioptc
+      verbose = (iopt(IOPT_DEBUG) == 1)
+      t0 = wall_seconds()
+      rc = NDSMK_EARG
+      if (int(iopt(IOPT_NGRIDS)) == ctx%ngr) rc = vecpot_run(ctx, iopt, ropt, A, B, on_device, VP_CURRENT, pJ=J)
+      ropt(ROPT_TIM) = wall_seconds() - t0
+      ioptc = int(iopt, c_int)
+      ierr = reported(who, rc)
+      if (ierr /= 0) ioptc(IOPT_IERR) = ierr            ! (as the field entries: ioptc is written by a call that ran)
+      if (ierr == 0) ierr = int(iopt(IOPT_IERR), c_int)
+    end if
+    if (ierr >= NDSMK_ENODEV) then
+      if (.not. on_device .and. usable(ctx)) &
+        call clear_host([A, B], [8, 8], spread(3_c_int64_t * product(int(ctx%n3, c_int64_t)), 1, 2))
+    end if
+  end function
+
+  ! The Grad-Rubin iteration.  B (nx,ny,nz,3) in: supplies B.n on the six faces (start 1: B^0 as well); out: the last
+  ! pass's field.  alpha0 (nx,ny) in.  A (nx,ny,nz,3): in A^0 with start 1, out the last pass's A.  alpha (nx,ny,nz),
+  ! status (nx,ny,nz; int32, may be NULL), hist (4,niter_max; on the HOST in both entries) and niter_out (one int, on
+  ! the HOST in both entries) out.  HOST arrays
+  function ndsm_hip_vecpot_nlfff(handle, ioptc, ropt, B, alpha0, polarity, start, niter_max, tol, step, max_steps, A, &
+                                 alpha, status, hist, niter_out) bind(c, name="ndsm_hip_vecpot_nlfff") result(ierr)
+    type(c_ptr), value :: handle, B, alpha0, A, alpha, status, hist, niter_out
+    integer(c_int), intent(inout) :: ioptc(0:OPT_LEN - 1)
+    real(c_double), intent(inout) :: ropt(0:OPT_LEN - 1)
+    integer(c_int), value :: polarity, start, niter_max, max_steps
+    real(c_double), value :: tol, step
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_nlfff(handle, ioptc, ropt, B, alpha0, polarity, start, niter_max, tol, step, max_steps, A, &
+                               alpha, status, hist, niter_out, .false., "ndsm_hip_vecpot_nlfff")
+  end function
+
+  ! the same on DEVICE arrays of the library's GPU: nothing crosses PCIe between the passes but the convergence
+  ! read-backs and the four numbers of a history row
+  function ndsm_hip_vecpot_nlfff_device(handle, ioptc, ropt, dB, dalpha0, polarity, start, niter_max, tol, step, &
+                                        max_steps, dA, dalpha, dstatus, hist, niter_out) &
+      bind(c, name="ndsm_hip_vecpot_nlfff_device") result(ierr)
+    type(c_ptr), value :: handle, dB, dalpha0, dA, dalpha, dstatus, hist, niter_out
+    integer(c_int), intent(inout) :: ioptc(0:OPT_LEN - 1)
+    real(c_double), intent(inout) :: ropt(0:OPT_LEN - 1)
+    integer(c_int), value :: polarity, start, niter_max, max_steps
+    real(c_double), value :: tol, step
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_nlfff(handle, ioptc, ropt, dB, dalpha0, polarity, start, niter_max, tol, step, max_steps, dA, &
+                               dalpha, dstatus, hist, niter_out, .true., "ndsm_hip_vecpot_nlfff_device")
+  end function
+
+  function vecpot_handle_nlfff(handle, ioptc, ropt, B, alpha0, polarity, start, niter_max, tol, step, max_steps, A, &
+                               alpha, status, hist, niter_out, on_device, who) result(ierr)
+    type(c_ptr), intent(in) :: handle, B, alpha0, A, alpha, status, hist, niter_out
+    integer(c_int), intent(inout) :: ioptc(0:OPT_LEN - 1)
+    real(c_double), intent(inout) :: ropt(0:OPT_LEN - 1)
+    integer(c_int), intent(in) :: polarity, start, niter_max, max_steps
+    real(c_double), intent(in) :: tol, step
+    logical, intent(in) :: on_device
+    character(len=*), intent(in) :: who
+    integer(c_int) :: ierr
+    type(vecpot_ctx), pointer :: ctx
+    type(nlfff_args) :: nl
+    integer(ik) :: iopt(0:OPT_LEN - 1)
+    integer(c_int), pointer :: nout
+    real(c_double) :: t0
+    integer(c_int) :: rc
+    if (c_associated(niter_out)) then
+      call c_f_pointer(niter_out, nout)
+      nout = 0
+    end if
+    ierr = live_ctx(handle, ctx)
+    if (ierr == 0 .and. .not. (c_associated(B) .and. c_associated(alpha0) .and. c_associated(A) .and. &
+                               c_associated(alpha) .and. c_associated(hist) .and. c_associated(niter_out))) &
+      ierr = NDSMK_EARG
+    if (ierr == 0 .and. ((polarity /= 1 .and. polarity /= -1) .or. start < 0 .or. start > 1 .or. niter_max < 1 .or. .not. (tol >= 0.0_c_double) &
+                         .or. tol > huge(tol) .or. .not. (step > 0.0_c_double) .or. step > 1.0e300_c_double .or. &
+                         max_steps < 1)) &
+      ierr = ndsmk_note_error(NDSMK_EVALUE, "nlfff: polarity +1 or -1, start 0 or 1, niter_max >= 1, tol >= 0 (finite), "// &
+                              "step > 0 (finite) and max_steps >= 1"//c_null_char)
+    if (ierr == 0) then
+      nl%alpha0 = alpha0; nl%alpha = alpha; nl%status = status; nl%hist = hist
+      nl%polarity = polarity; nl%start = start; nl%niter_max = niter_max; nl%max_steps = max_steps
+      nl%tol = tol; nl%step = step
+      iopt = ioptc
+      verbose = (iopt(IOPT_DEBUG) == 1)
+      t0 = wall_seconds()
+      rc = NDSMK_EARG
+      if (int(iopt(IOPT_NGRIDS)) == ctx%ngr) rc = vecpot_nlfff(ctx, iopt, ropt, A, B, nl, on_device)
+      ropt(ROPT_TIM) = wall_seconds() - t0
+      ioptc = int(iopt, c_int)
+      ierr = reported(who, rc)
+      if (ierr /= 0) ioptc(IOPT_IERR) = ierr            ! (as the field entries: ioptc is written by a call that ran)
+      if (ierr == 0) then
+        nout = nl%niter
+        ierr = int(iopt(IOPT_IERR), c_int)
+      end if
+    end if
+    if (ierr >= NDSMK_ENODEV) then
+      if (c_associated(hist) .and. niter_max >= 1) call clear_host([hist], [32], [int(niter_max, c_int64_t)])
+      if (.not. on_device .and. usable(ctx)) &
+        call clear_host([A, B, alpha, status], [24, 24, 8, 4], spread(product(int(ctx%n3, c_int64_t)), 1, 4))
+    end if
+  end function
+
   ! ---- shared by the handle entries of the line and null calls below ----------
   ! the prologue: the runtime is up (without a device: 9001, whatever the arguments), and handle is that of a live
   ! context, which comes back in ctx; else 9002

@@ -517,6 +517,32 @@ module ndsmh_iface
       integer(c_int), value :: c
       integer(c_int) :: rc
     end function
+    ! ---- the nonlinear force-free field (field.hip, alphamap.hip) ----
+    function ndsmk_current_rhs(F, alpha, rhs, n3, c) bind(c, name="ndsmk_current_rhs") result(rc)
+      import :: c_ptr, c_int, c_int32_t
+      type(c_ptr), value :: F, alpha, rhs
+      integer(c_int32_t), intent(in) :: n3(3)
+      integer(c_int), value :: c
+      integer(c_int) :: rc
+    end function
+    function ndsmk_nlfff_metrics(B, Bold, status, n3, dq3, out4) bind(c, name="ndsmk_nlfff_metrics") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_double
+      type(c_ptr), value :: B, Bold, status
+      integer(c_int32_t), intent(in) :: n3(3)
+      real(c_double), intent(in) :: dq3(3)
+      real(c_double), intent(out) :: out4(4)
+      integer(c_int) :: rc
+    end function
+    function ndsmk_alpha_map(B, n3, lo3, dq3, alpha0, polarity, step, max_steps, alpha, status) &
+        bind(c, name="ndsmk_alpha_map") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_double
+      type(c_ptr), value :: B, alpha0, alpha, status
+      integer(c_int32_t), intent(in) :: n3(3)
+      real(c_double), intent(in) :: lo3(3), dq3(3)
+      integer(c_int), value :: polarity, max_steps
+      real(c_double), value :: step
+      integer(c_int) :: rc
+    end function
     function ndsmk_helicity_reduce(A, Ap, B, Bp, Br, n3, dq3, out8) bind(c, name="ndsmk_helicity_reduce") result(rc)
       import :: c_ptr, c_int, c_int32_t, c_double
       type(c_ptr), value :: A, Ap, B, Bp, Br

@@ -32,8 +32,9 @@ module ndsmh_vecpot
 
   public :: vecpot_solve, poisson_solve
   public :: vecpot_ctx, vecpot_ctx_create, vecpot_ctx_destroy, vecpot_ctx_matches, vecpot_run, vecpot_cache_drop
+  public :: vecpot_alpha_map, vecpot_nlfff, nlfff_args
   public :: vecpot_project, vecpot_devore, vecpot_lines, vecpot_paths, vecpot_nulls, vecpot_skeleton, vecpot_separators
-  public :: VP_POTENTIAL, VP_FIELD, VP_HELICITY
+  public :: VP_POTENTIAL, VP_FIELD, VP_HELICITY, VP_CURRENT, VP_NLFFF
   ! pieces the distributed driver (ndsmh_wvecpot) shares with vecpot_solve
   public :: face_data, face_axis, face_upper, face_t1, face_t2, face_order, face_copy, vecpot_faces, say
   public :: OPT_LEN, IOPT_MS, IOPT_NCYCLES, IOPT_FACE1, IOPT_IERR, IOPT_FLXCRL, IOPT_DEBUG, IOPT_DUMAX, &
@@ -72,7 +73,10 @@ module ndsmh_vecpot
   !   VP_POTENTIAL  the reference pipeline: the potential field of B.n and its A_p (ndsm_vector_solve)
   !   VP_FIELD      A of the whole field B: the 3-D problems get rhs_c = -(curl B)_c, same letters and data
   !   VP_HELICITY   one face phase, then the potential and the field 3-D phases, then the helicity reduction
-  integer, parameter :: VP_POTENTIAL = 0, VP_FIELD = 1, VP_HELICITY = 2
+  !   VP_CURRENT    A for a current J the caller prescribes: the 3-D problems get rhs_c = -J_c; B supplies B.n only
+  !   VP_NLFFF      the Grad-Rubin iteration (DESIGN.md "Nonlinear force-free field"): one face phase, then per pass
+  !                 the alpha map of B^k, the 3-D phase with rhs_c = -(alpha B^k_c) and the post phase -> B^{k+1}
+  integer, parameter :: VP_POTENTIAL = 0, VP_FIELD = 1, VP_HELICITY = 2, VP_CURRENT = 3, VP_NLFFF = 4
 
   ! up to this many points the three 3-D component solves get a hierarchy each and run side by side (vecpot_run)
   integer(ik), parameter :: SIDE3D_MAX = 16_ik * 1024_ik * 1024_ik
@@ -99,6 +103,15 @@ module ndsmh_vecpot
     type(mg_solver) :: sp                   ! the 3-D all-Neumann hierarchy of vecpot_project (created at the first)
     logical :: livep = .false.
     integer(ik) :: foff(6) = 0, ftotal = 0
+  end type
+
+  ! what a Grad-Rubin call takes besides A and B (vecpot_run, mode VP_NLFFF): alpha0 (nx,ny) in, alpha (nx,ny,nz) and
+  ! status (nx,ny,nz; int32; may be c_null_ptr) out, DEVICE arrays; hist (4,niter_max) on the HOST; niter out
+  type :: nlfff_args
+    type(c_ptr) :: alpha0 = c_null_ptr, alpha = c_null_ptr, status = c_null_ptr, hist = c_null_ptr
+    integer(c_int) :: polarity = 1, start = 0, niter_max = 1, max_steps = 1
+    real(wp) :: tol = 0, step = 0.5_wp
+    integer(c_int) :: niter = 0
   end type
 
   ! one array of a host-array line entry in its staging buffer (carve, fetch)
@@ -458,18 +471,47 @@ contains
   !   VP_HELICITY  B: the whole field, read only; A, Ap, Bp: out (both solves start from zero).  The face
   !                phase once; the potential 3-D + post phase -> Ap, Bp; the field 3-D + post phase -> A and
   !                B_rec (library scratch); the reduction of field.hip -> out8.
-  ! Both: IOPT_IERR = 0 if every 2-D and 3-D solve reached vc_tol, else 1 (no Q3'); IOPT_FAIL3D bits 0-2 the
-  ! field solves, 3-5 the potential solves of a helicity call.
+  !   VP_CURRENT   as VP_FIELD, with the right-hand sides -J_c of the caller's current pJ (nx,ny,nz,3; host entry:
+  !                uploaded into the staging array dF(1)); B supplies B.n for the face phase and is not uploaded.
+  !   VP_NLFFF     DEVICE arrays only (vecpot_nlfff stages the host entry's).  B in: supplies B.n, and with start = 1
+  !                is B^0 (A in: A^0); start = 0: B^0, A^0 = the potential field of that B.n from a zero guess (the
+  !                bits of the potential mode on device arrays).  The face phase runs ONCE, from the input B - the
+  !                iterates' B.n equals it only to the solve tolerance.  Then up to niter_max passes (nlfff_loop);
+  !                B^k and B^{k+1} alternate between pB and the library's dB, and the last one ends in pB.
+  ! All of these: IOPT_IERR = 0 if every 2-D and 3-D solve reached vc_tol, else 1 (no Q3'); IOPT_FAIL3D bits 0-2 the
+  ! field solves (of any pass), 3-5 the potential solves of a helicity call.
   ! ------------------------------------------------------------------
-  function vecpot_run(ctx, iopt, ropt, pA, pB, on_device, mode, pAp, pBp, out8) result(rc)
+  ! The field modes keep up to five fields next to the 3-D hierarchy (at least five level-1 arrays): a grid the device
+  ! cannot hold at all is refused (9001) before anything is allocated.  Level-1 arrays of a mode besides the hierarchy:
+  ! A and B (field); five fields (helicity); A, B and J (current); A, two fields B, alpha and the status (Grad-Rubin).
+  function mode_fits(ctx, md) result(rc)
+    type(vecpot_ctx), intent(in) :: ctx
+    integer, intent(in) :: md
+    integer(c_int) :: rc
+    integer(c_size_t) :: fr, tot
+    integer :: k
+    select case (md)
+    case (VP_HELICITY); k = 15
+    case (VP_CURRENT); k = 9
+    case (VP_NLFFF); k = 11
+    case default
+      k = 6
+    end select
+    rc = ndsmk_mem_info(fr, tot); if (rc /= 0) return
+    if (real(product(int(ctx%n3, ik)), wp) * 8.0_wp * real(merge(5, 0, .not. ctx%live3) + k, wp) > real(tot, wp)) &
+      rc = ndsmk_note_error(NDSMK_ENODEV, "the grid needs more device memory than the device has"//c_null_char)
+  end function
+
+  function vecpot_run(ctx, iopt, ropt, pA, pB, on_device, mode, pAp, pBp, out8, pJ, nl) result(rc)
     type(vecpot_ctx), intent(inout), target :: ctx
     integer(ik), intent(inout) :: iopt(0:OPT_LEN - 1)
     real(wp), intent(inout) :: ropt(0:OPT_LEN - 1)
     type(c_ptr), intent(in) :: pA, pB
     logical, intent(in) :: on_device
     integer, intent(in), optional :: mode
-    type(c_ptr), intent(in), optional :: pAp, pBp
+    type(c_ptr), intent(in), optional :: pAp, pBp, pJ
     real(wp), intent(out), optional :: out8(8)
+    type(nlfff_args), intent(inout), optional :: nl
     integer(c_int) :: rc
 
     character(len=*), parameter :: me = "compute_vector_potential"
@@ -487,6 +529,8 @@ contains
     character(len=1) :: bc3(6)
     type(c_ptr) :: dAout, dBout, u3, rhs2, u2, rhs3
     type(c_ptr) :: dBsrc, dAp, dBp, hAdst, hBdst
+    type(c_ptr) :: dJ, dAl                  ! the 3-D right-hand sides are -(dJ)_c, or with dAl -(dAl dJ_c)
+    type(c_ptr) :: dst, scr                 ! the status array of the Grad-Rubin passes; scr: the library's own
     integer(c_size_t) :: nb, off_y, off_z, fr, tot
     type(face_data), target :: fc(6)
 
@@ -495,6 +539,11 @@ contains
     if (present(mode)) md = mode
     field = .false.; shift = 0; any2d = .false.
     dBsrc = c_null_ptr; dAp = c_null_ptr; dBp = c_null_ptr
+    dJ = c_null_ptr; dAl = c_null_ptr; scr = c_null_ptr
+    if (md == VP_NLFFF .and. .not. (on_device .and. present(nl))) then
+      rc = NDSMK_EARG
+      return
+    end if
     n3 = ctx%n3
     use_max = (iopt(IOPT_DUMAX) == 1)
     iopt(IOPT_FAIL3D) = 0
@@ -518,14 +567,8 @@ contains
       hAdst = pA; hBdst = pB
     end if
 
-    ! the field modes keep up to five fields next to the 3-D hierarchy (at least five level-1 arrays): a grid
-    ! the device cannot hold at all is refused before anything is allocated
     if (md /= VP_POTENTIAL) then
-      rc = ndsmk_mem_info(fr, tot); if (rc /= 0) return
-      if (real(nb, wp) * real(merge(5, 0, .not. ctx%live3) + 3 * merge(5, 2, md == VP_HELICITY), wp) > real(tot, wp)) then
-        rc = ndsmk_note_error(NDSMK_ENODEV, "the grid needs more device memory than the device has"//c_null_char)
-        return
-      end if
+      rc = mode_fits(ctx, md); if (rc /= 0) return
     end if
 
     ! ---- device arrays of this call ----------------------------------
@@ -557,6 +600,10 @@ contains
     if (on_device) then
       dAout = pA; dBout = pB
       if (md == VP_FIELD) dBsrc = pB                                 ! (read by the right-hand sides, then overwritten)
+      if (md == VP_CURRENT) dJ = pJ
+      if (md == VP_NLFFF .and. .not. c_associated(ctx%dB)) then      ! the second of the two fields B^k, B^{k+1}
+        rc = ndsmk_alloc(ctx%dB, 3_c_size_t * nb); if (rc /= 0) return
+      end if
       if (md == VP_HELICITY) then
         dBsrc = pB; dAp = pAp; dBp = pBp
         if (.not. c_associated(ctx%dB)) then                         ! B_rec
@@ -585,6 +632,9 @@ contains
         ! the whole field goes up: the right-hand sides are its curl (dB then receives curl A + balance)
         rc = ndsmk_h2d(ctx%dB, pB, 3_c_size_t * nb); if (rc /= 0) goto 900
         dBsrc = ctx%dB
+      else if (md == VP_CURRENT) then
+        rc = stage_field(ctx, 1, pJ); if (rc /= 0) goto 900
+        dJ = ctx%dF(1)
       else if (md == VP_HELICITY) then
         do i = 1, 3
           if (.not. c_associated(ctx%dF(i))) then
@@ -608,7 +658,15 @@ contains
     rc = face_phase(); if (rc /= 0) goto 900
 
     ! ---- 4. + 5. the 3-D phase and the post phase, once or (helicity) twice ----
-    if (md == VP_HELICITY) then
+    if (md == VP_NLFFF) then
+      ! (the caller passes no status: the history still counts the lines, in a scratch array of 4 B/pt)
+      dst = nl%status
+      if (.not. c_associated(dst)) then
+        rc = ndsmk_alloc(scr, nb / 2_c_size_t); if (rc /= 0) goto 900
+        dst = scr
+      end if
+      rc = nlfff_loop(); if (rc /= 0) goto 900
+    else if (md == VP_HELICITY) then
       ! the potential field of the same B.n -> Ap, Bp (FAIL3D bits 3-5) ...
       shift = 3
       dAout = dAp; dBout = dBp
@@ -647,11 +705,54 @@ contains
     rcb = ndsmk_bg_drain()                                  ! every byte of A and B is home (or the first error)
     if (rc == 0) rc = rcb
     if (rc == 0) rc = ndsmk_sync()
+    if (c_associated(scr)) then
+      if (rc /= 0) rcb = ndsmk_sync()                       ! (nothing may still write it)
+      rcb = ndsmk_free(scr)
+    end if
     if (.not. resident) then                                ! keep the peak at A + one hierarchy next time too
       rcb = ndsmk_free(ctx%dB); ctx%dB = c_null_ptr
     end if
 
   contains
+
+    ! The Grad-Rubin passes, after the face phase.  Pass k: alpha^k = the alpha map of B^k; the three solves with
+    ! rhs_c = -(alpha^k B^k_c), warm-started from A^k (pA, which finish3 overwrites component by component);
+    ! B^{k+1} = curl A^{k+1} + balance into the other of the two fields; the history row of the pass.  Every phase is
+    ! the one a VP_CURRENT call with J = alpha^k B^k and the initial guess A^k runs: the same kernels in the same order.
+    function nlfff_loop() result(rc)
+      integer(c_int) :: rc
+      real(wp) :: lo(3), row(4)
+      real(wp), pointer :: hh(:, :)
+      type(c_ptr) :: dBk, dBn, dtmp
+      integer :: it
+      lo = [ctx%qx(1), ctx%qy(1), ctx%qz(1)]
+      call c_f_pointer(nl%hist, hh, [4, int(nl%niter_max)])
+      nl%niter = 0
+      dBk = pB; dBn = ctx%dB
+      if (nl%start == 0) then
+        ! B^0, A^0: the potential field of the input's B.n from a zero guess (pB's faces have been read)
+        rc = ndsmk_fill0(pA, 3_c_size_t * nb); if (rc /= 0) return
+        rc = solve3_phase(); if (rc /= 0) return
+        rc = post_phase(); if (rc /= 0) return
+      end if
+      do it = 1, int(nl%niter_max)
+        call say(me, "Grad-Rubin pass: alpha along the field lines...")
+        rc = ndsmk_alpha_map(dBk, n3, lo, dq, nl%alpha0, nl%polarity, nl%step, nl%max_steps, nl%alpha, dst)
+        if (rc /= 0) return
+        dJ = dBk; dAl = nl%alpha
+        dBout = dBn; bz_done = .false.
+        rc = solve3_phase(); if (rc /= 0) return
+        rc = post_phase(); if (rc /= 0) return
+        rc = ndsmk_nlfff_metrics(dBn, dBk, dst, n3, dq, row); if (rc /= 0) return
+        hh(:, it) = row
+        nl%niter = int(it, c_int)
+        dtmp = dBk; dBk = dBn; dBn = dtmp
+        if (row(1) < nl%tol) exit
+      end do
+      if (.not. c_associated(dBk, pB)) then
+        rc = ndsmk_d2d(pB, dBk, 3_c_size_t * nb); if (rc /= 0) return
+      end if
+    end function
 
     ! 1.-3. B.n of the six faces, their fluxes, the six 2-D solves and chi (A_t is written per component by prep3)
     function face_phase() result(rc)
@@ -826,9 +927,14 @@ contains
           rc = ndsmk_face_write(u3, n3, ctx%dchi, int(f - 1, c_int), int(c - 1, c_int), fac); if (rc /= 0) return
         end if
       end do
-      ! its right-hand side: -(curl B)_c for the whole field, 0 for the potential field (:640-641).  The solvers
-      ! are cached: the state left by the previous call on this context is set either way.
-      if (field) then
+      ! its right-hand side: -J_c or -(alpha B_c) for a prescribed current or a Grad-Rubin pass, -(curl B)_c for the
+      ! whole field, 0 for the potential field (:640-641).  The solvers are cached: the state left by the previous
+      ! call on this context is set either way.
+      if (c_associated(dJ)) then
+        rhs3 = mg_level_ptr(s3, 1, MG_BUF_RHS, cnt)
+        rc = ndsmk_current_rhs(dJ, dAl, rhs3, n3, int(c - 1, c_int)); if (rc /= 0) return
+        call mg_mark_rhs_set(s3)
+      else if (field) then
         rhs3 = mg_level_ptr(s3, 1, MG_BUF_RHS, cnt)
         rc = ndsmk_curl_rhs(dBsrc, rhs3, n3, dq, int(c - 1, c_int)); if (rc /= 0) return
         call mg_mark_rhs_set(s3)
@@ -1240,6 +1346,105 @@ contains
         rc = ndsmk_trace(B, G, n3, lo, dq, nseeds, seeds, step, max_steps, sel, ends, length, integral, status, nsteps)
       end if
     end function
+  end function
+
+  ! ------------------------------------------------------------------
+  ! The alpha map on a prepared context (semantics in include/ndsm_hip.h, DESIGN.md "Nonlinear force-free field"):
+  ! palpha0 (nx,ny) on the lower face carried along the lines of pB (nx,ny,nz,3) to every node, palpha (nx,ny,nz) and
+  ! pstat (nx,ny,nz; int32, may be c_null_ptr) out - on the HOST (B goes up into the staging array dF(1), alpha0 and
+  ! the results through a scratch buffer) or (on_device) in HBM.  The context supplies the mesh only, as in
+  ! vecpot_lines: no solve, no hierarchy.
+  ! ------------------------------------------------------------------
+  function vecpot_alpha_map(ctx, pB, palpha0, polarity, step, max_steps, palpha, pstat, on_device) result(rc)
+    type(vecpot_ctx), intent(inout), target :: ctx
+    logical, intent(in) :: on_device
+    type(c_ptr), intent(in) :: pB, palpha0, palpha, pstat
+    integer(c_int), intent(in) :: polarity, max_steps
+    real(wp), intent(in) :: step
+    integer(c_int) :: rc
+    real(wp) :: dq(3), lo(3)
+    integer(c_int32_t) :: n3(3)
+    integer(c_size_t) :: np, nf
+    type(c_ptr) :: buf
+    type(slice) :: s(3)
+
+    call ctx_mesh(ctx, n3, lo, dq)
+    if (on_device .or. .not. (step > 0.0_wp) .or. max_steps < 1 .or. (polarity /= 1 .and. polarity /= -1)) then
+      ! (the argument errors are the kernel entry's to name; nothing is staged for them)
+      rc = ndsmk_alpha_map(pB, n3, lo, dq, palpha0, polarity, step, max_steps, palpha, pstat)
+      if (rc == 0) rc = ndsmk_sync()
+      return
+    end if
+    nf = int(n3(1), c_size_t) * int(n3(2), c_size_t)
+    np = nf * int(n3(3), c_size_t)
+    rc = stage_field(ctx, 1, pB); if (rc /= 0) return
+    s = [slice(palpha0, 8, nf, GOES_UP), slice(palpha, 8, np, COMES_HOME), slice(pstat, 4, np, COMES_HOME)]
+    rc = carve(buf, s)
+    if (rc == 0) then
+      call say("alpha_map", "Carrying alpha along the field lines...")
+      rc = ndsmk_alpha_map(ctx%dF(1), n3, lo, dq, s(1)%dev, polarity, step, max_steps, s(2)%dev, s(3)%dev)
+    end if
+    if (rc == 0) rc = fetch(s)
+    if (rc == 0) rc = ndsmk_sync()
+    call unstage(rc, [buf])
+  end function
+
+  ! ------------------------------------------------------------------
+  ! The Grad-Rubin iteration on a prepared context (vecpot_run, mode VP_NLFFF; semantics in include/ndsm_hip.h).  nl
+  ! holds the caller's alpha0, alpha, status (may be c_null_ptr: vecpot_run's scratch takes its place) and hist, and the
+  ! scalars, which the C ABI has checked; nl%niter comes back.  pA, pB (nx,ny,nz,3) and nl's three arrays on the HOST
+  ! (B, and with start = 1 A, go up into the staging arrays dF(1) and dA, alpha0 and the results through a scratch
+  ! buffer; between the upload and the downloads nothing crosses PCIe but the fluxes and the per-cycle and per-pass
+  ! read-backs) or (on_device) in HBM.  A grid whose arrays the device cannot hold is refused before anything is
+  ! allocated.
+  ! ------------------------------------------------------------------
+  function vecpot_nlfff(ctx, iopt, ropt, pA, pB, nl, on_device) result(rc)
+    type(vecpot_ctx), intent(inout), target :: ctx
+    integer(ik), intent(inout) :: iopt(0:OPT_LEN - 1)
+    real(wp), intent(inout) :: ropt(0:OPT_LEN - 1)
+    type(c_ptr), intent(in) :: pA, pB
+    type(nlfff_args), intent(inout) :: nl
+    logical, intent(in) :: on_device
+    integer(c_int) :: rc
+    type(nlfff_args) :: dv
+    integer(c_size_t) :: np, nf, nb3
+    type(c_ptr) :: buf
+    type(slice) :: s(3)
+
+    nl%niter = 0
+    nf = int(ctx%n3(1), c_size_t) * int(ctx%n3(2), c_size_t)
+    np = nf * int(ctx%n3(3), c_size_t)
+    nb3 = np * 24_c_size_t
+    buf = c_null_ptr
+    dv = nl
+    if (.not. on_device) then
+      rc = mode_fits(ctx, VP_NLFFF); if (rc /= 0) return
+      if (.not. c_associated(ctx%dA)) then
+        rc = ndsmk_alloc(ctx%dA, nb3); if (rc /= 0) return
+      end if
+      rc = stage_field(ctx, 1, pB); if (rc /= 0) return
+      if (nl%start == 1) then
+        rc = ndsmk_h2d(ctx%dA, pA, nb3); if (rc /= 0) return
+      end if
+      s = [slice(nl%alpha0, 8, nf, GOES_UP), slice(nl%alpha, 8, np, COMES_HOME), slice(nl%status, 4, np, COMES_HOME)]
+      rc = carve(buf, s)
+      dv%alpha0 = s(1)%dev; dv%alpha = s(2)%dev; dv%status = s(3)%dev
+    else
+      rc = 0
+    end if
+    if (rc == 0) then
+      if (on_device) then
+        rc = vecpot_run(ctx, iopt, ropt, pA, pB, .true., VP_NLFFF, nl=dv)
+      else
+        rc = vecpot_run(ctx, iopt, ropt, ctx%dA, ctx%dF(1), .true., VP_NLFFF, nl=dv)
+        if (rc == 0) rc = ndsmk_d2h(pA, ctx%dA, nb3)
+        if (rc == 0) rc = ndsmk_d2h(pB, ctx%dF(1), nb3)
+        if (rc == 0) rc = fetch(s)
+        if (rc == 0) rc = ndsmk_sync()
+      end if
+    end if
+    nl%niter = dv%niter
+    call unstage(rc, [buf])
   end function
 
   ! ------------------------------------------------------------------

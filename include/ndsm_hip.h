@@ -128,7 +128,8 @@ int ndsm_hip_mg_set_ms(void *handle, int ms);
 /* mode 0 fp64, 1 mixed where level 1 is large (>= 6 M points), 2 mixed wherever the fp32 kernels cover
  * level 1.  Returns 1 if ndsm_hip_mg_solve will run in mixed precision, 0 if fp64, < 0 bad mode. */
 int ndsm_hip_mg_set_precision(void *handle, int mode);
-/* which: 0 = u, 1 = rhs, 2 = residual scratch (level-1 sized) */
+/* which: 0 = u, 1 = rhs, 2 = residual scratch (level-1 sized), 3 = the partner array of u (out-of-place smoother
+ * passes leave the result there and the two swap; for tests) */
 int ndsm_hip_mg_upload(void *handle, int level, int which, const double *host);
 int ndsm_hip_mg_download(void *handle, int level, int which, double *host);
 /* declare rhs(1) == 0 (Laplace problem, the vector-potential case): kernels skip reading it; same bits */
@@ -895,6 +896,19 @@ int ndsm_hip_bound_libs(char *buf, int len);
  * parity tests can run the benchmarked 512^3 configurations on grids the oracle handles.
  * Results never depend on these values (bit for bit); only speed does. */
 int ndsm_hip_debug_fused_cfg(int two, int one, int res, int work_items, int big);
+/* Which launches a relax call makes (what = 0), or the z chunking of a fused launch (what = 1), as the one planner
+ * behind every smoother entry decides them ("Which launch a relax call makes").  Host code: works without
+ * a device and without ndsm_hip_init.
+ * what = 0: grid[15] = ndim, n[3], lb[3], ub[3], all_neumann, k0, nzg, zown0, zown1; req[12] = nsweeps, variant,
+ *   window, fp32, rhs, want_res, want_met, corr, coarse_plane, have[1], have[2], keep; knobs[8] = the five values of
+ *   NDSM_FUSED_CFG, the two of NDSM_BLOCK_CFG, NDSM_HIP_NO_BLOCK.  out[0..5] = error code, passes, result buffer,
+ *   residual covered, metric covered, interpolation only; then nine values per pass: kind, sweeps, mode,
+ *   instantiation, block height, src, dst, interpolation first, mean shift.
+ * what = 1: req[6] = owned planes, tiles, workgroup slots, pipeline depth, residual pipeline, work-item override;
+ *   out[0..1] = chunks, planes per chunk.
+ * Returns 9002 for a null array, a value out of range or cap (entries of out) too small for the answer. */
+int ndsm_hip_debug_relax_plan(int what, const int32_t *grid, const int64_t *req, const int64_t *knobs, int cap,
+                              int32_t *out);
 /* 0: the small levels at the bottom of a V-cycle run kernel by kernel even where the single-launch form
  * (csrc/tail.hip: all of them resident in LDS, one workgroup) covers them; 1 = default (environment
  * NDSM_HIP_NO_TAIL switches it off for a whole process).  Same bits either way. */

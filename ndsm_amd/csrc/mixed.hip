@@ -17,10 +17,12 @@
 // (u' = u + e ; e' = 0 ; r = rhs - L u' ; max|e|, sum|e|), and the fp32 smoother driver.  The level-1
 // arrays cost 8 + 4 + 4 + 4 + 4 B per point instead of 8 x 4.
 #include "common.hpp"
+#include "relax_plan.hpp"
 
 namespace ndsm {
-int launch_rbgs3_fused_f32(const ndsmk_grid &g, const float *u, float *uout, const float *rhs, int max_sweeps,
-                           bool force, int *sweeps_done, float *rout, int *res_done);
+plan::Knobs relax_knobs();
+int launch_rbgs3_fused_f32(const plan::Pass &p, const ndsmk_grid &g, const float *u, float *uout, const float *rhs,
+                           float *rout);
 }
 
 namespace {
@@ -284,22 +286,19 @@ extern "C" int ndsmk_relax_f32(const ndsmk_grid *gp, float *e, float *ealt, cons
   NDSM_CHECK_ARG(g.ndim == 3 && e && ealt && r && result_in_alt && nsweeps >= (r_out ? 1 : 0));
   NDSM_CHECK_ARG(!g.all_neumann);
   *result_in_alt = 0;
-  float *cur = e, *oth = ealt;
-  int res_done = 0;
-  for (int sw = 0; sw < nsweeps;) {
-    int ndone = 0, rd = 0;
-    int rc = ndsm::launch_rbgs3_fused_f32(g, cur, oth, r, nsweeps - sw, force != 0, &ndone, r_out, &rd);
-    if (rc) return rc;
-    if (ndone <= 0)
-      return ndsm::fail(NDSMK_EARG, "fp32 smoother: the fused kernel does not cover this level", __FILE__, __LINE__);
-    res_done |= rd;
-    sw += ndone;
-    float *t = cur;
-    cur = oth;
-    oth = t;
-  }
-  if (r_out && !res_done)
+  ndsm::plan::Request rq;
+  rq.fp32 = true;
+  rq.nsweeps = nsweeps;
+  rq.variant = force ? 2 : 0;
+  rq.want_res = r_out != nullptr;
+  rq.have[1] = true;
+  const ndsm::plan::Plan pl = ndsm::plan::relax_plan(g, rq, ndsm::relax_knobs());
+  if (pl.err) return ndsm::fail(pl.err, pl.what, __FILE__, __LINE__);
+  if (r_out && !pl.res_done)
     return ndsm::fail(NDSMK_EARG, "fp32 smoother: no residual stage was run", __FILE__, __LINE__);
-  *result_in_alt = (cur != e) ? 1 : 0;
+  float *const bufs[2] = {e, ealt};
+  for (const ndsm::plan::Pass &p : pl.pass)
+    if (int rc = ndsm::launch_rbgs3_fused_f32(p, g, bufs[p.src], bufs[p.dst], r, r_out)) return rc;
+  *result_in_alt = pl.result;
   return 0;
 }

@@ -372,6 +372,8 @@ int ndsmk_prolong_add_f32(const ndsmk_xfer *x, const double *u_c, float *e_f);
 
 /* tests / tuning: the five values of NDSM_FUSED_CFG (smooth_fused.hip) at run time */
 int ndsmk_debug_fused_cfg(int two, int one, int res, int work_items, int big);
+/* the plan of a relax call / the z chunking of a fused launch, on the host (smooth.hip has the array layouts) */
+int ndsmk_debug_relax_plan(int what, const int32_t *grid, const int64_t *req, const int64_t *knobs, int cap, int32_t *out);
 
 #ifdef __cplusplus
 }

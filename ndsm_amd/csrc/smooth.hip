@@ -13,17 +13,29 @@
 //   rbgs3_fused   : one launch per sweep (see smooth_fused.hip)
 //   rbgs3_block_k : two sweeps per launch on the cache-resident levels in between (see smooth_block.hip)
 #include "common.hpp"
+#include "relax_plan.hpp"
 
 namespace ndsm {
 void fused_metric_accumulate(bool on);
-int launch_rbgs3_fused(const ndsmk_grid &g, const double *u, double *uout, const double *rhs, int max_sweeps,
-                       bool force, int *sweeps_done, double *rout, int *res_done, const double *prev, int *met_done,
-                       const ndsmk_xfer *px, const double *uc);
-int launch_rbgs3_block(const ndsmk_grid &g, const double *u, double *uout, const double *rhs, int max_sweeps,
-                       int *sweeps_done);
-int64_t block_smoother_first_below();
+const int *fused_cfg();
+const int64_t *block_cfg();
+bool block_smoother_on();
+int64_t fused_coarse_plane(const ndsmk_grid &g, const ndsmk_xfer *px);
+int launch_rbgs3_fused(const plan::Pass &p, const ndsmk_grid &g, const double *u, double *uout, const double *rhs,
+                       double *rout, const double *prev, const ndsmk_xfer *px, const double *uc);
+int launch_rbgs3_block(const ndsmk_grid &g, const double *u, double *uout, const double *rhs, int sweeps, int bz);
 int fetch_fused_metric(double *h_out2);
 int launch_mean_shift(double *u, int64_t n);
+
+// the development knobs as the planner takes them (the environment is read where each knob lives)
+plan::Knobs relax_knobs() {
+  plan::Knobs kn;
+  for (int i = 0; i < 5; ++i) kn.fused[i] = fused_cfg()[i];
+  kn.block[0] = block_cfg()[0];
+  kn.block[1] = block_cfg()[1];
+  kn.block_on = block_smoother_on();
+  return kn;
+}
 }
 
 namespace {
@@ -166,7 +178,7 @@ __global__ __launch_bounds__(1024) void rbgs2_small(double *__restrict__ u_g, co
 // from global memory (L2-resident: one 8-byte read per update).  A level of 16384 points otherwise
 // costs ~5 launches per sweep (two colours, two-stage mean, subtraction), i.e. ~50 dispatch
 // latencies per level visit; this is one.
-constexpr int kMed2D = 19456;
+using ndsm::plan::kMed2D;
 __global__ __launch_bounds__(1024) void rbgs2_medium(double *__restrict__ u_g, const double *__restrict__ rhs_g,
                                                      ndsmk_grid g, int nsweeps) {
   extern __shared__ __attribute__((aligned(16))) double u[];  // the whole level
@@ -267,173 +279,85 @@ __global__ __launch_bounds__(256) void rbgs2_color(double *__restrict__ u, const
 
 }  // namespace
 
-// The sweeps of one relax call.  bufs[0] holds u on entry; the out-of-place fused and block passes write to
-// whichever of bufs[0..2] is neither the current one nor `keep` (bufs[2] may be null: plain
-// ping-pong); *where tells which buffer holds the result.  keep: a buffer that must survive (the
-// iterate the V-cycle started from, which the convergence metric is taken against); prev: evaluate
-// that metric in the launch of the last sweep (*met_done).  rout: residual on the last sweep.
-// px / uc: u += P uc comes first (coarse_to_fine); folded into the loads of the first launch
-// where that launch is the two-sweep Laplace one, else done by the stand-alone kernel.
+
+// the two colour passes of one sweep, in place
+static int launch_color(const ndsmk_grid &g, double *u, const double *rhs) {
+  const int half = (g.ub[0] - g.lb[0] + 2) / 2, my = g.ub[1] - g.lb[1] + 1;
+  const dim3 block(64, 4, 1);
+  const dim3 grid((half + 63) / 64, (my + 3) / 4, g.ndim == 3 ? g.ub[2] - g.lb[2] + 1 : 1);
+  for (int pass = 0; pass < 2; ++pass) {
+    if (g.ndim == 3)
+      hipLaunchKernelGGL(rbgs3_color, grid, block, 0, ndsm::stream(), u, rhs, g, (g.first_par + pass) & 1);
+    else
+      hipLaunchKernelGGL(rbgs2_color, grid, block, 0, ndsm::stream(), u, rhs, g, (g.first_par + pass) & 1);
+    NDSM_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+// The sweeps of one relax call, as plan::relax_plan (relax_plan.hpp; DESIGN.md "Which launch a relax call makes")
+// lays them out.  bufs[0] holds u on entry; the out-of-place fused and block passes write to whichever of
+// bufs[0..2] is neither the current one nor `keep` (bufs[2] may be null: plain ping-pong); *where tells which
+// buffer holds the result.  keep: a buffer that must survive (the iterate the V-cycle started from, which the
+// convergence metric is taken against); prev: evaluate that metric in the launch of the last sweep (*met_done).
+// rout: residual on the last sweep (*res_done).  px / uc: u += P uc comes first (coarse_to_fine).
 static int relax_impl(const ndsmk_grid *gp, double *const bufs[3], const double *keep, const double *rhs, int nsweeps,
                       int variant, int *where, double *rout, int *res_done, const double *prev, int *met_done,
                       const ndsmk_xfer *px = nullptr, const double *uc = nullptr) {
   NDSM_REQUIRE_READY();
-  if (res_done) *res_done = 0;
-  if (met_done) *met_done = 0;
   const ndsmk_grid g = *gp;
-  NDSM_CHECK_ARG(g.ndim == 2 || g.ndim == 3);
-  NDSM_CHECK_ARG(g.n[0] >= 2 && g.n[1] >= 2 && (g.ndim == 2 ? g.n[2] == 1 : g.n[2] >= 2));
-  for (int d = 0; d < g.ndim; ++d) NDSM_CHECK_ARG(g.lb[d] >= 0 && g.ub[d] <= g.n[d] - 1);
-  NDSM_CHECK_ARG(variant >= 0 && variant <= 2);
-  NDSM_CHECK_ARG(g.ndim == 2 || (g.zown0 >= 0 && g.zown1 <= g.n[2] && g.zown0 < g.zown1));
+  ndsm::plan::Request rq;
+  rq.nsweeps = nsweeps;
+  rq.variant = variant;
+  rq.rhs = rhs != nullptr;
+  rq.want_res = rout != nullptr;
+  rq.want_met = prev != nullptr;
+  rq.corr = px != nullptr;
+  if (px) rq.coarse_plane = ndsm::fused_coarse_plane(g, px);
+  for (int c = 0; c < 3; ++c) {
+    rq.have[c] = bufs[c] != nullptr;
+    if (keep && bufs[c] == keep) rq.keep = c;
+  }
+  const ndsm::plan::Plan pl = ndsm::plan::relax_plan(g, rq, ndsm::relax_knobs());
+  if (pl.err) return ndsm::fail(pl.err, pl.what, __FILE__, __LINE__);
+  if (res_done) *res_done = pl.res_done;
+  if (met_done) *met_done = pl.met_done;
+  if (where) *where = pl.result;
+  if (pl.prolong_only) return ndsmk_prolong_add(px, uc, bufs[0]);
   const int64_t npts = (int64_t)g.n[0] * g.n[1] * g.n[2];
   hipStream_t s = ndsm::stream();
-  const int mx = g.ub[0] - g.lb[0] + 1, my = g.ub[1] - g.lb[1] + 1, mz = g.ub[2] - g.lb[2] + 1;
-  int cur = 0;
-  if (where) *where = 0;
-  bool prol_pending = px != nullptr;
-  if (prol_pending && (nsweeps <= 0 || mx <= 0 || my <= 0 || (g.ndim == 3 && mz <= 0))) {
-    if (int rc = ndsmk_prolong_add(px, uc, bufs[0])) return rc;
-    prol_pending = false;
-  }
-  if (mx <= 0 || my <= 0 || (g.ndim == 3 && mz <= 0)) return 0;  // nothing to update
-  // an in-place kernel may not touch the buffer the caller wants kept
-  auto in_place_ok = [&]() { return keep == nullptr || bufs[cur] != keep; };
-  // small 3-D level: every sweep in one single-workgroup launch
-  if (g.ndim == 3 && variant == 0 && !g.all_neumann && npts <= 4096 && g.k0 == 0 && g.zown0 == 0 &&
-      g.zown1 == g.n[2] && nsweeps > 0) {
-    NDSM_CHECK_ARG(in_place_ok());
-    if (prol_pending) {
-      if (int rc = ndsmk_prolong_add(px, uc, bufs[0])) return rc;
+  for (const ndsm::plan::Pass &p : pl.pass) {
+    double *u = bufs[p.src], *uout = bufs[p.dst];
+    int rc = p.prolong_first ? ndsmk_prolong_add(px, uc, u) : 0;
+    if (rc) return rc;
+    switch (p.kind) {
+      case ndsm::plan::SMALL3D:
+        hipLaunchKernelGGL(rbgs3_small, dim3(1), dim3(1024), 0, s, u, rhs, g, p.sweeps);
+        break;
+      case ndsm::plan::SMALL2D:
+        hipLaunchKernelGGL(rbgs2_small, dim3(1), dim3(1024), 0, s, u, rhs, g, p.sweeps);
+        break;
+      case ndsm::plan::MEDIUM2D: {
+        static int attr_epoch = 0;
+        if (ndsm::first_in_epoch(attr_epoch))
+          NDSM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(rbgs2_medium), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       kMed2D * (int)sizeof(double)));
+        hipLaunchKernelGGL(rbgs2_medium, dim3(1), dim3(1024), (size_t)npts * sizeof(double), s, u, rhs, g, p.sweeps);
+        break;
+      }
+      case ndsm::plan::FUSED: rc = ndsm::launch_rbgs3_fused(p, g, u, uout, rhs, rout, prev, px, uc); break;
+      case ndsm::plan::BLOCK: rc = ndsm::launch_rbgs3_block(g, u, uout, rhs, p.sweeps, p.bz); break;
+      default: rc = launch_color(g, u, rhs); break;
     }
-    hipLaunchKernelGGL(rbgs3_small, dim3(1), dim3(1024), 0, s, bufs[0], rhs, g, nsweeps);
+    if (rc) return rc;
     NDSM_LAUNCH_CHECK();
-    return 0;
-  }
-  // small 2-D level: likewise (incl. the mean shift of all-Neumann problems)
-  if (g.ndim == 2 && variant == 0 && npts <= 4096 && nsweeps > 0) {
-    NDSM_CHECK_ARG(in_place_ok());
-    if (prol_pending) {
-      if (int rc = ndsmk_prolong_add(px, uc, bufs[0])) return rc;
-    }
-    hipLaunchKernelGGL(rbgs2_small, dim3(1), dim3(1024), 0, s, bufs[0], rhs, g, nsweeps);
-    NDSM_LAUNCH_CHECK();
-    return 0;
-  }
-  // mid-size 2-D level: the same single-workgroup scheme, u in (dynamic) LDS only
-  if (g.ndim == 2 && variant == 0 && npts <= kMed2D && nsweeps > 0) {
-    NDSM_CHECK_ARG(in_place_ok());
-    if (prol_pending) {
-      if (int rc = ndsmk_prolong_add(px, uc, bufs[0])) return rc;
-    }
-    static int attr_epoch = 0;
-    if (ndsm::first_in_epoch(attr_epoch))
-      NDSM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(rbgs2_medium), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   kMed2D * (int)sizeof(double)));
-    hipLaunchKernelGGL(rbgs2_medium, dim3(1), dim3(1024), (size_t)npts * sizeof(double), s, bufs[0], rhs, g, nsweeps);
-    NDSM_LAUNCH_CHECK();
-    return 0;
-  }
-  for (int sw = 0; sw < nsweeps; ++sw) {
-    double *u = bufs[cur];
-    if (g.ndim == 3) {
-      bool done = false;
-      if (variant != 1) {
-        // destination of an out-of-place pass: not the current buffer, not the kept one
-        int dst = -1;
-        for (int c = 0; c < 3; ++c)
-          if (c != cur && bufs[c] && bufs[c] != keep) {
-            dst = c;
-            break;
-          }
-        // all-Neumann levels shift the mean after EVERY sweep: one sweep per pass there
-        int ndone = 0;
-        // the block-resident launch (two sweeps, or a last single one) takes the whole, not all-Neumann levels
-        // above the single-workgroup limit that the fused launcher declines - up to 512 K points: measured per five
-        // sweeps at 32^3 / 64^3 / 96^3 / 128^3, block 19 / 28 / 65 / 123 us, colour passes 28 / 38 / 56 / 107 us,
-        // fused 62 / 65 / 67 / 73 us (scripts/time_small_levels.py, profiles/block_levels.txt; the lines cross near 600 K)
-        const int64_t blk_first_below = ndsm::block_smoother_first_below();   // (development knob: default 0)
-        const bool blk = variant == 0 && dst >= 0 && !g.all_neumann && npts > 4096 && g.k0 == 0 && g.zown0 == 0 &&
-                         g.zown1 == g.n[2] && (npts < (int64_t)512 * 1024 || npts < blk_first_below);
-        const bool blk_first = blk && npts < blk_first_below;
-        if (prol_pending) {  // first pass: try the launch that interpolates while it loads
-          int rc = blk_first ? 0
-                             : ndsm::launch_rbgs3_fused(g, u, dst >= 0 ? bufs[dst] : nullptr, rhs,
-                                                        g.all_neumann ? 1 : nsweeps - sw, variant == 2, &ndone, nullptr,
-                                                        nullptr, nullptr, nullptr, px, uc);
-          if (rc) return rc;
-          if (ndone == 0) {  // not that launch: interpolate in place, then sweep as usual
-            NDSM_CHECK_ARG(in_place_ok());
-            rc = ndsmk_prolong_add(px, uc, u);
-            if (rc) return rc;
-          }
-          prol_pending = false;
-        }
-        // the residual rides on the last sweep (not on all-Neumann levels: the mean shift comes in between)
-        int rc = ndone > 0 || blk_first
-                     ? 0
-                     : ndsm::launch_rbgs3_fused(g, u, dst >= 0 ? bufs[dst] : nullptr, rhs,
-                                                g.all_neumann ? 1 : nsweeps - sw, variant == 2, &ndone,
-                                                g.all_neumann ? nullptr : rout, res_done,
-                                                g.all_neumann ? nullptr : prev, met_done, nullptr, nullptr);
-        if (rc) return rc;
-        if (ndone == 0 && blk) {
-          rc = ndsm::launch_rbgs3_block(g, u, bufs[dst], rhs, nsweeps - sw, &ndone);
-          if (rc) return rc;
-        }
-        done = ndone > 0;
-        if (done) {  // the sweeps landed in the other array
-          sw += ndone - 1;
-          cur = dst;
-          u = bufs[cur];
-        }
-        if (!done && variant == 2)
-          return ndsm::fail(NDSMK_EARG, "fused smoother does not support this level shape", __FILE__, __LINE__);
-      }
-      if (!done && prol_pending) {
-        NDSM_CHECK_ARG(in_place_ok());
-        if (int rc = ndsmk_prolong_add(px, uc, u)) return rc;
-        prol_pending = false;
-      }
-      if (!done) {
-        if (g.zown0 != 0 || g.zown1 != g.n[2])
-          return ndsm::fail(NDSMK_EARG, "z-slab levels need the fused smoother (nx even, >= 16 x 16 x 8 owned)", __FILE__,
-                            __LINE__);
-        NDSM_CHECK_ARG(in_place_ok());
-        const int half = (mx + 1) / 2;
-        dim3 block(64, 4, 1);
-        dim3 grid((half + 63) / 64, (my + 3) / 4, mz);
-        for (int pass = 0; pass < 2; ++pass) {
-          hipLaunchKernelGGL(rbgs3_color, grid, block, 0, s, u, rhs, g, (g.first_par + pass) & 1);
-          NDSM_LAUNCH_CHECK();
-        }
-      }
-    } else {
-      NDSM_CHECK_ARG(in_place_ok());
-      if (prol_pending) {
-        if (int rc = ndsmk_prolong_add(px, uc, u)) return rc;
-        prol_pending = false;
-      }
-      const int half = (mx + 1) / 2;
-      dim3 block(64, 4, 1);
-      dim3 grid((half + 63) / 64, (my + 3) / 4, 1);
-      for (int pass = 0; pass < 2; ++pass) {
-        hipLaunchKernelGGL(rbgs2_color, grid, block, 0, s, u, rhs, g, (g.first_par + pass) & 1);
-        NDSM_LAUNCH_CHECK();
-      }
-    }
-    if (g.all_neumann) {
-      int rc = ndsm::launch_mean_shift(u, npts);
+    if (p.mean_shift) {
+      rc = ndsm::launch_mean_shift(uout, npts);
       if (rc) return rc;
     }
   }
-  if (cur != 0) {
-    if (where) {
-      *where = cur;
-    } else {  // caller cannot swap: bring the result home
-      NDSM_HIP(hipMemcpyAsync(bufs[0], bufs[cur], sizeof(double) * (size_t)npts, hipMemcpyDeviceToDevice, s));
-    }
-  }
+  if (pl.result != 0 && !where)   // caller cannot swap: bring the result home
+    NDSM_HIP(hipMemcpyAsync(bufs[0], bufs[pl.result], sizeof(double) * (size_t)npts, hipMemcpyDeviceToDevice, s));
   return 0;
 }
 
@@ -484,6 +408,26 @@ extern "C" int ndsmk_fetch_fused_metric(double *h_out2) {
   return ndsm::fetch_fused_metric(h_out2);
 }
 
+// The one fused pass of a window [z0, z1) of g's owned planes, u -> uout: planned and launched
+static int fused_window(const ndsmk_grid *gp, const double *u, double *uout, const double *rhs, int nsweeps, int z0,
+                        int z1, double *rout, const double *prev, const ndsmk_xfer *px, const double *uc) {
+  ndsmk_grid g = *gp;
+  g.zown0 = z0;
+  g.zown1 = z1;
+  ndsm::plan::Request rq;
+  rq.window = true;
+  rq.nsweeps = nsweeps;
+  rq.rhs = rhs != nullptr;
+  rq.want_res = rout != nullptr;
+  rq.want_met = prev != nullptr;
+  rq.corr = px != nullptr;
+  if (px) rq.coarse_plane = ndsm::fused_coarse_plane(g, px);
+  rq.have[1] = uout != nullptr;
+  const ndsm::plan::Plan pl = ndsm::plan::relax_plan(g, rq, ndsm::relax_knobs());
+  if (pl.err) return ndsm::fail(pl.err, pl.what, __FILE__, __LINE__);
+  return ndsm::launch_rbgs3_fused(pl.pass[0], g, u, uout, rhs, rout, prev, px, uc);
+}
+
 // One out-of-place fused pass (nsweeps = 1 or 2) over the owned planes [z0, z1) of a z-slab only:
 // the pieces of a pass whose halo exchange overlaps its interior (ndsmh_world).  u is read
 // (z0 - 2 nsweeps .. z1 + 2 nsweeps must be valid planes), uout written on [z0, z1).
@@ -499,20 +443,12 @@ extern "C" int ndsmk_fused_window(const ndsmk_grid *gp, const double *u, double 
                                   int z0, int z1, const ndsmk_xfer *px, const double *uc, const double *prev,
                                   int accumulate) {
   NDSM_REQUIRE_READY();
-  ndsmk_grid g = *gp;
-  NDSM_CHECK_ARG(g.ndim == 3 && (nsweeps == 1 || nsweeps == 2) && z0 >= g.zown0 && z1 <= g.zown1 && z0 < z1);
+  NDSM_CHECK_ARG(gp->ndim == 3 && (nsweeps == 1 || nsweeps == 2) && z0 >= gp->zown0 && z1 <= gp->zown1 && z0 < z1);
   NDSM_CHECK_ARG((!px || uc) && !(px && prev));
-  g.zown0 = z0;
-  g.zown1 = z1;
-  int ndone = 0, met = 0;
   ndsm::fused_metric_accumulate(accumulate != 0);
-  int rc = ndsm::launch_rbgs3_fused(g, u, uout, rhs, nsweeps, true, &ndone, nullptr, nullptr, prev, prev ? &met : nullptr,
-                                    px, uc);
+  const int rc = fused_window(gp, u, uout, rhs, nsweeps, z0, z1, nullptr, prev, px, uc);
   ndsm::fused_metric_accumulate(false);
-  if (rc) return rc;
-  if (ndone != nsweeps || (prev && !met))
-    return ndsm::fail(NDSMK_EARG, "fused smoother: this window / sweep count is not covered", __FILE__, __LINE__);
-  return 0;
+  return rc;
 }
 
 // The sweep + residual pass on a window of owned planes [z0, z1): ONE sweep u -> uout and r = rhs - L uout on the
@@ -521,22 +457,63 @@ extern "C" int ndsmk_fused_window(const ndsmk_grid *gp, const double *u, double 
 extern "C" int ndsmk_fused_window_res(const ndsmk_grid *gp, const double *u, double *uout, const double *rhs, double *rout,
                                       int z0, int z1) {
   NDSM_REQUIRE_READY();
-  ndsmk_grid g = *gp;
-  NDSM_CHECK_ARG(g.ndim == 3 && rout && z0 >= g.zown0 && z1 <= g.zown1 && z0 < z1);
-  g.zown0 = z0;
-  g.zown1 = z1;
-  int ndone = 0, res = 0;
-  int rc = ndsm::launch_rbgs3_fused(g, u, uout, rhs, 1, true, &ndone, rout, &res, nullptr, nullptr, nullptr, nullptr);
-  if (rc) return rc;
-  if (ndone != 1 || !res)
-    return ndsm::fail(NDSMK_EARG, "fused sweep + residual: this window is not covered", __FILE__, __LINE__);
-  return 0;
+  NDSM_CHECK_ARG(gp->ndim == 3 && rout && z0 >= gp->zown0 && z1 <= gp->zown1 && z0 < z1);
+  return fused_window(gp, u, uout, rhs, 1, z0, z1, rout, nullptr, nullptr, nullptr);
+}
+
+// would the window pass of nsweeps sweeps over g's owned planes be a launch of that mode?
+static int window_mode_ok(const ndsmk_grid *gp, bool rhs, int nsweeps, int mode) {
+  ndsm::plan::Request rq;
+  rq.window = true;
+  rq.nsweeps = nsweeps;
+  rq.rhs = rhs;
+  rq.want_met = mode == ndsm::plan::MET;
+  rq.corr = mode == ndsm::plan::CORR;
+  rq.have[1] = true;
+  const ndsm::plan::Plan pl = ndsm::plan::relax_plan(*gp, rq, ndsm::relax_knobs());
+  return !pl.err && pl.pass[0].mode == mode ? 1 : 0;
 }
 
 // can ndsmk_fused_window(..., prev) evaluate the metric? (fp64 level off the all-Neumann path)
-extern "C" int ndsmk_fused_metric_ok(const ndsmk_grid *gp) { return (gp->ndim == 3 && !gp->all_neumann) ? 1 : 0; }
+extern "C" int ndsmk_fused_metric_ok(const ndsmk_grid *gp) { return window_mode_ok(gp, true, 1, ndsm::plan::MET); }
 
 // can ndsmk_fused_window(..., px, uc) interpolate while it loads? (one sweep, or two without a right-hand side; fp64)
 extern "C" int ndsmk_fused_prolong_ok(const ndsmk_grid *gp, const double *rhs, int nsweeps) {
-  return (gp->ndim == 3 && (!rhs || nsweeps == 1) && (nsweeps == 1 || nsweeps == 2) && !gp->all_neumann) ? 1 : 0;
+  return window_mode_ok(gp, rhs != nullptr, nsweeps, ndsm::plan::CORR);
+}
+
+// tests / tools: the plan of a relax call (what = 0) or the z chunking of a fused launch (what = 1), on the host - no
+// device, no ndsmk_init.  include/ndsm_hip.h (ndsm_hip_debug_relax_plan) has the layouts of the four arrays.
+extern "C" int ndsmk_debug_relax_plan(int what, const int32_t *grid, const int64_t *req, const int64_t *knobs, int cap,
+                                      int32_t *out) {
+  namespace pn = ndsm::plan;
+  if (what == 1) {
+    NDSM_CHECK_ARG(req && out && cap >= 2 && req[0] >= 1 && req[0] < (1 << 30) && req[1] >= 1 && req[1] < (1 << 30) &&
+                   req[2] >= 1 && req[3] >= 1 && req[3] < (1 << 20));
+    const pn::Chunks ch = pn::z_chunks((int)req[0], (int)req[1], req[2], (int)req[3], req[4] != 0, (int)req[5]);
+    out[0] = ch.nzc;
+    out[1] = ch.zc;
+    return 0;
+  }
+  NDSM_CHECK_ARG(what == 0 && grid && req && knobs && out && cap >= 6 && req[0] < (1 << 16));
+  ndsmk_grid g = {};
+  g.ndim = grid[0];
+  for (int d = 0; d < 3; ++d) g.n[d] = grid[1 + d], g.lb[d] = grid[4 + d], g.ub[d] = grid[7 + d];
+  g.all_neumann = grid[10], g.k0 = grid[11], g.nzg = grid[12], g.zown0 = grid[13], g.zown1 = grid[14];
+  pn::Request rq;
+  rq.nsweeps = (int)req[0], rq.variant = (int)req[1], rq.window = req[2] != 0, rq.fp32 = req[3] != 0;
+  rq.rhs = req[4] != 0, rq.want_res = req[5] != 0, rq.want_met = req[6] != 0, rq.corr = req[7] != 0;
+  rq.coarse_plane = req[8], rq.have[1] = req[9] != 0, rq.have[2] = req[10] != 0, rq.keep = (int)req[11];
+  pn::Knobs kn;
+  for (int i = 0; i < 5; ++i) kn.fused[i] = (int)knobs[i];
+  kn.block[0] = knobs[5], kn.block[1] = knobs[6], kn.block_on = knobs[7] == 0;
+  const pn::Plan pl = pn::relax_plan(g, rq, kn);
+  const int32_t head[6] = {pl.err, (int32_t)pl.pass.size(), pl.result, pl.res_done, pl.met_done, pl.prolong_only};
+  for (int i = 0; i < 6; ++i) out[i] = head[i];
+  NDSM_CHECK_ARG((size_t)cap >= 6 + 9 * pl.pass.size());
+  for (const pn::Pass &p : pl.pass) {
+    const int32_t row[9] = {p.kind, p.sweeps, p.mode, p.inst, p.bz, p.src, p.dst, p.prolong_first, p.mean_shift};
+    for (int i = 0; i < 9; ++i) out[6 + 9 * (&p - pl.pass.data()) + i] = row[i];
+  }
+  return 0;
 }

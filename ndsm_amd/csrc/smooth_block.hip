@@ -1,6 +1,6 @@
 // Block-resident red-black Gauss-Seidel smoother for the 3-D levels above the single-workgroup
-// kernels (<= 4096 points) and far below the z-streaming fused kernel (>= 2 M points): relax_impl
-// (smooth.hip) sends levels of up to 512 K points here, the measured cut-over against the colour passes.
+// kernels (<= 4096 points) and far below the z-streaming fused kernel (>= 2 M points): plan::relax_plan
+// (relax_plan.hpp) sends levels of up to 512 K points here, the measured cut-over against the colour passes.
 //
 // There a colour pass (rbgs3_color) is shorter than the gap between two dependent launches, so a
 // sweep costs two dispatch latencies whatever the level holds.  Here ONE launch performs S = 1 or 2
@@ -134,6 +134,10 @@ int launch_block(const ndsmk_grid &g, const double *u, double *uout, const doubl
   return 0;
 }
 
+}  // namespace
+
+namespace ndsm {
+
 // Development knob: NDSM_BLOCK_CFG=<bz>,<points> - <bz> 4 or 8 fixes the block height (0: by level size),
 // <points> lets the block launch take levels below that many points BEFORE the fused launcher is asked
 // (scripts/time_small_levels.py measures the cut-over that way).  Default 0,0.
@@ -151,41 +155,22 @@ const int64_t *block_cfg() {
   return cfg;
 }
 
-}  // namespace
-
-namespace ndsm {
-
 // NDSM_HIP_NO_BLOCK=1 (read once per process): relax keeps the colour passes on these levels - A/B runs
 bool block_smoother_on() {
   static const bool on = std::getenv("NDSM_HIP_NO_BLOCK") == nullptr;
   return on;
 }
 
-// levels below this many points go to the block launch without asking the fused launcher (0: none do)
-int64_t block_smoother_first_below() { return block_cfg()[1]; }
-
-// One launch of min(max_sweeps, 2) sweeps u -> uout on a whole 3-D fp64 level (no z-slab window, not
-// all-Neumann: the mean shift comes between two sweeps there).  *sweeps_done = 0: not covered, nothing launched.
-int launch_rbgs3_block(const ndsmk_grid &g, const double *u, double *uout, const double *rhs, int max_sweeps,
-                       int *sweeps_done) {
-  *sweeps_done = 0;
-  if (!block_smoother_on() || !uout || uout == u || g.ndim != 3 || g.all_neumann || max_sweeps < 1) return 0;
-  if (g.k0 != 0 || g.zown0 != 0 || g.zown1 != g.n[2] || g.nzg != g.n[2]) return 0;
-  if (g.n[0] < 2 || g.n[1] < 2 || g.n[2] < 2) return 0;
-  const int64_t gx = (g.n[0] + 15) / 16, gy = (g.n[1] + 7) / 8, gz8 = (g.n[2] + 7) / 8, gz4 = (g.n[2] + 3) / 4;
-  if (gy > 65535 || gz4 > 65535) return 0;
-  // 16 x 8 x 8 blocks; where they give fewer than 64 workgroups (32^3: 32) half-height blocks spread the
-  // level over twice as many CUs
-  const int64_t bz = block_cfg()[0];
-  const bool low = bz == 4 || (bz != 8 && gx * gy * gz8 < 64);
-  int rc;
-  if (max_sweeps >= 2)
-    rc = low ? launch_block<2, 4>(g, u, uout, rhs) : launch_block<2, 8>(g, u, uout, rhs);
-  else
-    rc = low ? launch_block<1, 4>(g, u, uout, rhs) : launch_block<1, 8>(g, u, uout, rhs);
-  if (rc) return rc;
-  *sweeps_done = max_sweeps >= 2 ? 2 : 1;
-  return 0;
+// One block pass of a relax plan (relax_plan.hpp decides where it applies): `sweeps` = 1 or 2 sweeps u -> uout on a
+// whole 3-D fp64 level in blocks of height bz
+int launch_rbgs3_block(const ndsmk_grid &g, const double *u, double *uout, const double *rhs, int sweeps, int bz) {
+  switch (10 * sweeps + bz) {
+    case 24: return launch_block<2, 4>(g, u, uout, rhs);
+    case 28: return launch_block<2, 8>(g, u, uout, rhs);
+    case 14: return launch_block<1, 4>(g, u, uout, rhs);
+    case 18: return launch_block<1, 8>(g, u, uout, rhs);
+  }
+  return fail(NDSMK_EARG, "block smoother: no such instantiation", __FILE__, __LINE__);
 }
 
 }  // namespace ndsm

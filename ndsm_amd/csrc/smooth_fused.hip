@@ -45,6 +45,7 @@
 // neighbour, and the inner loop is unchanged; only loads (rows are 8-byte aligned now), stores
 // (the ghost is never written back) and the per-slot constants differ.
 #include "common.hpp"
+#include "relax_plan.hpp"
 
 #include <cstdlib>
 #include <cstring>
@@ -61,7 +62,7 @@ namespace {
 // 0 to -4 % - the pass was never waiting for memory latency.  Result stores carry the non-temporal hint: +2 %.)
 typedef unsigned v4u_t __attribute__((ext_vector_type(4)));
 typedef unsigned v2u_t __attribute__((ext_vector_type(2)));
-constexpr unsigned kDeadLane = 0x80000000u;   // >= any plane's byte count (launch_fused_t checks)
+constexpr unsigned kDeadLane = 0x80000000u;   // >= any plane's byte count (plan::kPlaneBytes)
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t plane_rsrc(const void *base, unsigned bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, (int)bytes, 0x00020000);
 }
@@ -1017,33 +1018,11 @@ int launch_cfg(const ndsmk_grid &g, const T *u, T *uout, const T *rhs, int targe
     NDSM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kfn, NT, lds_bytes));
     wgs_per_cu[v] = occ > 0 ? occ : 1;
   }
-  // z chunks.  A workgroup walks its chunk plus NST warm-up planes on either side, and
-  // the chip runs ncu * wgs_per_cu workgroups at a time: pick the chunk count that
-  // minimises (rounds of workgroups) x (planes walked per workgroup).
-  int nzc;
-  if (target_wgs > 0) {
-    nzc = (target_wgs + tiles - 1) / tiles;
-    if (nzc < 1) nzc = 1;
-    int zc = (nzo + nzc - 1) / nzc;
-    if (zc < NST) zc = NST < nzo ? NST : nzo;   // (down to the pipeline depth: what the chunk-count timings force)
-    nzc = (nzo + zc - 1) / zc;
-  } else {
-    const int64_t slots = (int64_t)ndsm::cu_count() * wgs_per_cu[v];
-    int64_t best = -1;
-    nzc = 1;
-    for (int c = 1; c <= (nzo + 7) / 8; ++c) {
-      const int zc = (nzo + c - 1) / c;
-      const int cc = (nzo + zc - 1) / zc;
-      const int64_t rounds = ((int64_t)tiles * cc + slots - 1) / slots;
-      const int64_t cost = rounds * (zc + 2 * NST + (RES ? 0 : NST - 1));
-      if (best < 0 || cost < best) {
-        best = cost;
-        nzc = cc;
-      }
-    }
-  }
-  pl.zc = (nzo + nzc - 1) / nzc;
-  pl.nzc = (nzo + pl.zc - 1) / pl.zc;
+  // z chunks: plan::z_chunks, for the workgroups the chip runs at a time
+  const ndsm::plan::Chunks ch =
+      ndsm::plan::z_chunks(nzo, tiles, (int64_t)ndsm::cu_count() * wgs_per_cu[v], NST, RES, target_wgs);
+  pl.zc = ch.zc;
+  pl.nzc = ch.nzc;
   pl.nwork = tiles * pl.nzc;
   const int nblk = ((pl.nwork + 7) / 8) * 8;
   ProlArgs pa = {};
@@ -1073,7 +1052,7 @@ namespace ndsm {
 // (>= 64 M points), 0 / 1 = never / always take the large-level tiles - the parity tests run them on
 // oracle-sized grids that way (ndsmk_debug_fused_cfg sets the same five values at run time).
 static int g_fcfg[5] = {-1, 0, 0, 0, -1};
-static const int *fused_cfg() {
+const int *fused_cfg() {
   int *cfg = g_fcfg;
   if (cfg[0] < 0) {
     cfg[0] = 0;
@@ -1087,163 +1066,79 @@ static const int *fused_cfg() {
   return cfg;
 }
 
-// rout != nullptr: the caller wants the residual of the swept field as well.  It is
-// produced (and *res_done set) only by the launch that performs the LAST of the
-// max_sweeps sweeps, i.e. when this call runs a single sweep with max_sweeps == 1.
-template <typename T, bool ODD = false>
-static int launch_fused_t(const ndsmk_grid &g, const T *u, T *uout, const T *rhs, int max_sweeps, bool force,
-                          int *sweeps_done, T *rout, int *res_done, const T *prev = nullptr, int *met_done = nullptr,
-                          const ProlArgs *prol = nullptr) {
-  *sweeps_done = 0;
-  if (res_done) *res_done = 0;
-  if (met_done) *met_done = 0;
-  if (!uout || g.ndim != 3 || ((g.n[0] & 1) != 0) != ODD || g.n[0] < 16 || g.n[1] < 16 || g.zown1 - g.zown0 < (force ? 1 : 8))
-    return 0;
-  // the buffer path addresses a plane with 32-bit byte offsets below kDeadLane (2 GiB: 16384 x 16384 doubles)
-  if ((int64_t)g.n[0] * g.n[1] * (int64_t)sizeof(T) >= (int64_t)kDeadLane) return 0;
-  // a z-streaming workgroup walks >= 16 planes serially: with fewer than ~one
-  // workgroup per CU the sweep is latency bound and the two colour passes win
-  const int64_t npts = (int64_t)g.n[0] * g.n[1] * (g.zown1 - g.zown0);
-  const bool slab = g.zown1 - g.zown0 != g.n[2];
-  if (npts < (int64_t)2 * 1024 * 1024 && !slab && !force) return 0;
-  // Tile choices measured on MI355X (scripts/tune_smoother.py); launch_cfg picks the z chunking.
-  int rc;
-  const int *cfg = fused_cfg();
-  const int tgt = cfg[3] > 0 ? cfg[3] : 0;  // > 0: that many work items instead of launch_cfg's own choice
-  const bool big = cfg[4] < 0 ? npts >= (int64_t)64 * 1024 * 1024 : cfg[4] != 0;
-  // A z-slab carries zown0 ghost planes below and n[2] - zown1 above its owned range; the caller
-  // (ndsmh_world) has exchanged as many as the pass it asks for consumes: 2 per sweep, +1 for
-  // the residual stage.
-  const int ghosts = slab ? (g.zown0 < g.n[2] - g.zown1 ? g.zown0 : g.n[2] - g.zown1) : 1 << 20;
-  const bool res = rout && res_done && ghosts >= 3 && cfg[2] != 9;
-  // two sweeps per pass - not for the last two sweeps when the residual is wanted (it rides
-  // on a one-sweep pass)
-  const bool two = max_sweeps >= 2 && ghosts >= 4 && cfg[0] != 9 && !(res && max_sweeps == 2);
-  // prev != nullptr: the launch that performs the last of the max_sweeps sweeps also evaluates
-  // the convergence metric against prev (fp64, single domain; *met_done says it did)
-  const bool met = std::is_same<T, double>::value && prev && met_done;
-  // prol != nullptr: u + P u_c is to be formed while the planes are loaded (MODE 3): a one-sweep pass (any
-  // right-hand side) or a two-sweep pass (rhs == 0 only).  If this call cannot be such a launch NOTHING is launched
-  // (*sweeps_done = 0) and the caller interpolates with the stand-alone kernel first.
-  // The interpolation costs ~100 instructions per plane-step and wave.  On top of a TWO-sweep pass - which is bound
-  // by instruction issue with it - that is +240 us at 512^3 (720 against 480); a ONE-sweep pass has the issue
-  // slots to spare (it is bound by memory: 430 us).  So an odd number of sweeps (NDSM's ms = 5) is taken as
-  // 1 + 2 + 2 with the correction on the one-sweep pass - the sweeps that remain are two-sweep passes, the last
-  // of which carries the convergence metric - instead of 2 + 2 + 1.
-  if (prol) {
-    if constexpr (std::is_same<T, double>::value) {
-      if (cfg[0] == 0 && (max_sweeps & 1) && (max_sweeps >= 3 || slab)) {   // (a slab window asks for exactly its pass)
-        rc = (launch_cfg<T, 1, 132, 31, 1024, 4, 3, false, ODD>(g, u, uout, rhs, tgt, nullptr, nullptr, prol));
-        if (rc) return rc;
-        *sweeps_done = 1;
-      } else if (!rhs && two && !(met && max_sweeps == 2) && cfg[0] == 0) {
-        rc = (launch_cfg<T, 2, 136, 30, 1024, 4, 3, false, ODD>(g, u, uout, rhs, tgt, nullptr, nullptr, prol));
-        if (rc) return rc;
-        *sweeps_done = 2;
-      }
-    }
-    return 0;
+// The launch of one fused pass of a relax plan (relax_plan.hpp decides which): instantiation enumerator -> launch_cfg.
+template <typename T>
+static int launch_fused_t(int inst, const ndsmk_grid &g, const T *u, T *uout, const T *rhs, T *rout, const T *prev,
+                          const ProlArgs *prol) {
+  using namespace plan;
+  const int tgt = fused_cfg()[3] > 0 ? fused_cfg()[3] : 0;  // > 0: that many work items instead of launch_cfg's own choice
+#define NDSM_FUSED_CASE(id, ...) \
+  case id: return (launch_cfg<T, __VA_ARGS__>(g, u, uout, rhs, tgt, rout, prev, prol))
+#define NDSM_FUSED_BOTH(id, ...)               \
+  NDSM_FUSED_CASE(id, __VA_ARGS__, false, false); \
+  NDSM_FUSED_CASE(id + kOddNx, __VA_ARGS__, false, true)
+  switch (inst) {
+    NDSM_FUSED_CASE(F2_136x30_1024, 2, 136, 30, 1024, 4);
+    NDSM_FUSED_CASE(F2_136x30_1024_L1, 2, 136, 30, 1024, 4, 0, true);
+    NDSM_FUSED_CASE(F2_136x22_768, 2, 136, 22, 768, 4);
+    NDSM_FUSED_CASE(F2_72x28_512, 2, 72, 28, 512, 4);
+    NDSM_FUSED_CASE(F1_132x23_768, 1, 132, 23, 768, 4);
+    NDSM_FUSED_CASE(F1_132x31_1024, 1, 132, 31, 1024, 4);
+    NDSM_FUSED_CASE(F1R_136x22_768, 1, 136, 22, 768, 4, 1);
   }
-  if constexpr (std::is_same<T, double>::value) {
-    if (met && two && max_sweeps == 2) {
-      rc = (launch_cfg<T, 2, 136, 30, 1024, 4, 2, false, ODD>(g, u, uout, rhs, tgt, nullptr, prev));
-      if (rc) return rc;
-      *sweeps_done = 2;
-      *met_done = 1;
-      return 0;
-    }
-    if (met && !two && max_sweeps == 1 && !res) {
-      if (big)
-        rc = (launch_cfg<T, 1, 132, 31, 1024, 4, 2, false, ODD>(g, u, uout, rhs, tgt, nullptr, prev));
-      else
-        rc = (launch_cfg<T, 1, 132, 23, 768, 4, 2, false, ODD>(g, u, uout, rhs, tgt, nullptr, prev));
-      if (rc) return rc;
-      *sweeps_done = 1;
-      *met_done = 1;
-      return 0;
+  if constexpr (std::is_same<T, double>::value) {   // odd nx, the metric and the correction: fp64 only
+    switch (inst) {
+      NDSM_FUSED_CASE(F2_136x30_1024 + kOddNx, 2, 136, 30, 1024, 4, 0, false, true);
+      NDSM_FUSED_CASE(F1_132x23_768 + kOddNx, 1, 132, 23, 768, 4, 0, false, true);
+      NDSM_FUSED_CASE(F1_132x31_1024 + kOddNx, 1, 132, 31, 1024, 4, 0, false, true);
+      NDSM_FUSED_CASE(F1R_136x22_768 + kOddNx, 1, 136, 22, 768, 4, 1, false, true);
+      NDSM_FUSED_BOTH(F2M_136x30_1024, 2, 136, 30, 1024, 4, 2);
+      NDSM_FUSED_BOTH(F1M_132x31_1024, 1, 132, 31, 1024, 4, 2);
+      NDSM_FUSED_BOTH(F1M_132x23_768, 1, 132, 23, 768, 4, 2);
+      NDSM_FUSED_BOTH(F1P_132x31_1024, 1, 132, 31, 1024, 4, 3);
+      NDSM_FUSED_BOTH(F2P_136x30_1024, 2, 136, 30, 1024, 4, 3);
     }
   }
-  // THREE sweeps per pass were tried and are not built: six LDS planes force a narrower tile (72 x 46 or
-  // 88 x 38 owned 60 x 34 / 76 x 26: 1.6-1.7x redundant stage work instead of 1.45x) and the pass turns
-  // LDS / issue bound - measured at 512^3 (Laplace): 1075-1120 us per three-sweep pass against 553 us per
-  // two-sweep pass, i.e. 358 against 282 us per sweep; same bits (scripts/time_s3.py, round 2).
-  if (two) {
-    if constexpr (ODD) {   // the tuning alternates and the level-1 symbol exist for even nx only
-      rc = (launch_cfg<T, 2, 136, 30, 1024, 4, 0, false, true>(g, u, uout, rhs, tgt));
-    } else {
-      // levels of a few million points (the 128^3 level of a 512^3 hierarchy) do not fill the chip with
-      // 136 x 30 tiles: the 72 x 28 tile (512 threads) gives four times the workgroups - measured 77 against
-      // 98 us per five sweeps at 128^3, 293 against 280 us at 256^3 (scripts/time_tail.py)
-      const int two_cfg = cfg[0] ? cfg[0] : (npts < (int64_t)6 * 1024 * 1024 && !slab ? 5 : 0);
-      switch (two_cfg) {
-        case 3: rc = launch_cfg<T, 2, 136, 22, 768, 4>(g, u, uout, rhs, tgt); break;
-        case 5: rc = launch_cfg<T, 2, 72, 28, 512, 4>(g, u, uout, rhs, tgt); break;
-        default:
-          // (fp32: four LDS planes are 65 KB, so two workgroups would fit a CU at <= 64 VGPRs - tried:
-          // __launch_bounds__(1024, 8) gives 64 VGPRs + 44 B of scratch and the mixed-precision cycle at 512^3
-          // goes from 6.5 to 7.9 ms; not built)
-          rc = big ? (launch_cfg<T, 2, 136, 30, 1024, 4, 0, true>(g, u, uout, rhs, tgt))
-                   : (launch_cfg<T, 2, 136, 30, 1024, 4>(g, u, uout, rhs, tgt));
-          break;
-      }
-    }
-    if (rc) return rc;
-    *sweeps_done = 2;
-    return 0;
-  }
-  if (res && max_sweeps == 1) {
-    if constexpr (ODD) {
-      rc = (launch_cfg<T, 1, 136, 22, 768, 4, 1, false, true>(g, u, uout, rhs, tgt, rout));
-    } else {
-      rc = (launch_cfg<T, 1, 136, 22, 768, 4, 1>(g, u, uout, rhs, tgt, rout));
-    }
-    if (rc) return rc;
-    *sweeps_done = 1;
-    *res_done = 1;
-    return 0;
-  }
-  switch (cfg[1] ? cfg[1] : (big ? 7 : 8)) {
-    case 8: rc = (launch_cfg<T, 1, 132, 23, 768, 4, 0, false, ODD>(g, u, uout, rhs, tgt)); break;
-    default: rc = (launch_cfg<T, 1, 132, 31, 1024, 4, 0, false, ODD>(g, u, uout, rhs, tgt)); break;
-  }
-  if (rc) return rc;
-  *sweeps_done = 1;
-  return 0;
+#undef NDSM_FUSED_BOTH
+#undef NDSM_FUSED_CASE
+  return fail(NDSMK_EARG, "fused smoother: no such instantiation", __FILE__, __LINE__);
 }
 
-int launch_rbgs3_fused(const ndsmk_grid &g, const double *u, double *uout, const double *rhs, int max_sweeps,
-                       bool force, int *sweeps_done, double *rout, int *res_done, const double *prev,
-                       int *met_done, const ndsmk_xfer *px, const double *uc) {
-  if (px) {
-    ProlArgs pa;
-    pa.uc = uc;
-    for (int d = 0; d < 3; ++d) {
-      pa.plo[d] = px->plo[d];
-      pa.pwl[d] = px->pwl[d];
-      pa.pwh[d] = px->pwh[d];
-    }
-    pa.ncx = px->nc[0];
-    pa.ncy = px->nc[1];
-    pa.ncz = px->nc[2];
-    // z windows: the fine array is the slab described by g, uc holds coarse planes [c_k0, c_k0 + c_cnt)
-    // (single domain: c_k0 = 0 and the whole coarse level); the caller guarantees that they cover the
-    // brackets of every fine plane the launch loads (owned planes + ghosts)
-    pa.fk0 = px->f_k0;
-    pa.nzf = px->nf[2];
-    pa.ck0 = px->c_k0;
-    pa.nczw = (px->f_k0 == 0 && px->c_k0 == 0 && px->nf[2] == g.n[2]) ? px->nc[2] : px->c_cnt;
-    if (px->f_k0 != g.k0 || px->nf[0] != g.n[0] || px->nf[1] != g.n[1] || px->nf[2] != g.nzg || pa.nczw < 1 ||
-        (int64_t)pa.ncx * pa.ncy * 8 >= (int64_t)kDeadLane) {   // (a coarse plane is addressed with 32-bit byte offsets)
-      *sweeps_done = 0;
-      return 0;
-    }
-    if (g.n[0] & 1)
-      return launch_fused_t<double, true>(g, u, uout, rhs, max_sweeps, force, sweeps_done, rout, res_done, prev, met_done, &pa);
-    return launch_fused_t<double>(g, u, uout, rhs, max_sweeps, force, sweeps_done, rout, res_done, prev, met_done, &pa);
+// px as the correction launch (MODE 3) takes it; false: its z windows do not describe g's arrays, or are empty
+static bool prol_args(const ndsmk_grid &g, const ndsmk_xfer *px, const double *uc, ProlArgs *pa) {
+  pa->uc = uc;
+  for (int d = 0; d < 3; ++d) {
+    pa->plo[d] = px->plo[d];
+    pa->pwl[d] = px->pwl[d];
+    pa->pwh[d] = px->pwh[d];
   }
-  if (g.n[0] & 1)
-    return launch_fused_t<double, true>(g, u, uout, rhs, max_sweeps, force, sweeps_done, rout, res_done, prev, met_done);
-  return launch_fused_t<double>(g, u, uout, rhs, max_sweeps, force, sweeps_done, rout, res_done, prev, met_done);
+  pa->ncx = px->nc[0];
+  pa->ncy = px->nc[1];
+  pa->ncz = px->nc[2];
+  // z windows: the fine array is the slab described by g, uc holds coarse planes [c_k0, c_k0 + c_cnt)
+  // (single domain: c_k0 = 0 and the whole coarse level); the caller guarantees that they cover the
+  // brackets of every fine plane the launch loads (owned planes + ghosts)
+  pa->fk0 = px->f_k0;
+  pa->nzf = px->nf[2];
+  pa->ck0 = px->c_k0;
+  pa->nczw = (px->f_k0 == 0 && px->c_k0 == 0 && px->nf[2] == g.n[2]) ? px->nc[2] : px->c_cnt;
+  return px->f_k0 == g.k0 && px->nf[0] == g.n[0] && px->nf[1] == g.n[1] && px->nf[2] == g.nzg && pa->nczw >= 1;
+}
+
+// points of a plane of the coarse level behind px (the planner's 2 GiB limit), -1: prol_args says no
+int64_t fused_coarse_plane(const ndsmk_grid &g, const ndsmk_xfer *px) {
+  ProlArgs pa;
+  return prol_args(g, px, nullptr, &pa) ? (int64_t)pa.ncx * pa.ncy : -1;
+}
+
+// one fused pass of a plan; rout / prev / px are looked at by the pass of that mode only
+int launch_rbgs3_fused(const plan::Pass &p, const ndsmk_grid &g, const double *u, double *uout, const double *rhs,
+                       double *rout, const double *prev, const ndsmk_xfer *px, const double *uc) {
+  ProlArgs pa;
+  if (p.mode == plan::CORR && !(px && prol_args(g, px, uc, &pa)))
+    return fail(NDSMK_EARG, "fused smoother: the transfer does not describe this level", __FILE__, __LINE__);
+  return launch_fused_t<double>(p.inst, g, u, uout, rhs, p.mode == plan::RES ? rout : nullptr,
+                                p.mode == plan::MET ? prev : nullptr, p.mode == plan::CORR ? &pa : nullptr);
 }
 
 // (max, sum) of |u_new - u_prev| left on the device by the last MET launch -> host (blocking)
@@ -1259,9 +1154,9 @@ void fused_metric_accumulate(bool on) { g_met_acc = on; }
 
 // fp32 instantiation: the correction equation L e = r of the mixed-precision mode (same tiles:
 // half the LDS and HBM bytes per point, the same instruction count)
-int launch_rbgs3_fused_f32(const ndsmk_grid &g, const float *u, float *uout, const float *rhs, int max_sweeps,
-                           bool force, int *sweeps_done, float *rout, int *res_done) {
-  return launch_fused_t<float>(g, u, uout, rhs, max_sweeps, force, sweeps_done, rout, res_done);
+int launch_rbgs3_fused_f32(const plan::Pass &p, const ndsmk_grid &g, const float *u, float *uout, const float *rhs,
+                           float *rout) {
+  return launch_fused_t<float>(p.inst, g, u, uout, rhs, p.mode == plan::RES ? rout : nullptr, nullptr, nullptr);
 }
 
 }  // namespace ndsm

@@ -495,7 +495,7 @@ contains
     rc = merge(1_c_int, 0_c_int, mg_mixed_applies(s))
   end function
 
-  ! which: 0 = u, 1 = rhs, 2 = residual scratch (level-1 sized, valid after op RESIDUAL)
+  ! which: 0 = u, 1 = rhs, 2 = residual scratch (level-1 sized, valid after op RESIDUAL), 3 = the partner array of u
   function ndsm_hip_mg_upload(handle, level, which, host) bind(c, name="ndsm_hip_mg_upload") result(rc)
     type(c_ptr), value :: handle, host
     integer(c_int), value :: level, which
@@ -1861,6 +1861,15 @@ contains
       end function
     end interface
     rc = ndsmk_debug_fused_cfg(two, one, res, work_items, big)
+  end function
+
+  ! development hook (tests, tools): the plan of a relax call (what = 0) or the z chunking of a fused launch
+  ! (what = 1) as csrc/relax_plan.hpp decides them - host code, no device and no ndsm_hip_init needed
+  function ndsm_hip_debug_relax_plan(what, grid, req, knobs, cap, out) bind(c, name="ndsm_hip_debug_relax_plan") result(rc)
+    integer(c_int), value :: what, cap
+    type(c_ptr), value :: grid, req, knobs, out
+    integer(c_int) :: rc
+    rc = ndsmk_debug_relax_plan(what, grid, req, knobs, cap, out)
   end function
 
   ! development hook: 0 = the levels of the V-cycle's tail run kernel by kernel even where the single-launch

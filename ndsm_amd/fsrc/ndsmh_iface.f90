@@ -392,6 +392,13 @@ module ndsmh_iface
       integer(c_int) :: rc
     end function
 
+    function ndsmk_debug_relax_plan(what, grid, req, knobs, cap, out) bind(c, name="ndsmk_debug_relax_plan") result(rc)
+      import :: c_int, c_ptr
+      integer(c_int), value :: what, cap
+      type(c_ptr), value :: grid, req, knobs, out
+      integer(c_int) :: rc
+    end function
+
     function ndsmk_debug_tail(on) bind(c, name="ndsmk_debug_tail") result(rc)
       import :: c_int
       integer(c_int), value :: on

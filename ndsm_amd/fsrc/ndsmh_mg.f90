@@ -31,12 +31,12 @@ module ndsmh_mg
   public :: mg_mark_rhs_set
   public :: mg_set_bcs, mg_export_u, mg_reset_info, mg_vcycle_from, mg_slab_restrict, mg_slab_prolong
   public :: mg_slab_restrict_f32, mg_slab_prolong_f32, mg_mixed_slab_ok, rhs_of
-  public :: MG_BUF_U, MG_BUF_RHS, MG_BUF_R
+  public :: MG_BUF_U, MG_BUF_RHS, MG_BUF_R, MG_BUF_UALT
   public :: MG_OP_RELAX_LAST
   public :: MG_OP_RELAX, MG_OP_RESIDUAL, MG_OP_RESTRICT, MG_OP_PROLONG, MG_OP_EXACT, MG_OP_RELAX_COLOR, &
             MG_OP_RELAX_FUSED, MG_OP_RESREST, MG_OP_RELAX_RES, MG_OP_RELAX_RES_FUSED
 
-  integer, parameter :: MG_BUF_U = 0, MG_BUF_RHS = 1, MG_BUF_R = 2
+  integer, parameter :: MG_BUF_U = 0, MG_BUF_RHS = 1, MG_BUF_R = 2, MG_BUF_UALT = 3
   integer, parameter :: MG_OP_RELAX = 0, MG_OP_RESIDUAL = 1, MG_OP_RESTRICT = 2, MG_OP_PROLONG = 3, &
                         MG_OP_EXACT = 4, MG_OP_RELAX_COLOR = 5, MG_OP_RELAX_FUSED = 6, &
                         MG_OP_RESREST = 7, MG_OP_RELAX_RES = 8, MG_OP_RELAX_RES_FUSED = 9, &
@@ -497,6 +497,7 @@ contains
     case (MG_BUF_RHS); p = s%dl(level)%rhs
     case (MG_BUF_R)
       p = s%r
+    case (MG_BUF_UALT); p = s%dl(level)%ualt   ! (tests: which array an out-of-place pass left the result in)
     end select
   end function
 

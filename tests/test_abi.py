@@ -162,3 +162,19 @@ def test_additive_entry_points_fail_cleanly_without_a_gpu(lib):
     with pytest.raises(ndsm_amd.NdsmHipError):
         ndsm_amd.VecPot(x, x, x)
 
+
+def test_debug_relax_plan_is_host_code(lib):
+    """ndsm_hip_debug_relax_plan answers without a device and without ndsm_hip_init, and refuses what it cannot hold"""
+    i32, i64 = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64)
+    lib.ndsm_hip_debug_relax_plan.argtypes = [ctypes.c_int, i32, i64, i64, ctypes.c_int, i32]
+    grid = np.array([3, 64, 64, 64, 0, 0, 0, 63, 63, 63, 0, 0, 64, 0, 64], dtype=np.intc)
+    req = np.array([5, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, -1], dtype=np.int64)
+    knobs = np.array([0, 0, 0, 0, -1, 0, 0, 0], dtype=np.int64)
+    out = np.full(6 + 9 * 3, -7, dtype=np.intc)
+    args = (grid.ctypes.data_as(i32), req.ctypes.data_as(i64), knobs.ctypes.data_as(i64))
+    assert lib.ndsm_hip_debug_relax_plan(0, *args, out.size, out.ctypes.data_as(i32)) == 0
+    assert list(out[:6]) == [0, 3, 1, 0, 0, 0] and (out != -7).all()
+    assert lib.ndsm_hip_debug_relax_plan(0, *args, out.size - 1, out.ctypes.data_as(i32)) == 9002    # one pass short
+    assert lib.ndsm_hip_debug_relax_plan(0, None, None, None, 0, None) == 9002
+    assert lib.ndsm_hip_debug_relax_plan(1, None, None, None, 2, None) == 9002
+    assert lib.ndsm_hip_debug_relax_plan(2, *args, out.size, out.ctypes.data_as(i32)) == 9002

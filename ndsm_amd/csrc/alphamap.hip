@@ -2,8 +2,8 @@
 // face, alpha0 (nx,ny), is carried along the field lines of B to every node of the grid.  One lane per node, x fastest,
 // so a wave starts the 64 neighbouring lines of one row; there is no seed array and nothing but alpha (8 B/pt) and the
 // optional status (4 B/pt) is written.  The line of a node is trace.hip's: the stage and the RK4 step are
-// trace_step.hpp's, the cell, the first-face search and the snap line.hpp's, the loop trace_k<false>'s, so the end
-// point and the status of node l hold the bits of ndsmk_trace with the seed
+// trace_step.hpp's, the cell, the first-face search and the snap line.hpp's, the loop line_walk.hpp's line_walk - the
+// one trace_k walks with -, so the end point and the status of node l hold the bits of ndsmk_trace with the seed
 //
 //   r_d = lo_d + (double) i_d * h_d                 (on the last node hi_d's own expression: every node is inside)
 //
@@ -17,11 +17,18 @@
 //                               finish carries no current)
 //
 // Fixed fp64 expressions in a fixed order (no contraction), no LDS; each node depends on its own line only.
-#include "trace_step.hpp"
+#include "line_walk.hpp"
 
 namespace {
 
 using namespace ndsm;
+
+// only the end and the status of the walk are wanted
+struct LineEndOnly {
+  __device__ __forceinline__ void step(int, const double *, const double *, const double *, double, double) {}
+  static constexpr int kArrived = 0;   // (never)
+  __device__ __forceinline__ bool arrived(const double *) { return false; }
+};
 
 __global__ __launch_bounds__(kLineBlock) void alpha_map_k(const double *__restrict__ B,
                                                           const double *__restrict__ alpha0,
@@ -36,30 +43,8 @@ __global__ __launch_bounds__(kLineBlock) void alpha_map_k(const double *__restri
   const double sgn = (double)p.sgn0;
 
   double r[3] = {p.lo[0] + (double)i * p.h[0], p.lo[1] + (double)j * p.h[1], p.lo[2] + (double)k * p.h[2]};
-  int st = NDSMK_TRACE_UNFINISHED;
-  for (int it = 0; it < p.max_steps; ++it) {
-    double k1[3], q1, rn[3], dI;
-    if (!tr_stage<false>(B, nullptr, p, N, sy, sz, sgn, r[0], r[1], r[2], k1, q1) ||
-        !tr_rk4<false>(B, nullptr, p, N, sy, sz, sgn, r, k1, q1, p.ds, rn, dI)) {
-      st = NDSMK_TRACE_NULL;
-      break;
-    }
-    double t;
-    const int face = line_first_face(p, r, rn, t);
-    if (face == 0) {
-      r[0] = rn[0], r[1] = rn[1], r[2] = rn[2];
-      continue;
-    }
-    // the step is redone with the length that reaches the face; stage 1 is the same
-    const double s = t * p.ds;
-    if (!tr_rk4<false>(B, nullptr, p, N, sy, sz, sgn, r, k1, q1, s, rn, dI)) {
-      st = NDSMK_TRACE_NULL;
-      break;
-    }
-    line_snap(p, face, rn, r);
-    st = face;
-    break;
-  }
+  LineEndOnly v;
+  const int st = line_walk<false, false>(B, nullptr, p, N, sy, sz, sgn, r, nullptr, nullptr, v);
   double a = 0.0;
   if (st == NDSMK_TRACE_ZLO) {
     // (z = lo_z: the cell's z index is 0, so its base is the index into alpha0)

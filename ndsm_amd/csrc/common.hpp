@@ -34,6 +34,8 @@ int not_ready(const char *file, int line);
 
 constexpr int kWave = 64;   // CDNA wavefront
 
+typedef long long i64;      // counts and slots of variable-length results (scan64.hpp, line_walk.hpp)
+
 }  // namespace ndsm
 
 #define NDSM_HIP(call)                                                               \

@@ -157,6 +157,25 @@ __device__ __forceinline__ void line_snap(const LineArgs &p, int face, const dou
   }
 }
 
+// the basis (e1, e2) of the plane perpendicular to the unit vector w, from the axis j of the smallest |w_d| (the
+// lowest on a tie): u = axis_j - w_j w, e1 = u / |u|, e2 = w x e1 (the fan of a null from its normal: skeleton.hip,
+// separators.hip; squash.hip states the same rule for its seed frame)
+__device__ __forceinline__ void line_fan_basis(const double w[3], double e1[3], double e2[3]) {
+  int j = 0;
+  double small = fabs(w[0]), wj = w[0];
+  if (fabs(w[1]) < small) j = 1, small = fabs(w[1]), wj = w[1];
+  if (fabs(w[2]) < small) j = 2, wj = w[2];
+  double u[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) u[d] = (d == j ? 1.0 : 0.0) - wj * w[d];
+  const double un = sqrt((u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]);
+#pragma unroll
+  for (int d = 0; d < 3; ++d) e1[d] = u[d] / un;
+  e2[0] = w[1] * e1[2] - w[2] * e1[1];
+  e2[1] = w[2] * e1[0] - w[0] * e1[2];
+  e2[2] = w[0] * e1[1] - w[1] * e1[0];
+}
+
 // the mesh, the box and the step of a call into p (the shape and the spacings have been checked)
 inline void line_mesh(const int32_t *n3, const double *lo3, const double *h_dq3, double step, int max_steps,
                       LineArgs &p) {

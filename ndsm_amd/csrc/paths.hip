@@ -8,16 +8,16 @@
 //           scan64_k      in place: offsets[l] = the exclusive sum, offsets[nl] = the total; one workgroup, every lane
 //                         sums a contiguous run (scan64.hpp's scan64_total, shared with skeleton.hip and
 //                         separators.hip; the int64 sibling of nulls.hip's scan_k)
-//   fill    paths_k       one lane per line, one wave per workgroup, as trace_k: the loop of trace_k with
-//                         trace_step.hpp's stage and step - the same r and I - which stores the state before step
+//   fill    paths_k       one lane per line, one wave per workgroup, as trace_k: line_walk.hpp's line_walk, the very
+//                         loop trace_k runs - the same r and I -, with a visitor that stores the state before step
 //                         0, every, 2 every, ... once that step is known to move the line, and the final state
 //                         with one more interpolation at it.  Point j of line l goes to slot offsets[l] + j.
 // A lane writes slot offsets[l] + j only for j < min(offsets[l + 1], max_points) - offsets[l]: its own count from the
 // first pass and the capacity bound every store, whatever the second pass computes.  No atomic append, no guessed
 // capacity, no result that depends on the launch geometry.  No vector is indexed with a run-time axis (the rule of
 // squash.hip): the state stays in registers.
+#include "line_walk.hpp"
 #include "scan64.hpp"
-#include "trace_step.hpp"
 
 namespace {
 
@@ -29,42 +29,29 @@ __global__ __launch_bounds__(kNptsBlock) void npts_k(const int32_t *__restrict__
                                                      i64 *__restrict__ npts) {
   const size_t l = (size_t)blockIdx.x * kNptsBlock + threadIdx.x;
   if (l >= nl) return;
-  const int n = nsteps[l];
-  npts[l] = n <= 0 ? 1 : (i64)((n - 1) / every) + 2;
+  npts[l] = line_npts(nsteps[l], every);
 }
 
-struct PathOut {
-  double *points, *bpt, *gpt, *ipt;   // bpt, gpt, ipt may be nullptr: skipped
-};
-
-// slot k of the concatenation (the caller has bounded k)
+// what the filling half adds to the walk: the running integral, and the sampled states into the lane's slots
 template <bool kHasG>
-__device__ __forceinline__ void put_point(const PathOut &o, i64 k, double x, double y, double z, const double bv[3],
-                                          const double gv[3], double I) {
-  o.points[3 * k] = x;
-  o.points[3 * k + 1] = y;
-  o.points[3 * k + 2] = z;
-  if (o.bpt) {
-    o.bpt[3 * k] = bv[0];
-    o.bpt[3 * k + 1] = bv[1];
-    o.bpt[3 * k + 2] = bv[2];
+struct PathVisitor {
+  LineSlots &w;
+  double I = 0.0;
+  __device__ __forceinline__ void step(int it, const double r[3], const double bv[3], const double gv[3], double,
+                                       double dI) {
+    w.template sample<kHasG>(it, r, bv, gv, I);
+    I = I + dI;
   }
-  if (kHasG) {
-    if (o.gpt) {
-      o.gpt[3 * k] = gv[0];
-      o.gpt[3 * k + 1] = gv[1];
-      o.gpt[3 * k + 2] = gv[2];
-    }
-    if (o.ipt) o.ipt[k] = I;
-  }
-}
+  static constexpr int kArrived = 0;   // (never)
+  __device__ __forceinline__ bool arrived(const double *) { return false; }
+};
 
 // lane l: seed l % nseeds, direction block l / nseeds, as trace_k; its points go to slots offsets[l] + j, j < room
 template <bool kHasG>
 __global__ __launch_bounds__(kLineBlock) void paths_k(const double *__restrict__ B, const double *__restrict__ G,
                                                       const double *__restrict__ seeds,
                                                       const i64 *__restrict__ offsets, i64 every, i64 max_points,
-                                                      PathOut o, TrArgs p) {
+                                                      LinePts o, TrArgs p) {
   const size_t l = (size_t)blockIdx.x * kLineBlock + threadIdx.x;
   const size_t nl = (size_t)p.nseeds * (size_t)p.ndir;
   if (l >= nl) return;
@@ -73,58 +60,16 @@ __global__ __launch_bounds__(kLineBlock) void paths_k(const double *__restrict__
   const size_t sy = (size_t)p.n[0], sz = (size_t)p.n[0] * (size_t)p.n[1];
   const size_t N = sz * (size_t)p.n[2];
 
-  // the slots of this lane: [base, min(offsets[l + 1], max_points)) and nothing else
-  const i64 base = offsets[l];
-  const i64 next_base = offsets[l + 1];
-  const i64 stop = next_base < max_points ? next_base : max_points;
-  const i64 room = (base >= 0 && stop > base) ? stop - base : 0;
-  if (room == 0) return;
+  LineSlots w(o, offsets, l, every, max_points);
+  if (w.room == 0) return;
 
   double r[3] = {seeds[3 * is], seeds[3 * is + 1], seeds[3 * is + 2]};
-  double I = 0.0;
   double bv[3] = {0.0, 0.0, 0.0}, gv[3] = {0.0, 0.0, 0.0};
-  i64 j = 0;            // points stored so far
-  i64 due = 0;          // the next step count whose state is stored
-  bool inside = true;
-#pragma unroll
-  for (int d = 0; d < 3; ++d) inside = inside && (r[d] >= p.lo[d]) && (r[d] <= p.hi[d]);
-  if (!inside) {
-    // OUTSIDE: the seed's bits as given, nothing interpolated
-    put_point<kHasG>(o, base, r[0], r[1], r[2], bv, gv, 0.0);
-    return;
-  }
-  for (int it = 0; it < p.max_steps; ++it) {
-    double k1[3], q1, rn[3], dI;
-    if (!tr_stage<kHasG, true>(B, G, p, N, sy, sz, sgn, r[0], r[1], r[2], k1, q1, bv, gv) ||
-        !tr_rk4<kHasG>(B, G, p, N, sy, sz, sgn, r, k1, q1, p.ds, rn, dI))
-      break;                                    // NULL: the state after `it` steps is the final one
-    double t;
-    const int face = line_first_face(p, r, rn, t);
-    double s = p.ds;
-    if (face != 0) {
-      s = t * p.ds;
-      if (!tr_rk4<kHasG>(B, G, p, N, sy, sz, sgn, r, k1, q1, s, rn, dI)) break;
-    }
-    // step `it` moves the line: the state before it is a point when `it` is a multiple of every
-    if ((i64)it == due) {
-      if (j < room) put_point<kHasG>(o, base + j, r[0], r[1], r[2], bv, gv, I);
-      j = j + 1;
-      due = due + every;
-    }
-    I = I + dI;
-    if (face == 0) {
-      r[0] = rn[0], r[1] = rn[1], r[2] = rn[2];
-      continue;
-    }
-    line_snap(p, face, rn, r);
-    break;
-  }
-  // the final state, with B and G interpolated at it (after the snap)
-  if (j < room) {
-    double k1[3], q1;
-    (void)tr_stage<kHasG, true>(B, G, p, N, sy, sz, sgn, r[0], r[1], r[2], k1, q1, bv, gv);
-    put_point<kHasG>(o, base + j, r[0], r[1], r[2], bv, gv, I);
-  }
+  PathVisitor<kHasG> v = {w};
+  // OUTSIDE: no line, the seed's bits as given and nothing interpolated
+  const bool run = line_inside(p, r);
+  if (run) (void)line_walk<kHasG, true>(B, G, p, N, sy, sz, sgn, r, bv, gv, v);
+  w.template last<kHasG>(B, G, p, N, sy, sz, sgn, run, r, bv, gv, v.I);
 }
 
 int path_args(const char *usage, bool own_ok, bool arrays_ok, const int32_t *n3, const double *lo3,
@@ -181,7 +126,7 @@ extern "C" int ndsmk_paths_fill(const double *B, const double *G, const int32_t 
   if (rc != 0 || nseeds == 0 || max_points == 0) return rc;
   const size_t nl = (size_t)nseeds * (size_t)p.ndir;
   const unsigned nb = (unsigned)((nl + kLineBlock - 1) / kLineBlock);
-  const PathOut o = {points, bpt, G ? gpt : nullptr, G ? ipt : nullptr};
+  const LinePts o = {points, bpt, G ? gpt : nullptr, G ? ipt : nullptr};
   hipStream_t s = ndsm::stream();
   if (G)
     hipLaunchKernelGGL(paths_k<true>, dim3(nb), dim3(kLineBlock), 0, s, B, G, seeds, (const i64 *)offsets, (i64)every,

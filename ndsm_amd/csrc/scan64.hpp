@@ -9,8 +9,6 @@ namespace {
 
 constexpr int kScanBlock = 1024;
 
-typedef long long i64;
-
 // in place: a[q] <- a[0] + ... + a[q - 1] for q < ng, a[ng] <- the sum of all.  One workgroup: every lane sums a
 // contiguous run and rewrites that run alone; the kScanBlock run totals are scanned in LDS.
 __global__ __launch_bounds__(kScanBlock) void scan64_k(i64 *a, size_t ng) {

@@ -7,23 +7,23 @@
 //
 //   check   sep_check_k      one lane per bracket: a pair index outside 0 .. nnulls - 1 raises the flag the host reads
 //   refine  sep_refine_k     one wave per bracket, all rounds inside the launch: lane i traces the fan line of the
-//                            direction ((1 - t) a + t b) / |.|, t = i / 63, with trace_step.hpp's stage and step and keeps
+//                            direction ((1 - t) a + t b) / |.|, t = i / 63, with line_walk.hpp's line_walk and keeps
 //                            the side of the fan of m' at its closest approach; a ballot finds the lowest lane whose side
 //                            differs from lane 0's, shuffles fetch the two directions round the change, and the arc
 //                            shrinks by 63 per round.  The per-bracket outputs, and the seed and the direction of the
 //                            bracket's line, go to scratch.
-//   count   sep_line_k<0>    one lane per bracket, as skel_line_k with the capture test against m' alone: ends, length,
-//                            status, nsteps, and offsets[l] = npts(l)
+//   count   sep_line_k<0>    one lane per bracket: line_walk.hpp's null_line, the body of skel_line_k, with the capture
+//                            test against m' alone: ends, length, status, nsteps, and offsets[l] = npts(l)
 //           scan64_total     scan64.hpp: the scan in place and the total, as paths.hip
-//   fill    sep_line_k<1>    the same loop - the same expressions, so the same bits - which stores the points
+//   fill    sep_line_k<1>    the same call, so the same bits, which stores the points
 // The flag of the check, the seeds and the directions live in g_sep, a line_scratch.hpp LineScratch with one leading
 // slot.
 // A lane writes slot offsets[l] + j only for j < min(offsets[l + 1], max_points) - offsets[l].  No wave ever leaves
 // sep_refine_k's round loop with part of its lanes: the exits are decided from ballots and lane 0's values, which every
 // lane holds.
 #include "line_scratch.hpp"
+#include "line_walk.hpp"
 #include "scan64.hpp"
-#include "trace_step.hpp"
 
 namespace {
 
@@ -46,36 +46,24 @@ struct SepOut {
   double *seeds, *sgn;              // scratch: 3 per bracket, 1 per bracket
 };
 
-// The fan line from r0 in the direction sgn, up to its end (a face, a null of the interpolant, max_steps, or the capture
-// by the null at tp): the smallest d2 to tp over the points after the accepted full steps (the first of them on a tie),
-// g = w' . (r - tp) there, and whether the line was captured.  Nothing is stored: the exit step is not redone.
-__device__ __forceinline__ void sep_trace(const double *__restrict__ B, const TrArgs &p, size_t N, size_t sy, size_t sz,
-                                          double sgn, const double r0[3], const double tp[3], const double tw[3],
-                                          double cap2, double &best, double &g, bool &captured) {
-  double r[3] = {r0[0], r0[1], r0[2]};
-  bool inside = true;
-#pragma unroll
-  for (int d = 0; d < 3; ++d) inside = inside && (r[d] >= p.lo[d]) && (r[d] <= p.hi[d]);
-  if (sgn == 0.0 || !inside) return;
-  for (int it = 0; it < p.max_steps; ++it) {
-    double k1[3], q1, rn[3], dI, t;
-    if (!tr_stage<false, false>(B, nullptr, p, N, sy, sz, sgn, r[0], r[1], r[2], k1, q1) ||
-        !tr_rk4<false>(B, nullptr, p, N, sy, sz, sgn, r, k1, q1, p.ds, rn, dI))
-      break;
-    if (line_first_face(p, r, rn, t) != 0) break;
-    r[0] = rn[0], r[1] = rn[1], r[2] = rn[2];
+// The closest approach of a fan line to the null at tp: the smallest d2 over the points after the accepted full steps
+// (the first of them on a tie), g = w' . (r - tp) there; the walk ends where the null captures the line.
+struct SepApproach {
+  const double *tp, *tw;
+  double cap2;
+  double best = INFINITY, g = 0.0;
+  __device__ __forceinline__ void step(int, const double *, const double *, const double *, double, double) {}
+  static constexpr int kArrived = NDSMK_SKEL_CAPTURED;
+  __device__ __forceinline__ bool arrived(const double r[3]) {
     const double dx = r[0] - tp[0], dy = r[1] - tp[1], dz = r[2] - tp[2];
     const double d2 = (dx * dx + dy * dy) + dz * dz;
     if (d2 < best) {
       best = d2;
       g = (tw[0] * dx + tw[1] * dy) + tw[2] * dz;
     }
-    if (d2 <= cap2) {
-      captured = true;
-      break;
-    }
+    return d2 <= cap2;
   }
-}
+};
 
 // workgroup = wave = bracket br.  rho = radius min(h), cap2 = (capture min(h))^2 > 0.
 __global__ __launch_bounds__(kLineBlock) void sep_refine_k(const double *__restrict__ B, const double *__restrict__ pos,
@@ -97,23 +85,9 @@ __global__ __launch_bounds__(kLineBlock) void sep_refine_k(const double *__restr
   const bool valid = m != m2 && ((k0 > 0 && k1 < 0) || (k0 < 0 && k1 > 0));
   const double sg = k0 > 0 ? 1.0 : -1.0;
 
-  // the fan basis of m from its normal: skel_type_k's expressions
+  // the fan basis of m from its normal, as skel_type_k forms it
   double e1[3], e2[3];
-  {
-    int j = 0;
-    double small = fabs(w[0]), wj = w[0];
-    if (fabs(w[1]) < small) j = 1, small = fabs(w[1]), wj = w[1];
-    if (fabs(w[2]) < small) j = 2, wj = w[2];
-    double u[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) u[d] = (d == j ? 1.0 : 0.0) - wj * w[d];
-    const double un = sqrt((u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]);
-#pragma unroll
-    for (int d = 0; d < 3; ++d) e1[d] = u[d] / un;
-    e2[0] = w[1] * e1[2] - w[2] * e1[1];
-    e2[1] = w[2] * e1[0] - w[0] * e1[2];
-    e2[2] = w[0] * e1[1] - w[1] * e1[0];
-  }
+  line_fan_basis(w, e1, e2);
 
   double ca = arc[4 * br], sa = arc[4 * br + 1], cb = arc[4 * br + 2], sb = arc[4 * br + 3];
   int state = kSepNone, nr = 0, side = 0;
@@ -131,9 +105,13 @@ __global__ __launch_bounds__(kLineBlock) void sep_refine_k(const double *__restr
       double seed[3];
 #pragma unroll
       for (int d = 0; d < 3; ++d) seed[d] = r0[d] + rho * (c * e1[d] + s * e2[d]);
-      double best = INFINITY, g = 0.0;
+      // (the walk without its exit step: nothing is stored, so the step that leaves the box is not redone)
+      SepApproach v = {tp, tw, cap2};
       bool captured = false;
-      sep_trace(B, p, N, sy, sz, ok ? sg : 0.0, seed, tp, tw, cap2, best, g, captured);
+      if (ok && line_inside(p, seed))
+        captured = line_walk<false, false, false>(B, nullptr, p, N, sy, sz, sg, seed, nullptr, nullptr, v) ==
+                   NDSMK_SKEL_CAPTURED;
+      const double best = v.best, g = v.g;
       const int cls = best < INFINITY ? (g >= 0.0 ? 1 : (g < 0.0 ? -1 : 0)) : 0;
 
       // the lowest lane >= 1 on another side than lane 0, and the two lanes round the change
@@ -187,26 +165,19 @@ __global__ __launch_bounds__(kLineBlock) void sep_refine_k(const double *__restr
   o.sgn[br] = line ? sg : 0.0;
 }
 
-struct SepLineOut {
-  double *ends, *length;            // the counting pass
-  int32_t *status, *nsteps;
-  i64 *npts;                        // offsets before the scan
-  double *points, *bpt;             // the filling pass (bpt may be nullptr)
+// the capture test of a separator: the one target null, always tested
+struct SepCapture {
+  static constexpr bool kHit = false;
+  double tp[3], cap2;
+  __device__ __forceinline__ bool test(const double r[3]) const {
+    const double dx = r[0] - tp[0], dy = r[1] - tp[1], dz = r[2] - tp[2];
+    return (dx * dx + dy * dy) + dz * dz <= cap2;
+  }
 };
 
-__device__ __forceinline__ void sep_put(const SepLineOut &o, i64 k, const double r[3], const double bv[3]) {
-  o.points[3 * k] = r[0];
-  o.points[3 * k + 1] = r[1];
-  o.points[3 * k + 2] = r[2];
-  if (o.bpt) {
-    o.bpt[3 * k] = bv[0];
-    o.bpt[3 * k + 1] = bv[1];
-    o.bpt[3 * k + 2] = bv[2];
-  }
-}
-
 // lane l: the line of bracket l, from seeds[l] in the direction sgn[l] (0: no line, one point), captured by the null
-// pair[2 l + 1] alone.  p.nseeds = nbr.  skel_line_k's loop, expression by expression.
+// pair[2 l + 1] alone.  p.nseeds = nbr.  The body is line_walk.hpp's null_line: skel_line_k's loop with this capture
+// test, on the shared walk.
 template <bool kFill>
 __global__ __launch_bounds__(kLineBlock) void sep_line_k(const double *__restrict__ B,
                                                          const double *__restrict__ seeds,
@@ -214,97 +185,12 @@ __global__ __launch_bounds__(kLineBlock) void sep_line_k(const double *__restric
                                                          const double *__restrict__ pos,
                                                          const int32_t *__restrict__ pair, double cap2,
                                                          const i64 *__restrict__ offsets, i64 every, i64 max_points,
-                                                         SepLineOut o, TrArgs p) {
+                                                         NullLineOut o, TrArgs p) {
   const size_t l = (size_t)blockIdx.x * kLineBlock + threadIdx.x;
   if (l >= (size_t)p.nseeds) return;
-  const double sgn = sgns[l];
-  const size_t sy = (size_t)p.n[0], sz = (size_t)p.n[0] * (size_t)p.n[1];
-  const size_t N = sz * (size_t)p.n[2];
-
-  i64 base = 0, room = 0;
-  if (kFill) {
-    // the slots of this lane: [base, min(offsets[l + 1], max_points)) and nothing else
-    base = offsets[l];
-    const i64 next_base = offsets[l + 1];
-    const i64 stop = next_base < max_points ? next_base : max_points;
-    room = (base >= 0 && stop > base) ? stop - base : 0;
-    if (room == 0) return;
-  }
-
   const size_t m2 = (size_t)pair[2 * l + 1];
-  const double tp[3] = {pos[3 * m2], pos[3 * m2 + 1], pos[3 * m2 + 2]};
-  double r[3] = {seeds[3 * l], seeds[3 * l + 1], seeds[3 * l + 2]};
-  double len = 0.0;
-  double bv[3] = {0.0, 0.0, 0.0};
-  int st = NDSMK_TRACE_UNFINISHED, ns = 0;
-  i64 j = 0, due = 0;
-  bool inside = true, run = true;
-#pragma unroll
-  for (int d = 0; d < 3; ++d) inside = inside && (r[d] >= p.lo[d]) && (r[d] <= p.hi[d]);
-  if (sgn == 0.0) {
-    st = NDSMK_SKEL_NONE;
-    run = false;
-  } else if (!inside) {
-    st = NDSMK_TRACE_OUTSIDE;
-    run = false;
-  }
-  if (run) {
-    for (int it = 0; it < p.max_steps; ++it) {
-      double k1[3], q1, rn[3], dI;
-      if (!tr_stage<false, true>(B, nullptr, p, N, sy, sz, sgn, r[0], r[1], r[2], k1, q1, bv, nullptr) ||
-          !tr_rk4<false>(B, nullptr, p, N, sy, sz, sgn, r, k1, q1, p.ds, rn, dI)) {
-        st = NDSMK_TRACE_NULL;
-        break;
-      }
-      double t;
-      const int face = line_first_face(p, r, rn, t);
-      double s = p.ds;
-      if (face != 0) {
-        s = t * p.ds;
-        if (!tr_rk4<false>(B, nullptr, p, N, sy, sz, sgn, r, k1, q1, s, rn, dI)) {
-          st = NDSMK_TRACE_NULL;
-          break;
-        }
-      }
-      // step `it` moves the line: the state before it is a point when `it` is a multiple of every
-      if ((i64)it == due) {
-        if (kFill && j < room) sep_put(o, base + j, r, bv);
-        j = j + 1;
-        due = due + every;
-      }
-      len = len + s;
-      ns = it + 1;
-      if (face != 0) {
-        line_snap(p, face, rn, r);
-        st = face;
-        break;
-      }
-      r[0] = rn[0], r[1] = rn[1], r[2] = rn[2];
-      const double dx = r[0] - tp[0], dy = r[1] - tp[1], dz = r[2] - tp[2];
-      if ((dx * dx + dy * dy) + dz * dz <= cap2) {
-        st = NDSMK_SKEL_CAPTURED;
-        break;
-      }
-    }
-  }
-  if (kFill) {
-    // the final state, with B interpolated at it (after the snap); nothing is interpolated where no line ran
-    if (j < room) {
-      if (run) {
-        double k1[3], q1;
-        (void)tr_stage<false, true>(B, nullptr, p, N, sy, sz, sgn, r[0], r[1], r[2], k1, q1, bv, nullptr);
-      }
-      sep_put(o, base + j, r, bv);
-    }
-  } else {
-    o.ends[3 * l] = r[0];
-    o.ends[3 * l + 1] = r[1];
-    o.ends[3 * l + 2] = r[2];
-    o.length[l] = len;
-    o.status[l] = st;
-    o.nsteps[l] = ns;
-    o.npts[l] = ns <= 0 ? 1 : (i64)((ns - 1) / (int)every) + 2;
-  }
+  SepCapture cap = {{pos[3 * m2], pos[3 * m2 + 1], pos[3 * m2 + 2]}, cap2};
+  null_line<kFill>(B, seeds, sgns, l, cap, offsets, every, max_points, o, p);
 }
 
 // (the leading slot is the flag of the check)
@@ -328,10 +214,7 @@ int sep_args(bool arrays_ok, const int32_t *n3, const double *lo3, const double 
   // (kLineBlock lanes per bracket in the refinement)
   const int rc = line_args(kSepUsage, own_ok, arrays_ok, n3, lo3, h_dq3, nbr, step, max_steps, kLineBlock, p);
   if (rc != 0 || nbr == 0) return rc;
-  const double hmin = fmin(fmin(h_dq3[0], h_dq3[1]), h_dq3[2]);
-  rho = radius * hmin;
-  const double cr = capture * hmin;
-  cap2 = cr * cr;
+  null_line_radii(h_dq3, radius, capture, rho, cap2);
   // (a capture whose square underflows would switch the test off)
   if (!(cap2 > 0.0)) return fail(NDSMK_EVALUE, kSepUsage, __FILE__, __LINE__);
   return 0;
@@ -375,7 +258,7 @@ extern "C" int ndsmk_sep_count(const double *B, const int32_t *n3, const double 
   hipLaunchKernelGGL(sep_refine_k, dim3((unsigned)nb), dim3(kLineBlock), 0, s, B, pos, kind, normal, pair, arc, rho, cap2,
                      rounds, tol, ro, p);
   NDSM_LAUNCH_CHECK();
-  const SepLineOut o = {ends, length, status, nsteps, (i64 *)offsets, nullptr, nullptr};
+  const NullLineOut o = {ends, length, status, nsteps, nullptr, (i64 *)offsets, {nullptr, nullptr, nullptr, nullptr}};
   hipLaunchKernelGGL(sep_line_k<false>, dim3((unsigned)((nb + kLineBlock - 1) / kLineBlock)), dim3(kLineBlock), 0, s, B,
                      seeds, sgns, pos, pair, cap2, (const i64 *)nullptr, (i64)every, (i64)max_points, o, p);
   NDSM_LAUNCH_CHECK();
@@ -400,7 +283,7 @@ extern "C" int ndsmk_sep_fill(const double *B, const int32_t *n3, const double *
   // (the seeds and directions are those the counting half of this call left in the scratch; it checked the pairs)
   NDSM_CHECK_ARG(g_sep.buf && g_sep.lanes == nb);
   const double *seeds = g_sep.seeds(), *sgns = g_sep.sgns(nb);
-  const SepLineOut o = {nullptr, nullptr, nullptr, nullptr, nullptr, points, bpt};
+  const NullLineOut o = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, {points, bpt, nullptr, nullptr}};
   hipStream_t s = ndsm::stream();
   hipLaunchKernelGGL(sep_line_k<true>, dim3((unsigned)((nb + kLineBlock - 1) / kLineBlock)), dim3(kLineBlock), 0, s, B,
                      seeds, sgns, pos, pair, cap2, (const i64 *)offsets, (i64)every, (i64)max_points, o, p);

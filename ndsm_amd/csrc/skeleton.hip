@@ -14,14 +14,18 @@
 //           scan64_total     scan64.hpp: the scan in place and the total, as paths.hip
 //   fill    skel_line_k<1>   the same loop - the same expressions, so the same bits - which stores the points as
 //                            paths_k does: point j of line l goes to slot offsets[l] + j
+// skel_line_k keeps its own text of the loop that line_walk.hpp's line_walk states for every other line kernel
+// (null_line there is this kernel's body with the capture test as a policy, and serves separators.hip): on the shared
+// walk the filling kernel with capture came out 7 % slower on an MI355X for no reason found in its instructions
+// (DESIGN.md "Shared line machinery").  A fix to line_walk is made here too.
 // The seeds and directions pass from the counting to the filling half in g_skel, a line_scratch.hpp LineScratch.
 // A lane writes slot offsets[l] + j only for j < min(offsets[l + 1], max_points) - offsets[l].  No atomic append, no
 // guessed capacity, no vector indexed with a run-time axis.  In the capture loop every lane reads the same null
 // positions in the same order: plain global loads at a lane-independent address, served by the caches (DESIGN.md
 // says why they are not staged in LDS).
 #include "line_scratch.hpp"
+#include "line_walk.hpp"
 #include "scan64.hpp"
-#include "trace_step.hpp"
 
 namespace {
 
@@ -146,19 +150,7 @@ __global__ __launch_bounds__(kTypeBlock) void skel_type_k(const double *__restri
   }
   if (ok) {
     // the fan basis, the squash entry's start rule with w in place of e
-    int j = 0;
-    double small = fabs(w[0]), wj = w[0];
-    if (fabs(w[1]) < small) j = 1, small = fabs(w[1]), wj = w[1];
-    if (fabs(w[2]) < small) j = 2, wj = w[2];
-    double u[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) u[d] = (d == j ? 1.0 : 0.0) - wj * w[d];
-    const double un = sqrt((u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]);
-#pragma unroll
-    for (int d = 0; d < 3; ++d) e1[d] = u[d] / un;
-    e2[0] = w[1] * e1[2] - w[2] * e1[1];
-    e2[1] = w[2] * e1[0] - w[0] * e1[2];
-    e2[2] = w[0] * e1[1] - w[1] * e1[0];
+    line_fan_basis(w, e1, e2);
   }
   const double p2 = cc / mu;
   const double disc = t * t - 4.0 * p2;
@@ -353,10 +345,7 @@ int skel_args(bool arrays_ok, const int32_t *n3, const double *lo3, const double
   const int rc = line_args(kSkelUsage, own_ok, arrays_ok, n3, lo3, h_dq3, nnulls, step, max_steps,
                            own_ok ? 2 + nring : 1, p);
   if (rc != 0 || nnulls == 0) return rc;
-  const double hmin = fmin(fmin(h_dq3[0], h_dq3[1]), h_dq3[2]);
-  rho = radius * hmin;
-  const double cr = capture * hmin;
-  cap2 = cr * cr;
+  null_line_radii(h_dq3, radius, capture, rho, cap2);
   return 0;
 }
 

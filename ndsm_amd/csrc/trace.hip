@@ -11,12 +11,27 @@
 //                               r' = r + (s / 6) (((k1 + 2 k2) + 2 k3) + k4), dI = (s / 6) (((q1 + 2 q2) + 2 q3) + q4)
 //   exit                        r' outside [lo, hi]: the step is redone from r with s = t ds (k1, q1 kept), t of the
 //                               first face; then the end is snapped onto that face.
-// Every lane's loop is bounded by max_steps.  The stage and the step are trace_step.hpp's, shared with paths.hip.
-#include "trace_step.hpp"
+// Every lane's loop is bounded by max_steps.  The stage and the step are trace_step.hpp's and the loop itself is
+// line_walk.hpp's line_walk, shared with paths.hip, alphamap.hip and separators.hip; this entry adds the sums of the
+// accepted steps.
+#include "line_walk.hpp"
 
 namespace {
 
 using namespace ndsm;
+
+// the sums of a line: formed for accepted steps only, so a null leaves them at the previous step's values
+struct TraceSums {
+  double len = 0.0, I = 0.0;
+  int ns = 0;
+  __device__ __forceinline__ void step(int it, const double *, const double *, const double *, double s, double dI) {
+    len = len + s;
+    I = I + dI;
+    ns = it + 1;
+  }
+  static constexpr int kArrived = 0;   // (never)
+  __device__ __forceinline__ bool arrived(const double *) { return false; }
+};
 
 // lane l: seed l % nseeds, direction block l / nseeds.  Outputs per lane: ends[3 l .. 3 l + 2], length[l],
 // integral[l], status[l], nsteps[l].
@@ -35,51 +50,16 @@ __global__ __launch_bounds__(kLineBlock) void trace_k(const double *__restrict__
   const size_t N = sz * (size_t)p.n[2];
 
   double r[3] = {seeds[3 * is], seeds[3 * is + 1], seeds[3 * is + 2]};
-  double len = 0.0, I = 0.0;
-  int st = NDSMK_TRACE_UNFINISHED, ns = 0;
-  bool inside = true;
-#pragma unroll
-  for (int d = 0; d < 3; ++d) inside = inside && (r[d] >= p.lo[d]) && (r[d] <= p.hi[d]);
-  if (!inside) {
-    st = NDSMK_TRACE_OUTSIDE;
-  } else {
-    for (int it = 0; it < p.max_steps; ++it) {
-      double k1[3], q1, rn[3], dI;
-      if (!tr_stage<kHasG>(B, G, p, N, sy, sz, sgn, r[0], r[1], r[2], k1, q1) ||
-          !tr_rk4<kHasG>(B, G, p, N, sy, sz, sgn, r, k1, q1, p.ds, rn, dI)) {
-        st = NDSMK_TRACE_NULL;
-        break;
-      }
-      double t;
-      const int face = line_first_face(p, r, rn, t);
-      if (face == 0) {
-        r[0] = rn[0], r[1] = rn[1], r[2] = rn[2];
-        len = len + p.ds;
-        I = I + dI;
-        ns = it + 1;
-        continue;
-      }
-      // the step is redone with the length that reaches the face; stage 1 is the same
-      const double s = t * p.ds;
-      if (!tr_rk4<kHasG>(B, G, p, N, sy, sz, sgn, r, k1, q1, s, rn, dI)) {
-        st = NDSMK_TRACE_NULL;
-        break;
-      }
-      line_snap(p, face, rn, r);
-      len = len + s;
-      I = I + dI;
-      ns = it + 1;
-      st = face;
-      break;
-    }
-  }
+  TraceSums v;
+  int st = NDSMK_TRACE_OUTSIDE;
+  if (line_inside(p, r)) st = line_walk<kHasG, false>(B, G, p, N, sy, sz, sgn, r, nullptr, nullptr, v);
   ends[3 * l] = r[0];
   ends[3 * l + 1] = r[1];
   ends[3 * l + 2] = r[2];
-  length[l] = len;
-  integral[l] = I;
+  length[l] = v.len;
+  integral[l] = v.I;
   status[l] = st;
-  nsteps[l] = ns;
+  nsteps[l] = v.ns;
 }
 
 }  // namespace

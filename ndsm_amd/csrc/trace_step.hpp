@@ -1,6 +1,6 @@
-// One stage and one RK4 step of a traced field line, shared by trace.hip and paths.hip (the expressions are written
-// out at the top of trace.hip and in include/ndsm_hip.h; fixed fp64 operand order, no contraction).  Both files trace
-// with these very functions, so a path's points carry the bits of the trace entry's states.
+// One stage and one RK4 step of a traced field line, shared by every line kernel (the expressions are written out at
+// the top of trace.hip and in include/ndsm_hip.h; fixed fp64 operand order, no contraction).  line_walk.hpp builds the
+// walk from these very functions, so a path's points carry the bits of the trace entry's states.
 #pragma once
 
 #include "line.hpp"

@@ -1,4 +1,4 @@
-"""GPU tests of the eight ndsm_hip_vecpot_*_device entries on caller arrays as a caller has them (run with -m gpu on an
+"""GPU tests of the ten ndsm_hip_vecpot_*_device entries on caller arrays as a caller has them (run with -m gpu on an
 MI355X): views into one larger allocation, aligned as far as their element type asks (doubles and int64 at 8 mod 16,
 int32 at 4 mod 8), with guard bands on both sides - NaN beside the input fields - and at the smallest shapes the handle
 takes (4 points per axis).  device_arena.Arena lays the arrays out, runs the entry and fails when a byte outside the
@@ -16,7 +16,7 @@ import pytest
 
 from device_arena import Arena, LibTransport, slot
 from golden_inputs import analytic_case, aniso_mesh, uniform_mesh
-from line_model import FACES, abc, face_seeds, inner_seeds, squash_numpy, trace_numpy
+from line_model import FACES, abc, face_seeds, inner_seeds, sheared, squash_numpy, trace_numpy
 from null_model import nulls_numpy
 from test_gpu_devore import assert_reduction, devore_numpy, flux
 from test_gpu_nulls import assert_bitwise
@@ -432,5 +432,109 @@ def test_project_on_offset_arrays(hip, mname, ns):
                 same_bits(got[1], phi, what + ": phi")
             assert out_d.tobytes() == out_h.tobytes(), (what, out_d, out_h)
         assert np.isfinite(out_h).all() and np.isfinite(B).all() and not np.array_equal(B, b.reshape(-1))
+    finally:
+        V.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# e. the two Grad-Rubin entries: the solve for a prescribed current and the iteration
+# ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("ns", SOLVE_SHAPES, ids=IDS)
+@pytest.mark.parametrize("mname", list(MESHES))
+def test_solve_current_on_offset_arrays(hip, mname, ns):
+    """ndsm_hip_vecpot_solve_current_device: J is read only, A and B go in and come out (line_model's sheared field for
+    B.n, a third of the ABC field as the current, test_gpu_field's guess)"""
+    import ndsm_amd
+    mesh = MESHES[mname](ns)
+    L = ndsm_amd.load_library()
+    b, j, a0 = sheared(mesh), 0.3 * abc(mesh), 0.01 * np.cos(abc(mesh))
+    V = ndsm_amd.VecPot(*mesh)
+    try:
+        io_h, ro_h = options(V)
+        J, A, B = j.reshape(-1).copy(), a0.reshape(-1).copy(), b.reshape(-1).copy()
+        rc_h = L.ndsm_hip_vecpot_solve_current(V.h, io_h.ctypes.data_as(_ip), ro_h.ctypes.data_as(_dp),
+                                               J.ctypes.data_as(_dp), A.ctypes.data_as(_dp), B.ctypes.data_as(_dp))
+        assert np.array_equal(J, j.reshape(-1))
+        for plain in (False, True):
+            io_d, ro_d = options(V)
+            R = arena(V, [slot("J", j.reshape(-1), field=True), slot("A", a0.reshape(-1), output=True, field=True),
+                          slot("B", b.reshape(-1), output=True, field=True)], plain=plain)
+            _gJ, gA, gB = R.run(lambda dJ, dA, dB: L.ndsm_hip_vecpot_solve_current_device(
+                V.h, io_d.ctypes.data_as(_ip), ro_d.ctypes.data_as(_dp), dJ, dA, dB))
+            what = "solve_current %s %s (plain %s)" % (mname, ns, plain)
+            same_options(V, (R.rc, io_d, ro_d), (rc_h, io_h, ro_h), what)
+            same_bits(gA, A, what + ": A")
+            same_bits(gB, B, what + ": B")
+        assert np.isfinite(A).all() and np.isfinite(B).all() and not np.array_equal(A, a0.reshape(-1))
+    finally:
+        V.close()
+
+
+def nlfff_host(V, b, alpha0, a0, start, passes, max_steps, with_status=True):
+    """one call of ndsm_hip_vecpot_nlfff on host arrays: (rc, ioptc, ropt), [B, A, alpha, status], hist, niter"""
+    io, ro = options(V)
+    B, A, al0 = b.reshape(-1).copy(), a0.reshape(-1).copy(), alpha0.reshape(-1).copy()
+    alpha, status = np.full(B.size // 3, float(FILL)), np.full(B.size // 3, FILL, dtype=np.int32)
+    hist, niter = np.full((passes, 4), np.nan), ctypes.c_int(FILL)
+    rc = V.L.ndsm_hip_vecpot_nlfff(V.h, io.ctypes.data_as(_ip), ro.ctypes.data_as(_dp), B.ctypes.data, al0.ctypes.data,
+                                   1, start, passes, 0.0, 0.5, max_steps, A.ctypes.data, alpha.ctypes.data,
+                                   status.ctypes.data if with_status else None, hist.ctypes.data_as(_dp),
+                                   ctypes.byref(niter))
+    assert np.array_equal(al0, alpha0.reshape(-1))
+    return (rc, io, ro), [B, A, alpha, status], hist, niter.value
+
+
+@pytest.mark.parametrize("ns", SOLVE_SHAPES, ids=IDS)
+@pytest.mark.parametrize("mname", list(MESHES))
+def test_nlfff_on_offset_arrays(hip, mname, ns):
+    """ndsm_hip_vecpot_nlfff_device: B and A go in and come out, alpha0 (a 2-D array, NaN beside it) is read only,
+    alpha and status come out; hist and niter_out stay on the host.  The fields B^k and B^{k+1} alternate between the
+    caller's B and the handle's own, so the last one lies in the caller's array after an even number of passes and is
+    copied there after an odd one: 1, 2 and 3 passes, from the potential start (A is not read) and from the given one
+    (the sheared field, boundary_alpha's alpha0, a small guess).  Once without a status array: the count of the
+    history is taken in a scratch array, and nothing of the caller's is written in its place."""
+    import ndsm_amd
+    mesh = MESHES[mname](ns)
+    L = ndsm_amd.load_library()
+    b, a0 = sheared(mesh), 0.01 * np.cos(abc(mesh))
+    alpha0 = ndsm_amd.boundary_alpha(mesh[0], mesh[1], b, 1e-3)
+    assert np.abs(alpha0).max() > 0.1
+    npts = b.size // 3
+    V = ndsm_amd.VecPot(*mesh)
+    max_steps = V.default_max_steps(0.5)
+    try:
+        for start in (0, 1):
+            for passes in (1, 2, 3):
+                opt_h, host, hist_h, niter_h = nlfff_host(V, b, alpha0, a0, start, passes, max_steps)
+                assert niter_h == passes and np.isfinite(hist_h).all() and hist_h[-1, 3] == (host[3] == 5).sum() > 0
+                for plain, with_status in ((False, True), (True, True)) + (((False, False),) if passes == 2 else ()):
+                    io_d, ro_d = options(V)
+                    hist_d, niter_d = np.full((passes, 4), np.nan), ctypes.c_int(FILL)
+                    slots = [slot("B", b.reshape(-1), output=True, field=True), slot("alpha0", alpha0, field=True),
+                             slot("A", a0.reshape(-1), output=True, field=True),
+                             slot("alpha", np.full(npts, float(FILL)), output=True)]
+                    if with_status:
+                        slots.append(slot("status", np.full(npts, FILL, dtype=np.int32), output=True))
+                    R = arena(V, slots, plain=plain)
+                    got = R.run(lambda dB, da0, dA, dal, dst=None: L.ndsm_hip_vecpot_nlfff_device(
+                        V.h, io_d.ctypes.data_as(_ip), ro_d.ctypes.data_as(_dp), dB, da0, 1, start, passes, 0.0, 0.5,
+                        max_steps, dA, dal, dst, hist_d.ctypes.data_as(_dp), ctypes.byref(niter_d)))
+                    what = "nlfff %s %s start %d, %d passes (plain %s, status %s)" % (mname, ns, start, passes, plain,
+                                                                                     with_status)
+                    same_options(V, (R.rc, io_d, ro_d), opt_h, what)
+                    same_bits(got[0], host[0], what + ": B")
+                    same_bits(got[2], host[1], what + ": A")
+                    same_bits(got[3], host[2], what + ": alpha")
+                    if with_status:
+                        same_bits(got[4], host[3], what + ": status")
+                    assert niter_d.value == niter_h and hist_d.tobytes() == hist_h.tobytes(), (what, hist_d, hist_h)
+                if passes == 2:
+                    # the host entry without a status array: the same fields and history
+                    opt_n, none, hist_n, niter_n = nlfff_host(V, b, alpha0, a0, start, passes, max_steps, with_status=False)
+                    same_options(V, opt_n, opt_h, "nlfff host entry, status NULL")
+                    for k in range(3):
+                        same_bits(none[k], host[k], "nlfff host entry, status NULL: array %d" % k)
+                    assert niter_n == niter_h and hist_n.tobytes() == hist_h.tobytes()
+                    assert np.all(none[3] == FILL)
     finally:
         V.close()

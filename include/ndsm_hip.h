@@ -904,6 +904,9 @@ int ndsm_hip_debug_fused_cfg(int two, int one, int res, int work_items, int big)
  *   NDSM_FUSED_CFG, the two of NDSM_BLOCK_CFG, NDSM_HIP_NO_BLOCK.  out[0..5] = error code, passes, result buffer,
  *   residual covered, metric covered, interpolation only; then nine values per pass: kind, sweeps, mode,
  *   instantiation, block height, src, dst, interpolation first, mean shift.
+ * what = 2: what = 0 with the zero-source field (a coarse level's zero first guess that was never written): req[13],
+ *   req[12] = the source is zero; out[0..6], out[6] = the zeros have to be written first; ten values per pass, the
+ *   tenth = this pass takes its source from a descriptor of zero records.
  * what = 1: req[6] = owned planes, tiles, workgroup slots, pipeline depth, residual pipeline, work-item override;
  *   out[0..1] = chunks, planes per chunk.
  * Returns 9002 for a null array, a value out of range or cap (entries of out) too small for the answer. */
@@ -913,6 +916,17 @@ int ndsm_hip_debug_relax_plan(int what, const int32_t *grid, const int64_t *req,
  * (csrc/tail.hip: all of them resident in LDS, one workgroup) covers them; 1 = default (environment
  * NDSM_HIP_NO_TAIL switches it off for a whole process).  Same bits either way. */
 int ndsm_hip_debug_tail(int on);
+/* 0: the descent of a V-cycle writes the zero first guess of every coarse level and the level's pre-smoothing loads
+ * it, as before; 1 = default: where the first pre-smoothing launch of the level is an out-of-place fused pass the
+ * restriction leaves u alone and that launch takes the zeros from a buffer descriptor of zero records (environment
+ * NDSM_HIP_NO_ZERO_GUESS=1 switches it off for a whole process).  Same bits either way.
+ * For the tests of this, ndsm_hip_mg_op has two more operations: 11 = u(level) is zero the way the descent leaves
+ * it (declared while the feature is on, written otherwise), 12 = the restriction level -> level+1 the way the
+ * descent of a V-cycle from level 1 does it. */
+int ndsm_hip_debug_zero_guess(int on);
+/* 1: u(level) of this ndsm_hip_mg_create handle is at present a zero guess that was declared and not written (any
+ * download, upload or single operation that reads it writes the zeros first), 0: it is in memory */
+int ndsm_hip_debug_u_declared_zero(void *handle, int level);
 
 #ifdef __cplusplus
 }

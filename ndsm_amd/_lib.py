@@ -133,6 +133,8 @@ def load_library(path=None):
     L.ndsm_hip_memcpy_d2h.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
     L.ndsm_hip_debug_relax_plan.argtypes = [ctypes.c_int, _ip, ctypes.POINTER(ctypes.c_int64),
                                             ctypes.POINTER(ctypes.c_int64), ctypes.c_int, _ip]
+    L.ndsm_hip_debug_zero_guess.argtypes = [ctypes.c_int]
+    L.ndsm_hip_debug_u_declared_zero.argtypes = [ctypes.c_void_p, ctypes.c_int]
     if path is None:
         _LIB = L
     return L
@@ -169,6 +171,7 @@ def _f64(a):
 # ops / buffers of ndsm_hip_mg_op, ndsm_hip_mg_upload (ndsmh_mg.f90)
 BUF_U, BUF_RHS, BUF_R, BUF_UALT = 0, 1, 2, 3   # BUF_UALT: the partner array of u (tests)
 OP_RELAX, OP_RESIDUAL, OP_RESTRICT, OP_PROLONG, OP_EXACT, OP_RELAX_COLOR, OP_RELAX_FUSED, _OP_RETIRED_7, OP_RELAX_RES, OP_RELAX_RES_FUSED = range(10)
+OP_ZERO_U, OP_DESCEND = 11, 12   # tests of the zero first guess (ndsm_hip_debug_zero_guess in include/ndsm_hip.h)
 
 
 class MGSolver:

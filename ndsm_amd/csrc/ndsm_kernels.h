@@ -129,6 +129,18 @@ int ndsmk_relax(const ndsmk_grid *g, double *u, double *ualt, const double *rhs,
 /* nsweeps sweeps, then r = rhs - L u of the result (fused into the last sweep's launch where possible) */
 int ndsmk_relax_residual(const ndsmk_grid *g, double *u, double *ualt, const double *rhs, double *r, int nsweeps,
                          int variant, int *result_in_alt);
+/* The zero first guess of a coarse level, kept out of memory: either call above on a level whose u
+ * IS ZERO BUT WAS NEVER WRITTEN - u may hold anything.  Where the planner lets the first launch take its source from
+ * a buffer descriptor of zero records (an out-of-place fused pass) u is never read; otherwise u is zero-filled first.
+ * r == NULL: ndsmk_relax, else ndsmk_relax_residual.  Same bits as those calls on an array of zeros.
+ * ndsmk_relax_zero_src_ok: 1 if that call would not have to write the zeros (has_rhs / with_res: rhs / r != NULL);
+ * 0 always while the feature is off - NDSM_HIP_NO_ZERO_GUESS=1 in the environment, or ndsmk_debug_zero_guess(0)
+ * (tests: A/B in one process; 1 = back to the default).  ndsmk_zero_guess_on: 1 / 0. */
+int ndsmk_relax_zero_src(const ndsmk_grid *g, double *u, double *ualt, const double *rhs, double *r, int nsweeps,
+                         int variant, int *result_in_alt);
+int ndsmk_relax_zero_src_ok(const ndsmk_grid *g, int has_rhs, int nsweeps, int variant, int with_res);
+int ndsmk_zero_guess_on(void);
+int ndsmk_debug_zero_guess(int on);
 /* r = rhs - L u, zero on Dirichlet faces (ndsm_optimized.f90:346-447 / ndsm_poisson.f90:280-353) */
 int ndsmk_residual(const ndsmk_grid *g, const double *u, const double *rhs, double *r);
 /* rhs_c = R r_f ; also u_c = 0 if u_c != NULL (ndsm_multigrid_core.f90:551,557-558) */

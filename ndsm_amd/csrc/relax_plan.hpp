@@ -54,6 +54,7 @@ struct Request {
   int64_t coarse_plane = 0;   // points of a plane of uc; < 0: the transfer's windows do not fit g (stand-alone only)
   bool have[3] = {true, false, false};   // buffers that exist; buffer 0 holds u
   int keep = -1;              // index of the buffer that must survive, or -1
+  bool src_zero = false;      // buffer 0 is zero but was never written: the first guess of a coarse level
 };
 
 struct Pass {
@@ -63,6 +64,8 @@ struct Pass {
   int src = 0, dst = 0;               // in-place passes: src == dst
   bool prolong_first = false;         // the stand-alone interpolation runs on src in front of this pass
   bool mean_shift = false;            // the mean of dst is subtracted after it
+  bool src_zero = false;              // fused passes: src is not read, every plane of it comes from a descriptor of
+                                      // zero records (a zero source that was never written)
 };
 
 struct Plan {
@@ -72,6 +75,7 @@ struct Plan {
   bool prolong_only = false;    // no pass at all, but the stand-alone interpolation runs on buffer 0
   int result = 0;               // the buffer that ends up holding the swept field
   bool res_done = false, met_done = false;   // a pass covered them; else the stand-alone kernels follow
+  bool materialise = false;     // the request's zero source has to be written to buffer 0 before anything runs
 };
 
 struct FusedPass {
@@ -179,7 +183,28 @@ inline Plan fail(const char *what) {
   return p;
 }
 
+inline Plan relax_plan_as_stored(const ndsmk_grid &g, const Request &rq, const Knobs &kn);
+
+// A zero source that was never written (Request::src_zero) changes no launch: the plan is the one of the same
+// request on an array of zeros, and its FIRST pass takes the zeros from a descriptor of zero records where it is
+// an out-of-place fused pass of a whole fp64 level in mode plain or + residual - one or two sweeps, even or odd
+// nx.  Everything else reads its source from memory - in-place passes, the block-resident and single-workgroup
+// launches, the stand-alone interpolation, no pass at all - or is out of scope (windows and z-slabs, fp32,
+// all-Neumann levels, whose mean shift follows every sweep): the zeros are written first (Plan::materialise).
 inline Plan relax_plan(const ndsmk_grid &g, const Request &rq, const Knobs &kn) {
+  Plan pl = relax_plan_as_stored(g, rq, kn);
+  if (!rq.src_zero || pl.err) return pl;
+  const bool direct = !pl.pass.empty() && pl.pass[0].kind == FUSED && pl.pass[0].src == 0 && pl.pass[0].dst != 0 &&
+                      (pl.pass[0].mode == PLAIN || pl.pass[0].mode == RES) && !pl.pass[0].prolong_first &&
+                      !rq.window && !rq.fp32 && !rq.corr && !g.all_neumann && whole_level(g);
+  if (direct)
+    pl.pass[0].src_zero = true;
+  else
+    pl.materialise = true;
+  return pl;
+}
+
+inline Plan relax_plan_as_stored(const ndsmk_grid &g, const Request &rq, const Knobs &kn) {
   if (!(g.ndim == 2 || g.ndim == 3) || !(g.n[0] >= 2 && g.n[1] >= 2 && (g.ndim == 2 ? g.n[2] == 1 : g.n[2] >= 2)))
     return fail("relax: 2 or 3 dimensions of >= 2 points each");
   for (int d = 0; d < g.ndim; ++d)

@@ -15,6 +15,8 @@
 #include "common.hpp"
 #include "relax_plan.hpp"
 
+#include <cstdlib>
+
 namespace ndsm {
 void fused_metric_accumulate(bool on);
 const int *fused_cfg();
@@ -301,12 +303,15 @@ static int launch_color(const ndsmk_grid &g, double *u, const double *rhs) {
 // buffer holds the result.  keep: a buffer that must survive (the iterate the V-cycle started from, which the
 // convergence metric is taken against); prev: evaluate that metric in the launch of the last sweep (*met_done).
 // rout: residual on the last sweep (*res_done).  px / uc: u += P uc comes first (coarse_to_fine).
+// src_zero: bufs[0] is zero but was never written (the first guess of a coarse level): the first launch takes the
+// zeros from a descriptor of zero records where the plan says it can, otherwise they are written here first.
 static int relax_impl(const ndsmk_grid *gp, double *const bufs[3], const double *keep, const double *rhs, int nsweeps,
                       int variant, int *where, double *rout, int *res_done, const double *prev, int *met_done,
-                      const ndsmk_xfer *px = nullptr, const double *uc = nullptr) {
+                      const ndsmk_xfer *px = nullptr, const double *uc = nullptr, bool src_zero = false) {
   NDSM_REQUIRE_READY();
   const ndsmk_grid g = *gp;
   ndsm::plan::Request rq;
+  rq.src_zero = src_zero;
   rq.nsweeps = nsweeps;
   rq.variant = variant;
   rq.rhs = rhs != nullptr;
@@ -323,9 +328,10 @@ static int relax_impl(const ndsmk_grid *gp, double *const bufs[3], const double 
   if (res_done) *res_done = pl.res_done;
   if (met_done) *met_done = pl.met_done;
   if (where) *where = pl.result;
-  if (pl.prolong_only) return ndsmk_prolong_add(px, uc, bufs[0]);
   const int64_t npts = (int64_t)g.n[0] * g.n[1] * g.n[2];
   hipStream_t s = ndsm::stream();
+  if (pl.materialise) NDSM_HIP(hipMemsetAsync(bufs[0], 0, sizeof(double) * (size_t)npts, s));
+  if (pl.prolong_only) return ndsmk_prolong_add(px, uc, bufs[0]);
   for (const ndsm::plan::Pass &p : pl.pass) {
     double *u = bufs[p.src], *uout = bufs[p.dst];
     int rc = p.prolong_first ? ndsmk_prolong_add(px, uc, u) : 0;
@@ -383,6 +389,49 @@ extern "C" int ndsmk_relax_residual(const ndsmk_grid *gp, double *u, double *ual
     rc = ndsmk_residual(gp, *result_in_alt ? ualt : u, rhs, r);
   }
   return rc;
+}
+
+// The zero first guess of a coarse level (ndsm_kernels.h): on by default
+static bool zero_guess_env() {
+  static const bool on = std::getenv("NDSM_HIP_NO_ZERO_GUESS") == nullptr;
+  return on;
+}
+static int g_zero_guess_off = 0;   // ndsmk_debug_zero_guess(0) switches it off at run time (tests: A/B in one process)
+
+extern "C" int ndsmk_zero_guess_on(void) { return zero_guess_env() && !g_zero_guess_off ? 1 : 0; }
+
+extern "C" int ndsmk_debug_zero_guess(int on) {
+  g_zero_guess_off = on ? 0 : 1;
+  return 0;
+}
+
+extern "C" int ndsmk_relax_zero_src(const ndsmk_grid *gp, double *u, double *ualt, const double *rhs, double *r,
+                                    int nsweeps, int variant, int *result_in_alt) {
+  NDSM_CHECK_ARG(result_in_alt != nullptr && (!r || variant == 0 || variant == 2));
+  int res_done = 0;
+  double *const bufs[3] = {u, ualt, nullptr};
+  int rc = relax_impl(gp, bufs, nullptr, rhs, nsweeps, variant, result_in_alt, r, &res_done, nullptr, nullptr, nullptr,
+                      nullptr, true);
+  if (rc || !r) return rc;
+  if (!res_done) {
+    if (variant == 2)
+      return ndsm::fail(NDSMK_EARG, "fused sweep + residual does not cover this level", __FILE__, __LINE__);
+    rc = ndsmk_residual(gp, *result_in_alt ? ualt : u, rhs, r);
+  }
+  return rc;
+}
+
+extern "C" int ndsmk_relax_zero_src_ok(const ndsmk_grid *gp, int has_rhs, int nsweeps, int variant, int with_res) {
+  if (!ndsmk_zero_guess_on()) return 0;
+  ndsm::plan::Request rq;
+  rq.src_zero = true;
+  rq.nsweeps = nsweeps;
+  rq.variant = variant;
+  rq.rhs = has_rhs != 0;
+  rq.want_res = with_res != 0;
+  rq.have[1] = true;
+  const ndsm::plan::Plan pl = ndsm::plan::relax_plan(*gp, rq, ndsm::relax_knobs());
+  return !pl.err && !pl.materialise && !pl.pass.empty() && pl.pass[0].src_zero ? 1 : 0;
 }
 
 // The V-cycle driver's level-1 form of the two calls above: three buffers (u on entry, two
@@ -495,7 +544,10 @@ extern "C" int ndsmk_debug_relax_plan(int what, const int32_t *grid, const int64
     out[1] = ch.zc;
     return 0;
   }
-  NDSM_CHECK_ARG(what == 0 && grid && req && knobs && out && cap >= 6 && req[0] < (1 << 16));
+  // what = 2: what = 0 with the zero-source field - req[12], a seventh head value and a tenth value per pass
+  const bool zs = what == 2;
+  const int nh = zs ? 7 : 6, nr = zs ? 10 : 9;
+  NDSM_CHECK_ARG((what == 0 || zs) && grid && req && knobs && out && cap >= nh && req[0] < (1 << 16));
   ndsmk_grid g = {};
   g.ndim = grid[0];
   for (int d = 0; d < 3; ++d) g.n[d] = grid[1 + d], g.lb[d] = grid[4 + d], g.ub[d] = grid[7 + d];
@@ -504,16 +556,18 @@ extern "C" int ndsmk_debug_relax_plan(int what, const int32_t *grid, const int64
   rq.nsweeps = (int)req[0], rq.variant = (int)req[1], rq.window = req[2] != 0, rq.fp32 = req[3] != 0;
   rq.rhs = req[4] != 0, rq.want_res = req[5] != 0, rq.want_met = req[6] != 0, rq.corr = req[7] != 0;
   rq.coarse_plane = req[8], rq.have[1] = req[9] != 0, rq.have[2] = req[10] != 0, rq.keep = (int)req[11];
+  if (zs) rq.src_zero = req[12] != 0;
   pn::Knobs kn;
   for (int i = 0; i < 5; ++i) kn.fused[i] = (int)knobs[i];
   kn.block[0] = knobs[5], kn.block[1] = knobs[6], kn.block_on = knobs[7] == 0;
   const pn::Plan pl = pn::relax_plan(g, rq, kn);
-  const int32_t head[6] = {pl.err, (int32_t)pl.pass.size(), pl.result, pl.res_done, pl.met_done, pl.prolong_only};
-  for (int i = 0; i < 6; ++i) out[i] = head[i];
-  NDSM_CHECK_ARG((size_t)cap >= 6 + 9 * pl.pass.size());
+  const int32_t head[7] = {pl.err,      (int32_t)pl.pass.size(), pl.result,     pl.res_done,
+                           pl.met_done, pl.prolong_only,         pl.materialise};
+  for (int i = 0; i < nh; ++i) out[i] = head[i];
+  NDSM_CHECK_ARG((size_t)cap >= nh + nr * pl.pass.size());
   for (const pn::Pass &p : pl.pass) {
-    const int32_t row[9] = {p.kind, p.sweeps, p.mode, p.inst, p.bz, p.src, p.dst, p.prolong_first, p.mean_shift};
-    for (int i = 0; i < 9; ++i) out[6 + 9 * (&p - pl.pass.data()) + i] = row[i];
+    const int32_t row[10] = {p.kind, p.sweeps, p.mode, p.inst, p.bz, p.src, p.dst, p.prolong_first, p.mean_shift, p.src_zero};
+    for (int i = 0; i < nr; ++i) out[nh + nr * (&p - pl.pass.data()) + i] = row[i];
   }
   return 0;
 }

@@ -82,6 +82,7 @@ struct FusedPlan {
   int ntx, nty, nzc;  // tiles in x, y and chunks in z
   int zc;             // planes per chunk
   int nwork;          // ntx * nty * nzc
+  int src_zero;       // u is zero and was never written: every plane of it comes from a descriptor of zero records
 };
 
 // an x-pair of the working precision T (double: the reference's arithmetic; float: the
@@ -278,8 +279,12 @@ __global__ __launch_bounds__(NT, WPS) void rbgs3_fused_k(const T *__restrict__ u
   const bool openxh = x0 + TXH < nx, openyh = y0 + TYH < ny;
   // descriptor of plane k of a field; ok == false: zero records (every load returns 0, every store is dropped)
   const unsigned plane_bytes = (unsigned)(sz * (size_t)SZ);
-  auto rsrc_of = [&](const T *base, int k_, bool ok) {
-    return plane_rsrc(base + sz * (size_t)(ok ? k_ : 0), ok ? plane_bytes : 0u);
+  // (a zero source that was never written - the first guess of a coarse level, relax_plan.hpp: the planes of u have
+  // zero records wherever they are, so u is never read and every load of it returns +0.0, what the array would hold)
+  // (fp64, modes plain and + residual only - what the planner asks for: the other kernels stay as they were built)
+  const unsigned u_bytes = (SZ == 8 && !MET && !PROL && pl.src_zero) ? 0u : plane_bytes;
+  auto rsrc_of = [&](const T *base, int k_, bool ok, unsigned bytes) {
+    return plane_rsrc(base + sz * (size_t)(ok ? k_ : 0), ok ? bytes : 0u);
   };
   // A pair through descriptor r, ONE 16-byte (8-byte) access per lane.  Odd nx: rows are only sizeof(T)-aligned,
   // so half of these accesses straddle a 16-byte boundary - still cheaper than two element-sized ones - and the
@@ -300,9 +305,9 @@ __global__ __launch_bounds__(NT, WPS) void rbgs3_fused_k(const T *__restrict__ u
     if constexpr (ODD) stbuf1<T, STAUX>(r, og, v.x);
   };
 
-#define NDSM_LOAD_PLANE(base, k, dst)                                                                  \
+#define NDSM_LOAD_PLANE(base, bytes, k, dst)                                                           \
   do {                                                                                                  \
-    const auto r_ = rsrc_of(base, k, (k) >= kl && (k) <= ke);                                           \
+    const auto r_ = rsrc_of(base, k, (k) >= kl && (k) <= ke, bytes);                                    \
     _Pragma("unroll") for (int s_ = 0; s_ < NS; ++s_) dst[s_] = ldp(r_, scs[s_].ldo, ODD && (scs[s_].fl & 16)); \
   } while (0)
 
@@ -595,14 +600,14 @@ __global__ __launch_bounds__(NT, WPS) void rbgs3_fused_k(const T *__restrict__ u
   // ---- prologue: plane ks into its LDS buffer, plane ks+1 into registers ----
   {
     d2 c0[NS];
-    NDSM_LOAD_PLANE(u, ks, c0);
+    NDSM_LOAD_PLANE(u, u_bytes, ks, c0);
     if (!RHS0) {
       d2 r0[NS];
-      NDSM_LOAD_PLANE(rhs, ks, r0);
+      NDSM_LOAD_PLANE(rhs, plane_bytes, ks, r0);
 #pragma unroll
       for (int s = 0; s < (RHS0 ? 1 : NS); ++s) rw[s][0] = by_class(r0[s], s);
     }
-    NDSM_LOAD_PLANE(u, ks + 1, nxt);
+    NDSM_LOAD_PLANE(u, u_bytes, ks + 1, nxt);
     if (PROL) {  // the two planes loaded here get their correction here
       kcur = pa.plo[2][min(max(ks + pa.fk0, 0), pa.nzf - 1)];
       prol_ztab(ks);
@@ -677,7 +682,7 @@ __global__ __launch_bounds__(NT, WPS) void rbgs3_fused_k(const T *__restrict__ u
       for (int s = 0; s < (RHS0 ? 1 : NS); ++s) rn[s] = ldp(rr_, scs[s].ldo, ODD && (scs[s].fl & 16));
     }
     {
-      const auto ru = rsrc_at(a_ld, k + 2 >= kl && k + 2 <= ke);
+      const auto ru = plane_rsrc(a_ld, (k + 2 >= kl && k + 2 <= ke) ? u_bytes : 0u);
 #pragma unroll
       for (int s = 0; s < NS; ++s) nn[s] = ldp(ru, scs[s].ldo, ODD && (scs[s].fl & 16));
     }
@@ -982,7 +987,7 @@ int met_scratch(size_t nblk, double **part, double **out2) {
 
 template <typename T, int S, int TXH, int TYH, int NT, int WPS, int MODE = 0, bool LVL1 = false, bool ODD = false>
 int launch_cfg(const ndsmk_grid &g, const T *u, T *uout, const T *rhs, int target_wgs, T *rout = nullptr,
-               const T *prev = nullptr, const ProlArgs *prol = nullptr) {
+               const T *prev = nullptr, const ProlArgs *prol = nullptr, bool src_zero = false) {
   constexpr bool RES = MODE == 1;
   constexpr int NST = RES ? 2 * S + 1 : 2 * S;
   constexpr int TXI = TXH - 2 * ((NST + 1) & ~1), TYI = TYH - 2 * NST;
@@ -1024,6 +1029,7 @@ int launch_cfg(const ndsmk_grid &g, const T *u, T *uout, const T *rhs, int targe
   pl.zc = ch.zc;
   pl.nzc = ch.nzc;
   pl.nwork = tiles * pl.nzc;
+  pl.src_zero = src_zero ? 1 : 0;
   const int nblk = ((pl.nwork + 7) / 8) * 8;
   ProlArgs pa = {};
   if (prol) pa = *prol;
@@ -1069,11 +1075,11 @@ const int *fused_cfg() {
 // The launch of one fused pass of a relax plan (relax_plan.hpp decides which): instantiation enumerator -> launch_cfg.
 template <typename T>
 static int launch_fused_t(int inst, const ndsmk_grid &g, const T *u, T *uout, const T *rhs, T *rout, const T *prev,
-                          const ProlArgs *prol) {
+                          const ProlArgs *prol, bool src_zero = false) {
   using namespace plan;
   const int tgt = fused_cfg()[3] > 0 ? fused_cfg()[3] : 0;  // > 0: that many work items instead of launch_cfg's own choice
 #define NDSM_FUSED_CASE(id, ...) \
-  case id: return (launch_cfg<T, __VA_ARGS__>(g, u, uout, rhs, tgt, rout, prev, prol))
+  case id: return (launch_cfg<T, __VA_ARGS__>(g, u, uout, rhs, tgt, rout, prev, prol, src_zero))
 #define NDSM_FUSED_BOTH(id, ...)               \
   NDSM_FUSED_CASE(id, __VA_ARGS__, false, false); \
   NDSM_FUSED_CASE(id + kOddNx, __VA_ARGS__, false, true)
@@ -1137,8 +1143,10 @@ int launch_rbgs3_fused(const plan::Pass &p, const ndsmk_grid &g, const double *u
   ProlArgs pa;
   if (p.mode == plan::CORR && !(px && prol_args(g, px, uc, &pa)))
     return fail(NDSMK_EARG, "fused smoother: the transfer does not describe this level", __FILE__, __LINE__);
+  if (p.src_zero && !(p.mode == plan::PLAIN || p.mode == plan::RES))
+    return fail(NDSMK_EARG, "fused smoother: a zero source goes with the plain and the residual mode only", __FILE__, __LINE__);
   return launch_fused_t<double>(p.inst, g, u, uout, rhs, p.mode == plan::RES ? rout : nullptr,
-                                p.mode == plan::MET ? prev : nullptr, p.mode == plan::CORR ? &pa : nullptr);
+                                p.mode == plan::MET ? prev : nullptr, p.mode == plan::CORR ? &pa : nullptr, p.src_zero);
 }
 
 // (max, sum) of |u_new - u_prev| left on the device by the last MET launch -> host (blocking)

@@ -504,6 +504,9 @@ contains
     type(c_ptr) :: d
     integer(ik) :: n
     call c_f_pointer(handle, s)
+    if (which == MG_BUF_U) then      ! (a zero guess that was declared only is written out before it is replaced)
+      rc = mg_ensure_u(s, int(level)); if (rc /= 0) return
+    end if
     d = mg_level_ptr(s, int(level), int(which), n)
     rc = NDSMK_EARG
     if (.not. c_associated(d)) return
@@ -529,6 +532,9 @@ contains
     type(c_ptr) :: d
     integer(ik) :: n
     call c_f_pointer(handle, s)
+    if (which == MG_BUF_U) then      ! (a zero guess that was declared only reads as zeros)
+      rc = mg_ensure_u(s, int(level)); if (rc /= 0) return
+    end if
     d = mg_level_ptr(s, int(level), int(which), n)
     rc = NDSMK_EARG
     if (.not. c_associated(d)) return
@@ -1878,6 +1884,21 @@ contains
     integer(c_int), value :: on
     integer(c_int) :: rc
     rc = ndsmk_debug_tail(on)
+  end function
+
+  function ndsm_hip_debug_zero_guess(on) bind(c, name="ndsm_hip_debug_zero_guess") result(rc)
+    integer(c_int), value :: on
+    integer(c_int) :: rc
+    rc = ndsmk_debug_zero_guess(on)
+  end function
+
+  function ndsm_hip_debug_u_declared_zero(handle, level) bind(c, name="ndsm_hip_debug_u_declared_zero") result(yes)
+    type(c_ptr), value :: handle
+    integer(c_int), value :: level
+    integer(c_int) :: yes
+    type(mg_solver), pointer :: s
+    call c_f_pointer(handle, s)
+    yes = merge(1_c_int, 0_c_int, mg_u_declared_zero(s, int(level)))
   end function
 
   function ndsm_hip_world_vcycle(handle, ncycles) bind(c, name="ndsm_hip_world_vcycle") result(rc)

@@ -159,6 +159,37 @@ module ndsmh_iface
       integer(c_int) :: rc
     end function
 
+    ! the same two calls on a level whose u is zero and was never written: r = c_null_ptr: no residual
+    function ndsmk_relax_zero_src(g, u, ualt, rhs, r, nsweeps, variant, result_in_alt) &
+        bind(c, name="ndsmk_relax_zero_src") result(rc)
+      import :: ndsmk_grid, c_ptr, c_int
+      type(ndsmk_grid), intent(in) :: g
+      type(c_ptr), value :: u, ualt, rhs, r
+      integer(c_int), value :: nsweeps, variant
+      integer(c_int), intent(out) :: result_in_alt
+      integer(c_int) :: rc
+    end function
+
+    ! 1: that call would take the zeros from a descriptor of zero records, 0: it would write them first
+    function ndsmk_relax_zero_src_ok(g, has_rhs, nsweeps, variant, with_res) &
+        bind(c, name="ndsmk_relax_zero_src_ok") result(ok)
+      import :: ndsmk_grid, c_int
+      type(ndsmk_grid), intent(in) :: g
+      integer(c_int), value :: has_rhs, nsweeps, variant, with_res
+      integer(c_int) :: ok
+    end function
+
+    function ndsmk_zero_guess_on() bind(c, name="ndsmk_zero_guess_on") result(on)
+      import :: c_int
+      integer(c_int) :: on
+    end function
+
+    function ndsmk_debug_zero_guess(on) bind(c, name="ndsmk_debug_zero_guess") result(rc)
+      import :: c_int
+      integer(c_int), value :: on
+      integer(c_int) :: rc
+    end function
+
     ! px: c_loc of an ndsmk_xfer (u += P uc before the sweeps) or c_null_ptr
     function ndsmk_relax3(g, u, a, b, keep, rhs, nsweeps, r, prev, where, met_done, px, uc) &
         bind(c, name="ndsmk_relax3") result(rc)

@@ -32,7 +32,7 @@ module ndsmh_mg
   public :: mg_set_bcs, mg_export_u, mg_reset_info, mg_vcycle_from, mg_slab_restrict, mg_slab_prolong
   public :: mg_slab_restrict_f32, mg_slab_prolong_f32, mg_mixed_slab_ok, rhs_of
   public :: MG_BUF_U, MG_BUF_RHS, MG_BUF_R, MG_BUF_UALT
-  public :: MG_OP_RELAX_LAST
+  public :: MG_OP_RELAX_LAST, MG_OP_ZERO_U, MG_OP_DESCEND, mg_ensure_u, mg_u_declared_zero
   public :: MG_OP_RELAX, MG_OP_RESIDUAL, MG_OP_RESTRICT, MG_OP_PROLONG, MG_OP_EXACT, MG_OP_RELAX_COLOR, &
             MG_OP_RELAX_FUSED, MG_OP_RESREST, MG_OP_RELAX_RES, MG_OP_RELAX_RES_FUSED
 
@@ -40,13 +40,20 @@ module ndsmh_mg
   integer, parameter :: MG_OP_RELAX = 0, MG_OP_RESIDUAL = 1, MG_OP_RESTRICT = 2, MG_OP_PROLONG = 3, &
                         MG_OP_EXACT = 4, MG_OP_RELAX_COLOR = 5, MG_OP_RELAX_FUSED = 6, &
                         MG_OP_RESREST = 7, MG_OP_RELAX_RES = 8, MG_OP_RELAX_RES_FUSED = 9, &
-                        MG_OP_RELAX_LAST = 10   ! the sweeps that end a V-cycle (level 1)
+                        MG_OP_RELAX_LAST = 10, &   ! the sweeps that end a V-cycle (level 1)
+                        MG_OP_ZERO_U = 11, &       ! u(level) = 0 the way the descent leaves it (tests)
+                        MG_OP_DESCEND = 12         ! the restriction level -> level+1 the way the descent does it (tests)
 
   integer(c_size_t), parameter :: R8 = 8_c_size_t, I4 = 4_c_size_t
 
   type :: dev_level
     type(c_ptr) :: u = c_null_ptr, rhs = c_null_ptr
     type(c_ptr) :: ualt = c_null_ptr   ! ping-pong partner of u for the out-of-place fused smoother
+    ! u IS ZERO AND NOT MATERIALISED: the descent restricted into this level without writing the zero first guess
+    ! (restrict_down), so the array holds whatever it held.  The relax call that comes next takes its source from a
+    ! descriptor of zero records and leaves the swept field in the partner array; every other reader of u calls
+    ! mg_ensure_u first, which writes the zeros.  (NDSM_HIP_NO_ZERO_GUESS=1: never set.)
+    logical :: uzero = .false.
   end type
 
   type :: dev_xfer
@@ -530,10 +537,29 @@ contains
     integer(c_int) :: swapped
     integer :: variant
     type(c_ptr) :: tmp
+    logical :: zsrc
     rc = NDSMK_EARG
     if (level < 1 .or. level > s%ngrids) return
     if (level >= 2 .and. .not. s%has_coarse) return
-    if (s%slab .and. level == 1 .and. (op == MG_OP_RESTRICT .or. op == MG_OP_PROLONG)) return  ! mg_slab_* instead
+    if (s%slab .and. level == 1 .and. (op == MG_OP_RESTRICT .or. op == MG_OP_PROLONG .or. op == MG_OP_DESCEND)) return  ! mg_slab_* instead
+    ! a zero first guess that was never written: the relax calls take it as it is, every other reader of u finds
+    ! the zeros in memory
+    zsrc = .false.
+    rc = 0
+    select case (op)
+    case (MG_OP_RELAX, MG_OP_RELAX_COLOR, MG_OP_RELAX_FUSED, MG_OP_RELAX_LAST, MG_OP_RELAX_RES, MG_OP_RELAX_RES_FUSED)
+      zsrc = s%dl(level)%uzero .and. .not. (level == 1 .and. s%track)
+      if (.not. zsrc) rc = mg_ensure_u(s, level)
+    case (MG_OP_PROLONG)
+      rc = mg_ensure_u(s, level)
+      if (rc == 0 .and. level < s%ngrids) rc = mg_ensure_u(s, level + 1)
+    case (MG_OP_RESIDUAL, MG_OP_EXACT)
+      rc = mg_ensure_u(s, level)
+    case default
+      rc = 0
+    end select
+    if (rc /= 0) return
+    rc = NDSMK_EARG
     if (level == 1 .and. s%track .and. (op == MG_OP_RELAX .or. op == MG_OP_RELAX_RES .or. op == MG_OP_RELAX_LAST)) then
       rc = relax_tracked(s, int(count), op == MG_OP_RELAX_RES, op == MG_OP_RELAX_LAST)
       return
@@ -541,16 +567,28 @@ contains
     select case (op)
     case (MG_OP_RELAX, MG_OP_RELAX_COLOR, MG_OP_RELAX_FUSED, MG_OP_RELAX_LAST)
       variant = merge(0, merge(1, 2, op == MG_OP_RELAX_COLOR), op == MG_OP_RELAX .or. op == MG_OP_RELAX_LAST)
-      rc = ndsmk_relax(s%lev(level)%g, s%dl(level)%u, s%dl(level)%ualt, rhs_of(s, level), int(count, c_int), &
-                       int(variant, c_int), swapped)
+      if (zsrc) then
+        rc = ndsmk_relax_zero_src(s%lev(level)%g, s%dl(level)%u, s%dl(level)%ualt, rhs_of(s, level), c_null_ptr, &
+                                  int(count, c_int), int(variant, c_int), swapped)
+        if (rc == 0) s%dl(level)%uzero = .false.
+      else
+        rc = ndsmk_relax(s%lev(level)%g, s%dl(level)%u, s%dl(level)%ualt, rhs_of(s, level), int(count, c_int), &
+                         int(variant, c_int), swapped)
+      end if
       if (rc == 0 .and. swapped /= 0) then      ! the swept field lives in the partner array now
         tmp = s%dl(level)%u
         s%dl(level)%u = s%dl(level)%ualt
         s%dl(level)%ualt = tmp
       end if
     case (MG_OP_RELAX_RES, MG_OP_RELAX_RES_FUSED)  ! count sweeps, then residual -> scratch (last sweep + residual in one launch)
-      rc = ndsmk_relax_residual(s%lev(level)%g, s%dl(level)%u, s%dl(level)%ualt, rhs_of(s, level), s%r, &
-                                int(count, c_int), merge(0_c_int, 2_c_int, op == MG_OP_RELAX_RES), swapped)
+      if (zsrc) then
+        rc = ndsmk_relax_zero_src(s%lev(level)%g, s%dl(level)%u, s%dl(level)%ualt, rhs_of(s, level), s%r, &
+                                  int(count, c_int), merge(0_c_int, 2_c_int, op == MG_OP_RELAX_RES), swapped)
+        if (rc == 0) s%dl(level)%uzero = .false.
+      else
+        rc = ndsmk_relax_residual(s%lev(level)%g, s%dl(level)%u, s%dl(level)%ualt, rhs_of(s, level), s%r, &
+                                  int(count, c_int), merge(0_c_int, 2_c_int, op == MG_OP_RELAX_RES), swapped)
+      end if
       if (rc == 0 .and. swapped /= 0) then
         tmp = s%dl(level)%u
         s%dl(level)%u = s%dl(level)%ualt
@@ -561,6 +599,18 @@ contains
     case (MG_OP_RESTRICT)       ! r(level) -> rhs(level+1), u(level+1) = 0
       if (level >= s%ngrids) return
       rc = ndsmk_restrict(s%xf(level)%x, s%r, s%dl(level + 1)%rhs, s%dl(level + 1)%u)
+      if (rc == 0) s%dl(level + 1)%uzero = .false.
+    case (MG_OP_DESCEND)        ! the same as the descent of a V-cycle from level 1 does it: the zeros may stay unwritten
+      if (level >= s%ngrids) return
+      rc = restrict_down(s, level, level + 1 < min(tail_first(s, 1), s%ngrids))
+    case (MG_OP_ZERO_U)         ! u(level) = 0, in memory or - where the feature is on - by declaration only
+      if (ndsmk_zero_guess_on() /= 0) then
+        s%dl(level)%uzero = .true.
+        rc = 0
+      else
+        rc = ndsmk_fill0(s%dl(level)%u, int(merge(s%npts1, s%lev(level)%npts, level == 1), c_size_t) * R8)
+        if (rc == 0) s%dl(level)%uzero = .false.
+      end if
     case (MG_OP_RESREST)        ! (retired: the fused residual + restriction kernel was slower than sweep + residual
       return                    !  in one launch followed by the streamed restriction; the slot keeps its number)
     case (MG_OP_PROLONG)        ! u(level) += P u(level+1)
@@ -570,6 +620,50 @@ contains
       rc = ndsmk_solve_exact(s%lev(level)%g, s%dl(level)%u, s%dl(level)%rhs, s%scr, s%ex_tol, &
                              merge(1_c_int, 0_c_int, s%use_max), int(s%nmax_exact, c_int), s%info)
     end select
+  end function
+
+  ! writes the zeros of a first guess that was declared only (dev_level%uzero); nothing to do otherwise
+  function mg_ensure_u(s, level) result(rc)
+    type(mg_solver), intent(inout) :: s
+    integer, intent(in) :: level
+    integer(c_int) :: rc
+    rc = 0
+    if (level < 1 .or. level > s%ngrids .or. .not. allocated(s%dl)) return
+    if (.not. s%dl(level)%uzero) return
+    rc = ndsmk_fill0(s%dl(level)%u, int(merge(s%npts1, s%lev(level)%npts, level == 1), c_size_t) * R8)
+    if (rc == 0) s%dl(level)%uzero = .false.
+  end function
+
+  ! tests: is u(level) a zero guess that was declared and not written?
+  function mg_u_declared_zero(s, level) result(yes)
+    type(mg_solver), intent(in) :: s
+    integer, intent(in) :: level
+    logical :: yes
+    yes = .false.
+    if (level >= 1 .and. level <= s%ngrids .and. allocated(s%dl)) yes = s%dl(level)%uzero
+  end function
+
+  ! The restriction of the descent: r(l) -> rhs(l+1), u(l+1) = 0 (fine_to_coarse, :551-558).  relax_next: the
+  ! pre-smoothing of level l+1 (ms sweeps + residual) is what reads u(l+1) next.  Where that call can take a zero
+  ! source from a descriptor of zero records (ndsmk_relax_zero_src_ok: an out-of-place fused pass comes first, and
+  ! the feature is on) the zeros are declared, not written: 8 bytes per coarse point less to store here and to load
+  ! there, the same bits.
+  function restrict_down(s, l, relax_next) result(rc)
+    type(mg_solver), intent(inout) :: s
+    integer, intent(in) :: l
+    logical, intent(in) :: relax_next
+    integer(c_int) :: rc
+    logical :: zg
+    rc = NDSMK_EARG
+    if (l < 1 .or. l >= s%ngrids .or. (s%slab .and. l == 1)) return   ! (a slab's level 1: mg_slab_restrict instead)
+    zg = .false.
+    if (relax_next) zg = ndsmk_relax_zero_src_ok(s%lev(l + 1)%g, 1_c_int, int(s%ms, c_int), 0_c_int, 1_c_int) /= 0
+    if (zg) then
+      rc = ndsmk_restrict(s%xf(l)%x, s%r, s%dl(l + 1)%rhs, c_null_ptr)
+    else
+      rc = ndsmk_restrict(s%xf(l)%x, s%r, s%dl(l + 1)%rhs, s%dl(l + 1)%u)
+    end if
+    if (rc == 0) s%dl(l + 1)%uzero = zg
   end function
 
   ! level-1 sweeps in track mode: three rotating buffers, s%keep is never written
@@ -586,8 +680,10 @@ contains
     rr = c_null_ptr; if (with_res) rr = s%r
     pv = c_null_ptr; if (last) pv = s%keep
     px = c_null_ptr; uc = c_null_ptr
+    rc = mg_ensure_u(s, 1); if (rc /= 0) return
     if (present(prolong)) then
       if (prolong) then
+        rc = mg_ensure_u(s, 2); if (rc /= 0) return
         px = c_loc(s%xf(1)%x); uc = s%dl(2)%u
       end if
     end if
@@ -617,6 +713,22 @@ contains
     type(mg_solver), intent(inout) :: s
     integer, intent(in) :: ltop
     integer(c_int) :: rc
+    integer(c_int) :: rc2
+    integer :: l
+    rc = vcycle_levels(s, ltop)
+    ! every zero guess the descent declared has been consumed by the level's pre-smoothing; after an error one may
+    ! be left: no array leaves this function with zeros that are not in memory
+    if (rc /= 0) then
+      do l = 1, s%ngrids
+        rc2 = mg_ensure_u(s, l)
+      end do
+    end if
+  end function
+
+  function vcycle_levels(s, ltop) result(rc)
+    type(mg_solver), intent(inout) :: s
+    integer, intent(in) :: ltop
+    integer(c_int) :: rc
     integer :: l, lt
 
     ! levels lt .. ngrids run as ONE launch with all of them in LDS (tail.hip); lt = ngrids + 1: none do
@@ -625,7 +737,7 @@ contains
     ! descend: pre-smooth, residual, restrict (fine_to_coarse, :482-560)
     do l = ltop, min(lt, s%ngrids) - 1
       rc = mg_op(s, MG_OP_RELAX_RES, l, s%ms); if (rc /= 0) return
-      rc = mg_op(s, MG_OP_RESTRICT, l, 1); if (rc /= 0) return
+      rc = restrict_down(s, l, l + 1 < min(lt, s%ngrids)); if (rc /= 0) return
     end do
 
     ! coarsest grid: iterate the smoother to ex_tol (solve_exact, :728-800)
@@ -695,6 +807,7 @@ contains
     type(ndsmk_xfer) :: xx(5)
     type(c_ptr) :: uu(6), rr(6)
     nlev = s%ngrids - lt + 1
+    rc = mg_ensure_u(s, lt); if (rc /= 0) return   ! (the launch loads its top level's iterate)
     do q = 1, nlev
       gg(q) = s%lev(lt + q - 1)%g
       if (q < nlev) xx(q) = s%xf(lt + q - 1)%x

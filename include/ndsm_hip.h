@@ -411,6 +411,50 @@ int ndsm_hip_vecpot_nlfff_device(void *h, int ioptc[16], double ropt[16], double
                                  int polarity, int start, int niter_max, double tol, double step, int max_steps,
                                  double *dA, double *dalpha, int32_t *dstatus, double *hist, int *niter_out);
 
+/* ---- Optimization-method force-free field (DESIGN.md "Optimization-method force-free field") ------------------------
+ * The other standard extrapolation (Wheatland, Sturrock & Roumeliotis 2000; Wiegelmann 2004), for the data a vector
+ * magnetogram gives: all three components of B on the lower face.  The field is relaxed by pseudo-time steps that
+ * lower  L = L_f + L_d,  L_f = sum W w |J x B|^2 / |B|^2,  L_d = sum W w (div_h B)^2,  with the six faces held fixed.
+ * Everything is node-based on the handle's uniform mesh; differences are derivq's (centred inside, 3-point one-sided on
+ * the end planes), J = curl_h B in ndsm_hip_vecpot_solve_field's expressions, W the trapezoid weight of
+ * ndsm_hip_vecpot_helicity, w the caller's weight function.
+ *   B         (nx,ny,nz,3) in and out.  start 1: in B^0.  start 0: in the magnetogram on the k = 0 plane (all three
+ *             components) and B.n on the other five faces; B^0 is the potential field of the input's B.n (the bits
+ *             ndsm_hip_vecpot_solve_device gives from a zero guess) with its whole k = 0 plane overwritten by the
+ *             input's; the side and top faces keep the potential field's values.  out: the relaxed field; its face
+ *             nodes are bit for bit those of B^0.
+ *   w         (nx,ny,nz) in, or NULL for 1 everywhere (ndsm_amd.boundary_weight builds the usual cosine profile)
+ *   At every node, faces included: D = div_h B, bb = (bx^2 + by^2) + bz^2, Omega = ((J x B) - D B) / bb (0 where bb
+ *   is not > 0; such nodes add nothing to L), P = Omega x B, s = Omega.B.  On the interior nodes
+ *     F  = curl_h P - Omega x J - grad_h s + Omega D + |Omega|^2 B
+ *     F~ = w F - P x grad_h w - s grad_h w
+ *   and dB/dt = F~ gives dL/dt = -2 sum |F~|^2 dV <= 0 in the continuum.
+ *   One try: T = B + dt F~ inside, T = B on the faces; L of T; L_T < L (strictly; a NaN fails) accepts - T becomes the
+ *   field, dt *= 1.01 - and anything else rejects: dt *= 0.5.  The decision is taken on the device, so nothing is read
+ *   back between two checks.
+ *   niter_max >= 1 tries at most.  dt0 > 0 the first step (a good value: 0.1 min(h)^2).  The loop stops before a try
+ *   when dt < dt_min, and at a check - after every `check` tries - when L_prev - L <= tol L_prev, L_prev the L of the
+ *   previous check (of the start at the first).
+ *   hist      (hist_rows >= 2 rows of 6 doubles, on the HOST in both entries): [tries, L, L_f, L_d, dt, accepted].
+ *             Row 0 is the start field, then one row per check, the final state always last; when the rows run out
+ *             the last row is overwritten.  Deterministic sums: the same input gives the same bits.
+ *   info      (3 ints, on the HOST in both entries): rows written, tries, stop reason (0 niter_max, 1 tol, 2 dt_min)
+ *   Returns 0; 1 when a solve of start 0 missed vc_tol (options in the usual slots); >= 9001 errors: 9001 without a
+ *   GPU whatever the arguments, 9002 a NULL handle, B, hist or info, 9004 start not 0 / 1, niter_max < 1, check < 1,
+ *   hist_rows < 2, tol < 0 or not finite, dt0 <= 0 or not finite, dt_min < 0 or not finite.  A failed call clears
+ *   hist and info.
+ *   Device memory: a second field, two Omega fields and 32 KiB of state next to the caller's B (the host entry stages
+ *   B and w as well), for the length of the call; start 0 also needs the hierarchy.  A grid that cannot fit is
+ *   refused (9001) before any allocation.  Not included: a final divergence cleaning (ndsm_hip_vecpot_project). */
+/* HOST arrays */
+int ndsm_hip_vecpot_optimize(void *h, int ioptc[16], double ropt[16], double *B, const double *w, int start,
+                             int niter_max, int check, double tol, double dt0, double dt_min, double *hist,
+                             int hist_rows, int *info);
+/* the same on DEVICE arrays of the library's GPU (hist and info stay on the host) */
+int ndsm_hip_vecpot_optimize_device(void *h, int ioptc[16], double ropt[16], double *dB, const double *dw, int start,
+                                    int niter_max, int check, double tol, double dt0, double dt_min, double *hist,
+                                    int hist_rows, int *info);
+
 /* ---- Field-line paths: the points of the same lines (DESIGN.md "Field-line paths") ---------------------------------
  * Where a line runs, not only where it ends: every `every`-th point of each traced line, with B, G and the running
  * integral at it - for drawing lines over a Q map, sampling a field along a loop, or following lines started near a

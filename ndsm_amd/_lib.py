@@ -106,6 +106,10 @@ def load_library(path=None):
            [ctypes.c_int] + [ctypes.c_void_p] * 3 + [_dp, _ip])
     L.ndsm_hip_vecpot_nlfff.argtypes = _nl
     L.ndsm_hip_vecpot_nlfff_device.argtypes = _nl
+    _op = ([ctypes.c_void_p, _ip, _dp] + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 3 + [ctypes.c_double] * 3 +
+           [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p])
+    L.ndsm_hip_vecpot_optimize.argtypes = _op
+    L.ndsm_hip_vecpot_optimize_device.argtypes = _op
     _pa = ([ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64] +
            [ctypes.c_void_p] * 11)
     L.ndsm_hip_vecpot_paths.argtypes = [ctypes.c_void_p] * 3 + _pa
@@ -628,6 +632,68 @@ class VecPot:
         self.last_ioptc, self.last_ropt = ioptc, ropt
         return (ierr, A.reshape(shape), B.reshape(shape), alpha.reshape(shape[1:]), status.reshape(shape[1:]),
                 hist[:niter.value].copy())
+
+    def optimize(self, b, w=None, start="potential", niter_max=10000, check=50, tol=1e-4, dt0=None, dt_min=None,
+                 hist_rows=None, niterex_max=10000, ncycles_max=1024, ex_tol=1e-13, vc_tol=1e-10, ms=5, mean=False,
+                 mixed_precision=False, flxcrl=False, device=False):
+        """Nonlinear force-free field from a vector magnetogram by the optimization method (Wheatland et al. 2000,
+        Wiegelmann 2004) on the device (semantics: include/ndsm_hip.h, ndsm_hip_vecpot_optimize): b (3,nz,ny,nx) is
+        relaxed by pseudo-time steps that lower L = sum W w (|J x B|^2 / |B|^2 + (div B)^2), its six faces held fixed.
+        start: "potential" (the first field is solve()'s potential field of the B.n of b with the k = 0 plane of b -
+        the magnetogram, all three components - put back) or "given" (it is b itself).  w (nz,ny,nx): the weight
+        function, None for 1 everywhere (boundary_weight() builds the usual one).  At most niter_max tries; every
+        `check` tries the loop looks at L and stops when it fell by no more than tol * L since the last look, or
+        when dt < dt_min.  dt0: the first step (None: 0.1 min(h)^2); dt_min None: 1e-6 dt0.  hist_rows None: one row
+        per check and two more.  Returns (ierr, B, hist, info): hist (rows, 6) = [tries, L, L_f, L_d, dt, accepted]
+        - row 0 the start field, the final state last -, info = (rows, tries, stop reason: 0 niter_max, 1 tol,
+        2 dt_min); ierr 1 when a solve of the potential start missed vc_tol.  The field is not cleaned of its
+        remaining divergence: project() does that.  device=True: the arrays are staged in device memory and the
+        device-resident entry point runs."""
+        if start not in ("potential", "given"):
+            raise ValueError(f"start must be 'potential' or 'given', not {start!r}")
+        for name, v in (("niter_max", niter_max), ("check", check)):
+            if int(v) != v or v < 1:
+                raise ValueError(f"{name} must be a whole number >= 1, not {v!r}")
+        if not (tol >= 0.0 and np.isfinite(tol)):
+            raise ValueError(f"tol must be finite and >= 0, not {tol!r}")
+        if dt0 is not None and not (dt0 > 0.0 and np.isfinite(dt0)):
+            raise ValueError(f"dt0 must be finite and > 0, not {dt0!r}")
+        if dt_min is not None and not (dt_min >= 0.0 and np.isfinite(dt_min)):
+            raise ValueError(f"dt_min must be finite and >= 0, not {dt_min!r}")
+        if hist_rows is None:
+            hist_rows = -(-int(niter_max) // int(check)) + 2
+        if int(hist_rows) != hist_rows or hist_rows < 2:
+            raise ValueError(f"hist_rows must be a whole number >= 2, not {hist_rows!r}")
+        shape = tuple(int(v) for v in self.nshape4[::-1])
+        B = self._field_arg(b, "optimize")
+        W = None
+        if w is not None:
+            W = np.asarray(w)
+            if W.shape != shape[1:]:
+                raise NdsmHipError(f"optimize: weight of shape {W.shape}, the handle's grid needs {shape[1:]} (code 9002)")
+            W = _f64(W).reshape(-1).copy()
+        if dt0 is None:
+            dt0 = 0.1 * min(float(q[1]) - float(q[0]) for q in (self.x, self.y, self.z)) ** 2
+        if dt_min is None:
+            dt_min = 1e-6 * dt0
+        ioptc, ropt = self._options(niterex_max, ncycles_max, ex_tol, vc_tol, ms, mean, mixed_precision, flxcrl)
+        hist = np.zeros((int(hist_rows), 6))
+        info = np.zeros(3, dtype=np.intc)
+        args = (0 if start == "potential" else 1, int(niter_max), int(check), float(tol), float(dt0), float(dt_min),
+                hist.ctypes.data, int(hist_rows), info.ctypes.data)
+        if not device:
+            ierr = self.L.ndsm_hip_vecpot_optimize(self.h, ioptc.ctypes.data_as(_ip), _d(ropt), B.ctypes.data,
+                                                   None if W is None else W.ctypes.data, *args)
+        elif W is None:
+            ierr = self._on_device([B], lambda dB: self.L.ndsm_hip_vecpot_optimize_device(
+                self.h, ioptc.ctypes.data_as(_ip), _d(ropt), dB, None, *args))
+        else:
+            ierr = self._on_device([B, W], lambda dB, dW: self.L.ndsm_hip_vecpot_optimize_device(
+                self.h, ioptc.ctypes.data_as(_ip), _d(ropt), dB, dW, *args))
+        if ierr >= 9000:
+            _check(ierr, "ndsm_hip_vecpot_optimize", self.L)
+        self.last_ioptc, self.last_ropt = ioptc, ropt
+        return ierr, B.reshape(shape), hist[:int(info[0])].copy(), tuple(int(v) for v in info)
 
     def paths(self, b, seeds, g=None, step=0.5, max_steps=None, direction="both", every=1, max_points=None,
               values=True, device=False):
@@ -1445,6 +1511,42 @@ def force_free_field(x, y, z, b, alpha0, polarity=1, start="potential", a_init=N
                             step=step, max_steps=max_steps, niterex_max=niterex_max, ncycles_max=ncycles_max,
                             ex_tol=ex_tol, vc_tol=vc_tol, ms=ms, mean=mean, mixed_precision=mixed_precision,
                             flxcrl=flxcrl)
+    finally:
+        V.close()
+
+
+def boundary_weight(shape, nd):
+    """The weight function w (nz,ny,nx) of optimize() for a grid of that shape: 1 inside, and over the nd nodes next
+    to the two side faces in x, the two in y and the top face a cosine fall 1/2 (1 + cos(pi (nd - d) / nd)), d the
+    node distance to the face (0 on the face itself); the per-axis factors are multiplied.  The lower face - the
+    magnetogram - is untouched.  nd = 0 gives ones.  Plain numpy."""
+    nz, ny, nx = (int(v) for v in shape)
+    nd = int(nd)
+    if nd < 0:
+        raise ValueError(f"nd must be >= 0, not {nd!r}")
+
+    def profile(n, both):
+        f = np.ones(n)
+        for d in range(min(nd, n)):
+            v = 0.5 * (1.0 + np.cos(np.pi * (nd - d) / nd))
+            f[n - 1 - d] = min(f[n - 1 - d], v)
+            if both:
+                f[d] = min(f[d], v)
+        return f
+    return (profile(nz, False)[:, None, None] * profile(ny, True)[None, :, None]) * profile(nx, True)[None, None, :]
+
+
+def force_free_optimize(x, y, z, b, w=None, start="potential", niter_max=10000, check=50, tol=1e-4, dt0=None,
+                        dt_min=None, hist_rows=None, niterex_max=10000, ncycles_max=1024, ex_tol=1e-13, vc_tol=1e-10,
+                        ms=5, mean=False, mixed_precision=False, flxcrl=False, ngrids=0, lib=None):
+    """Nonlinear force-free field from the vector magnetogram on the lower face of b (3,nz,ny,nx) by the optimization
+    method: one-shot form of VecPot.optimize (returns its (ierr, B, hist, info)).  Raises NdsmHipError on device /
+    runtime failures (>= 9001)."""
+    V = _grid_handle(x, y, z, b, ngrids, lib)
+    try:
+        return V.optimize(b, w=w, start=start, niter_max=niter_max, check=check, tol=tol, dt0=dt0, dt_min=dt_min,
+                          hist_rows=hist_rows, niterex_max=niterex_max, ncycles_max=ncycles_max, ex_tol=ex_tol,
+                          vc_tol=vc_tol, ms=ms, mean=mean, mixed_precision=mixed_precision, flxcrl=flxcrl)
     finally:
         V.close()
 

@@ -211,6 +211,19 @@ int ndsmk_current_rhs(const double *F, const double *alpha, double *rhs, const i
 int ndsmk_nlfff_metrics(const double *B, const double *Bold, const int32_t *status, const int32_t *n3,
                         const double *h_dq3, double *h_out4);
 
+/* The optimization-method force-free solver (optimize.hip; semantics: include/ndsm_hip.h, ndsm_hip_vecpot_optimize).
+ * B0, B1 (nx,ny,nz,3): the two field buffers, B0 holds the start; O (nx,ny,nz,3,2): the two Omega buffers; w (nx,ny,nz)
+ * or NULL (1 everywhere); work: ndsmk_optimize_work_bytes() bytes, the state and the block partials; all DEVICE arrays.
+ * begin: the state (dt0, buffer 0 current) and Omega, L of B0.  tries: ntries tries, each decided on the device; a dt
+ * below dt_min stops the rest.  Both asynchronous.  row: blocking, h_row8 (host) = [tries, L, L_f, L_d, dt, accepted,
+ * the index of the buffer that holds the current field, 1 once dt < dt_min]. */
+size_t ndsmk_optimize_work_bytes(void);
+int ndsmk_optimize_begin(double *B0, double *B1, double *O, const double *w, double *work, const int32_t *n3,
+                         const double *h_dq3, double dt0, double dt_min);
+int ndsmk_optimize_tries(double *B0, double *B1, double *O, const double *w, double *work, const int32_t *n3,
+                         const double *h_dq3, double dt_min, int ntries);
+int ndsmk_optimize_row(const double *work, double *h_row8);
+
 /* the solenoidal projection (project.hip), all DEVICE arrays: rhs = div_h B - c into the projection solver's
  * level-1 rhs (c = sum w div_h B / sum w stays on the device); B -= G_h phi, the normal component on the end
  * planes of its axis untouched; then, blocking, max |div_h B'| and h_out4 = [c, max |div_h B| before, after,

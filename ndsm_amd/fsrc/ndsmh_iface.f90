@@ -581,6 +581,36 @@ module ndsmh_iface
       real(c_double), value :: step
       integer(c_int) :: rc
     end function
+    ! ---- the optimization-method force-free solver (optimize.hip) ----
+    function ndsmk_optimize_work_bytes() bind(c, name="ndsmk_optimize_work_bytes") result(nb)
+      import :: c_size_t
+      integer(c_size_t) :: nb
+    end function
+    function ndsmk_optimize_begin(B0, B1, O, w, work, n3, dq3, dt0, dt_min) bind(c, name="ndsmk_optimize_begin") &
+        result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_double
+      type(c_ptr), value :: B0, B1, O, w, work
+      integer(c_int32_t), intent(in) :: n3(3)
+      real(c_double), intent(in) :: dq3(3)
+      real(c_double), value :: dt0, dt_min
+      integer(c_int) :: rc
+    end function
+    function ndsmk_optimize_tries(B0, B1, O, w, work, n3, dq3, dt_min, ntries) bind(c, name="ndsmk_optimize_tries") &
+        result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_double
+      type(c_ptr), value :: B0, B1, O, w, work
+      integer(c_int32_t), intent(in) :: n3(3)
+      real(c_double), intent(in) :: dq3(3)
+      real(c_double), value :: dt_min
+      integer(c_int), value :: ntries
+      integer(c_int) :: rc
+    end function
+    function ndsmk_optimize_row(work, row8) bind(c, name="ndsmk_optimize_row") result(rc)
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: work
+      real(c_double), intent(out) :: row8(8)
+      integer(c_int) :: rc
+    end function
     function ndsmk_helicity_reduce(A, Ap, B, Bp, Br, n3, dq3, out8) bind(c, name="ndsmk_helicity_reduce") result(rc)
       import :: c_ptr, c_int, c_int32_t, c_double
       type(c_ptr), value :: A, Ap, B, Bp, Br

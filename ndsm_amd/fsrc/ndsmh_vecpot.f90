@@ -32,7 +32,7 @@ module ndsmh_vecpot
 
   public :: vecpot_solve, poisson_solve
   public :: vecpot_ctx, vecpot_ctx_create, vecpot_ctx_destroy, vecpot_ctx_matches, vecpot_run, vecpot_cache_drop
-  public :: vecpot_alpha_map, vecpot_nlfff, nlfff_args
+  public :: vecpot_alpha_map, vecpot_nlfff, nlfff_args, vecpot_optimize, optimize_args
   public :: vecpot_project, vecpot_devore, vecpot_lines, vecpot_paths, vecpot_nulls, vecpot_skeleton, vecpot_separators
   public :: VP_POTENTIAL, VP_FIELD, VP_HELICITY, VP_CURRENT, VP_NLFFF
   ! pieces the distributed driver (ndsmh_wvecpot) shares with vecpot_solve
@@ -112,6 +112,15 @@ module ndsmh_vecpot
     integer(c_int) :: polarity = 1, start = 0, niter_max = 1, max_steps = 1
     real(wp) :: tol = 0, step = 0.5_wp
     integer(c_int) :: niter = 0
+  end type
+
+  ! what an optimization-method call takes besides B (vecpot_optimize): w (nx,ny,nz) in, on the side B is on, may be
+  ! c_null_ptr (1 everywhere); hist (6,hist_rows) on the HOST; info out: rows written, tries, stop reason
+  type :: optimize_args
+    type(c_ptr) :: w = c_null_ptr, hist = c_null_ptr
+    integer(c_int) :: start = 0, niter_max = 1, check = 1, hist_rows = 2
+    real(wp) :: tol = 0, dt0 = 0, dt_min = 0
+    integer(c_int) :: info(3) = 0
   end type
 
   ! one array of a host-array line entry in its staging buffer (carve, fetch)
@@ -1444,6 +1453,117 @@ contains
       end if
     end if
     nl%niter = dv%niter
+    call unstage(rc, [buf])
+  end function
+
+  ! ------------------------------------------------------------------
+  ! The optimization method on a prepared context (semantics in include/ndsm_hip.h, DESIGN.md "Optimization-method
+  ! force-free field").  pB (nx,ny,nz,3) in and out and op%w (nx,ny,nz; may be c_null_ptr) in, on the HOST (both go up
+  ! once, B comes home once; between the two only history rows cross PCIe) or (on_device) in HBM; op%hist on the HOST.
+  ! start = 1: the input is B^0, the context supplies the mesh only - no solve, no hierarchy.  start = 0: B^0 is the
+  ! potential field of the input's B.n (vecpot_run's potential mode on device arrays, a zero guess), its k = 0 plane
+  ! then replaced by the input's.  One buffer holds the second field, the two Omega and the state for the length of
+  ! the call; a grid whose arrays the device cannot hold is refused before it is allocated.  The tries of one check
+  ! interval are queued without a read-back: the device decides each (optimize.hip).
+  ! ------------------------------------------------------------------
+  function vecpot_optimize(ctx, iopt, ropt, pB, op, on_device) result(rc)
+    type(vecpot_ctx), intent(inout), target :: ctx
+    integer(ik), intent(inout) :: iopt(0:OPT_LEN - 1)
+    real(wp), intent(inout) :: ropt(0:OPT_LEN - 1)
+    type(c_ptr), intent(in) :: pB
+    type(optimize_args), intent(inout) :: op
+    logical, intent(in) :: on_device
+    integer(c_int) :: rc
+    real(wp) :: dq(3), lo(3), row(8), lprev
+    real(wp), pointer :: hh(:, :)
+    integer(c_int32_t) :: n3(3)
+    integer(c_size_t) :: nb, wk, total, fr, tot, plane
+    integer(c_int) :: rows, tries, n
+    integer :: c, k
+    type(c_ptr) :: buf, dB0, dB1, dO, dwork, dw
+
+    op%info = 0
+    buf = c_null_ptr
+    call ctx_mesh(ctx, n3, lo, dq)
+    nb = int(product(int(n3, ik)), c_size_t) * 8_c_size_t
+    wk = ndsmk_optimize_work_bytes()
+    ! two fields, two Omega and w are 13 level-1 arrays; a potential start adds the 3-D hierarchy (at least five)
+    k = 13 + merge(5, 0, op%start == 0 .and. .not. ctx%live3)
+    rc = ndsmk_mem_info(fr, tot); if (rc /= 0) return
+    if (real(nb, wp) * real(k, wp) + real(wk, wp) > real(tot, wp)) then
+      rc = ndsmk_note_error(NDSMK_ENODEV, "the grid needs more device memory than the device has"//c_null_char)
+      return
+    end if
+    ! [B1 | Omega 0, Omega 1 | work], and for the host entry [B0 | w]
+    total = 9_c_size_t * nb + wk
+    if (.not. on_device) total = total + merge(4_c_size_t, 3_c_size_t, c_associated(op%w)) * nb
+    rc = ndsmk_alloc(buf, total); if (rc /= 0) return
+    dB1 = buf
+    dO = dptr_offset(buf, 3_c_size_t * nb)
+    dwork = dptr_offset(buf, 9_c_size_t * nb)
+    if (on_device) then
+      dB0 = pB; dw = op%w
+    else
+      dB0 = dptr_offset(buf, 9_c_size_t * nb + wk)
+      rc = ndsmk_h2d(dB0, pB, 3_c_size_t * nb); if (rc /= 0) goto 900
+      dw = c_null_ptr
+      if (c_associated(op%w)) then
+        dw = dptr_offset(buf, 12_c_size_t * nb + wk)
+        rc = ndsmk_h2d(dw, op%w, nb); if (rc /= 0) goto 900
+      end if
+    end if
+
+    if (op%start == 0) then
+      call say("optimize", "Potential start field...")
+      rc = ndsmk_d2d(dB1, dB0, 3_c_size_t * nb); if (rc /= 0) goto 900        ! (the magnetogram comes back from here)
+      rc = ndsmk_fill0(dO, 3_c_size_t * nb); if (rc /= 0) goto 900            ! A: a zero guess, in Omega 0's place
+      rc = ndsmk_sync(); if (rc /= 0) goto 900
+      rc = vecpot_run(ctx, iopt, ropt, dO, dB0, .true., VP_POTENTIAL); if (rc /= 0) goto 900
+      iopt(IOPT_IERR) = merge(1_ik, 0_ik, iopt(IOPT_IERR) /= 0 .or. iopt(IOPT_FAIL3D) /= 0)
+      plane = int(n3(1), c_size_t) * int(n3(2), c_size_t) * 8_c_size_t
+      do c = 0, 2
+        rc = ndsmk_d2d(dptr_offset(dB0, int(c, c_size_t) * nb), dptr_offset(dB1, int(c, c_size_t) * nb), plane)
+        if (rc /= 0) goto 900
+      end do
+    else
+      iopt(IOPT_IERR) = 0
+    end if
+
+    call say("optimize", "Descent...")
+    call c_f_pointer(op%hist, hh, [6, int(op%hist_rows)])
+    rc = ndsmk_optimize_begin(dB0, dB1, dO, dw, dwork, n3, dq, op%dt0, op%dt_min); if (rc /= 0) goto 900
+    rc = ndsmk_optimize_row(dwork, row); if (rc /= 0) goto 900
+    hh(:, 1) = row(1:6)
+    rows = 1; tries = 0
+    lprev = row(2)
+    op%info(3) = 0
+    if (row(8) /= 0.0_wp) op%info(3) = 2
+    do while (op%info(3) == 0 .and. tries < op%niter_max)
+      n = min(op%check, op%niter_max - tries)
+      rc = ndsmk_optimize_tries(dB0, dB1, dO, dw, dwork, n3, dq, op%dt_min, n); if (rc /= 0) goto 900
+      rc = ndsmk_optimize_row(dwork, row); if (rc /= 0) goto 900
+      tries = tries + n
+      rows = min(rows + 1_c_int, op%hist_rows)
+      hh(:, rows) = row(1:6)
+      if (row(8) /= 0.0_wp) then
+        op%info(3) = 2
+      else if (n == op%check) then
+        if (lprev - row(2) <= op%tol * lprev) op%info(3) = 1
+        lprev = row(2)
+      end if
+      if (op%info(3) == 1) exit
+    end do
+    op%info(1) = rows
+    op%info(2) = int(row(1), c_int)
+    if (row(7) /= 0.0_wp) then
+      rc = ndsmk_d2d(dB0, dB1, 3_c_size_t * nb); if (rc /= 0) goto 900
+    end if
+    if (.not. on_device) then
+      rc = ndsmk_d2h(pB, dB0, 3_c_size_t * nb); if (rc /= 0) goto 900
+    end if
+    rc = ndsmk_sync()
+900 continue
+    if (rc /= 0) op%info = 0
     call unstage(rc, [buf])
   end function
 

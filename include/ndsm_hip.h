@@ -455,6 +455,53 @@ int ndsm_hip_vecpot_optimize_device(void *h, int ioptc[16], double ropt[16], dou
                                     int niter_max, int check, double tol, double dt0, double dt_min, double *hist,
                                     int hist_rows, int *info);
 
+/* ---- Magnetogram preprocessing (DESIGN.md "Magnetogram preprocessing") ---------------------------------------------
+ * What comes before ndsm_hip_vecpot_optimize when the lower-face data are measured (Wiegelmann, Inhester & Sakurai
+ * 2006): a photospheric vector magnetogram is not the boundary of a force-free field - its net Maxwell force and
+ * torque (Aly's integrals) do not vanish and its transverse components are noisy.  The call moves it, within the
+ * measurement error, towards a force-free, torque-free and smooth one by descending
+ *   L = mu1 L1 + mu2 L2 + mu3h L3h + mu3z L3z + mu4 L4
+ * on the k = 0 face of the handle's mesh: nx x ny nodes, spacings hx, hy, hh = hx hy, W the trapezoid weight of the
+ * plane, x_i = (i - (nx-1)/2) hx and y_j = (j - (ny-1)/2) hy (moments about the centre), e = Bz^2 - Bx^2 - By^2,
+ * Bo the observation:
+ *   S1 = sum W Bx Bz   S2 = sum W By Bz   S3 = sum W e   S4 = sum W x e   S5 = sum W y e
+ *   S6 = sum W (y Bx Bz - x By Bz)   S7 = sum W ((Bx-Box)^2 + (By-Boy)^2)   S8 = sum W (Bz-Boz)^2
+ *   S9 = hh sum |Lambda|^2, Lambda_c the 5-point Laplacian of B_c on interior nodes, 0 on the edge nodes
+ *   S10 = sum W |B|^2   S11 = sum W sqrt(x^2+y^2) |B|^2;   E = S10 and M = S11 of Bo, fixed for the call
+ *   L1 = (S1^2+S2^2+S3^2)/E^2   L2 = (S4^2+S5^2+S6^2)/M^2   L3h = S7/E   L3z = S8/E   L4 = hh^2 S9/E
+ * L is dimensionless: rescaling B or the mesh leaves it unchanged.  G = dL/dB is the exact discrete gradient at every
+ * node, edge nodes included.
+ *   B         (nx,ny,3) in: the magnetogram, out: the preprocessed one.  Nothing else of the handle is used or kept.
+ *   obs       (nx,ny,3) in, the observation Bo, or NULL: the input B.  (A continued call passes the original.)
+ *   mu        5 doubles on the HOST: mu1, mu2, mu3h, mu3z, mu4, each finite and >= 0
+ *   One try: T = B - dt (E/hh) G, dt dimensionless; L of T; L_T < L (strictly; a NaN fails) accepts - T becomes the
+ *   field, dt *= 1.01 - and anything else rejects: dt *= 0.5.  The decision is taken on the device, so nothing is read
+ *   back between two checks.
+ *   niter_max >= 1 tries at most.  dt0 > 0 the first step.  The loop stops before a try when dt < dt_min, and at a
+ *   check - after every `check` tries - when L_prev - L <= tol L_prev, L_prev the L of the previous check (of the
+ *   start at the first).
+ *   hist      (hist_rows >= 2 rows of 17 doubles, on the HOST in both entries): [tries, L, L1, L2, L3h, L3z, L4, dt,
+ *             accepted, S1, S2, S3, S4, S5, S6, S10, S11].  Row 0 is the start, then one row per check, the final
+ *             state always last; when the rows run out the last row is overwritten.  (|S1|+|S2|+|S3|)/S10 and
+ *             (|S4|+|S5|+|S6|)/S11 are the usual force and torque balance figures.  Deterministic sums: the same
+ *             input gives the same bits.
+ *   info      (3 ints, on the HOST in both entries): rows written, tries, stop reason (0 niter_max, 1 tol, 2 dt_min)
+ *   Returns 0; >= 9001 errors: 9001 without a GPU whatever the arguments, 9002 a NULL handle, B, mu, hist or info,
+ *   9004 a negative or non-finite mu, niter_max < 1, check < 1, hist_rows < 2, tol < 0 or not finite, dt0 <= 0 or not
+ *   finite, dt_min < 0 or not finite, an observation whose E or M is not > 0.  A failed call clears hist and info,
+ *   never B.
+ *   Device memory: a second field, two Lambda fields, the observation and 176 KiB of state next to the caller's B
+ *   (the host entry stages B as well), for the length of the call.  Not included: confidence masks, chromospheric
+ *   terms, a flux-balance correction, an automatic call from ndsm_hip_vecpot_optimize - the caller puts the result
+ *   on the k = 0 plane of the field handed to it. */
+/* HOST arrays */
+int ndsm_hip_vecpot_preprocess(void *h, double *B, const double *obs, const double mu[5], int niter_max, int check,
+                               double tol, double dt0, double dt_min, double *hist, int hist_rows, int *info);
+/* the same on DEVICE arrays of the library's GPU (mu, hist and info stay on the host) */
+int ndsm_hip_vecpot_preprocess_device(void *h, double *dB, const double *dobs, const double mu[5], int niter_max,
+                                      int check, double tol, double dt0, double dt_min, double *hist, int hist_rows,
+                                      int *info);
+
 /* ---- Field-line paths: the points of the same lines (DESIGN.md "Field-line paths") ---------------------------------
  * Where a line runs, not only where it ends: every `every`-th point of each traced line, with B, G and the running
  * integral at it - for drawing lines over a Q map, sampling a field along a loop, or following lines started near a

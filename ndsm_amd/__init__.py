@@ -13,7 +13,8 @@ from ._lib import (load_library, lib_path, MGSolver, VecPot, World, slab_plan, p
                    field_line_helicity, QMap, squashing_factor, seed_plane, Nulls, find_nulls, FieldPaths, trace_paths,
                    path_of, whole_line, Skeleton, find_skeleton, spine_of, fan_of, connections, Separators,
                    find_separators, separator_of, QPerpMap, perpendicular_squashing, seed_cut, boundary_alpha,
-                   map_alpha, vector_potential_current, force_free_field, boundary_weight, force_free_optimize)
+                   map_alpha, vector_potential_current, force_free_field, boundary_weight, force_free_optimize,
+                   preprocess_magnetogram, magnetogram_balance)
 
 __all__ = ["vector_potential", "vector_potential_slab", "get_lib_path", "load_library", "lib_path", "MGSolver", "VecPot", "poisson_solve",
            "NdsmHipError", "Helicity", "vector_potential_field", "relative_helicity", "Projection", "solenoidal_projection",
@@ -21,4 +22,5 @@ __all__ = ["vector_potential", "vector_potential_slab", "get_lib_path", "load_li
            "squashing_factor", "seed_plane", "Nulls", "find_nulls", "FieldPaths", "trace_paths", "path_of", "whole_line",
            "Skeleton", "find_skeleton", "spine_of", "fan_of", "connections", "Separators", "find_separators",
            "separator_of", "QPerpMap", "perpendicular_squashing", "seed_cut", "boundary_alpha", "map_alpha",
-           "vector_potential_current", "force_free_field", "boundary_weight", "force_free_optimize"]
+           "vector_potential_current", "force_free_field", "boundary_weight", "force_free_optimize",
+           "preprocess_magnetogram", "magnetogram_balance"]

@@ -110,6 +110,10 @@ def load_library(path=None):
            [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p])
     L.ndsm_hip_vecpot_optimize.argtypes = _op
     L.ndsm_hip_vecpot_optimize_device.argtypes = _op
+    _pp = ([ctypes.c_void_p] * 4 + [ctypes.c_int] * 2 + [ctypes.c_double] * 3 +
+           [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p])
+    L.ndsm_hip_vecpot_preprocess.argtypes = _pp
+    L.ndsm_hip_vecpot_preprocess_device.argtypes = _pp
     _pa = ([ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64] +
            [ctypes.c_void_p] * 11)
     L.ndsm_hip_vecpot_paths.argtypes = [ctypes.c_void_p] * 3 + _pa
@@ -693,6 +697,68 @@ class VecPot:
         if ierr >= 9000:
             _check(ierr, "ndsm_hip_vecpot_optimize", self.L)
         self.last_ioptc, self.last_ropt = ioptc, ropt
+        return ierr, B.reshape(shape), hist[:int(info[0])].copy(), tuple(int(v) for v in info)
+
+    def preprocess(self, bm, obs=None, mu=(1, 1, 1e-3, 1e-2, 1e-2), niter_max=10000, check=50, tol=1e-4, dt0=None,
+                   dt_min=None, hist_rows=None, device=False):
+        """Preprocessing of a measured vector magnetogram for optimize() (Wiegelmann, Inhester & Sakurai 2006) on the
+        device (semantics: include/ndsm_hip.h, ndsm_hip_vecpot_preprocess): bm (3,ny,nx), the field on the lower face
+        of the handle's mesh, is moved by descent steps that lower L = mu1 L1 + mu2 L2 + mu3h L3h + mu3z L3z + mu4 L4
+        - net force, net torque, distance of the horizontal and of the vertical component from the observation,
+        roughness.  obs (3,ny,nx): the observation the distance terms refer to, None for bm itself (a continued call
+        passes the original).  mu = (mu1, mu2, mu3h, mu3z, mu4), each >= 0.  At most niter_max tries; every `check`
+        tries the loop looks at L and stops when it fell by no more than tol * L since the last look, or when
+        dt < dt_min.  dt0: the first step, dimensionless (None: 0.01); dt_min None: 1e-6 dt0.  The default mu and dt0
+        are those of a numerical prototype on a synthetic field; they are NOT tuned on real data - choose mu3h, mu3z
+        from the measurement errors.  hist_rows None: one row per check and two more.  Returns (ierr, Bm, hist, info):
+        hist (rows, 17) = [tries, L, L1, L2, L3h, L3z, L4, dt, accepted, S1 .. S6, S10, S11] - row 0 the start, the
+        final state last (magnetogram_balance() turns it into the force and torque figures) -, info = (rows, tries,
+        stop reason: 0 niter_max, 1 tol, 2 dt_min).  Nothing of the handle changes; the caller puts Bm on the k = 0
+        plane of the b handed to optimize().  device=True: the arrays are staged in device memory and the
+        device-resident entry point runs."""
+        for name, v in (("niter_max", niter_max), ("check", check)):
+            if int(v) != v or v < 1:
+                raise ValueError(f"{name} must be a whole number >= 1, not {v!r}")
+        if not (tol >= 0.0 and np.isfinite(tol)):
+            raise ValueError(f"tol must be finite and >= 0, not {tol!r}")
+        if dt0 is not None and not (dt0 > 0.0 and np.isfinite(dt0)):
+            raise ValueError(f"dt0 must be finite and > 0, not {dt0!r}")
+        if dt_min is not None and not (dt_min >= 0.0 and np.isfinite(dt_min)):
+            raise ValueError(f"dt_min must be finite and >= 0, not {dt_min!r}")
+        if hist_rows is None:
+            hist_rows = -(-int(niter_max) // int(check)) + 2
+        if int(hist_rows) != hist_rows or hist_rows < 2:
+            raise ValueError(f"hist_rows must be a whole number >= 2, not {hist_rows!r}")
+        muv = np.array(mu, dtype=np.float64).reshape(-1)
+        if muv.size != 5 or not (np.isfinite(muv).all() and (muv >= 0.0).all()):
+            raise ValueError(f"mu must be five finite numbers >= 0, not {mu!r}")
+        shape = (3,) + tuple(int(v) for v in self.nshape4[1::-1])
+        arrays = []
+        for name, v in (("magnetogram", bm), ("observation", obs)):
+            if v is None:
+                continue
+            a = np.asarray(v)
+            if a.shape != shape:
+                raise NdsmHipError(f"preprocess: {name} of shape {a.shape}, the handle's lower face needs {shape} "
+                                   "(code 9002)")
+            arrays.append(_f64(a).reshape(-1).copy())
+        B = arrays[0]
+        if dt0 is None:
+            dt0 = 0.01
+        if dt_min is None:
+            dt_min = 1e-6 * dt0
+        hist = np.zeros((int(hist_rows), 17))
+        info = np.zeros(3, dtype=np.intc)
+        args = (muv.ctypes.data, int(niter_max), int(check), float(tol), float(dt0), float(dt_min), hist.ctypes.data,
+                int(hist_rows), info.ctypes.data)
+        if not device:
+            ierr = self.L.ndsm_hip_vecpot_preprocess(self.h, B.ctypes.data,
+                                                     None if obs is None else arrays[1].ctypes.data, *args)
+        elif obs is None:
+            ierr = self._on_device([B], lambda dB: self.L.ndsm_hip_vecpot_preprocess_device(self.h, dB, None, *args))
+        else:
+            ierr = self._on_device(arrays, lambda dB, dO: self.L.ndsm_hip_vecpot_preprocess_device(self.h, dB, dO, *args))
+        _check(ierr, "ndsm_hip_vecpot_preprocess", self.L)
         return ierr, B.reshape(shape), hist[:int(info[0])].copy(), tuple(int(v) for v in info)
 
     def paths(self, b, seeds, g=None, step=0.5, max_steps=None, direction="both", every=1, max_points=None,
@@ -1549,6 +1615,33 @@ def force_free_optimize(x, y, z, b, w=None, start="potential", niter_max=10000, 
                           vc_tol=vc_tol, ms=ms, mean=mean, mixed_precision=mixed_precision, flxcrl=flxcrl)
     finally:
         V.close()
+
+
+def preprocess_magnetogram(x, y, z, bm, obs=None, mu=(1, 1, 1e-3, 1e-2, 1e-2), niter_max=10000, check=50, tol=1e-4,
+                           dt0=None, dt_min=None, hist_rows=None, lib=None):
+    """Preprocessing of the vector magnetogram bm (3,ny,nx) on the lower face of the mesh x, y, z towards a force-free,
+    torque-free, smooth one: one-shot form of VecPot.preprocess (returns its (ierr, Bm, hist, info); the defaults are
+    not tuned on real data).  Raises NdsmHipError on device / runtime failures (>= 9001)."""
+    want = (3, len(y), len(x))
+    if tuple(np.shape(bm)) != want:
+        raise NdsmHipError(f"magnetogram of shape {tuple(np.shape(bm))}, the mesh needs {want} (code 9002)")
+    V = VecPot(x, y, z, lib=lib)
+    try:
+        return V.preprocess(bm, obs=obs, mu=mu, niter_max=niter_max, check=check, tol=tol, dt0=dt0, dt_min=dt_min,
+                            hist_rows=hist_rows)
+    finally:
+        V.close()
+
+
+def magnetogram_balance(hist):
+    """(eps_force, eps_torque) per row of a preprocess() history (one row or many): (|S1| + |S2| + |S3|) / S10 and
+    (|S4| + |S5| + |S6|) / S11, the net Maxwell force and torque of the magnetogram relative to its magnetic pressure
+    force and its moment.  Plain numpy."""
+    h = np.asarray(hist, dtype=np.float64)
+    if h.shape[-1] != 17:
+        raise ValueError(f"history rows have 17 entries, not {h.shape[-1]}")
+    s = np.abs(h[..., 9:15])
+    return (s[..., 0] + s[..., 1] + s[..., 2]) / h[..., 15], (s[..., 3] + s[..., 4] + s[..., 5]) / h[..., 16]
 
 
 def trace_paths(x, y, z, b, seeds, g=None, step=0.5, max_steps=None, direction="both", every=1, max_points=None,

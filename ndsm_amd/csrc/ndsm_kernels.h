@@ -224,6 +224,20 @@ int ndsmk_optimize_tries(double *B0, double *B1, double *O, const double *w, dou
                          const double *h_dq3, double dt_min, int ntries);
 int ndsmk_optimize_row(const double *work, double *h_row8);
 
+/* Magnetogram preprocessing (preprocess.hip; semantics: include/ndsm_hip.h, ndsm_hip_vecpot_preprocess).  B0, B1
+ * (nx,ny,3): the two field buffers, B0 holds the start; La (nx,ny,3,2): the two Lambda buffers; obs (nx,ny,3): the
+ * observation, never written; work: ndsmk_preprocess_work_bytes() bytes, the state and the block partials; all DEVICE
+ * arrays.  n2, h_dq2: nodes and spacing of the plane; h_mu5 (host) = mu1, mu2, mu3h, mu3z, mu4.  begin: the state (dt0,
+ * buffer 0 current), E and M of obs, then Lambda, the sums and L of B0.  tries: ntries tries, each decided on the
+ * device; a dt below dt_min stops the rest.  Both asynchronous.  row: blocking, h_row21 (host) = the 17 doubles of a
+ * history row, then [the index of the buffer that holds the current field, 1 once dt < dt_min, E, M]. */
+size_t ndsmk_preprocess_work_bytes(void);
+int ndsmk_preprocess_begin(double *B0, double *B1, double *La, const double *obs, double *work, const int32_t *n2,
+                           const double *h_dq2, const double *h_mu5, double dt0, double dt_min);
+int ndsmk_preprocess_tries(double *B0, double *B1, double *La, const double *obs, double *work, const int32_t *n2,
+                           const double *h_dq2, const double *h_mu5, double dt_min, int ntries);
+int ndsmk_preprocess_row(const double *work, double *h_row21);
+
 /* the solenoidal projection (project.hip), all DEVICE arrays: rhs = div_h B - c into the projection solver's
  * level-1 rhs (c = sum w div_h B / sum w stays on the device); B -= G_h phi, the normal component on the end
  * planes of its axis untouched; then, blocking, max |div_h B'| and h_out4 = [c, max |div_h B| before, after,

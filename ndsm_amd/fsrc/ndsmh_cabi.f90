@@ -1286,6 +1286,76 @@ contains
     end if
   end function
 
+  ! Magnetogram preprocessing (semantics in include/ndsm_hip.h).  B (nx,ny,3) in: the magnetogram on the handle's
+  ! lower face; out: the preprocessed one.  obs (nx,ny,3) in, may be NULL (the input B).  mu (5) in.  hist (hist_rows,17)
+  ! and info (3 ints) out, on the HOST in both entries.  HOST arrays
+  function ndsm_hip_vecpot_preprocess(handle, B, obs, mu, niter_max, check, tol, dt0, dt_min, hist, hist_rows, info) &
+      bind(c, name="ndsm_hip_vecpot_preprocess") result(ierr)
+    type(c_ptr), value :: handle, B, obs, mu, hist, info
+    integer(c_int), value :: niter_max, check, hist_rows
+    real(c_double), value :: tol, dt0, dt_min
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_preprocess(handle, B, obs, mu, niter_max, check, tol, dt0, dt_min, hist, hist_rows, info, &
+                                    .false., "ndsm_hip_vecpot_preprocess")
+  end function
+
+  ! the same on DEVICE arrays of the library's GPU: only history rows cross PCIe
+  function ndsm_hip_vecpot_preprocess_device(handle, dB, dobs, mu, niter_max, check, tol, dt0, dt_min, hist, &
+                                             hist_rows, info) &
+      bind(c, name="ndsm_hip_vecpot_preprocess_device") result(ierr)
+    type(c_ptr), value :: handle, dB, dobs, mu, hist, info
+    integer(c_int), value :: niter_max, check, hist_rows
+    real(c_double), value :: tol, dt0, dt_min
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_preprocess(handle, dB, dobs, mu, niter_max, check, tol, dt0, dt_min, hist, hist_rows, info, &
+                                    .true., "ndsm_hip_vecpot_preprocess_device")
+  end function
+
+  function vecpot_handle_preprocess(handle, B, obs, mu, niter_max, check, tol, dt0, dt_min, hist, hist_rows, info, &
+                                    on_device, who) result(ierr)
+    type(c_ptr), intent(in) :: handle, B, obs, mu, hist, info
+    integer(c_int), intent(in) :: niter_max, check, hist_rows
+    real(c_double), intent(in) :: tol, dt0, dt_min
+    logical, intent(in) :: on_device
+    character(len=*), intent(in) :: who
+    integer(c_int) :: ierr
+    type(vecpot_ctx), pointer :: ctx
+    type(preprocess_args) :: pp
+    integer(c_int), pointer :: iout(:)
+    real(c_double), pointer :: pmu(:)
+    integer(c_int) :: rc
+    if (c_associated(info)) then
+      call c_f_pointer(info, iout, [3])
+      iout = 0
+    end if
+    ierr = live_ctx(handle, ctx)
+    if (ierr == 0 .and. .not. (c_associated(B) .and. c_associated(mu) .and. c_associated(hist) .and. &
+                               c_associated(info))) ierr = NDSMK_EARG
+    if (ierr == 0) then
+      call c_f_pointer(mu, pmu, [5])
+      pp%mu = pmu
+      if (niter_max < 1 .or. check < 1 .or. hist_rows < 2 .or. &
+          .not. all(pp%mu >= 0.0_c_double) .or. any(pp%mu > huge(tol)) .or. &
+          .not. (tol >= 0.0_c_double) .or. tol > huge(tol) .or. .not. (dt0 > 0.0_c_double) .or. &
+          dt0 > huge(dt0) .or. .not. (dt_min >= 0.0_c_double) .or. dt_min > huge(dt_min)) &
+        ierr = ndsmk_note_error(NDSMK_EVALUE, "preprocess: mu >= 0, niter_max >= 1, check >= 1, hist_rows >= 2, "// &
+                                "tol >= 0, dt0 > 0 and dt_min >= 0 (all finite)"//c_null_char)
+    end if
+    if (ierr == 0) then
+      pp%obs = obs; pp%hist = hist
+      pp%niter_max = niter_max; pp%check = check; pp%hist_rows = hist_rows
+      pp%tol = tol; pp%dt0 = dt0; pp%dt_min = dt_min
+      verbose = .false.
+      rc = vecpot_preprocess(ctx, B, pp, on_device)
+      ierr = reported(who, rc)
+      if (ierr == 0) iout = pp%info
+    end if
+    if (ierr >= NDSMK_ENODEV) then
+      if (c_associated(info)) iout = 0
+      if (c_associated(hist) .and. hist_rows >= 1) call clear_host([hist], [136], [int(hist_rows, c_int64_t)])
+    end if
+  end function
+
   ! ---- shared by the handle entries of the line and null calls below ----------
   ! the prologue: the runtime is up (without a device: 9001, whatever the arguments), and handle is that of a live
   ! context, which comes back in ctx; else 9002

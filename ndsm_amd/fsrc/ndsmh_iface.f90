@@ -611,6 +611,36 @@ module ndsmh_iface
       real(c_double), intent(out) :: row8(8)
       integer(c_int) :: rc
     end function
+    ! ---- magnetogram preprocessing (preprocess.hip) ----
+    function ndsmk_preprocess_work_bytes() bind(c, name="ndsmk_preprocess_work_bytes") result(nb)
+      import :: c_size_t
+      integer(c_size_t) :: nb
+    end function
+    function ndsmk_preprocess_begin(B0, B1, La, obs, work, n2, dq2, mu5, dt0, dt_min) &
+        bind(c, name="ndsmk_preprocess_begin") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_double
+      type(c_ptr), value :: B0, B1, La, obs, work
+      integer(c_int32_t), intent(in) :: n2(2)
+      real(c_double), intent(in) :: dq2(2), mu5(5)
+      real(c_double), value :: dt0, dt_min
+      integer(c_int) :: rc
+    end function
+    function ndsmk_preprocess_tries(B0, B1, La, obs, work, n2, dq2, mu5, dt_min, ntries) &
+        bind(c, name="ndsmk_preprocess_tries") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_double
+      type(c_ptr), value :: B0, B1, La, obs, work
+      integer(c_int32_t), intent(in) :: n2(2)
+      real(c_double), intent(in) :: dq2(2), mu5(5)
+      real(c_double), value :: dt_min
+      integer(c_int), value :: ntries
+      integer(c_int) :: rc
+    end function
+    function ndsmk_preprocess_row(work, row21) bind(c, name="ndsmk_preprocess_row") result(rc)
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: work
+      real(c_double), intent(out) :: row21(21)
+      integer(c_int) :: rc
+    end function
     function ndsmk_helicity_reduce(A, Ap, B, Bp, Br, n3, dq3, out8) bind(c, name="ndsmk_helicity_reduce") result(rc)
       import :: c_ptr, c_int, c_int32_t, c_double
       type(c_ptr), value :: A, Ap, B, Bp, Br

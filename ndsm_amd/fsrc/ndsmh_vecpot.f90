@@ -32,7 +32,7 @@ module ndsmh_vecpot
 
   public :: vecpot_solve, poisson_solve
   public :: vecpot_ctx, vecpot_ctx_create, vecpot_ctx_destroy, vecpot_ctx_matches, vecpot_run, vecpot_cache_drop
-  public :: vecpot_alpha_map, vecpot_nlfff, nlfff_args, vecpot_optimize, optimize_args
+  public :: vecpot_alpha_map, vecpot_nlfff, nlfff_args, vecpot_optimize, optimize_args, vecpot_preprocess, preprocess_args
   public :: vecpot_project, vecpot_devore, vecpot_lines, vecpot_paths, vecpot_nulls, vecpot_skeleton, vecpot_separators
   public :: VP_POTENTIAL, VP_FIELD, VP_HELICITY, VP_CURRENT, VP_NLFFF
   ! pieces the distributed driver (ndsmh_wvecpot) shares with vecpot_solve
@@ -119,6 +119,17 @@ module ndsmh_vecpot
   type :: optimize_args
     type(c_ptr) :: w = c_null_ptr, hist = c_null_ptr
     integer(c_int) :: start = 0, niter_max = 1, check = 1, hist_rows = 2
+    real(wp) :: tol = 0, dt0 = 0, dt_min = 0
+    integer(c_int) :: info(3) = 0
+  end type
+
+  ! what a preprocessing call takes besides B (vecpot_preprocess): obs (nx,ny,3) in, on the side B is on, may be
+  ! c_null_ptr (the input B is the observation); mu = mu1, mu2, mu3h, mu3z, mu4; hist (17,hist_rows) on the HOST; info
+  ! out: rows written, tries, stop reason
+  type :: preprocess_args
+    type(c_ptr) :: obs = c_null_ptr, hist = c_null_ptr
+    real(wp) :: mu(5) = 0
+    integer(c_int) :: niter_max = 1, check = 1, hist_rows = 2
     real(wp) :: tol = 0, dt0 = 0, dt_min = 0
     integer(c_int) :: info(3) = 0
   end type
@@ -1564,6 +1575,109 @@ contains
     rc = ndsmk_sync()
 900 continue
     if (rc /= 0) op%info = 0
+    call unstage(rc, [buf])
+  end function
+
+  ! ------------------------------------------------------------------
+  ! Magnetogram preprocessing on a prepared context (semantics in include/ndsm_hip.h, DESIGN.md "Magnetogram
+  ! preprocessing").  pB (nx,ny,3) in and out and pp%obs (the same; may be c_null_ptr: the input B) in, on the HOST
+  ! (both go up once, B comes home once; between the two only history rows cross PCIe) or (on_device) in HBM; pp%hist
+  ! on the HOST.  The context supplies the mesh of its lower face only - no solve, no hierarchy, nothing kept on it.
+  ! One buffer holds the second field, the two Lambda, the observation and the state for the length of the call.  The
+  ! tries of one check interval are queued without a read-back: the device decides each (preprocess.hip).
+  ! ------------------------------------------------------------------
+  function vecpot_preprocess(ctx, pB, pp, on_device) result(rc)
+    type(vecpot_ctx), intent(inout), target :: ctx
+    type(c_ptr), intent(in) :: pB
+    type(preprocess_args), intent(inout) :: pp
+    logical, intent(in) :: on_device
+    integer(c_int) :: rc
+    real(wp) :: dq(3), lo(3), row(21), lprev
+    real(wp), pointer :: hh(:, :)
+    integer(c_int32_t) :: n3(3)
+    integer(c_size_t) :: nb, wk, total, fr, tot
+    integer(c_int) :: rows, tries, n
+    type(c_ptr) :: buf, dB0, dB1, dLa, dobs, dwork
+
+    pp%info = 0
+    buf = c_null_ptr
+    call ctx_mesh(ctx, n3, lo, dq)
+    nb = int(n3(1), c_size_t) * int(n3(2), c_size_t) * 24_c_size_t          ! one field of the plane
+    wk = ndsmk_preprocess_work_bytes()
+    ! [B1 | Lambda 0, Lambda 1 | obs | work], and for the host entry [B0]
+    total = 4_c_size_t * nb + wk
+    if (.not. on_device) total = total + nb
+    rc = ndsmk_mem_info(fr, tot); if (rc /= 0) return
+    if (real(total, wp) + merge(real(nb, wp), 0.0_wp, on_device) > real(tot, wp)) then
+      rc = ndsmk_note_error(NDSMK_ENODEV, "the plane needs more device memory than the device has"//c_null_char)
+      return
+    end if
+    rc = ndsmk_alloc(buf, total); if (rc /= 0) return
+    dB1 = buf
+    dLa = dptr_offset(buf, nb)
+    dobs = dptr_offset(buf, 3_c_size_t * nb)
+    dwork = dptr_offset(buf, 4_c_size_t * nb)
+    if (on_device) then
+      dB0 = pB
+      if (c_associated(pp%obs)) then
+        rc = ndsmk_d2d(dobs, pp%obs, nb)
+      else
+        rc = ndsmk_d2d(dobs, pB, nb)
+      end if
+      if (rc /= 0) goto 900
+    else
+      dB0 = dptr_offset(buf, 4_c_size_t * nb + wk)
+      rc = ndsmk_h2d(dB0, pB, nb); if (rc /= 0) goto 900
+      if (c_associated(pp%obs)) then
+        rc = ndsmk_h2d(dobs, pp%obs, nb)
+      else
+        rc = ndsmk_d2d(dobs, dB0, nb)
+      end if
+      if (rc /= 0) goto 900
+    end if
+
+    call say("preprocess", "Descent...")
+    call c_f_pointer(pp%hist, hh, [17, int(pp%hist_rows)])
+    rc = ndsmk_preprocess_begin(dB0, dB1, dLa, dobs, dwork, n3(1:2), dq(1:2), pp%mu, pp%dt0, pp%dt_min)
+    if (rc /= 0) goto 900
+    rc = ndsmk_preprocess_row(dwork, row); if (rc /= 0) goto 900
+    if (.not. (row(20) > 0.0_wp .and. row(21) > 0.0_wp)) then
+      rc = ndsmk_note_error(NDSMK_EVALUE, "preprocess: the observation needs sum W |B|^2 > 0 and sum W r |B|^2 > 0"// &
+                            c_null_char)
+      goto 900
+    end if
+    hh(:, 1) = row(1:17)
+    rows = 1; tries = 0
+    lprev = row(2)
+    pp%info(3) = 0
+    if (row(19) /= 0.0_wp) pp%info(3) = 2
+    do while (pp%info(3) == 0 .and. tries < pp%niter_max)
+      n = min(pp%check, pp%niter_max - tries)
+      rc = ndsmk_preprocess_tries(dB0, dB1, dLa, dobs, dwork, n3(1:2), dq(1:2), pp%mu, pp%dt_min, n)
+      if (rc /= 0) goto 900
+      rc = ndsmk_preprocess_row(dwork, row); if (rc /= 0) goto 900
+      tries = tries + n
+      rows = min(rows + 1_c_int, pp%hist_rows)
+      hh(:, rows) = row(1:17)
+      if (row(19) /= 0.0_wp) then
+        pp%info(3) = 2
+      else if (n == pp%check) then
+        if (lprev - row(2) <= pp%tol * lprev) pp%info(3) = 1
+        lprev = row(2)
+      end if
+      if (pp%info(3) == 1) exit
+    end do
+    pp%info(1) = rows
+    pp%info(2) = int(row(1), c_int)
+    if (row(18) /= 0.0_wp) then
+      rc = ndsmk_d2d(dB0, dB1, nb); if (rc /= 0) goto 900
+    end if
+    if (.not. on_device) then
+      rc = ndsmk_d2h(pB, dB0, nb); if (rc /= 0) goto 900
+    end if
+    rc = ndsmk_sync()
+900 continue
+    if (rc /= 0) pp%info = 0
     call unstage(rc, [buf])
   end function
 

@@ -455,6 +455,79 @@ int ndsm_hip_vecpot_optimize_device(void *h, int ioptc[16], double ropt[16], dou
                                     int niter_max, int check, double tol, double dt0, double dt_min, double *hist,
                                     int hist_rows, int *info);
 
+/* ---- Coarse-to-fine cascade of the optimization method (DESIGN.md "Coarse-to-fine cascade") --------------------------
+ * The descent of ndsm_hip_vecpot_optimize is a local pseudo-time relaxation: long-wavelength error decays over
+ * thousands of tries on a fine grid and within a few hundred cheap ones on a coarse grid.  Production codes
+ * (Wiegelmann 2008) therefore solve on a coarser grid first, interpolate to the next finer one and go on there.
+ *
+ * Resampling between two uniform meshes that span the same box (so no coordinates are needed).  Node arrays
+ * (nx,ny,nz,ncomp); no handle.  The operator is separable: one 1-D rule along x, then y, then z, each axis by itself.
+ * With ns source and nd destination nodes on an axis, in 64-bit whole numbers:
+ *   mode 0, linear interpolation (any ns, nd >= 2): a = i (ns - 1), j = a div (nd - 1), r = a mod (nd - 1).  r = 0:
+ *     the value is v[j], copied, and no other node is read.  Otherwise theta = double(r) / double(nd - 1) and the value
+ *     is (1.0 - theta) v[j] + theta v[j + 1].
+ *   mode 1, hat average (nd <= ns on every axis): node 0 copies v[0], node nd - 1 copies v[ns - 1].  Any other node i
+ *     takes the source nodes f, ascending, whose weight q_f = (ns - 1) - |f (nd - 1) - i (ns - 1)| is > 0; its value
+ *     is (sum double(q_f) v[f]) / double(sum q_f), the sum formed left to right from its first term, sum q_f a whole
+ *     number.  A single such node is copied.  For a 2:1 nested pair this is the 1-2-1 full weighting.
+ *   An axis of one node on both sides (a plane, such as ndsm_hip_vecpot_preprocess's magnetogram) is copied.
+ * What follows: a face, edge or corner of dst depends on the same face, edge or corner of src only (the interior of src
+ * may hold anything); ns = nd gives src bit for bit; a power of two - a weight of 1 - is reproduced exactly; mode 0
+ * reproduces a function linear in x, y, z to rounding.  Deterministic: built without contraction, the operand order
+ * above is the bits.
+ *   Returns 0 or: 9001 without a GPU whatever the arguments; 9002 a NULL array or shape; 9004 ncomp < 1, a mode other
+ *   than 0 or 1, an axis with fewer than 2 nodes on either side unless both have 1, nd > ns on an axis in mode 1.  A
+ *   failed call leaves dst untouched.  src and dst must not overlap. */
+/* HOST arrays */
+int ndsm_hip_resample(const int nsrc[3], const int ndst[3], int ncomp, int mode, const double *src, double *dst);
+/* the same on DEVICE arrays of the library's GPU */
+int ndsm_hip_resample_device(const int nsrc[3], const int ndst[3], int ncomp, int mode, const double *dsrc,
+                             double *ddst);
+
+/* The cascade.  handles[0] is the handle of the finest mesh, the one B and w live on; handles[1 .. nlevels - 1] are
+ * handles the caller created on coarser meshes of the same box (level l has no more nodes per axis than level l - 1;
+ * the first and last coordinates of every axis equal the finest mesh's bit for bit: build each axis as first + k
+ * (last - first) / (n - 1) with the end put in, numpy's linspace).  L = nlevels - 1 is the coarsest level.
+ *   1. G_l = mode-1 resample of the input B, straight from the finest mesh, for l = 1 .. L; w_l = mode-0 resample of
+ *      w when w is given.  G_0 = B, w_0 = w.
+ *   2. Level L is ndsm_hip_vecpot_optimize_device on handles[L] with G_L, w_L and the caller's start: start 0 takes
+ *      the potential field of G_L's B.n with G_L's k = 0 plane put back (faces depend on faces only, so the caller
+ *      may leave the interior of B unset, as in the single-level call), start 1 starts from G_L.
+ *   3. For l = L - 1 .. 0: B_l = mode-0 resample of the finished B_{l+1}.  start 0: the k = 0 plane of all three
+ *      components is overwritten by G_l's; the side and top faces keep the interpolated values - on the finest level
+ *      they are the prolonged boundary of the coarsest mesh's potential field, NOT the finest mesh's own potential
+ *      field as in the single-level call.  start 1: all six faces are overwritten by G_l's, so the result's face
+ *      nodes are the input's bit for bit.  Then ndsm_hip_vecpot_optimize_device with start 1 on handles[l] with w_l,
+ *      niter_max[l], dt0[l], dt_min[l] and the shared check and tol.
+ *   4. B is the finest level's result.  With nlevels = 1 the call is ndsm_hip_vecpot_optimize bit for bit, in B, hist
+ *      and info.
+ *   niter_max, dt0, dt_min   (nlevels each, on the HOST) per level, index 0 the finest
+ *   hist      (nlevels, hist_rows, 6) and info (nlevels, 3), on the HOST in both entries, indexed by level; each
+ *             level's rows and info are ndsm_hip_vecpot_optimize's; rows past the written ones are untouched.  A
+ *             level that stops at dt_min (even before its first try) hands its field on like any other.
+ *   Returns 0, or 1 when the coarsest level's potential solve missed vc_tol: the options in ioptc / ropt are that
+ *   solve's, and the ngrids slot must be handles[L]'s.  >= 9001 errors, in this order: 9001 without a GPU; 9002 NULL
+ *   handles, a NULL handle among them, NULL B, niter_max, dt0, dt_min, hist or info; 9004 nlevels < 1, start not 0 /
+ *   1, a niter_max[l] < 1, check < 1, hist_rows < 2, tol, a dt0[l] or a dt_min[l] outside ndsm_hip_vecpot_optimize's
+ *   rules, a coarser level with more nodes on an axis than the next finer one, a level whose box differs from the
+ *   finest's.  A failed call clears the hist rows it was given and info; it never clears B.
+ *   Device memory: every G_l and w_l first (together about 1/7 of a fine field); the levels one after the other, each
+ *   level's buffers freed before the next finer level allocates; level 1's start is interpolated into the caller's
+ *   device B, beside which the input stands (one field) only until its faces are pasted.  The peak is
+ *   ndsm_hip_vecpot_optimize's on the finest level, and a finest grid that cannot fit is refused (9001) before any
+ *   allocation.  The host entry stages B and w once; only history rows cross PCIe in between.
+ *   Not included: z-slab worlds, a potential solve on every level, non-uniform spacing, a final
+ *   ndsm_hip_vecpot_project. */
+/* HOST arrays */
+int ndsm_hip_vecpot_optimize_cascade(void *const *handles, int nlevels, int ioptc[16], double ropt[16], double *B,
+                                     const double *w, int start, const int *niter_max, int check, double tol,
+                                     const double *dt0, const double *dt_min, double *hist, int hist_rows, int *info);
+/* the same on DEVICE arrays of the library's GPU (the per-level arrays, hist and info stay on the host) */
+int ndsm_hip_vecpot_optimize_cascade_device(void *const *handles, int nlevels, int ioptc[16], double ropt[16],
+                                            double *dB, const double *dw, int start, const int *niter_max, int check,
+                                            double tol, const double *dt0, const double *dt_min, double *hist,
+                                            int hist_rows, int *info);
+
 /* ---- Magnetogram preprocessing (DESIGN.md "Magnetogram preprocessing") ---------------------------------------------
  * What comes before ndsm_hip_vecpot_optimize when the lower-face data are measured (Wiegelmann, Inhester & Sakurai
  * 2006): a photospheric vector magnetogram is not the boundary of a force-free field - its net Maxwell force and

@@ -110,6 +110,13 @@ def load_library(path=None):
            [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p])
     L.ndsm_hip_vecpot_optimize.argtypes = _op
     L.ndsm_hip_vecpot_optimize_device.argtypes = _op
+    _oc = ([ctypes.c_void_p, ctypes.c_int, _ip, _dp] + [ctypes.c_void_p] * 2 + [ctypes.c_int, ctypes.c_void_p,
+           ctypes.c_int, ctypes.c_double] + [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p])
+    L.ndsm_hip_vecpot_optimize_cascade.argtypes = _oc
+    L.ndsm_hip_vecpot_optimize_cascade_device.argtypes = _oc
+    _rs = [_ip, _ip, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    L.ndsm_hip_resample.argtypes = _rs
+    L.ndsm_hip_resample_device.argtypes = _rs
     _pp = ([ctypes.c_void_p] * 4 + [ctypes.c_int] * 2 + [ctypes.c_double] * 3 +
            [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p])
     L.ndsm_hip_vecpot_preprocess.argtypes = _pp
@@ -698,6 +705,97 @@ class VecPot:
             _check(ierr, "ndsm_hip_vecpot_optimize", self.L)
         self.last_ioptc, self.last_ropt = ioptc, ropt
         return ierr, B.reshape(shape), hist[:int(info[0])].copy(), tuple(int(v) for v in info)
+
+    def optimize_cascade(self, coarser, b, w=None, start="potential", niter_max=10000, check=50, tol=1e-4, dt0=None,
+                         dt_min=None, hist_rows=None, niterex_max=10000, ncycles_max=1024, ex_tol=1e-13, vc_tol=1e-10,
+                         ms=5, mean=False, mixed_precision=False, flxcrl=False, device=False):
+        """optimize() as a coarse-to-fine cascade (semantics: include/ndsm_hip.h, ndsm_hip_vecpot_optimize_cascade):
+        this handle is the finest mesh, `coarser` a sequence of VecPot handles on coarser meshes of the same box, finest
+        first (cascade_shapes() proposes their shapes).  b and w live on this handle's mesh.  The hat average of b -
+        and the interpolated w - goes to every coarser level; the coarsest level runs optimize() with `start`, and
+        every finer level starts from the interpolated result of the level below with the k = 0 plane ("potential") or
+        all six faces ("given") of its own average of b put over it.  With start "potential" the side and top faces of
+        the result are therefore the prolonged boundary of the coarsest mesh's potential field, not the finest mesh's
+        own potential field as in optimize().  niter_max, dt0, dt_min: one value for every level or a sequence, one per
+        level, finest first; dt0 None: 0.1 min(h)^2 of each level's own mesh, dt_min None: 1e-6 of that level's dt0.
+        check, tol and hist_rows are shared.  Returns (ierr, B, hist, info): hist a list of per-level arrays
+        (rows, 6), info a list of per-level tuples, both as optimize() gives them; ierr 1 when the coarsest level's
+        potential solve missed vc_tol.  No coarser handle: optimize() itself, bit for bit."""
+        levels = [self] + list(coarser)
+        nl = len(levels)
+        if start not in ("potential", "given"):
+            raise ValueError(f"start must be 'potential' or 'given', not {start!r}")
+
+        def each(name, v):
+            if isinstance(v, (list, tuple, np.ndarray)):
+                if len(v) != nl:
+                    raise ValueError(f"{name} needs one value per level ({nl}), not {len(v)}")
+                return list(v)
+            return [v] * nl
+        nit, d0, dm = each("niter_max", niter_max), each("dt0", dt0), each("dt_min", dt_min)
+        for name, v in [("niter_max", v) for v in nit] + [("check", check)]:
+            if int(v) != v or v < 1:
+                raise ValueError(f"{name} must be a whole number >= 1, not {v!r}")
+        if not (tol >= 0.0 and np.isfinite(tol)):
+            raise ValueError(f"tol must be finite and >= 0, not {tol!r}")
+        for v in d0:
+            if v is not None and not (v > 0.0 and np.isfinite(v)):
+                raise ValueError(f"dt0 must be finite and > 0, not {v!r}")
+        for v in dm:
+            if v is not None and not (v >= 0.0 and np.isfinite(v)):
+                raise ValueError(f"dt_min must be finite and >= 0, not {v!r}")
+        if hist_rows is None:
+            hist_rows = -(-int(max(nit)) // int(check)) + 2
+        if int(hist_rows) != hist_rows or hist_rows < 2:
+            raise ValueError(f"hist_rows must be a whole number >= 2, not {hist_rows!r}")
+        for V in levels[1:]:
+            if not isinstance(V, VecPot):
+                raise ValueError(f"coarser must hold VecPot handles, not {type(V).__name__}")
+        for fine, V in zip(levels, levels[1:]):
+            if any(int(c) > int(f) for c, f in zip(V.nshape4[:3], fine.nshape4[:3])):
+                raise ValueError(f"a coarser level has more nodes than the level before it: {tuple(V.nshape4[:3])} "
+                                 f"after {tuple(fine.nshape4[:3])}")
+            for q, r in zip((V.x, V.y, V.z), (self.x, self.y, self.z)):
+                if q[0].tobytes() != r[0].tobytes() or q[-1].tobytes() != r[-1].tobytes():
+                    raise ValueError("every level must span the box of the finest mesh: first and last coordinates "
+                                     f"{q[0]!r}, {q[-1]!r} against {r[0]!r}, {r[-1]!r}")
+        shape = tuple(int(v) for v in self.nshape4[::-1])
+        B = self._field_arg(b, "optimize_cascade")
+        W = None
+        if w is not None:
+            W = np.asarray(w)
+            if W.shape != shape[1:]:
+                raise NdsmHipError(f"optimize_cascade: weight of shape {W.shape}, the handle's grid needs {shape[1:]} "
+                                   "(code 9002)")
+            W = _f64(W).reshape(-1).copy()
+        for l, V in enumerate(levels):
+            if d0[l] is None:
+                d0[l] = 0.1 * min(float(q[1]) - float(q[0]) for q in (V.x, V.y, V.z)) ** 2
+            if dm[l] is None:
+                dm[l] = 1e-6 * d0[l]
+        ioptc, ropt = self._options(niterex_max, ncycles_max, ex_tol, vc_tol, ms, mean, mixed_precision, flxcrl)
+        ioptc[self.L.get_iopt_ngrids()] = levels[-1].ngrids
+        handles = (ctypes.c_void_p * nl)(*[V.h for V in levels])
+        nit_a = np.array([int(v) for v in nit], dtype=np.intc)
+        d0_a, dm_a = np.array(d0, dtype=np.float64), np.array(dm, dtype=np.float64)
+        hist = np.zeros((nl, int(hist_rows), 6))
+        info = np.zeros((nl, 3), dtype=np.intc)
+
+        def call(fn, pB, pW):
+            return fn(handles, nl, ioptc.ctypes.data_as(_ip), _d(ropt), pB, pW, 0 if start == "potential" else 1,
+                      nit_a.ctypes.data, int(check), float(tol), d0_a.ctypes.data, dm_a.ctypes.data, hist.ctypes.data,
+                      int(hist_rows), info.ctypes.data)
+        if not device:
+            ierr = call(self.L.ndsm_hip_vecpot_optimize_cascade, B.ctypes.data, None if W is None else W.ctypes.data)
+        elif W is None:
+            ierr = self._on_device([B], lambda dB: call(self.L.ndsm_hip_vecpot_optimize_cascade_device, dB, None))
+        else:
+            ierr = self._on_device([B, W], lambda dB, dW: call(self.L.ndsm_hip_vecpot_optimize_cascade_device, dB, dW))
+        if ierr >= 9000:
+            _check(ierr, "ndsm_hip_vecpot_optimize_cascade", self.L)
+        self.last_ioptc, self.last_ropt = ioptc, ropt
+        return (ierr, B.reshape(shape), [hist[l, :int(info[l, 0])].copy() for l in range(nl)],
+                [tuple(int(v) for v in info[l]) for l in range(nl)])
 
     def preprocess(self, bm, obs=None, mu=(1, 1, 1e-3, 1e-2, 1e-2), niter_max=10000, check=50, tol=1e-4, dt0=None,
                    dt_min=None, hist_rows=None, device=False):
@@ -1615,6 +1713,99 @@ def force_free_optimize(x, y, z, b, w=None, start="potential", niter_max=10000, 
                           vc_tol=vc_tol, ms=ms, mean=mean, mixed_precision=mixed_precision, flxcrl=flxcrl)
     finally:
         V.close()
+
+
+RESAMPLE_MODES = {"linear": 0, "average": 1}
+
+
+def resample(a, shape, mode="linear", device=False, lib=None):
+    """A node array on a uniform mesh resampled to another uniform mesh on the same box, on the device (semantics:
+    include/ndsm_hip.h, ndsm_hip_resample).  a: (ncomp, nz, ny, nx) or (nz, ny, nx); shape: the destination
+    (nz, ny, nx).  mode "linear": linear interpolation, any two shapes; "average": the hat average (full weighting for
+    a 2:1 pair), which cannot refine.  An axis of one node on both sides is copied.  A face, edge or corner of the
+    result depends on the same face, edge or corner of a only.  device=True: the arrays are staged in device memory
+    and the device-resident entry point runs."""
+    if mode not in RESAMPLE_MODES:
+        raise ValueError(f"mode must be 'linear' or 'average', not {mode!r}")
+    src = np.asarray(a)
+    if src.ndim not in (3, 4) or src.size == 0:
+        raise NdsmHipError(f"resample: an array of shape {src.shape}, (ncomp, nz, ny, nx) or (nz, ny, nx) is needed "
+                           "(code 9002)")
+    dshape = tuple(int(v) for v in shape)
+    if len(dshape) != 3 or any(int(v) != v for v in shape):
+        raise ValueError(f"shape must be three whole numbers (nz, ny, nx), not {shape!r}")
+    ncomp = 1 if src.ndim == 3 else src.shape[0]
+    sshape = src.shape[-3:]
+    for ns, nd in zip(sshape, dshape):
+        if not ((ns == 1 and nd == 1) or (ns >= 2 and nd >= 2)):
+            raise ValueError(f"an axis needs at least 2 nodes on both sides, or 1 on both: {sshape} -> {dshape}")
+        if mode == "average" and nd > ns:
+            raise ValueError(f"the hat average cannot refine: {sshape} -> {dshape}")
+    L = lib or load_library()
+    S = _f64(src).reshape(-1).copy()
+    D = np.zeros(ncomp * int(np.prod(dshape)))
+    ns3, nd3 = np.array(sshape[::-1], dtype=np.intc), np.array(dshape[::-1], dtype=np.intc)
+    args = (ns3.ctypes.data_as(_ip), nd3.ctypes.data_as(_ip), ncomp, RESAMPLE_MODES[mode])
+    if not device:
+        _check(L.ndsm_hip_resample(*args, S.ctypes.data, D.ctypes.data), "ndsm_hip_resample", L)
+    else:
+        ptrs = []
+        try:
+            for h in (S, D):
+                p = ctypes.c_void_p()
+                _check(L.ndsm_hip_device_alloc(h.nbytes, ctypes.byref(p)), "device_alloc", L)
+                ptrs.append(p)
+            _check(L.ndsm_hip_memcpy_h2d(ptrs[0], S.ctypes.data, S.nbytes), "h2d", L)
+            _check(L.ndsm_hip_resample_device(*args, ptrs[0], ptrs[1]), "ndsm_hip_resample_device", L)
+            _check(L.ndsm_hip_memcpy_d2h(D.ctypes.data, ptrs[1], D.nbytes), "d2h", L)
+        finally:
+            for p in ptrs:
+                L.ndsm_hip_device_free(p)
+    return D.reshape(src.shape[:-3] + dshape)
+
+
+def cascade_shapes(shape, levels, min_nodes=4):
+    """The shapes (nz, ny, nx) of a cascade of that many levels, finest first: each axis follows n -> (n + 1) // 2
+    (33 -> 17, 32 -> 16, 9 -> 5); an axis that would fall below min_nodes stays where it is.  ValueError when a
+    level is asked for and no axis can shrink."""
+    if int(levels) != levels or levels < 1:
+        raise ValueError(f"levels must be a whole number >= 1, not {levels!r}")
+    out = [tuple(int(n) for n in shape)]
+    for _ in range(int(levels) - 1):
+        nxt = tuple((n + 1) // 2 if (n + 1) // 2 >= min_nodes else n for n in out[-1])
+        if nxt == out[-1]:
+            raise ValueError(f"no axis of {out[-1]} can shrink further (min_nodes {min_nodes}): "
+                             f"{len(out)} levels at the most")
+        out.append(nxt)
+    return out
+
+
+def force_free_cascade(x, y, z, b, levels=3, shapes=None, w=None, start="potential", niter_max=10000, check=50,
+                       tol=1e-4, dt0=None, dt_min=None, hist_rows=None, niterex_max=10000, ncycles_max=1024,
+                       ex_tol=1e-13, vc_tol=1e-10, ms=5, mean=False, mixed_precision=False, flxcrl=False, lib=None):
+    """Nonlinear force-free field from a vector magnetogram by the optimization method run as a coarse-to-fine
+    cascade: one-shot form of VecPot.optimize_cascade (returns its (ierr, B, hist, info)).  shapes: the (nz, ny, nx)
+    of every level, finest first (None: cascade_shapes() of b's grid for `levels`); every level's mesh is
+    linspace(first, last, n) per axis, which keeps the end coordinates exact.  Raises NdsmHipError on device /
+    argument errors."""
+    x, y, z = _f64(x), _f64(y), _f64(z)
+    if shapes is None:
+        shapes = cascade_shapes((len(z), len(y), len(x)), levels)
+    shapes = [tuple(int(n) for n in s) for s in shapes]
+    if not shapes or shapes[0] != (len(z), len(y), len(x)):
+        raise ValueError(f"shapes must start with the finest grid {(len(z), len(y), len(x))}, not {shapes[:1]}")
+    handles = []
+    try:
+        handles.append(VecPot(x, y, z, lib=lib))
+        for nz, ny, nx in shapes[1:]:
+            handles.append(VecPot(*[np.linspace(q[0], q[-1], n) for q, n in ((x, nx), (y, ny), (z, nz))], lib=lib))
+        return handles[0].optimize_cascade(handles[1:], b, w=w, start=start, niter_max=niter_max, check=check, tol=tol,
+                                           dt0=dt0, dt_min=dt_min, hist_rows=hist_rows, niterex_max=niterex_max,
+                                           ncycles_max=ncycles_max, ex_tol=ex_tol, vc_tol=vc_tol, ms=ms, mean=mean,
+                                           mixed_precision=mixed_precision, flxcrl=flxcrl)
+    finally:
+        for V in handles:
+            V.close()
 
 
 def preprocess_magnetogram(x, y, z, bm, obs=None, mu=(1, 1, 1e-3, 1e-2, 1e-2), niter_max=10000, check=50, tol=1e-4,

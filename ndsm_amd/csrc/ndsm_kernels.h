@@ -224,6 +224,14 @@ int ndsmk_optimize_tries(double *B0, double *B1, double *O, const double *w, dou
                          const double *h_dq3, double dt_min, int ntries);
 int ndsmk_optimize_row(const double *work, double *h_row8);
 
+/* The coarse-to-fine cascade's level changes (resample.hip; semantics: include/ndsm_hip.h, ndsm_hip_resample).
+ * resample: dst (ndst3, ncomp) = src (nsrc3, ncomp) resampled on the same box, mode 0 linear interpolation, mode 1 hat
+ * average (no axis of dst finer than src's); DEVICE arrays that do not overlap; 9004 for a bad ncomp, mode or shape.
+ * paste_faces: dst = src on the k = 0 plane (which = 0) or on the six faces (which = 1) of two (n3, ncomp) arrays.
+ * Both asynchronous. */
+int ndsmk_resample(const int32_t *nsrc3, const int32_t *ndst3, int ncomp, int mode, const double *src, double *dst);
+int ndsmk_paste_faces(const int32_t *n3, int ncomp, int which, const double *src, double *dst);
+
 /* Magnetogram preprocessing (preprocess.hip; semantics: include/ndsm_hip.h, ndsm_hip_vecpot_preprocess).  B0, B1
  * (nx,ny,3): the two field buffers, B0 holds the start; La (nx,ny,3,2): the two Lambda buffers; obs (nx,ny,3): the
  * observation, never written; work: ndsmk_preprocess_work_bytes() bytes, the state and the block partials; all DEVICE

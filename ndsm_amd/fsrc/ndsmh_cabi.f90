@@ -1286,6 +1286,212 @@ contains
     end if
   end function
 
+  ! Resampling of a node array between two uniform meshes on the same box (semantics in include/ndsm_hip.h).  src
+  ! (nsrc,ncomp) in, dst (ndst,ncomp) out; mode 0 linear interpolation, 1 hat average.  No handle.  HOST arrays
+  function ndsm_hip_resample(nsrc, ndst, ncomp, mode, src, dst) bind(c, name="ndsm_hip_resample") result(ierr)
+    type(c_ptr), value :: nsrc, ndst, src, dst
+    integer(c_int), value :: ncomp, mode
+    integer(c_int) :: ierr
+    ierr = resample_entry(nsrc, ndst, ncomp, mode, src, dst, .false., "ndsm_hip_resample")
+  end function
+
+  ! the same on DEVICE arrays of the library's GPU (they must not overlap)
+  function ndsm_hip_resample_device(nsrc, ndst, ncomp, mode, dsrc, ddst) bind(c, name="ndsm_hip_resample_device") &
+      result(ierr)
+    type(c_ptr), value :: nsrc, ndst, dsrc, ddst
+    integer(c_int), value :: ncomp, mode
+    integer(c_int) :: ierr
+    ierr = resample_entry(nsrc, ndst, ncomp, mode, dsrc, ddst, .true., "ndsm_hip_resample_device")
+  end function
+
+  function resample_entry(nsrc, ndst, ncomp, mode, src, dst, on_device, who) result(ierr)
+    type(c_ptr), intent(in) :: nsrc, ndst, src, dst
+    integer(c_int), intent(in) :: ncomp, mode
+    logical, intent(in) :: on_device
+    character(len=*), intent(in) :: who
+    integer(c_int) :: ierr
+    integer(c_int), pointer :: ns(:), nd(:)
+    integer(c_int32_t) :: ns3(3), nd3(3)
+    integer(c_size_t) :: bs, bd
+    type(c_ptr) :: buf, ddst
+    integer(c_int) :: rc
+    integer :: d
+    logical :: ok
+    ierr = ndsmk_init(-1_c_int)
+    if (ierr /= 0) return
+    ierr = NDSMK_EARG
+    if (.not. (c_associated(nsrc) .and. c_associated(ndst) .and. c_associated(src) .and. c_associated(dst))) return
+    call c_f_pointer(nsrc, ns, [3])
+    call c_f_pointer(ndst, nd, [3])
+    ok = ncomp >= 1 .and. (mode == 0 .or. mode == 1)
+    do d = 1, 3
+      ok = ok .and. ((ns(d) == 1 .and. nd(d) == 1) .or. (ns(d) >= 2 .and. nd(d) >= 2))
+      ok = ok .and. .not. (mode == 1 .and. nd(d) > ns(d))
+    end do
+    if (.not. ok) then
+      ierr = ndsmk_note_error(NDSMK_EVALUE, "resample: ncomp >= 1, mode 0 or 1, at least 2 nodes per axis on both "// &
+                              "sides (or 1 on both), and no axis finer than its source in mode 1"//c_null_char)
+      return
+    end if
+    ns3 = ns; nd3 = nd
+    if (on_device) then
+      rc = ndsmk_resample(ns3, nd3, ncomp, mode, src, dst)
+      if (rc == 0) rc = ndsmk_sync()
+    else
+      bs = int(product(int(ns3, c_int64_t)) * int(ncomp, c_int64_t) * 8_c_int64_t, c_size_t)
+      bd = int(product(int(nd3, c_int64_t)) * int(ncomp, c_int64_t) * 8_c_int64_t, c_size_t)
+      buf = c_null_ptr
+      rc = ndsmk_alloc(buf, bs + bd)
+      if (rc == 0) then
+        ddst = dptr_offset(buf, bs)
+        rc = ndsmk_h2d(buf, src, bs)
+        if (rc == 0) rc = ndsmk_resample(ns3, nd3, ncomp, mode, buf, ddst)
+        if (rc == 0) rc = ndsmk_d2h(dst, ddst, bd)
+        if (rc == 0) rc = ndsmk_sync()
+        d = ndsmk_free(buf)
+        if (rc == 0) rc = int(d, c_int)
+      end if
+    end if
+    ierr = reported(who, rc)
+  end function
+
+  ! The coarse-to-fine cascade of the optimization method (semantics in include/ndsm_hip.h).  handles (nlevels): the
+  ! finest mesh's handle first, then coarser meshes of the same box.  B (nx,ny,nz,3) and w (nx,ny,nz; may be NULL) on
+  ! the finest mesh, as for ndsm_hip_vecpot_optimize.  niter_max, dt0, dt_min (nlevels) per level; hist
+  ! (nlevels,hist_rows,6) and info (nlevels,3) out, on the HOST in both entries.  HOST arrays
+  function ndsm_hip_vecpot_optimize_cascade(handles, nlevels, ioptc, ropt, B, w, start, niter_max, check, tol, dt0, &
+                                            dt_min, hist, hist_rows, info) &
+      bind(c, name="ndsm_hip_vecpot_optimize_cascade") result(ierr)
+    type(c_ptr), value :: handles, B, w, niter_max, dt0, dt_min, hist, info
+    integer(c_int), intent(inout) :: ioptc(0:OPT_LEN - 1)
+    real(c_double), intent(inout) :: ropt(0:OPT_LEN - 1)
+    integer(c_int), value :: nlevels, start, check, hist_rows
+    real(c_double), value :: tol
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_cascade(handles, nlevels, ioptc, ropt, B, w, start, niter_max, check, tol, dt0, dt_min, hist, &
+                                 hist_rows, info, .false., "ndsm_hip_vecpot_optimize_cascade")
+  end function
+
+  ! the same on DEVICE arrays of the library's GPU: only history rows cross PCIe
+  function ndsm_hip_vecpot_optimize_cascade_device(handles, nlevels, ioptc, ropt, dB, dw, start, niter_max, check, tol, &
+                                                   dt0, dt_min, hist, hist_rows, info) &
+      bind(c, name="ndsm_hip_vecpot_optimize_cascade_device") result(ierr)
+    type(c_ptr), value :: handles, dB, dw, niter_max, dt0, dt_min, hist, info
+    integer(c_int), intent(inout) :: ioptc(0:OPT_LEN - 1)
+    real(c_double), intent(inout) :: ropt(0:OPT_LEN - 1)
+    integer(c_int), value :: nlevels, start, check, hist_rows
+    real(c_double), value :: tol
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_cascade(handles, nlevels, ioptc, ropt, dB, dw, start, niter_max, check, tol, dt0, dt_min, &
+                                 hist, hist_rows, info, .true., "ndsm_hip_vecpot_optimize_cascade_device")
+  end function
+
+  function vecpot_handle_cascade(handles, nlevels, ioptc, ropt, B, w, start, niter_max, check, tol, dt0, dt_min, hist, &
+                                 hist_rows, info, on_device, who) result(ierr)
+    type(c_ptr), intent(in) :: handles, B, w, niter_max, dt0, dt_min, hist, info
+    integer(c_int), intent(inout) :: ioptc(0:OPT_LEN - 1)
+    real(c_double), intent(inout) :: ropt(0:OPT_LEN - 1)
+    integer(c_int), intent(in) :: nlevels, start, check, hist_rows
+    real(c_double), intent(in) :: tol
+    logical, intent(in) :: on_device
+    character(len=*), intent(in) :: who
+    integer(c_int) :: ierr
+    type(vecpot_ref), allocatable :: lev(:)
+    type(optimize_args), allocatable :: ops(:)
+    type(c_ptr), pointer :: hs(:)
+    integer(c_int), pointer :: iout(:, :), nit(:)
+    real(c_double), pointer :: d0(:), dm(:)
+    integer(ik) :: iopt(0:OPT_LEN - 1)
+    real(c_double) :: t0
+    integer(c_int) :: rc
+    integer :: l
+    logical :: ok
+    nullify (iout)
+    if (c_associated(info) .and. nlevels >= 1) then
+      call c_f_pointer(info, iout, [3, int(nlevels)])
+      iout = 0
+    end if
+    ierr = ndsmk_init(-1_c_int)
+    if (ierr == 0 .and. .not. (c_associated(handles) .and. c_associated(B) .and. c_associated(niter_max) .and. &
+                               c_associated(dt0) .and. c_associated(dt_min) .and. c_associated(hist) .and. &
+                               c_associated(info))) ierr = NDSMK_EARG
+    if (ierr == 0 .and. nlevels >= 1) then
+      call c_f_pointer(handles, hs, [int(nlevels)])
+      allocate (lev(nlevels), ops(nlevels))
+      do l = 1, nlevels
+        if (ierr == 0) ierr = live_ctx(hs(l), lev(l)%p)
+      end do
+    end if
+    if (ierr == 0) then
+      ok = nlevels >= 1 .and. start >= 0 .and. start <= 1 .and. check >= 1 .and. hist_rows >= 2 .and. tol >= 0.0_c_double &
+           .and. tol <= huge(tol)
+      if (ok) then
+        call c_f_pointer(niter_max, nit, [int(nlevels)])
+        call c_f_pointer(dt0, d0, [int(nlevels)])
+        call c_f_pointer(dt_min, dm, [int(nlevels)])
+        do l = 1, nlevels
+          ok = ok .and. nit(l) >= 1 .and. d0(l) > 0.0_c_double .and. d0(l) <= huge(tol) .and. dm(l) >= 0.0_c_double &
+               .and. dm(l) <= huge(tol)
+        end do
+      end if
+      if (.not. ok) &
+        ierr = ndsmk_note_error(NDSMK_EVALUE, "optimize cascade: nlevels >= 1, start 0 or 1, check >= 1, hist_rows >= 2, "// &
+                                "tol >= 0, and on every level niter_max >= 1, dt0 > 0 and dt_min >= 0 (all finite)"// &
+                                c_null_char)
+    end if
+    if (ierr == 0) then
+      do l = 2, nlevels
+        ok = ok .and. all(lev(l)%p%n3 <= lev(l - 1)%p%n3) .and. same_box(lev(l)%p, lev(1)%p)
+      end do
+      if (.not. ok) &
+        ierr = ndsmk_note_error(NDSMK_EVALUE, "optimize cascade: every level spans the box of the finest mesh (the first "// &
+                                "and last coordinates are compared bit for bit) with no more nodes per axis than the "// &
+                                "level before it"//c_null_char)
+    end if
+    if (ierr == 0) then
+      do l = 1, nlevels
+        ops(l)%hist = dptr_offset(hist, int(l - 1, c_size_t) * int(hist_rows, c_size_t) * 48_c_size_t)
+        ops(l)%start = start; ops(l)%niter_max = nit(l); ops(l)%check = check; ops(l)%hist_rows = hist_rows
+        ops(l)%tol = tol; ops(l)%dt0 = d0(l); ops(l)%dt_min = dm(l)
+      end do
+      ops(1)%w = w
+      iopt = ioptc
+      verbose = (iopt(IOPT_DEBUG) == 1)
+      t0 = wall_seconds()
+      rc = NDSMK_EARG
+      if (int(iopt(IOPT_NGRIDS)) == lev(nlevels)%p%ngr) rc = vecpot_optimize_cascade(lev, iopt, ropt, B, ops, on_device)
+      ropt(ROPT_TIM) = wall_seconds() - t0
+      ioptc = int(iopt, c_int)
+      ierr = reported(who, rc)
+      if (ierr /= 0) ioptc(IOPT_IERR) = ierr            ! (as the field entries: ioptc is written by a call that ran)
+      if (ierr == 0) then
+        do l = 1, nlevels
+          iout(:, l) = ops(l)%info
+        end do
+        ierr = int(iopt(IOPT_IERR), c_int)
+      end if
+    end if
+    if (ierr >= NDSMK_ENODEV) then
+      if (associated(iout)) iout = 0
+      if (c_associated(hist) .and. hist_rows >= 1 .and. nlevels >= 1) &
+        call clear_host([hist], [48], [int(hist_rows, c_int64_t) * int(nlevels, c_int64_t)])
+    end if
+  contains
+    ! the first and the last node of every axis, bit for bit
+    function same_box(a, b) result(yes)
+      type(vecpot_ctx), intent(in) :: a, b
+      logical :: yes
+      yes = same_bits(a%qx(1), b%qx(1)) .and. same_bits(a%qx(size(a%qx)), b%qx(size(b%qx))) .and. &
+            same_bits(a%qy(1), b%qy(1)) .and. same_bits(a%qy(size(a%qy)), b%qy(size(b%qy))) .and. &
+            same_bits(a%qz(1), b%qz(1)) .and. same_bits(a%qz(size(a%qz)), b%qz(size(b%qz)))
+    end function
+    function same_bits(u, v) result(yes)
+      real(c_double), intent(in) :: u, v
+      logical :: yes
+      yes = transfer(u, 0_c_int64_t) == transfer(v, 0_c_int64_t)
+    end function
+  end function
+
   ! Magnetogram preprocessing (semantics in include/ndsm_hip.h).  B (nx,ny,3) in: the magnetogram on the handle's
   ! lower face; out: the preprocessed one.  obs (nx,ny,3) in, may be NULL (the input B).  mu (5) in.  hist (hist_rows,17)
   ! and info (3 ints) out, on the HOST in both entries.  HOST arrays

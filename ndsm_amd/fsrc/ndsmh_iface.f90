@@ -611,6 +611,21 @@ module ndsmh_iface
       real(c_double), intent(out) :: row8(8)
       integer(c_int) :: rc
     end function
+    ! ---- the cascade's level changes (resample.hip) ----
+    function ndsmk_resample(nsrc3, ndst3, ncomp, mode, src, dst) bind(c, name="ndsmk_resample") result(rc)
+      import :: c_ptr, c_int, c_int32_t
+      integer(c_int32_t), intent(in) :: nsrc3(3), ndst3(3)
+      integer(c_int), value :: ncomp, mode
+      type(c_ptr), value :: src, dst
+      integer(c_int) :: rc
+    end function
+    function ndsmk_paste_faces(n3, ncomp, which, src, dst) bind(c, name="ndsmk_paste_faces") result(rc)
+      import :: c_ptr, c_int, c_int32_t
+      integer(c_int32_t), intent(in) :: n3(3)
+      integer(c_int), value :: ncomp, which
+      type(c_ptr), value :: src, dst
+      integer(c_int) :: rc
+    end function
     ! ---- magnetogram preprocessing (preprocess.hip) ----
     function ndsmk_preprocess_work_bytes() bind(c, name="ndsmk_preprocess_work_bytes") result(nb)
       import :: c_size_t

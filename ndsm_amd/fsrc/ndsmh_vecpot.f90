@@ -33,6 +33,7 @@ module ndsmh_vecpot
   public :: vecpot_solve, poisson_solve
   public :: vecpot_ctx, vecpot_ctx_create, vecpot_ctx_destroy, vecpot_ctx_matches, vecpot_run, vecpot_cache_drop
   public :: vecpot_alpha_map, vecpot_nlfff, nlfff_args, vecpot_optimize, optimize_args, vecpot_preprocess, preprocess_args
+  public :: vecpot_optimize_cascade, vecpot_ref
   public :: vecpot_project, vecpot_devore, vecpot_lines, vecpot_paths, vecpot_nulls, vecpot_skeleton, vecpot_separators
   public :: VP_POTENTIAL, VP_FIELD, VP_HELICITY, VP_CURRENT, VP_NLFFF
   ! pieces the distributed driver (ndsmh_wvecpot) shares with vecpot_solve
@@ -121,6 +122,11 @@ module ndsmh_vecpot
     integer(c_int) :: start = 0, niter_max = 1, check = 1, hist_rows = 2
     real(wp) :: tol = 0, dt0 = 0, dt_min = 0
     integer(c_int) :: info(3) = 0
+  end type
+
+  ! one level of a cascade (vecpot_optimize_cascade): a context somebody else owns
+  type :: vecpot_ref
+    type(vecpot_ctx), pointer :: p => null()
   end type
 
   ! what a preprocessing call takes besides B (vecpot_preprocess): obs (nx,ny,3) in, on the side B is on, may be
@@ -1576,6 +1582,123 @@ contains
 900 continue
     if (rc /= 0) op%info = 0
     call unstage(rc, [buf])
+  end function
+
+  ! ------------------------------------------------------------------
+  ! The coarse-to-fine cascade of the optimization method (semantics in include/ndsm_hip.h, DESIGN.md "Coarse-to-fine
+  ! cascade").  lev(1) is the finest context - pB and ops(1)%w live on its mesh, on the HOST (both go up once, B comes
+  ! home once) or (on_device) in HBM -, lev(2:) the coarser ones on the same box; ops(l) carries level l's niter_max,
+  ! dt0, dt_min and history (HOST), its w and start are set here.  One level is vecpot_optimize itself.  Otherwise:
+  ! G_l = the hat average of the input B and w_l = the interpolated w on every coarser level, straight from the finest;
+  ! the coarsest level runs from G_L with the caller's start; every finer level starts from the interpolated result of
+  ! the level below with the k = 0 plane (start 0) or the six faces (start 1) of G_l pasted over it.  Level 1's start
+  ! is interpolated into the caller's device B, whose input stands beside it only until the faces are pasted: each
+  ! level's buffers are freed before the next finer level allocates, so the peak is vecpot_optimize's on the finest.
+  ! iopt, ropt: the options and results of the coarsest level's potential solve.
+  ! ------------------------------------------------------------------
+  function vecpot_optimize_cascade(lev, iopt, ropt, pB, ops, on_device) result(rc)
+    type(vecpot_ref), intent(in) :: lev(:)
+    integer(ik), intent(inout) :: iopt(0:OPT_LEN - 1)
+    real(wp), intent(inout) :: ropt(0:OPT_LEN - 1)
+    type(c_ptr), intent(in) :: pB
+    type(optimize_args), intent(inout) :: ops(:)
+    logical, intent(in) :: on_device
+    integer(c_int) :: rc
+    integer(c_int32_t) :: n3(3, size(lev))
+    integer(c_size_t) :: nb(size(lev)), wk, fr, tot
+    integer(ik) :: iopt1(0:OPT_LEN - 1)
+    real(wp) :: ropt1(0:OPT_LEN - 1)
+    type(c_ptr) :: gb(size(lev)), bb(size(lev)), stage, keep, dB, dw, dcur, dprev
+    integer(c_int) :: start
+    integer :: l, nl
+    logical :: has_w
+
+    nl = size(lev)
+    start = ops(1)%start
+    if (nl == 1) then
+      rc = vecpot_optimize(lev(1)%p, iopt, ropt, pB, ops(1), on_device)
+      return
+    end if
+    gb = c_null_ptr; bb = c_null_ptr; stage = c_null_ptr; keep = c_null_ptr
+    has_w = c_associated(ops(1)%w)
+    do l = 1, nl
+      ops(l)%info = 0
+      n3(:, l) = lev(l)%p%n3
+      nb(l) = int(product(int(n3(:, l), ik)), c_size_t) * 8_c_size_t
+    end do
+    ! the finest level's call, the largest by far, is vecpot_optimize's 13 level-1 arrays
+    wk = ndsmk_optimize_work_bytes()
+    rc = ndsmk_mem_info(fr, tot); if (rc /= 0) return
+    if (real(nb(1), wp) * 13.0_wp + real(wk, wp) > real(tot, wp)) then
+      rc = ndsmk_note_error(NDSMK_ENODEV, "the grid needs more device memory than the device has"//c_null_char)
+      return
+    end if
+    if (on_device) then
+      dB = pB; dw = ops(1)%w
+    else
+      rc = ndsmk_alloc(stage, merge(4_c_size_t, 3_c_size_t, has_w) * nb(1)); if (rc /= 0) goto 900
+      dB = stage
+      rc = ndsmk_h2d(dB, pB, 3_c_size_t * nb(1)); if (rc /= 0) goto 900
+      dw = c_null_ptr
+      if (has_w) then
+        dw = dptr_offset(stage, 3_c_size_t * nb(1))
+        rc = ndsmk_h2d(dw, ops(1)%w, nb(1)); if (rc /= 0) goto 900
+      end if
+    end if
+
+    call say("optimize", "Cascade: level data...")
+    do l = 2, nl
+      rc = ndsmk_alloc(gb(l), merge(4_c_size_t, 3_c_size_t, has_w) * nb(l)); if (rc /= 0) goto 900
+      rc = ndsmk_resample(n3(:, 1), n3(:, l), 3_c_int, 1_c_int, dB, gb(l)); if (rc /= 0) goto 900
+      ops(l)%w = c_null_ptr
+      if (has_w) then
+        ops(l)%w = dptr_offset(gb(l), 3_c_size_t * nb(l))
+        rc = ndsmk_resample(n3(:, 1), n3(:, l), 1_c_int, 0_c_int, dw, ops(l)%w); if (rc /= 0) goto 900
+      end if
+    end do
+
+    ! the coarsest level: G_L is its start field (start 1) or carries its magnetogram and B.n (start 0)
+    ops(nl)%start = start
+    rc = vecpot_optimize(lev(nl)%p, iopt, ropt, gb(nl), ops(nl), .true.); if (rc /= 0) goto 900
+    dprev = gb(nl)
+    do l = nl - 1, 1, -1
+      if (l > 1) then
+        rc = ndsmk_alloc(bb(l), 3_c_size_t * nb(l)); if (rc /= 0) goto 900
+        dcur = bb(l)
+        rc = ndsmk_resample(n3(:, l + 1), n3(:, l), 3_c_int, 0_c_int, dprev, dcur); if (rc /= 0) goto 900
+        rc = ndsmk_paste_faces(n3(:, l), 3_c_int, start, gb(l), dcur); if (rc /= 0) goto 900
+      else
+        ! G_0 is the input itself: it stands aside while level 1's start is interpolated into the caller's array
+        rc = ndsmk_alloc(keep, 3_c_size_t * nb(1)); if (rc /= 0) goto 900
+        rc = ndsmk_d2d(keep, dB, 3_c_size_t * nb(1)); if (rc /= 0) goto 900
+        dcur = dB
+        rc = ndsmk_resample(n3(:, 2), n3(:, 1), 3_c_int, 0_c_int, dprev, dcur); if (rc /= 0) goto 900
+        rc = ndsmk_paste_faces(n3(:, 1), 3_c_int, start, keep, dcur); if (rc /= 0) goto 900
+      end if
+      rc = ndsmk_sync(); if (rc /= 0) goto 900
+      ! the level below is done with: its buffers go before this level's call allocates
+      call unstage(rc, [keep, bb(l + 1), gb(l + 1)])
+      keep = c_null_ptr; bb(l + 1) = c_null_ptr; gb(l + 1) = c_null_ptr
+      if (rc /= 0) goto 900
+      if (l == 1) ops(1)%w = dw
+      ops(l)%start = 1
+      iopt1 = iopt; ropt1 = ropt
+      rc = vecpot_optimize(lev(l)%p, iopt1, ropt1, dcur, ops(l), .true.); if (rc /= 0) goto 900
+      dprev = dcur
+    end do
+    if (.not. on_device) then
+      rc = ndsmk_d2h(pB, dB, 3_c_size_t * nb(1)); if (rc /= 0) goto 900
+    end if
+    rc = ndsmk_sync()
+900 continue
+    if (rc /= 0) then
+      do l = 1, nl
+        ops(l)%info = 0
+      end do
+    end if
+    call unstage(rc, [keep, stage])
+    call unstage(rc, gb)
+    call unstage(rc, bb)
   end function
 
   ! ------------------------------------------------------------------

@@ -455,6 +455,54 @@ int ndsm_hip_vecpot_optimize_device(void *h, int ioptc[16], double ropt[16], dou
                                     int niter_max, int check, double tol, double dt0, double dt_min, double *hist,
                                     int hist_rows, int *info);
 
+/* ---- Measurement errors and a freed lower face (DESIGN.md "Measurement errors and a freed lower face") --------------
+ * ndsm_hip_vecpot_optimize holds the lower face at whatever the caller puts there: the 2004 form of the method.  Since
+ * Wiegelmann & Inhester (2010) and Wiegelmann et al. (2012) a measured magnetogram is fitted within its errors instead:
+ * the functional gets a surface term on the k = 0 plane and that plane moves with the descent,
+ *   L = (L_f + L_d) + nu L_m,   L_m = sum over ALL nodes of the k = 0 plane of
+ *                                     W2 ((wm_x dx^2 + wm_y dy^2) + wm_z dz^2),   d = B(k = 0) - Bobs,
+ * W2 the trapezoid weight of the plane (no z factor); every node of the plane adds, whatever |B| is.  Everything not
+ * said here - the mesh, the differences, W, w, Omega, P, s, F~, the try, the decision, the stop rules, start, info - is
+ * exactly as in ndsm_hip_vecpot_optimize above.
+ *   Bobs      (nx,ny,3) in: the observation, the layout of ndsm_hip_vecpot_preprocess's B.  Only the target of the fit:
+ *             the start field is built from B alone (start 0: the potential field of the input's B.n with the k = 0
+ *             plane of the INPUT B put back).  Never written.
+ *   wm        (nx,ny,3) in, or NULL for 1 everywhere: the confidence in each component at each pixel
+ *             (ndsm_amd.measurement_weight builds the usual one: 1 for the vertical component, |B_t| / max |B_t| for the
+ *             transverse ones)
+ *   nu        >= 0, the weight of L_m in L
+ *   free      1: the nodes of the k = 0 plane with 1 <= i <= nx - 2 and 1 <= j <= ny - 2 move,  T = B + dt H,
+ *               H = (F~ + c G) - c (nu (wm (B - Bobs)))   per component,   c = 2 / h_z,
+ *             F~ evaluated at the face node with the difference rows as they are there (centred in x and y, 3-point
+ *             one-sided in z, for curl_h P, grad_h s and grad_h w alike), G = w (-P_y, P_x, -s) the surface term
+ *             w (P x n + s n) of the variation for n = -z (w = 1 without a weight array).  2 / h_z is the node's
+ *             surface weight over its volume weight: the face runs in the same pseudo-time as the interior.  H is the
+ *             consistent discretisation of the continuum gradient, not the exact gradient of the discrete L (DESIGN.md
+ *             gives the measured difference).  The rim of the plane (i = 0, nx - 1 or j = 0, ny - 1) belongs to the side
+ *             faces: it and the five other faces are held, bit for bit.
+ *             0: the whole plane is held and L_m is only reported; with nu = 0 the call is then
+ *             ndsm_hip_vecpot_optimize bit for bit, in B, info and the columns of hist they share.
+ *   hist      (hist_rows >= 2 rows of 7 doubles, on the HOST in both entries): [tries, L, L_f, L_d, L_m, dt, accepted];
+ *             L is formed as (L_f + L_d) + nu L_m by the thread that decides, so the identity holds exactly.  Rows and
+ *             info as in ndsm_hip_vecpot_optimize.  Deterministic sums, no atomics: the same input gives the same bits.
+ *   Returns 0; 1 when a solve of start 0 missed vc_tol; >= 9001 errors: 9001 without a GPU whatever the arguments, 9002
+ *   a NULL handle, B, Bobs, hist or info, 9004 ndsm_hip_vecpot_optimize's and: free not 0 / 1, nu negative or not
+ *   finite.  A failed call clears hist and info, never B.
+ *   Device memory: ndsm_hip_vecpot_optimize's (the state is 48 KiB); the host entry stages the two planes as well,
+ *   once.  A grid that cannot fit is refused (9001) before any allocation.  Not included: the cascade with this term
+ *   (it needs Bobs and wm per level), separate weights for L_f and L_d, freed side and top faces, z-slab worlds,
+ *   non-uniform spacing. */
+/* HOST arrays */
+int ndsm_hip_vecpot_optimize_obs(void *h, int ioptc[16], double ropt[16], double *B, const double *w,
+                                 const double *Bobs, const double *wm, double nu, int free, int start, int niter_max,
+                                 int check, double tol, double dt0, double dt_min, double *hist, int hist_rows,
+                                 int *info);
+/* the same on DEVICE arrays of the library's GPU (hist and info stay on the host) */
+int ndsm_hip_vecpot_optimize_obs_device(void *h, int ioptc[16], double ropt[16], double *dB, const double *dw,
+                                        const double *dBobs, const double *dwm, double nu, int free, int start,
+                                        int niter_max, int check, double tol, double dt0, double dt_min, double *hist,
+                                        int hist_rows, int *info);
+
 /* ---- Coarse-to-fine cascade of the optimization method (DESIGN.md "Coarse-to-fine cascade") --------------------------
  * The descent of ndsm_hip_vecpot_optimize is a local pseudo-time relaxation: long-wavelength error decays over
  * thousands of tries on a fine grid and within a few hundred cheap ones on a coarse grid.  Production codes

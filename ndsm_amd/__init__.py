@@ -14,7 +14,8 @@ from ._lib import (load_library, lib_path, MGSolver, VecPot, World, slab_plan, p
                    path_of, whole_line, Skeleton, find_skeleton, spine_of, fan_of, connections, Separators,
                    find_separators, separator_of, QPerpMap, perpendicular_squashing, seed_cut, boundary_alpha,
                    map_alpha, vector_potential_current, force_free_field, boundary_weight, force_free_optimize,
-                   preprocess_magnetogram, magnetogram_balance, resample, cascade_shapes, force_free_cascade)
+                   preprocess_magnetogram, magnetogram_balance, resample, cascade_shapes, force_free_cascade,
+                   measurement_weight, force_free_optimize_obs)
 
 __all__ = ["vector_potential", "vector_potential_slab", "get_lib_path", "load_library", "lib_path", "MGSolver", "VecPot", "poisson_solve",
            "NdsmHipError", "Helicity", "vector_potential_field", "relative_helicity", "Projection", "solenoidal_projection",
@@ -23,4 +24,5 @@ __all__ = ["vector_potential", "vector_potential_slab", "get_lib_path", "load_li
            "Skeleton", "find_skeleton", "spine_of", "fan_of", "connections", "Separators", "find_separators",
            "separator_of", "QPerpMap", "perpendicular_squashing", "seed_cut", "boundary_alpha", "map_alpha",
            "vector_potential_current", "force_free_field", "boundary_weight", "force_free_optimize",
-           "preprocess_magnetogram", "magnetogram_balance", "resample", "cascade_shapes", "force_free_cascade"]
+           "preprocess_magnetogram", "magnetogram_balance", "resample", "cascade_shapes", "force_free_cascade",
+           "measurement_weight", "force_free_optimize_obs"]

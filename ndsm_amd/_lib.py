@@ -110,6 +110,10 @@ def load_library(path=None):
            [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p])
     L.ndsm_hip_vecpot_optimize.argtypes = _op
     L.ndsm_hip_vecpot_optimize_device.argtypes = _op
+    _ob = ([ctypes.c_void_p, _ip, _dp] + [ctypes.c_void_p] * 4 + [ctypes.c_double] + [ctypes.c_int] * 4 +
+           [ctypes.c_double] * 3 + [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p])
+    L.ndsm_hip_vecpot_optimize_obs.argtypes = _ob
+    L.ndsm_hip_vecpot_optimize_obs_device.argtypes = _ob
     _oc = ([ctypes.c_void_p, ctypes.c_int, _ip, _dp] + [ctypes.c_void_p] * 2 + [ctypes.c_int, ctypes.c_void_p,
            ctypes.c_int, ctypes.c_double] + [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p])
     L.ndsm_hip_vecpot_optimize_cascade.argtypes = _oc
@@ -703,6 +707,87 @@ class VecPot:
                 self.h, ioptc.ctypes.data_as(_ip), _d(ropt), dB, dW, *args))
         if ierr >= 9000:
             _check(ierr, "ndsm_hip_vecpot_optimize", self.L)
+        self.last_ioptc, self.last_ropt = ioptc, ropt
+        return ierr, B.reshape(shape), hist[:int(info[0])].copy(), tuple(int(v) for v in info)
+
+    def optimize_obs(self, b, bobs=None, wm=None, nu=0.01, free=True, w=None, start="potential", niter_max=10000,
+                     check=50, tol=1e-4, dt0=None, dt_min=None, hist_rows=None, niterex_max=10000, ncycles_max=1024,
+                     ex_tol=1e-13, vc_tol=1e-10, ms=5, mean=False, mixed_precision=False, flxcrl=False, device=False):
+        """optimize() with the lower face fitted to a measured magnetogram within its errors (Wiegelmann & Inhester
+        2010; semantics: include/ndsm_hip.h, ndsm_hip_vecpot_optimize_obs): L = (L_f + L_d) + nu L_m with
+        L_m = sum W2 wm (B(k = 0) - bobs)^2 over the lower face, and with free=True that face - except its rim, which
+        belongs to the side faces - moves with the descent.  bobs (3,ny,nx): the observation, None for a copy of b's
+        k = 0 plane; it is only the target of the fit, the start field is built from b as in optimize().  wm (3,ny,nx):
+        the confidence per pixel and component, None for 1 everywhere (measurement_weight() builds the usual one).
+        nu >= 0: the weight of L_m.  free=False holds the face and only reports L_m; with nu = 0 that is optimize()
+        bit for bit.  Everything else as optimize().  Returns (ierr, B, hist, info): hist (rows, 7) = [tries, L, L_f,
+        L_d, L_m, dt, accepted].  device=True: the arrays are staged in device memory and the device-resident entry
+        point runs."""
+        if start not in ("potential", "given"):
+            raise ValueError(f"start must be 'potential' or 'given', not {start!r}")
+        if free not in (True, False, 0, 1):
+            raise ValueError(f"free must be True or False, not {free!r}")
+        if not (nu >= 0.0 and np.isfinite(nu)):
+            raise ValueError(f"nu must be finite and >= 0, not {nu!r}")
+        for name, v in (("niter_max", niter_max), ("check", check)):
+            if int(v) != v or v < 1:
+                raise ValueError(f"{name} must be a whole number >= 1, not {v!r}")
+        if not (tol >= 0.0 and np.isfinite(tol)):
+            raise ValueError(f"tol must be finite and >= 0, not {tol!r}")
+        if dt0 is not None and not (dt0 > 0.0 and np.isfinite(dt0)):
+            raise ValueError(f"dt0 must be finite and > 0, not {dt0!r}")
+        if dt_min is not None and not (dt_min >= 0.0 and np.isfinite(dt_min)):
+            raise ValueError(f"dt_min must be finite and >= 0, not {dt_min!r}")
+        if hist_rows is None:
+            hist_rows = -(-int(niter_max) // int(check)) + 2
+        if int(hist_rows) != hist_rows or hist_rows < 2:
+            raise ValueError(f"hist_rows must be a whole number >= 2, not {hist_rows!r}")
+        shape = tuple(int(v) for v in self.nshape4[::-1])
+        B = self._field_arg(b, "optimize_obs")
+        W = None
+        if w is not None:
+            W = np.asarray(w)
+            if W.shape != shape[1:]:
+                raise NdsmHipError(f"optimize_obs: weight of shape {W.shape}, the handle's grid needs {shape[1:]} "
+                                   "(code 9002)")
+            W = _f64(W).reshape(-1).copy()
+        pshape = (3,) + shape[2:]
+        planes = []
+        for name, v in (("observation", bobs), ("measurement weight", wm)):
+            if v is None:
+                planes.append(None)
+                continue
+            a = np.asarray(v)
+            if a.shape != pshape:
+                raise NdsmHipError(f"optimize_obs: {name} of shape {a.shape}, the handle's lower face needs {pshape} "
+                                   "(code 9002)")
+            planes.append(_f64(a).reshape(-1).copy())
+        if planes[0] is None:
+            planes[0] = B.reshape(shape)[:, 0].reshape(-1).copy()
+        if dt0 is None:
+            dt0 = 0.1 * min(float(q[1]) - float(q[0]) for q in (self.x, self.y, self.z)) ** 2
+        if dt_min is None:
+            dt_min = 1e-6 * dt0
+        ioptc, ropt = self._options(niterex_max, ncycles_max, ex_tol, vc_tol, ms, mean, mixed_precision, flxcrl)
+        hist = np.zeros((int(hist_rows), 7))
+        info = np.zeros(3, dtype=np.intc)
+        args = (float(nu), int(bool(free)), 0 if start == "potential" else 1, int(niter_max), int(check), float(tol),
+                float(dt0), float(dt_min), hist.ctypes.data, int(hist_rows), info.ctypes.data)
+        arrays = [B, W] + planes
+        if not device:
+            ierr = self.L.ndsm_hip_vecpot_optimize_obs(self.h, ioptc.ctypes.data_as(_ip), _d(ropt),
+                                                       *[None if a is None else a.ctypes.data for a in arrays], *args)
+        else:
+            given = [a for a in arrays if a is not None]
+
+            def call(*dev):
+                it = iter(dev)
+                ptrs = [None if a is None else next(it) for a in arrays]
+                return self.L.ndsm_hip_vecpot_optimize_obs_device(self.h, ioptc.ctypes.data_as(_ip), _d(ropt), *ptrs,
+                                                                  *args)
+            ierr = self._on_device(given, call)
+        if ierr >= 9000:
+            _check(ierr, "ndsm_hip_vecpot_optimize_obs", self.L)
         self.last_ioptc, self.last_ropt = ioptc, ropt
         return ierr, B.reshape(shape), hist[:int(info[0])].copy(), tuple(int(v) for v in info)
 
@@ -1711,6 +1796,39 @@ def force_free_optimize(x, y, z, b, w=None, start="potential", niter_max=10000, 
         return V.optimize(b, w=w, start=start, niter_max=niter_max, check=check, tol=tol, dt0=dt0, dt_min=dt_min,
                           hist_rows=hist_rows, niterex_max=niterex_max, ncycles_max=ncycles_max, ex_tol=ex_tol,
                           vc_tol=vc_tol, ms=ms, mean=mean, mixed_precision=mixed_precision, flxcrl=flxcrl)
+    finally:
+        V.close()
+
+
+def measurement_weight(bobs, floor=0.0):
+    """The confidence wm (3,ny,nx) of optimize_obs() for an observed magnetogram bobs (3,ny,nx), the usual choice for
+    HMI data: 1 for the vertical component, and for both transverse components max(|B_t| / max |B_t|, floor) with
+    |B_t| = sqrt(Bx^2 + By^2) - the transverse field is known far worse than the vertical one, and weak-field pixels
+    hardly at all.  An all-zero transverse field gives `floor`.  0 <= floor <= 1.  Plain numpy."""
+    a = np.asarray(bobs, dtype=np.float64)
+    if a.ndim != 3 or a.shape[0] != 3:
+        raise ValueError(f"bobs must have the shape (3, ny, nx), not {a.shape}")
+    if not (0.0 <= floor <= 1.0):
+        raise ValueError(f"floor must lie in [0, 1], not {floor!r}")
+    bt = np.sqrt(a[0] * a[0] + a[1] * a[1])
+    top = bt.max() if bt.size else 0.0
+    t = np.maximum(bt / top, floor) if top > 0.0 else np.full(bt.shape, float(floor))
+    return np.array([t, t, np.ones(bt.shape)])
+
+
+def force_free_optimize_obs(x, y, z, b, bobs=None, wm=None, nu=0.01, free=True, w=None, start="potential",
+                            niter_max=10000, check=50, tol=1e-4, dt0=None, dt_min=None, hist_rows=None,
+                            niterex_max=10000, ncycles_max=1024, ex_tol=1e-13, vc_tol=1e-10, ms=5, mean=False,
+                            mixed_precision=False, flxcrl=False, ngrids=0, lib=None):
+    """Nonlinear force-free field whose lower face is fitted to the measured magnetogram bobs within its errors wm:
+    one-shot form of VecPot.optimize_obs (returns its (ierr, B, hist, info)).  Raises NdsmHipError on device / runtime
+    failures (>= 9001)."""
+    V = _grid_handle(x, y, z, b, ngrids, lib)
+    try:
+        return V.optimize_obs(b, bobs=bobs, wm=wm, nu=nu, free=free, w=w, start=start, niter_max=niter_max,
+                              check=check, tol=tol, dt0=dt0, dt_min=dt_min, hist_rows=hist_rows,
+                              niterex_max=niterex_max, ncycles_max=ncycles_max, ex_tol=ex_tol, vc_tol=vc_tol, ms=ms,
+                              mean=mean, mixed_precision=mixed_precision, flxcrl=flxcrl)
     finally:
         V.close()
 

@@ -224,6 +224,21 @@ int ndsmk_optimize_tries(double *B0, double *B1, double *O, const double *w, dou
                          const double *h_dq3, double dt_min, int ntries);
 int ndsmk_optimize_row(const double *work, double *h_row8);
 
+/* The same with a measurement term and a freed lower face (optimize_obs.hip; semantics: include/ndsm_hip.h,
+ * ndsm_hip_vecpot_optimize_obs).  B0, B1, O, w as above; Bobs (nx,ny,3): the observation on the k = 0 plane, never
+ * written; wm (nx,ny,3) or NULL (1 everywhere); work: ndsmk_optimize_obs_work_bytes() bytes; all DEVICE arrays.  nu >=
+ * 0 the weight of L_m in L; free 1: the nodes of the k = 0 plane off its rim move, 0: they are held.  begin, tries:
+ * asynchronous, as above.  row: blocking, h_row9 (host) = [tries, L, L_f, L_d, L_m, dt, accepted, the index of the
+ * buffer that holds the current field, 1 once dt < dt_min]. */
+size_t ndsmk_optimize_obs_work_bytes(void);
+int ndsmk_optimize_obs_begin(double *B0, double *B1, double *O, const double *w, const double *Bobs, const double *wm,
+                             double *work, const int32_t *n3, const double *h_dq3, double nu, double dt0,
+                             double dt_min);
+int ndsmk_optimize_obs_tries(double *B0, double *B1, double *O, const double *w, const double *Bobs, const double *wm,
+                             double *work, const int32_t *n3, const double *h_dq3, double nu, int free, double dt_min,
+                             int ntries);
+int ndsmk_optimize_obs_row(const double *work, double *h_row9);
+
 /* The coarse-to-fine cascade's level changes (resample.hip; semantics: include/ndsm_hip.h, ndsm_hip_resample).
  * resample: dst (ndst3, ncomp) = src (nsrc3, ncomp) resampled on the same box, mode 0 linear interpolation, mode 1 hat
  * average (no axis of dst finer than src's); DEVICE arrays that do not overlap; 9004 for a bad ncomp, mode or shape.

@@ -18,10 +18,14 @@
 // iteration in numpy bit for bit.
 #include "common.hpp"
 #include "diffq.hpp"
+#include "optimize_ps.hpp"
 
 namespace {
 
+using ndsm::dcen;
 using ndsm::ddq;
+using ndsm::PS;
+using ndsm::ps_at;
 using ndsm::trap_w;
 
 constexpr int kOptBlock = 256;        // kHelBlock of field.hip
@@ -36,31 +40,6 @@ struct OptArgs {
   double dq[3];
   size_t nrows;   // ny * nz
 };
-
-// ddq's centred row on two values that are not in an array
-__device__ __forceinline__ double dcen(double vm, double vp, double h) {
-  const double half = 0.5;
-  double d = 0.0;
-  d = d + vm * (-1 * half / h);
-  d = d + vp * (+1 * half / h);
-  return d;
-}
-
-struct PS {
-  double px, py, pz, s;
-};
-
-// P = Omega x B and s = Omega.B at node c
-__device__ __forceinline__ PS ps_at(const double *__restrict__ B, const double *__restrict__ O, size_t c, size_t N) {
-  const double bx = B[c], by = B[c + N], bz = B[c + 2 * N];
-  const double ox = O[c], oy = O[c + N], oz = O[c + 2 * N];
-  PS r;
-  r.px = oy * bz - oz * by;
-  r.py = oz * bx - ox * bz;
-  r.pz = ox * by - oy * bx;
-  r.s = (ox * bx + oy * by) + oz * bz;
-  return r;
-}
 
 // which = 0: Omega and the sums of the current field (the start); which = 1: of the trial field
 __global__ __launch_bounds__(kOptBlock) void opt_omega_k(const double *__restrict__ B0, const double *__restrict__ B1,

@@ -611,6 +611,36 @@ module ndsmh_iface
       real(c_double), intent(out) :: row8(8)
       integer(c_int) :: rc
     end function
+    ! ---- the same with a measurement term and a freed lower face (optimize_obs.hip) ----
+    function ndsmk_optimize_obs_work_bytes() bind(c, name="ndsmk_optimize_obs_work_bytes") result(nb)
+      import :: c_size_t
+      integer(c_size_t) :: nb
+    end function
+    function ndsmk_optimize_obs_begin(B0, B1, O, w, Bobs, wm, work, n3, dq3, nu, dt0, dt_min) &
+        bind(c, name="ndsmk_optimize_obs_begin") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_double
+      type(c_ptr), value :: B0, B1, O, w, Bobs, wm, work
+      integer(c_int32_t), intent(in) :: n3(3)
+      real(c_double), intent(in) :: dq3(3)
+      real(c_double), value :: nu, dt0, dt_min
+      integer(c_int) :: rc
+    end function
+    function ndsmk_optimize_obs_tries(B0, B1, O, w, Bobs, wm, work, n3, dq3, nu, free, dt_min, ntries) &
+        bind(c, name="ndsmk_optimize_obs_tries") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_double
+      type(c_ptr), value :: B0, B1, O, w, Bobs, wm, work
+      integer(c_int32_t), intent(in) :: n3(3)
+      real(c_double), intent(in) :: dq3(3)
+      real(c_double), value :: nu, dt_min
+      integer(c_int), value :: free, ntries
+      integer(c_int) :: rc
+    end function
+    function ndsmk_optimize_obs_row(work, row9) bind(c, name="ndsmk_optimize_obs_row") result(rc)
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: work
+      real(c_double), intent(out) :: row9(9)
+      integer(c_int) :: rc
+    end function
     ! ---- the cascade's level changes (resample.hip) ----
     function ndsmk_resample(nsrc3, ndst3, ncomp, mode, src, dst) bind(c, name="ndsmk_resample") result(rc)
       import :: c_ptr, c_int, c_int32_t

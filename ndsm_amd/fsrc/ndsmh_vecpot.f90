@@ -33,7 +33,7 @@ module ndsmh_vecpot
   public :: vecpot_solve, poisson_solve
   public :: vecpot_ctx, vecpot_ctx_create, vecpot_ctx_destroy, vecpot_ctx_matches, vecpot_run, vecpot_cache_drop
   public :: vecpot_alpha_map, vecpot_nlfff, nlfff_args, vecpot_optimize, optimize_args, vecpot_preprocess, preprocess_args
-  public :: vecpot_optimize_cascade, vecpot_ref
+  public :: vecpot_optimize_cascade, vecpot_ref, vecpot_optimize_obs, optimize_obs_args
   public :: vecpot_project, vecpot_devore, vecpot_lines, vecpot_paths, vecpot_nulls, vecpot_skeleton, vecpot_separators
   public :: VP_POTENTIAL, VP_FIELD, VP_HELICITY, VP_CURRENT, VP_NLFFF
   ! pieces the distributed driver (ndsmh_wvecpot) shares with vecpot_solve
@@ -121,6 +121,16 @@ module ndsmh_vecpot
     type(c_ptr) :: w = c_null_ptr, hist = c_null_ptr
     integer(c_int) :: start = 0, niter_max = 1, check = 1, hist_rows = 2
     real(wp) :: tol = 0, dt0 = 0, dt_min = 0
+    integer(c_int) :: info(3) = 0
+  end type
+
+  ! the same for vecpot_optimize_obs: bobs (nx,ny,3) in, the observation on the k = 0 plane, and wm (nx,ny,3) in, its
+  ! per-component confidence, may be c_null_ptr (1 everywhere), both on the side B is on; nu the weight of L_m in L;
+  ! free 1: the lower face moves, 0: it is held; hist (7,hist_rows) on the HOST
+  type :: optimize_obs_args
+    type(c_ptr) :: w = c_null_ptr, bobs = c_null_ptr, wm = c_null_ptr, hist = c_null_ptr
+    integer(c_int) :: start = 0, free = 1, niter_max = 1, check = 1, hist_rows = 2
+    real(wp) :: nu = 0, tol = 0, dt0 = 0, dt_min = 0
     integer(c_int) :: info(3) = 0
   end type
 
@@ -1494,9 +1504,9 @@ contains
     real(wp) :: dq(3), lo(3), row(8), lprev
     real(wp), pointer :: hh(:, :)
     integer(c_int32_t) :: n3(3)
-    integer(c_size_t) :: nb, wk, total, fr, tot, plane
+    integer(c_size_t) :: nb, wk, total, fr, tot
     integer(c_int) :: rows, tries, n
-    integer :: c, k
+    integer :: k
     type(c_ptr) :: buf, dB0, dB1, dO, dwork, dw
 
     op%info = 0
@@ -1530,21 +1540,7 @@ contains
       end if
     end if
 
-    if (op%start == 0) then
-      call say("optimize", "Potential start field...")
-      rc = ndsmk_d2d(dB1, dB0, 3_c_size_t * nb); if (rc /= 0) goto 900        ! (the magnetogram comes back from here)
-      rc = ndsmk_fill0(dO, 3_c_size_t * nb); if (rc /= 0) goto 900            ! A: a zero guess, in Omega 0's place
-      rc = ndsmk_sync(); if (rc /= 0) goto 900
-      rc = vecpot_run(ctx, iopt, ropt, dO, dB0, .true., VP_POTENTIAL); if (rc /= 0) goto 900
-      iopt(IOPT_IERR) = merge(1_ik, 0_ik, iopt(IOPT_IERR) /= 0 .or. iopt(IOPT_FAIL3D) /= 0)
-      plane = int(n3(1), c_size_t) * int(n3(2), c_size_t) * 8_c_size_t
-      do c = 0, 2
-        rc = ndsmk_d2d(dptr_offset(dB0, int(c, c_size_t) * nb), dptr_offset(dB1, int(c, c_size_t) * nb), plane)
-        if (rc /= 0) goto 900
-      end do
-    else
-      iopt(IOPT_IERR) = 0
-    end if
+    rc = optimize_start(ctx, iopt, ropt, op%start, dB0, dB1, dO, n3, nb); if (rc /= 0) goto 900
 
     call say("optimize", "Descent...")
     call c_f_pointer(op%hist, hh, [6, int(op%hist_rows)])
@@ -1573,6 +1569,149 @@ contains
     op%info(1) = rows
     op%info(2) = int(row(1), c_int)
     if (row(7) /= 0.0_wp) then
+      rc = ndsmk_d2d(dB0, dB1, 3_c_size_t * nb); if (rc /= 0) goto 900
+    end if
+    if (.not. on_device) then
+      rc = ndsmk_d2h(pB, dB0, 3_c_size_t * nb); if (rc /= 0) goto 900
+    end if
+    rc = ndsmk_sync()
+900 continue
+    if (rc /= 0) op%info = 0
+    call unstage(rc, [buf])
+  end function
+
+  ! The start field of an optimization-method call, in dB0 (DEVICE).  start = 1: the input as it is.  start = 0: the
+  ! potential field of the input's B.n with the input's k = 0 plane put back; dB1 keeps the input meanwhile and dO
+  ! (Omega 0's place) holds the zero guess of A.  iopt(IOPT_IERR) = 1 when a solve missed vc_tol, else 0.
+  function optimize_start(ctx, iopt, ropt, start, dB0, dB1, dO, n3, nb) result(rc)
+    type(vecpot_ctx), intent(inout), target :: ctx
+    integer(ik), intent(inout) :: iopt(0:OPT_LEN - 1)
+    real(wp), intent(inout) :: ropt(0:OPT_LEN - 1)
+    integer(c_int), intent(in) :: start
+    type(c_ptr), intent(in) :: dB0, dB1, dO
+    integer(c_int32_t), intent(in) :: n3(3)
+    integer(c_size_t), intent(in) :: nb
+    integer(c_int) :: rc
+    integer(c_size_t) :: plane
+    integer :: c
+    rc = 0
+    if (start /= 0) then
+      iopt(IOPT_IERR) = 0
+      return
+    end if
+    call say("optimize", "Potential start field...")
+    rc = ndsmk_d2d(dB1, dB0, 3_c_size_t * nb); if (rc /= 0) return            ! (the magnetogram comes back from here)
+    rc = ndsmk_fill0(dO, 3_c_size_t * nb); if (rc /= 0) return                ! A: a zero guess, in Omega 0's place
+    rc = ndsmk_sync(); if (rc /= 0) return
+    rc = vecpot_run(ctx, iopt, ropt, dO, dB0, .true., VP_POTENTIAL); if (rc /= 0) return
+    iopt(IOPT_IERR) = merge(1_ik, 0_ik, iopt(IOPT_IERR) /= 0 .or. iopt(IOPT_FAIL3D) /= 0)
+    plane = int(n3(1), c_size_t) * int(n3(2), c_size_t) * 8_c_size_t
+    do c = 0, 2
+      rc = ndsmk_d2d(dptr_offset(dB0, int(c, c_size_t) * nb), dptr_offset(dB1, int(c, c_size_t) * nb), plane)
+      if (rc /= 0) return
+    end do
+  end function
+
+  ! ------------------------------------------------------------------
+  ! The optimization method with a measurement term and a freed lower face (semantics in include/ndsm_hip.h, DESIGN.md
+  ! "Measurement errors and a freed lower face").  vecpot_optimize with op%bobs (nx,ny,3) and op%wm (nx,ny,3; may be
+  ! c_null_ptr) on the side B is on: the host entry stages the two planes once, behind B and w.  The start field is
+  ! vecpot_optimize's, on B alone; the kernels are optimize_obs.hip's.  op%hist rows have 7 entries.
+  ! ------------------------------------------------------------------
+  function vecpot_optimize_obs(ctx, iopt, ropt, pB, op, on_device) result(rc)
+    type(vecpot_ctx), intent(inout), target :: ctx
+    integer(ik), intent(inout) :: iopt(0:OPT_LEN - 1)
+    real(wp), intent(inout) :: ropt(0:OPT_LEN - 1)
+    type(c_ptr), intent(in) :: pB
+    type(optimize_obs_args), intent(inout) :: op
+    logical, intent(in) :: on_device
+    integer(c_int) :: rc
+    real(wp) :: dq(3), lo(3), row(9), lprev
+    real(wp), pointer :: hh(:, :)
+    integer(c_int32_t) :: n3(3)
+    integer(c_size_t) :: nb, pl3, wk, total, fr, tot, at
+    integer(c_int) :: rows, tries, n
+    integer :: k
+    type(c_ptr) :: buf, dB0, dB1, dO, dwork, dw, dbobs, dwm
+
+    op%info = 0
+    buf = c_null_ptr
+    call ctx_mesh(ctx, n3, lo, dq)
+    nb = int(product(int(n3, ik)), c_size_t) * 8_c_size_t
+    pl3 = int(n3(1), c_size_t) * int(n3(2), c_size_t) * 24_c_size_t            ! a plane of three components
+    wk = ndsmk_optimize_obs_work_bytes()
+    ! vecpot_optimize's 13 level-1 arrays (a potential start adds the hierarchy: at least five), and the two planes
+    k = 13 + merge(5, 0, op%start == 0 .and. .not. ctx%live3)
+    rc = ndsmk_mem_info(fr, tot); if (rc /= 0) return
+    if (real(nb, wp) * real(k, wp) + 2.0_wp * real(pl3, wp) + real(wk, wp) > real(tot, wp)) then
+      rc = ndsmk_note_error(NDSMK_ENODEV, "the grid needs more device memory than the device has"//c_null_char)
+      return
+    end if
+    ! [B1 | Omega 0, Omega 1 | work], and for the host entry [B0 | w | Bobs | wm]
+    total = 9_c_size_t * nb + wk
+    if (.not. on_device) then
+      total = total + merge(4_c_size_t, 3_c_size_t, c_associated(op%w)) * nb
+      total = total + merge(2_c_size_t, 1_c_size_t, c_associated(op%wm)) * pl3
+    end if
+    rc = ndsmk_alloc(buf, total); if (rc /= 0) return
+    dB1 = buf
+    dO = dptr_offset(buf, 3_c_size_t * nb)
+    dwork = dptr_offset(buf, 9_c_size_t * nb)
+    if (on_device) then
+      dB0 = pB; dw = op%w; dbobs = op%bobs; dwm = op%wm
+    else
+      ! (the work area's size is a multiple of 8 bytes, so every array behind it is aligned as a double)
+      at = 9_c_size_t * nb + wk
+      dB0 = dptr_offset(buf, at)
+      rc = ndsmk_h2d(dB0, pB, 3_c_size_t * nb); if (rc /= 0) goto 900
+      at = at + 3_c_size_t * nb
+      dw = c_null_ptr
+      if (c_associated(op%w)) then
+        dw = dptr_offset(buf, at)
+        rc = ndsmk_h2d(dw, op%w, nb); if (rc /= 0) goto 900
+        at = at + nb
+      end if
+      dbobs = dptr_offset(buf, at)
+      rc = ndsmk_h2d(dbobs, op%bobs, pl3); if (rc /= 0) goto 900
+      at = at + pl3
+      dwm = c_null_ptr
+      if (c_associated(op%wm)) then
+        dwm = dptr_offset(buf, at)
+        rc = ndsmk_h2d(dwm, op%wm, pl3); if (rc /= 0) goto 900
+      end if
+    end if
+
+    rc = optimize_start(ctx, iopt, ropt, op%start, dB0, dB1, dO, n3, nb); if (rc /= 0) goto 900
+
+    call say("optimize_obs", "Descent...")
+    call c_f_pointer(op%hist, hh, [7, int(op%hist_rows)])
+    rc = ndsmk_optimize_obs_begin(dB0, dB1, dO, dw, dbobs, dwm, dwork, n3, dq, op%nu, op%dt0, op%dt_min)
+    if (rc /= 0) goto 900
+    rc = ndsmk_optimize_obs_row(dwork, row); if (rc /= 0) goto 900
+    hh(:, 1) = row(1:7)
+    rows = 1; tries = 0
+    lprev = row(2)
+    op%info(3) = 0
+    if (row(9) /= 0.0_wp) op%info(3) = 2
+    do while (op%info(3) == 0 .and. tries < op%niter_max)
+      n = min(op%check, op%niter_max - tries)
+      rc = ndsmk_optimize_obs_tries(dB0, dB1, dO, dw, dbobs, dwm, dwork, n3, dq, op%nu, op%free, op%dt_min, n)
+      if (rc /= 0) goto 900
+      rc = ndsmk_optimize_obs_row(dwork, row); if (rc /= 0) goto 900
+      tries = tries + n
+      rows = min(rows + 1_c_int, op%hist_rows)
+      hh(:, rows) = row(1:7)
+      if (row(9) /= 0.0_wp) then
+        op%info(3) = 2
+      else if (n == op%check) then
+        if (lprev - row(2) <= op%tol * lprev) op%info(3) = 1
+        lprev = row(2)
+      end if
+      if (op%info(3) == 1) exit
+    end do
+    op%info(1) = rows
+    op%info(2) = int(row(1), c_int)
+    if (row(8) /= 0.0_wp) then
       rc = ndsmk_d2d(dB0, dB1, 3_c_size_t * nb); if (rc /= 0) goto 900
     end if
     if (.not. on_device) then

@@ -648,6 +648,10 @@ class VecPot:
         return (ierr, A.reshape(shape), B.reshape(shape), alpha.reshape(shape[1:]), status.reshape(shape[1:]),
                 hist[:niter.value].copy())
 
+    def _dt0_default(self):
+        """the default first step of optimize() on this handle's mesh: 0.1 min(h)^2"""
+        return 0.1 * min(float(q[1]) - float(q[0]) for q in (self.x, self.y, self.z)) ** 2
+
     def optimize(self, b, w=None, start="potential", niter_max=10000, check=50, tol=1e-4, dt0=None, dt_min=None,
                  hist_rows=None, niterex_max=10000, ncycles_max=1024, ex_tol=1e-13, vc_tol=1e-10, ms=5, mean=False,
                  mixed_precision=False, flxcrl=False, device=False):
@@ -666,19 +670,7 @@ class VecPot:
         device-resident entry point runs."""
         if start not in ("potential", "given"):
             raise ValueError(f"start must be 'potential' or 'given', not {start!r}")
-        for name, v in (("niter_max", niter_max), ("check", check)):
-            if int(v) != v or v < 1:
-                raise ValueError(f"{name} must be a whole number >= 1, not {v!r}")
-        if not (tol >= 0.0 and np.isfinite(tol)):
-            raise ValueError(f"tol must be finite and >= 0, not {tol!r}")
-        if dt0 is not None and not (dt0 > 0.0 and np.isfinite(dt0)):
-            raise ValueError(f"dt0 must be finite and > 0, not {dt0!r}")
-        if dt_min is not None and not (dt_min >= 0.0 and np.isfinite(dt_min)):
-            raise ValueError(f"dt_min must be finite and >= 0, not {dt_min!r}")
-        if hist_rows is None:
-            hist_rows = -(-int(niter_max) // int(check)) + 2
-        if int(hist_rows) != hist_rows or hist_rows < 2:
-            raise ValueError(f"hist_rows must be a whole number >= 2, not {hist_rows!r}")
+        hist_rows, hist, info = _descent_options([niter_max], check, tol, [dt0], [dt_min], hist_rows, 6)
         shape = tuple(int(v) for v in self.nshape4[::-1])
         B = self._field_arg(b, "optimize")
         W = None
@@ -687,13 +679,8 @@ class VecPot:
             if W.shape != shape[1:]:
                 raise NdsmHipError(f"optimize: weight of shape {W.shape}, the handle's grid needs {shape[1:]} (code 9002)")
             W = _f64(W).reshape(-1).copy()
-        if dt0 is None:
-            dt0 = 0.1 * min(float(q[1]) - float(q[0]) for q in (self.x, self.y, self.z)) ** 2
-        if dt_min is None:
-            dt_min = 1e-6 * dt0
+        dt0, dt_min = _descent_steps(dt0, dt_min, self._dt0_default())
         ioptc, ropt = self._options(niterex_max, ncycles_max, ex_tol, vc_tol, ms, mean, mixed_precision, flxcrl)
-        hist = np.zeros((int(hist_rows), 6))
-        info = np.zeros(3, dtype=np.intc)
         args = (0 if start == "potential" else 1, int(niter_max), int(check), float(tol), float(dt0), float(dt_min),
                 hist.ctypes.data, int(hist_rows), info.ctypes.data)
         if not device:
@@ -708,7 +695,7 @@ class VecPot:
         if ierr >= 9000:
             _check(ierr, "ndsm_hip_vecpot_optimize", self.L)
         self.last_ioptc, self.last_ropt = ioptc, ropt
-        return ierr, B.reshape(shape), hist[:int(info[0])].copy(), tuple(int(v) for v in info)
+        return (ierr, B.reshape(shape)) + _descent_result(hist, info)
 
     def optimize_obs(self, b, bobs=None, wm=None, nu=0.01, free=True, w=None, start="potential", niter_max=10000,
                      check=50, tol=1e-4, dt0=None, dt_min=None, hist_rows=None, niterex_max=10000, ncycles_max=1024,
@@ -729,19 +716,7 @@ class VecPot:
             raise ValueError(f"free must be True or False, not {free!r}")
         if not (nu >= 0.0 and np.isfinite(nu)):
             raise ValueError(f"nu must be finite and >= 0, not {nu!r}")
-        for name, v in (("niter_max", niter_max), ("check", check)):
-            if int(v) != v or v < 1:
-                raise ValueError(f"{name} must be a whole number >= 1, not {v!r}")
-        if not (tol >= 0.0 and np.isfinite(tol)):
-            raise ValueError(f"tol must be finite and >= 0, not {tol!r}")
-        if dt0 is not None and not (dt0 > 0.0 and np.isfinite(dt0)):
-            raise ValueError(f"dt0 must be finite and > 0, not {dt0!r}")
-        if dt_min is not None and not (dt_min >= 0.0 and np.isfinite(dt_min)):
-            raise ValueError(f"dt_min must be finite and >= 0, not {dt_min!r}")
-        if hist_rows is None:
-            hist_rows = -(-int(niter_max) // int(check)) + 2
-        if int(hist_rows) != hist_rows or hist_rows < 2:
-            raise ValueError(f"hist_rows must be a whole number >= 2, not {hist_rows!r}")
+        hist_rows, hist, info = _descent_options([niter_max], check, tol, [dt0], [dt_min], hist_rows, 7)
         shape = tuple(int(v) for v in self.nshape4[::-1])
         B = self._field_arg(b, "optimize_obs")
         W = None
@@ -764,13 +739,8 @@ class VecPot:
             planes.append(_f64(a).reshape(-1).copy())
         if planes[0] is None:
             planes[0] = B.reshape(shape)[:, 0].reshape(-1).copy()
-        if dt0 is None:
-            dt0 = 0.1 * min(float(q[1]) - float(q[0]) for q in (self.x, self.y, self.z)) ** 2
-        if dt_min is None:
-            dt_min = 1e-6 * dt0
+        dt0, dt_min = _descent_steps(dt0, dt_min, self._dt0_default())
         ioptc, ropt = self._options(niterex_max, ncycles_max, ex_tol, vc_tol, ms, mean, mixed_precision, flxcrl)
-        hist = np.zeros((int(hist_rows), 7))
-        info = np.zeros(3, dtype=np.intc)
         args = (float(nu), int(bool(free)), 0 if start == "potential" else 1, int(niter_max), int(check), float(tol),
                 float(dt0), float(dt_min), hist.ctypes.data, int(hist_rows), info.ctypes.data)
         arrays = [B, W] + planes
@@ -789,7 +759,7 @@ class VecPot:
         if ierr >= 9000:
             _check(ierr, "ndsm_hip_vecpot_optimize_obs", self.L)
         self.last_ioptc, self.last_ropt = ioptc, ropt
-        return ierr, B.reshape(shape), hist[:int(info[0])].copy(), tuple(int(v) for v in info)
+        return (ierr, B.reshape(shape)) + _descent_result(hist, info)
 
     def optimize_cascade(self, coarser, b, w=None, start="potential", niter_max=10000, check=50, tol=1e-4, dt0=None,
                          dt_min=None, hist_rows=None, niterex_max=10000, ncycles_max=1024, ex_tol=1e-13, vc_tol=1e-10,
@@ -818,21 +788,7 @@ class VecPot:
                 return list(v)
             return [v] * nl
         nit, d0, dm = each("niter_max", niter_max), each("dt0", dt0), each("dt_min", dt_min)
-        for name, v in [("niter_max", v) for v in nit] + [("check", check)]:
-            if int(v) != v or v < 1:
-                raise ValueError(f"{name} must be a whole number >= 1, not {v!r}")
-        if not (tol >= 0.0 and np.isfinite(tol)):
-            raise ValueError(f"tol must be finite and >= 0, not {tol!r}")
-        for v in d0:
-            if v is not None and not (v > 0.0 and np.isfinite(v)):
-                raise ValueError(f"dt0 must be finite and > 0, not {v!r}")
-        for v in dm:
-            if v is not None and not (v >= 0.0 and np.isfinite(v)):
-                raise ValueError(f"dt_min must be finite and >= 0, not {v!r}")
-        if hist_rows is None:
-            hist_rows = -(-int(max(nit)) // int(check)) + 2
-        if int(hist_rows) != hist_rows or hist_rows < 2:
-            raise ValueError(f"hist_rows must be a whole number >= 2, not {hist_rows!r}")
+        hist_rows, hist, info = _descent_options(nit, check, tol, d0, dm, hist_rows, 6, nl)
         for V in levels[1:]:
             if not isinstance(V, VecPot):
                 raise ValueError(f"coarser must hold VecPot handles, not {type(V).__name__}")
@@ -854,17 +810,12 @@ class VecPot:
                                    "(code 9002)")
             W = _f64(W).reshape(-1).copy()
         for l, V in enumerate(levels):
-            if d0[l] is None:
-                d0[l] = 0.1 * min(float(q[1]) - float(q[0]) for q in (V.x, V.y, V.z)) ** 2
-            if dm[l] is None:
-                dm[l] = 1e-6 * d0[l]
+            d0[l], dm[l] = _descent_steps(d0[l], dm[l], V._dt0_default())
         ioptc, ropt = self._options(niterex_max, ncycles_max, ex_tol, vc_tol, ms, mean, mixed_precision, flxcrl)
         ioptc[self.L.get_iopt_ngrids()] = levels[-1].ngrids
         handles = (ctypes.c_void_p * nl)(*[V.h for V in levels])
         nit_a = np.array([int(v) for v in nit], dtype=np.intc)
         d0_a, dm_a = np.array(d0, dtype=np.float64), np.array(dm, dtype=np.float64)
-        hist = np.zeros((nl, int(hist_rows), 6))
-        info = np.zeros((nl, 3), dtype=np.intc)
 
         def call(fn, pB, pW):
             return fn(handles, nl, ioptc.ctypes.data_as(_ip), _d(ropt), pB, pW, 0 if start == "potential" else 1,
@@ -879,8 +830,8 @@ class VecPot:
         if ierr >= 9000:
             _check(ierr, "ndsm_hip_vecpot_optimize_cascade", self.L)
         self.last_ioptc, self.last_ropt = ioptc, ropt
-        return (ierr, B.reshape(shape), [hist[l, :int(info[l, 0])].copy() for l in range(nl)],
-                [tuple(int(v) for v in info[l]) for l in range(nl)])
+        per_level = [_descent_result(hist[l], info[l]) for l in range(nl)]
+        return ierr, B.reshape(shape), [h for h, _ in per_level], [i for _, i in per_level]
 
     def preprocess(self, bm, obs=None, mu=(1, 1, 1e-3, 1e-2, 1e-2), niter_max=10000, check=50, tol=1e-4, dt0=None,
                    dt_min=None, hist_rows=None, device=False):
@@ -899,19 +850,7 @@ class VecPot:
         stop reason: 0 niter_max, 1 tol, 2 dt_min).  Nothing of the handle changes; the caller puts Bm on the k = 0
         plane of the b handed to optimize().  device=True: the arrays are staged in device memory and the
         device-resident entry point runs."""
-        for name, v in (("niter_max", niter_max), ("check", check)):
-            if int(v) != v or v < 1:
-                raise ValueError(f"{name} must be a whole number >= 1, not {v!r}")
-        if not (tol >= 0.0 and np.isfinite(tol)):
-            raise ValueError(f"tol must be finite and >= 0, not {tol!r}")
-        if dt0 is not None and not (dt0 > 0.0 and np.isfinite(dt0)):
-            raise ValueError(f"dt0 must be finite and > 0, not {dt0!r}")
-        if dt_min is not None and not (dt_min >= 0.0 and np.isfinite(dt_min)):
-            raise ValueError(f"dt_min must be finite and >= 0, not {dt_min!r}")
-        if hist_rows is None:
-            hist_rows = -(-int(niter_max) // int(check)) + 2
-        if int(hist_rows) != hist_rows or hist_rows < 2:
-            raise ValueError(f"hist_rows must be a whole number >= 2, not {hist_rows!r}")
+        hist_rows, hist, info = _descent_options([niter_max], check, tol, [dt0], [dt_min], hist_rows, 17)
         muv = np.array(mu, dtype=np.float64).reshape(-1)
         if muv.size != 5 or not (np.isfinite(muv).all() and (muv >= 0.0).all()):
             raise ValueError(f"mu must be five finite numbers >= 0, not {mu!r}")
@@ -926,12 +865,7 @@ class VecPot:
                                    "(code 9002)")
             arrays.append(_f64(a).reshape(-1).copy())
         B = arrays[0]
-        if dt0 is None:
-            dt0 = 0.01
-        if dt_min is None:
-            dt_min = 1e-6 * dt0
-        hist = np.zeros((int(hist_rows), 17))
-        info = np.zeros(3, dtype=np.intc)
+        dt0, dt_min = _descent_steps(dt0, dt_min, 0.01)
         args = (muv.ctypes.data, int(niter_max), int(check), float(tol), float(dt0), float(dt_min), hist.ctypes.data,
                 int(hist_rows), info.ctypes.data)
         if not device:
@@ -942,7 +876,7 @@ class VecPot:
         else:
             ierr = self._on_device(arrays, lambda dB, dO: self.L.ndsm_hip_vecpot_preprocess_device(self.h, dB, dO, *args))
         _check(ierr, "ndsm_hip_vecpot_preprocess", self.L)
-        return ierr, B.reshape(shape), hist[:int(info[0])].copy(), tuple(int(v) for v in info)
+        return (ierr, B.reshape(shape)) + _descent_result(hist, info)
 
     def paths(self, b, seeds, g=None, step=0.5, max_steps=None, direction="both", every=1, max_points=None,
               values=True, device=False):
@@ -1328,6 +1262,44 @@ def _with_capacity(run, cap, count_only=False):
         cap = total
         total, arrays = run(cap)
     return min(total, cap), arrays
+
+
+def _descent_options(niter_max, check, tol, dt0, dt_min, hist_rows, width, nlevels=None):
+    """The options every descent (optimize, optimize_obs, optimize_cascade, preprocess) shares, checked: niter_max, dt0
+    and dt_min are lists, one entry per level (a dt0 or dt_min of None is left for _descent_steps).  Returns (hist_rows
+    - None: one row per check of the longest level and two more -, hist, info): the zeroed buffers of the call, hist
+    (hist_rows, width) and info (3), with nlevels a leading axis of that length on both."""
+    for name, v in [("niter_max", v) for v in niter_max] + [("check", check)]:
+        if int(v) != v or v < 1:
+            raise ValueError(f"{name} must be a whole number >= 1, not {v!r}")
+    if not (tol >= 0.0 and np.isfinite(tol)):
+        raise ValueError(f"tol must be finite and >= 0, not {tol!r}")
+    for v in dt0:
+        if v is not None and not (v > 0.0 and np.isfinite(v)):
+            raise ValueError(f"dt0 must be finite and > 0, not {v!r}")
+    for v in dt_min:
+        if v is not None and not (v >= 0.0 and np.isfinite(v)):
+            raise ValueError(f"dt_min must be finite and >= 0, not {v!r}")
+    if hist_rows is None:
+        hist_rows = -(-int(max(niter_max)) // int(check)) + 2
+    if int(hist_rows) != hist_rows or hist_rows < 2:
+        raise ValueError(f"hist_rows must be a whole number >= 2, not {hist_rows!r}")
+    lead = () if nlevels is None else (nlevels,)
+    return hist_rows, np.zeros(lead + (int(hist_rows), width)), np.zeros(lead + (3,), dtype=np.intc)
+
+
+def _descent_steps(dt0, dt_min, dt0_default):
+    """the first and the smallest step with their defaults: dt0_default, 1e-6 dt0"""
+    if dt0 is None:
+        dt0 = dt0_default
+    if dt_min is None:
+        dt_min = 1e-6 * dt0
+    return dt0, dt_min
+
+
+def _descent_result(hist, info):
+    """(the written rows of hist, info as a tuple of ints) of one descent"""
+    return hist[:int(info[0])].copy(), tuple(int(v) for v in info)
 
 
 def _helicity_tuple(ierr, out, A, Ap, Bp):

@@ -15,7 +15,7 @@
 //              reconstruction error and the two divergences (15 arrays, 120 B/pt).  Deterministic: every
 //              block sums a fixed set of grid rows in a fixed order, one block then sums the block
 //              partials in a fixed order; the grid size depends on the shape alone.
-#include "common.hpp"
+#include "descent.hpp"
 #include "diffq.hpp"
 
 namespace {
@@ -61,8 +61,8 @@ __global__ __launch_bounds__(256) void current_rhs_k(const double *__restrict__ 
   rhs[c] = alpha ? -(alpha[c] * F[c]) : -F[c];
 }
 
-constexpr int kHelBlock = 256;
-constexpr int kHelMaxBlocks = 2048;   // 256 CUs x 8 blocks; rows beyond that are strided
+constexpr int kHelBlock = ndsm::kRedBlock;           // descent.hpp's reduction: block_part, block_final
+constexpr int kHelMaxBlocks = ndsm::kRedMaxBlocks;
 constexpr int kHelVals = 9;           // 6 sums, 3 maxima
 constexpr int kHelSums = 6;
 
@@ -118,38 +118,15 @@ __global__ __launch_bounds__(kHelBlock) void helicity_part_k(const double *__res
       v[8] = fmax(v[8], fabs(diva));
     }
   }
-  for (int q = 0; q < kHelVals; ++q) sh[q][t] = v[q];
-  __syncthreads();
-  for (int o = kHelBlock / 2; o > 0; o >>= 1) {
-    if (t < o)
-      for (int q = 0; q < kHelVals; ++q)
-        sh[q][t] = q < kHelSums ? sh[q][t] + sh[q][t + o] : fmax(sh[q][t], sh[q][t + o]);
-    __syncthreads();
-  }
-  if (t < kHelVals) part[(size_t)blockIdx.x * kHelVals + t] = sh[t][0];
+  ndsm::block_part<kHelVals, kHelSums>(sh, v, part);
 }
 
-// one block: thread t folds the partials of blocks t, t + 256, ... in that order, then the same halving tree
+// one block: descent.hpp's fold (thread t: the partials of blocks t, t + 256, ... in that order) and halving tree
 __global__ __launch_bounds__(kHelBlock) void helicity_final_k(const double *__restrict__ part, int nb,
                                                              double *__restrict__ out) {
   __shared__ double sh[kHelVals][kHelBlock];
-  const int t = threadIdx.x;
-  double v[kHelVals];
-  for (int q = 0; q < kHelVals; ++q) v[q] = 0.0;
-  for (int b = t; b < nb; b += kHelBlock)
-    for (int q = 0; q < kHelVals; ++q) {
-      const double x = part[(size_t)b * kHelVals + q];
-      v[q] = q < kHelSums ? v[q] + x : fmax(v[q], x);
-    }
-  for (int q = 0; q < kHelVals; ++q) sh[q][t] = v[q];
-  __syncthreads();
-  for (int o = kHelBlock / 2; o > 0; o >>= 1) {
-    if (t < o)
-      for (int q = 0; q < kHelVals; ++q)
-        sh[q][t] = q < kHelSums ? sh[q][t] + sh[q][t + o] : fmax(sh[q][t], sh[q][t + o]);
-    __syncthreads();
-  }
-  if (t < kHelVals) out[t] = sh[t][0];
+  ndsm::block_final<kHelVals, kHelSums>(sh, part, nb);
+  if (threadIdx.x < kHelVals) out[threadIdx.x] = sh[threadIdx.x][0];
 }
 
 constexpr int kNlVals = 5;            // 4 sums, 1 maximum
@@ -194,38 +171,15 @@ __global__ __launch_bounds__(kHelBlock) void nlfff_part_k(const double *__restri
       v[4] = fmax(v[4], em);
     }
   }
-  for (int q = 0; q < kNlVals; ++q) sh[q][t] = v[q];
-  __syncthreads();
-  for (int o = kHelBlock / 2; o > 0; o >>= 1) {
-    if (t < o)
-      for (int q = 0; q < kNlVals; ++q)
-        sh[q][t] = q < kNlSums ? sh[q][t] + sh[q][t + o] : fmax(sh[q][t], sh[q][t + o]);
-    __syncthreads();
-  }
-  if (t < kNlVals) part[(size_t)blockIdx.x * kNlVals + t] = sh[t][0];
+  ndsm::block_part<kNlVals, kNlSums>(sh, v, part);
 }
 
 // one block: helicity_final_k's fold and tree over the partials of nlfff_part_k
 __global__ __launch_bounds__(kHelBlock) void nlfff_final_k(const double *__restrict__ part, int nb,
                                                           double *__restrict__ out) {
   __shared__ double sh[kNlVals][kHelBlock];
-  const int t = threadIdx.x;
-  double v[kNlVals];
-  for (int q = 0; q < kNlVals; ++q) v[q] = 0.0;
-  for (int b = t; b < nb; b += kHelBlock)
-    for (int q = 0; q < kNlVals; ++q) {
-      const double x = part[(size_t)b * kNlVals + q];
-      v[q] = q < kNlSums ? v[q] + x : fmax(v[q], x);
-    }
-  for (int q = 0; q < kNlVals; ++q) sh[q][t] = v[q];
-  __syncthreads();
-  for (int o = kHelBlock / 2; o > 0; o >>= 1) {
-    if (t < o)
-      for (int q = 0; q < kNlVals; ++q)
-        sh[q][t] = q < kNlSums ? sh[q][t] + sh[q][t + o] : fmax(sh[q][t], sh[q][t + o]);
-    __syncthreads();
-  }
-  if (t < kNlVals) out[t] = sh[t][0];
+  ndsm::block_final<kNlVals, kNlSums>(sh, part, nb);
+  if (threadIdx.x < kNlVals) out[threadIdx.x] = sh[threadIdx.x][0];
 }
 
 struct HelScratch {
@@ -301,7 +255,7 @@ extern "C" int ndsmk_helicity_reduce(const double *A, const double *Ap, const do
     p.dq[d] = h_dq3[d];
   }
   p.nrows = (size_t)n3[1] * (size_t)n3[2];
-  const int nb = (int)(p.nrows < (size_t)kHelMaxBlocks ? p.nrows : (size_t)kHelMaxBlocks);
+  const int nb = ndsm::red_blocks(p.nrows);
   double *out = g_hel.d_part + (size_t)kHelMaxBlocks * kHelVals;
   hipStream_t s = ndsm::stream();
   hipLaunchKernelGGL(helicity_part_k, dim3(nb), dim3(kHelBlock), 0, s, A, Ap, B, Bp, Br, g_hel.d_part, p);
@@ -338,7 +292,7 @@ extern "C" int ndsmk_nlfff_metrics(const double *B, const double *Bold, const in
     p.dq[d] = h_dq3[d];
   }
   p.nrows = (size_t)n3[1] * (size_t)n3[2];
-  const int nb = (int)(p.nrows < (size_t)kHelMaxBlocks ? p.nrows : (size_t)kHelMaxBlocks);
+  const int nb = ndsm::red_blocks(p.nrows);
   double *out = g_hel.d_part + (size_t)kHelMaxBlocks * kHelVals;
   hipStream_t s = ndsm::stream();
   hipLaunchKernelGGL(nlfff_part_k, dim3(nb), dim3(kHelBlock), 0, s, B, Bold, status, g_hel.d_part, p);

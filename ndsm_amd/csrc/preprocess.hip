@@ -6,31 +6,34 @@
 //                  S1 .. S6 of the current field from the state; writes the TRIAL field T = B - dt (E / hh) G at every
 //                  node, G the exact gradient of L.  Streaming, one thread per node: 72 B/pt in, 24 out.
 //   pre_sums_k   : reads the trial (at the start: the current, or the observed) field, writes its Lambda and the block
-//                  partials of the eleven sums with opt_omega_k's row walk and 256-wide tree: 48 B/pt in, 24 out.
-//   pre_final_k  : one block: the fold and tree over the partials, then ONE thread forms L1 .. L4 and L and decides:
-//                  L_T < L accepts (the buffer index flips, dt grows by 1.01), anything else - a NaN included -
-//                  rejects (dt halves).  The sums of the accepted field stay in the state for the next update pass.
+//                  partials of the eleven sums with opt_omega_k's row walk and descent.hpp's tree: 48 B/pt in, 24 out.
+//   pre_final_k  : one block: descent.hpp's fold and tree over the partials, then ONE thread forms L1 .. L4 and L and
+//                  runs descent.hpp's decision: L_T < L accepts (the buffer index flips, dt grows by 1.01), anything
+//                  else - a NaN included - rejects (dt halves).  The sums of the accepted field stay in the state for
+//                  the next update pass.  The pass over the observation (PRE_OBS) only stores its two norms.
 //
-// Which of the two B and the two Lambda buffers is "current" is a number in the device-resident state, and so are dt,
+// Which of the two B and the two Lambda buffers is "current" is a number in the device-resident state (descent.hpp's
+// DescentState: five terms, eight sums in the row, two norms behind the control words), and so are dt,
 // L, the sums and the counters: the host reads nothing back between two checks.  A dt below dt_min raises the state's
 // stop flag; the launches already queued behind it return at once.  Every step is deterministic and the library is
 // built without contraction: tests/preprocess_model.py restates the iteration in numpy bit for bit.
-#include "common.hpp"
+#include "descent.hpp"
 #include "diffq.hpp"
 
 namespace {
 
+using ndsm::kRedBlock;
 using ndsm::trap_w;
 
-constexpr int kPreBlock = 256;        // kOptBlock of optimize.hip
-constexpr int kPreMaxBlocks = 2048;   // kOptMaxBlocks
 constexpr int kPreSums = 11;          // S1 .. S11
 
-// the device-resident state, all doubles: one history row, then the control words and the norms of the observation
+// the device-resident state: the history row [tries, L, L1, L2, L3h, L3z, L4, dt, accepted, S1 .. S6, S10, S11], the
+// control words, then the norms E and M of the observation
+using PreState = ndsm::DescentState<5, 8, 2>;
 enum {
-  ST_TRIES = 0, ST_L = 1, ST_L1 = 2, ST_L2 = 3, ST_L3H = 4, ST_L3Z = 5, ST_L4 = 6, ST_DT = 7, ST_ACCEPTED = 8,
-  ST_S1 = 9, ST_S2 = 10, ST_S3 = 11, ST_S4 = 12, ST_S5 = 13, ST_S6 = 14, ST_S10 = 15, ST_S11 = 16,
-  ST_CUR = 17, ST_STOP = 18, ST_E = 19, ST_M = 20, ST_LEN = 21
+  ST_L1 = PreState::TERM, ST_L2, ST_L3H, ST_L3Z, ST_L4,
+  ST_S1 = PreState::EXTRA, ST_S2, ST_S3, ST_S4, ST_S5, ST_S6, ST_S10, ST_S11,
+  ST_E = PreState::TAIL, ST_M
 };
 
 // which field a sums pass and the decision behind it are about
@@ -62,13 +65,13 @@ __device__ __forceinline__ double lap5t(const double *__restrict__ v, size_t c, 
 
 // which = PRE_START: Lambda and the sums of the current field; PRE_TRIAL: of the trial field; PRE_OBS: the sums of the
 // observation (its Lambda goes to the trial buffer's place, which the first try overwrites)
-__global__ __launch_bounds__(kPreBlock) void pre_sums_k(const double *__restrict__ B0, const double *__restrict__ B1,
+__global__ __launch_bounds__(kRedBlock) void pre_sums_k(const double *__restrict__ B0, const double *__restrict__ B1,
                                                        double *__restrict__ La0, double *__restrict__ La1,
                                                        const double *__restrict__ obs, double *__restrict__ part,
                                                        const double *__restrict__ state, int which, PreArgs p) {
-  __shared__ double sh[kPreSums][kPreBlock];
-  if (state[ST_STOP] != 0.0) return;
-  const int cur = (int)state[ST_CUR];
+  __shared__ double sh[kPreSums][kRedBlock];
+  if (state[PreState::STOP] != 0.0) return;
+  const int cur = (int)state[PreState::CUR];
   const int src = which == PRE_START ? cur : 1 - cur;
   const double *B = which == PRE_OBS ? obs : (src ? B1 : B0);
   double *La = src ? La1 : La0;
@@ -85,7 +88,7 @@ __global__ __launch_bounds__(kPreBlock) void pre_sums_k(const double *__restrict
     const int j = (int)r;
     const double wy = trap_w(j, ny, hy);
     const double y = centred(j, ny, hy);
-    for (int i = t; i < nx; i += kPreBlock) {
+    for (int i = t; i < nx; i += kRedBlock) {
       const size_t c = (size_t)i + sy * (size_t)j;
       const double w = trap_w(i, nx, hx) * wy;
       const double x = centred(i, nx, hx);
@@ -115,35 +118,17 @@ __global__ __launch_bounds__(kPreBlock) void pre_sums_k(const double *__restrict
       v[10] = v[10] + w * (sqrt(x * x + y * y) * bb);
     }
   }
-  for (int q = 0; q < kPreSums; ++q) sh[q][t] = v[q];
-  __syncthreads();
-  for (int o = kPreBlock / 2; o > 0; o >>= 1) {
-    if (t < o)
-      for (int q = 0; q < kPreSums; ++q) sh[q][t] = sh[q][t] + sh[q][t + o];
-    __syncthreads();
-  }
-  if (t < kPreSums) part[(size_t)blockIdx.x * kPreSums + t] = sh[t][0];
+  ndsm::block_part<kPreSums, kPreSums>(sh, v, part);
 }
 
-// one block: opt_final_k's fold and tree over the partials of pre_sums_k, then thread 0 decides
-__global__ __launch_bounds__(kPreBlock) void pre_final_k(const double *__restrict__ part, int nb,
+// one block: the fold and tree over the partials of pre_sums_k, then thread 0 forms L and decides
+__global__ __launch_bounds__(kRedBlock) void pre_final_k(const double *__restrict__ part, int nb,
                                                         double *__restrict__ state, int which, double dt_min,
                                                         PreArgs p) {
-  __shared__ double sh[kPreSums][kPreBlock];
-  if (state[ST_STOP] != 0.0) return;
-  const int t = threadIdx.x;
-  double v[kPreSums];
-  for (int q = 0; q < kPreSums; ++q) v[q] = 0.0;
-  for (int b = t; b < nb; b += kPreBlock)
-    for (int q = 0; q < kPreSums; ++q) v[q] = v[q] + part[(size_t)b * kPreSums + q];
-  for (int q = 0; q < kPreSums; ++q) sh[q][t] = v[q];
-  __syncthreads();
-  for (int o = kPreBlock / 2; o > 0; o >>= 1) {
-    if (t < o)
-      for (int q = 0; q < kPreSums; ++q) sh[q][t] = sh[q][t] + sh[q][t + o];
-    __syncthreads();
-  }
-  if (t != 0) return;
+  __shared__ double sh[kPreSums][kRedBlock];
+  if (state[PreState::STOP] != 0.0) return;
+  ndsm::block_final<kPreSums, kPreSums>(sh, part, nb);
+  if (threadIdx.x != 0) return;
   if (which == PRE_OBS) {   // the norms of the observation, fixed for the call
     state[ST_E] = sh[9][0];
     state[ST_M] = sh[10][0];
@@ -158,22 +143,7 @@ __global__ __launch_bounds__(kPreBlock) void pre_final_k(const double *__restric
   const double l3h = sh[6][0] / E, l3z = sh[7][0] / E;
   const double l4 = ((hh * hh) * s9) / E;
   const double l = (((p.mu[0] * l1 + p.mu[1] * l2) + p.mu[2] * l3h) + p.mu[3] * l3z) + p.mu[4] * l4;
-  double dt = state[ST_DT];
-  bool keep = which == PRE_START;
-  if (which == PRE_TRIAL) {
-    state[ST_TRIES] = state[ST_TRIES] + 1.0;
-    if (l < state[ST_L]) {   // (false for a NaN on either side: a rejection)
-      keep = true;
-      state[ST_CUR] = 1.0 - state[ST_CUR];
-      state[ST_ACCEPTED] = state[ST_ACCEPTED] + 1.0;
-      dt = dt * 1.01;
-    } else {
-      dt = dt * 0.5;
-    }
-    state[ST_DT] = dt;
-  }
-  if (keep) {
-    state[ST_L] = l;
+  if (ndsm::descent_decide<PreState>(state, l, which == PRE_TRIAL, dt_min)) {
     state[ST_L1] = l1;
     state[ST_L2] = l2;
     state[ST_L3H] = l3h;
@@ -188,7 +158,6 @@ __global__ __launch_bounds__(kPreBlock) void pre_final_k(const double *__restric
     state[ST_S10] = sh[9][0];
     state[ST_S11] = sh[10][0];
   }
-  if (dt < dt_min) state[ST_STOP] = 1.0;
 }
 
 // T = B - dt (E / hh) G at every node; B, Lambda: the current buffers, T: the other B buffer
@@ -196,12 +165,12 @@ __global__ __launch_bounds__(256) void pre_update_k(double *__restrict__ B0, dou
                                                     const double *__restrict__ La0, const double *__restrict__ La1,
                                                     const double *__restrict__ obs, const double *__restrict__ state,
                                                     PreArgs p) {
-  if (state[ST_STOP] != 0.0) return;
+  if (state[PreState::STOP] != 0.0) return;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const int j = blockIdx.y * blockDim.y + threadIdx.y;
   const int nx = p.n[0], ny = p.n[1];
   if (i >= nx || j >= ny) return;
-  const int cur = (int)state[ST_CUR];
+  const int cur = (int)state[PreState::CUR];
   const double *B = cur ? B1 : B0;
   const double *La = cur ? La1 : La0;
   double *T = cur ? B0 : B1;
@@ -213,7 +182,7 @@ __global__ __launch_bounds__(256) void pre_update_k(double *__restrict__ B0, dou
   const double E = state[ST_E], M = state[ST_M];
   const double s1 = state[ST_S1], s2 = state[ST_S2], s3 = state[ST_S3];
   const double s4 = state[ST_S4], s5 = state[ST_S5], s6 = state[ST_S6];
-  const double step = state[ST_DT] * (E / hh);
+  const double step = state[PreState::DT] * (E / hh);
   const double a = (2.0 * p.mu[0]) / (E * E), b = (2.0 * p.mu[1]) / (M * M);
   const double c3h = (2.0 * p.mu[2]) / E, c3z = (2.0 * p.mu[3]) / E;
   const double c4 = ((2.0 * p.mu[4]) * ((hh * hh) * hh)) / E;
@@ -238,10 +207,6 @@ __global__ __launch_bounds__(256) void pre_update_k(double *__restrict__ B0, dou
   T[c + 2 * N] = bz - step * gz;
 }
 
-__global__ void pre_state_k(double *__restrict__ state, double dt0) {
-  if (threadIdx.x < ST_LEN) state[threadIdx.x] = threadIdx.x == ST_DT ? dt0 : 0.0;
-}
-
 int pre_args(const int32_t *n2, const double *h_dq2, const double *h_mu5, PreArgs &p) {
   NDSM_CHECK_ARG(n2 && h_dq2 && h_mu5);
   NDSM_CHECK_ARG(n2[0] >= 3 && n2[1] >= 3 && (n2[1] + 3) / 4 <= 65535);
@@ -256,21 +221,19 @@ int pre_args(const int32_t *n2, const double *h_dq2, const double *h_mu5, PreArg
 int pre_evaluate(double *B0, double *B1, double *La, const double *obs, double *work, const PreArgs &p, int which,
                  double dt_min) {
   const size_t N3 = 3 * (size_t)p.n[0] * (size_t)p.n[1];
-  const int nb = p.n[1] < kPreMaxBlocks ? p.n[1] : kPreMaxBlocks;
-  double *state = work, *part = work + ST_LEN;
+  const int nb = ndsm::red_blocks((size_t)p.n[1]);
+  double *state = work, *part = work + PreState::LEN;
   hipStream_t s = ndsm::stream();
-  hipLaunchKernelGGL(pre_sums_k, dim3(nb), dim3(kPreBlock), 0, s, B0, B1, La, La + N3, obs, part, state, which, p);
+  hipLaunchKernelGGL(pre_sums_k, dim3(nb), dim3(kRedBlock), 0, s, B0, B1, La, La + N3, obs, part, state, which, p);
   NDSM_LAUNCH_CHECK();
-  hipLaunchKernelGGL(pre_final_k, dim3(1), dim3(kPreBlock), 0, s, part, nb, state, which, dt_min, p);
+  hipLaunchKernelGGL(pre_final_k, dim3(1), dim3(kRedBlock), 0, s, part, nb, state, which, dt_min, p);
   NDSM_LAUNCH_CHECK();
   return 0;
 }
 
 }  // namespace
 
-extern "C" size_t ndsmk_preprocess_work_bytes(void) {
-  return sizeof(double) * (ST_LEN + (size_t)kPreMaxBlocks * kPreSums);
-}
+extern "C" size_t ndsmk_preprocess_work_bytes(void) { return ndsm::descent_work_bytes<PreState, kPreSums>(); }
 
 // The start: the state (tries 0, dt0, buffer 0 current), E and M of the observation, then Lambda, the sums and L of
 // B0.  Asynchronous.
@@ -281,8 +244,7 @@ extern "C" int ndsmk_preprocess_begin(double *B0, double *B1, double *La, const 
   NDSM_CHECK_ARG(B0 && B1 && La && obs && work);
   PreArgs p;
   if (int rc = pre_args(n2, h_dq2, h_mu5, p)) return rc;
-  hipLaunchKernelGGL(pre_state_k, dim3(1), dim3(64), 0, ndsm::stream(), work, dt0);
-  NDSM_LAUNCH_CHECK();
+  if (int rc = ndsm::descent_begin<PreState>(work, dt0)) return rc;
   if (int rc = pre_evaluate(B0, B1, La, obs, work, p, PRE_OBS, dt_min)) return rc;
   return pre_evaluate(B0, B1, La, obs, work, p, PRE_START, dt_min);
 }
@@ -312,8 +274,5 @@ extern "C" int ndsmk_preprocess_tries(double *B0, double *B1, double *La, const 
 extern "C" int ndsmk_preprocess_row(const double *work, double *h_row21) {
   NDSM_REQUIRE_READY();
   NDSM_CHECK_ARG(work && h_row21);
-  hipStream_t s = ndsm::stream();
-  NDSM_HIP(hipMemcpyAsync(h_row21, work, ST_LEN * sizeof(double), hipMemcpyDeviceToHost, s));
-  NDSM_HIP(hipStreamSynchronize(s));
-  return 0;
+  return ndsm::descent_row<PreState>(work, h_row21);
 }

@@ -13,7 +13,7 @@
 //              24 B/pt.
 // Every reduction is deterministic: block b sums grid rows b, b + gridDim.x, ... in that order (the grid size
 // depends on the shape alone), one block folds the block partials in a fixed order and a fixed halving tree.
-#include "common.hpp"
+#include "descent.hpp"
 #include "diffq.hpp"
 
 namespace {
@@ -22,8 +22,8 @@ using ndsm::ddq;
 using ndsm::ddq0;
 using ndsm::trap_w;
 
-constexpr int kPrjBlock = 256;
-constexpr int kPrjMaxBlocks = 2048;   // 256 CUs x 8 blocks; rows beyond that are strided
+constexpr int kPrjBlock = ndsm::kRedBlock;           // descent.hpp's reduction: block_part, block_final
+constexpr int kPrjMaxBlocks = ndsm::kRedMaxBlocks;
 constexpr int kPrjVals = 3;           // per block: sum w d, sum w, max |d|  (grad_sub: sum w |G phi|^2)
 constexpr int kPrjRes = 8;            // device results: [0..3] div_rhs (+ c), [4] grad_sub, [5..7] div_max
 
@@ -43,19 +43,7 @@ PrjArgs prj_args(const int32_t *n3, const double *h_dq3) {
   return p;
 }
 
-int prj_blocks(const PrjArgs &p) { return (int)(p.nrows < (size_t)kPrjMaxBlocks ? p.nrows : (size_t)kPrjMaxBlocks); }
-
-// halving tree over the block: the first NS of the NV values are sums, the others maxima; thread 0 holds the result
-template <int NV, int NS>
-__device__ __forceinline__ void block_fold(double (*sh)[kPrjBlock], const double *v, int t) {
-  for (int q = 0; q < NV; ++q) sh[q][t] = v[q];
-  __syncthreads();
-  for (int o = kPrjBlock / 2; o > 0; o >>= 1) {
-    if (t < o)
-      for (int q = 0; q < NV; ++q) sh[q][t] = q < NS ? sh[q][t] + sh[q][t + o] : fmax(sh[q][t], sh[q][t + o]);
-    __syncthreads();
-  }
-}
+int prj_blocks(const PrjArgs &p) { return ndsm::red_blocks(p.nrows); }
 
 // d = div_h B with ddq0 on every axis, in the order x, y, z
 __device__ __forceinline__ double div_h(const double *__restrict__ B, size_t c, int i, int j, int k, size_t N,
@@ -86,8 +74,7 @@ __global__ __launch_bounds__(kPrjBlock) void div_part_k(const double *__restrict
       v[2] = fmax(v[2], fabs(d));
     }
   }
-  block_fold<kPrjVals, 2>(sh, v, t);
-  if (t < kPrjVals) part[(size_t)blockIdx.x * kPrjVals + t] = sh[t][0];
+  ndsm::block_part<kPrjVals, 2>(sh, v, part);
 }
 
 // B_q -= (G_h phi)_q where index q is inside its axis; block partials of sum w |G_h phi|^2 in slot 0
@@ -124,25 +111,17 @@ __global__ __launch_bounds__(kPrjBlock) void grad_sub_k(double *__restrict__ B, 
       v[0] = v[0] + w * e;
     }
   }
-  block_fold<1, 1>(sh, v, t);
-  if (t == 0) part[(size_t)blockIdx.x * kPrjVals] = sh[0][0];
+  ndsm::block_part<1, 1>(sh, v, part, kPrjVals);
 }
 
-// one block: thread t folds the partials of blocks t, t + 256, ... in that order, then the halving tree; the NV
-// results go to out[0..NV-1], and (MEAN) out[NV] = out[0] / out[1]
+// one block: descent.hpp's fold (thread t: the partials of blocks t, t + 256, ... in that order) and halving tree; the
+// NV results go to out[0..NV-1], and (MEAN) out[NV] = out[0] / out[1]
 template <int NV, int NS, bool MEAN>
 __global__ __launch_bounds__(kPrjBlock) void prj_fold_k(const double *__restrict__ part, int nb,
                                                         double *__restrict__ out) {
   __shared__ double sh[NV][kPrjBlock];
   const int t = threadIdx.x;
-  double v[NV];
-  for (int q = 0; q < NV; ++q) v[q] = 0.0;
-  for (int b = t; b < nb; b += kPrjBlock)
-    for (int q = 0; q < NV; ++q) {
-      const double x = part[(size_t)b * kPrjVals + q];
-      v[q] = q < NS ? v[q] + x : fmax(v[q], x);
-    }
-  block_fold<NV, NS>(sh, v, t);
+  ndsm::block_final<NV, NS>(sh, part, nb, kPrjVals);
   if (t < NV) out[t] = sh[t][0];
   if (MEAN && t == 0) out[NV] = sh[0][0] / sh[1][0];
 }

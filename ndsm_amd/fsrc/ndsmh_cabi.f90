@@ -1235,8 +1235,9 @@ contains
                                   hist_rows, info, .true., "ndsm_hip_vecpot_optimize_device")
   end function
 
+  ! the four entries above and below: with Bobs (and then wm, nu, free) the measurement term and the freed lower face
   function vecpot_handle_optimize(handle, ioptc, ropt, B, w, start, niter_max, check, tol, dt0, dt_min, hist, &
-                                  hist_rows, info, on_device, who) result(ierr)
+                                  hist_rows, info, on_device, who, Bobs, wm, nu, free) result(ierr)
     type(c_ptr), intent(in) :: handle, B, w, hist, info
     integer(c_int), intent(inout) :: ioptc(0:OPT_LEN - 1)
     real(c_double), intent(inout) :: ropt(0:OPT_LEN - 1)
@@ -1244,6 +1245,9 @@ contains
     real(c_double), intent(in) :: tol, dt0, dt_min
     logical, intent(in) :: on_device
     character(len=*), intent(in) :: who
+    type(c_ptr), intent(in), optional :: Bobs, wm
+    real(c_double), intent(in), optional :: nu
+    integer(c_int), intent(in), optional :: free
     integer(c_int) :: ierr
     type(vecpot_ctx), pointer :: ctx
     type(optimize_args) :: op
@@ -1251,26 +1255,48 @@ contains
     integer(c_int), pointer :: iout(:)
     real(c_double) :: t0
     integer(c_int) :: rc
+    logical :: obs, ok
+    obs = present(Bobs)
     if (c_associated(info)) then
       call c_f_pointer(info, iout, [3])
       iout = 0
     end if
     ierr = live_ctx(handle, ctx)
     if (ierr == 0 .and. .not. (c_associated(B) .and. c_associated(hist) .and. c_associated(info))) ierr = NDSMK_EARG
-    if (ierr == 0 .and. (start < 0 .or. start > 1 .or. niter_max < 1 .or. check < 1 .or. hist_rows < 2 .or. &
-                         .not. (tol >= 0.0_c_double) .or. tol > huge(tol) .or. .not. (dt0 > 0.0_c_double) .or. &
-                         dt0 > huge(dt0) .or. .not. (dt_min >= 0.0_c_double) .or. dt_min > huge(dt_min))) &
-      ierr = ndsmk_note_error(NDSMK_EVALUE, "optimize: start 0 or 1, niter_max >= 1, check >= 1, hist_rows >= 2, "// &
-                              "tol >= 0, dt0 > 0 and dt_min >= 0 (all finite)"//c_null_char)
+    if (ierr == 0 .and. obs) then
+      if (.not. c_associated(Bobs)) ierr = NDSMK_EARG
+    end if
+    if (ierr == 0) then
+      ok = .not. (start < 0 .or. start > 1 .or. niter_max < 1 .or. check < 1 .or. hist_rows < 2 .or. &
+                  .not. (tol >= 0.0_c_double) .or. tol > huge(tol) .or. .not. (dt0 > 0.0_c_double) .or. &
+                  dt0 > huge(dt0) .or. .not. (dt_min >= 0.0_c_double) .or. dt_min > huge(dt_min))
+      if (obs) then
+        if (.not. ok .or. free < 0 .or. free > 1 .or. .not. (nu >= 0.0_c_double) .or. nu > huge(nu)) &
+          ierr = ndsmk_note_error(NDSMK_EVALUE, "optimize_obs: free 0 or 1, nu >= 0, start 0 or 1, niter_max >= 1, "// &
+                                  "check >= 1, hist_rows >= 2, tol >= 0, dt0 > 0 and dt_min >= 0 (all finite)"//c_null_char)
+      else if (.not. ok) then
+        ierr = ndsmk_note_error(NDSMK_EVALUE, "optimize: start 0 or 1, niter_max >= 1, check >= 1, hist_rows >= 2, "// &
+                                "tol >= 0, dt0 > 0 and dt_min >= 0 (all finite)"//c_null_char)
+      end if
+    end if
     if (ierr == 0) then
       op%w = w; op%hist = hist
+      if (obs) then
+        op%bobs = Bobs; op%wm = wm; op%nu = nu; op%free = free
+      end if
       op%start = start; op%niter_max = niter_max; op%check = check; op%hist_rows = hist_rows
       op%tol = tol; op%dt0 = dt0; op%dt_min = dt_min
       iopt = ioptc
       verbose = (iopt(IOPT_DEBUG) == 1)
       t0 = wall_seconds()
       rc = NDSMK_EARG
-      if (int(iopt(IOPT_NGRIDS)) == ctx%ngr) rc = vecpot_optimize(ctx, iopt, ropt, B, op, on_device)
+      if (int(iopt(IOPT_NGRIDS)) == ctx%ngr) then
+        if (obs) then
+          rc = vecpot_optimize_obs(ctx, iopt, ropt, B, op, on_device)
+        else
+          rc = vecpot_optimize(ctx, iopt, ropt, B, op, on_device)
+        end if
+      end if
       ropt(ROPT_TIM) = wall_seconds() - t0
       ioptc = int(iopt, c_int)
       ierr = reported(who, rc)
@@ -1282,7 +1308,8 @@ contains
     end if
     if (ierr >= NDSMK_ENODEV) then
       if (c_associated(info)) iout = 0
-      if (c_associated(hist) .and. hist_rows >= 1) call clear_host([hist], [48], [int(hist_rows, c_int64_t)])
+      if (c_associated(hist) .and. hist_rows >= 1) &
+        call clear_host([hist], [merge(56, 48, obs)], [int(hist_rows, c_int64_t)])
     end if
   end function
 
@@ -1298,8 +1325,8 @@ contains
     integer(c_int), value :: free, start, niter_max, check, hist_rows
     real(c_double), value :: nu, tol, dt0, dt_min
     integer(c_int) :: ierr
-    ierr = vecpot_handle_optimize_obs(handle, ioptc, ropt, B, w, Bobs, wm, nu, free, start, niter_max, check, tol, dt0, &
-                                      dt_min, hist, hist_rows, info, .false., "ndsm_hip_vecpot_optimize_obs")
+    ierr = vecpot_handle_optimize(handle, ioptc, ropt, B, w, start, niter_max, check, tol, dt0, dt_min, hist, &
+                                  hist_rows, info, .false., "ndsm_hip_vecpot_optimize_obs", Bobs, wm, nu, free)
   end function
 
   ! the same on DEVICE arrays of the library's GPU: only history rows cross PCIe
@@ -1312,62 +1339,8 @@ contains
     integer(c_int), value :: free, start, niter_max, check, hist_rows
     real(c_double), value :: nu, tol, dt0, dt_min
     integer(c_int) :: ierr
-    ierr = vecpot_handle_optimize_obs(handle, ioptc, ropt, dB, dw, dBobs, dwm, nu, free, start, niter_max, check, tol, &
-                                      dt0, dt_min, hist, hist_rows, info, .true., "ndsm_hip_vecpot_optimize_obs_device")
-  end function
-
-  function vecpot_handle_optimize_obs(handle, ioptc, ropt, B, w, Bobs, wm, nu, free, start, niter_max, check, tol, dt0, &
-                                      dt_min, hist, hist_rows, info, on_device, who) result(ierr)
-    type(c_ptr), intent(in) :: handle, B, w, Bobs, wm, hist, info
-    integer(c_int), intent(inout) :: ioptc(0:OPT_LEN - 1)
-    real(c_double), intent(inout) :: ropt(0:OPT_LEN - 1)
-    integer(c_int), intent(in) :: free, start, niter_max, check, hist_rows
-    real(c_double), intent(in) :: nu, tol, dt0, dt_min
-    logical, intent(in) :: on_device
-    character(len=*), intent(in) :: who
-    integer(c_int) :: ierr
-    type(vecpot_ctx), pointer :: ctx
-    type(optimize_obs_args) :: op
-    integer(ik) :: iopt(0:OPT_LEN - 1)
-    integer(c_int), pointer :: iout(:)
-    real(c_double) :: t0
-    integer(c_int) :: rc
-    if (c_associated(info)) then
-      call c_f_pointer(info, iout, [3])
-      iout = 0
-    end if
-    ierr = live_ctx(handle, ctx)
-    if (ierr == 0 .and. .not. (c_associated(B) .and. c_associated(Bobs) .and. c_associated(hist) .and. &
-                               c_associated(info))) ierr = NDSMK_EARG
-    if (ierr == 0 .and. (start < 0 .or. start > 1 .or. niter_max < 1 .or. check < 1 .or. hist_rows < 2 .or. &
-                         .not. (tol >= 0.0_c_double) .or. tol > huge(tol) .or. .not. (dt0 > 0.0_c_double) .or. &
-                         dt0 > huge(dt0) .or. .not. (dt_min >= 0.0_c_double) .or. dt_min > huge(dt_min) .or. &
-                         free < 0 .or. free > 1 .or. .not. (nu >= 0.0_c_double) .or. nu > huge(nu))) &
-      ierr = ndsmk_note_error(NDSMK_EVALUE, "optimize_obs: free 0 or 1, nu >= 0, start 0 or 1, niter_max >= 1, "// &
-                              "check >= 1, hist_rows >= 2, tol >= 0, dt0 > 0 and dt_min >= 0 (all finite)"//c_null_char)
-    if (ierr == 0) then
-      op%w = w; op%bobs = Bobs; op%wm = wm; op%hist = hist
-      op%nu = nu; op%free = free
-      op%start = start; op%niter_max = niter_max; op%check = check; op%hist_rows = hist_rows
-      op%tol = tol; op%dt0 = dt0; op%dt_min = dt_min
-      iopt = ioptc
-      verbose = (iopt(IOPT_DEBUG) == 1)
-      t0 = wall_seconds()
-      rc = NDSMK_EARG
-      if (int(iopt(IOPT_NGRIDS)) == ctx%ngr) rc = vecpot_optimize_obs(ctx, iopt, ropt, B, op, on_device)
-      ropt(ROPT_TIM) = wall_seconds() - t0
-      ioptc = int(iopt, c_int)
-      ierr = reported(who, rc)
-      if (ierr /= 0) ioptc(IOPT_IERR) = ierr            ! (as the field entries: ioptc is written by a call that ran)
-      if (ierr == 0) then
-        iout = op%info
-        ierr = int(iopt(IOPT_IERR), c_int)
-      end if
-    end if
-    if (ierr >= NDSMK_ENODEV) then
-      if (c_associated(info)) iout = 0
-      if (c_associated(hist) .and. hist_rows >= 1) call clear_host([hist], [56], [int(hist_rows, c_int64_t)])
-    end if
+    ierr = vecpot_handle_optimize(handle, ioptc, ropt, dB, dw, start, niter_max, check, tol, dt0, dt_min, hist, &
+                                  hist_rows, info, .true., "ndsm_hip_vecpot_optimize_obs_device", dBobs, dwm, nu, free)
   end function
 
   ! Resampling of a node array between two uniform meshes on the same box (semantics in include/ndsm_hip.h).  src

@@ -33,7 +33,7 @@ module ndsmh_vecpot
   public :: vecpot_solve, poisson_solve
   public :: vecpot_ctx, vecpot_ctx_create, vecpot_ctx_destroy, vecpot_ctx_matches, vecpot_run, vecpot_cache_drop
   public :: vecpot_alpha_map, vecpot_nlfff, nlfff_args, vecpot_optimize, optimize_args, vecpot_preprocess, preprocess_args
-  public :: vecpot_optimize_cascade, vecpot_ref, vecpot_optimize_obs, optimize_obs_args
+  public :: vecpot_optimize_cascade, vecpot_ref, vecpot_optimize_obs, descent_ctl
   public :: vecpot_project, vecpot_devore, vecpot_lines, vecpot_paths, vecpot_nulls, vecpot_skeleton, vecpot_separators
   public :: VP_POTENTIAL, VP_FIELD, VP_HELICITY, VP_CURRENT, VP_NLFFF
   ! pieces the distributed driver (ndsmh_wvecpot) shares with vecpot_solve
@@ -115,23 +115,25 @@ module ndsmh_vecpot
     integer(c_int) :: niter = 0
   end type
 
-  ! what an optimization-method call takes besides B (vecpot_optimize): w (nx,ny,nz) in, on the side B is on, may be
-  ! c_null_ptr (1 everywhere); hist (6,hist_rows) on the HOST; info out: rows written, tries, stop reason
-  type :: optimize_args
-    type(c_ptr) :: w = c_null_ptr, hist = c_null_ptr
-    integer(c_int) :: start = 0, niter_max = 1, check = 1, hist_rows = 2
+  ! what every descent call takes (descent_open .. descent_close): at most niter_max tries, a look at L every check
+  ! tries, the stop rule's tol, the first step and the smallest; hist (width,hist_rows) on the HOST; info out: rows
+  ! written, tries, stop reason (0 niter_max, 1 tol, 2 dt_min)
+  type :: descent_ctl
+    type(c_ptr) :: hist = c_null_ptr
+    integer(c_int) :: niter_max = 1, check = 1, hist_rows = 2
     real(wp) :: tol = 0, dt0 = 0, dt_min = 0
     integer(c_int) :: info(3) = 0
   end type
 
-  ! the same for vecpot_optimize_obs: bobs (nx,ny,3) in, the observation on the k = 0 plane, and wm (nx,ny,3) in, its
-  ! per-component confidence, may be c_null_ptr (1 everywhere), both on the side B is on; nu the weight of L_m in L;
-  ! free 1: the lower face moves, 0: it is held; hist (7,hist_rows) on the HOST
-  type :: optimize_obs_args
-    type(c_ptr) :: w = c_null_ptr, bobs = c_null_ptr, wm = c_null_ptr, hist = c_null_ptr
-    integer(c_int) :: start = 0, free = 1, niter_max = 1, check = 1, hist_rows = 2
-    real(wp) :: nu = 0, tol = 0, dt0 = 0, dt_min = 0
-    integer(c_int) :: info(3) = 0
+  ! what an optimization-method call takes besides B (vecpot_optimize): w (nx,ny,nz) in, on the side B is on, may be
+  ! c_null_ptr (1 everywhere); hist rows have 6 entries.  With bobs the call has a measurement term and a freed lower
+  ! face: bobs (nx,ny,3) in, the observation on the k = 0 plane, and wm (nx,ny,3) in, its per-component confidence, may
+  ! be c_null_ptr (1 everywhere), both on the side B is on; nu the weight of L_m in L; free 1: the lower face moves, 0:
+  ! it is held; hist rows then have 7 entries
+  type, extends(descent_ctl) :: optimize_args
+    type(c_ptr) :: w = c_null_ptr, bobs = c_null_ptr, wm = c_null_ptr
+    integer(c_int) :: start = 0, free = 1
+    real(wp) :: nu = 0
   end type
 
   ! one level of a cascade (vecpot_optimize_cascade): a context somebody else owns
@@ -140,14 +142,22 @@ module ndsmh_vecpot
   end type
 
   ! what a preprocessing call takes besides B (vecpot_preprocess): obs (nx,ny,3) in, on the side B is on, may be
-  ! c_null_ptr (the input B is the observation); mu = mu1, mu2, mu3h, mu3z, mu4; hist (17,hist_rows) on the HOST; info
-  ! out: rows written, tries, stop reason
-  type :: preprocess_args
-    type(c_ptr) :: obs = c_null_ptr, hist = c_null_ptr
+  ! c_null_ptr (the input B is the observation); mu = mu1, mu2, mu3h, mu3z, mu4; hist rows have 17 entries
+  type, extends(descent_ctl) :: preprocess_args
+    type(c_ptr) :: obs = c_null_ptr
     real(wp) :: mu(5) = 0
-    integer(c_int) :: niter_max = 1, check = 1, hist_rows = 2
-    real(wp) :: tol = 0, dt0 = 0, dt_min = 0
-    integer(c_int) :: info(3) = 0
+  end type
+
+  ! the check loop of a descent between descent_open and descent_close: the state row as the device holds it - a
+  ! history row of `width` doubles, then the index of the current buffer and the stop flag (descent.hpp's DescentState)
+  integer, parameter :: DESCENT_ROW_MAX = 21
+  type :: descent_loop
+    real(wp) :: row(DESCENT_ROW_MAX) = 0  ! the caller's ndsmk_*_row reads into it
+    integer(c_int) :: n = 0               ! the tries of the interval to queue next (descent_more)
+    integer :: width = 0
+    integer(c_int) :: rows = 0, tries = 0
+    real(wp) :: lprev = 0
+    real(wp), pointer :: hh(:, :) => null()
   end type
 
   ! one array of a host-array line entry in its staging buffer (carve, fetch)
@@ -1484,6 +1494,74 @@ contains
   end function
 
   ! ------------------------------------------------------------------
+  ! The check loop of the descents (vecpot_optimize, vecpot_preprocess), which all decide their steps on the device.
+  ! The caller owns the kernel-layer calls and nothing else:
+  !     <begin>;  <row> into lp%row;  call descent_open(lp, ctl, width)
+  !     do while (descent_more(lp, ctl))
+  !       <tries> with lp%n;  <row> into lp%row;  call descent_note(lp, ctl)
+  !     end do
+  !     rc = descent_close(lp, ctl, ...)
+  ! Row 1 of the history is the start; every interval of ctl%check tries (the last may be shorter) adds a row, the last
+  ! row being overwritten once hist_rows are full.  Stop reasons: 2 the device raised its stop flag (dt < dt_min), 1 L
+  ! fell by no more than tol * L over a FULL interval, 0 niter_max.
+  ! ------------------------------------------------------------------
+  subroutine descent_open(lp, ctl, width)
+    type(descent_loop), intent(inout) :: lp
+    type(descent_ctl), intent(inout) :: ctl
+    integer, intent(in) :: width
+    lp%width = width
+    call c_f_pointer(ctl%hist, lp%hh, [width, int(ctl%hist_rows)])
+    lp%hh(:, 1) = lp%row(1:width)
+    lp%rows = 1; lp%tries = 0
+    lp%lprev = lp%row(2)
+    ctl%info(3) = 0
+    if (lp%row(width + 2) /= 0.0_wp) ctl%info(3) = 2
+  end subroutine
+
+  ! whether another interval runs; lp%n: its tries
+  function descent_more(lp, ctl) result(more)
+    type(descent_loop), intent(inout) :: lp
+    type(descent_ctl), intent(in) :: ctl
+    logical :: more
+    more = ctl%info(3) == 0 .and. lp%tries < ctl%niter_max
+    if (more) lp%n = min(ctl%check, ctl%niter_max - lp%tries)
+  end function
+
+  ! after the row of an interval has been read back
+  subroutine descent_note(lp, ctl)
+    type(descent_loop), intent(inout) :: lp
+    type(descent_ctl), intent(inout) :: ctl
+    lp%tries = lp%tries + lp%n
+    lp%rows = min(lp%rows + 1_c_int, ctl%hist_rows)
+    lp%hh(:, lp%rows) = lp%row(1:lp%width)
+    if (lp%row(lp%width + 2) /= 0.0_wp) then
+      ctl%info(3) = 2
+    else if (lp%n == ctl%check) then
+      if (lp%lprev - lp%row(2) <= ctl%tol * lp%lprev) ctl%info(3) = 1
+      lp%lprev = lp%row(2)
+    end if
+  end subroutine
+
+  ! info, then the result (nbytes) into dB0 when buffer 1 is the current one, home to pB for the host entry, and the sync
+  function descent_close(lp, ctl, dB0, dB1, nbytes, pB, on_device) result(rc)
+    type(descent_loop), intent(in) :: lp
+    type(descent_ctl), intent(inout) :: ctl
+    type(c_ptr), intent(in) :: dB0, dB1, pB
+    integer(c_size_t), intent(in) :: nbytes
+    logical, intent(in) :: on_device
+    integer(c_int) :: rc
+    ctl%info(1) = lp%rows
+    ctl%info(2) = int(lp%row(1), c_int)
+    if (lp%row(lp%width + 1) /= 0.0_wp) then
+      rc = ndsmk_d2d(dB0, dB1, nbytes); if (rc /= 0) return
+    end if
+    if (.not. on_device) then
+      rc = ndsmk_d2h(pB, dB0, nbytes); if (rc /= 0) return
+    end if
+    rc = ndsmk_sync()
+  end function
+
+  ! ------------------------------------------------------------------
   ! The optimization method on a prepared context (semantics in include/ndsm_hip.h, DESIGN.md "Optimization-method
   ! force-free field").  pB (nx,ny,nz,3) in and out and op%w (nx,ny,nz; may be c_null_ptr) in, on the HOST (both go up
   ! once, B comes home once; between the two only history rows cross PCIe) or (on_device) in HBM; op%hist on the HOST.
@@ -1492,6 +1570,9 @@ contains
   ! then replaced by the input's.  One buffer holds the second field, the two Omega and the state for the length of
   ! the call; a grid whose arrays the device cannot hold is refused before it is allocated.  The tries of one check
   ! interval are queued without a read-back: the device decides each (optimize.hip).
+  ! With op%bobs the call has a measurement term and a freed lower face (DESIGN.md "Measurement errors and a freed
+  ! lower face"): op%bobs (nx,ny,3) and op%wm (nx,ny,3; may be c_null_ptr) on the side B is on - the host entry stages
+  ! the two planes once, behind B and w.  The start field is the same, on B alone; the kernels are optimize_obs.hip's.
   ! ------------------------------------------------------------------
   function vecpot_optimize(ctx, iopt, ropt, pB, op, on_device) result(rc)
     type(vecpot_ctx), intent(inout), target :: ctx
@@ -1501,83 +1582,119 @@ contains
     type(optimize_args), intent(inout) :: op
     logical, intent(in) :: on_device
     integer(c_int) :: rc
-    real(wp) :: dq(3), lo(3), row(8), lprev
-    real(wp), pointer :: hh(:, :)
+    real(wp) :: dq(3), lo(3)
     integer(c_int32_t) :: n3(3)
-    integer(c_size_t) :: nb, wk, total, fr, tot
-    integer(c_int) :: rows, tries, n
+    integer(c_size_t) :: nb, pl3, wk, total, fr, tot, at
     integer :: k
-    type(c_ptr) :: buf, dB0, dB1, dO, dwork, dw
+    logical :: obs
+    type(descent_loop) :: lp
+    type(c_ptr) :: buf, dB0, dB1, dO, dwork, dw, dbobs, dwm
 
     op%info = 0
     buf = c_null_ptr
+    obs = c_associated(op%bobs)
     call ctx_mesh(ctx, n3, lo, dq)
     nb = int(product(int(n3, ik)), c_size_t) * 8_c_size_t
-    wk = ndsmk_optimize_work_bytes()
-    ! two fields, two Omega and w are 13 level-1 arrays; a potential start adds the 3-D hierarchy (at least five)
+    pl3 = 0
+    if (obs) pl3 = int(n3(1), c_size_t) * int(n3(2), c_size_t) * 24_c_size_t   ! a plane of three components
+    if (obs) then
+      wk = ndsmk_optimize_obs_work_bytes()
+    else
+      wk = ndsmk_optimize_work_bytes()
+    end if
+    ! two fields, two Omega and w are 13 level-1 arrays; a potential start adds the 3-D hierarchy (at least five);
+    ! with an observation, its two planes
     k = 13 + merge(5, 0, op%start == 0 .and. .not. ctx%live3)
     rc = ndsmk_mem_info(fr, tot); if (rc /= 0) return
-    if (real(nb, wp) * real(k, wp) + real(wk, wp) > real(tot, wp)) then
+    if (real(nb, wp) * real(k, wp) + 2.0_wp * real(pl3, wp) + real(wk, wp) > real(tot, wp)) then
       rc = ndsmk_note_error(NDSMK_ENODEV, "the grid needs more device memory than the device has"//c_null_char)
       return
     end if
-    ! [B1 | Omega 0, Omega 1 | work], and for the host entry [B0 | w]
+    ! [B1 | Omega 0, Omega 1 | work], and for the host entry [B0 | w | Bobs | wm]
     total = 9_c_size_t * nb + wk
-    if (.not. on_device) total = total + merge(4_c_size_t, 3_c_size_t, c_associated(op%w)) * nb
+    if (.not. on_device) then
+      total = total + merge(4_c_size_t, 3_c_size_t, c_associated(op%w)) * nb
+      if (obs) total = total + merge(2_c_size_t, 1_c_size_t, c_associated(op%wm)) * pl3
+    end if
     rc = ndsmk_alloc(buf, total); if (rc /= 0) return
     dB1 = buf
     dO = dptr_offset(buf, 3_c_size_t * nb)
     dwork = dptr_offset(buf, 9_c_size_t * nb)
     if (on_device) then
-      dB0 = pB; dw = op%w
+      dB0 = pB; dw = op%w; dbobs = op%bobs; dwm = op%wm
     else
-      dB0 = dptr_offset(buf, 9_c_size_t * nb + wk)
+      ! (the work area's size is a multiple of 8 bytes, so every array behind it is aligned as a double)
+      at = 9_c_size_t * nb + wk
+      dB0 = dptr_offset(buf, at)
       rc = ndsmk_h2d(dB0, pB, 3_c_size_t * nb); if (rc /= 0) goto 900
+      at = at + 3_c_size_t * nb
       dw = c_null_ptr
       if (c_associated(op%w)) then
-        dw = dptr_offset(buf, 12_c_size_t * nb + wk)
+        dw = dptr_offset(buf, at)
         rc = ndsmk_h2d(dw, op%w, nb); if (rc /= 0) goto 900
+        at = at + nb
+      end if
+      dbobs = c_null_ptr
+      if (obs) then
+        dbobs = dptr_offset(buf, at)
+        rc = ndsmk_h2d(dbobs, op%bobs, pl3); if (rc /= 0) goto 900
+        at = at + pl3
+      end if
+      dwm = c_null_ptr
+      if (c_associated(op%wm)) then
+        dwm = dptr_offset(buf, at)
+        rc = ndsmk_h2d(dwm, op%wm, pl3); if (rc /= 0) goto 900
       end if
     end if
 
     rc = optimize_start(ctx, iopt, ropt, op%start, dB0, dB1, dO, n3, nb); if (rc /= 0) goto 900
 
-    call say("optimize", "Descent...")
-    call c_f_pointer(op%hist, hh, [6, int(op%hist_rows)])
-    rc = ndsmk_optimize_begin(dB0, dB1, dO, dw, dwork, n3, dq, op%dt0, op%dt_min); if (rc /= 0) goto 900
-    rc = ndsmk_optimize_row(dwork, row); if (rc /= 0) goto 900
-    hh(:, 1) = row(1:6)
-    rows = 1; tries = 0
-    lprev = row(2)
-    op%info(3) = 0
-    if (row(8) /= 0.0_wp) op%info(3) = 2
-    do while (op%info(3) == 0 .and. tries < op%niter_max)
-      n = min(op%check, op%niter_max - tries)
-      rc = ndsmk_optimize_tries(dB0, dB1, dO, dw, dwork, n3, dq, op%dt_min, n); if (rc /= 0) goto 900
-      rc = ndsmk_optimize_row(dwork, row); if (rc /= 0) goto 900
-      tries = tries + n
-      rows = min(rows + 1_c_int, op%hist_rows)
-      hh(:, rows) = row(1:6)
-      if (row(8) /= 0.0_wp) then
-        op%info(3) = 2
-      else if (n == op%check) then
-        if (lprev - row(2) <= op%tol * lprev) op%info(3) = 1
-        lprev = row(2)
+    if (obs) then
+      call say("optimize_obs", "Descent...")
+      rc = ndsmk_optimize_obs_begin(dB0, dB1, dO, dw, dbobs, dwm, dwork, n3, dq, op%nu, op%dt0, op%dt_min)
+    else
+      call say("optimize", "Descent...")
+      rc = ndsmk_optimize_begin(dB0, dB1, dO, dw, dwork, n3, dq, op%dt0, op%dt_min)
+    end if
+    if (rc /= 0) goto 900
+    rc = row(); if (rc /= 0) goto 900
+    call descent_open(lp, op%descent_ctl, merge(7, 6, obs))
+    do while (descent_more(lp, op%descent_ctl))
+      if (obs) then
+        rc = ndsmk_optimize_obs_tries(dB0, dB1, dO, dw, dbobs, dwm, dwork, n3, dq, op%nu, op%free, op%dt_min, lp%n)
+      else
+        rc = ndsmk_optimize_tries(dB0, dB1, dO, dw, dwork, n3, dq, op%dt_min, lp%n)
       end if
-      if (op%info(3) == 1) exit
+      if (rc /= 0) goto 900
+      rc = row(); if (rc /= 0) goto 900
+      call descent_note(lp, op%descent_ctl)
     end do
-    op%info(1) = rows
-    op%info(2) = int(row(1), c_int)
-    if (row(7) /= 0.0_wp) then
-      rc = ndsmk_d2d(dB0, dB1, 3_c_size_t * nb); if (rc /= 0) goto 900
-    end if
-    if (.not. on_device) then
-      rc = ndsmk_d2h(pB, dB0, 3_c_size_t * nb); if (rc /= 0) goto 900
-    end if
-    rc = ndsmk_sync()
+    rc = descent_close(lp, op%descent_ctl, dB0, dB1, 3_c_size_t * nb, pB, on_device)
 900 continue
     if (rc /= 0) op%info = 0
     call unstage(rc, [buf])
+  contains
+    function row() result(rc)
+      integer(c_int) :: rc
+      if (obs) then
+        rc = ndsmk_optimize_obs_row(dwork, lp%row)
+      else
+        rc = ndsmk_optimize_row(dwork, lp%row)
+      end if
+    end function
+  end function
+
+  ! vecpot_optimize with the measurement term and the freed lower face: the observation op%bobs is required
+  function vecpot_optimize_obs(ctx, iopt, ropt, pB, op, on_device) result(rc)
+    type(vecpot_ctx), intent(inout), target :: ctx
+    integer(ik), intent(inout) :: iopt(0:OPT_LEN - 1)
+    real(wp), intent(inout) :: ropt(0:OPT_LEN - 1)
+    type(c_ptr), intent(in) :: pB
+    type(optimize_args), intent(inout) :: op
+    logical, intent(in) :: on_device
+    integer(c_int) :: rc
+    rc = NDSMK_EARG
+    if (c_associated(op%bobs)) rc = vecpot_optimize(ctx, iopt, ropt, pB, op, on_device)
   end function
 
   ! The start field of an optimization-method call, in dB0 (DEVICE).  start = 1: the input as it is.  start = 0: the
@@ -1610,117 +1727,6 @@ contains
       rc = ndsmk_d2d(dptr_offset(dB0, int(c, c_size_t) * nb), dptr_offset(dB1, int(c, c_size_t) * nb), plane)
       if (rc /= 0) return
     end do
-  end function
-
-  ! ------------------------------------------------------------------
-  ! The optimization method with a measurement term and a freed lower face (semantics in include/ndsm_hip.h, DESIGN.md
-  ! "Measurement errors and a freed lower face").  vecpot_optimize with op%bobs (nx,ny,3) and op%wm (nx,ny,3; may be
-  ! c_null_ptr) on the side B is on: the host entry stages the two planes once, behind B and w.  The start field is
-  ! vecpot_optimize's, on B alone; the kernels are optimize_obs.hip's.  op%hist rows have 7 entries.
-  ! ------------------------------------------------------------------
-  function vecpot_optimize_obs(ctx, iopt, ropt, pB, op, on_device) result(rc)
-    type(vecpot_ctx), intent(inout), target :: ctx
-    integer(ik), intent(inout) :: iopt(0:OPT_LEN - 1)
-    real(wp), intent(inout) :: ropt(0:OPT_LEN - 1)
-    type(c_ptr), intent(in) :: pB
-    type(optimize_obs_args), intent(inout) :: op
-    logical, intent(in) :: on_device
-    integer(c_int) :: rc
-    real(wp) :: dq(3), lo(3), row(9), lprev
-    real(wp), pointer :: hh(:, :)
-    integer(c_int32_t) :: n3(3)
-    integer(c_size_t) :: nb, pl3, wk, total, fr, tot, at
-    integer(c_int) :: rows, tries, n
-    integer :: k
-    type(c_ptr) :: buf, dB0, dB1, dO, dwork, dw, dbobs, dwm
-
-    op%info = 0
-    buf = c_null_ptr
-    call ctx_mesh(ctx, n3, lo, dq)
-    nb = int(product(int(n3, ik)), c_size_t) * 8_c_size_t
-    pl3 = int(n3(1), c_size_t) * int(n3(2), c_size_t) * 24_c_size_t            ! a plane of three components
-    wk = ndsmk_optimize_obs_work_bytes()
-    ! vecpot_optimize's 13 level-1 arrays (a potential start adds the hierarchy: at least five), and the two planes
-    k = 13 + merge(5, 0, op%start == 0 .and. .not. ctx%live3)
-    rc = ndsmk_mem_info(fr, tot); if (rc /= 0) return
-    if (real(nb, wp) * real(k, wp) + 2.0_wp * real(pl3, wp) + real(wk, wp) > real(tot, wp)) then
-      rc = ndsmk_note_error(NDSMK_ENODEV, "the grid needs more device memory than the device has"//c_null_char)
-      return
-    end if
-    ! [B1 | Omega 0, Omega 1 | work], and for the host entry [B0 | w | Bobs | wm]
-    total = 9_c_size_t * nb + wk
-    if (.not. on_device) then
-      total = total + merge(4_c_size_t, 3_c_size_t, c_associated(op%w)) * nb
-      total = total + merge(2_c_size_t, 1_c_size_t, c_associated(op%wm)) * pl3
-    end if
-    rc = ndsmk_alloc(buf, total); if (rc /= 0) return
-    dB1 = buf
-    dO = dptr_offset(buf, 3_c_size_t * nb)
-    dwork = dptr_offset(buf, 9_c_size_t * nb)
-    if (on_device) then
-      dB0 = pB; dw = op%w; dbobs = op%bobs; dwm = op%wm
-    else
-      ! (the work area's size is a multiple of 8 bytes, so every array behind it is aligned as a double)
-      at = 9_c_size_t * nb + wk
-      dB0 = dptr_offset(buf, at)
-      rc = ndsmk_h2d(dB0, pB, 3_c_size_t * nb); if (rc /= 0) goto 900
-      at = at + 3_c_size_t * nb
-      dw = c_null_ptr
-      if (c_associated(op%w)) then
-        dw = dptr_offset(buf, at)
-        rc = ndsmk_h2d(dw, op%w, nb); if (rc /= 0) goto 900
-        at = at + nb
-      end if
-      dbobs = dptr_offset(buf, at)
-      rc = ndsmk_h2d(dbobs, op%bobs, pl3); if (rc /= 0) goto 900
-      at = at + pl3
-      dwm = c_null_ptr
-      if (c_associated(op%wm)) then
-        dwm = dptr_offset(buf, at)
-        rc = ndsmk_h2d(dwm, op%wm, pl3); if (rc /= 0) goto 900
-      end if
-    end if
-
-    rc = optimize_start(ctx, iopt, ropt, op%start, dB0, dB1, dO, n3, nb); if (rc /= 0) goto 900
-
-    call say("optimize_obs", "Descent...")
-    call c_f_pointer(op%hist, hh, [7, int(op%hist_rows)])
-    rc = ndsmk_optimize_obs_begin(dB0, dB1, dO, dw, dbobs, dwm, dwork, n3, dq, op%nu, op%dt0, op%dt_min)
-    if (rc /= 0) goto 900
-    rc = ndsmk_optimize_obs_row(dwork, row); if (rc /= 0) goto 900
-    hh(:, 1) = row(1:7)
-    rows = 1; tries = 0
-    lprev = row(2)
-    op%info(3) = 0
-    if (row(9) /= 0.0_wp) op%info(3) = 2
-    do while (op%info(3) == 0 .and. tries < op%niter_max)
-      n = min(op%check, op%niter_max - tries)
-      rc = ndsmk_optimize_obs_tries(dB0, dB1, dO, dw, dbobs, dwm, dwork, n3, dq, op%nu, op%free, op%dt_min, n)
-      if (rc /= 0) goto 900
-      rc = ndsmk_optimize_obs_row(dwork, row); if (rc /= 0) goto 900
-      tries = tries + n
-      rows = min(rows + 1_c_int, op%hist_rows)
-      hh(:, rows) = row(1:7)
-      if (row(9) /= 0.0_wp) then
-        op%info(3) = 2
-      else if (n == op%check) then
-        if (lprev - row(2) <= op%tol * lprev) op%info(3) = 1
-        lprev = row(2)
-      end if
-      if (op%info(3) == 1) exit
-    end do
-    op%info(1) = rows
-    op%info(2) = int(row(1), c_int)
-    if (row(8) /= 0.0_wp) then
-      rc = ndsmk_d2d(dB0, dB1, 3_c_size_t * nb); if (rc /= 0) goto 900
-    end if
-    if (.not. on_device) then
-      rc = ndsmk_d2h(pB, dB0, 3_c_size_t * nb); if (rc /= 0) goto 900
-    end if
-    rc = ndsmk_sync()
-900 continue
-    if (rc /= 0) op%info = 0
-    call unstage(rc, [buf])
   end function
 
   ! ------------------------------------------------------------------
@@ -1854,11 +1860,10 @@ contains
     type(preprocess_args), intent(inout) :: pp
     logical, intent(in) :: on_device
     integer(c_int) :: rc
-    real(wp) :: dq(3), lo(3), row(21), lprev
-    real(wp), pointer :: hh(:, :)
+    real(wp) :: dq(3), lo(3)
     integer(c_int32_t) :: n3(3)
     integer(c_size_t) :: nb, wk, total, fr, tot
-    integer(c_int) :: rows, tries, n
+    type(descent_loop) :: lp
     type(c_ptr) :: buf, dB0, dB1, dLa, dobs, dwork
 
     pp%info = 0
@@ -1899,45 +1904,22 @@ contains
     end if
 
     call say("preprocess", "Descent...")
-    call c_f_pointer(pp%hist, hh, [17, int(pp%hist_rows)])
     rc = ndsmk_preprocess_begin(dB0, dB1, dLa, dobs, dwork, n3(1:2), dq(1:2), pp%mu, pp%dt0, pp%dt_min)
     if (rc /= 0) goto 900
-    rc = ndsmk_preprocess_row(dwork, row); if (rc /= 0) goto 900
-    if (.not. (row(20) > 0.0_wp .and. row(21) > 0.0_wp)) then
+    rc = ndsmk_preprocess_row(dwork, lp%row); if (rc /= 0) goto 900
+    if (.not. (lp%row(20) > 0.0_wp .and. lp%row(21) > 0.0_wp)) then
       rc = ndsmk_note_error(NDSMK_EVALUE, "preprocess: the observation needs sum W |B|^2 > 0 and sum W r |B|^2 > 0"// &
                             c_null_char)
       goto 900
     end if
-    hh(:, 1) = row(1:17)
-    rows = 1; tries = 0
-    lprev = row(2)
-    pp%info(3) = 0
-    if (row(19) /= 0.0_wp) pp%info(3) = 2
-    do while (pp%info(3) == 0 .and. tries < pp%niter_max)
-      n = min(pp%check, pp%niter_max - tries)
-      rc = ndsmk_preprocess_tries(dB0, dB1, dLa, dobs, dwork, n3(1:2), dq(1:2), pp%mu, pp%dt_min, n)
+    call descent_open(lp, pp%descent_ctl, 17)
+    do while (descent_more(lp, pp%descent_ctl))
+      rc = ndsmk_preprocess_tries(dB0, dB1, dLa, dobs, dwork, n3(1:2), dq(1:2), pp%mu, pp%dt_min, lp%n)
       if (rc /= 0) goto 900
-      rc = ndsmk_preprocess_row(dwork, row); if (rc /= 0) goto 900
-      tries = tries + n
-      rows = min(rows + 1_c_int, pp%hist_rows)
-      hh(:, rows) = row(1:17)
-      if (row(19) /= 0.0_wp) then
-        pp%info(3) = 2
-      else if (n == pp%check) then
-        if (lprev - row(2) <= pp%tol * lprev) pp%info(3) = 1
-        lprev = row(2)
-      end if
-      if (pp%info(3) == 1) exit
+      rc = ndsmk_preprocess_row(dwork, lp%row); if (rc /= 0) goto 900
+      call descent_note(lp, pp%descent_ctl)
     end do
-    pp%info(1) = rows
-    pp%info(2) = int(row(1), c_int)
-    if (row(18) /= 0.0_wp) then
-      rc = ndsmk_d2d(dB0, dB1, nb); if (rc /= 0) goto 900
-    end if
-    if (.not. on_device) then
-      rc = ndsmk_d2h(pB, dB0, nb); if (rc /= 0) goto 900
-    end if
-    rc = ndsmk_sync()
+    rc = descent_close(lp, pp%descent_ctl, dB0, dB1, nb, pB, on_device)
 900 continue
     if (rc /= 0) pp%info = 0
     call unstage(rc, [buf])

@@ -489,9 +489,9 @@ int ndsm_hip_vecpot_optimize_device(void *h, int ioptc[16], double ropt[16], dou
  *   a NULL handle, B, Bobs, hist or info, 9004 ndsm_hip_vecpot_optimize's and: free not 0 / 1, nu negative or not
  *   finite.  A failed call clears hist and info, never B.
  *   Device memory: ndsm_hip_vecpot_optimize's (the state is 48 KiB); the host entry stages the two planes as well,
- *   once.  A grid that cannot fit is refused (9001) before any allocation.  Not included: the cascade with this term
- *   (it needs Bobs and wm per level), separate weights for L_f and L_d, freed side and top faces, z-slab worlds,
- *   non-uniform spacing. */
+ *   once.  A grid that cannot fit is refused (9001) before any allocation.  Not included: separate weights for L_f
+ *   and L_d, freed side and top faces, z-slab worlds, non-uniform spacing.  (The cascade with this term is
+ *   ndsm_hip_vecpot_optimize_obs_cascade below.) */
 /* HOST arrays */
 int ndsm_hip_vecpot_optimize_obs(void *h, int ioptc[16], double ropt[16], double *B, const double *w,
                                  const double *Bobs, const double *wm, double nu, int free, int start, int niter_max,
@@ -575,6 +575,76 @@ int ndsm_hip_vecpot_optimize_cascade_device(void *const *handles, int nlevels, i
                                             double *dB, const double *dw, int start, const int *niter_max, int check,
                                             double tol, const double *dt0, const double *dt_min, double *hist,
                                             int hist_rows, int *info);
+
+/* ---- Cascade of the measurement fit (DESIGN.md "Cascade of the measurement fit") -------------------------------------
+ * ndsm_hip_vecpot_optimize_obs run coarse-to-fine, as production codes do with measured data (Wiegelmann et al. 2012).
+ * Two things are added to the cascade above: the observation and its confidence on every level, and a paste that
+ * leaves the freed nodes alone.
+ *
+ * Confidence-weighted restriction.  The hat average is wrong for an observation with a confidence: a coarse pixel that
+ * covers one trusted and three untrusted fine pixels must take the trusted value, not the mean.  Node arrays
+ * (nx,ny,nz,ncomp) as for ndsm_hip_resample; wsrc has src's shape, wdst has dst's; nd <= ns on every axis.  All values
+ * must be FINITE (an infinite value or weight gives NaN where it is a tap).  The taps of an axis are mode 1's: a
+ * destination node with one tap - an end node, an axis of one node on both sides, an axis with ns = nd - copies it,
+ * with q = 1 and qsum = 1; any other node takes the ascending source nodes f with q_f > 0, qsum = sum q_f.  The rule
+ * is NOT normalised axis by axis.  For every destination node and component three sums run over the tensor of taps,
+ * nested as ndsm_hip_resample nests its rule - for every z tap, for every y tap, the finished x sum; then the y sum;
+ * then the z sum -, each sum left to right from its first term, each level sum double(q_f) (inner value):
+ *   num   innermost term wsrc[f] src[f]        den   innermost term wsrc[f]        pln   innermost term src[f]
+ * With Q = (double(qsum_x) double(qsum_y)) double(qsum_z):
+ *   wdst = den / Q;   dst = num / den where den > 0.0, otherwise dst = pln / Q
+ * - a patch without a trusted pixel (and a negative or NaN sum) gets the plain hat average, and wdst whatever den / Q
+ * is.  A node with one tap on every axis (a corner; every node where ns = nd on all three axes) copies: dst = src[f]
+ * itself, not (wsrc[f] src[f]) / wsrc[f], and wdst = wsrc[f].  What follows: a face, edge or corner of dst and wdst reads the same face, edge or corner of src and wsrc only;
+ * ns = nd returns both arrays bit for bit; wsrc times a power of two leaves dst bit for bit and scales wdst exactly;
+ * wsrc = 1 everywhere gives wdst = 1 exactly and dst = mode 1's value to a few ulp (one division instead of three).
+ *   Returns 0 or: 9001 without a GPU whatever the arguments; 9002 a NULL array or shape; 9004 ncomp < 1, an axis with
+ *   fewer than 2 nodes on either side unless both have 1, nd > ns on an axis.  A failed call leaves dst and wdst
+ *   untouched.  The four arrays must not overlap. */
+/* HOST arrays */
+int ndsm_hip_resample_weighted(const int nsrc[3], const int ndst[3], int ncomp, const double *src, const double *wsrc,
+                               double *dst, double *wdst);
+/* the same on DEVICE arrays of the library's GPU */
+int ndsm_hip_resample_weighted_device(const int nsrc[3], const int ndst[3], int ncomp, const double *dsrc,
+                                      const double *dwsrc, double *ddst, double *dwdst);
+
+/* The cascade.  Everything not said here is ndsm_hip_vecpot_optimize_cascade's: the handles, the boxes, G_l, w_l, the
+ * per-level options, the memory order, the return values, ioptc / ropt.  Each level is ndsm_hip_vecpot_optimize_obs.
+ *   Bobs, wm  (nx,ny,3) on the finest mesh, as for ndsm_hip_vecpot_optimize_obs; wm may be NULL.  Never written.
+ *   nu        (nlevels, on the HOST in both entries) the weight of L_m per level, index 0 the finest
+ *   free      0 or 1, shared by the levels
+ *   Level data: with wm, (Bobs_l, wm_l) = the confidence-weighted restriction of (Bobs, wm), shapes (nx,ny,1) ->
+ *     (nx_l,ny_l,1), ncomp 3, straight from the finest mesh; without wm, Bobs_l = mode-1 resample of Bobs and wm_l stays
+ *     NULL.  The planes are computed with the G_l and lie beside them.
+ *   Level L runs with the caller's start on G_L (the start field is built from G_L alone), with Bobs_L, wm_L, nu[L].
+ *   A finer level l starts from the mode-0 resample of level l + 1's result.  free 0: the paste of
+ *     ndsm_hip_vecpot_optimize_cascade (start 0: the k = 0 plane of G_l, start 1: its six faces).  free 1: the same
+ *     paste WITHOUT the nodes of the k = 0 plane with 1 <= i <= nx_l - 2 and 1 <= j <= ny_l - 2 - start 0: the rim of the
+ *     k = 0 plane only; start 1: the six faces minus those nodes.  The freed nodes keep the interpolated values: the
+ *     level below has already moved them towards the fit, and G_l there would undo that.  Then
+ *     ndsm_hip_vecpot_optimize_obs_device with start 1, Bobs_l, wm_l, nu[l].
+ *   hist      (nlevels, hist_rows, 7), info (nlevels, 3): each level's are ndsm_hip_vecpot_optimize_obs's.
+ *   nlevels = 1 is ndsm_hip_vecpot_optimize_obs bit for bit, in B, hist and info.  free 0 with every nu[l] = 0 is
+ *   ndsm_hip_vecpot_optimize_cascade bit for bit in B, info and the columns of hist they share, whatever Bobs and wm
+ *   hold.
+ *   Errors: the union of the two parents', in ndsm_hip_vecpot_optimize_cascade's order: 9002 also for a NULL Bobs or
+ *   nu; 9004 also for free not 0 / 1 or a nu[l] negative or not finite.  A failed call clears hist and info, never B.
+ *   Device memory: the peak stays ndsm_hip_vecpot_optimize_obs's on the finest mesh, refused (9001) before any
+ *   allocation when it cannot fit.  The host entry stages B, w, Bobs and wm once; only history rows cross PCIe in
+ *   between.  Not included: freed side and top faces, a potential solve on every level, z-slab worlds, non-uniform
+ *   spacing, a final ndsm_hip_vecpot_project. */
+/* HOST arrays */
+int ndsm_hip_vecpot_optimize_obs_cascade(void *const *handles, int nlevels, int ioptc[16], double ropt[16], double *B,
+                                         const double *w, const double *Bobs, const double *wm, const double *nu,
+                                         int free, int start, const int *niter_max, int check, double tol,
+                                         const double *dt0, const double *dt_min, double *hist, int hist_rows,
+                                         int *info);
+/* the same on DEVICE arrays of the library's GPU (nu, the per-level arrays, hist and info stay on the host) */
+int ndsm_hip_vecpot_optimize_obs_cascade_device(void *const *handles, int nlevels, int ioptc[16], double ropt[16],
+                                                double *dB, const double *dw, const double *dBobs, const double *dwm,
+                                                const double *nu, int free, int start, const int *niter_max, int check,
+                                                double tol, const double *dt0, const double *dt_min, double *hist,
+                                                int hist_rows, int *info);
 
 /* ---- Magnetogram preprocessing (DESIGN.md "Magnetogram preprocessing") ---------------------------------------------
  * What comes before ndsm_hip_vecpot_optimize when the lower-face data are measured (Wiegelmann, Inhester & Sakurai

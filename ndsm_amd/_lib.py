@@ -121,6 +121,13 @@ def load_library(path=None):
     _rs = [_ip, _ip, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     L.ndsm_hip_resample.argtypes = _rs
     L.ndsm_hip_resample_device.argtypes = _rs
+    _rw = [_ip, _ip, ctypes.c_int] + [ctypes.c_void_p] * 4
+    L.ndsm_hip_resample_weighted.argtypes = _rw
+    L.ndsm_hip_resample_weighted_device.argtypes = _rw
+    _obc = ([ctypes.c_void_p, ctypes.c_int, _ip, _dp] + [ctypes.c_void_p] * 5 + [ctypes.c_int, ctypes.c_int,
+            ctypes.c_void_p, ctypes.c_int, ctypes.c_double] + [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p])
+    L.ndsm_hip_vecpot_optimize_obs_cascade.argtypes = _obc
+    L.ndsm_hip_vecpot_optimize_obs_cascade_device.argtypes = _obc
     _pp = ([ctypes.c_void_p] * 4 + [ctypes.c_int] * 2 + [ctypes.c_double] * 3 +
            [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p])
     L.ndsm_hip_vecpot_preprocess.argtypes = _pp
@@ -776,41 +783,10 @@ class VecPot:
         check, tol and hist_rows are shared.  Returns (ierr, B, hist, info): hist a list of per-level arrays
         (rows, 6), info a list of per-level tuples, both as optimize() gives them; ierr 1 when the coarsest level's
         potential solve missed vc_tol.  No coarser handle: optimize() itself, bit for bit."""
-        levels = [self] + list(coarser)
+        levels, nit, d0, dm, hist_rows, hist, info, B, W = self._cascade_setup(
+            "optimize_cascade", coarser, b, w, start, niter_max, check, tol, dt0, dt_min, hist_rows, 6)
         nl = len(levels)
-        if start not in ("potential", "given"):
-            raise ValueError(f"start must be 'potential' or 'given', not {start!r}")
-
-        def each(name, v):
-            if isinstance(v, (list, tuple, np.ndarray)):
-                if len(v) != nl:
-                    raise ValueError(f"{name} needs one value per level ({nl}), not {len(v)}")
-                return list(v)
-            return [v] * nl
-        nit, d0, dm = each("niter_max", niter_max), each("dt0", dt0), each("dt_min", dt_min)
-        hist_rows, hist, info = _descent_options(nit, check, tol, d0, dm, hist_rows, 6, nl)
-        for V in levels[1:]:
-            if not isinstance(V, VecPot):
-                raise ValueError(f"coarser must hold VecPot handles, not {type(V).__name__}")
-        for fine, V in zip(levels, levels[1:]):
-            if any(int(c) > int(f) for c, f in zip(V.nshape4[:3], fine.nshape4[:3])):
-                raise ValueError(f"a coarser level has more nodes than the level before it: {tuple(V.nshape4[:3])} "
-                                 f"after {tuple(fine.nshape4[:3])}")
-            for q, r in zip((V.x, V.y, V.z), (self.x, self.y, self.z)):
-                if q[0].tobytes() != r[0].tobytes() or q[-1].tobytes() != r[-1].tobytes():
-                    raise ValueError("every level must span the box of the finest mesh: first and last coordinates "
-                                     f"{q[0]!r}, {q[-1]!r} against {r[0]!r}, {r[-1]!r}")
         shape = tuple(int(v) for v in self.nshape4[::-1])
-        B = self._field_arg(b, "optimize_cascade")
-        W = None
-        if w is not None:
-            W = np.asarray(w)
-            if W.shape != shape[1:]:
-                raise NdsmHipError(f"optimize_cascade: weight of shape {W.shape}, the handle's grid needs {shape[1:]} "
-                                   "(code 9002)")
-            W = _f64(W).reshape(-1).copy()
-        for l, V in enumerate(levels):
-            d0[l], dm[l] = _descent_steps(d0[l], dm[l], V._dt0_default())
         ioptc, ropt = self._options(niterex_max, ncycles_max, ex_tol, vc_tol, ms, mean, mixed_precision, flxcrl)
         ioptc[self.L.get_iopt_ngrids()] = levels[-1].ngrids
         handles = (ctypes.c_void_p * nl)(*[V.h for V in levels])
@@ -829,6 +805,103 @@ class VecPot:
             ierr = self._on_device([B, W], lambda dB, dW: call(self.L.ndsm_hip_vecpot_optimize_cascade_device, dB, dW))
         if ierr >= 9000:
             _check(ierr, "ndsm_hip_vecpot_optimize_cascade", self.L)
+        self.last_ioptc, self.last_ropt = ioptc, ropt
+        per_level = [_descent_result(hist[l], info[l]) for l in range(nl)]
+        return ierr, B.reshape(shape), [h for h, _ in per_level], [i for _, i in per_level]
+
+    def _cascade_setup(self, who, coarser, b, w, start, niter_max, check, tol, dt0, dt_min, hist_rows, width):
+        """What optimize_cascade() and optimize_obs_cascade() share, checked before the library is reached: (levels,
+        niter_max, dt0, dt_min per level - the steps with their defaults -, hist_rows, hist, info, B, W)"""
+        levels = [self] + list(coarser)
+        nl = len(levels)
+        if start not in ("potential", "given"):
+            raise ValueError(f"start must be 'potential' or 'given', not {start!r}")
+        nit, d0, dm = (_per_level(name, v, nl) for name, v in (("niter_max", niter_max), ("dt0", dt0), ("dt_min", dt_min)))
+        hist_rows, hist, info = _descent_options(nit, check, tol, d0, dm, hist_rows, width, nl)
+        for V in levels[1:]:
+            if not isinstance(V, VecPot):
+                raise ValueError(f"coarser must hold VecPot handles, not {type(V).__name__}")
+        for fine, V in zip(levels, levels[1:]):
+            if any(int(c) > int(f) for c, f in zip(V.nshape4[:3], fine.nshape4[:3])):
+                raise ValueError(f"a coarser level has more nodes than the level before it: {tuple(V.nshape4[:3])} "
+                                 f"after {tuple(fine.nshape4[:3])}")
+            for q, r in zip((V.x, V.y, V.z), (self.x, self.y, self.z)):
+                if q[0].tobytes() != r[0].tobytes() or q[-1].tobytes() != r[-1].tobytes():
+                    raise ValueError("every level must span the box of the finest mesh: first and last coordinates "
+                                     f"{q[0]!r}, {q[-1]!r} against {r[0]!r}, {r[-1]!r}")
+        shape = tuple(int(v) for v in self.nshape4[::-1])
+        B = self._field_arg(b, who)
+        W = None
+        if w is not None:
+            W = np.asarray(w)
+            if W.shape != shape[1:]:
+                raise NdsmHipError(f"{who}: weight of shape {W.shape}, the handle's grid needs {shape[1:]} "
+                                   "(code 9002)")
+            W = _f64(W).reshape(-1).copy()
+        for l, V in enumerate(levels):
+            d0[l], dm[l] = _descent_steps(d0[l], dm[l], V._dt0_default())
+        return levels, nit, d0, dm, hist_rows, hist, info, B, W
+
+    def optimize_obs_cascade(self, coarser, b, bobs=None, wm=None, nu=0.01, free=True, w=None, start="potential",
+                             niter_max=10000, check=50, tol=1e-4, dt0=None, dt_min=None, hist_rows=None,
+                             niterex_max=10000, ncycles_max=1024, ex_tol=1e-13, vc_tol=1e-10, ms=5, mean=False,
+                             mixed_precision=False, flxcrl=False, device=False):
+        """optimize_obs() as a coarse-to-fine cascade (semantics: include/ndsm_hip.h,
+        ndsm_hip_vecpot_optimize_obs_cascade): the handles, b, w and the per-level options as optimize_cascade(); bobs,
+        wm, free as optimize_obs(), on this handle's lower face (bobs None: a copy of b's k = 0 plane).  nu: one value
+        for every level or a sequence, one per level, finest first.  Every coarser level gets the confidence-weighted
+        restriction of (bobs, wm) - resample_weighted() -, or the hat average of bobs when wm is None.  The coarsest
+        level runs optimize_obs() with `start`; every finer level starts from the interpolated result of the level
+        below with its own average of b pasted over the k = 0 plane ("potential") or the six faces ("given") - with
+        free=True without the freed nodes of the k = 0 plane, which keep what the level below has fitted.  Returns
+        (ierr, B, hist, info): hist a list of per-level arrays (rows, 7), info a list of per-level tuples, both as
+        optimize_obs() gives them.  No coarser handle: optimize_obs() itself, bit for bit; free=False with nu = 0:
+        optimize_cascade() bit for bit."""
+        if free not in (True, False, 0, 1):
+            raise ValueError(f"free must be True or False, not {free!r}")
+        levels, nit, d0, dm, hist_rows, hist, info, B, W = self._cascade_setup(
+            "optimize_obs_cascade", coarser, b, w, start, niter_max, check, tol, dt0, dt_min, hist_rows, 7)
+        nl = len(levels)
+        nus = _per_level("nu", nu, nl)
+        for v in nus:
+            if not (v >= 0.0 and np.isfinite(v)):
+                raise ValueError(f"nu must be finite and >= 0, not {v!r}")
+        shape = tuple(int(v) for v in self.nshape4[::-1])
+        pshape = (3,) + shape[2:]
+        planes = []
+        for name, v in (("observation", bobs), ("measurement weight", wm)):
+            if v is None:
+                planes.append(None)
+                continue
+            a = np.asarray(v)
+            if a.shape != pshape:
+                raise NdsmHipError(f"optimize_obs_cascade: {name} of shape {a.shape}, the handle's lower face needs "
+                                   f"{pshape} (code 9002)")
+            planes.append(_f64(a).reshape(-1).copy())
+        if planes[0] is None:
+            planes[0] = B.reshape(shape)[:, 0].reshape(-1).copy()
+        ioptc, ropt = self._options(niterex_max, ncycles_max, ex_tol, vc_tol, ms, mean, mixed_precision, flxcrl)
+        ioptc[self.L.get_iopt_ngrids()] = levels[-1].ngrids
+        handles = (ctypes.c_void_p * nl)(*[V.h for V in levels])
+        nit_a = np.array([int(v) for v in nit], dtype=np.intc)
+        d0_a, dm_a = np.array(d0, dtype=np.float64), np.array(dm, dtype=np.float64)
+        nu_a = np.array([float(v) for v in nus], dtype=np.float64)
+        arrays = [B, W] + planes
+
+        def call(fn, ptrs):
+            return fn(handles, nl, ioptc.ctypes.data_as(_ip), _d(ropt), *ptrs, nu_a.ctypes.data, int(bool(free)),
+                      0 if start == "potential" else 1, nit_a.ctypes.data, int(check), float(tol), d0_a.ctypes.data,
+                      dm_a.ctypes.data, hist.ctypes.data, int(hist_rows), info.ctypes.data)
+        if not device:
+            ierr = call(self.L.ndsm_hip_vecpot_optimize_obs_cascade, [None if a is None else a.ctypes.data for a in arrays])
+        else:
+            def on_device(*dev):
+                it = iter(dev)
+                return call(self.L.ndsm_hip_vecpot_optimize_obs_cascade_device,
+                            [None if a is None else next(it) for a in arrays])
+            ierr = self._on_device([a for a in arrays if a is not None], on_device)
+        if ierr >= 9000:
+            _check(ierr, "ndsm_hip_vecpot_optimize_obs_cascade", self.L)
         self.last_ioptc, self.last_ropt = ioptc, ropt
         per_level = [_descent_result(hist[l], info[l]) for l in range(nl)]
         return ierr, B.reshape(shape), [h for h, _ in per_level], [i for _, i in per_level]
@@ -1286,6 +1359,15 @@ def _descent_options(niter_max, check, tol, dt0, dt_min, hist_rows, width, nleve
         raise ValueError(f"hist_rows must be a whole number >= 2, not {hist_rows!r}")
     lead = () if nlevels is None else (nlevels,)
     return hist_rows, np.zeros(lead + (int(hist_rows), width)), np.zeros(lead + (3,), dtype=np.intc)
+
+
+def _per_level(name, v, nlevels):
+    """a per-level option of a cascade as a list: one value for every level, or a sequence with one per level"""
+    if isinstance(v, (list, tuple, np.ndarray)):
+        if len(v) != nlevels:
+            raise ValueError(f"{name} needs one value per level ({nlevels}), not {len(v)}")
+        return list(v)
+    return [v] * nlevels
 
 
 def _descent_steps(dt0, dt_min, dt0_default):
@@ -1854,6 +1936,57 @@ def resample(a, shape, mode="linear", device=False, lib=None):
     return D.reshape(src.shape[:-3] + dshape)
 
 
+def resample_weighted(a, wa, shape, device=False, lib=None):
+    """The confidence-weighted restriction of an observation a with its confidence wa (the same shape) to a coarser
+    uniform mesh on the same box, on the device (semantics: include/ndsm_hip.h, ndsm_hip_resample_weighted): every
+    destination node takes sum q wa a / sum q wa over the taps of the hat average - a trusted pixel among untrusted
+    ones gives its own value, not the mean -, its confidence the hat average of wa; where no tap is trusted, the plain
+    hat average.  a: (ncomp, nz, ny, nx) or (nz, ny, nx), planes with nz = 1; shape: the destination (nz, ny, nx), no
+    axis finer than a's.  The values must be finite.  Returns (a', wa').  device=True: the arrays are staged in device
+    memory and the device-resident entry point runs."""
+    src, wsrc = np.asarray(a), np.asarray(wa)
+    if src.ndim not in (3, 4) or src.size == 0:
+        raise NdsmHipError(f"resample_weighted: an array of shape {src.shape}, (ncomp, nz, ny, nx) or (nz, ny, nx) is "
+                           "needed (code 9002)")
+    if wsrc.shape != src.shape:
+        raise NdsmHipError(f"resample_weighted: a confidence of shape {wsrc.shape} for an array of shape {src.shape} "
+                           "(code 9002)")
+    dshape = tuple(int(v) for v in shape)
+    if len(dshape) != 3 or any(int(v) != v for v in shape):
+        raise ValueError(f"shape must be three whole numbers (nz, ny, nx), not {shape!r}")
+    ncomp = 1 if src.ndim == 3 else src.shape[0]
+    sshape = src.shape[-3:]
+    for ns, nd in zip(sshape, dshape):
+        if not ((ns == 1 and nd == 1) or (ns >= 2 and nd >= 2)):
+            raise ValueError(f"an axis needs at least 2 nodes on both sides, or 1 on both: {sshape} -> {dshape}")
+        if nd > ns:
+            raise ValueError(f"the weighted restriction cannot refine: {sshape} -> {dshape}")
+    L = lib or load_library()
+    S, WS = _f64(src).reshape(-1).copy(), _f64(wsrc).reshape(-1).copy()
+    D, WD = np.zeros(ncomp * int(np.prod(dshape))), np.zeros(ncomp * int(np.prod(dshape)))
+    ns3, nd3 = np.array(sshape[::-1], dtype=np.intc), np.array(dshape[::-1], dtype=np.intc)
+    args = (ns3.ctypes.data_as(_ip), nd3.ctypes.data_as(_ip), ncomp)
+    if not device:
+        _check(L.ndsm_hip_resample_weighted(*args, S.ctypes.data, WS.ctypes.data, D.ctypes.data, WD.ctypes.data),
+               "ndsm_hip_resample_weighted", L)
+    else:
+        ptrs = []
+        try:
+            for h in (S, WS, D, WD):
+                p = ctypes.c_void_p()
+                _check(L.ndsm_hip_device_alloc(h.nbytes, ctypes.byref(p)), "device_alloc", L)
+                ptrs.append(p)
+            _check(L.ndsm_hip_memcpy_h2d(ptrs[0], S.ctypes.data, S.nbytes), "h2d", L)
+            _check(L.ndsm_hip_memcpy_h2d(ptrs[1], WS.ctypes.data, WS.nbytes), "h2d", L)
+            _check(L.ndsm_hip_resample_weighted_device(*args, *ptrs), "ndsm_hip_resample_weighted_device", L)
+            _check(L.ndsm_hip_memcpy_d2h(D.ctypes.data, ptrs[2], D.nbytes), "d2h", L)
+            _check(L.ndsm_hip_memcpy_d2h(WD.ctypes.data, ptrs[3], WD.nbytes), "d2h", L)
+        finally:
+            for p in ptrs:
+                L.ndsm_hip_device_free(p)
+    return D.reshape(src.shape[:-3] + dshape), WD.reshape(src.shape[:-3] + dshape)
+
+
 def cascade_shapes(shape, levels, min_nodes=4):
     """The shapes (nz, ny, nx) of a cascade of that many levels, finest first: each axis follows n -> (n + 1) // 2
     (33 -> 17, 32 -> 16, 9 -> 5); an axis that would fall below min_nodes stays where it is.  ValueError when a
@@ -1878,17 +2011,9 @@ def force_free_cascade(x, y, z, b, levels=3, shapes=None, w=None, start="potenti
     of every level, finest first (None: cascade_shapes() of b's grid for `levels`); every level's mesh is
     linspace(first, last, n) per axis, which keeps the end coordinates exact.  Raises NdsmHipError on device /
     argument errors."""
-    x, y, z = _f64(x), _f64(y), _f64(z)
-    if shapes is None:
-        shapes = cascade_shapes((len(z), len(y), len(x)), levels)
-    shapes = [tuple(int(n) for n in s) for s in shapes]
-    if not shapes or shapes[0] != (len(z), len(y), len(x)):
-        raise ValueError(f"shapes must start with the finest grid {(len(z), len(y), len(x))}, not {shapes[:1]}")
     handles = []
     try:
-        handles.append(VecPot(x, y, z, lib=lib))
-        for nz, ny, nx in shapes[1:]:
-            handles.append(VecPot(*[np.linspace(q[0], q[-1], n) for q, n in ((x, nx), (y, ny), (z, nz))], lib=lib))
+        _cascade_handles(handles, x, y, z, levels, shapes, lib)
         return handles[0].optimize_cascade(handles[1:], b, w=w, start=start, niter_max=niter_max, check=check, tol=tol,
                                            dt0=dt0, dt_min=dt_min, hist_rows=hist_rows, niterex_max=niterex_max,
                                            ncycles_max=ncycles_max, ex_tol=ex_tol, vc_tol=vc_tol, ms=ms, mean=mean,
@@ -1896,6 +2021,39 @@ def force_free_cascade(x, y, z, b, levels=3, shapes=None, w=None, start="potenti
     finally:
         for V in handles:
             V.close()
+
+
+def force_free_obs_cascade(x, y, z, b, levels=3, shapes=None, bobs=None, wm=None, nu=0.01, free=True, w=None,
+                           start="potential", niter_max=10000, check=50, tol=1e-4, dt0=None, dt_min=None,
+                           hist_rows=None, niterex_max=10000, ncycles_max=1024, ex_tol=1e-13, vc_tol=1e-10, ms=5,
+                           mean=False, mixed_precision=False, flxcrl=False, lib=None):
+    """Nonlinear force-free field whose lower face is fitted to the measured magnetogram bobs within its errors wm, run
+    as a coarse-to-fine cascade: one-shot form of VecPot.optimize_obs_cascade (returns its (ierr, B, hist, info)).
+    levels, shapes and the meshes as force_free_cascade.  Raises NdsmHipError on device / argument errors."""
+    handles = []
+    try:
+        _cascade_handles(handles, x, y, z, levels, shapes, lib)
+        return handles[0].optimize_obs_cascade(handles[1:], b, bobs=bobs, wm=wm, nu=nu, free=free, w=w, start=start,
+                                               niter_max=niter_max, check=check, tol=tol, dt0=dt0, dt_min=dt_min,
+                                               hist_rows=hist_rows, niterex_max=niterex_max, ncycles_max=ncycles_max,
+                                               ex_tol=ex_tol, vc_tol=vc_tol, ms=ms, mean=mean,
+                                               mixed_precision=mixed_precision, flxcrl=flxcrl)
+    finally:
+        for V in handles:
+            V.close()
+
+
+def _cascade_handles(handles, x, y, z, levels, shapes, lib):
+    """appends the handles of a one-shot cascade's levels, finest first, to `handles` (the caller closes them)"""
+    x, y, z = _f64(x), _f64(y), _f64(z)
+    if shapes is None:
+        shapes = cascade_shapes((len(z), len(y), len(x)), levels)
+    shapes = [tuple(int(n) for n in s) for s in shapes]
+    if not shapes or shapes[0] != (len(z), len(y), len(x)):
+        raise ValueError(f"shapes must start with the finest grid {(len(z), len(y), len(x))}, not {shapes[:1]}")
+    handles.append(VecPot(x, y, z, lib=lib))
+    for nz, ny, nx in shapes[1:]:
+        handles.append(VecPot(*[np.linspace(q[0], q[-1], n) for q, n in ((x, nx), (y, ny), (z, nz))], lib=lib))
 
 
 def preprocess_magnetogram(x, y, z, bm, obs=None, mu=(1, 1, 1e-3, 1e-2, 1e-2), niter_max=10000, check=50, tol=1e-4,

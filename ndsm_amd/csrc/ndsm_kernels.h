@@ -242,9 +242,15 @@ int ndsmk_optimize_obs_row(const double *work, double *h_row9);
 /* The coarse-to-fine cascade's level changes (resample.hip; semantics: include/ndsm_hip.h, ndsm_hip_resample).
  * resample: dst (ndst3, ncomp) = src (nsrc3, ncomp) resampled on the same box, mode 0 linear interpolation, mode 1 hat
  * average (no axis of dst finer than src's); DEVICE arrays that do not overlap; 9004 for a bad ncomp, mode or shape.
- * paste_faces: dst = src on the k = 0 plane (which = 0) or on the six faces (which = 1) of two (n3, ncomp) arrays.
- * Both asynchronous. */
+ * resample_weighted: (dst, wdst) (ndst3, ncomp) = the confidence-weighted restriction of the observation src with its
+ * confidence wsrc (nsrc3, ncomp) (semantics: ndsm_hip_resample_weighted); no axis of dst finer than src's; four DEVICE
+ * arrays that do not overlap, finite values; 9004 for a bad ncomp or shape.
+ * paste_faces: dst = src on the k = 0 plane (which = 0) or on the six faces (which = 1) of two (n3, ncomp) arrays;
+ * which = 2, 3: the same minus the nodes of the k = 0 plane off its rim.
+ * All asynchronous. */
 int ndsmk_resample(const int32_t *nsrc3, const int32_t *ndst3, int ncomp, int mode, const double *src, double *dst);
+int ndsmk_resample_weighted(const int32_t *nsrc3, const int32_t *ndst3, int ncomp, const double *src,
+                            const double *wsrc, double *dst, double *wdst);
 int ndsmk_paste_faces(const int32_t *n3, int ncomp, int which, const double *src, double *dst);
 
 /* Magnetogram preprocessing (preprocess.hip; semantics: include/ndsm_hip.h, ndsm_hip_vecpot_preprocess).  B0, B1

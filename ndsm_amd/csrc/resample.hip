@@ -13,9 +13,19 @@
 //                    several give (sum double(q_f) v[f]) / double(sum q_f), the sum left to right from its first term.
 //                An axis of one node on both sides is copied.  A destination face, edge or corner reads the same
 //                face, edge or corner of the source only.
-//   paste_k    : dst = src on the k = 0 plane (which = 0) or on all six faces (which = 1) of two arrays of one shape.
+//   resample_weighted_k : the confidence-weighted restriction of an observation v with its confidence w (nd <= ns;
+//                DESIGN.md "Cascade of the measurement fit"), one thread per destination node and component, the grid
+//                and the taps of mode 1.  NOT normalised axis by axis: three sums run over the tensor of taps, nested
+//                as above, each level sum double(q_f) (inner value) left to right from its first term - num from
+//                w[f] v[f], den from w[f], pln from v[f].  A node with one tap on an axis (an end node, an axis of one
+//                node, an axis with ns = nd) copies it: q = 1 and qsum = 1 there.  Q = (qsum_x qsum_y) qsum_z in
+//                doubles; wdst = den / Q; dst = num / den where den > 0.0, otherwise pln / Q (the plain hat average).
+//                A node with one tap on every axis copies v[f] and w[f]: ns = nd returns both arrays bit for bit.
+//   paste_k    : dst = src on the k = 0 plane (which = 0) or on all six faces (which = 1) of two arrays of one shape;
+//                which = 2 and 3 are the same two minus the nodes of the k = 0 plane off its rim (the freed nodes).
 //
-// Plain C++ under -ffp-contract=off: the operand order above is the bits, and tests/cascade_model.py restates it.
+// Plain C++ under -ffp-contract=off: the operand order above is the bits, and tests/cascade_model.py and
+// tests/obs_cascade_model.py restate it.
 #include "common.hpp"
 
 namespace {
@@ -121,18 +131,82 @@ __global__ __launch_bounds__(256) void resample_k(const double *__restrict__ src
   }
 }
 
+// the three sums of the weighted rule over the taps seen so far
+struct WSums {
+  double num, den, pln;
+};
+
+// one level of the weighted rule: sum double(q_f) (inner sums), left to right from its first term; a single tap has q = 1
+template <class F>
+__device__ __forceinline__ WSums wcombine(const Taps &t, F val) {
+  WSums a = val(t.lo);
+  if (t.cnt == 1) return a;
+  const double q0 = (double)hat_q(t, t.lo);
+  a.num = q0 * a.num;
+  a.den = q0 * a.den;
+  a.pln = q0 * a.pln;
+  for (int m = 1; m < t.cnt; ++m) {
+    const double q = (double)hat_q(t, t.lo + m);
+    const WSums b = val(t.lo + m);
+    a.num = a.num + q * b.num;
+    a.den = a.den + q * b.den;
+    a.pln = a.pln + q * b.pln;
+  }
+  return a;
+}
+
+__device__ __forceinline__ double wq_sum(const Taps &t) { return t.cnt == 1 ? 1.0 : (double)t.qsum; }
+
+__global__ __launch_bounds__(256) void resample_weighted_k(const double *__restrict__ src, const double *__restrict__ wsrc,
+                                                           double *__restrict__ dst, double *__restrict__ wdst, ResArgs p) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= p.nd[0]) return;
+  const size_t sxs = (size_t)p.ns[0], sys = sxs * (size_t)p.ns[1], Ns = sys * (size_t)p.ns[2];
+  const size_t sxd = (size_t)p.nd[0], syd = sxd * (size_t)p.nd[1], Nd = syd * (size_t)p.nd[2];
+  const Taps tx = taps_of(i, p.ns[0], p.nd[0], 1);
+  const i64 planes = (i64)p.nd[2] * (i64)p.ncomp;
+  for (int j = blockIdx.y * blockDim.y + threadIdx.y; j < p.nd[1]; j += gridDim.y * blockDim.y) {
+    const Taps ty = taps_of(j, p.ns[1], p.nd[1], 1);
+    for (i64 kc = blockIdx.z; kc < planes; kc += gridDim.z) {
+      i64 kk;
+      const size_t c = (size_t)div_mod(kc, (i64)p.nd[2], kk);
+      const int k = (int)kk;
+      const Taps tz = taps_of(k, p.ns[2], p.nd[2], 1);
+      const double *v = src + c * Ns, *w = wsrc + c * Ns;
+      const WSums s = wcombine(tz, [&](i64 fz) {
+        return wcombine(ty, [&](i64 fy) {
+          const size_t row = sys * (size_t)fz + sxs * (size_t)fy;
+          return wcombine(tx, [&](i64 fx) {
+            const double wf = w[row + (size_t)fx], vf = v[row + (size_t)fx];
+            return WSums{wf * vf, wf, vf};
+          });
+        });
+      });
+      const double Q = (wq_sum(tx) * wq_sum(ty)) * wq_sum(tz);
+      const size_t at = c * Nd + (size_t)i + sxd * (size_t)j + syd * (size_t)k;
+      wdst[at] = s.den / Q;
+      // (one tap in all: the value itself, not (w v) / w)
+      const bool copy = tx.cnt == 1 && ty.cnt == 1 && tz.cnt == 1;
+      dst[at] = copy ? s.pln : (s.den > 0.0 ? s.num / s.den : s.pln / Q);
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void paste_k(const double *__restrict__ src, double *__restrict__ dst, int nx, int ny,
                                                int nz, int ncomp, int which) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nx) return;
   const size_t sy = (size_t)nx, sz = sy * (size_t)ny, N = sz * (size_t)nz;
-  const i64 planes = which ? (i64)nz * (i64)ncomp : (i64)ncomp;
+  const bool box = which == 1 || which == 3;     // all six faces; otherwise the k = 0 plane alone
+  const i64 planes = box ? (i64)nz * (i64)ncomp : (i64)ncomp;
   for (int j = blockIdx.y * blockDim.y + threadIdx.y; j < ny; j += gridDim.y * blockDim.y) {
+    const bool rim = i == 0 || i == nx - 1 || j == 0 || j == ny - 1;
     for (i64 kc = blockIdx.z; kc < planes; kc += gridDim.z) {
       i64 kk = 0;
-      const size_t c = (size_t)(which ? div_mod(kc, (i64)nz, kk) : kc);
+      const size_t c = (size_t)(box ? div_mod(kc, (i64)nz, kk) : kc);
       const int k = (int)kk;
-      if (which && !(i == 0 || i == nx - 1 || j == 0 || j == ny - 1 || k == 0 || k == nz - 1)) continue;
+      if (box && !(rim || k == 0 || k == nz - 1)) continue;
+      if (which >= 2 && k == 0 && !rim) continue;      // the freed nodes keep what they hold
       const size_t at = c * N + (size_t)i + sy * (size_t)j + sz * (size_t)k;
       dst[at] = src[at];
     }
@@ -170,11 +244,38 @@ extern "C" int ndsmk_resample(const int32_t *nsrc3, const int32_t *ndst3, int nc
   return 0;
 }
 
-// dst = src on the k = 0 plane (which = 0) or on the six faces (which = 1); both (n3, ncomp), DEVICE.  Asynchronous.
+// (dst, wdst) (ndst, ncomp) = the confidence-weighted restriction of (src, wsrc) (nsrc, ncomp), four DEVICE arrays that
+// do not overlap; finite values.  Asynchronous.
+extern "C" int ndsmk_resample_weighted(const int32_t *nsrc3, const int32_t *ndst3, int ncomp, const double *src,
+                                       const double *wsrc, double *dst, double *wdst) {
+  NDSM_REQUIRE_READY();
+  NDSM_CHECK_ARG(nsrc3 && ndst3 && src && wsrc && dst && wdst);
+  ResArgs p;
+  p.ncomp = ncomp;
+  p.mode = 1;
+  bool ok = ncomp >= 1;
+  for (int d = 0; d < 3; ++d) {
+    p.ns[d] = nsrc3[d];
+    p.nd[d] = ndst3[d];
+    const bool one = nsrc3[d] == 1 && ndst3[d] == 1;
+    ok = ok && (one || (nsrc3[d] >= 2 && ndst3[d] >= 2)) && ndst3[d] <= nsrc3[d];
+  }
+  if (!ok)
+    return ndsmk_note_error(NDSMK_EVALUE, "resample_weighted: ncomp >= 1, at least 2 nodes per axis on both sides (or 1 "
+                                          "on both), and no axis finer than its source");
+  hipLaunchKernelGGL(resample_weighted_k, grid_of(p.nd[0], p.nd[1], (i64)p.nd[2] * ncomp), dim3(64, 4, 1), 0,
+                     ndsm::stream(), src, wsrc, dst, wdst, p);
+  NDSM_LAUNCH_CHECK();
+  return 0;
+}
+
+// dst = src on the k = 0 plane (which = 0) or on the six faces (which = 1), or on those minus the nodes of the k = 0
+// plane off its rim (which = 2, 3); both (n3, ncomp), DEVICE.  Asynchronous.
 extern "C" int ndsmk_paste_faces(const int32_t *n3, int ncomp, int which, const double *src, double *dst) {
   NDSM_REQUIRE_READY();
-  NDSM_CHECK_ARG(n3 && src && dst && ncomp >= 1 && (which == 0 || which == 1) && n3[0] >= 1 && n3[1] >= 1 && n3[2] >= 1);
-  hipLaunchKernelGGL(paste_k, grid_of(n3[0], n3[1], which ? (i64)n3[2] * ncomp : (i64)ncomp), dim3(64, 4, 1), 0,
+  NDSM_CHECK_ARG(n3 && src && dst && ncomp >= 1 && which >= 0 && which <= 3 && n3[0] >= 1 && n3[1] >= 1 && n3[2] >= 1);
+  const bool box = which == 1 || which == 3;
+  hipLaunchKernelGGL(paste_k, grid_of(n3[0], n3[1], box ? (i64)n3[2] * ncomp : (i64)ncomp), dim3(64, 4, 1), 0,
                      ndsm::stream(), src, dst, n3[0], n3[1], n3[2], ncomp, which);
   NDSM_LAUNCH_CHECK();
   return 0;

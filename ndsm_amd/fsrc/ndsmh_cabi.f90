@@ -1443,9 +1443,12 @@ contains
                                  hist, hist_rows, info, .true., "ndsm_hip_vecpot_optimize_cascade_device")
   end function
 
+  ! the two entries above and the two below: with Bobs (and then wm, nu, free) every level is the measurement fit
   function vecpot_handle_cascade(handles, nlevels, ioptc, ropt, B, w, start, niter_max, check, tol, dt0, dt_min, hist, &
-                                 hist_rows, info, on_device, who) result(ierr)
+                                 hist_rows, info, on_device, who, Bobs, wm, nu, free) result(ierr)
     type(c_ptr), intent(in) :: handles, B, w, niter_max, dt0, dt_min, hist, info
+    type(c_ptr), intent(in), optional :: Bobs, wm, nu
+    integer(c_int), intent(in), optional :: free
     integer(c_int), intent(inout) :: ioptc(0:OPT_LEN - 1)
     real(c_double), intent(inout) :: ropt(0:OPT_LEN - 1)
     integer(c_int), intent(in) :: nlevels, start, check, hist_rows
@@ -1457,12 +1460,14 @@ contains
     type(optimize_args), allocatable :: ops(:)
     type(c_ptr), pointer :: hs(:)
     integer(c_int), pointer :: iout(:, :), nit(:)
-    real(c_double), pointer :: d0(:), dm(:)
+    real(c_double), pointer :: d0(:), dm(:), nul(:)
     integer(ik) :: iopt(0:OPT_LEN - 1)
     real(c_double) :: t0
     integer(c_int) :: rc
-    integer :: l
-    logical :: ok
+    integer :: l, width
+    logical :: ok, obs
+    obs = present(Bobs)
+    width = merge(7, 6, obs)
     nullify (iout)
     if (c_associated(info) .and. nlevels >= 1) then
       call c_f_pointer(info, iout, [3, int(nlevels)])
@@ -1472,6 +1477,9 @@ contains
     if (ierr == 0 .and. .not. (c_associated(handles) .and. c_associated(B) .and. c_associated(niter_max) .and. &
                                c_associated(dt0) .and. c_associated(dt_min) .and. c_associated(hist) .and. &
                                c_associated(info))) ierr = NDSMK_EARG
+    if (ierr == 0 .and. obs) then
+      if (.not. (c_associated(Bobs) .and. c_associated(nu))) ierr = NDSMK_EARG
+    end if
     if (ierr == 0 .and. nlevels >= 1) then
       call c_f_pointer(handles, hs, [int(nlevels)])
       allocate (lev(nlevels), ops(nlevels))
@@ -1491,10 +1499,20 @@ contains
                .and. dm(l) <= huge(tol)
         end do
       end if
-      if (.not. ok) &
+      if (ok .and. obs) then
+        ok = free == 0 .or. free == 1
+        call c_f_pointer(nu, nul, [int(nlevels)])
+        do l = 1, nlevels
+          ok = ok .and. nul(l) >= 0.0_c_double .and. nul(l) <= huge(tol)
+        end do
+        if (.not. ok) &
+          ierr = ndsmk_note_error(NDSMK_EVALUE, "optimize_obs cascade: free 0 or 1, and on every level nu >= 0 "// &
+                                  "(finite)"//c_null_char)
+      else if (.not. ok) then
         ierr = ndsmk_note_error(NDSMK_EVALUE, "optimize cascade: nlevels >= 1, start 0 or 1, check >= 1, hist_rows >= 2, "// &
                                 "tol >= 0, and on every level niter_max >= 1, dt0 > 0 and dt_min >= 0 (all finite)"// &
                                 c_null_char)
+      end if
     end if
     if (ierr == 0) then
       do l = 2, nlevels
@@ -1507,11 +1525,17 @@ contains
     end if
     if (ierr == 0) then
       do l = 1, nlevels
-        ops(l)%hist = dptr_offset(hist, int(l - 1, c_size_t) * int(hist_rows, c_size_t) * 48_c_size_t)
+        ops(l)%hist = dptr_offset(hist, int(l - 1, c_size_t) * int(hist_rows, c_size_t) * int(8 * width, c_size_t))
         ops(l)%start = start; ops(l)%niter_max = nit(l); ops(l)%check = check; ops(l)%hist_rows = hist_rows
         ops(l)%tol = tol; ops(l)%dt0 = d0(l); ops(l)%dt_min = dm(l)
+        if (obs) then
+          ops(l)%nu = nul(l); ops(l)%free = free
+        end if
       end do
       ops(1)%w = w
+      if (obs) then
+        ops(1)%bobs = Bobs; ops(1)%wm = wm
+      end if
       iopt = ioptc
       verbose = (iopt(IOPT_DEBUG) == 1)
       t0 = wall_seconds()
@@ -1531,7 +1555,7 @@ contains
     if (ierr >= NDSMK_ENODEV) then
       if (associated(iout)) iout = 0
       if (c_associated(hist) .and. hist_rows >= 1 .and. nlevels >= 1) &
-        call clear_host([hist], [48], [int(hist_rows, c_int64_t) * int(nlevels, c_int64_t)])
+        call clear_host([hist], [8 * width], [int(hist_rows, c_int64_t) * int(nlevels, c_int64_t)])
     end if
   contains
     ! the first and the last node of every axis, bit for bit
@@ -1547,6 +1571,113 @@ contains
       logical :: yes
       yes = transfer(u, 0_c_int64_t) == transfer(v, 0_c_int64_t)
     end function
+  end function
+
+  ! The cascade of the measurement fit (semantics in include/ndsm_hip.h): ndsm_hip_vecpot_optimize_cascade whose every
+  ! level is ndsm_hip_vecpot_optimize_obs.  Bobs (nx,ny,3) and wm (nx,ny,3; may be NULL) on the finest mesh; nu
+  ! (nlevels) per level, on the HOST in both entries; free 0 or 1.  hist (nlevels,hist_rows,7).  HOST arrays
+  function ndsm_hip_vecpot_optimize_obs_cascade(handles, nlevels, ioptc, ropt, B, w, Bobs, wm, nu, free, start, &
+                                                niter_max, check, tol, dt0, dt_min, hist, hist_rows, info) &
+      bind(c, name="ndsm_hip_vecpot_optimize_obs_cascade") result(ierr)
+    type(c_ptr), value :: handles, B, w, Bobs, wm, nu, niter_max, dt0, dt_min, hist, info
+    integer(c_int), intent(inout) :: ioptc(0:OPT_LEN - 1)
+    real(c_double), intent(inout) :: ropt(0:OPT_LEN - 1)
+    integer(c_int), value :: nlevels, free, start, check, hist_rows
+    real(c_double), value :: tol
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_cascade(handles, nlevels, ioptc, ropt, B, w, start, niter_max, check, tol, dt0, dt_min, hist, &
+                                 hist_rows, info, .false., "ndsm_hip_vecpot_optimize_obs_cascade", Bobs, wm, nu, free)
+  end function
+
+  ! the same on DEVICE arrays of the library's GPU: only history rows cross PCIe
+  function ndsm_hip_vecpot_optimize_obs_cascade_device(handles, nlevels, ioptc, ropt, dB, dw, dBobs, dwm, nu, free, &
+                                                       start, niter_max, check, tol, dt0, dt_min, hist, hist_rows, info) &
+      bind(c, name="ndsm_hip_vecpot_optimize_obs_cascade_device") result(ierr)
+    type(c_ptr), value :: handles, dB, dw, dBobs, dwm, nu, niter_max, dt0, dt_min, hist, info
+    integer(c_int), intent(inout) :: ioptc(0:OPT_LEN - 1)
+    real(c_double), intent(inout) :: ropt(0:OPT_LEN - 1)
+    integer(c_int), value :: nlevels, free, start, check, hist_rows
+    real(c_double), value :: tol
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_cascade(handles, nlevels, ioptc, ropt, dB, dw, start, niter_max, check, tol, dt0, dt_min, &
+                                 hist, hist_rows, info, .true., "ndsm_hip_vecpot_optimize_obs_cascade_device", dBobs, &
+                                 dwm, nu, free)
+  end function
+
+  ! The confidence-weighted restriction of an observation with its confidence (semantics in include/ndsm_hip.h).  src,
+  ! wsrc (nsrc,ncomp) in, dst, wdst (ndst,ncomp) out.  No handle.  HOST arrays
+  function ndsm_hip_resample_weighted(nsrc, ndst, ncomp, src, wsrc, dst, wdst) &
+      bind(c, name="ndsm_hip_resample_weighted") result(ierr)
+    type(c_ptr), value :: nsrc, ndst, src, wsrc, dst, wdst
+    integer(c_int), value :: ncomp
+    integer(c_int) :: ierr
+    ierr = resample_weighted_entry(nsrc, ndst, ncomp, src, wsrc, dst, wdst, .false., "ndsm_hip_resample_weighted")
+  end function
+
+  ! the same on DEVICE arrays of the library's GPU (they must not overlap)
+  function ndsm_hip_resample_weighted_device(nsrc, ndst, ncomp, dsrc, dwsrc, ddst, dwdst) &
+      bind(c, name="ndsm_hip_resample_weighted_device") result(ierr)
+    type(c_ptr), value :: nsrc, ndst, dsrc, dwsrc, ddst, dwdst
+    integer(c_int), value :: ncomp
+    integer(c_int) :: ierr
+    ierr = resample_weighted_entry(nsrc, ndst, ncomp, dsrc, dwsrc, ddst, dwdst, .true., &
+                                   "ndsm_hip_resample_weighted_device")
+  end function
+
+  function resample_weighted_entry(nsrc, ndst, ncomp, src, wsrc, dst, wdst, on_device, who) result(ierr)
+    type(c_ptr), intent(in) :: nsrc, ndst, src, wsrc, dst, wdst
+    integer(c_int), intent(in) :: ncomp
+    logical, intent(in) :: on_device
+    character(len=*), intent(in) :: who
+    integer(c_int) :: ierr
+    integer(c_int), pointer :: ns(:), nd(:)
+    integer(c_int32_t) :: ns3(3), nd3(3)
+    integer(c_size_t) :: bs, bd
+    type(c_ptr) :: buf, dwsrc, ddst, dwdst
+    integer(c_int) :: rc
+    integer :: d
+    logical :: ok
+    ierr = ndsmk_init(-1_c_int)
+    if (ierr /= 0) return
+    ierr = NDSMK_EARG
+    if (.not. (c_associated(nsrc) .and. c_associated(ndst) .and. c_associated(src) .and. c_associated(wsrc) .and. &
+               c_associated(dst) .and. c_associated(wdst))) return
+    call c_f_pointer(nsrc, ns, [3])
+    call c_f_pointer(ndst, nd, [3])
+    ok = ncomp >= 1
+    do d = 1, 3
+      ok = ok .and. ((ns(d) == 1 .and. nd(d) == 1) .or. (ns(d) >= 2 .and. nd(d) >= 2)) .and. nd(d) <= ns(d)
+    end do
+    if (.not. ok) then
+      ierr = ndsmk_note_error(NDSMK_EVALUE, "resample_weighted: ncomp >= 1, at least 2 nodes per axis on both sides "// &
+                              "(or 1 on both), and no axis finer than its source"//c_null_char)
+      return
+    end if
+    ns3 = ns; nd3 = nd
+    if (on_device) then
+      rc = ndsmk_resample_weighted(ns3, nd3, ncomp, src, wsrc, dst, wdst)
+      if (rc == 0) rc = ndsmk_sync()
+    else
+      bs = int(product(int(ns3, c_int64_t)) * int(ncomp, c_int64_t) * 8_c_int64_t, c_size_t)
+      bd = int(product(int(nd3, c_int64_t)) * int(ncomp, c_int64_t) * 8_c_int64_t, c_size_t)
+      buf = c_null_ptr
+      ! [src | wsrc | dst | wdst]
+      rc = ndsmk_alloc(buf, 2_c_size_t * (bs + bd))
+      if (rc == 0) then
+        dwsrc = dptr_offset(buf, bs)
+        ddst = dptr_offset(buf, 2_c_size_t * bs)
+        dwdst = dptr_offset(buf, 2_c_size_t * bs + bd)
+        rc = ndsmk_h2d(buf, src, bs)
+        if (rc == 0) rc = ndsmk_h2d(dwsrc, wsrc, bs)
+        if (rc == 0) rc = ndsmk_resample_weighted(ns3, nd3, ncomp, buf, dwsrc, ddst, dwdst)
+        if (rc == 0) rc = ndsmk_d2h(dst, ddst, bd)
+        if (rc == 0) rc = ndsmk_d2h(wdst, dwdst, bd)
+        if (rc == 0) rc = ndsmk_sync()
+        d = ndsmk_free(buf)
+        if (rc == 0) rc = int(d, c_int)
+      end if
+    end if
+    ierr = reported(who, rc)
   end function
 
   ! Magnetogram preprocessing (semantics in include/ndsm_hip.h).  B (nx,ny,3) in: the magnetogram on the handle's

@@ -649,6 +649,14 @@ module ndsmh_iface
       type(c_ptr), value :: src, dst
       integer(c_int) :: rc
     end function
+    function ndsmk_resample_weighted(nsrc3, ndst3, ncomp, src, wsrc, dst, wdst) &
+        bind(c, name="ndsmk_resample_weighted") result(rc)
+      import :: c_ptr, c_int, c_int32_t
+      integer(c_int32_t), intent(in) :: nsrc3(3), ndst3(3)
+      integer(c_int), value :: ncomp
+      type(c_ptr), value :: src, wsrc, dst, wdst
+      integer(c_int) :: rc
+    end function
     function ndsmk_paste_faces(n3, ncomp, which, src, dst) bind(c, name="ndsmk_paste_faces") result(rc)
       import :: c_ptr, c_int, c_int32_t
       integer(c_int32_t), intent(in) :: n3(3)

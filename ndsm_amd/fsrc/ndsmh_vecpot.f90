@@ -1740,6 +1740,12 @@ contains
   ! is interpolated into the caller's device B, whose input stands beside it only until the faces are pasted: each
   ! level's buffers are freed before the next finer level allocates, so the peak is vecpot_optimize's on the finest.
   ! iopt, ropt: the options and results of the coarsest level's potential solve.
+  ! With ops(1)%bobs every level is the measurement fit (DESIGN.md "Cascade of the measurement fit"): ops(1)%bobs
+  ! (nx,ny,3), ops(1)%wm (the same; may be c_null_ptr) and ops(1)%free on the finest mesh, on the side B is on - the
+  ! host entry stages the two planes once, behind B and w -, ops(l)%nu per level.  (Bobs_l, wm_l) = the
+  ! confidence-weighted restriction of the two planes, straight from the finest (without wm: the hat average of Bobs);
+  ! they lie behind G_l and w_l in the level's buffer.  With free = 1 the paste of a finer level leaves out the freed
+  ! nodes of the k = 0 plane (which = start + 2): they keep the interpolated values the level below has fitted.
   ! ------------------------------------------------------------------
   function vecpot_optimize_cascade(lev, iopt, ropt, pB, ops, on_device) result(rc)
     type(vecpot_ref), intent(in) :: lev(:)
@@ -1749,14 +1755,14 @@ contains
     type(optimize_args), intent(inout) :: ops(:)
     logical, intent(in) :: on_device
     integer(c_int) :: rc
-    integer(c_int32_t) :: n3(3, size(lev))
-    integer(c_size_t) :: nb(size(lev)), wk, fr, tot
+    integer(c_int32_t) :: n3(3, size(lev)), n2(3, size(lev))
+    integer(c_size_t) :: nb(size(lev)), pl3(size(lev)), wk, fr, tot, at
     integer(ik) :: iopt1(0:OPT_LEN - 1)
     real(wp) :: ropt1(0:OPT_LEN - 1)
-    type(c_ptr) :: gb(size(lev)), bb(size(lev)), stage, keep, dB, dw, dcur, dprev
-    integer(c_int) :: start
+    type(c_ptr) :: gb(size(lev)), bb(size(lev)), stage, keep, dB, dw, dbobs, dwm, dcur, dprev
+    integer(c_int) :: start, which
     integer :: l, nl
-    logical :: has_w
+    logical :: has_w, obs, has_wm
 
     nl = size(lev)
     start = ops(1)%start
@@ -1766,41 +1772,86 @@ contains
     end if
     gb = c_null_ptr; bb = c_null_ptr; stage = c_null_ptr; keep = c_null_ptr
     has_w = c_associated(ops(1)%w)
+    obs = c_associated(ops(1)%bobs)
+    has_wm = obs .and. c_associated(ops(1)%wm)
     do l = 1, nl
       ops(l)%info = 0
       n3(:, l) = lev(l)%p%n3
+      n2(:, l) = [n3(1, l), n3(2, l), 1_c_int32_t]
       nb(l) = int(product(int(n3(:, l), ik)), c_size_t) * 8_c_size_t
+      pl3(l) = 0
+      if (obs) pl3(l) = int(n3(1, l), c_size_t) * int(n3(2, l), c_size_t) * 24_c_size_t   ! a plane of three components
     end do
-    ! the finest level's call, the largest by far, is vecpot_optimize's 13 level-1 arrays
-    wk = ndsmk_optimize_work_bytes()
+    ! the finest level's call, the largest by far, is vecpot_optimize's 13 level-1 arrays (and the two planes)
+    if (obs) then
+      wk = ndsmk_optimize_obs_work_bytes()
+    else
+      wk = ndsmk_optimize_work_bytes()
+    end if
     rc = ndsmk_mem_info(fr, tot); if (rc /= 0) return
-    if (real(nb(1), wp) * 13.0_wp + real(wk, wp) > real(tot, wp)) then
+    if (real(nb(1), wp) * 13.0_wp + 2.0_wp * real(pl3(1), wp) + real(wk, wp) > real(tot, wp)) then
       rc = ndsmk_note_error(NDSMK_ENODEV, "the grid needs more device memory than the device has"//c_null_char)
       return
     end if
     if (on_device) then
-      dB = pB; dw = ops(1)%w
+      dB = pB; dw = ops(1)%w; dbobs = ops(1)%bobs; dwm = ops(1)%wm
     else
-      rc = ndsmk_alloc(stage, merge(4_c_size_t, 3_c_size_t, has_w) * nb(1)); if (rc /= 0) goto 900
+      ! [B | w | Bobs | wm]
+      rc = ndsmk_alloc(stage, merge(4_c_size_t, 3_c_size_t, has_w) * nb(1) + merge(2_c_size_t, 1_c_size_t, has_wm) * pl3(1))
+      if (rc /= 0) goto 900
       dB = stage
       rc = ndsmk_h2d(dB, pB, 3_c_size_t * nb(1)); if (rc /= 0) goto 900
+      at = 3_c_size_t * nb(1)
       dw = c_null_ptr
       if (has_w) then
-        dw = dptr_offset(stage, 3_c_size_t * nb(1))
+        dw = dptr_offset(stage, at)
         rc = ndsmk_h2d(dw, ops(1)%w, nb(1)); if (rc /= 0) goto 900
+        at = at + nb(1)
+      end if
+      dbobs = c_null_ptr
+      if (obs) then
+        dbobs = dptr_offset(stage, at)
+        rc = ndsmk_h2d(dbobs, ops(1)%bobs, pl3(1)); if (rc /= 0) goto 900
+        at = at + pl3(1)
+      end if
+      dwm = c_null_ptr
+      if (has_wm) then
+        dwm = dptr_offset(stage, at)
+        rc = ndsmk_h2d(dwm, ops(1)%wm, pl3(1)); if (rc /= 0) goto 900
       end if
     end if
 
     call say("optimize", "Cascade: level data...")
     do l = 2, nl
-      rc = ndsmk_alloc(gb(l), merge(4_c_size_t, 3_c_size_t, has_w) * nb(l)); if (rc /= 0) goto 900
+      ! [G_l | w_l | Bobs_l | wm_l]
+      rc = ndsmk_alloc(gb(l), merge(4_c_size_t, 3_c_size_t, has_w) * nb(l) + merge(2_c_size_t, 1_c_size_t, has_wm) * pl3(l))
+      if (rc /= 0) goto 900
       rc = ndsmk_resample(n3(:, 1), n3(:, l), 3_c_int, 1_c_int, dB, gb(l)); if (rc /= 0) goto 900
+      at = 3_c_size_t * nb(l)
       ops(l)%w = c_null_ptr
       if (has_w) then
-        ops(l)%w = dptr_offset(gb(l), 3_c_size_t * nb(l))
+        ops(l)%w = dptr_offset(gb(l), at)
         rc = ndsmk_resample(n3(:, 1), n3(:, l), 1_c_int, 0_c_int, dw, ops(l)%w); if (rc /= 0) goto 900
+        at = at + nb(l)
+      end if
+      ops(l)%bobs = c_null_ptr; ops(l)%wm = c_null_ptr
+      if (obs) then
+        ops(l)%free = ops(1)%free
+        ops(l)%bobs = dptr_offset(gb(l), at)
+        if (has_wm) then
+          ops(l)%wm = dptr_offset(gb(l), at + pl3(l))
+          rc = ndsmk_resample_weighted(n2(:, 1), n2(:, l), 3_c_int, dbobs, dwm, ops(l)%bobs, ops(l)%wm)
+        else
+          rc = ndsmk_resample(n2(:, 1), n2(:, l), 3_c_int, 1_c_int, dbobs, ops(l)%bobs)
+        end if
+        if (rc /= 0) goto 900
       end if
     end do
+    ! a freed lower face keeps the values interpolated from the level below: the pastes leave its nodes out
+    which = start
+    if (obs) then
+      if (ops(1)%free == 1) which = start + 2_c_int
+    end if
 
     ! the coarsest level: G_L is its start field (start 1) or carries its magnetogram and B.n (start 0)
     ops(nl)%start = start
@@ -1811,21 +1862,23 @@ contains
         rc = ndsmk_alloc(bb(l), 3_c_size_t * nb(l)); if (rc /= 0) goto 900
         dcur = bb(l)
         rc = ndsmk_resample(n3(:, l + 1), n3(:, l), 3_c_int, 0_c_int, dprev, dcur); if (rc /= 0) goto 900
-        rc = ndsmk_paste_faces(n3(:, l), 3_c_int, start, gb(l), dcur); if (rc /= 0) goto 900
+        rc = ndsmk_paste_faces(n3(:, l), 3_c_int, which, gb(l), dcur); if (rc /= 0) goto 900
       else
         ! G_0 is the input itself: it stands aside while level 1's start is interpolated into the caller's array
         rc = ndsmk_alloc(keep, 3_c_size_t * nb(1)); if (rc /= 0) goto 900
         rc = ndsmk_d2d(keep, dB, 3_c_size_t * nb(1)); if (rc /= 0) goto 900
         dcur = dB
         rc = ndsmk_resample(n3(:, 2), n3(:, 1), 3_c_int, 0_c_int, dprev, dcur); if (rc /= 0) goto 900
-        rc = ndsmk_paste_faces(n3(:, 1), 3_c_int, start, keep, dcur); if (rc /= 0) goto 900
+        rc = ndsmk_paste_faces(n3(:, 1), 3_c_int, which, keep, dcur); if (rc /= 0) goto 900
       end if
       rc = ndsmk_sync(); if (rc /= 0) goto 900
       ! the level below is done with: its buffers go before this level's call allocates
       call unstage(rc, [keep, bb(l + 1), gb(l + 1)])
       keep = c_null_ptr; bb(l + 1) = c_null_ptr; gb(l + 1) = c_null_ptr
       if (rc /= 0) goto 900
-      if (l == 1) ops(1)%w = dw
+      if (l == 1) then
+        ops(1)%w = dw; ops(1)%bobs = dbobs; ops(1)%wm = dwm
+      end if
       ops(l)%start = 1
       iopt1 = iopt; ropt1 = ropt
       rc = vecpot_optimize(lev(l)%p, iopt1, ropt1, dcur, ops(l), .true.); if (rc /= 0) goto 900

@@ -32,7 +32,8 @@ import numpy as np  # noqa: E402
 from golden_inputs import (BCS3, BCS_ANISO, BCS_RANDOM, analytic_case, aniso_mesh, aniso_pipeline_cases,  # noqa: E402
                            digest, digest16, manufactured_poisson, negative_option_cases, noisy_case, option_matrix,
                            pipeline_option_cases, quirk_case, rand_field, random_reference_cases, scalar_kw,
-                           scalar_option_problems, zero_field_cases,
+                           scalar_option_problems, zero_field_cases, bc_matrix_case,
+                           ALL_BCS_2D, ALL_BCS_3D, BC_MATRIX_2D, BC_MATRIX_3D,
                            ANISO_SHAPE_2D, ANISO_SHAPES_3D, KERNEL_SHAPES_3D, KERNEL_SHAPES_2D, OPTION_PIPELINE_SHAPE,
                            OPTION_SCALAR_3D)
 from oracle import Oracle, have_ref, uniform_mesh  # noqa: E402
@@ -252,6 +253,7 @@ def aniso(R):
         np.savez_compressed(os.path.join(HERE, f"pipeline_aniso_{name}.npz"), A=A, B=B, ioptc=ioptc)
     print("wrote reference_aniso*, pipeline_aniso_*")
     options(R)
+    bc_matrix(R)
 
 
 def options(R):
@@ -291,9 +293,48 @@ def options(R):
     print("wrote reference_options.json")
 
 
+def bc_matrix(R):
+    """test_oracle_bc_matrix.py: every boundary letter set (golden_inputs.ALL_BCS_3D / ALL_BCS_2D) on the shapes of
+    BC_MATRIX_3D / BC_MATRIX_2D - sha256 of relax3d, residual3d and vcycle (3-D) and of relax_nd and residual_nd (2-D)
+    in reference_bc_matrix.json for every set but the all-Neumann one, whose outputs (the mean is summed in the
+    reference's own order) go to reference_bc_matrix_NN.npz in full"""
+    want, nn = {}, {}
+    for ns, mname in BC_MATRIX_3D:
+        tag = "x".join(str(n) for n in ns)
+        mesh, u, rhs = bc_matrix_case(ns, mname)
+        for bcs in ALL_BCS_3D:
+            out = {"relax": R.relax3d(u, rhs, mesh, bcs), "residual": R.residual3d(u, rhs, mesh, bcs),
+                   "vcycle": R.vcycle(u, rhs, mesh, bcs)}
+            for k, a in out.items():
+                assert np.isfinite(a).all(), (tag, bcs, k)
+                if bcs == "NNNNNN":
+                    nn[f"{k}_{tag}"] = a
+                else:
+                    want[f"{k}_{tag}_{bcs}"] = digest(a)
+    for ns, mname in BC_MATRIX_2D:
+        tag = "x".join(str(n) for n in ns)
+        mesh, u, rhs = bc_matrix_case(ns, mname)
+        for bcs in ALL_BCS_2D:
+            out = {"relax": R.relax_nd(u, rhs, mesh, bcs), "residual": R.residual_nd(u, rhs, mesh, bcs)}
+            for k, a in out.items():
+                assert np.isfinite(a).all(), (tag, bcs, k)
+                if bcs == "NNNN":
+                    nn[f"{k}_{tag}"] = a
+                else:
+                    want[f"{k}_{tag}_{bcs}"] = digest(a)
+    with open(os.path.join(HERE, "reference_bc_matrix.json"), "w") as fh:
+        json.dump(want, fh, indent=0, sort_keys=True)
+        fh.write("\n")
+    np.savez_compressed(os.path.join(HERE, "reference_bc_matrix_NN.npz"), **nn)
+    print("wrote reference_bc_matrix*")
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["options"]:         # only reference_options.json
         assert have_ref(), "build the reference first: make -C oracle ref"
         options(Oracle("ref"))
+    elif sys.argv[1:] == ["bc_matrix"]:     # only reference_bc_matrix*
+        assert have_ref(), "build the reference first: make -C oracle ref"
+        bc_matrix(Oracle("ref"))
     else:
         main()

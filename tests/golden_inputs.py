@@ -4,6 +4,8 @@ The golden files hold only the reference's OUTPUTS; the matching inputs are
 re-created here from fixed seeds (numpy default_rng,
 seeds 2112 / 2113, U(-1,1)).
 """
+import itertools
+
 import numpy as np
 
 # BC letter sets of the three vector-potential components, lower x,y,z then
@@ -203,6 +205,35 @@ def scalar_option_problems():
 def scalar_kw(ms, nc, nex, mean):
     """option_matrix tuple -> keywords of Oracle.solve_bvp"""
     return dict(ms=ms, nmax=nc, nmax_exact=nex, du_max=not mean)
+
+
+# ---- every boundary letter set (tests/golden/reference_bc_matrix.json, test_oracle_bc_matrix.py, test_gpu_bc_matrix.py) ----
+ALL_BCS_3D = tuple("".join(p) for p in itertools.product("DN", repeat=6))   # 64, "DDDDDD" first, "NNNNNN" last
+ALL_BCS_2D = tuple("".join(p) for p in itertools.product("DN", repeat=4))   # 16
+# (shape, mesh function name) of the matrix: odd nx on aniso_mesh, even nx on uniform_mesh; inputs rand_field 2112 / 2113
+BC_MATRIX_3D = (([17, 12, 9], "aniso"), ([18, 17, 17], "uniform"))
+BC_MATRIX_2D = (([27, 36], "aniso"), ([22, 22], "uniform"))
+BC_MATRIX_SEEDS = (2112, 2113)          # u, rhs
+
+_AXIS_PAIRS = ("DD", "DN", "ND", "NN")  # (lower, upper) letters of one axis, coded 0 ... 3
+
+
+def bc_orthogonal_array():
+    """16 of the 64 sets, a strength-2 orthogonal array: x, y in 0 ... 3 and z = (x + y) mod 4, so that every pair of
+    axes sees all 16 combinations of (lower, upper) letters.  Holds DDDDDD; NNNNNN is not a member (x = y = 3, z = 2)."""
+    out = []
+    for x in range(4):
+        for y in range(4):
+            p = (_AXIS_PAIRS[x], _AXIS_PAIRS[y], _AXIS_PAIRS[(x + y) % 4])
+            out.append("".join(q[0] for q in p) + "".join(q[1] for q in p))
+    return tuple(out)
+
+
+def bc_matrix_case(ns, mesh_name):
+    """(mesh, u, rhs) of one shape of the boundary-set matrix"""
+    shp = tuple(int(n) for n in ns[::-1])
+    mesh = aniso_mesh(ns) if mesh_name == "aniso" else uniform_mesh(ns)
+    return mesh, rand_field(shp, BC_MATRIX_SEEDS[0]), rand_field(shp, BC_MATRIX_SEEDS[1])
 
 
 def digest16(a):

@@ -1210,6 +1210,69 @@ int ndsm_hip_debug_zero_guess(int on);
  * download, upload or single operation that reads it writes the zeros first), 0: it is in memory */
 int ndsm_hip_debug_u_declared_zero(void *handle, int level);
 
+/* ---- Open-box potential field from a magnetogram (DESIGN.md "Open-box potential field") ------------------------------
+ * Every entry that starts from a potential field reads B.n on all six faces of the box; a magnetogram gives the lower
+ * face only.  The Green's-function field of the half space above the magnetogram (Schmidt 1964; Sakurai 1982) gives
+ * the other five: it is evaluated on the faces, and the interior is solved by ndsm_hip_vecpot_solve.  The magnetogram
+ * may be wider than the box - flux outside the box's footprint decides the side faces.  No handle.
+ *
+ * Source.  bz (nsx,nsy) on the uniform mesh xs (nsx >= 2), ys (nsy >= 2) at height zs.  hx = xs[1] - xs[0] and
+ *   hy = ys[1] - ys[0], both > 0; c = (hx hy) / 6.283185307179586; npix = nsx nsy; pixel p = i + nsx j.
+ * One target (X, Y, Z), w = Z - zs.  For pixel p: q = bz[p] c; dx = X - xs[i]; dy = Y - ys[j];
+ *   r2 = (dx dx + dy dy) + w w; if r2 > 0: t = q / (r2 sqrt(r2)) and the three terms are dx t, dy t, w t; otherwise
+ *   the pixel contributes no term (the punctured point rule for a target on a source node).
+ * Order of the sum: a function of npix only - not of the targets, the entry or the launch.
+ *   NS = min(64, ceil(npix / 4096)), len = ceil(npix / NS); slice s covers the pixels [s len, min(npix, (s + 1) len)).
+ *   A slice sum starts at 0.0 and adds its terms left to right; the result is the slice sums added in ascending order,
+ *   starting from slice 0's.  Built without contraction, with IEEE division and sqrt: the order above is the bits.
+ * Targets on or below the plane.  w < 0: all three components are NaN.  w == 0: Bx and By are the sums; Bz is the
+ *   bilinear interpolation of bz at (X, Y), 0 outside xs[0] <= X <= xs[nsx - 1], ys[0] <= Y <= ys[nsy - 1].  Inside,
+ *   i0 is the largest node <= nsx - 2 with xs[i0] <= X, theta_x = (X - xs[i0]) / (xs[i0 + 1] - xs[i0]), likewise j0
+ *   and theta_y; L(v0, v1, theta) = v0 if theta == 0, v1 if theta == 1, else (1.0 - theta) v0 + theta v1; and
+ *   Bz = L(L(bz[i0,j0], bz[i0+1,j0], theta_x), L(bz[i0,j0+1], bz[i0+1,j0+1], theta_x), theta_y): a target that sits
+ *   bitwise on a source node gets that pixel's value bit for bit.  Non-finite bz propagates.
+ * The rule is first order in h for the tangential field on the plane itself (w == 0) and accurate to the truncation
+ * of the magnetogram two or more mesh rows above it.  The punctured rule knows bitwise equality only: a target on the
+ * plane that misses a source node by a rounding error gets a term of the order q / eps^2 from it.  Where the box
+ * starts on the plane (z[0] == zs), build the box's x and y as slices of xs and ys (or pass the box's own x and y as
+ * the source mesh), so that its nodes on the plane are source nodes bit for bit, or keep them well apart.
+ *
+ * ndsm_hip_green_points: B (3,npts) at pts (3,npts) - x, y, z of each point, as the seeds of ndsm_hip_vecpot_trace.
+ * ndsm_hip_green_box: B (nx,ny,nz,3) on the box mesh x, y, z.  which = 0 writes the nodes with an index at either end
+ *   of an axis and leaves every interior node of B untouched; which = 1 writes all nodes.  The same node gets the same
+ *   bits from both, and from the points entry at its coordinates.
+ * ndsm_hip_vecpot_open: ndsm_hip_green_box_device (which = 0) on the handle's mesh into the device B, then
+ *   ndsm_hip_vecpot_solve_device, bit for bit that composition: A in the first guess, out A; B out (the host form
+ *   starts from a B of zeros; the device form leaves the interior of dB as it is until the solve overwrites it).
+ *   No field crosses PCIe in between.  Options and return value as ndsm_hip_vecpot_solve.
+ * The mesh vectors xs, ys, x, y, z stay on the HOST in both forms, as for ndsm_hip_vecpot_create.
+ *   Returns 0 or: 9001 without a GPU whatever the arguments; 9001 before anything is allocated - as soon as the shapes
+ *   can be read, in all three entries - when the arrays and the scratch (at most 384 MiB: the targets go through in
+ *   chunks) exceed the device's TOTAL memory.  That is a screen, not a reservation: it does not count what else is
+ *   resident (a handle's hierarchies among it), and a call that passes it and finds too little memory free fails in
+ *   its allocation, with 9001 as well and the outputs untouched.  9002 a NULL array, shape or handle; 9004 nsx or
+ *   nsy < 2, a spacing not > 0, npts < 0, which outside 0/1, a box axis < 2, z[0] < zs.
+ *   npts == 0 returns 0 and touches nothing.  A failed call leaves the outputs untouched. */
+/* HOST arrays */
+int ndsm_hip_green_points(const int nsrc[2], const double *xs, const double *ys, double zs, const double *bz, int npts,
+                          const double *pts, double *B);
+/* the same with bz, pts and B DEVICE arrays of the library's GPU */
+int ndsm_hip_green_points_device(const int nsrc[2], const double *xs, const double *ys, double zs, const double *dbz,
+                                 int npts, const double *dpts, double *dB);
+/* HOST arrays */
+int ndsm_hip_green_box(const int nsrc[2], const double *xs, const double *ys, double zs, const double *bz,
+                       const int nshape[3], const double *x, const double *y, const double *z, int which, double *B);
+/* the same with bz and B DEVICE arrays of the library's GPU */
+int ndsm_hip_green_box_device(const int nsrc[2], const double *xs, const double *ys, double zs, const double *dbz,
+                              const int nshape[3], const double *x, const double *y, const double *z, int which,
+                              double *dB);
+/* HOST arrays */
+int ndsm_hip_vecpot_open(void *h, int ioptc[16], double ropt[16], const int nsrc[2], const double *xs,
+                         const double *ys, double zs, const double *bz, double *A, double *B);
+/* the same with bz, A and B DEVICE arrays of the library's GPU */
+int ndsm_hip_vecpot_open_device(void *h, int ioptc[16], double ropt[16], const int nsrc[2], const double *xs,
+                                const double *ys, double zs, const double *dbz, double *dA, double *dB);
+
 #ifdef __cplusplus
 }
 #endif

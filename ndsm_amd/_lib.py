@@ -124,6 +124,13 @@ def load_library(path=None):
     _rw = [_ip, _ip, ctypes.c_int] + [ctypes.c_void_p] * 4
     L.ndsm_hip_resample_weighted.argtypes = _rw
     L.ndsm_hip_resample_weighted_device.argtypes = _rw
+    _gs = [_ip, _dp, _dp, ctypes.c_double, ctypes.c_void_p]           # the source: nsrc, xs, ys, zs, bz
+    L.ndsm_hip_green_points.argtypes = _gs + [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    L.ndsm_hip_green_points_device.argtypes = _gs + [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    L.ndsm_hip_green_box.argtypes = _gs + [_ip, _dp, _dp, _dp, ctypes.c_int, ctypes.c_void_p]
+    L.ndsm_hip_green_box_device.argtypes = _gs + [_ip, _dp, _dp, _dp, ctypes.c_int, ctypes.c_void_p]
+    L.ndsm_hip_vecpot_open.argtypes = [ctypes.c_void_p, _ip, _dp] + _gs + [ctypes.c_void_p] * 2
+    L.ndsm_hip_vecpot_open_device.argtypes = [ctypes.c_void_p, _ip, _dp] + _gs + [ctypes.c_void_p] * 2
     _obc = ([ctypes.c_void_p, ctypes.c_int, _ip, _dp] + [ctypes.c_void_p] * 5 + [ctypes.c_int, ctypes.c_int,
             ctypes.c_void_p, ctypes.c_int, ctypes.c_double] + [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p])
     L.ndsm_hip_vecpot_optimize_obs_cascade.argtypes = _obc
@@ -368,6 +375,28 @@ class VecPot:
         self.last_ioptc, self.last_ropt = ioptc, ropt
         return ierr, A.reshape(shape), B.reshape(shape)
 
+    def solve_open(self, bz, xs=None, ys=None, zs=None, a_init=None, niterex_max=10000, ncycles_max=1024,
+                   ex_tol=1e-13, vc_tol=1e-10, ms=5, mean=False, mixed_precision=False, flxcrl=False, device=False):
+        """The open-box potential field of the magnetogram bz (nsy,nsx) on the mesh xs, ys at height zs (defaults:
+        the handle's x, y and z[0]): the Green's-function field of the half space above bz on the six faces, then
+        solve() - in one call, bit for bit magnetogram_field() followed by solve(), and no field crosses PCIe in
+        between (semantics: include/ndsm_hip.h, ndsm_hip_vecpot_open).  Returns (ierr, A, B) as solve()."""
+        ns2, qx, qy, zs_, S = _green_source(self.x, self.y, self.z, bz, xs, ys, zs)
+        shape = tuple(int(v) for v in self.nshape4[::-1])
+        n = int(np.prod(shape))
+        A = np.zeros(n) if a_init is None else self._field_arg(a_init, "solve_open")
+        B = np.zeros(n)
+        ioptc, ropt = self._options(niterex_max, ncycles_max, ex_tol, vc_tol, ms, mean, mixed_precision, flxcrl)
+        head = (self.h, ioptc.ctypes.data_as(_ip), _d(ropt), ns2.ctypes.data_as(_ip), _d(qx), _d(qy), zs_)
+        if not device:
+            ierr = self.L.ndsm_hip_vecpot_open(*head, S.ctypes.data, A.ctypes.data, B.ctypes.data)
+        else:
+            ierr = self._on_device([S, A, B], lambda dS, dA, dB: self.L.ndsm_hip_vecpot_open_device(*head, dS, dA, dB))
+        if ierr >= 9000:
+            _check(ierr, "ndsm_hip_vecpot_open", self.L)
+        self.last_ioptc, self.last_ropt = ioptc, ropt
+        return ierr, A.reshape(shape), B.reshape(shape)
+
     def _field_arg(self, b, what):
         """b as a flat float64 copy; a shape other than (3, nz, ny, nx) is an argument error (9002)"""
         shape = tuple(int(v) for v in self.nshape4[::-1])
@@ -378,20 +407,7 @@ class VecPot:
 
     def _on_device(self, host_arrays, call):
         """stage host_arrays in device memory, run call(*device pointers), copy every array back"""
-        ptrs = []
-        try:
-            for a in host_arrays:
-                p = ctypes.c_void_p()
-                _check(self.L.ndsm_hip_device_alloc(a.nbytes, ctypes.byref(p)), "device_alloc", self.L)
-                ptrs.append(p)
-                _check(self.L.ndsm_hip_memcpy_h2d(p, a.ctypes.data, a.nbytes), "h2d", self.L)
-            ierr = call(*ptrs)
-            for a, p in zip(host_arrays, ptrs):
-                _check(self.L.ndsm_hip_memcpy_d2h(a.ctypes.data, p, a.nbytes), "d2h", self.L)
-        finally:
-            for p in ptrs:
-                self.L.ndsm_hip_device_free(p)
-        return ierr
+        return _staged(self.L, host_arrays, call)
 
     def _entry(self, name, args, device, who=None):
         """One call of an entry that takes arrays: L.<name>(h, *args) on host arrays, or (device) L.<name>_device with
@@ -1985,6 +2001,117 @@ def resample_weighted(a, wa, shape, device=False, lib=None):
             for p in ptrs:
                 L.ndsm_hip_device_free(p)
     return D.reshape(src.shape[:-3] + dshape), WD.reshape(src.shape[:-3] + dshape)
+
+
+GREEN_WHICH = {"faces": 0, "volume": 1}
+
+
+def _green_source(x, y, z, bz, xs, ys, zs):
+    """the source of a Green's-function call as (nsrc, xs, ys, zs, bz flat): the magnetogram bz (nsy,nsx) on the mesh
+    xs, ys at height zs; the defaults are the box's x, y and z[0].  ValueError for what the library would answer with
+    9004 and for a bz that does not fit its mesh"""
+    qx = _f64(x if xs is None else xs).reshape(-1)
+    qy = _f64(y if ys is None else ys).reshape(-1)
+    if zs is None:
+        if z is None or len(z) == 0:
+            raise ValueError("zs is needed")
+        zs = z[0]
+    zs = float(zs)
+    if len(qx) < 2 or len(qy) < 2:
+        raise ValueError(f"the source mesh needs at least 2 nodes per axis, not {len(qx)} x {len(qy)}")
+    if not (qx[1] - qx[0] > 0.0 and qy[1] - qy[0] > 0.0):
+        raise ValueError("the source mesh needs spacings > 0")
+    S = np.asarray(bz)
+    if S.shape != (len(qy), len(qx)):
+        raise ValueError(f"bz of shape {S.shape}, the source mesh needs {(len(qy), len(qx))}")
+    if z is not None and len(z) > 0 and not (z[0] >= zs):
+        raise ValueError(f"the box starts below the magnetogram: z[0] = {z[0]!r} < zs = {zs!r}")
+    return np.array([len(qx), len(qy)], dtype=np.intc), qx, qy, zs, _f64(S).reshape(-1).copy()
+
+
+def _staged(L, host_arrays, call):
+    """stage host_arrays in device memory, run call(*device pointers), copy every array back"""
+    ptrs = []
+    try:
+        for a in host_arrays:
+            p = ctypes.c_void_p()
+            _check(L.ndsm_hip_device_alloc(a.nbytes, ctypes.byref(p)), "device_alloc", L)
+            ptrs.append(p)
+            _check(L.ndsm_hip_memcpy_h2d(p, a.ctypes.data, a.nbytes), "h2d", L)
+        rc = call(*ptrs)
+        for a, p in zip(host_arrays, ptrs):
+            _check(L.ndsm_hip_memcpy_d2h(a.ctypes.data, p, a.nbytes), "d2h", L)
+    finally:
+        for p in ptrs:
+            L.ndsm_hip_device_free(p)
+    return rc
+
+
+def green_field_points(xs, ys, zs, bz, pts, device=False, lib=None):
+    """The Green's-function field of the half space above the magnetogram bz (nsy,nsx) - given on the uniform mesh
+    xs, ys at height zs - at the points pts (npts,3; x, y, z), on the device (semantics: include/ndsm_hip.h,
+    ndsm_hip_green_points).  Returns B (npts,3).  Below the plane the field is NaN; on it Bz is the bilinear
+    interpolation of bz (0 outside the mesh).  device=True: the arrays are staged in device memory and the
+    device-resident entry point runs."""
+    P = np.asarray(pts, dtype=np.float64)
+    if P.ndim != 2 or P.shape[1] != 3:
+        raise ValueError(f"pts of shape {P.shape}, (npts, 3) is needed")
+    ns2, qx, qy, zs, S = _green_source(None, None, None, bz, xs, ys, zs)
+    L = lib or load_library()
+    P = np.ascontiguousarray(P).reshape(-1).copy()
+    B = np.zeros(P.size)
+    head = (ns2.ctypes.data_as(_ip), _d(qx), _d(qy), zs)
+    if not device:
+        _check(L.ndsm_hip_green_points(*head, S.ctypes.data, len(P) // 3, P.ctypes.data, B.ctypes.data),
+               "ndsm_hip_green_points", L)
+    else:
+        _check(_staged(L, [S, P, B], lambda dS, dP, dB: L.ndsm_hip_green_points_device(*head, dS, len(P) // 3, dP, dB)),
+               "ndsm_hip_green_points_device", L)
+    return B.reshape(-1, 3)
+
+
+def magnetogram_field(x, y, z, bz, xs=None, ys=None, zs=None, which="faces", device=False, lib=None):
+    """The Green's-function field of the half space above the magnetogram bz (nsy,nsx) on the box mesh x, y, z, as the
+    b (3,nz,ny,nx) every entry that starts from a potential field takes (semantics: include/ndsm_hip.h,
+    ndsm_hip_green_box).  xs, ys, zs: the magnetogram's mesh and height, by default x, y and z[0] - it may be wider
+    than the box, and the flux outside the box's footprint then shapes the side faces.  which "faces": the nodes of
+    the six faces, zeros inside (all that solve(), force_free_field(), optimize(start="potential") and the cascades
+    read); "volume": every node.  Where the box starts on the magnetogram's plane, take x and y as slices of xs and
+    ys (xs[i0:i0 + nx]): a box node on the plane must be a source node bit for bit - the rule leaves that pixel out -
+    or lie well away from every source node; a miss by a rounding error gives a term of the order 1 / eps^2.
+    device=True: the arrays are staged in device memory and the device-resident entry point runs."""
+    if which not in GREEN_WHICH:
+        raise ValueError(f"which must be 'faces' or 'volume', not {which!r}")
+    qx, qy, qz = (_f64(v).reshape(-1) for v in (x, y, z))
+    if min(len(qx), len(qy), len(qz)) < 2:
+        raise ValueError(f"the box needs at least 2 nodes per axis, not {(len(qz), len(qy), len(qx))}")
+    ns2, sx, sy, zs, S = _green_source(qx, qy, qz, bz, xs, ys, zs)
+    L = lib or load_library()
+    n3 = np.array([len(qx), len(qy), len(qz)], dtype=np.intc)
+    B = np.zeros(3 * len(qx) * len(qy) * len(qz))
+    head = (ns2.ctypes.data_as(_ip), _d(sx), _d(sy), zs)
+    tail = (n3.ctypes.data_as(_ip), _d(qx), _d(qy), _d(qz), GREEN_WHICH[which])
+    if not device:
+        _check(L.ndsm_hip_green_box(*head, S.ctypes.data, *tail, B.ctypes.data), "ndsm_hip_green_box", L)
+    else:
+        _check(_staged(L, [S, B], lambda dS, dB: L.ndsm_hip_green_box_device(*head, dS, *tail, dB)),
+               "ndsm_hip_green_box_device", L)
+    return B.reshape(3, len(qz), len(qy), len(qx))
+
+
+def potential_open(x, y, z, bz, xs=None, ys=None, zs=None, a_init=None, niterex_max=10000, ncycles_max=1024,
+                   ex_tol=1e-13, vc_tol=1e-10, ms=5, mean=False, mixed_precision=False, flxcrl=False, ngrids=0,
+                   lib=None):
+    """The open-box potential field of the magnetogram bz (nsy,nsx): one-shot form of VecPot.solve_open (returns its
+    (ierr, A, B)).  Raises NdsmHipError on device / runtime failures (>= 9001)."""
+    _green_source(x, y, z, bz, xs, ys, zs)           # (a ValueError comes before the handle is made)
+    V = VecPot(x, y, z, ngrids=ngrids, lib=lib)
+    try:
+        return V.solve_open(bz, xs=xs, ys=ys, zs=zs, a_init=a_init, niterex_max=niterex_max, ncycles_max=ncycles_max,
+                            ex_tol=ex_tol, vc_tol=vc_tol, ms=ms, mean=mean, mixed_precision=mixed_precision,
+                            flxcrl=flxcrl)
+    finally:
+        V.close()
 
 
 def cascade_shapes(shape, levels, min_nodes=4):

@@ -1,0 +1,326 @@
+// Green's-function field of the half space above a magnetogram (DESIGN.md "Open-box potential field"; semantics:
+// include/ndsm_hip.h, ndsm_hip_green_points): an all-pairs sum of targets times magnetogram pixels.
+//
+//   green_k : the classic all-pairs form.  A block of 256 threads owns 256 targets, one per thread, with X, Y, w and
+//             the three sums in registers.  blockIdx.y is the slice of the pixels (the order of the sum is a function
+//             of npix alone: NS = min(64, ceil(npix / 4096)) slices of len = ceil(npix / NS) pixels).  The slice goes
+//             through LDS in tiles of 256 pixels: thread l stages pixel p = tile + l as xs[p mod nsx], ys[p div nsx]
+//             and q = bz[p] c, and every lane then reads the same address (a broadcast, no bank conflict) pixel after
+//             pixel, so the terms are added left to right.  The three slice sums go to scratch (NS, 3, chunk).
+//   fold_k  : one thread per target adds the slice sums in ascending order, starting from slice 0's, applies the rules
+//             of the plane (w < 0: NaN; w == 0: Bz is the bilinear interpolation of bz) and writes the target's three
+//             components where its generator says.
+//
+// Three target generators share both kernels: a point list (3,npts), the face nodes of a box mesh and all nodes of a
+// box mesh.  Targets are processed in chunks of at most 262144, which keeps the scratch at 384 MiB or less; a target's
+// sums depend on nothing but the target and the source, so the chunking and the generator leave no trace in the bits.
+//
+// Plain C++ under -ffp-contract=off with IEEE division and sqrt: the operand order of the header is the bits, and
+// tests/green_model.py restates it.
+#include "common.hpp"
+
+#include <cmath>
+
+namespace {
+
+using ndsm::i64;
+
+constexpr int kBlock = 256;             // targets per block and pixels per LDS tile
+constexpr i64 kChunk = 262144;          // targets per launch: 64 slices x 3 x 8 B x 262144 = 384 MiB of scratch
+constexpr i64 kSliceMin = 4096;         // pixels per slice before the 64-slice cap
+constexpr int kSliceCap = 64;
+
+enum { GEN_POINTS = 0, GEN_FACES = 1, GEN_VOLUME = 2 };
+
+struct Source {
+  const double *xs, *ys, *bz;           // DEVICE
+  int nsx, nsy;
+  i64 npix, len;
+  int nslices;
+  double zs, c;
+};
+
+struct Targets {
+  int gen;
+  i64 count;                            // all targets of the call
+  const double *pts;                    // GEN_POINTS: (3,npts), DEVICE
+  const double *x, *y, *z;              // the box mesh, DEVICE
+  int nx, ny, nz;
+};
+
+// the node (i, j, k) of face target t: the k = 0 plane, the k = nz - 1 plane, then plane after plane the ring of the
+// rows j = 0 and j = ny - 1 and the columns i = 0 and i = nx - 1 between them
+__device__ __forceinline__ void face_node(const Targets &g, i64 t, int &i, int &j, int &k) {
+  const i64 plane = (i64)g.nx * g.ny;
+  if (t < 2 * plane) {
+    k = t < plane ? 0 : g.nz - 1;
+    const i64 r = t < plane ? t : t - plane;
+    j = (int)(r / g.nx);
+    i = (int)(r - (i64)j * g.nx);
+    return;
+  }
+  const i64 ring = 2 * (i64)g.nx + 2 * (i64)(g.ny - 2);
+  const i64 u = t - 2 * plane;
+  const i64 kk = u / ring;
+  i64 r = u - kk * ring;
+  k = 1 + (int)kk;
+  if (r < g.nx) {
+    j = 0;
+    i = (int)r;
+  } else if (r < 2 * (i64)g.nx) {
+    j = g.ny - 1;
+    i = (int)(r - g.nx);
+  } else {
+    r -= 2 * (i64)g.nx;
+    j = 1 + (int)(r / 2);
+    i = (r & 1) ? g.nx - 1 : 0;
+  }
+}
+
+// coordinates of target t and where its component c goes: out[at + c * stride]
+__device__ __forceinline__ void target_of(const Targets &g, i64 t, double &X, double &Y, double &Z, size_t &at,
+                                          size_t &stride) {
+  if (g.gen == GEN_POINTS) {
+    X = g.pts[3 * t];
+    Y = g.pts[3 * t + 1];
+    Z = g.pts[3 * t + 2];
+    at = (size_t)(3 * t);
+    stride = 1;
+    return;
+  }
+  int i, j, k;
+  const i64 plane = (i64)g.nx * g.ny;
+  if (g.gen == GEN_FACES) {
+    face_node(g, t, i, j, k);
+  } else {
+    k = (int)(t / plane);
+    const i64 r = t - (i64)k * plane;
+    j = (int)(r / g.nx);
+    i = (int)(r - (i64)j * g.nx);
+  }
+  X = g.x[i];
+  Y = g.y[j];
+  Z = g.z[k];
+  at = (size_t)i + (size_t)g.nx * (size_t)j + (size_t)plane * (size_t)k;
+  stride = (size_t)plane * (size_t)g.nz;
+}
+
+// part[(s * 3 + c) * cnt + (t - t0)]: slice s's sum of component c for the targets t0 .. t0 + cnt - 1
+__global__ __launch_bounds__(kBlock) void green_k(Source s, Targets g, i64 t0, i64 cnt, double *__restrict__ part) {
+  __shared__ double lx[kBlock], ly[kBlock], lq[kBlock];
+  const int l = threadIdx.x;
+  const i64 lt = (i64)blockIdx.x * kBlock + l;
+  const bool live = lt < cnt;
+  double X = 0.0, Y = 0.0, Z = 0.0;
+  if (live) {
+    size_t at, stride;
+    target_of(g, t0 + lt, X, Y, Z, at, stride);
+  }
+  const double w = Z - s.zs, ww = w * w;
+  double ax = 0.0, ay = 0.0, az = 0.0;
+  const i64 p0 = (i64)blockIdx.y * s.len;
+  const i64 p1 = p0 + s.len < s.npix ? p0 + s.len : s.npix;
+  for (i64 tile = p0; tile < p1; tile += kBlock) {
+    const i64 p = tile + l;
+    if (p < p1) {
+      const i64 j = p / s.nsx;
+      lx[l] = s.xs[p - j * s.nsx];
+      ly[l] = s.ys[j];
+      lq[l] = s.bz[p] * s.c;
+    }
+    __syncthreads();
+    const int m = p1 - tile < kBlock ? (int)(p1 - tile) : kBlock;
+    for (int n = 0; n < m; ++n) {
+      const double dx = X - lx[n], dy = Y - ly[n];
+      const double r2 = (dx * dx + dy * dy) + ww;
+      if (r2 > 0.0) {
+        const double t = lq[n] / (r2 * sqrt(r2));
+        ax = ax + dx * t;
+        ay = ay + dy * t;
+        az = az + w * t;
+      }
+    }
+    __syncthreads();
+  }
+  if (live) {
+    double *o = part + (size_t)blockIdx.y * 3 * (size_t)cnt + (size_t)lt;
+    o[0] = ax;
+    o[(size_t)cnt] = ay;
+    o[2 * (size_t)cnt] = az;
+  }
+}
+
+// the largest node i0 <= n - 2 with v[i0] <= q, for v[0] <= q <= v[n - 1]: an estimate from the spacing, corrected
+__device__ __forceinline__ int bracket(const double *v, int n, double q) {
+  const double e = floor((q - v[0]) / (v[1] - v[0]));
+  int i0 = e < 0.0 ? 0 : (e > (double)(n - 2) ? n - 2 : (int)e);
+  while (i0 > 0 && v[i0] > q) --i0;
+  while (i0 < n - 2 && v[i0 + 1] <= q) ++i0;
+  return i0;
+}
+
+// theta = 0 and theta = 1 copy an end: a target on a node gets the node's value bit for bit
+__device__ __forceinline__ double lerp(double v0, double v1, double th) {
+  if (th == 0.0) return v0;
+  if (th == 1.0) return v1;
+  return (1.0 - th) * v0 + th * v1;
+}
+
+__device__ __forceinline__ double plane_bz(const Source &s, double X, double Y) {
+  if (!(X >= s.xs[0] && X <= s.xs[s.nsx - 1] && Y >= s.ys[0] && Y <= s.ys[s.nsy - 1])) return 0.0;
+  const int i0 = bracket(s.xs, s.nsx, X), j0 = bracket(s.ys, s.nsy, Y);
+  const double tx = (X - s.xs[i0]) / (s.xs[i0 + 1] - s.xs[i0]);
+  const double ty = (Y - s.ys[j0]) / (s.ys[j0 + 1] - s.ys[j0]);
+  const double *r0 = s.bz + (size_t)s.nsx * (size_t)j0 + (size_t)i0, *r1 = r0 + s.nsx;
+  return lerp(lerp(r0[0], r0[1], tx), lerp(r1[0], r1[1], tx), ty);
+}
+
+__global__ __launch_bounds__(kBlock) void fold_k(Source s, Targets g, i64 t0, i64 cnt, const double *__restrict__ part,
+                                                 double *__restrict__ out) {
+  const i64 lt = (i64)blockIdx.x * kBlock + threadIdx.x;
+  if (lt >= cnt) return;
+  double X, Y, Z;
+  size_t at, stride;
+  target_of(g, t0 + lt, X, Y, Z, at, stride);
+  double b[3];
+  for (int c = 0; c < 3; ++c) {
+    const double *q = part + (size_t)c * (size_t)cnt + (size_t)lt;
+    double acc = q[0];
+    for (int sl = 1; sl < s.nslices; ++sl) acc = acc + q[(size_t)sl * 3 * (size_t)cnt];
+    b[c] = acc;
+  }
+  const double w = Z - s.zs;
+  if (w < 0.0) {
+    b[0] = b[1] = b[2] = __builtin_nan("");
+  } else if (w == 0.0) {
+    b[2] = plane_bz(s, X, Y);
+  }
+  for (int c = 0; c < 3; ++c) out[at + (size_t)c * stride] = b[c];
+}
+
+int slices_of(i64 npix) {
+  const i64 ns = (npix + kSliceMin - 1) / kSliceMin;
+  return (int)(ns < kSliceCap ? ns : kSliceCap);
+}
+
+bool source_ok(const int32_t *nsrc2, const double *h_xs, const double *h_ys) {
+  if (nsrc2[0] < 2 || nsrc2[1] < 2) return false;
+  return h_xs[1] - h_xs[0] > 0.0 && h_ys[1] - h_ys[0] > 0.0;     // (false for a NaN as well)
+}
+
+// the targets of a box call, in doubles: three axes of up to 2^31 nodes overflow 64-bit whole numbers
+double box_targets(const int32_t *n3, int which) {
+  const double nx = n3[0], ny = n3[1], nz = n3[2];
+  return which == 0 ? nx * ny * nz - (nx - 2.0) * (ny - 2.0) * (nz - 2.0) : nx * ny * nz;
+}
+constexpr double kMaxTargets = 4.0e15;   // above any device's memory at 24 B per target, exact in a double and an i64
+
+// device bytes of a call besides the caller's own arrays: the mesh vectors and the scratch of the largest chunk
+double own_bytes(const int32_t *nsrc2, const int32_t *n3, double ntargets) {
+  const double chunk = ntargets < (double)kChunk ? ntargets : (double)kChunk;
+  double b = 8.0 * ((double)nsrc2[0] + (double)nsrc2[1]);
+  if (n3) b += 8.0 * ((double)n3[0] + (double)n3[1] + (double)n3[2]);
+  return b + 24.0 * chunk * (double)slices_of((i64)nsrc2[0] * nsrc2[1]);
+}
+
+// the shared driver: mesh vectors up, then chunk after chunk the all-pairs launch and the fold
+int run(const int32_t *nsrc2, const double *h_xs, const double *h_ys, double zs, const double *bz, Targets g,
+        const int32_t *n3, const double *h_x, const double *h_y, const double *h_z, double *out) {
+  Source s;
+  s.nsx = nsrc2[0];
+  s.nsy = nsrc2[1];
+  s.npix = (i64)s.nsx * s.nsy;
+  s.nslices = slices_of(s.npix);
+  s.len = (s.npix + s.nslices - 1) / s.nslices;
+  s.zs = zs;
+  s.c = ((h_xs[1] - h_xs[0]) * (h_ys[1] - h_ys[0])) / 6.283185307179586;
+  s.bz = bz;
+  const i64 chunk = g.count < kChunk ? g.count : kChunk;
+  const size_t nmesh = (size_t)s.nsx + (size_t)s.nsy + (n3 ? (size_t)n3[0] + (size_t)n3[1] + (size_t)n3[2] : 0);
+  void *buf = nullptr;
+  int rc = ndsmk_alloc(&buf, 8 * (nmesh + 3 * (size_t)chunk * (size_t)s.nslices));
+  if (rc != 0) return rc;
+  double *d = (double *)buf;
+  s.xs = d;
+  s.ys = d + s.nsx;
+  rc = ndsmk_h2d(d, h_xs, 8 * (size_t)s.nsx);
+  if (rc == 0) rc = ndsmk_h2d(d + s.nsx, h_ys, 8 * (size_t)s.nsy);
+  double *m = d + s.nsx + s.nsy;
+  if (n3 && rc == 0) {
+    g.x = m;
+    g.y = m + n3[0];
+    g.z = m + n3[0] + n3[1];
+    rc = ndsmk_h2d(m, h_x, 8 * (size_t)n3[0]);
+    if (rc == 0) rc = ndsmk_h2d(m + n3[0], h_y, 8 * (size_t)n3[1]);
+    if (rc == 0) rc = ndsmk_h2d(m + n3[0] + n3[1], h_z, 8 * (size_t)n3[2]);
+  }
+  double *part = d + nmesh;
+  for (i64 t0 = 0; t0 < g.count && rc == 0; t0 += chunk) {
+    const i64 cnt = g.count - t0 < chunk ? g.count - t0 : chunk;
+    const unsigned nb = (unsigned)((cnt + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(green_k, dim3(nb, (unsigned)s.nslices), dim3(kBlock), 0, ndsm::stream(), s, g, t0, cnt, part);
+    hipLaunchKernelGGL(fold_k, dim3(nb), dim3(kBlock), 0, ndsm::stream(), s, g, t0, cnt, part, out);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) rc = ndsm::fail((int)e, hipGetErrorString(e), __FILE__, __LINE__);
+  }
+  const int rf = ndsmk_free(buf);       // (drains the stream first)
+  return rc != 0 ? rc : rf;
+}
+
+}  // namespace
+
+// 0, or 9001 when the device cannot hold a call's arrays: caller_bytes of the caller's side (staged host arrays) plus
+// the mesh vectors and the scratch, against the device's TOTAL memory - a screen that needs no allocation, all in
+// doubles; what is free at the moment shows when the allocation itself fails.  n3 NULL: the points entry with ntargets
+// points; else the box entry (which as there; positive axes).
+extern "C" int ndsmk_green_fits(const int32_t *nsrc2, const int32_t *n3, int which, long long ntargets,
+                                double caller_bytes) {
+  NDSM_REQUIRE_READY();
+  NDSM_CHECK_ARG(nsrc2);
+  const double nt = n3 ? box_targets(n3, which) : (double)ntargets;
+  size_t fr = 0, tot = 0;
+  const int rc = ndsmk_mem_info(&fr, &tot);
+  if (rc != 0) return rc;
+  if (nt > kMaxTargets || caller_bytes + own_bytes(nsrc2, n3, nt) > (double)tot)
+    return ndsmk_note_error(NDSMK_ENODEV, "green: the arrays and the scratch need more device memory than the device has");
+  return 0;
+}
+
+// B (3,npts) = the field at pts (3,npts); bz (nsx,nsy), pts and B are DEVICE arrays, h_xs and h_ys on the HOST.
+// Returns when B is complete.
+extern "C" int ndsmk_green_points(const int32_t *nsrc2, const double *h_xs, const double *h_ys, double zs,
+                                  const double *bz, int npts, const double *pts, double *B) {
+  NDSM_REQUIRE_READY();
+  NDSM_CHECK_ARG(nsrc2 && h_xs && h_ys && bz);
+  if (!source_ok(nsrc2, h_xs, h_ys) || npts < 0)
+    return ndsmk_note_error(NDSMK_EVALUE, "green_points: at least 2 source nodes per axis, spacings > 0 and npts >= 0");
+  if (npts == 0) return 0;
+  NDSM_CHECK_ARG(pts && B);
+  Targets g = {};
+  g.gen = GEN_POINTS;
+  g.count = npts;
+  g.pts = pts;
+  return run(nsrc2, h_xs, h_ys, zs, bz, g, nullptr, nullptr, nullptr, nullptr, B);
+}
+
+// B (nx,ny,nz,3): which = 0 the nodes with an index at either end of an axis (every other node keeps what it holds),
+// which = 1 all nodes.  bz and B are DEVICE arrays, the five mesh vectors on the HOST.  Returns when B is complete.
+extern "C" int ndsmk_green_box(const int32_t *nsrc2, const double *h_xs, const double *h_ys, double zs,
+                               const double *bz, const int32_t *n3, const double *h_x, const double *h_y,
+                               const double *h_z, int which, double *B) {
+  NDSM_REQUIRE_READY();
+  NDSM_CHECK_ARG(nsrc2 && h_xs && h_ys && bz && n3 && h_x && h_y && h_z && B);
+  if (!source_ok(nsrc2, h_xs, h_ys) || (which != 0 && which != 1) || n3[0] < 2 || n3[1] < 2 || n3[2] < 2 ||
+      !(h_z[0] >= zs))
+    return ndsmk_note_error(NDSMK_EVALUE, "green_box: at least 2 source nodes per axis, spacings > 0, which 0 or 1, "
+                                          "at least 2 box nodes per axis and z[0] >= zs");
+  if (box_targets(n3, which) > kMaxTargets)
+    return ndsmk_note_error(NDSMK_ENODEV, "green_box: more targets than any device holds");
+  Targets g = {};
+  g.gen = which == 0 ? GEN_FACES : GEN_VOLUME;
+  g.count = (i64)box_targets(n3, which);      // (exact: whole numbers below 2^53)
+  g.nx = n3[0];
+  g.ny = n3[1];
+  g.nz = n3[2];
+  return run(nsrc2, h_xs, h_ys, zs, bz, g, n3, h_x, h_y, h_z, B);
+}

@@ -253,6 +253,19 @@ int ndsmk_resample_weighted(const int32_t *nsrc3, const int32_t *ndst3, int ncom
                             const double *wsrc, double *dst, double *wdst);
 int ndsmk_paste_faces(const int32_t *n3, int ncomp, int which, const double *src, double *dst);
 
+/* Green's-function field of the half space above a magnetogram (green.hip; semantics: include/ndsm_hip.h,
+ * ndsm_hip_green_points).  bz (nsx,nsy), pts (3,npts) and B are DEVICE arrays; the mesh vectors h_* stay on the HOST.
+ * green_points: B (3,npts) at pts.  green_box: B (nx,ny,nz,3) on the mesh h_x, h_y, h_z - which = 0 the nodes with an
+ * index at either end of an axis (the others keep what they hold), 1 all nodes.  9004 for a source axis < 2, a spacing
+ * not > 0, npts < 0, which outside 0/1, a box axis < 2 or h_z[0] < zs; npts = 0 touches nothing.  Both return when B is
+ * complete.  green_fits: 0, or 9001 when caller_bytes plus the mesh vectors and the scratch exceed the device's memory
+ * (n3 NULL: ntargets points; else the box entry with which). */
+int ndsmk_green_fits(const int32_t *nsrc2, const int32_t *n3, int which, long long ntargets, double caller_bytes);
+int ndsmk_green_points(const int32_t *nsrc2, const double *h_xs, const double *h_ys, double zs, const double *bz,
+                       int npts, const double *pts, double *B);
+int ndsmk_green_box(const int32_t *nsrc2, const double *h_xs, const double *h_ys, double zs, const double *bz,
+                    const int32_t *n3, const double *h_x, const double *h_y, const double *h_z, int which, double *B);
+
 /* Magnetogram preprocessing (preprocess.hip; semantics: include/ndsm_hip.h, ndsm_hip_vecpot_preprocess).  B0, B1
  * (nx,ny,3): the two field buffers, B0 holds the start; La (nx,ny,3,2): the two Lambda buffers; obs (nx,ny,3): the
  * observation, never written; work: ndsmk_preprocess_work_bytes() bytes, the state and the block partials; all DEVICE

@@ -1412,6 +1412,250 @@ contains
     ierr = reported(who, rc)
   end function
 
+  ! ---- Green's-function field of the half space above a magnetogram (semantics in include/ndsm_hip.h) ----
+  ! bz (nsx,nsy) on the mesh xs, ys at height zs; pts (3,npts) in, B (3,npts) out.  No handle.  The mesh vectors stay
+  ! on the host in both forms.  HOST arrays
+  function ndsm_hip_green_points(nsrc, xs, ys, zs, bz, npts, pts, B) bind(c, name="ndsm_hip_green_points") result(ierr)
+    type(c_ptr), value :: nsrc, xs, ys, bz, pts, B
+    real(c_double), value :: zs
+    integer(c_int), value :: npts
+    integer(c_int) :: ierr
+    ierr = green_entry(.false., nsrc, xs, ys, zs, bz, npts, pts, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, &
+                       0_c_int, B, .false., "ndsm_hip_green_points")
+  end function
+
+  ! the same with bz, pts and B DEVICE arrays of the library's GPU
+  function ndsm_hip_green_points_device(nsrc, xs, ys, zs, dbz, npts, dpts, dB) &
+      bind(c, name="ndsm_hip_green_points_device") result(ierr)
+    type(c_ptr), value :: nsrc, xs, ys, dbz, dpts, dB
+    real(c_double), value :: zs
+    integer(c_int), value :: npts
+    integer(c_int) :: ierr
+    ierr = green_entry(.false., nsrc, xs, ys, zs, dbz, npts, dpts, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, &
+                       0_c_int, dB, .true., "ndsm_hip_green_points_device")
+  end function
+
+  ! B (nx,ny,nz,3) on the box mesh x, y, z: which = 0 the nodes with an index at either end of an axis (every other
+  ! node of B keeps what it holds), 1 all nodes.  HOST arrays
+  function ndsm_hip_green_box(nsrc, xs, ys, zs, bz, nshape, x, y, z, which, B) bind(c, name="ndsm_hip_green_box") &
+      result(ierr)
+    type(c_ptr), value :: nsrc, xs, ys, bz, nshape, x, y, z, B
+    real(c_double), value :: zs
+    integer(c_int), value :: which
+    integer(c_int) :: ierr
+    ierr = green_entry(.true., nsrc, xs, ys, zs, bz, 0_c_int, c_null_ptr, nshape, x, y, z, which, B, .false., &
+                       "ndsm_hip_green_box")
+  end function
+
+  ! the same with bz and B DEVICE arrays of the library's GPU
+  function ndsm_hip_green_box_device(nsrc, xs, ys, zs, dbz, nshape, x, y, z, which, dB) &
+      bind(c, name="ndsm_hip_green_box_device") result(ierr)
+    type(c_ptr), value :: nsrc, xs, ys, dbz, nshape, x, y, z, dB
+    real(c_double), value :: zs
+    integer(c_int), value :: which
+    integer(c_int) :: ierr
+    ierr = green_entry(.true., nsrc, xs, ys, zs, dbz, 0_c_int, c_null_ptr, nshape, x, y, z, which, dB, .true., &
+                       "ndsm_hip_green_box_device")
+  end function
+
+  ! the source of a Green's-function call: 0, or 9004 unless there are 2 nodes per axis and both spacings are > 0
+  function green_source_ok(ns, xs, ys) result(ierr)
+    integer(c_int), intent(in) :: ns(2)
+    type(c_ptr), intent(in) :: xs, ys
+    integer(c_int) :: ierr
+    real(c_double), pointer :: qx(:), qy(:)
+    ierr = NDSMK_EVALUE
+    if (any(ns < 2)) return
+    call c_f_pointer(xs, qx, [2])
+    call c_f_pointer(ys, qy, [2])
+    if (qx(2) - qx(1) > 0.0_c_double .and. qy(2) - qy(1) > 0.0_c_double) ierr = 0
+  end function
+
+  function green_entry(box, nsrc, xs, ys, zs, bz, npts, pts, nshape, x, y, z, which, B, on_device, who) result(ierr)
+    logical, intent(in) :: box, on_device
+    type(c_ptr), intent(in) :: nsrc, xs, ys, bz, pts, nshape, x, y, z, B
+    real(c_double), intent(in) :: zs
+    integer(c_int), intent(in) :: npts, which
+    character(len=*), intent(in) :: who
+    integer(c_int) :: ierr
+    integer(c_int), pointer :: ns(:), nb(:)
+    real(c_double), pointer :: qz(:)
+    integer(c_int32_t) :: ns2(2)
+    integer(c_int32_t), target :: n3(3)
+    integer(c_size_t) :: bsrc, bout
+    real(c_double) :: dsrc, dout
+    type(c_ptr) :: buf, dpts, pout, p3
+    integer(c_int) :: rc
+    integer :: d
+    ierr = ndsmk_init(-1_c_int)
+    if (ierr /= 0) return
+    ! a call the device cannot hold is refused before anything is allocated - as soon as its shapes can be read
+    if (c_associated(nsrc) .and. (c_associated(nshape) .or. .not. box)) then
+      call c_f_pointer(nsrc, ns, [2])
+      ns2 = ns; n3 = 1; p3 = c_null_ptr
+      if (box) then
+        call c_f_pointer(nshape, nb, [3])
+        n3 = nb; p3 = c_loc(n3)
+      end if
+      if (all(ns2 >= 1) .and. all(n3 >= 1) .and. npts >= 0) then
+        ! (in doubles: three axes of up to 2^31 nodes overflow 64-bit whole numbers; past the screen they do not)
+        dsrc = 8.0_c_double * product(real(ns2, c_double))
+        dout = 24.0_c_double * merge(product(real(n3, c_double)), real(npts, c_double), box)
+        ierr = ndsmk_green_fits(ns2, p3, merge(0_c_int, 1_c_int, which == 0), int(npts, c_long_long), &
+                                merge(0.0_c_double, dsrc + dout * merge(1.0_c_double, 2.0_c_double, box), on_device))
+        if (ierr /= 0) return
+        bsrc = int(dsrc, c_size_t)
+        bout = int(dout, c_size_t)
+      end if
+    end if
+    ierr = NDSMK_EARG
+    if (.not. (c_associated(nsrc) .and. c_associated(xs) .and. c_associated(ys) .and. c_associated(bz))) return
+    if (box .and. .not. (c_associated(nshape) .and. c_associated(x) .and. c_associated(y) .and. c_associated(z) .and. &
+                         c_associated(B))) return
+    ierr = green_source_ok(ns, xs, ys)
+    if (ierr == 0 .and. box) then
+      call c_f_pointer(z, qz, [1])
+      if (any(n3 < 2) .or. (which /= 0 .and. which /= 1) .or. .not. (qz(1) >= zs)) ierr = NDSMK_EVALUE
+    end if
+    if (ierr == 0 .and. npts < 0) ierr = NDSMK_EVALUE
+    if (ierr /= 0) then
+      ierr = ndsmk_note_error(NDSMK_EVALUE, "green: at least 2 source nodes per axis, spacings > 0, npts >= 0, which "// &
+                              "0 or 1, at least 2 box nodes per axis and z[0] >= zs"//c_null_char)
+      return
+    end if
+    if (.not. box) then
+      if (npts == 0) return
+      ierr = NDSMK_EARG
+      if (.not. (c_associated(pts) .and. c_associated(B))) return
+    end if
+    if (on_device) then
+      if (box) then
+        rc = ndsmk_green_box(ns2, xs, ys, zs, bz, n3, x, y, z, which, B)
+      else
+        rc = ndsmk_green_points(ns2, xs, ys, zs, bz, npts, pts, B)
+      end if
+    else
+      ! bz, then (points) pts, then B; which = 0 leaves nodes of B untouched, so B goes up first
+      buf = c_null_ptr
+      rc = ndsmk_alloc(buf, bsrc + bout * merge(1_c_size_t, 2_c_size_t, box))
+      if (rc == 0) then
+        dpts = dptr_offset(buf, bsrc)
+        pout = dptr_offset(buf, bsrc + merge(0_c_size_t, bout, box))
+        rc = ndsmk_h2d(buf, bz, bsrc)
+        if (box) then
+          if (rc == 0 .and. which == 0) rc = ndsmk_h2d(pout, B, bout)
+          if (rc == 0) rc = ndsmk_green_box(ns2, xs, ys, zs, buf, n3, x, y, z, which, pout)
+        else
+          if (rc == 0) rc = ndsmk_h2d(dpts, pts, bout)
+          if (rc == 0) rc = ndsmk_green_points(ns2, xs, ys, zs, buf, npts, dpts, pout)
+        end if
+        if (rc == 0) rc = ndsmk_d2h(B, pout, bout)
+        d = ndsmk_free(buf)
+        if (rc == 0) rc = int(d, c_int)
+      end if
+    end if
+    ierr = reported(who, rc)
+  end function
+
+  ! The open-box potential field: ndsm_hip_green_box_device (which = 0) on the handle's mesh into the device B, then
+  ! ndsm_hip_vecpot_solve_device - bit for bit that composition, no field crossing PCIe in between.  A: in the first
+  ! guess, out A; B: out (its interior nodes are read by nothing).  HOST arrays (nx,ny,nz,3), bz (nsx,nsy)
+  function ndsm_hip_vecpot_open(handle, ioptc, ropt, nsrc, xs, ys, zs, bz, A, B) bind(c, name="ndsm_hip_vecpot_open") &
+      result(ierr)
+    type(c_ptr), value :: handle, nsrc, xs, ys, bz, A, B
+    integer(c_int), intent(inout) :: ioptc(0:OPT_LEN - 1)
+    real(c_double), intent(inout) :: ropt(0:OPT_LEN - 1)
+    real(c_double), value :: zs
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_open(handle, ioptc, ropt, nsrc, xs, ys, zs, bz, A, B, .false., "ndsm_hip_vecpot_open")
+  end function
+
+  ! the same with bz, A and B DEVICE arrays of the library's GPU; the face nodes of dB are written, then the solve runs
+  function ndsm_hip_vecpot_open_device(handle, ioptc, ropt, nsrc, xs, ys, zs, dbz, dA, dB) &
+      bind(c, name="ndsm_hip_vecpot_open_device") result(ierr)
+    type(c_ptr), value :: handle, nsrc, xs, ys, dbz, dA, dB
+    integer(c_int), intent(inout) :: ioptc(0:OPT_LEN - 1)
+    real(c_double), intent(inout) :: ropt(0:OPT_LEN - 1)
+    real(c_double), value :: zs
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_open(handle, ioptc, ropt, nsrc, xs, ys, zs, dbz, dA, dB, .true., "ndsm_hip_vecpot_open_device")
+  end function
+
+  function vecpot_handle_open(handle, ioptc, ropt, nsrc, xs, ys, zs, bz, A, B, on_device, who) result(ierr)
+    type(c_ptr), intent(in) :: handle, nsrc, xs, ys, bz, A, B
+    integer(c_int), intent(inout) :: ioptc(0:OPT_LEN - 1)
+    real(c_double), intent(inout) :: ropt(0:OPT_LEN - 1)
+    real(c_double), intent(in) :: zs
+    logical, intent(in) :: on_device
+    character(len=*), intent(in) :: who
+    integer(c_int) :: ierr
+    type(vecpot_ctx), pointer :: ctx
+    integer(c_int), pointer :: ns(:)
+    integer(c_int32_t) :: ns2(2)
+    integer(c_int32_t), target :: n3(3)
+    integer(c_size_t) :: bsrc, nb3
+    type(c_ptr) :: buf, dA, dB
+    integer(c_int) :: rc
+    integer :: d
+    ierr = live_ctx(handle, ctx)
+    if (ierr /= 0) return
+    n3 = ctx%n3
+    ! as in green_entry: refused before anything is allocated, as soon as the shapes can be read (in doubles)
+    if (c_associated(nsrc)) then
+      call c_f_pointer(nsrc, ns, [2])
+      ns2 = ns
+      if (all(ns2 >= 1)) then
+        ierr = ndsmk_green_fits(ns2, c_loc(n3), 0_c_int, 0_c_long_long, &
+                                merge(0.0_c_double, 8.0_c_double * product(real(ns2, c_double)) + &
+                                      48.0_c_double * product(real(n3, c_double)), on_device))
+        if (ierr /= 0) return
+      end if
+    end if
+    ierr = NDSMK_EARG
+    if (.not. (c_associated(nsrc) .and. c_associated(xs) .and. c_associated(ys) .and. c_associated(bz) .and. &
+               c_associated(A) .and. c_associated(B))) return
+    ierr = green_source_ok(ns, xs, ys)
+    if (ierr == 0 .and. .not. (ctx%qz(1) >= zs)) ierr = NDSMK_EVALUE
+    if (ierr /= 0) then
+      ierr = ndsmk_note_error(NDSMK_EVALUE, "vecpot_open: at least 2 source nodes per axis, spacings > 0 and "// &
+                              "z[0] >= zs"//c_null_char)
+      return
+    end if
+    bsrc = int(product(int(ns2, c_int64_t)) * 8_c_int64_t, c_size_t)
+    nb3 = int(product(int(n3, c_int64_t)) * 24_c_int64_t, c_size_t)
+    if (on_device) then
+      rc = ndsmk_green_box(ns2, xs, ys, zs, bz, n3, c_loc(ctx%qx), c_loc(ctx%qy), c_loc(ctx%qz), 0_c_int, B)
+      ierr = reported(who, rc)
+      if (ierr == 0) ierr = vecpot_handle_solve(handle, ioptc, ropt, A, B, .true., who)
+    else
+      ! bz, A and a B of zeros on the device; only A and B come home
+      buf = c_null_ptr
+      rc = ndsmk_alloc(buf, bsrc + 2_c_size_t * nb3)
+      if (rc == 0) then
+        dA = dptr_offset(buf, bsrc)
+        dB = dptr_offset(buf, bsrc + nb3)
+        rc = ndsmk_h2d(buf, bz, bsrc)
+        if (rc == 0) rc = ndsmk_h2d(dA, A, nb3)
+        if (rc == 0) rc = ndsmk_fill0(dB, nb3)
+        if (rc == 0) rc = ndsmk_green_box(ns2, xs, ys, zs, buf, n3, c_loc(ctx%qx), c_loc(ctx%qy), c_loc(ctx%qz), &
+                                          0_c_int, dB)
+        ierr = reported(who, rc)
+        if (ierr == 0) then
+          ierr = vecpot_handle_solve(handle, ioptc, ropt, dA, dB, .true., who)
+          if (ierr < NDSMK_ENODEV) then
+            rc = ndsmk_d2h(A, dA, nb3)
+            if (rc == 0) rc = ndsmk_d2h(B, dB, nb3)
+            if (rc /= 0) ierr = reported(who, rc)
+          end if
+        end if
+        d = ndsmk_free(buf)
+        if (ierr < NDSMK_ENODEV .and. d /= 0) ierr = reported(who, int(d, c_int))
+      else
+        ierr = reported(who, rc)
+      end if
+    end if
+  end function
+
   ! The coarse-to-fine cascade of the optimization method (semantics in include/ndsm_hip.h).  handles (nlevels): the
   ! finest mesh's handle first, then coarser meshes of the same box.  B (nx,ny,nz,3) and w (nx,ny,nz; may be NULL) on
   ! the finest mesh, as for ndsm_hip_vecpot_optimize.  niter_max, dt0, dt_min (nlevels) per level; hist

@@ -664,6 +664,33 @@ module ndsmh_iface
       type(c_ptr), value :: src, dst
       integer(c_int) :: rc
     end function
+    ! ---- the Green's-function field of a magnetogram (green.hip) ----
+    function ndsmk_green_fits(nsrc2, n3, which, ntargets, caller_bytes) bind(c, name="ndsmk_green_fits") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_long_long, c_double
+      integer(c_int32_t), intent(in) :: nsrc2(2)
+      type(c_ptr), value :: n3
+      integer(c_int), value :: which
+      integer(c_long_long), value :: ntargets
+      real(c_double), value :: caller_bytes
+      integer(c_int) :: rc
+    end function
+    function ndsmk_green_points(nsrc2, h_xs, h_ys, zs, bz, npts, pts, B) bind(c, name="ndsmk_green_points") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_double
+      integer(c_int32_t), intent(in) :: nsrc2(2)
+      type(c_ptr), value :: h_xs, h_ys, bz, pts, B
+      real(c_double), value :: zs
+      integer(c_int), value :: npts
+      integer(c_int) :: rc
+    end function
+    function ndsmk_green_box(nsrc2, h_xs, h_ys, zs, bz, n3, h_x, h_y, h_z, which, B) &
+        bind(c, name="ndsmk_green_box") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_double
+      integer(c_int32_t), intent(in) :: nsrc2(2), n3(3)
+      type(c_ptr), value :: h_xs, h_ys, bz, h_x, h_y, h_z, B
+      real(c_double), value :: zs
+      integer(c_int), value :: which
+      integer(c_int) :: rc
+    end function
     ! ---- magnetogram preprocessing (preprocess.hip) ----
     function ndsmk_preprocess_work_bytes() bind(c, name="ndsmk_preprocess_work_bytes") result(nb)
       import :: c_size_t

@@ -1209,6 +1209,26 @@ int ndsm_hip_debug_zero_guess(int on);
 /* 1: u(level) of this ndsm_hip_mg_create handle is at present a zero guess that was declared and not written (any
  * download, upload or single operation that reads it writes the zeros first), 0: it is in memory */
 int ndsm_hip_debug_u_declared_zero(void *handle, int level);
+/* Which kernel an inter-level transfer takes is decided by the size of the fine level; this sets the sizes and the
+ * streamed restriction's launch so that the parity tests can run every form on grids the oracle handles.  A negative
+ * value restores the built-in choice of that knob; (-1, -1, -1, -1) restores all four.
+ *   restrict_min_points: fine points from which a 3-D level pair is sent to the LDS-streamed restriction
+ *     (csrc/restrict_stream.hip) instead of the gather kernel - built in: 6 Mi.  Read when a hierarchy is built: set it
+ *     before ndsm_hip_mg_create / ndsm_hip_world_create.  The kernel's tile must still cover the pair's taps.
+ *   prolong_min_points: fine points from which u_f += P u_c runs the LDS-tiled kernel - built in: 2 Mi.  Read at every
+ *     call; nx >= 64 and at least 16 coarse points per axis are needed as before.
+ *   rs_variant: 5, 8 or 10 - the form of the streamed restriction (environment NDSM_RS_VARIANT, which is read once per
+ *     process; this overrides it at run time).  The launcher's own demotions stay: 10 -> 8 for odd nx, fp32 fine fields
+ *     and planes of 2 GiB or more, -> 5 where the pair's z windows do not fit the schedule.  Another value >= 0: 9002.
+ *   rs_chunk: coarse planes per z chunk of the streamed restriction, clamped to [1, min(planes, 64)].
+ * Results never depend on these values (bit for bit); only speed does. */
+int ndsm_hip_debug_transfer_cfg(long long restrict_min_points, long long prolong_min_points, int rs_variant,
+                                int rs_chunk);
+/* The kernels the transfers level -> level + 1 (level >= 1) of an ndsm_hip_mg_create handle take, as the launchers
+ * themselves decide them: out[0] = 0 the gather restriction / 5, 8, 10 the streamed form after the demotions,
+ * out[1], out[2] = coarse planes per chunk and chunks of that launch (0, 0 for the gather kernel), out[3] = 1 the
+ * tiled prolongation / 0 the per-point one.  Needs ndsm_hip_init.  9002: no such level pair. */
+int ndsm_hip_debug_transfer_form(void *handle, int level, int out[4]);
 
 /* ---- Open-box potential field from a magnetogram (DESIGN.md "Open-box potential field") ------------------------------
  * Every entry that starts from a potential field reads B.n on all six faces of the box; a magnetogram gives the lower

@@ -168,6 +168,8 @@ def load_library(path=None):
                                             ctypes.POINTER(ctypes.c_int64), ctypes.c_int, _ip]
     L.ndsm_hip_debug_zero_guess.argtypes = [ctypes.c_int]
     L.ndsm_hip_debug_u_declared_zero.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    L.ndsm_hip_debug_transfer_cfg.argtypes = [ctypes.c_longlong, ctypes.c_longlong, ctypes.c_int, ctypes.c_int]
+    L.ndsm_hip_debug_transfer_form.argtypes = [ctypes.c_void_p, ctypes.c_int, _ip]
     if path is None:
         _LIB = L
     return L
@@ -191,6 +193,15 @@ def last_error(L=None):
 def _check(rc, what, L=None):
     if rc != 0:
         raise NdsmHipError(f"{what} failed with code {rc}: {last_error(L)}")
+
+
+def transfer_cfg(restrict_min_points=-1, prolong_min_points=-1, rs_variant=-1, rs_chunk=-1, L=None):
+    """development hook (ndsm_hip_debug_transfer_cfg): the level sizes from which the streamed restriction (read when
+    a solver is created) and the tiled prolongation run, the streamed restriction's form (5, 8, 10) and its coarse
+    planes per chunk; negative = the built-in choice, no arguments = all four built in"""
+    L = L or load_library()
+    _check(L.ndsm_hip_debug_transfer_cfg(int(restrict_min_points), int(prolong_min_points), int(rs_variant),
+                                         int(rs_chunk)), "ndsm_hip_debug_transfer_cfg", L)
 
 
 def _d(a):
@@ -269,6 +280,14 @@ class MGSolver:
         if rc < 0:
             raise NdsmHipError(f"bad precision mode {mode}")
         return rc == 1
+
+    def transfer_form(self, level):
+        """(restriction form, kc, nkc, tiled prolongation) of the transfers level -> level + 1 as the launchers
+        decide them now (ndsm_hip_debug_transfer_form): form 0 = gather, 5 / 8 / 10 = streamed"""
+        out = np.zeros(4, dtype=np.intc)
+        _check(self.L.ndsm_hip_debug_transfer_form(self.h, int(level), out.ctypes.data_as(_ip)), "transfer_form",
+               self.L)
+        return tuple(int(v) for v in out)
 
     def op(self, op, level, count=1):
         _check(self.L.ndsm_hip_mg_op(self.h, op, level, count), f"op {op}", self.L)

@@ -149,6 +149,15 @@ int ndsmk_restrict(const ndsmk_xfer *x, const double *r_f, double *rhs_c, double
 void ndsmk_restrict_stream_tile(int *ci, int *cj, int *fx, int *fy, int *maxt);
 /* u_f += P u_c (ndsm_multigrid_core.f90:659,672) */
 int ndsmk_prolong_add(const ndsmk_xfer *x, const double *u_c, double *u_f);
+/* Which form the two calls above take is decided by level size.  ndsmk_debug_transfer_cfg (tests) replaces the sizes
+ * (fine points from which a pair is marked for the streamed restriction when its hierarchy is built / from which
+ * ndsmk_prolong_add takes the tiled kernel), the streamed restriction's form (5, 8, 10 - NDSM_RS_VARIANT) and its coarse
+ * planes per chunk; a negative value restores the built-in choice.  ndsmk_debug_transfer_form: out[0] = 0 gather /
+ * 5, 8, 10 the streamed form ndsmk_restrict runs for x, out[1..2] = its kc and nkc, out[3] = 1 if ndsmk_prolong_add
+ * runs the tiled kernel - answered by the functions the launchers themselves ask. */
+long long ndsmk_restrict_stream_min_points(void);
+int ndsmk_debug_transfer_cfg(long long restrict_min_points, long long prolong_min_points, int rs_variant, int rs_chunk);
+int ndsmk_debug_transfer_form(const ndsmk_xfer *x, int out[4]);
 /* blocking: out[0] = max|a-b|, out[1] = sum|a-b| ; then b <- a if copy != 0
  * (update_u, ndsm_multigrid_core.f90:1077-1122 ; du_metrics :808-853) */
 int ndsmk_diff_metrics(const double *a, double *b, int64_t n, int copy, double *h_out2);

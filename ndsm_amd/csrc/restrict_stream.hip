@@ -486,6 +486,9 @@ __global__ __launch_bounds__(CI *CJ, WPS) void restrict_stream_k(const TF *__res
 
 constexpr int kCI = 64, kCJ = 8, kMT = 5, kKCMax = 64;
 
+// ndsmk_debug_transfer_cfg (tests): the form / the coarse planes per chunk to run, < 0 = the built-in choice
+int g_cfg_variant = -1, g_cfg_chunk = -1;
+
 // Which form runs (NDSM_RS_VARIANT, tuning aid): 10 (default) = DMA + schedule + ordered accumulators where the level
 // pair allows it, 8 = register-staged with the schedule, 5 = register-staged with the table walk (what 10 and 8 fall
 // back to where the schedule's limits do not hold).  512^3 -> 256^3 on MI355X: 383 / 361-373 / 290-305 us for 5 / 8 / 10.
@@ -506,6 +509,7 @@ constexpr int kCI = 64, kCJ = 8, kMT = 5, kKCMax = 64;
 // (3 multiplications + 1 addition per tap and coarse plane: the reference's weight chain) whose issue floor is
 // ~125-200 us, in basic blocks of one tap behind uniform tests.
 int rs_variant() {
+  if (g_cfg_variant > 0) return g_cfg_variant;   // ndsmk_debug_transfer_cfg: tests pick the form in-process
   static int variant = -1;
   if (variant < 0) {
     const char *e = std::getenv("NDSM_RS_VARIANT");
@@ -528,34 +532,32 @@ extern "C" void ndsmk_restrict_stream_tile(int *ci, int *cj, int *fx, int *fy, i
   *maxt = kMT;
 }
 
+// What a launch of one form looks like - the kernel, its dynamic LDS, its tiles and its z chunks -, decided in one
+// place for the launcher and for ndsmk_debug_transfer_form.  Not a pure function: the first call per kernel and
+// runtime epoch sets the kernel's dynamic-LDS attribute and asks the runtime for its occupancy - so the query does
+// that too when it comes before the first launch (the same calls the launch would make, nothing else).
+struct RSPlan {
+  const void *kfn;
+  size_t lds_bytes;
+  int nti, ntj, kc, nkc;
+};
+
 template <typename TF, bool SCHED, bool DMA>
-static int launch_rs_v(const ndsmk_xfer *x, const TF *r_f, double *rhs_c, double *u_c) {
+static int plan_rs_v(const ndsmk_xfer *x, RSPlan *p) {
   constexpr int WPS = 4;
-  RSArgs a;
-  for (int d = 0; d < 3; ++d) {
-    a.nf[d] = x->nf[d];
-    a.nc[d] = x->nc[d];
-    a.rlo[d] = x->rlo[d];
-    a.rcnt[d] = x->rcnt[d];
-    a.rw[d] = x->rw[d];
-    a.maxt[d] = x->maxt[d];
-    a.w2[d] = x->w2[d];
-  }
-  a.f_k0 = x->f_k0;
-  a.c_k0 = x->c_k0;
-  a.c_beg = x->c_beg;
-  a.c_cnt = x->c_cnt;
-  a.nti = (x->nc[0] + kCI - 1) / kCI;
-  a.ntj = (x->nc[1] + kCJ - 1) / kCJ;
-  const int tiles = a.nti * a.ntj;
+  p->nti = (x->nc[0] + kCI - 1) / kCI;
+  p->ntj = (x->nc[1] + kCJ - 1) / kCJ;
+  const int tiles = p->nti * p->ntj;
   constexpr size_t lds_bytes = sizeof(double) * ((DMA ? 3 : 2) * (2 * kCI + 6) * (2 * kCJ + 5) + (2 * kCI + 6));
   const bool odd = (x->nf[0] & 1) != 0;
   const void *kfn;
-  if constexpr (DMA)   // (launch_rs_t sends only fp64 levels with even nx here)
+  if constexpr (DMA)   // (rs_form sends only fp64 levels with even nx here)
     kfn = reinterpret_cast<const void *>(restrict_stream_k<TF, kCI, kCJ, kMT, kKCMax, WPS, false, SCHED, true>);
   else
     kfn = odd ? reinterpret_cast<const void *>(restrict_stream_k<TF, kCI, kCJ, kMT, kKCMax, WPS, true, SCHED, false>)
               : reinterpret_cast<const void *>(restrict_stream_k<TF, kCI, kCJ, kMT, kKCMax, WPS, false, SCHED, false>);
+  p->kfn = kfn;
+  p->lds_bytes = lds_bytes;
   // coarse planes per chunk: a chunk of kc coarse planes walks ~2 kc + 3 fine planes: minimise (rounds of
   // workgroups at the kernel's occupancy) x (planes walked); the chunk's z tables must fit their LDS
   // arrays (kc <= kKCMax)
@@ -581,38 +583,90 @@ static int launch_rs_v(const ndsmk_xfer *x, const TF *r_f, double *rhs_c, double
     }
     if (k1 <= 4) break;
   }
-  a.kc = kc;
-  a.nkc = (x->c_cnt + kc - 1) / kc;
-  a.nwork = tiles * a.nkc;
+  if (g_cfg_chunk >= 0) {   // forced (tests): clamped to what the chunk's z tables hold
+    const int top = x->c_cnt < kKCMax ? x->c_cnt : kKCMax;
+    kc = g_cfg_chunk < 1 ? 1 : (g_cfg_chunk > top ? top : g_cfg_chunk);
+  }
+  p->kc = kc;
+  p->nkc = (x->c_cnt + kc - 1) / kc;
+  return 0;
+}
+
+template <typename TF, bool SCHED, bool DMA>
+static int launch_rs_v(const ndsmk_xfer *x, const TF *r_f, double *rhs_c, double *u_c) {
+  RSPlan p;
+  if (int rc = plan_rs_v<TF, SCHED, DMA>(x, &p)) return rc;
+  RSArgs a;
+  for (int d = 0; d < 3; ++d) {
+    a.nf[d] = x->nf[d];
+    a.nc[d] = x->nc[d];
+    a.rlo[d] = x->rlo[d];
+    a.rcnt[d] = x->rcnt[d];
+    a.rw[d] = x->rw[d];
+    a.maxt[d] = x->maxt[d];
+    a.w2[d] = x->w2[d];
+  }
+  a.f_k0 = x->f_k0;
+  a.c_k0 = x->c_k0;
+  a.c_beg = x->c_beg;
+  a.c_cnt = x->c_cnt;
+  a.nti = p.nti;
+  a.ntj = p.ntj;
+  a.kc = p.kc;
+  a.nkc = p.nkc;
+  a.nwork = p.nti * p.ntj * a.nkc;
   static int probe = -1;
   if (probe < 0) probe = std::getenv("NDSM_RS_PROBE") ? std::atoi(std::getenv("NDSM_RS_PROBE")) : 0;
   a.probe = probe;
   const int nblk = ((a.nwork + 7) / 8) * 8;
   void *args[] = {(void *)&r_f, (void *)&rhs_c, (void *)&u_c, (void *)&a};
-  NDSM_HIP(hipLaunchKernel(kfn, dim3(nblk), dim3(kCI * kCJ), args, lds_bytes, stream()));
+  NDSM_HIP(hipLaunchKernel(p.kfn, dim3(nblk), dim3(kCI * kCJ), args, p.lds_bytes, stream()));
   return 0;
 }
 
+// The form a level pair takes: the requested one (rs_variant) after the demotions the kernels' limits ask for
 template <typename TF>
-static int launch_rs_t(const ndsmk_xfer *x, const TF *r_f, double *rhs_c, double *u_c) {
+static int rs_form(const ndsmk_xfer *x) {
   int v = rs_variant();
   // The scheduled forms hold a chunk's z windows in a fixed-size table: at most four coarse windows per fine plane
   // (four weight slots, four accumulators) and at most 2 * kKCMax + 16 fine planes per chunk (KPL records).  The host
   // measures both for a level pair (ndsmh_mg.f90: stream_restrict_applies); they are checked HERE, against the
   // kernel's limits - a descriptor that does not carry the numbers takes the table walk instead.
-  {
-    const int wmax = (x->stream_ok >> 8) & 255, smax = (x->stream_ok >> 16) & 32767;
-    if (v != 5 && (!(x->stream_ok & 4) || wmax < 1 || wmax > 4 || smax < 1 || smax > 2 * kKCMax + 16)) v = 5;
-    // the DMA form: fp64 fine planes whose rows are 16-byte aligned and whose byte offsets fit the descriptor
-    if (v == 10 && (!std::is_same<TF, double>::value || (x->nf[0] & 1) ||
-                    (int64_t)x->nf[0] * x->nf[1] * (int64_t)sizeof(double) >= (int64_t)0x80000000ll))
-      v = 8;
-  }
+  const int wmax = (x->stream_ok >> 8) & 255, smax = (x->stream_ok >> 16) & 32767;
+  if (v != 5 && (!(x->stream_ok & 4) || wmax < 1 || wmax > 4 || smax < 1 || smax > 2 * kKCMax + 16)) v = 5;
+  // the DMA form: fp64 fine planes whose rows are 16-byte aligned and whose byte offsets fit the descriptor
+  if (v == 10 && (!std::is_same<TF, double>::value || (x->nf[0] & 1) ||
+                  (int64_t)x->nf[0] * x->nf[1] * (int64_t)sizeof(double) >= (int64_t)0x80000000ll))
+    v = 8;
+  return v;
+}
+
+template <typename TF>
+static int launch_rs_t(const ndsmk_xfer *x, const TF *r_f, double *rhs_c, double *u_c) {
+  const int v = rs_form<TF>(x);
   if (v == 10) {
     if constexpr (std::is_same<TF, double>::value) return launch_rs_v<TF, true, true>(x, r_f, rhs_c, u_c);
   }
   if (v == 8) return launch_rs_v<TF, true, false>(x, r_f, rhs_c, u_c);
   return launch_rs_v<TF, false, false>(x, r_f, rhs_c, u_c);
+}
+
+void restrict_stream_cfg(int variant, int chunk) {
+  g_cfg_variant = (variant == 5 || variant == 8 || variant == 10) ? variant : -1;
+  g_cfg_chunk = chunk < 0 ? -1 : chunk;
+}
+
+// out = the form (5, 8, 10), kc and nkc of the launch launch_restrict_stream would make for this pair
+int restrict_stream_form(const ndsmk_xfer *x, int out[3]) {
+  const int v = rs_form<double>(x);
+  RSPlan p;
+  const int rc = v == 10 ? plan_rs_v<double, true, true>(x, &p)
+                         : (v == 8 ? plan_rs_v<double, true, false>(x, &p) : plan_rs_v<double, false, false>(x, &p));
+  if (rc) return rc;
+  out[0] = v;
+  out[1] = p.kc;
+  out[2] = p.nkc;
+  return 0;
 }
 
 int launch_restrict_stream(const ndsmk_xfer *x, const double *r_f, double *rhs_c, double *u_c) {

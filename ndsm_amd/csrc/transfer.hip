@@ -20,6 +20,8 @@
 namespace ndsm {
 int launch_restrict_stream(const ndsmk_xfer *x, const double *r_f, double *rhs_c, double *u_c);
 int launch_restrict_stream_f32(const ndsmk_xfer *x, const float *r_f, double *rhs_c, double *u_c);
+void restrict_stream_cfg(int variant, int chunk);
+int restrict_stream_form(const ndsmk_xfer *x, int out[3]);
 }
 
 namespace {
@@ -265,14 +267,57 @@ int to_dev(const ndsmk_xfer *x, XferDev *d, int *ndim) {
   return 0;
 }
 
+// ndsmk_debug_transfer_cfg (tests): the level sizes from which the large-level forms run, < 0 = built in
+long long g_restrict_min = -1, g_prolong_min = -1;
+constexpr long long kRestrictStreamMin = 6ll << 20, kProlongTileMin = 1ll << 21;
+
+// which kernel a call takes - asked by the launchers below and by ndsmk_debug_transfer_form
+bool restrict_streamed(const ndsmk_xfer *x, int ndim) { return ndim == 3 && (x->stream_ok & 1); }
+
+// the tiled kernel assumes a fine tile spans at most PC_* coarse points: true for every
+// ratio (n_f-1)/(n_c-1) <= 2.2, i.e. all but the tiniest levels - which do not need it
+bool prolong_tiled(const XferDev &d, int ndim) {
+  return ndim == 3 && (int64_t)d.nf[0] * d.nf[1] * d.f_cnt >= (g_prolong_min >= 0 ? g_prolong_min : kProlongTileMin) &&
+         d.nf[0] >= 64 && d.nc[0] >= 16 && d.nc[1] >= 16 && d.nc[2] >= 16;
+}
+
 }  // namespace
+
+// the fine level's size from which the host marks a pair for the streamed restriction (ndsmh_mg.f90:
+// stream_restrict_applies; read when a hierarchy is built)
+extern "C" long long ndsmk_restrict_stream_min_points(void) {
+  return g_restrict_min >= 0 ? g_restrict_min : kRestrictStreamMin;
+}
+
+extern "C" int ndsmk_debug_transfer_cfg(long long restrict_min_points, long long prolong_min_points, int rs_variant,
+                                        int rs_chunk) {
+  if (rs_variant >= 0 && rs_variant != 5 && rs_variant != 8 && rs_variant != 10)
+    return ndsm::fail(NDSMK_EARG, "transfer_cfg: the streamed restriction's forms are 5, 8 and 10", __FILE__, __LINE__);
+  g_restrict_min = restrict_min_points < 0 ? -1 : restrict_min_points;
+  g_prolong_min = prolong_min_points < 0 ? -1 : prolong_min_points;
+  ndsm::restrict_stream_cfg(rs_variant, rs_chunk);
+  return 0;
+}
+
+extern "C" int ndsmk_debug_transfer_form(const ndsmk_xfer *x, int out[4]) {
+  NDSM_REQUIRE_READY();
+  XferDev d;
+  int ndim;
+  if (int rc = to_dev(x, &d, &ndim)) return rc;
+  out[0] = out[1] = out[2] = 0;
+  if (restrict_streamed(x, ndim)) {
+    if (int rc = ndsm::restrict_stream_form(x, out)) return rc;
+  }
+  out[3] = prolong_tiled(d, ndim) ? 1 : 0;
+  return 0;
+}
 
 extern "C" int ndsmk_restrict(const ndsmk_xfer *x, const double *r_f, double *rhs_c, double *u_c) {
   NDSM_REQUIRE_READY();
   XferDev d;
   int ndim;
   if (int rc = to_dev(x, &d, &ndim)) return rc;
-  if (ndim == 3 && (x->stream_ok & 1)) return ndsm::launch_restrict_stream(x, r_f, rhs_c, u_c);
+  if (restrict_streamed(x, ndim)) return ndsm::launch_restrict_stream(x, r_f, rhs_c, u_c);
   dim3 block(32, 8, 1);
   dim3 grid((d.nc[0] + 31) / 32, (d.nc[1] + 7) / 8, d.c_cnt);
   if (ndim == 3)
@@ -290,10 +335,7 @@ extern "C" int ndsmk_prolong_add(const ndsmk_xfer *x, const double *u_c, double 
   if (int rc = to_dev(x, &d, &ndim)) return rc;
   dim3 block(64, 4, 1);
   dim3 grid((d.nf[0] + 63) / 64, (d.nf[1] + 3) / 4, d.f_cnt);
-  // the tiled kernel assumes a fine tile spans at most PC_* coarse points: true for every
-  // ratio (n_f-1)/(n_c-1) <= 2.2, i.e. all but the tiniest levels - which do not need it
-  if (ndim == 3 && (int64_t)d.nf[0] * d.nf[1] * d.f_cnt >= (int64_t)1 << 21 && d.nf[0] >= 64 && d.nc[0] >= 16 &&
-      d.nc[1] >= 16 && d.nc[2] >= 16) {
+  if (prolong_tiled(d, ndim)) {
     dim3 g2((d.nf[0] + PT_X - 1) / PT_X, (d.nf[1] + PT_Y - 1) / PT_Y, (d.f_cnt + PT_Z - 1) / PT_Z);
     hipLaunchKernelGGL(prolong_tile_k<double>, g2, block, 0, ndsm::stream(), u_c, u_f, d);
     NDSM_LAUNCH_CHECK();

@@ -2674,6 +2674,29 @@ contains
     rc = ndsmk_debug_tail(on)
   end function
 
+  ! development hook (tests): the level sizes from which the streamed restriction / the tiled prolongation run, the
+  ! streamed restriction's form and its chunk length (transfer.hip, restrict_stream.hip); negative = built in
+  function ndsm_hip_debug_transfer_cfg(restrict_min_points, prolong_min_points, rs_variant, rs_chunk) &
+      bind(c, name="ndsm_hip_debug_transfer_cfg") result(rc)
+    integer(c_long_long), value :: restrict_min_points, prolong_min_points
+    integer(c_int), value :: rs_variant, rs_chunk
+    integer(c_int) :: rc
+    rc = ndsmk_debug_transfer_cfg(restrict_min_points, prolong_min_points, rs_variant, rs_chunk)
+  end function
+
+  ! development hook (tests): the kernels the transfers level -> level + 1 of an ndsm_hip_mg_create handle take
+  function ndsm_hip_debug_transfer_form(handle, level, out) bind(c, name="ndsm_hip_debug_transfer_form") result(rc)
+    type(c_ptr), value :: handle
+    integer(c_int), value :: level
+    integer(c_int), intent(out) :: out(4)
+    integer(c_int) :: rc
+    type(mg_solver), pointer :: s
+    rc = NDSMK_EARG
+    if (.not. c_associated(handle)) return
+    call c_f_pointer(handle, s)
+    rc = mg_transfer_form(s, int(level), out)
+  end function
+
   function ndsm_hip_debug_zero_guess(on) bind(c, name="ndsm_hip_debug_zero_guess") result(rc)
     integer(c_int), value :: on
     integer(c_int) :: rc

@@ -369,6 +369,26 @@ module ndsmh_iface
       integer(c_int), intent(out) :: ci, cj, fx, fy, maxt
     end subroutine
 
+    function ndsmk_restrict_stream_min_points() bind(c, name="ndsmk_restrict_stream_min_points") result(n)
+      import :: c_long_long
+      integer(c_long_long) :: n
+    end function
+
+    function ndsmk_debug_transfer_cfg(restrict_min_points, prolong_min_points, rs_variant, rs_chunk) &
+        bind(c, name="ndsmk_debug_transfer_cfg") result(rc)
+      import :: c_long_long, c_int
+      integer(c_long_long), value :: restrict_min_points, prolong_min_points
+      integer(c_int), value :: rs_variant, rs_chunk
+      integer(c_int) :: rc
+    end function
+
+    function ndsmk_debug_transfer_form(x, out) bind(c, name="ndsmk_debug_transfer_form") result(rc)
+      import :: ndsmk_xfer, c_int
+      type(ndsmk_xfer), intent(in) :: x
+      integer(c_int), intent(out) :: out(4)
+      integer(c_int) :: rc
+    end function
+
     function ndsmk_prolong_add(x, u_c, u_f) bind(c, name="ndsmk_prolong_add") result(rc)
       import :: ndsmk_xfer, c_ptr, c_int
       type(ndsmk_xfer), intent(in) :: x

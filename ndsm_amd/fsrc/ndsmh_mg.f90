@@ -32,7 +32,7 @@ module ndsmh_mg
   public :: mg_set_bcs, mg_export_u, mg_reset_info, mg_vcycle_from, mg_slab_restrict, mg_slab_prolong
   public :: mg_slab_restrict_f32, mg_slab_prolong_f32, mg_mixed_slab_ok, rhs_of
   public :: MG_BUF_U, MG_BUF_RHS, MG_BUF_R, MG_BUF_UALT
-  public :: MG_OP_RELAX_LAST, MG_OP_ZERO_U, MG_OP_DESCEND, mg_ensure_u, mg_u_declared_zero
+  public :: MG_OP_RELAX_LAST, MG_OP_ZERO_U, MG_OP_DESCEND, mg_ensure_u, mg_u_declared_zero, mg_transfer_form
   public :: MG_OP_RELAX, MG_OP_RESIDUAL, MG_OP_RESTRICT, MG_OP_PROLONG, MG_OP_EXACT, MG_OP_RELAX_COLOR, &
             MG_OP_RELAX_FUSED, MG_OP_RESREST, MG_OP_RELAX_RES, MG_OP_RELAX_RES_FUSED
 
@@ -297,7 +297,7 @@ contains
       if (t(2)%rlo(a1) + t(2)%rcnt(a1) - 1 > f0 + fy - 1) return
     end do
     ok = 2
-    if (s%lev(l)%npts >= 6_ik * 1024_ik * 1024_ik) ok = 3
+    if (s%lev(l)%npts >= int(ndsmk_restrict_stream_min_points(), ik)) ok = 3   ! 6 Mi points (ndsmk_debug_transfer_cfg: tests)
     ! What the kernel's per-chunk SCHEDULE of the z windows has to hold, MEASURED here and checked by the launcher
     ! against the kernel's own limits (restrict_stream.hip: launch_rs_t): bits 8-15 the largest number of coarse
     ! windows a fine plane lies in, bits 16-31 the most fine planes 64 consecutive coarse planes (the longest
@@ -641,6 +641,19 @@ contains
     logical :: yes
     yes = .false.
     if (level >= 1 .and. level <= s%ngrids .and. allocated(s%dl)) yes = s%dl(level)%uzero
+  end function
+
+  ! tests: which kernels the transfers level -> level+1 of this hierarchy take (ndsmk_debug_transfer_form)
+  function mg_transfer_form(s, level, out) result(rc)
+    type(mg_solver), intent(in) :: s
+    integer, intent(in) :: level
+    integer(c_int), intent(out) :: out(4)
+    integer(c_int) :: rc
+    out = 0
+    rc = NDSMK_EARG
+    if (level < 1 .or. level >= s%ngrids .or. .not. allocated(s%xf)) return
+    if (level >= 2 .and. .not. s%has_coarse) return
+    rc = ndsmk_debug_transfer_form(s%xf(level)%x, out)
   end function
 
   ! The restriction of the descent: r(l) -> rhs(l+1), u(l+1) = 0 (fine_to_coarse, :551-558).  relax_next: the

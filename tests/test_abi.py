@@ -155,6 +155,10 @@ def test_additive_entry_points_fail_cleanly_without_a_gpu(lib):
     assert lib.ndsm_hip_shutdown() == 0 and lib.ndsm_hip_shutdown() == 0
     assert lib.ndsm_hip_debug_fused_cfg(0, 0, 0, 0, -1) == 0
     assert lib.ndsm_hip_debug_tail(1) == 0
+    assert lib.ndsm_hip_debug_transfer_cfg(0, 0, 8, 4) == 0 and lib.ndsm_hip_debug_transfer_cfg(-1, -1, 7, -1) == 9002
+    assert lib.ndsm_hip_debug_transfer_cfg(-1, -1, -1, -1) == 0
+    form = (ctypes.c_int * 4)(9, 9, 9, 9)
+    assert lib.ndsm_hip_debug_transfer_form(None, 1, form) == 9002 and list(form) == [9, 9, 9, 9]
     p = ctypes.c_void_p()
     lib.ndsm_hip_device_alloc.argtypes = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
     assert lib.ndsm_hip_device_alloc(1024, ctypes.byref(p)) == 9001 and not p.value

@@ -116,17 +116,28 @@ def test_transfer3d_bitwise(hip, port, ns, meshf):
     S.close()
 
 
+# the restriction each shape of test_large_level_kernels_bitwise takes by itself: 0 the gather kernel (under 6 Mi points),
+# 10 / 8 the streamed one's DMA / register-staged form (odd nx); all five take the tiled prolongation
+LARGE_LEVEL_FORMS = {(128, 128, 128): 0, (200, 100, 120): 0, (256, 192, 160): 10, (129, 128, 130): 0, (257, 161, 158): 8}
+
+
 @pytest.mark.parametrize("ns,meshf", _meshes(([128, 128, 128], [200, 100, 120], [256, 192, 160], [129, 128, 130], [257, 161, 158]),
                                              ([200, 100, 120], [257, 161, 158])))
 def test_large_level_kernels_bitwise(hip, port, ns, meshf):
-    """the kernels that only serve large levels - temporally blocked fused smoother (odd nx: its
-    ghost-column variant), LDS-streamed restriction, LDS-tiled prolongation, fused residual+restriction -
-    against the oracle, level 1 -> 2"""
+    """the kernels that only serve large levels against the oracle, level 1 -> 2, at their own sizes: the temporally
+    blocked fused smoother (odd nx: its ghost-column variant) and the LDS-tiled prolongation (from 2 Mi points) at all
+    five shapes; the LDS-streamed restriction (from 6 Mi points) at 256x192x160 - its DMA form - and 257x161x158 - odd
+    nx: its register-staged, scheduled form.  128^3, 200x100x120 and 129x128x130 have 2.1-2.4 Mi points: their
+    restriction is the gather kernel.  Which form runs is asserted from ndsm_hip_debug_transfer_form, not assumed; the
+    streamed forms at their edges are test_gpu_transfer_matrix.py's."""
     mesh = meshf(ns)
     shp = tuple(ns[::-1])
     u, rhs = rand_field(shp, 2112), rand_field(shp, 2113)
     bcs = "DNDDND"
     S = hip.MGSolver(ns, mesh, bcs)
+    form, kc, nkc, tiled = S.transfer_form(1)
+    assert (form, tiled) == (LARGE_LEVEL_FORMS[tuple(ns)], 1), (ns, form, tiled)
+    assert (kc >= 1 and nkc == -(-(ns[2] // 2) // kc)) if form else (kc, nkc) == (0, 0)
     shapes, _ = port.hierarchy(ns, mesh)
     c = rand_field(tuple(int(v) for v in shapes[1][::-1]), 4001)
     S.upload(1, hip.BUF_U, u)

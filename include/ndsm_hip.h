@@ -1293,6 +1293,59 @@ int ndsm_hip_vecpot_open(void *h, int ioptc[16], double ropt[16], const int nsrc
 int ndsm_hip_vecpot_open_device(void *h, int ioptc[16], double ropt[16], const int nsrc[2], const double *xs,
                                 const double *ys, double zs, const double *dbz, double *dA, double *dB);
 
+/* ---- Constant-alpha (linear) force-free field of a magnetogram (DESIGN.md "Linear force-free field") ---------------
+ * curl B = alpha B with one alpha for the whole half space above the magnetogram: the middle rung between the
+ * potential field above and the nonlinear entries, and the only current-carrying field a line-of-sight magnetogram
+ * gives.  B = integral of G bz dA' with the kernel of Chiu & Hilton (1977) for their C = 0 family - with R the
+ * horizontal and r the full distance, Gamma = [z cos(alpha r) / r - cos(alpha z)] / (2 pi R),
+ * Gx = (x / R) dGamma/dz + alpha Gamma y / R, Gy = (y / R) dGamma/dz - alpha Gamma x / R,
+ * Gz = z [cos(alpha r) / r^3 + alpha sin(alpha r) / r^2] / (2 pi) - summed over the pixels as the potential field is:
+ * the same all-pairs sum with a richer pair term, written so that nothing divides by R where R = 0.  No handle.
+ *
+ * Source, pixels, c, slices and fold: exactly those of ndsm_hip_green_points - NS = min(64, ceil(npix / 4096)) slices,
+ *   each slice sum starting at 0.0 and adding left to right, the slice sums folded in ascending order.
+ * alpha: a finite double of either sign, in 1 / (length unit of the mesh).
+ * One target (X, Y, Z), w = Z - zs: ww = w w; sz = sin(alpha w); cz = cos(alpha w).
+ * For pixel p: q = bz[p] c; dx = X - xs[i]; dy = Y - ys[j]; R2 = dx dx + dy dy; r2 = R2 + ww.
+ *   If r2 > 0: r = sqrt(r2); t = q / (r2 r); ar = alpha r; cr = cos(ar); sr = sin(ar);
+ *     Sx = Sx + (dx t) cr;  Sy = Sy + (dy t) cr;  Sz = Sz + (w t) (cr + ar sr);
+ *     then, if R2 > 0: u = alpha (q / R2); e = sz - (ww / r2) sr; f = (w / r) cr - cz;
+ *       Sx = Sx + u (dx e + dy f);  Sy = Sy + u (dy e - dx f).
+ *   Otherwise the pixel contributes no term (the punctured rule of the potential field).
+ *   Plain C++ without contraction, IEEE division and sqrt; sin and cos are the device library's double-precision
+ *   functions (the pair's two come from one sincos call).  Up to those two functions the order above is the bits.
+ * Targets on or below the plane: the rules of ndsm_hip_green_points - w < 0 gives NaN, at w == 0 Bz is the bilinear
+ *   interpolation of bz.
+ * alpha == 0 with a finite bz gives the bits of the Green's-function entries: cos 0 = 1 and sin 0 = 0 make every added
+ *   quantity the old term or a zero of either sign.  For finite bz only: with alpha = 0 a non-finite pixel makes u NaN
+ *   (0 times an infinity), where the potential entries give an infinity.
+ * A hazard, wider than the punctured rule's.  e and f cancel to O(R^2) as R -> 0 at w > 0, where u is of the order
+ *   1 / R^2: a target that misses the vertical through a source node by a rounding error gets a finite result that has
+ *   lost digits, about eps z^2 / R^2 relative.  The rule is the punctured rule's, for every height: build the box's x
+ *   and y as slices of xs and ys, so that box nodes are source nodes bit for bit, or keep them well away.
+ * A limit of the solution.  It is not unique: the C = 0 member is the customary one.  The horizontal field falls only
+ *   like 1 / R, so the result depends on the magnetogram's width more than the potential field does; and for
+ *   |alpha| L of the order of 2 pi (L the magnetogram's width) the field oscillates with height and is of little use.
+ *
+ * ndsm_hip_lfff_points: B (3,npts) at pts (3,npts).  ndsm_hip_lfff_box: B (nx,ny,nz,3) on the box mesh x, y, z, which
+ *   as for ndsm_hip_green_box.  The same node gets the same bits from the faces, the volume and the points entry.
+ *   Returns, chunks, scratch and the memory screen: as the Green's-function entries, in their order - 9001, 9002,
+ *   9004; a non-finite alpha is 9004.  npts == 0 returns 0 and touches nothing.  A failed call leaves the outputs
+ *   untouched. */
+/* HOST arrays */
+int ndsm_hip_lfff_points(const int nsrc[2], const double *xs, const double *ys, double zs, const double *bz,
+                         double alpha, int npts, const double *pts, double *B);
+/* the same with bz, pts and B DEVICE arrays of the library's GPU */
+int ndsm_hip_lfff_points_device(const int nsrc[2], const double *xs, const double *ys, double zs, const double *dbz,
+                                double alpha, int npts, const double *dpts, double *dB);
+/* HOST arrays */
+int ndsm_hip_lfff_box(const int nsrc[2], const double *xs, const double *ys, double zs, const double *bz, double alpha,
+                      const int nshape[3], const double *x, const double *y, const double *z, int which, double *B);
+/* the same with bz and B DEVICE arrays of the library's GPU */
+int ndsm_hip_lfff_box_device(const int nsrc[2], const double *xs, const double *ys, double zs, const double *dbz,
+                             double alpha, const int nshape[3], const double *x, const double *y, const double *z,
+                             int which, double *dB);
+
 #ifdef __cplusplus
 }
 #endif

@@ -129,6 +129,11 @@ def load_library(path=None):
     L.ndsm_hip_green_points_device.argtypes = _gs + [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     L.ndsm_hip_green_box.argtypes = _gs + [_ip, _dp, _dp, _dp, ctypes.c_int, ctypes.c_void_p]
     L.ndsm_hip_green_box_device.argtypes = _gs + [_ip, _dp, _dp, _dp, ctypes.c_int, ctypes.c_void_p]
+    _ls = _gs + [ctypes.c_double]                                      # the same and alpha
+    L.ndsm_hip_lfff_points.argtypes = _ls + [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    L.ndsm_hip_lfff_points_device.argtypes = _ls + [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    L.ndsm_hip_lfff_box.argtypes = _ls + [_ip, _dp, _dp, _dp, ctypes.c_int, ctypes.c_void_p]
+    L.ndsm_hip_lfff_box_device.argtypes = _ls + [_ip, _dp, _dp, _dp, ctypes.c_int, ctypes.c_void_p]
     L.ndsm_hip_vecpot_open.argtypes = [ctypes.c_void_p, _ip, _dp] + _gs + [ctypes.c_void_p] * 2
     L.ndsm_hip_vecpot_open_device.argtypes = [ctypes.c_void_p, _ip, _dp] + _gs + [ctypes.c_void_p] * 2
     _obc = ([ctypes.c_void_p, ctypes.c_int, _ip, _dp] + [ctypes.c_void_p] * 5 + [ctypes.c_int, ctypes.c_int,
@@ -2116,6 +2121,86 @@ def magnetogram_field(x, y, z, bz, xs=None, ys=None, zs=None, which="faces", dev
         _check(_staged(L, [S, B], lambda dS, dB: L.ndsm_hip_green_box_device(*head, dS, *tail, dB)),
                "ndsm_hip_green_box_device", L)
     return B.reshape(3, len(qz), len(qy), len(qx))
+
+
+def _lfff_alpha(alpha):
+    """alpha as a finite float; ValueError for what the library would answer with 9004"""
+    try:
+        a = np.asarray(alpha, dtype=np.float64)
+    except (TypeError, ValueError):
+        a = np.zeros(2)
+    if a.ndim != 0 or not np.isfinite(a):
+        raise ValueError(f"alpha must be one finite number, not {alpha!r}")
+    return float(a)
+
+
+def lfff_field_points(xs, ys, zs, bz, alpha, pts, device=False, lib=None):
+    """The constant-alpha force-free field (curl B = alpha B, Chiu & Hilton's half-space solution) above the
+    magnetogram bz (nsy,nsx) - given on the uniform mesh xs, ys at height zs - at the points pts (npts,3; x, y, z), on
+    the device (semantics: include/ndsm_hip.h, ndsm_hip_lfff_points).  alpha: one finite number of either sign, in
+    1 / (length unit of the mesh), e.g. best_alpha()'s.  Returns B (npts,3); the plane rules are green_field_points',
+    and alpha = 0 gives its bits.  device=True: the arrays are staged in device memory and the device-resident entry
+    point runs."""
+    P = np.asarray(pts, dtype=np.float64)
+    if P.ndim != 2 or P.shape[1] != 3:
+        raise ValueError(f"pts of shape {P.shape}, (npts, 3) is needed")
+    alpha = _lfff_alpha(alpha)
+    ns2, qx, qy, zs, S = _green_source(None, None, None, bz, xs, ys, zs)
+    L = lib or load_library()
+    P = np.ascontiguousarray(P).reshape(-1).copy()
+    B = np.zeros(P.size)
+    head = (ns2.ctypes.data_as(_ip), _d(qx), _d(qy), zs)
+    if not device:
+        _check(L.ndsm_hip_lfff_points(*head, S.ctypes.data, alpha, len(P) // 3, P.ctypes.data, B.ctypes.data),
+               "ndsm_hip_lfff_points", L)
+    else:
+        _check(_staged(L, [S, P, B],
+                       lambda dS, dP, dB: L.ndsm_hip_lfff_points_device(*head, dS, alpha, len(P) // 3, dP, dB)),
+               "ndsm_hip_lfff_points_device", L)
+    return B.reshape(-1, 3)
+
+
+def linear_force_free_field(x, y, z, bz, alpha, xs=None, ys=None, zs=None, which="volume", device=False, lib=None):
+    """The constant-alpha force-free field above the magnetogram bz (nsy,nsx) on the box mesh x, y, z, as the
+    b (3,nz,ny,nx) that helicity(), trace(), squashing(), nulls() and optimize(start="given") take (semantics:
+    include/ndsm_hip.h, ndsm_hip_lfff_box).  alpha, xs, ys, zs, device: as lfff_field_points and magnetogram_field;
+    which "volume": every node; "faces": the nodes of the six faces, zeros inside.  Take x and y as slices of xs and
+    ys: a box node must lie on the vertical through a source node bit for bit, or well away from it, at every
+    height - a miss by a rounding error costs digits of the order eps z^2 / R^2.  The field depends on the
+    magnetogram's width more than the potential field does (its horizontal part falls like 1 / R)."""
+    if which not in GREEN_WHICH:
+        raise ValueError(f"which must be 'faces' or 'volume', not {which!r}")
+    alpha = _lfff_alpha(alpha)
+    qx, qy, qz = (_f64(v).reshape(-1) for v in (x, y, z))
+    if min(len(qx), len(qy), len(qz)) < 2:
+        raise ValueError(f"the box needs at least 2 nodes per axis, not {(len(qz), len(qy), len(qx))}")
+    ns2, sx, sy, zs, S = _green_source(qx, qy, qz, bz, xs, ys, zs)
+    L = lib or load_library()
+    n3 = np.array([len(qx), len(qy), len(qz)], dtype=np.intc)
+    B = np.zeros(3 * len(qx) * len(qy) * len(qz))
+    head = (ns2.ctypes.data_as(_ip), _d(sx), _d(sy), zs)
+    tail = (n3.ctypes.data_as(_ip), _d(qx), _d(qy), _d(qz), GREEN_WHICH[which])
+    if not device:
+        _check(L.ndsm_hip_lfff_box(*head, S.ctypes.data, alpha, *tail, B.ctypes.data), "ndsm_hip_lfff_box", L)
+    else:
+        _check(_staged(L, [S, B], lambda dS, dB: L.ndsm_hip_lfff_box_device(*head, dS, alpha, *tail, dB)),
+               "ndsm_hip_lfff_box_device", L)
+    return B.reshape(3, len(qz), len(qy), len(qx))
+
+
+def best_alpha(x, y, b, bz_min=0.0):
+    """The least-squares alpha of a vector magnetogram: sum Jz Bz / sum Bz^2 over the pixels of the lower face k = 0
+    of b (3,nz,ny,nx) with |Bz| >= bz_min, Jz = d_x B_y - d_y B_x formed with the differences of boundary_alpha().
+    Plain numpy: the number lfff_field_points() and linear_force_free_field() take.  ValueError when no pixel
+    qualifies or the sum of Bz^2 is 0."""
+    b = np.asarray(b, dtype=np.float64)
+    bx, by, bz = b[0, 0], b[1, 0], b[2, 0]
+    jz = np.gradient(by, _f64(x), axis=1, edge_order=2) - np.gradient(bx, _f64(y), axis=0, edge_order=2)
+    use = np.abs(bz) >= bz_min
+    den = float(np.sum(bz[use] * bz[use]))
+    if not den > 0.0:
+        raise ValueError("no pixel with |Bz| >= bz_min and Bz != 0: alpha is undefined")
+    return float(np.sum(jz[use] * bz[use])) / den
 
 
 def potential_open(x, y, z, bz, xs=None, ys=None, zs=None, a_init=None, niterex_max=10000, ncycles_max=1024,

@@ -7,6 +7,9 @@
 //             through LDS in tiles of 256 pixels: thread l stages pixel p = tile + l as xs[p mod nsx], ys[p div nsx]
 //             and q = bz[p] c, and every lane then reads the same address (a broadcast, no bank conflict) pixel after
 //             pixel, so the terms are added left to right.  The three slice sums go to scratch (NS, 3, chunk).
+//   lfff_k  : the same layout for the constant-alpha field (semantics: include/ndsm_hip.h, ndsm_hip_lfff_points): the
+//             pair term of Chiu & Hilton's half-space solution.  sin(alpha w) and cos(alpha w) are per target and stay
+//             in registers with X, Y, w, ww and the sums; a pair costs one sqrt, four divisions and one sincos.
 //   fold_k  : one thread per target adds the slice sums in ascending order, starting from slice 0's, applies the rules
 //             of the plane (w < 0: NaN; w == 0: Bz is the bilinear interpolation of bz) and writes the target's three
 //             components where its generator says.
@@ -150,6 +153,67 @@ __global__ __launch_bounds__(kBlock) void green_k(Source s, Targets g, i64 t0, i
   }
 }
 
+// the same sum with the pair term of the constant-alpha field; green_k above is left as it is, and so are its bits
+__global__ __launch_bounds__(kBlock) void lfff_k(Source s, double alpha, Targets g, i64 t0, i64 cnt,
+                                                 double *__restrict__ part) {
+  __shared__ double lx[kBlock], ly[kBlock], lq[kBlock];
+  const int l = threadIdx.x;
+  const i64 lt = (i64)blockIdx.x * kBlock + l;
+  const bool live = lt < cnt;
+  double X = 0.0, Y = 0.0, Z = 0.0;
+  if (live) {
+    size_t at, stride;
+    target_of(g, t0 + lt, X, Y, Z, at, stride);
+  }
+  const double w = Z - s.zs, ww = w * w;
+  const double aw = alpha * w;
+  const double sz = sin(aw), cz = cos(aw);
+  double ax = 0.0, ay = 0.0, az = 0.0;
+  const i64 p0 = (i64)blockIdx.y * s.len;
+  const i64 p1 = p0 + s.len < s.npix ? p0 + s.len : s.npix;
+  for (i64 tile = p0; tile < p1; tile += kBlock) {
+    const i64 p = tile + l;
+    if (p < p1) {
+      const i64 j = p / s.nsx;
+      lx[l] = s.xs[p - j * s.nsx];
+      ly[l] = s.ys[j];
+      lq[l] = s.bz[p] * s.c;
+    }
+    __syncthreads();
+    const int m = p1 - tile < kBlock ? (int)(p1 - tile) : kBlock;
+    for (int n = 0; n < m; ++n) {
+      const double dx = X - lx[n], dy = Y - ly[n];
+      const double R2 = dx * dx + dy * dy;
+      const double r2 = R2 + ww;
+      if (r2 > 0.0) {
+        const double q = lq[n];
+        const double r = sqrt(r2);
+        const double t = q / (r2 * r);
+        const double ar = alpha * r;
+        double sr, cr;
+        sincos(ar, &sr, &cr);
+        ax = ax + (dx * t) * cr;
+        ay = ay + (dy * t) * cr;
+        az = az + (w * t) * (cr + ar * sr);
+        if (R2 > 0.0) {
+          const double u = alpha * (q / R2);
+          const double e = sz - (ww / r2) * sr;
+          const double f = (w / r) * cr - cz;
+          ax = ax + u * (dx * e + dy * f);
+          ay = ay + u * (dy * e - dx * f);
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (live) {
+    double *o = part + (size_t)blockIdx.y * 3 * (size_t)cnt + (size_t)lt;
+    o[0] = ax;
+    o[(size_t)cnt] = ay;
+    o[2 * (size_t)cnt] = az;
+  }
+}
+
 // the largest node i0 <= n - 2 with v[i0] <= q, for v[0] <= q <= v[n - 1]: an estimate from the spacing, corrected
 __device__ __forceinline__ int bracket(const double *v, int n, double q) {
   const double e = floor((q - v[0]) / (v[1] - v[0]));
@@ -223,8 +287,10 @@ double own_bytes(const int32_t *nsrc2, const int32_t *n3, double ntargets) {
   return b + 24.0 * chunk * (double)slices_of((i64)nsrc2[0] * nsrc2[1]);
 }
 
-// the shared driver: mesh vectors up, then chunk after chunk the all-pairs launch and the fold
-int run(const int32_t *nsrc2, const double *h_xs, const double *h_ys, double zs, const double *bz, Targets g,
+// the shared driver: mesh vectors up, then chunk after chunk the all-pairs launch and the fold.  alpha NULL: the
+// potential field (green_k); else the constant-alpha field (lfff_k)
+int run(const int32_t *nsrc2, const double *h_xs, const double *h_ys, double zs, const double *bz, const double *alpha,
+        Targets g,
         const int32_t *n3, const double *h_x, const double *h_y, const double *h_z, double *out) {
   Source s;
   s.nsx = nsrc2[0];
@@ -258,7 +324,11 @@ int run(const int32_t *nsrc2, const double *h_xs, const double *h_ys, double zs,
   for (i64 t0 = 0; t0 < g.count && rc == 0; t0 += chunk) {
     const i64 cnt = g.count - t0 < chunk ? g.count - t0 : chunk;
     const unsigned nb = (unsigned)((cnt + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(green_k, dim3(nb, (unsigned)s.nslices), dim3(kBlock), 0, ndsm::stream(), s, g, t0, cnt, part);
+    if (alpha)
+      hipLaunchKernelGGL(lfff_k, dim3(nb, (unsigned)s.nslices), dim3(kBlock), 0, ndsm::stream(), s, *alpha, g, t0, cnt,
+                         part);
+    else
+      hipLaunchKernelGGL(green_k, dim3(nb, (unsigned)s.nslices), dim3(kBlock), 0, ndsm::stream(), s, g, t0, cnt, part);
     hipLaunchKernelGGL(fold_k, dim3(nb), dim3(kBlock), 0, ndsm::stream(), s, g, t0, cnt, part, out);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) rc = ndsm::fail((int)e, hipGetErrorString(e), __FILE__, __LINE__);
@@ -300,7 +370,7 @@ extern "C" int ndsmk_green_points(const int32_t *nsrc2, const double *h_xs, cons
   g.gen = GEN_POINTS;
   g.count = npts;
   g.pts = pts;
-  return run(nsrc2, h_xs, h_ys, zs, bz, g, nullptr, nullptr, nullptr, nullptr, B);
+  return run(nsrc2, h_xs, h_ys, zs, bz, nullptr, g, nullptr, nullptr, nullptr, nullptr, B);
 }
 
 // B (nx,ny,nz,3): which = 0 the nodes with an index at either end of an axis (every other node keeps what it holds),
@@ -322,5 +392,44 @@ extern "C" int ndsmk_green_box(const int32_t *nsrc2, const double *h_xs, const d
   g.nx = n3[0];
   g.ny = n3[1];
   g.nz = n3[2];
-  return run(nsrc2, h_xs, h_ys, zs, bz, g, n3, h_x, h_y, h_z, B);
+  return run(nsrc2, h_xs, h_ys, zs, bz, nullptr, g, n3, h_x, h_y, h_z, B);
+}
+
+// The constant-alpha field (semantics: include/ndsm_hip.h, ndsm_hip_lfff_points): the arguments of ndsmk_green_points
+// and alpha, a finite double.  alpha = 0 gives the bits of ndsmk_green_points for a finite bz.
+extern "C" int ndsmk_lfff_points(const int32_t *nsrc2, const double *h_xs, const double *h_ys, double zs,
+                                 const double *bz, double alpha, int npts, const double *pts, double *B) {
+  NDSM_REQUIRE_READY();
+  NDSM_CHECK_ARG(nsrc2 && h_xs && h_ys && bz);
+  if (!source_ok(nsrc2, h_xs, h_ys) || npts < 0 || !std::isfinite(alpha))
+    return ndsmk_note_error(NDSMK_EVALUE, "lfff_points: at least 2 source nodes per axis, spacings > 0, npts >= 0 and "
+                                          "a finite alpha");
+  if (npts == 0) return 0;
+  NDSM_CHECK_ARG(pts && B);
+  Targets g = {};
+  g.gen = GEN_POINTS;
+  g.count = npts;
+  g.pts = pts;
+  return run(nsrc2, h_xs, h_ys, zs, bz, &alpha, g, nullptr, nullptr, nullptr, nullptr, B);
+}
+
+// the arguments of ndsmk_green_box and alpha
+extern "C" int ndsmk_lfff_box(const int32_t *nsrc2, const double *h_xs, const double *h_ys, double zs,
+                              const double *bz, double alpha, const int32_t *n3, const double *h_x, const double *h_y,
+                              const double *h_z, int which, double *B) {
+  NDSM_REQUIRE_READY();
+  NDSM_CHECK_ARG(nsrc2 && h_xs && h_ys && bz && n3 && h_x && h_y && h_z && B);
+  if (!source_ok(nsrc2, h_xs, h_ys) || (which != 0 && which != 1) || n3[0] < 2 || n3[1] < 2 || n3[2] < 2 ||
+      !(h_z[0] >= zs) || !std::isfinite(alpha))
+    return ndsmk_note_error(NDSMK_EVALUE, "lfff_box: at least 2 source nodes per axis, spacings > 0, which 0 or 1, "
+                                          "at least 2 box nodes per axis, z[0] >= zs and a finite alpha");
+  if (box_targets(n3, which) > kMaxTargets)
+    return ndsmk_note_error(NDSMK_ENODEV, "lfff_box: more targets than any device holds");
+  Targets g = {};
+  g.gen = which == 0 ? GEN_FACES : GEN_VOLUME;
+  g.count = (i64)box_targets(n3, which);      // (exact: whole numbers below 2^53)
+  g.nx = n3[0];
+  g.ny = n3[1];
+  g.nz = n3[2];
+  return run(nsrc2, h_xs, h_ys, zs, bz, &alpha, g, n3, h_x, h_y, h_z, B);
 }

@@ -274,6 +274,14 @@ int ndsmk_green_points(const int32_t *nsrc2, const double *h_xs, const double *h
                        int npts, const double *pts, double *B);
 int ndsmk_green_box(const int32_t *nsrc2, const double *h_xs, const double *h_ys, double zs, const double *bz,
                     const int32_t *n3, const double *h_x, const double *h_y, const double *h_z, int which, double *B);
+/* The constant-alpha (linear force-free) field of the same source (green.hip; semantics: include/ndsm_hip.h,
+ * ndsm_hip_lfff_points): the arguments of the two launchers above and alpha; a non-finite alpha is 9004 as well.  The
+ * chunks, the scratch and ndsmk_green_fits are shared. */
+int ndsmk_lfff_points(const int32_t *nsrc2, const double *h_xs, const double *h_ys, double zs, const double *bz,
+                      double alpha, int npts, const double *pts, double *B);
+int ndsmk_lfff_box(const int32_t *nsrc2, const double *h_xs, const double *h_ys, double zs, const double *bz,
+                   double alpha, const int32_t *n3, const double *h_x, const double *h_y, const double *h_z, int which,
+                   double *B);
 
 /* Magnetogram preprocessing (preprocess.hip; semantics: include/ndsm_hip.h, ndsm_hip_vecpot_preprocess).  B0, B1
  * (nx,ny,3): the two field buffers, B0 holds the start; La (nx,ny,3,2): the two Lambda buffers; obs (nx,ny,3): the

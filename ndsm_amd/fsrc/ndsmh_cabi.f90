@@ -1421,7 +1421,7 @@ contains
     integer(c_int), value :: npts
     integer(c_int) :: ierr
     ierr = green_entry(.false., nsrc, xs, ys, zs, bz, npts, pts, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, &
-                       0_c_int, B, .false., "ndsm_hip_green_points")
+                       0_c_int, B, .false., "ndsm_hip_green_points", .false., 0.0_c_double)
   end function
 
   ! the same with bz, pts and B DEVICE arrays of the library's GPU
@@ -1432,7 +1432,7 @@ contains
     integer(c_int), value :: npts
     integer(c_int) :: ierr
     ierr = green_entry(.false., nsrc, xs, ys, zs, dbz, npts, dpts, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, &
-                       0_c_int, dB, .true., "ndsm_hip_green_points_device")
+                       0_c_int, dB, .true., "ndsm_hip_green_points_device", .false., 0.0_c_double)
   end function
 
   ! B (nx,ny,nz,3) on the box mesh x, y, z: which = 0 the nodes with an index at either end of an axis (every other
@@ -1444,7 +1444,7 @@ contains
     integer(c_int), value :: which
     integer(c_int) :: ierr
     ierr = green_entry(.true., nsrc, xs, ys, zs, bz, 0_c_int, c_null_ptr, nshape, x, y, z, which, B, .false., &
-                       "ndsm_hip_green_box")
+                       "ndsm_hip_green_box", .false., 0.0_c_double)
   end function
 
   ! the same with bz and B DEVICE arrays of the library's GPU
@@ -1455,7 +1455,7 @@ contains
     integer(c_int), value :: which
     integer(c_int) :: ierr
     ierr = green_entry(.true., nsrc, xs, ys, zs, dbz, 0_c_int, c_null_ptr, nshape, x, y, z, which, dB, .true., &
-                       "ndsm_hip_green_box_device")
+                       "ndsm_hip_green_box_device", .false., 0.0_c_double)
   end function
 
   ! the source of a Green's-function call: 0, or 9004 unless there are 2 nodes per axis and both spacings are > 0
@@ -1471,10 +1471,12 @@ contains
     if (qx(2) - qx(1) > 0.0_c_double .and. qy(2) - qy(1) > 0.0_c_double) ierr = 0
   end function
 
-  function green_entry(box, nsrc, xs, ys, zs, bz, npts, pts, nshape, x, y, z, which, B, on_device, who) result(ierr)
-    logical, intent(in) :: box, on_device
+  ! lfff: the constant-alpha field with that alpha (a non-finite alpha is 9004); otherwise alpha is not looked at
+  function green_entry(box, nsrc, xs, ys, zs, bz, npts, pts, nshape, x, y, z, which, B, on_device, who, lfff, alpha) &
+      result(ierr)
+    logical, intent(in) :: box, on_device, lfff
     type(c_ptr), intent(in) :: nsrc, xs, ys, bz, pts, nshape, x, y, z, B
-    real(c_double), intent(in) :: zs
+    real(c_double), intent(in) :: zs, alpha
     integer(c_int), intent(in) :: npts, which
     character(len=*), intent(in) :: who
     integer(c_int) :: ierr
@@ -1518,9 +1520,10 @@ contains
       if (any(n3 < 2) .or. (which /= 0 .and. which /= 1) .or. .not. (qz(1) >= zs)) ierr = NDSMK_EVALUE
     end if
     if (ierr == 0 .and. npts < 0) ierr = NDSMK_EVALUE
+    if (ierr == 0 .and. lfff .and. .not. (abs(alpha) <= huge(alpha))) ierr = NDSMK_EVALUE      ! (a NaN fails it too)
     if (ierr /= 0) then
       ierr = ndsmk_note_error(NDSMK_EVALUE, "green: at least 2 source nodes per axis, spacings > 0, npts >= 0, which "// &
-                              "0 or 1, at least 2 box nodes per axis and z[0] >= zs"//c_null_char)
+                              "0 or 1, at least 2 box nodes per axis, z[0] >= zs and (lfff) a finite alpha"//c_null_char)
       return
     end if
     if (.not. box) then
@@ -1529,11 +1532,7 @@ contains
       if (.not. (c_associated(pts) .and. c_associated(B))) return
     end if
     if (on_device) then
-      if (box) then
-        rc = ndsmk_green_box(ns2, xs, ys, zs, bz, n3, x, y, z, which, B)
-      else
-        rc = ndsmk_green_points(ns2, xs, ys, zs, bz, npts, pts, B)
-      end if
+      rc = launch(bz, pts, B)
     else
       ! bz, then (points) pts, then B; which = 0 leaves nodes of B untouched, so B goes up first
       buf = c_null_ptr
@@ -1544,17 +1543,76 @@ contains
         rc = ndsmk_h2d(buf, bz, bsrc)
         if (box) then
           if (rc == 0 .and. which == 0) rc = ndsmk_h2d(pout, B, bout)
-          if (rc == 0) rc = ndsmk_green_box(ns2, xs, ys, zs, buf, n3, x, y, z, which, pout)
         else
           if (rc == 0) rc = ndsmk_h2d(dpts, pts, bout)
-          if (rc == 0) rc = ndsmk_green_points(ns2, xs, ys, zs, buf, npts, dpts, pout)
         end if
+        if (rc == 0) rc = launch(buf, dpts, pout)
         if (rc == 0) rc = ndsmk_d2h(B, pout, bout)
         d = ndsmk_free(buf)
         if (rc == 0) rc = int(d, c_int)
       end if
     end if
     ierr = reported(who, rc)
+  contains
+    ! the launcher of this entry on the device arrays dbz, dp (points only) and dout
+    function launch(dbz, dp, dout) result(lrc)
+      type(c_ptr), intent(in) :: dbz, dp, dout
+      integer(c_int) :: lrc
+      if (box .and. lfff) then
+        lrc = ndsmk_lfff_box(ns2, xs, ys, zs, dbz, alpha, n3, x, y, z, which, dout)
+      else if (box) then
+        lrc = ndsmk_green_box(ns2, xs, ys, zs, dbz, n3, x, y, z, which, dout)
+      else if (lfff) then
+        lrc = ndsmk_lfff_points(ns2, xs, ys, zs, dbz, alpha, npts, dp, dout)
+      else
+        lrc = ndsmk_green_points(ns2, xs, ys, zs, dbz, npts, dp, dout)
+      end if
+    end function
+  end function
+
+  ! ---- Constant-alpha (linear force-free) field of a magnetogram (semantics in include/ndsm_hip.h) ----
+  ! the arguments of the Green's-function entries and alpha, through the same path.  HOST arrays
+  function ndsm_hip_lfff_points(nsrc, xs, ys, zs, bz, alpha, npts, pts, B) bind(c, name="ndsm_hip_lfff_points") &
+      result(ierr)
+    type(c_ptr), value :: nsrc, xs, ys, bz, pts, B
+    real(c_double), value :: zs, alpha
+    integer(c_int), value :: npts
+    integer(c_int) :: ierr
+    ierr = green_entry(.false., nsrc, xs, ys, zs, bz, npts, pts, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, &
+                       0_c_int, B, .false., "ndsm_hip_lfff_points", .true., alpha)
+  end function
+
+  ! the same with bz, pts and B DEVICE arrays of the library's GPU
+  function ndsm_hip_lfff_points_device(nsrc, xs, ys, zs, dbz, alpha, npts, dpts, dB) &
+      bind(c, name="ndsm_hip_lfff_points_device") result(ierr)
+    type(c_ptr), value :: nsrc, xs, ys, dbz, dpts, dB
+    real(c_double), value :: zs, alpha
+    integer(c_int), value :: npts
+    integer(c_int) :: ierr
+    ierr = green_entry(.false., nsrc, xs, ys, zs, dbz, npts, dpts, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, &
+                       0_c_int, dB, .true., "ndsm_hip_lfff_points_device", .true., alpha)
+  end function
+
+  ! HOST arrays
+  function ndsm_hip_lfff_box(nsrc, xs, ys, zs, bz, alpha, nshape, x, y, z, which, B) &
+      bind(c, name="ndsm_hip_lfff_box") result(ierr)
+    type(c_ptr), value :: nsrc, xs, ys, bz, nshape, x, y, z, B
+    real(c_double), value :: zs, alpha
+    integer(c_int), value :: which
+    integer(c_int) :: ierr
+    ierr = green_entry(.true., nsrc, xs, ys, zs, bz, 0_c_int, c_null_ptr, nshape, x, y, z, which, B, .false., &
+                       "ndsm_hip_lfff_box", .true., alpha)
+  end function
+
+  ! the same with bz and B DEVICE arrays of the library's GPU
+  function ndsm_hip_lfff_box_device(nsrc, xs, ys, zs, dbz, alpha, nshape, x, y, z, which, dB) &
+      bind(c, name="ndsm_hip_lfff_box_device") result(ierr)
+    type(c_ptr), value :: nsrc, xs, ys, dbz, nshape, x, y, z, dB
+    real(c_double), value :: zs, alpha
+    integer(c_int), value :: which
+    integer(c_int) :: ierr
+    ierr = green_entry(.true., nsrc, xs, ys, zs, dbz, 0_c_int, c_null_ptr, nshape, x, y, z, which, dB, .true., &
+                       "ndsm_hip_lfff_box_device", .true., alpha)
   end function
 
   ! The open-box potential field: ndsm_hip_green_box_device (which = 0) on the handle's mesh into the device B, then

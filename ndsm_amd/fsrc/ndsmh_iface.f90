@@ -711,6 +711,25 @@ module ndsmh_iface
       integer(c_int), value :: which
       integer(c_int) :: rc
     end function
+    ! the constant-alpha field of the same source: the two launchers above with alpha
+    function ndsmk_lfff_points(nsrc2, h_xs, h_ys, zs, bz, alpha, npts, pts, B) bind(c, name="ndsmk_lfff_points") &
+        result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_double
+      integer(c_int32_t), intent(in) :: nsrc2(2)
+      type(c_ptr), value :: h_xs, h_ys, bz, pts, B
+      real(c_double), value :: zs, alpha
+      integer(c_int), value :: npts
+      integer(c_int) :: rc
+    end function
+    function ndsmk_lfff_box(nsrc2, h_xs, h_ys, zs, bz, alpha, n3, h_x, h_y, h_z, which, B) &
+        bind(c, name="ndsmk_lfff_box") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_double
+      integer(c_int32_t), intent(in) :: nsrc2(2), n3(3)
+      type(c_ptr), value :: h_xs, h_ys, bz, h_x, h_y, h_z, B
+      real(c_double), value :: zs, alpha
+      integer(c_int), value :: which
+      integer(c_int) :: rc
+    end function
     ! ---- magnetogram preprocessing (preprocess.hip) ----
     function ndsmk_preprocess_work_bytes() bind(c, name="ndsmk_preprocess_work_bytes") result(nb)
       import :: c_size_t

@@ -1346,6 +1346,66 @@ int ndsm_hip_lfff_box_device(const int nsrc[2], const double *xs, const double *
                              double alpha, const int nshape[3], const double *x, const double *y, const double *z,
                              int which, double *dB);
 
+/* ---- Magnetic dips and bald patches of a field on the same handle (DESIGN.md "Dips and bald patches") ---------------
+ * Where a field line is locally lowest: B_z = 0 with (B.grad)B_z > 0 (Titov, Priest & Demoulin 1993).  On the lower
+ * boundary these points are the BALD PATCHES, the stretches of the polarity inversion line where field lines touch the
+ * boundary from above - the third kind of separatrix next to the fans of the nulls and the quasi-separatrix layers -;
+ * in the volume they are the DIPS that can hold the material of a filament (Aulanier & Demoulin 1998).  They are looked
+ * for on the EDGES of the mesh.  fp64 + - * / only, in the operand order written here, no contraction: a restatement
+ * in the same order gives the same bits.
+ *   B           (nx,ny,nz,3) on the handle's mesh; lo_d, h_d its first point and spacing per axis (h_d = the difference
+ *               of the first two mesh points); nodes are numbered node = i + nx (j + ny k)
+ *   plane_only  0, or 1: the magnetogram's own question, see below
+ *   max_dips    >= 0 (int64): the capacity of the record arrays; 0 counts only (no record array is looked at)
+ *   counts      int64[3], a HOST array in both entries: (crossings, dips, bald patches), exact whatever the capacity
+ *   out         records: edge (int64), pos, bpt, grad (3 each), curv doubles; flag int32
+ * Semantics:
+ *   gradient    nodal: G_d = the difference quotient of B_z along axis d at the node, the field entries' ddq with
+ *               exactly its operand order: inside, G = (0 + v[-1] (-0.5 / h)) + v[+1] (0.5 / h); on the lower end
+ *               plane ((0 + v[0] (-1.5 / h)) + v[+1] (2 / h)) + v[+2] (-0.5 / h); on the upper end plane
+ *               ((0 + v[0] (1.5 / h)) + v[-1] (-2 / h)) + v[-2] (0.5 / h): centred inside and 3-point one-sided on
+ *               the end planes.
+ *   edges       edge e = 3 node + d, d = 0, 1, 2 for x, y, z, runs from node p to its +d neighbour p'.  A node on the
+ *               upper end plane of axis d has no edge d.
+ *   crossing    with a = B_z(p) and b = B_z(p'): the edge is a CROSSING iff (a > 0) != (b > 0).  A zero or NaN counts
+ *               as not positive, so an exact zero at a node is reported by exactly one edge of each family.
+ *   at it       t = a / (a - b): one quotient, no reciprocal.  Every nodal quantity q of B_x, B_y, B_z, G_x, G_y, G_z is
+ *               taken as q_t = q(p) + t (q(p') - q(p)).  pos_d = lo_d + (i_d + t) h_d, the sum formed first; on the
+ *               other two axes pos = lo + i h.  curv = B_x,t G_x,t + B_y,t G_y,t: (B.grad)B_z where B_z = 0; the z term
+ *               is left out, not rounded in.
+ *   dip         a crossing is a DIP iff curv > 0, strict.  There is no separate rule for values that are not finite: a
+ *               NaN among the values that enter t or curv makes them NaN, the comparison false, and excludes the
+ *               edge; so does every Inf that meets another Inf or a zero factor there (Inf - Inf, 0 Inf), as all do in
+ *               a block of Inf over all three components.  G_z,t enters neither t nor curv: next to a block of NaN a
+ *               record's grad_z can be NaN.  A lone Inf can pass - curv = +Inf where it reaches one of the two ends'
+ *               values only, or a finite curv next to a B_z,t that is not finite on a z edge -: a field with Inf in it
+ *               is the caller's to mask.
+ *   record      of a dip: edge; pos; bpt = (B_x,t, B_y,t, B_z,t); grad = (G_x,t, G_y,t, G_z,t); curv; flag, bit 0: a
+ *               BALD PATCH, k = 0 and d != 2 (an edge of the lower boundary plane).  The curvature of the field line
+ *               at its lowest point is curv / (B_x,t^2 + B_y,t^2) (ndsm_amd's Dips.kappa).
+ *   order       records come out in ascending edge, whatever the launch geometry, with the same bits on every run and
+ *               from both entries: output positions come from counts and a scan - no atomic append, no sort, and no
+ *               result that depends on an internal buffer's size.  counts[1] > max_dips: max_dips only truncates the
+ *               records written - the first max_dips in edge order - and the call still returns 0.
+ *   plane_only  = 1: only the nodes of k = 0 and the families 0 and 1 are looked at, at O(nx ny) cost (the gradient
+ *               along z reads the planes k = 1, 2 at the crossings).  The records are, bit for bit, those records of
+ *               the full call that carry flag bit 0, counts[0] counts the crossings of that plane's x and y edges, and
+ *               counts[1] == counts[2].
+ * Returns 0, or >= 9001 errors: 9001 without a GPU whatever the arguments; 9002 a NULL handle, B or counts, or with
+ * max_dips > 0 a NULL record array; 9004 max_dips < 0, plane_only not 0 or 1, a mesh with fewer than 3 nodes on an
+ * axis.  On every failure counts is cleared; the host entry also clears the max_dips slots of every record array (on
+ * success the slots past min(counts[1], max_dips) are zero), the device entry leaves its device arrays (on success it
+ * writes the first min(counts[1], max_dips) slots only).
+ * Device memory: the host entry stages B in the handle's scratch (24 B/pt) and max_dips records (92 B each); the call
+ * keeps 3 bits per node and 24 B per 1024 nodes. */
+/* HOST arrays */
+int ndsm_hip_vecpot_dips(void *h, const double *B, int plane_only, int64_t max_dips, int64_t *counts, int64_t *edge,
+                         double *pos, double *bpt, double *grad, double *curv, int32_t *flag);
+/* the same on DEVICE arrays of the library's GPU (B and the six record arrays; counts stays on the host) */
+int ndsm_hip_vecpot_dips_device(void *h, const double *dB, int plane_only, int64_t max_dips, int64_t *counts,
+                                int64_t *dedge, double *dpos, double *dbpt, double *dgrad, double *dcurv,
+                                int32_t *dflag);
+
 #ifdef __cplusplus
 }
 #endif

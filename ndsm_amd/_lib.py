@@ -156,6 +156,9 @@ def load_library(path=None):
     _nu = [ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 8
     L.ndsm_hip_vecpot_nulls.argtypes = _nu
     L.ndsm_hip_vecpot_nulls_device.argtypes = _nu
+    _di = [ctypes.c_void_p] * 2 + [ctypes.c_int, ctypes.c_int64] + [ctypes.c_void_p] * 7
+    L.ndsm_hip_vecpot_dips.argtypes = _di
+    L.ndsm_hip_vecpot_dips_device.argtypes = _di
     _sk = ([ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_int, ctypes.c_void_p] +
            [ctypes.c_double] * 3 + [ctypes.c_int, ctypes.c_int, ctypes.c_int64] + [ctypes.c_void_p] * 13)
     L.ndsm_hip_vecpot_skeleton.argtypes = _sk
@@ -1146,6 +1149,48 @@ class VecPot:
         return _nulls_tuple([a[:n] for a in out], int(counts[0]), int(counts[1]), None if merge is None else
                             float(merge) * hmin)
 
+    def dips(self, b, plane_only=False, max_dips=None, device=False):
+        """Magnetic dips and bald patches of b (3,nz,ny,nx), on the device (semantics: include/ndsm_hip.h,
+        ndsm_hip_vecpot_dips): the mesh edges on which b_z changes sign with (b.grad)b_z > 0 at the crossing - the
+        points where a field line is locally lowest; on the plane k = 0 they are the bald patches, where field lines
+        touch the lower boundary from above.  plane_only=True: the plane k = 0 and its x and y edges alone, the bald
+        patches at O(nx ny) cost.  max_dips: the capacity of the first call; when more are found the call is repeated
+        once with that number (None: a counting call, then one call of the exact size; 0: count only - ncrossings,
+        ndips and nbald, no records).  Returns a Dips tuple:
+        position (n,3), edge (n; int64, 3 node + axis), axis (n; 0, 1, 2: the edge runs along x, y, z), node (n,3; i,
+        j, k of the edge's low node), b, grad (n,3; the field and the gradient of b_z at the position), curv (n;
+        (b.grad)b_z there, > 0), kappa (n; curv / (b_x^2 + b_y^2), the field line's curvature at its lowest point),
+        bald (n; bool), ncrossings (the edges on which b_z changes sign), ndips, nbald (exact counts whatever the
+        capacity), in ascending edge.  device=True: the arrays are staged in device memory and the device-resident
+        entry point runs."""
+        plane_only, max_dips = _dips_args(plane_only, max_dips)
+        B = self._field_arg(b, "dips")
+        def run(cap):
+            counts = np.zeros(3, dtype=np.int64)
+            m = max(cap, 1)
+            out = [np.zeros(m, dtype=np.int64), np.zeros((m, 3)), np.zeros((m, 3)), np.zeros((m, 3)), np.zeros(m),
+                   np.zeros(m, dtype=np.int32)]
+            self._entry("ndsm_hip_vecpot_dips", [B, plane_only, cap, counts.ctypes.data, *out], device)
+            return int(counts[1]), (counts, out)
+        if max_dips is None:
+            n, (counts, out) = _with_capacity(run, 0)
+        else:
+            n, (counts, out) = _with_capacity(run, max_dips, count_only=True)
+        return _dips_tuple([a[:n] for a in out], counts, int(self.nshape4[0]), int(self.nshape4[1]))
+
+    def bald_patch_lines(self, b, dips, lift=1e-3, **paths_options):
+        """The field lines that generate the bald-patch separatrix surface of b: the records of `dips` (a Dips tuple
+        of dips() or bald_patches()) with `bald` seed one line each at position + (0, 0, lift h_z), traced in both
+        directions by paths() (paths_options: its g, step, max_steps, every, max_points, values, device).  Returns
+        paths()'s FieldPaths; whole_line(paths, i) joins the two halves of the line through bald patch i."""
+        if (isinstance(lift, bool) or not isinstance(lift, (int, float, np.integer, np.floating)) or
+                not (np.isfinite(lift) and lift >= 0.0)):
+            raise ValueError(f"lift must be a finite number >= 0, not {lift!r}")
+        if "direction" in paths_options:
+            raise ValueError("bald_patch_lines traces in both directions: direction is not an option")
+        return self.paths(b, _bald_seeds(dips, lift, float(self.z[1]) - float(self.z[0])), direction="both",
+                          **paths_options)
+
     def skeleton(self, b, nulls=None, radius=0.5, nring=16, ring=None, capture=None, step=0.5, max_steps=None, every=1,
                  max_points=None, values=True, device=False):
         """The spine-fan skeleton of the nulls of b (3,nz,ny,nx), on the device (semantics: include/ndsm_hip.h,
@@ -1565,6 +1610,43 @@ def _skeleton_args(radius, nring, ring, capture):
     if not number(capture) or capture < 0.0:
         raise ValueError(f"capture must be None or a finite number >= 0, not {capture!r}")
     return float(radius), float(capture), _skeleton_ring(nring, ring)
+
+
+DIPS_MAX = 2 ** 28                # capacity of one dips() call: 92 B of host arrays per slot
+Dips = collections.namedtuple("Dips", ["position", "edge", "axis", "node", "b", "grad", "curv", "kappa", "bald",
+                                        "ncrossings", "ndips", "nbald"])
+
+
+def _dips_args(plane_only, max_dips):
+    """(plane_only as 0 / 1, max_dips or None) of dips(); ValueError before anything is launched"""
+    if not isinstance(plane_only, (bool, np.bool_)):
+        raise ValueError(f"plane_only must be True or False, not {plane_only!r}")
+    if max_dips is not None and (isinstance(max_dips, bool) or
+                                 not isinstance(max_dips, (int, float, np.integer, np.floating)) or
+                                 not np.isfinite(max_dips) or int(max_dips) != max_dips or
+                                 not 0 <= max_dips <= DIPS_MAX):
+        raise ValueError(f"max_dips must be None or an integer in 0 .. {DIPS_MAX}, not {max_dips!r}")
+    return int(bool(plane_only)), None if max_dips is None else int(max_dips)
+
+
+def _dips_tuple(rec, counts, nx, ny):
+    """a Dips tuple from the records [edge, pos, bpt, grad, curv, flag] and counts (crossings, dips, bald patches)"""
+    edge, pos, bpt, grad, curv, flag = rec
+    node = edge // 3
+    ijk = np.stack([node % nx, (node // nx) % ny, node // (nx * ny)], axis=1)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        kappa = curv / (bpt[:, 0] * bpt[:, 0] + bpt[:, 1] * bpt[:, 1])
+    return Dips(pos, edge, (edge % 3).astype(np.int32), ijk, bpt, grad, curv, kappa, (flag & 1).astype(bool),
+                int(counts[0]), int(counts[1]), int(counts[2]))
+
+
+def _bald_seeds(dips, lift, hz):
+    """the seeds of bald_patch_lines: position + (0, 0, lift hz) of the records with bald"""
+    pos, bald = np.asarray(dips.position, dtype=np.float64), np.asarray(dips.bald, dtype=bool)
+    if pos.ndim != 2 or pos.shape[1] != 3 or bald.shape != pos.shape[:1]:
+        raise NdsmHipError(f"bald_patch_lines: dips of shapes {pos.shape}, {bald.shape}: (n, 3) and (n) are needed "
+                           "(code 9002)")
+    return pos[bald] + np.array([0.0, 0.0, float(lift) * hz])
 
 
 def _skeleton_nulls(nulls):
@@ -2362,6 +2444,24 @@ def find_nulls(x, y, z, b, max_nulls=4096, merge=1e-6, lib=None):
         return V.nulls(b, max_nulls=max_nulls, merge=merge)
     finally:
         V.close()
+
+
+def find_dips(x, y, z, b, plane_only=False, max_dips=None, lib=None):
+    """Magnetic dips and bald patches of b (3,nz,ny,nx): one-shot form of VecPot.dips (returns its Dips tuple).
+    Raises NdsmHipError on device / runtime failures (>= 9001)."""
+    _dips_args(plane_only, max_dips)
+    V = _grid_handle(x, y, z, b, 0, lib)
+    try:
+        return V.dips(b, plane_only=plane_only, max_dips=max_dips)
+    finally:
+        V.close()
+
+
+def bald_patches(x, y, z, b, max_dips=None, lib=None):
+    """The bald patches of b (3,nz,ny,nx) - where field lines touch the plane k = 0 from above -: find_dips with
+    plane_only=True (returns VecPot.dips' Dips tuple, every record with bald).  Raises NdsmHipError on device /
+    runtime failures (>= 9001)."""
+    return find_dips(x, y, z, b, plane_only=True, max_dips=max_dips, lib=lib)
 
 
 def find_skeleton(x, y, z, b, nulls=None, radius=0.5, nring=16, ring=None, capture=None, step=0.5, max_steps=None,

@@ -356,6 +356,16 @@ int ndsmk_nulls(const double *B, const int32_t *n3, const double *lo3, const dou
                 int64_t *h_counts2, int64_t *cell, double *pos, double *jac, double *det, double *resid, int32_t *sign,
                 int32_t *iters);
 
+/* Dips and bald patches (dips.hip; semantics: include/ndsm_hip.h, ndsm_hip_vecpot_dips).  B a DEVICE array (nx,ny,nz,3);
+ * lo3, h_dq3: first mesh point and spacing per axis; plane_only 1: the nodes of k = 0 and the edges along x and y only.
+ * h_counts3 (HOST, int64): crossings, dips, bald patches, exact whatever max_dips.  The first min(dips, max_dips) records
+ * in ascending edge order go into the DEVICE arrays edge (int64), pos, bpt, grad (3 each), curv (doubles), flag (int32);
+ * with max_dips == 0 they are not looked at.  NDSMK_EVALUE for max_dips < 0, a plane_only that is not 0 or 1 and a mesh
+ * with fewer than 3 nodes on an axis.  Blocks for the three counts; the records are written asynchronously. */
+int ndsmk_dips(const double *B, const int32_t *n3, const double *lo3, const double *h_dq3, int plane_only,
+               int64_t max_dips, int64_t *h_counts3, int64_t *edge, double *pos, double *bpt, double *grad, double *curv,
+               int32_t *flag);
+
 /* Field-line paths (paths.hip; semantics: include/ndsm_hip.h, ndsm_hip_vecpot_paths), in two halves with the same
  * leading arguments, which are ndsmk_trace's.  ndsmk_paths_count: ndsmk_trace itself (ends, length, integral, status,
  * nsteps are its outputs), then offsets (nl + 1, int64, DEVICE) = the exclusive sums of the lines' point counts for the

@@ -2484,6 +2484,67 @@ contains
     end subroutine
   end function
 
+  ! ---- dips and bald patches on the same handle ------------------------------
+  ! B (nx,ny,nz,3) in; plane_only 0 or 1 (1: the plane k = 0 and its x and y edges alone); max_dips >= 0 the capacity of
+  ! the record arrays; counts (3, int64, on the HOST in both entries): crossings, dips, bald patches.  Out, the first
+  ! min(counts(2), max_dips) records in ascending edge order: edge (int64), pos, bpt, grad (3 each), curv (doubles),
+  ! flag (int32).  The handle supplies the mesh; no solve runs.  Return value: 0, or >= 9001 errors (9002 a NULL handle,
+  ! B or counts, or with max_dips > 0 a NULL record array; 9004 max_dips < 0, plane_only not 0 or 1, fewer than 3 nodes
+  ! on an axis).  On every failure counts is cleared, and the host entry clears the max_dips slots of its record arrays.
+
+  ! HOST arrays
+  function ndsm_hip_vecpot_dips(handle, B, plane_only, max_dips, counts, edge, pos, bpt, grad, curv, flag) &
+      bind(c, name="ndsm_hip_vecpot_dips") result(ierr)
+    type(c_ptr), value :: handle, B, counts, edge, pos, bpt, grad, curv, flag
+    integer(c_int), value :: plane_only
+    integer(c_int64_t), value :: max_dips
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_dips(handle, B, plane_only, max_dips, counts, edge, pos, bpt, grad, curv, flag, .false., &
+                              "ndsm_hip_vecpot_dips")
+  end function
+
+  ! the same on DEVICE arrays of the library's GPU (counts stays a host array; no record array is touched on the host)
+  function ndsm_hip_vecpot_dips_device(handle, dB, plane_only, max_dips, counts, dedge, dpos, dbpt, dgrad, dcurv, dflag) &
+      bind(c, name="ndsm_hip_vecpot_dips_device") result(ierr)
+    type(c_ptr), value :: handle, dB, counts, dedge, dpos, dbpt, dgrad, dcurv, dflag
+    integer(c_int), value :: plane_only
+    integer(c_int64_t), value :: max_dips
+    integer(c_int) :: ierr
+    ierr = vecpot_handle_dips(handle, dB, plane_only, max_dips, counts, dedge, dpos, dbpt, dgrad, dcurv, dflag, .true., &
+                              "ndsm_hip_vecpot_dips_device")
+  end function
+
+  function vecpot_handle_dips(handle, B, plane_only, max_dips, counts, edge, pos, bpt, grad, curv, flag, on_device, who) &
+      result(ierr)
+    type(c_ptr), intent(in) :: handle, B, counts, edge, pos, bpt, grad, curv, flag
+    integer(c_int), intent(in) :: plane_only
+    integer(c_int64_t), intent(in) :: max_dips
+    logical, intent(in) :: on_device
+    character(len=*), intent(in) :: who
+    integer(c_int) :: ierr
+    type(vecpot_ctx), pointer :: ctx
+    integer(c_int64_t), pointer :: cnt(:)
+    call clear_outputs()
+    ierr = live_ctx(handle, ctx)
+    if (ierr /= 0) return
+    ierr = NDSMK_EARG
+    if (.not. (c_associated(B) .and. c_associated(counts))) return
+    if (max_dips > 0 .and. .not. (c_associated(edge) .and. c_associated(pos) .and. c_associated(bpt) .and. &
+                                  c_associated(grad) .and. c_associated(curv) .and. c_associated(flag))) return
+    call c_f_pointer(counts, cnt, [3])
+    ierr = reported(who, vecpot_dips(ctx, B, plane_only, max_dips, cnt, edge, pos, bpt, grad, curv, flag, on_device))
+    if (ierr /= 0) call clear_outputs()
+  contains
+    ! counts, and (host entry) the max_dips slots of every record array
+    subroutine clear_outputs()
+      call clear_host([counts], [8], [3_c_int64_t])
+      if (on_device .or. max_dips <= 0) return
+      if (max_dips > huge(0_c_int64_t) / 24) return
+      call clear_host([edge, pos, bpt, grad, curv, flag], [8, 24, 24, 24, 8, 4], &
+                      [max_dips, max_dips, max_dips, max_dips, max_dips, max_dips])
+    end subroutine
+  end function
+
   ! ---- z-slab decomposition over GPUs (SURVEY 8e) -----------------------
 
   ! rank 0 creates the 128-byte RCCL id; the launcher hands it to every rank

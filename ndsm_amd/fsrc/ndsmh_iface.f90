@@ -850,6 +850,19 @@ module ndsmh_iface
       integer(c_int) :: rc
     end function
 
+    ! ---- dips and bald patches (dips.hip) ----
+    function ndsmk_dips(B, n3, lo3, dq3, plane_only, max_dips, counts3, edge, pos, bpt, grad, curv, flag) &
+        bind(c, name="ndsmk_dips") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_int64_t, c_double
+      type(c_ptr), value :: B, edge, pos, bpt, grad, curv, flag
+      integer(c_int32_t), intent(in) :: n3(3)
+      real(c_double), intent(in) :: lo3(3), dq3(3)
+      integer(c_int), value :: plane_only
+      integer(c_int64_t), value :: max_dips
+      integer(c_int64_t), intent(out) :: counts3(3)
+      integer(c_int) :: rc
+    end function
+
     ! ---- field-line paths (paths.hip): the counting half (blocks for total) and the filling half ----
     function ndsmk_paths_count(B, G, n3, lo3, dq3, nseeds, seeds, step, max_steps, direction, every, max_points, ends, &
                                length, integral, status, nsteps, offsets, total) bind(c, name="ndsmk_paths_count") result(rc)

@@ -35,6 +35,7 @@ module ndsmh_vecpot
   public :: vecpot_alpha_map, vecpot_nlfff, nlfff_args, vecpot_optimize, optimize_args, vecpot_preprocess, preprocess_args
   public :: vecpot_optimize_cascade, vecpot_ref, vecpot_optimize_obs, descent_ctl
   public :: vecpot_project, vecpot_devore, vecpot_lines, vecpot_paths, vecpot_nulls, vecpot_skeleton, vecpot_separators
+  public :: vecpot_dips
   public :: VP_POTENTIAL, VP_FIELD, VP_HELICITY, VP_CURRENT, VP_NLFFF
   ! pieces the distributed driver (ndsmh_wvecpot) shares with vecpot_solve
   public :: face_data, face_axis, face_upper, face_t1, face_t2, face_order, face_copy, vecpot_faces, say
@@ -2257,6 +2258,50 @@ contains
     rc = ndsmk_nulls(ctx%dF(1), n3, lo, dq, max_nulls, counts, s(1)%dev, s(2)%dev, s(3)%dev, s(4)%dev, s(5)%dev, &
                      s(6)%dev, s(7)%dev)
     if (rc == 0) rc = fetch(s, rows=int(min(counts(2), int(max_nulls, c_int64_t)), c_size_t))
+    if (rc == 0) rc = ndsmk_sync()
+    call unstage(rc, [buf])
+  end function
+
+  ! ------------------------------------------------------------------
+  ! The dip entries on a prepared context (semantics in include/ndsm_hip.h, DESIGN.md "Dips and bald patches"): the
+  ! edges of the mesh on which B_z changes sign with (B.grad)B_z > 0 at the crossing (ndsmk_dips).  The context
+  ! supplies the mesh only, as in vecpot_nulls; no solve.  pB (nx,ny,nz,3) in; plane_only 1: the plane k = 0 and its x
+  ! and y edges alone; counts(3) out on the host: crossings, dips, bald patches; the first min(counts(2), max_dips)
+  ! records in ascending edge order out: pedge int64, ppos, pbpt, pgrad (3 each), pcurv doubles, pflag int32 - on the
+  ! HOST (B goes up into the staging array dF(1), the records come home from a scratch buffer) or (on_device) in HBM.
+  ! ------------------------------------------------------------------
+  function vecpot_dips(ctx, pB, plane_only, max_dips, counts, pedge, ppos, pbpt, pgrad, pcurv, pflag, on_device) result(rc)
+    type(vecpot_ctx), intent(inout), target :: ctx
+    logical, intent(in) :: on_device
+    type(c_ptr), intent(in) :: pB, pedge, ppos, pbpt, pgrad, pcurv, pflag
+    integer(c_int), intent(in) :: plane_only
+    integer(c_int64_t), intent(in) :: max_dips
+    integer(c_int64_t), intent(out) :: counts(3)
+    integer(c_int) :: rc
+    real(wp) :: dq(3), lo(3)
+    integer(c_int32_t) :: n3(3)
+    integer(c_size_t) :: nm
+    type(c_ptr) :: buf
+    type(slice) :: s(6)
+
+    counts = 0
+    call ctx_mesh(ctx, n3, lo, dq)
+    if (on_device .or. max_dips < 0 .or. plane_only < 0 .or. plane_only > 1 .or. any(n3 < 3)) then
+      ! (the argument errors are the kernel entry's to name; nothing is staged for them)
+      rc = ndsmk_dips(pB, n3, lo, dq, plane_only, max_dips, counts, pedge, ppos, pbpt, pgrad, pcurv, pflag)
+      if (rc == 0) rc = ndsmk_sync()
+      return
+    end if
+    rc = stage_field(ctx, 1, pB); if (rc /= 0) return
+    ! one scratch buffer of max_dips records (none for max_dips = 0: the arrays are c_null_ptr)
+    nm = int(max_dips, c_size_t)
+    s = [slice(pedge, 8, nm, COMES_HOME), slice(ppos, 24, nm, COMES_HOME), slice(pbpt, 24, nm, COMES_HOME), &
+         slice(pgrad, 24, nm, COMES_HOME), slice(pcurv, 8, nm, COMES_HOME), slice(pflag, 4, nm, COMES_HOME)]
+    rc = carve(buf, s); if (rc /= 0) return
+    call say("find_dips", "Voting on the edges and filling the records...")
+    rc = ndsmk_dips(ctx%dF(1), n3, lo, dq, plane_only, max_dips, counts, s(1)%dev, s(2)%dev, s(3)%dev, s(4)%dev, &
+                    s(5)%dev, s(6)%dev)
+    if (rc == 0) rc = fetch(s, rows=int(min(counts(2), max_dips), c_size_t))
     if (rc == 0) rc = ndsmk_sync()
     call unstage(rc, [buf])
   end function

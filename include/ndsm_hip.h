@@ -1406,6 +1406,96 @@ int ndsm_hip_vecpot_dips_device(void *h, const double *dB, int plane_only, int64
                                 int64_t *dedge, double *dpos, double *dbpt, double *dgrad, double *dcurv,
                                 int32_t *dflag);
 
+/* ---- Flow inversion and boundary fluxes (DESIGN.md "Flow inversion and boundary fluxes") ---------------------------
+ * Every entry above reads one magnetogram.  These take two: the plasma velocity on the lower face from a pair of
+ * vector magnetograms - a local affine fit of the normal component of the induction equation, in the manner of
+ * DAVE4VM (Schuck 2008) -, the potential field's vector potential ON the plane, and with both the fluxes of relative
+ * helicity and of magnetic energy through the face (Berger & Field 1984): how fast the H and E of
+ * ndsm_hip_vecpot_helicity enter the box.  No handle.  Fields are component planes with x fastest, B (nsx,nsy,3); the
+ * mesh is uniform, hx = xs[1] - xs[0] and hy = ys[1] - ys[0], both > 0; pixel (i,j) is c = i + nsx j.  fp64 + - * /
+ * and sqrt only, in the operand order written here, no contraction: a restatement in the same order gives the same
+ * bits (tests/flow_model.py).
+ *
+ * ndsm_hip_flow_fit.  B0, B1 (nsx,nsy,3) at two times dt apart (dt finite, != 0, of either sign); nsx, nsy >= 3;
+ *   r the half width of the window, 1 <= r <= 16: the (2r+1)^2 pixels around a target, each with weight 1 (top-hat);
+ *   rcond with 0 <= rcond < 1.  Out: V (nsx,nsy,3), coef (nsx,nsy,9), status (nsx,nsy; int32).
+ *   staged    per pixel, seven quantities:  Bm_c = 0.5 (B0_c + B1_c) for c = x, y, z;  T = (B1_z - B0_z) / dt;
+ *             Zx = ddq_x(Bm_z), Zy = ddq_y(Bm_z), D = ddq_x(Bm_x) + ddq_y(Bm_y), with ddq the nodal difference
+ *             quotient of ndsm_hip_vecpot_dips ("gradient") in exactly its operand order: centred inside, 3-point
+ *             one-sided on the end rows.
+ *   model     inside the window of the target (i,j) the flow is affine, u = u0 + ux x' + uy y', v = v0 + vx x' + vy y',
+ *             w = w0 + wx x' + wy y', with x' = (double)a hx and y' = (double)b hy at the window pixel (i + a, j + b).
+ *             The residual of d_t B_z + div_h (B_z V_h - V_z B_h) there is T + s.p, p = (u0, ux, uy, v0, vx, vy, w0,
+ *             wx, wy), and with every quantity taken at the window pixel
+ *               s = ( Zx,  Zx x' + Bz,  Zx y',   Zy,  Zy x',  Zy y' + Bz,   -D,  -(D x') - Bx,  -(D y') - By ).
+ *   sums      G_kl = sum s_k s_l (k <= l) and g_k = sum (-T) s_k over the window pixels that lie inside the
+ *             magnetogram - windows are clipped, not padded -, b ascending outer, a ascending inner, every sum starting
+ *             at 0.0: G_kl = G_kl + s_k s_l; g_k = g_k + (-T) s_k.
+ *   scaling   d_k = 1.0 / sqrt(G_kk);  Gs_kl = (G_kl d_k) d_l;  gs_k = g_k d_k.
+ *   LDL^T     of Gs without pivoting, k ascending; every inner sum starts at 0.0 and adds left to right:
+ *               for j < k (ascending):  w_kj = Gs_jk - sum_{m<j} w_km L_jm;   L_kj = w_kj / D_j;
+ *               D_k = Gs_kk - sum_{j<k} w_kj L_kj.
+ *             Then y_k = gs_k - sum_{j<k} L_kj y_j (k ascending);  z_k = y_k / D_k;
+ *             ps_k = z_k - sum_{j>k} L_jk ps_j (k descending, j ascending);  p_k = ps_k d_k.
+ *   status    2: one of the seven staged quantities of a window pixel is not finite; V and coef are NaN.  Otherwise
+ *             1: rank-deficient - the aperture problem -: some G_kk is not > 0, or some pivot D_k is not > rcond; V
+ *             and coef are 0.0.  Otherwise 0: solved; coef = p, V = (p_0, p_3, p_6) = (u0, v0, w0).
+ *   A separable running-sum form of the sums would be O(1) per pixel but has another order and cancellation; it is not
+ *   what runs.  Device memory: seven planes of scratch (56 B per pixel), kept between calls and grown on demand.
+ *
+ * ndsm_hip_green_ap_points, ndsm_hip_green_ap_plane.  A_p with A_p.n = 0, div_h A_p = 0 and z.curl A_p = B_z on the
+ *   plane: the third pair term of the all-pairs sum of ndsm_hip_green_points.  Source, c = (hx hy) /
+ *   6.283185307179586, slices, order of the sum and fold: exactly those of ndsm_hip_green_points (zs is not needed).
+ *   One target (X, Y) on the plane.  For pixel p: q = bz[p] c; dx = X - xs[i]; dy = Y - ys[j]; r2 = dx dx + dy dy; if
+ *   r2 > 0: t = q / r2 and the two terms are (-dy) t and dx t; otherwise the pixel contributes no term (the punctured
+ *   rule).  With the punctured rule the sum is second order in h on the source's own nodes: the singular part of the
+ *   kernel is odd about the target, so the pixel left out costs O(h^2).
+ *   _points: Ap (2,npts) at pts (2,npts).  _plane: Ap (nsx,nsy,2) on the source's own nodes (xs[i], ys[j]).  A node
+ *   gets the same bits from both.  npts == 0 returns 0 and touches nothing.
+ *
+ * ndsm_hip_flow_flux.  B, V (nsx,nsy,3), Ap (nsx,nsy,2); nsx, nsy >= 2.  Out dens (nsx,nsy,4), per pixel
+ *     h_em = 2.0 ((Apx Bx + Apy By) Vz)        h_sh = -2.0 ((Apx Vx + Apy Vy) Bz)
+ *     s_em = (Bx Bx + By By) Vz                 s_sh = -((Bx Vx + By Vy) Bz)
+ *   the emergence and shear terms of dH/dt = 2 int [(A_p.B_h) V_z - (A_p.V_h) B_z] dA and of the Poynting flux
+ *   dE/dt = int [B_h^2 V_z - (B_h.V_h) B_z] dA - without 4 pi, as E = 1/2 sum w |B|^2 of ndsm_hip_vecpot_helicity.
+ *   out[8], on the HOST in both forms: [0] sum w h_em, [1] sum w h_sh, [2] out[0] + out[1], [3] sum w s_em,
+ *   [4] sum w s_sh, [5] out[3] + out[4], [6] sum w |Bz|, [7] sum w Bz;  w = wx(i) wy(j), wx = hx inside and 0.5 hx
+ *   on both end rows, likewise wy: the trapezoid weights.  Each sum is sum = sum + w term in the order of the
+ *   reduction behind ndsm_hip_vecpot_helicity: NB = min(nsy, 2048) blocks of 256 lanes; lane t of block b adds, from
+ *   0.0, the rows j = b, b + NB, ... and in a row the pixels i = t, t + 256, ...; a halving tree over the lanes
+ *   (lane t += lane t + o, o = 128 .. 1); then lane t of one block adds, from 0.0, the results of the blocks t,
+ *   t + 256, ..., and the same tree.  No atomics: the same input gives the same bits.  One blocking read.
+ *
+ * The mesh vectors stay on the HOST in both forms.  Returns 0 or, in this order: 9001 without a GPU whatever the
+ *   arguments; 9001 before anything is allocated - as soon as the shapes can be read - when the arrays and the scratch
+ *   exceed the device's TOTAL memory (the screen of the Green's-function entries); 9002 a NULL array or shape; 9004 an
+ *   axis < 2 (the fit: < 3), a spacing not > 0, npts < 0, and for the fit a dt that is 0 or not finite, r outside
+ *   1..16, rcond outside [0, 1) or not finite.  A failed call leaves the outputs untouched. */
+/* HOST arrays */
+int ndsm_hip_flow_fit(const int nsrc[2], const double *xs, const double *ys, const double *B0, const double *B1,
+                      double dt, int r, double rcond, double *V, double *coef, int32_t *status);
+/* the same with B0, B1, V, coef and status DEVICE arrays of the library's GPU */
+int ndsm_hip_flow_fit_device(const int nsrc[2], const double *xs, const double *ys, const double *dB0,
+                             const double *dB1, double dt, int r, double rcond, double *dV, double *dcoef,
+                             int32_t *dstatus);
+/* HOST arrays */
+int ndsm_hip_green_ap_points(const int nsrc[2], const double *xs, const double *ys, const double *bz, int npts,
+                             const double *pts, double *Ap);
+/* the same with bz, pts and Ap DEVICE arrays of the library's GPU */
+int ndsm_hip_green_ap_points_device(const int nsrc[2], const double *xs, const double *ys, const double *dbz, int npts,
+                                    const double *dpts, double *dAp);
+/* HOST arrays */
+int ndsm_hip_green_ap_plane(const int nsrc[2], const double *xs, const double *ys, const double *bz, double *Ap);
+/* the same with bz and Ap DEVICE arrays of the library's GPU */
+int ndsm_hip_green_ap_plane_device(const int nsrc[2], const double *xs, const double *ys, const double *dbz,
+                                   double *dAp);
+/* HOST arrays (out too) */
+int ndsm_hip_flow_flux(const int nsrc[2], const double *xs, const double *ys, const double *B, const double *V,
+                       const double *Ap, double *dens, double out[8]);
+/* the same with B, V, Ap and dens DEVICE arrays of the library's GPU; out stays on the host */
+int ndsm_hip_flow_flux_device(const int nsrc[2], const double *xs, const double *ys, const double *dB,
+                              const double *dV, const double *dAp, double *ddens, double out[8]);
+
 #ifdef __cplusplus
 }
 #endif

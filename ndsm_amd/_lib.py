@@ -159,6 +159,16 @@ def load_library(path=None):
     _di = [ctypes.c_void_p] * 2 + [ctypes.c_int, ctypes.c_int64] + [ctypes.c_void_p] * 7
     L.ndsm_hip_vecpot_dips.argtypes = _di
     L.ndsm_hip_vecpot_dips_device.argtypes = _di
+    _pm = [_ip, _dp, _dp]                                              # the mesh of a plane: nsrc, xs, ys
+    _ff = _pm + [ctypes.c_void_p] * 2 + [ctypes.c_double, ctypes.c_int, ctypes.c_double] + [ctypes.c_void_p] * 3
+    L.ndsm_hip_flow_fit.argtypes = _ff
+    L.ndsm_hip_flow_fit_device.argtypes = _ff
+    L.ndsm_hip_green_ap_points.argtypes = _pm + [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    L.ndsm_hip_green_ap_points_device.argtypes = _pm + [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    L.ndsm_hip_green_ap_plane.argtypes = _pm + [ctypes.c_void_p] * 2
+    L.ndsm_hip_green_ap_plane_device.argtypes = _pm + [ctypes.c_void_p] * 2
+    L.ndsm_hip_flow_flux.argtypes = _pm + [ctypes.c_void_p] * 4 + [_dp]
+    L.ndsm_hip_flow_flux_device.argtypes = _pm + [ctypes.c_void_p] * 4 + [_dp]
     _sk = ([ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_int, ctypes.c_void_p] +
            [ctypes.c_double] * 3 + [ctypes.c_int, ctypes.c_int, ctypes.c_int64] + [ctypes.c_void_p] * 13)
     L.ndsm_hip_vecpot_skeleton.argtypes = _sk
@@ -2283,6 +2293,138 @@ def best_alpha(x, y, b, bz_min=0.0):
     if not den > 0.0:
         raise ValueError("no pixel with |Bz| >= bz_min and Bz != 0: alpha is undefined")
     return float(np.sum(jz[use] * bz[use])) / den
+
+
+Flow = collections.namedtuple("Flow", ["v", "coef", "status"])
+Fluxes = collections.namedtuple("Fluxes", ["dens", "helicity", "energy", "flux"])
+
+
+def _plane_mesh(xs, ys, nmin):
+    """the uniform mesh of a magnetogram as (nsrc, xs, ys); ValueError for what the library would answer with 9004"""
+    qx, qy = _f64(xs).reshape(-1), _f64(ys).reshape(-1)
+    if len(qx) < nmin or len(qy) < nmin:
+        raise ValueError(f"the mesh needs at least {nmin} nodes per axis, not {len(qx)} x {len(qy)}")
+    if not (qx[1] - qx[0] > 0.0 and qy[1] - qy[0] > 0.0):
+        raise ValueError("the mesh needs spacings > 0")
+    return np.array([len(qx), len(qy)], dtype=np.intc), qx, qy
+
+
+def _plane_field(a, ncomp, qx, qy, name):
+    """a (ncomp,nsy,nsx) as a flat float64 copy; ValueError for another shape"""
+    A = np.asarray(a)
+    want = (ncomp, len(qy), len(qx)) if ncomp else (len(qy), len(qx))
+    if A.shape != want:
+        raise ValueError(f"{name} of shape {A.shape}, the mesh needs {want}")
+    return _f64(A).reshape(-1).copy()
+
+
+def flow_fit(xs, ys, b0, b1, dt, r=5, rcond=1e-10, device=False, lib=None):
+    """The plasma velocity on the plane of two vector magnetograms b0, b1 (3,nsy,nsx) taken dt apart on the uniform mesh
+    xs, ys: a local affine fit of the normal component of the induction equation over top-hat windows of (2r+1)^2
+    pixels, in the manner of DAVE4VM (Schuck 2008), on the device (semantics: include/ndsm_hip.h, ndsm_hip_flow_fit).
+    Returns Flow(v (3,nsy,nsx), coef (9,nsy,nsx) = u0, ux, uy, v0, vx, vy, w0, wx, wy, status (nsy,nsx)): status 0
+    solved; 1 rank-deficient (the aperture problem; a scaled pivot not above rcond), v and coef 0; 2 a value that is not
+    finite in the window, v and coef NaN.  device=True: the arrays are staged in device memory and the device-resident
+    entry point runs."""
+    ns2, qx, qy = _plane_mesh(xs, ys, 3)
+    dt, rcond = float(dt), float(rcond)
+    if not np.isfinite(dt) or dt == 0.0:
+        raise ValueError(f"dt must be finite and not 0, not {dt!r}")
+    if int(r) != r or not 1 <= r <= 16:
+        raise ValueError(f"r must be a whole number in 1..16, not {r!r}")
+    if not 0.0 <= rcond < 1.0:
+        raise ValueError(f"rcond must be in [0, 1), not {rcond!r}")
+    B0, B1 = _plane_field(b0, 3, qx, qy, "b0"), _plane_field(b1, 3, qx, qy, "b1")
+    L = lib or load_library()
+    npix = len(qx) * len(qy)
+    V, C, S = np.zeros(3 * npix), np.zeros(9 * npix), np.zeros(npix, dtype=np.int32)
+    head = (ns2.ctypes.data_as(_ip), _d(qx), _d(qy))
+    if not device:
+        _check(L.ndsm_hip_flow_fit(*head, B0.ctypes.data, B1.ctypes.data, dt, int(r), rcond, V.ctypes.data, C.ctypes.data,
+                                   S.ctypes.data), "ndsm_hip_flow_fit", L)
+    else:
+        _check(_staged(L, [B0, B1, V, C, S], lambda d0, d1, dV, dC, dS: L.ndsm_hip_flow_fit_device(
+            *head, d0, d1, dt, int(r), rcond, dV, dC, dS)), "ndsm_hip_flow_fit_device", L)
+    shape = (len(qy), len(qx))
+    return Flow(V.reshape((3,) + shape), C.reshape((9,) + shape), S.reshape(shape))
+
+
+def plane_vector_potential(xs, ys, bz, device=False, lib=None):
+    """The potential field's vector potential on the plane of the magnetogram bz (nsy,nsx) itself - A_p.n = 0,
+    div_h A_p = 0, z.curl A_p = bz - on the magnetogram's own nodes, on the device (semantics: include/ndsm_hip.h,
+    ndsm_hip_green_ap_plane).  Returns ap (2,nsy,nsx).  device=True: the arrays are staged in device memory and the
+    device-resident entry point runs."""
+    ns2, qx, qy = _plane_mesh(xs, ys, 2)
+    S = _plane_field(bz, 0, qx, qy, "bz")
+    L = lib or load_library()
+    A = np.zeros(2 * S.size)
+    head = (ns2.ctypes.data_as(_ip), _d(qx), _d(qy))
+    if not device:
+        _check(L.ndsm_hip_green_ap_plane(*head, S.ctypes.data, A.ctypes.data), "ndsm_hip_green_ap_plane", L)
+    else:
+        _check(_staged(L, [S, A], lambda dS, dA: L.ndsm_hip_green_ap_plane_device(*head, dS, dA)),
+               "ndsm_hip_green_ap_plane_device", L)
+    return A.reshape(2, len(qy), len(qx))
+
+
+def plane_vector_potential_points(xs, ys, bz, pts, device=False, lib=None):
+    """The same vector potential at the points pts (npts,2; x, y) of the plane (semantics: include/ndsm_hip.h,
+    ndsm_hip_green_ap_points).  Returns ap (npts,2).  A point that is a node of the mesh bit for bit gets the bits of
+    plane_vector_potential() there."""
+    P = np.asarray(pts, dtype=np.float64)
+    if P.ndim != 2 or P.shape[1] != 2:
+        raise ValueError(f"pts of shape {P.shape}, (npts, 2) is needed")
+    ns2, qx, qy = _plane_mesh(xs, ys, 2)
+    S = _plane_field(bz, 0, qx, qy, "bz")
+    L = lib or load_library()
+    P = np.ascontiguousarray(P).reshape(-1).copy()
+    A = np.zeros(P.size)
+    head = (ns2.ctypes.data_as(_ip), _d(qx), _d(qy))
+    if not device:
+        _check(L.ndsm_hip_green_ap_points(*head, S.ctypes.data, len(P) // 2, P.ctypes.data, A.ctypes.data),
+               "ndsm_hip_green_ap_points", L)
+    else:
+        _check(_staged(L, [S, P, A], lambda dS, dP, dA: L.ndsm_hip_green_ap_points_device(*head, dS, len(P) // 2, dP, dA)),
+               "ndsm_hip_green_ap_points_device", L)
+    return A.reshape(-1, 2)
+
+
+def boundary_fluxes(xs, ys, b, v, ap=None, status=None, device=False, lib=None):
+    """The fluxes of relative helicity and of magnetic energy through the plane of the magnetogram b (3,nsy,nsx) under
+    the flow v (3,nsy,nsx) (Berger & Field 1984; semantics: include/ndsm_hip.h, ndsm_hip_flow_flux).  ap (2,nsy,nsx):
+    the potential field's vector potential on the plane; None computes it from b[2] on the device
+    (ndsm_hip_green_ap_plane_device), and it goes into the fluxes without crossing PCIe in between.  status
+    (nsy,nsx), e.g. flow_fit()'s: v is taken as 0 where it is not 0.  Returns Fluxes(dens (4,nsy,nsx) = h_em, h_sh,
+    s_em, s_sh per pixel; helicity = (emergence, shear, total); energy = (emergence, shear, total) - no 4 pi, as
+    relative_helicity()'s energies -; flux = (unsigned, signed) magnetic flux).  device=True: ap too is staged and the
+    device-resident entry point runs."""
+    ns2, qx, qy = _plane_mesh(xs, ys, 2)
+    B, V = _plane_field(b, 3, qx, qy, "b"), _plane_field(v, 3, qx, qy, "v")
+    A = None if ap is None else _plane_field(ap, 2, qx, qy, "ap")
+    npix = len(qx) * len(qy)
+    if status is not None:
+        st = np.asarray(status)
+        if st.shape != (len(qy), len(qx)):
+            raise ValueError(f"status of shape {st.shape}, the mesh needs {(len(qy), len(qx))}")
+        V.reshape(3, npix)[:, st.reshape(-1) != 0] = 0.0
+    L = lib or load_library()
+    D, out = np.zeros(4 * npix), np.zeros(8)
+    head = (ns2.ctypes.data_as(_ip), _d(qx), _d(qy))
+    if A is not None and not device:
+        _check(L.ndsm_hip_flow_flux(*head, B.ctypes.data, V.ctypes.data, A.ctypes.data, D.ctypes.data, _d(out)),
+               "ndsm_hip_flow_flux", L)
+    elif A is not None:
+        _check(_staged(L, [B, V, A, D], lambda dB, dV, dA, dD: L.ndsm_hip_flow_flux_device(*head, dB, dV, dA, dD, _d(out))),
+               "ndsm_hip_flow_flux_device", L)
+    else:
+        A = np.zeros(2 * npix)
+
+        def both(dB, dV, dA, dD):
+            rc = L.ndsm_hip_green_ap_plane_device(*head, ctypes.c_void_p(dB.value + 16 * npix), dA)
+            return rc if rc != 0 else L.ndsm_hip_flow_flux_device(*head, dB, dV, dA, dD, _d(out))
+        _check(_staged(L, [B, V, A, D], both), "ndsm_hip_green_ap_plane_device + ndsm_hip_flow_flux_device", L)
+    return Fluxes(D.reshape(4, len(qy), len(qx)), tuple(float(x) for x in out[0:3]), tuple(float(x) for x in out[3:6]),
+                  (float(out[6]), float(out[7])))
 
 
 def potential_open(x, y, z, bz, xs=None, ys=None, zs=None, a_init=None, niterex_max=10000, ncycles_max=1024,

@@ -10,12 +10,15 @@
 //   lfff_k  : the same layout for the constant-alpha field (semantics: include/ndsm_hip.h, ndsm_hip_lfff_points): the
 //             pair term of Chiu & Hilton's half-space solution.  sin(alpha w) and cos(alpha w) are per target and stay
 //             in registers with X, Y, w, ww and the sums; a pair costs one sqrt, four divisions and one sincos.
+//   ap_k    : the same layout for the potential field's vector potential ON the plane (semantics: include/ndsm_hip.h,
+//             ndsm_hip_green_ap_points): targets (X, Y), two sums, and a pair term without a square root - one
+//             division.
 //   fold_k  : one thread per target adds the slice sums in ascending order, starting from slice 0's, applies the rules
-//             of the plane (w < 0: NaN; w == 0: Bz is the bilinear interpolation of bz) and writes the target's three
-//             components where its generator says.
+//             of the plane (w < 0: NaN; w == 0: Bz is the bilinear interpolation of bz; neither for ap_k's two sums)
+//             and writes the target's components where its generator says.
 //
-// Three target generators share both kernels: a point list (3,npts), the face nodes of a box mesh and all nodes of a
-// box mesh.  Targets are processed in chunks of at most 262144, which keeps the scratch at 384 MiB or less; a target's
+// Three target generators share green_k and lfff_k: a point list (3,npts), the face nodes of a box mesh and all nodes
+// of a box mesh; two more serve ap_k: a point list (2,npts) and the source's own nodes.  Targets are processed in chunks of at most 262144, which keeps the scratch at 384 MiB or less; a target's
 // sums depend on nothing but the target and the source, so the chunking and the generator leave no trace in the bits.
 //
 // Plain C++ under -ffp-contract=off with IEEE division and sqrt: the operand order of the header is the bits, and
@@ -33,7 +36,7 @@ constexpr i64 kChunk = 262144;          // targets per launch: 64 slices x 3 x 8
 constexpr i64 kSliceMin = 4096;         // pixels per slice before the 64-slice cap
 constexpr int kSliceCap = 64;
 
-enum { GEN_POINTS = 0, GEN_FACES = 1, GEN_VOLUME = 2 };
+enum { GEN_POINTS = 0, GEN_FACES = 1, GEN_VOLUME = 2, GEN_POINTS2 = 3, GEN_PLANE = 4 };
 
 struct Source {
   const double *xs, *ys, *bz;           // DEVICE
@@ -45,9 +48,10 @@ struct Source {
 
 struct Targets {
   int gen;
+  int nc;                               // components per target: 3, or 2 for the plane's vector potential
   i64 count;                            // all targets of the call
-  const double *pts;                    // GEN_POINTS: (3,npts), DEVICE
-  const double *x, *y, *z;              // the box mesh, DEVICE
+  const double *pts;                    // GEN_POINTS: (3,npts), GEN_POINTS2: (2,npts), DEVICE
+  const double *x, *y, *z;              // the box mesh (GEN_PLANE: the source's xs and ys), DEVICE
   int nx, ny, nz;
 };
 
@@ -89,6 +93,23 @@ __device__ __forceinline__ void target_of(const Targets &g, i64 t, double &X, do
     Z = g.pts[3 * t + 2];
     at = (size_t)(3 * t);
     stride = 1;
+    return;
+  }
+  if (g.gen == GEN_POINTS2) {
+    X = g.pts[2 * t];
+    Y = g.pts[2 * t + 1];
+    Z = 0.0;
+    at = (size_t)(2 * t);
+    stride = 1;
+    return;
+  }
+  if (g.gen == GEN_PLANE) {
+    const i64 jp = t / g.nx;
+    X = g.x[t - jp * g.nx];
+    Y = g.y[jp];
+    Z = 0.0;
+    at = (size_t)t;
+    stride = (size_t)g.nx * (size_t)g.ny;
     return;
   }
   int i, j, k;
@@ -214,6 +235,48 @@ __global__ __launch_bounds__(kBlock) void lfff_k(Source s, double alpha, Targets
   }
 }
 
+// the plane's vector potential: part[(s * 2 + c) * cnt + (t - t0)], two sums per target and slice
+__global__ __launch_bounds__(kBlock) void ap_k(Source s, Targets g, i64 t0, i64 cnt, double *__restrict__ part) {
+  __shared__ double lx[kBlock], ly[kBlock], lq[kBlock];
+  const int l = threadIdx.x;
+  const i64 lt = (i64)blockIdx.x * kBlock + l;
+  const bool live = lt < cnt;
+  double X = 0.0, Y = 0.0, Z = 0.0;
+  if (live) {
+    size_t at, stride;
+    target_of(g, t0 + lt, X, Y, Z, at, stride);
+  }
+  double ax = 0.0, ay = 0.0;
+  const i64 p0 = (i64)blockIdx.y * s.len;
+  const i64 p1 = p0 + s.len < s.npix ? p0 + s.len : s.npix;
+  for (i64 tile = p0; tile < p1; tile += kBlock) {
+    const i64 p = tile + l;
+    if (p < p1) {
+      const i64 j = p / s.nsx;
+      lx[l] = s.xs[p - j * s.nsx];
+      ly[l] = s.ys[j];
+      lq[l] = s.bz[p] * s.c;
+    }
+    __syncthreads();
+    const int m = p1 - tile < kBlock ? (int)(p1 - tile) : kBlock;
+    for (int n = 0; n < m; ++n) {
+      const double dx = X - lx[n], dy = Y - ly[n];
+      const double r2 = dx * dx + dy * dy;
+      if (r2 > 0.0) {
+        const double t = lq[n] / r2;
+        ax = ax + (-dy) * t;
+        ay = ay + dx * t;
+      }
+    }
+    __syncthreads();
+  }
+  if (live) {
+    double *o = part + (size_t)blockIdx.y * 2 * (size_t)cnt + (size_t)lt;
+    o[0] = ax;
+    o[(size_t)cnt] = ay;
+  }
+}
+
 // the largest node i0 <= n - 2 with v[i0] <= q, for v[0] <= q <= v[n - 1]: an estimate from the spacing, corrected
 __device__ __forceinline__ int bracket(const double *v, int n, double q) {
   const double e = floor((q - v[0]) / (v[1] - v[0]));
@@ -247,19 +310,26 @@ __global__ __launch_bounds__(kBlock) void fold_k(Source s, Targets g, i64 t0, i6
   size_t at, stride;
   target_of(g, t0 + lt, X, Y, Z, at, stride);
   double b[3];
+#pragma unroll
   for (int c = 0; c < 3; ++c) {
+    b[c] = 0.0;
+    if (c >= g.nc) continue;
     const double *q = part + (size_t)c * (size_t)cnt + (size_t)lt;
     double acc = q[0];
-    for (int sl = 1; sl < s.nslices; ++sl) acc = acc + q[(size_t)sl * 3 * (size_t)cnt];
+    for (int sl = 1; sl < s.nslices; ++sl) acc = acc + q[(size_t)sl * (size_t)g.nc * (size_t)cnt];
     b[c] = acc;
   }
-  const double w = Z - s.zs;
-  if (w < 0.0) {
-    b[0] = b[1] = b[2] = __builtin_nan("");
-  } else if (w == 0.0) {
-    b[2] = plane_bz(s, X, Y);
+  if (g.nc == 3) {
+    const double w = Z - s.zs;
+    if (w < 0.0) {
+      b[0] = b[1] = b[2] = __builtin_nan("");
+    } else if (w == 0.0) {
+      b[2] = plane_bz(s, X, Y);
+    }
   }
-  for (int c = 0; c < 3; ++c) out[at + (size_t)c * stride] = b[c];
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+    if (c < g.nc) out[at + (size_t)c * stride] = b[c];
 }
 
 int slices_of(i64 npix) {
@@ -288,7 +358,7 @@ double own_bytes(const int32_t *nsrc2, const int32_t *n3, double ntargets) {
 }
 
 // the shared driver: mesh vectors up, then chunk after chunk the all-pairs launch and the fold.  alpha NULL: the
-// potential field (green_k); else the constant-alpha field (lfff_k)
+// potential field (green_k); else the constant-alpha field (lfff_k).  g.nc == 2: the plane's vector potential (ap_k)
 int run(const int32_t *nsrc2, const double *h_xs, const double *h_ys, double zs, const double *bz, const double *alpha,
         Targets g,
         const int32_t *n3, const double *h_x, const double *h_y, const double *h_z, double *out) {
@@ -304,7 +374,7 @@ int run(const int32_t *nsrc2, const double *h_xs, const double *h_ys, double zs,
   const i64 chunk = g.count < kChunk ? g.count : kChunk;
   const size_t nmesh = (size_t)s.nsx + (size_t)s.nsy + (n3 ? (size_t)n3[0] + (size_t)n3[1] + (size_t)n3[2] : 0);
   void *buf = nullptr;
-  int rc = ndsmk_alloc(&buf, 8 * (nmesh + 3 * (size_t)chunk * (size_t)s.nslices));
+  int rc = ndsmk_alloc(&buf, 8 * (nmesh + (size_t)g.nc * (size_t)chunk * (size_t)s.nslices));
   if (rc != 0) return rc;
   double *d = (double *)buf;
   s.xs = d;
@@ -312,6 +382,10 @@ int run(const int32_t *nsrc2, const double *h_xs, const double *h_ys, double zs,
   rc = ndsmk_h2d(d, h_xs, 8 * (size_t)s.nsx);
   if (rc == 0) rc = ndsmk_h2d(d + s.nsx, h_ys, 8 * (size_t)s.nsy);
   double *m = d + s.nsx + s.nsy;
+  if (g.gen == GEN_PLANE) {
+    g.x = s.xs;
+    g.y = s.ys;
+  }
   if (n3 && rc == 0) {
     g.x = m;
     g.y = m + n3[0];
@@ -324,7 +398,9 @@ int run(const int32_t *nsrc2, const double *h_xs, const double *h_ys, double zs,
   for (i64 t0 = 0; t0 < g.count && rc == 0; t0 += chunk) {
     const i64 cnt = g.count - t0 < chunk ? g.count - t0 : chunk;
     const unsigned nb = (unsigned)((cnt + kBlock - 1) / kBlock);
-    if (alpha)
+    if (g.nc == 2)
+      hipLaunchKernelGGL(ap_k, dim3(nb, (unsigned)s.nslices), dim3(kBlock), 0, ndsm::stream(), s, g, t0, cnt, part);
+    else if (alpha)
       hipLaunchKernelGGL(lfff_k, dim3(nb, (unsigned)s.nslices), dim3(kBlock), 0, ndsm::stream(), s, *alpha, g, t0, cnt,
                          part);
     else
@@ -368,6 +444,7 @@ extern "C" int ndsmk_green_points(const int32_t *nsrc2, const double *h_xs, cons
   NDSM_CHECK_ARG(pts && B);
   Targets g = {};
   g.gen = GEN_POINTS;
+  g.nc = 3;
   g.count = npts;
   g.pts = pts;
   return run(nsrc2, h_xs, h_ys, zs, bz, nullptr, g, nullptr, nullptr, nullptr, nullptr, B);
@@ -388,6 +465,7 @@ extern "C" int ndsmk_green_box(const int32_t *nsrc2, const double *h_xs, const d
     return ndsmk_note_error(NDSMK_ENODEV, "green_box: more targets than any device holds");
   Targets g = {};
   g.gen = which == 0 ? GEN_FACES : GEN_VOLUME;
+  g.nc = 3;
   g.count = (i64)box_targets(n3, which);      // (exact: whole numbers below 2^53)
   g.nx = n3[0];
   g.ny = n3[1];
@@ -408,6 +486,7 @@ extern "C" int ndsmk_lfff_points(const int32_t *nsrc2, const double *h_xs, const
   NDSM_CHECK_ARG(pts && B);
   Targets g = {};
   g.gen = GEN_POINTS;
+  g.nc = 3;
   g.count = npts;
   g.pts = pts;
   return run(nsrc2, h_xs, h_ys, zs, bz, &alpha, g, nullptr, nullptr, nullptr, nullptr, B);
@@ -427,9 +506,45 @@ extern "C" int ndsmk_lfff_box(const int32_t *nsrc2, const double *h_xs, const do
     return ndsmk_note_error(NDSMK_ENODEV, "lfff_box: more targets than any device holds");
   Targets g = {};
   g.gen = which == 0 ? GEN_FACES : GEN_VOLUME;
+  g.nc = 3;
   g.count = (i64)box_targets(n3, which);      // (exact: whole numbers below 2^53)
   g.nx = n3[0];
   g.ny = n3[1];
   g.nz = n3[2];
   return run(nsrc2, h_xs, h_ys, zs, bz, &alpha, g, n3, h_x, h_y, h_z, B);
+}
+
+// The potential field's vector potential on the plane of the magnetogram (semantics: include/ndsm_hip.h,
+// ndsm_hip_green_ap_points): Ap (2,npts) at pts (2,npts); bz, pts and Ap DEVICE arrays.  Chunks, scratch and screen are
+// ndsmk_green_points'.
+extern "C" int ndsmk_green_ap_points(const int32_t *nsrc2, const double *h_xs, const double *h_ys, const double *bz,
+                                     int npts, const double *pts, double *Ap) {
+  NDSM_REQUIRE_READY();
+  NDSM_CHECK_ARG(nsrc2 && h_xs && h_ys && bz);
+  if (!source_ok(nsrc2, h_xs, h_ys) || npts < 0)
+    return ndsmk_note_error(NDSMK_EVALUE, "green_ap_points: at least 2 source nodes per axis, spacings > 0 and npts >= 0");
+  if (npts == 0) return 0;
+  NDSM_CHECK_ARG(pts && Ap);
+  Targets g = {};
+  g.gen = GEN_POINTS2;
+  g.nc = 2;
+  g.count = npts;
+  g.pts = pts;
+  return run(nsrc2, h_xs, h_ys, 0.0, bz, nullptr, g, nullptr, nullptr, nullptr, nullptr, Ap);
+}
+
+// the same on the source's own nodes: Ap (nsx,nsy,2)
+extern "C" int ndsmk_green_ap_plane(const int32_t *nsrc2, const double *h_xs, const double *h_ys, const double *bz,
+                                    double *Ap) {
+  NDSM_REQUIRE_READY();
+  NDSM_CHECK_ARG(nsrc2 && h_xs && h_ys && bz && Ap);
+  if (!source_ok(nsrc2, h_xs, h_ys))
+    return ndsmk_note_error(NDSMK_EVALUE, "green_ap_plane: at least 2 source nodes per axis and spacings > 0");
+  Targets g = {};
+  g.gen = GEN_PLANE;
+  g.nc = 2;
+  g.count = (i64)nsrc2[0] * nsrc2[1];
+  g.nx = nsrc2[0];
+  g.ny = nsrc2[1];
+  return run(nsrc2, h_xs, h_ys, 0.0, bz, nullptr, g, nullptr, nullptr, nullptr, nullptr, Ap);
 }

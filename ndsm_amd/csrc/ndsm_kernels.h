@@ -282,6 +282,27 @@ int ndsmk_lfff_points(const int32_t *nsrc2, const double *h_xs, const double *h_
 int ndsmk_lfff_box(const int32_t *nsrc2, const double *h_xs, const double *h_ys, double zs, const double *bz,
                    double alpha, const int32_t *n3, const double *h_x, const double *h_y, const double *h_z, int which,
                    double *B);
+/* The potential field's vector potential on the plane of the magnetogram (green.hip; semantics: include/ndsm_hip.h,
+ * ndsm_hip_green_ap_points): the third pair term of the same all-pairs sum.  green_ap_points: Ap (2,npts) at pts
+ * (2,npts); green_ap_plane: Ap (nsx,nsy,2) on the source's own nodes; bz, pts and Ap DEVICE arrays.  9004 for a source
+ * axis < 2, a spacing not > 0, npts < 0; npts = 0 touches nothing.  Both return when Ap is complete; the chunks, the
+ * scratch and ndsmk_green_fits are shared. */
+int ndsmk_green_ap_points(const int32_t *nsrc2, const double *h_xs, const double *h_ys, const double *bz, int npts,
+                          const double *pts, double *Ap);
+int ndsmk_green_ap_plane(const int32_t *nsrc2, const double *h_xs, const double *h_ys, const double *bz, double *Ap);
+
+/* Flows from two magnetograms and the boundary fluxes (flow.hip; semantics: include/ndsm_hip.h, ndsm_hip_flow_fit and
+ * ndsm_hip_flow_flux).  flow_fit: B0, B1, V (nsx,nsy,3), coef (nsx,nsy,9), status (nsx,nsy; int32) DEVICE arrays; 9004
+ * for an axis < 3, a spacing not > 0, dt not finite or 0, r outside 1..16, rcond outside [0, 1).  Returns when the
+ * outputs are complete; seven planes of scratch are kept between calls and grown on demand.  flow_flux: B, V
+ * (nsx,nsy,3), Ap (nsx,nsy,2), dens (nsx,nsy,4) DEVICE arrays, h_out8 on the HOST; 9004 for an axis < 2 or a spacing
+ * not > 0; blocking, one read of the sums.  flow_fits: 0, or 9001 when caller_bytes plus (fit = 1) the fit's scratch exceed
+ * the device's memory. */
+int ndsmk_flow_fits(const int32_t *nsrc2, int fit, double caller_bytes);
+int ndsmk_flow_fit(const int32_t *nsrc2, const double *h_xs, const double *h_ys, const double *B0, const double *B1,
+                   double dt, int r, double rcond, double *V, double *coef, int32_t *status);
+int ndsmk_flow_flux(const int32_t *nsrc2, const double *h_xs, const double *h_ys, const double *B, const double *V,
+                    const double *Ap, double *dens, double *h_out8);
 
 /* Magnetogram preprocessing (preprocess.hip; semantics: include/ndsm_hip.h, ndsm_hip_vecpot_preprocess).  B0, B1
  * (nx,ny,3): the two field buffers, B0 holds the start; La (nx,ny,3,2): the two Lambda buffers; obs (nx,ny,3): the

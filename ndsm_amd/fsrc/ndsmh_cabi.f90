@@ -1615,6 +1615,202 @@ contains
                        "ndsm_hip_lfff_box_device", .true., alpha)
   end function
 
+  ! ---- Flows from two magnetograms, the plane's vector potential and the boundary fluxes (include/ndsm_hip.h) ----
+  ! No handle; the mesh vectors stay on the host in both forms.  B0, B1 (nsx,nsy,3) in; V (nsx,nsy,3), coef (nsx,nsy,9)
+  ! and status (nsx,nsy; int32) out.  HOST arrays
+  function ndsm_hip_flow_fit(nsrc, xs, ys, B0, B1, dt, r, rcond, V, coef, status) bind(c, name="ndsm_hip_flow_fit") &
+      result(ierr)
+    type(c_ptr), value :: nsrc, xs, ys, B0, B1, V, coef, status
+    real(c_double), value :: dt, rcond
+    integer(c_int), value :: r
+    integer(c_int) :: ierr
+    ierr = flow_entry(1, nsrc, xs, ys, [B0, B1, c_null_ptr], [V, coef, status], dt, r, rcond, 0_c_int, c_null_ptr, &
+                      .false., "ndsm_hip_flow_fit")
+  end function
+
+  ! the same with B0, B1, V, coef and status DEVICE arrays of the library's GPU
+  function ndsm_hip_flow_fit_device(nsrc, xs, ys, dB0, dB1, dt, r, rcond, dV, dcoef, dstatus) &
+      bind(c, name="ndsm_hip_flow_fit_device") result(ierr)
+    type(c_ptr), value :: nsrc, xs, ys, dB0, dB1, dV, dcoef, dstatus
+    real(c_double), value :: dt, rcond
+    integer(c_int), value :: r
+    integer(c_int) :: ierr
+    ierr = flow_entry(1, nsrc, xs, ys, [dB0, dB1, c_null_ptr], [dV, dcoef, dstatus], dt, r, rcond, 0_c_int, &
+                      c_null_ptr, .true., "ndsm_hip_flow_fit_device")
+  end function
+
+  ! B, V (nsx,nsy,3), Ap (nsx,nsy,2) in; dens (nsx,nsy,4) out; out (8) on the HOST in both forms.  HOST arrays
+  function ndsm_hip_flow_flux(nsrc, xs, ys, B, V, Ap, dens, out) bind(c, name="ndsm_hip_flow_flux") result(ierr)
+    type(c_ptr), value :: nsrc, xs, ys, B, V, Ap, dens, out
+    integer(c_int) :: ierr
+    ierr = flow_entry(2, nsrc, xs, ys, [B, V, Ap], [dens, c_null_ptr, c_null_ptr], 0.0_c_double, 0_c_int, &
+                      0.0_c_double, 0_c_int, out, .false., "ndsm_hip_flow_flux")
+  end function
+
+  ! the same with B, V, Ap and dens DEVICE arrays of the library's GPU
+  function ndsm_hip_flow_flux_device(nsrc, xs, ys, dB, dV, dAp, ddens, out) bind(c, name="ndsm_hip_flow_flux_device") &
+      result(ierr)
+    type(c_ptr), value :: nsrc, xs, ys, dB, dV, dAp, ddens, out
+    integer(c_int) :: ierr
+    ierr = flow_entry(2, nsrc, xs, ys, [dB, dV, dAp], [ddens, c_null_ptr, c_null_ptr], 0.0_c_double, 0_c_int, &
+                      0.0_c_double, 0_c_int, out, .true., "ndsm_hip_flow_flux_device")
+  end function
+
+  ! bz (nsx,nsy) in; Ap (nsx,nsy,2) on the source's own nodes out.  HOST arrays
+  function ndsm_hip_green_ap_plane(nsrc, xs, ys, bz, Ap) bind(c, name="ndsm_hip_green_ap_plane") result(ierr)
+    type(c_ptr), value :: nsrc, xs, ys, bz, Ap
+    integer(c_int) :: ierr
+    ierr = flow_entry(3, nsrc, xs, ys, [bz, c_null_ptr, c_null_ptr], [Ap, c_null_ptr, c_null_ptr], 0.0_c_double, &
+                      0_c_int, 0.0_c_double, 0_c_int, c_null_ptr, .false., "ndsm_hip_green_ap_plane")
+  end function
+
+  ! the same with bz and Ap DEVICE arrays of the library's GPU
+  function ndsm_hip_green_ap_plane_device(nsrc, xs, ys, dbz, dAp) bind(c, name="ndsm_hip_green_ap_plane_device") &
+      result(ierr)
+    type(c_ptr), value :: nsrc, xs, ys, dbz, dAp
+    integer(c_int) :: ierr
+    ierr = flow_entry(3, nsrc, xs, ys, [dbz, c_null_ptr, c_null_ptr], [dAp, c_null_ptr, c_null_ptr], 0.0_c_double, &
+                      0_c_int, 0.0_c_double, 0_c_int, c_null_ptr, .true., "ndsm_hip_green_ap_plane_device")
+  end function
+
+  ! bz (nsx,nsy) and pts (2,npts) in; Ap (2,npts) out.  HOST arrays
+  function ndsm_hip_green_ap_points(nsrc, xs, ys, bz, npts, pts, Ap) bind(c, name="ndsm_hip_green_ap_points") &
+      result(ierr)
+    type(c_ptr), value :: nsrc, xs, ys, bz, pts, Ap
+    integer(c_int), value :: npts
+    integer(c_int) :: ierr
+    ierr = flow_entry(4, nsrc, xs, ys, [bz, pts, c_null_ptr], [Ap, c_null_ptr, c_null_ptr], 0.0_c_double, 0_c_int, &
+                      0.0_c_double, npts, c_null_ptr, .false., "ndsm_hip_green_ap_points")
+  end function
+
+  ! the same with bz, pts and Ap DEVICE arrays of the library's GPU
+  function ndsm_hip_green_ap_points_device(nsrc, xs, ys, dbz, npts, dpts, dAp) &
+      bind(c, name="ndsm_hip_green_ap_points_device") result(ierr)
+    type(c_ptr), value :: nsrc, xs, ys, dbz, dpts, dAp
+    integer(c_int), value :: npts
+    integer(c_int) :: ierr
+    ierr = flow_entry(4, nsrc, xs, ys, [dbz, dpts, c_null_ptr], [dAp, c_null_ptr, c_null_ptr], 0.0_c_double, 0_c_int, &
+                      0.0_c_double, npts, c_null_ptr, .true., "ndsm_hip_green_ap_points_device")
+  end function
+
+  ! The eight entries above.  kind 1: the fit, 2: the fluxes, 3: the vector potential on the source's nodes, 4: at
+  ! points.  pin, pout: the arrays a kind reads and writes, in the order of its launcher; the host forms stage them in
+  ! one allocation and copy the outputs back, the device forms pass them on.  In this order: 9001 without a GPU; 9001
+  ! from the memory screen as soon as the shapes can be read; 9002; 9004; nothing is written before the launch.
+  function flow_entry(kind, nsrc, xs, ys, pin, pout, dt, r, rcond, npts, out8, on_device, who) result(ierr)
+    integer, intent(in) :: kind
+    type(c_ptr), intent(in) :: nsrc, xs, ys, pin(3), pout(3), out8
+    real(c_double), intent(in) :: dt, rcond
+    integer(c_int), intent(in) :: r, npts
+    logical, intent(in) :: on_device
+    character(len=*), intent(in) :: who
+    integer(c_int) :: ierr
+    integer(c_int), pointer :: ns(:)
+    integer(c_int32_t) :: ns2(2)
+    integer :: nin, nout, i, d
+    real(c_double) :: bin(3), bout(3), npix, total
+    integer(c_size_t) :: off(6), at
+    type(c_ptr) :: buf, din(3), dout(3)
+    integer(c_int) :: rc
+    ierr = ndsmk_init(-1_c_int)
+    if (ierr /= 0) return
+    nin = merge(2, merge(3, merge(1, 2, kind == 3), kind == 2), kind == 1)
+    nout = merge(3, 1, kind == 1)
+    bin = 0.0_c_double; bout = 0.0_c_double
+    ! a call the device cannot hold is refused before anything is allocated - as soon as its shapes can be read
+    if (c_associated(nsrc)) then
+      call c_f_pointer(nsrc, ns, [2])
+      ns2 = ns
+      if (all(ns2 >= 1) .and. npts >= 0) then
+        npix = product(real(ns2, c_double))            ! (in doubles: past the screen the sizes fit whole numbers)
+        select case (kind)
+        case (1); bin(1:2) = 24.0_c_double * npix; bout = [24.0_c_double, 72.0_c_double, 4.0_c_double] * npix
+        case (2); bin = [24.0_c_double, 24.0_c_double, 16.0_c_double] * npix; bout(1) = 32.0_c_double * npix
+        case (3); bin(1) = 8.0_c_double * npix; bout(1) = 16.0_c_double * npix
+        case default
+          bin(1) = 8.0_c_double * npix; bin(2) = 16.0_c_double * real(npts, c_double)
+          bout(1) = 16.0_c_double * real(npts, c_double)
+        end select
+        total = merge(0.0_c_double, sum(bin) + sum(bout), on_device)
+        if (kind <= 2) then
+          ierr = ndsmk_flow_fits(ns2, merge(1_c_int, 0_c_int, kind == 1), total)
+        else
+          ierr = ndsmk_green_fits(ns2, c_null_ptr, 1_c_int, &
+                                  merge(int(npts, c_long_long), int(npix, c_long_long), kind == 4), total)
+        end if
+        if (ierr /= 0) return
+      end if
+    end if
+    ierr = NDSMK_EARG
+    if (.not. (c_associated(nsrc) .and. c_associated(xs) .and. c_associated(ys) .and. c_associated(pin(1)))) return
+    if (kind /= 4) then
+      do i = 1, nin
+        if (.not. c_associated(pin(i))) return
+      end do
+      do i = 1, nout
+        if (.not. c_associated(pout(i))) return
+      end do
+    end if
+    if (kind == 2 .and. .not. c_associated(out8)) return
+    ierr = green_source_ok(ns, xs, ys)
+    if (ierr == 0 .and. npts < 0) ierr = NDSMK_EVALUE
+    if (ierr == 0 .and. kind == 1) then
+      if (any(ns < 3) .or. .not. (abs(dt) <= huge(dt)) .or. dt == 0.0_c_double .or. r < 1 .or. r > 16 .or. &
+          .not. (rcond >= 0.0_c_double .and. rcond < 1.0_c_double)) ierr = NDSMK_EVALUE       ! (a NaN fails them too)
+    end if
+    if (ierr /= 0) then
+      ierr = ndsmk_note_error(NDSMK_EVALUE, "flow: at least 2 nodes per axis (the fit: 3), spacings > 0, npts >= 0, "// &
+                              "(the fit) a finite dt /= 0, 1 <= r <= 16 and 0 <= rcond < 1"//c_null_char)
+      return
+    end if
+    if (kind == 4) then
+      if (npts == 0) return
+      ierr = NDSMK_EARG
+      if (.not. (c_associated(pin(2)) .and. c_associated(pout(1)))) return
+    end if
+    if (on_device) then
+      rc = launch(pin, pout)
+    else
+      at = 0
+      do i = 1, nin
+        off(i) = at; at = at + int(bin(i), c_size_t)
+      end do
+      do i = 1, nout
+        off(3 + i) = at; at = at + int(bout(i), c_size_t)
+      end do
+      buf = c_null_ptr
+      din = c_null_ptr; dout = c_null_ptr
+      rc = ndsmk_alloc(buf, at)
+      if (rc == 0) then
+        do i = 1, nin
+          din(i) = dptr_offset(buf, off(i))
+          if (rc == 0) rc = ndsmk_h2d(din(i), pin(i), int(bin(i), c_size_t))
+        end do
+        do i = 1, nout
+          dout(i) = dptr_offset(buf, off(3 + i))
+        end do
+        if (rc == 0) rc = launch(din, dout)
+        do i = 1, nout
+          if (rc == 0) rc = ndsmk_d2h(pout(i), dout(i), int(bout(i), c_size_t))
+        end do
+        d = ndsmk_free(buf)
+        if (rc == 0) rc = int(d, c_int)
+      end if
+    end if
+    ierr = reported(who, rc)
+  contains
+    function launch(a, b) result(lrc)
+      type(c_ptr), intent(in) :: a(3), b(3)
+      integer(c_int) :: lrc
+      select case (kind)
+      case (1); lrc = ndsmk_flow_fit(ns2, xs, ys, a(1), a(2), dt, r, rcond, b(1), b(2), b(3))
+      case (2); lrc = ndsmk_flow_flux(ns2, xs, ys, a(1), a(2), a(3), b(1), out8)
+      case (3); lrc = ndsmk_green_ap_plane(ns2, xs, ys, a(1), b(1))
+      case default; lrc = ndsmk_green_ap_points(ns2, xs, ys, a(1), npts, a(2), b(1))
+      end select
+    end function
+  end function
+
   ! The open-box potential field: ndsm_hip_green_box_device (which = 0) on the handle's mesh into the device B, then
   ! ndsm_hip_vecpot_solve_device - bit for bit that composition, no field crossing PCIe in between.  A: in the first
   ! guess, out A; B: out (its interior nodes are read by nothing).  HOST arrays (nx,ny,nz,3), bz (nsx,nsy)

@@ -730,6 +730,44 @@ module ndsmh_iface
       integer(c_int), value :: which
       integer(c_int) :: rc
     end function
+    ! the plane's vector potential of the same source: the third pair term
+    function ndsmk_green_ap_points(nsrc2, h_xs, h_ys, bz, npts, pts, Ap) bind(c, name="ndsmk_green_ap_points") &
+        result(rc)
+      import :: c_ptr, c_int, c_int32_t
+      integer(c_int32_t), intent(in) :: nsrc2(2)
+      type(c_ptr), value :: h_xs, h_ys, bz, pts, Ap
+      integer(c_int), value :: npts
+      integer(c_int) :: rc
+    end function
+    function ndsmk_green_ap_plane(nsrc2, h_xs, h_ys, bz, Ap) bind(c, name="ndsmk_green_ap_plane") result(rc)
+      import :: c_ptr, c_int, c_int32_t
+      integer(c_int32_t), intent(in) :: nsrc2(2)
+      type(c_ptr), value :: h_xs, h_ys, bz, Ap
+      integer(c_int) :: rc
+    end function
+    ! ---- flows from two magnetograms and the boundary fluxes (flow.hip) ----
+    function ndsmk_flow_fits(nsrc2, fit, caller_bytes) bind(c, name="ndsmk_flow_fits") result(rc)
+      import :: c_int, c_int32_t, c_double
+      integer(c_int32_t), intent(in) :: nsrc2(2)
+      integer(c_int), value :: fit
+      real(c_double), value :: caller_bytes
+      integer(c_int) :: rc
+    end function
+    function ndsmk_flow_fit(nsrc2, h_xs, h_ys, B0, B1, dt, r, rcond, V, coef, status) &
+        bind(c, name="ndsmk_flow_fit") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_double
+      integer(c_int32_t), intent(in) :: nsrc2(2)
+      type(c_ptr), value :: h_xs, h_ys, B0, B1, V, coef, status
+      real(c_double), value :: dt, rcond
+      integer(c_int), value :: r
+      integer(c_int) :: rc
+    end function
+    function ndsmk_flow_flux(nsrc2, h_xs, h_ys, B, V, Ap, dens, out8) bind(c, name="ndsmk_flow_flux") result(rc)
+      import :: c_ptr, c_int, c_int32_t
+      integer(c_int32_t), intent(in) :: nsrc2(2)
+      type(c_ptr), value :: h_xs, h_ys, B, V, Ap, dens, out8
+      integer(c_int) :: rc
+    end function
     ! ---- magnetogram preprocessing (preprocess.hip) ----
     function ndsmk_preprocess_work_bytes() bind(c, name="ndsmk_preprocess_work_bytes") result(nb)
       import :: c_size_t

@@ -2163,27 +2163,69 @@ def _staged(L, host_arrays, call):
     return rc
 
 
+def _lfff_alpha(alpha):
+    """alpha as a finite float; ValueError for what the library would answer with 9004"""
+    try:
+        a = np.asarray(alpha, dtype=np.float64)
+    except (TypeError, ValueError):
+        a = np.zeros(2)
+    if a.ndim != 0 or not np.isfinite(a):
+        raise ValueError(f"alpha must be one finite number, not {alpha!r}")
+    return float(a)
+
+
+def _field_points(kind, xs, ys, zs, bz, alpha, pts, device, lib):
+    """green_field_points (kind "green", alpha unused) and lfff_field_points (kind "lfff"): B (npts,3) from
+    ndsm_hip_<kind>_points or, for device=True, its _device form on staged arrays"""
+    P = np.asarray(pts, dtype=np.float64)
+    if P.ndim != 2 or P.shape[1] != 3:
+        raise ValueError(f"pts of shape {P.shape}, (npts, 3) is needed")
+    mid = (_lfff_alpha(alpha),) if kind == "lfff" else ()
+    ns2, qx, qy, zs, S = _green_source(None, None, None, bz, xs, ys, zs)
+    L = lib or load_library()
+    P = np.ascontiguousarray(P).reshape(-1).copy()
+    B = np.zeros(P.size)
+    head = (ns2.ctypes.data_as(_ip), _d(qx), _d(qy), zs)
+    name = f"ndsm_hip_{kind}_points" + ("_device" if device else "")
+    fn = getattr(L, name)
+    if not device:
+        _check(fn(*head, S.ctypes.data, *mid, len(P) // 3, P.ctypes.data, B.ctypes.data), name, L)
+    else:
+        _check(_staged(L, [S, P, B], lambda dS, dP, dB: fn(*head, dS, *mid, len(P) // 3, dP, dB)), name, L)
+    return B.reshape(-1, 3)
+
+
+def _field_box(kind, x, y, z, bz, alpha, xs, ys, zs, which, device, lib):
+    """magnetogram_field (kind "green", alpha unused) and linear_force_free_field (kind "lfff"): b (3,nz,ny,nx) from
+    ndsm_hip_<kind>_box or, for device=True, its _device form on staged arrays"""
+    if which not in GREEN_WHICH:
+        raise ValueError(f"which must be 'faces' or 'volume', not {which!r}")
+    mid = (_lfff_alpha(alpha),) if kind == "lfff" else ()
+    qx, qy, qz = (_f64(v).reshape(-1) for v in (x, y, z))
+    if min(len(qx), len(qy), len(qz)) < 2:
+        raise ValueError(f"the box needs at least 2 nodes per axis, not {(len(qz), len(qy), len(qx))}")
+    ns2, sx, sy, zs, S = _green_source(qx, qy, qz, bz, xs, ys, zs)
+    L = lib or load_library()
+    n3 = np.array([len(qx), len(qy), len(qz)], dtype=np.intc)
+    B = np.zeros(3 * len(qx) * len(qy) * len(qz))
+    head = (ns2.ctypes.data_as(_ip), _d(sx), _d(sy), zs)
+    tail = (n3.ctypes.data_as(_ip), _d(qx), _d(qy), _d(qz), GREEN_WHICH[which])
+    name = f"ndsm_hip_{kind}_box" + ("_device" if device else "")
+    fn = getattr(L, name)
+    if not device:
+        _check(fn(*head, S.ctypes.data, *mid, *tail, B.ctypes.data), name, L)
+    else:
+        _check(_staged(L, [S, B], lambda dS, dB: fn(*head, dS, *mid, *tail, dB)), name, L)
+    return B.reshape(3, len(qz), len(qy), len(qx))
+
+
 def green_field_points(xs, ys, zs, bz, pts, device=False, lib=None):
     """The Green's-function field of the half space above the magnetogram bz (nsy,nsx) - given on the uniform mesh
     xs, ys at height zs - at the points pts (npts,3; x, y, z), on the device (semantics: include/ndsm_hip.h,
     ndsm_hip_green_points).  Returns B (npts,3).  Below the plane the field is NaN; on it Bz is the bilinear
     interpolation of bz (0 outside the mesh).  device=True: the arrays are staged in device memory and the
     device-resident entry point runs."""
-    P = np.asarray(pts, dtype=np.float64)
-    if P.ndim != 2 or P.shape[1] != 3:
-        raise ValueError(f"pts of shape {P.shape}, (npts, 3) is needed")
-    ns2, qx, qy, zs, S = _green_source(None, None, None, bz, xs, ys, zs)
-    L = lib or load_library()
-    P = np.ascontiguousarray(P).reshape(-1).copy()
-    B = np.zeros(P.size)
-    head = (ns2.ctypes.data_as(_ip), _d(qx), _d(qy), zs)
-    if not device:
-        _check(L.ndsm_hip_green_points(*head, S.ctypes.data, len(P) // 3, P.ctypes.data, B.ctypes.data),
-               "ndsm_hip_green_points", L)
-    else:
-        _check(_staged(L, [S, P, B], lambda dS, dP, dB: L.ndsm_hip_green_points_device(*head, dS, len(P) // 3, dP, dB)),
-               "ndsm_hip_green_points_device", L)
-    return B.reshape(-1, 3)
+    return _field_points("green", xs, ys, zs, bz, None, pts, device, lib)
 
 
 def magnetogram_field(x, y, z, bz, xs=None, ys=None, zs=None, which="faces", device=False, lib=None):
@@ -2196,34 +2238,7 @@ def magnetogram_field(x, y, z, bz, xs=None, ys=None, zs=None, which="faces", dev
     ys (xs[i0:i0 + nx]): a box node on the plane must be a source node bit for bit - the rule leaves that pixel out -
     or lie well away from every source node; a miss by a rounding error gives a term of the order 1 / eps^2.
     device=True: the arrays are staged in device memory and the device-resident entry point runs."""
-    if which not in GREEN_WHICH:
-        raise ValueError(f"which must be 'faces' or 'volume', not {which!r}")
-    qx, qy, qz = (_f64(v).reshape(-1) for v in (x, y, z))
-    if min(len(qx), len(qy), len(qz)) < 2:
-        raise ValueError(f"the box needs at least 2 nodes per axis, not {(len(qz), len(qy), len(qx))}")
-    ns2, sx, sy, zs, S = _green_source(qx, qy, qz, bz, xs, ys, zs)
-    L = lib or load_library()
-    n3 = np.array([len(qx), len(qy), len(qz)], dtype=np.intc)
-    B = np.zeros(3 * len(qx) * len(qy) * len(qz))
-    head = (ns2.ctypes.data_as(_ip), _d(sx), _d(sy), zs)
-    tail = (n3.ctypes.data_as(_ip), _d(qx), _d(qy), _d(qz), GREEN_WHICH[which])
-    if not device:
-        _check(L.ndsm_hip_green_box(*head, S.ctypes.data, *tail, B.ctypes.data), "ndsm_hip_green_box", L)
-    else:
-        _check(_staged(L, [S, B], lambda dS, dB: L.ndsm_hip_green_box_device(*head, dS, *tail, dB)),
-               "ndsm_hip_green_box_device", L)
-    return B.reshape(3, len(qz), len(qy), len(qx))
-
-
-def _lfff_alpha(alpha):
-    """alpha as a finite float; ValueError for what the library would answer with 9004"""
-    try:
-        a = np.asarray(alpha, dtype=np.float64)
-    except (TypeError, ValueError):
-        a = np.zeros(2)
-    if a.ndim != 0 or not np.isfinite(a):
-        raise ValueError(f"alpha must be one finite number, not {alpha!r}")
-    return float(a)
+    return _field_box("green", x, y, z, bz, None, xs, ys, zs, which, device, lib)
 
 
 def lfff_field_points(xs, ys, zs, bz, alpha, pts, device=False, lib=None):
@@ -2233,23 +2248,7 @@ def lfff_field_points(xs, ys, zs, bz, alpha, pts, device=False, lib=None):
     1 / (length unit of the mesh), e.g. best_alpha()'s.  Returns B (npts,3); the plane rules are green_field_points',
     and alpha = 0 gives its bits.  device=True: the arrays are staged in device memory and the device-resident entry
     point runs."""
-    P = np.asarray(pts, dtype=np.float64)
-    if P.ndim != 2 or P.shape[1] != 3:
-        raise ValueError(f"pts of shape {P.shape}, (npts, 3) is needed")
-    alpha = _lfff_alpha(alpha)
-    ns2, qx, qy, zs, S = _green_source(None, None, None, bz, xs, ys, zs)
-    L = lib or load_library()
-    P = np.ascontiguousarray(P).reshape(-1).copy()
-    B = np.zeros(P.size)
-    head = (ns2.ctypes.data_as(_ip), _d(qx), _d(qy), zs)
-    if not device:
-        _check(L.ndsm_hip_lfff_points(*head, S.ctypes.data, alpha, len(P) // 3, P.ctypes.data, B.ctypes.data),
-               "ndsm_hip_lfff_points", L)
-    else:
-        _check(_staged(L, [S, P, B],
-                       lambda dS, dP, dB: L.ndsm_hip_lfff_points_device(*head, dS, alpha, len(P) // 3, dP, dB)),
-               "ndsm_hip_lfff_points_device", L)
-    return B.reshape(-1, 3)
+    return _field_points("lfff", xs, ys, zs, bz, alpha, pts, device, lib)
 
 
 def linear_force_free_field(x, y, z, bz, alpha, xs=None, ys=None, zs=None, which="volume", device=False, lib=None):
@@ -2260,24 +2259,7 @@ def linear_force_free_field(x, y, z, bz, alpha, xs=None, ys=None, zs=None, which
     ys: a box node must lie on the vertical through a source node bit for bit, or well away from it, at every
     height - a miss by a rounding error costs digits of the order eps z^2 / R^2.  The field depends on the
     magnetogram's width more than the potential field does (its horizontal part falls like 1 / R)."""
-    if which not in GREEN_WHICH:
-        raise ValueError(f"which must be 'faces' or 'volume', not {which!r}")
-    alpha = _lfff_alpha(alpha)
-    qx, qy, qz = (_f64(v).reshape(-1) for v in (x, y, z))
-    if min(len(qx), len(qy), len(qz)) < 2:
-        raise ValueError(f"the box needs at least 2 nodes per axis, not {(len(qz), len(qy), len(qx))}")
-    ns2, sx, sy, zs, S = _green_source(qx, qy, qz, bz, xs, ys, zs)
-    L = lib or load_library()
-    n3 = np.array([len(qx), len(qy), len(qz)], dtype=np.intc)
-    B = np.zeros(3 * len(qx) * len(qy) * len(qz))
-    head = (ns2.ctypes.data_as(_ip), _d(sx), _d(sy), zs)
-    tail = (n3.ctypes.data_as(_ip), _d(qx), _d(qy), _d(qz), GREEN_WHICH[which])
-    if not device:
-        _check(L.ndsm_hip_lfff_box(*head, S.ctypes.data, alpha, *tail, B.ctypes.data), "ndsm_hip_lfff_box", L)
-    else:
-        _check(_staged(L, [S, B], lambda dS, dB: L.ndsm_hip_lfff_box_device(*head, dS, alpha, *tail, dB)),
-               "ndsm_hip_lfff_box_device", L)
-    return B.reshape(3, len(qz), len(qy), len(qx))
+    return _field_box("lfff", x, y, z, bz, alpha, xs, ys, zs, which, device, lib)
 
 
 def best_alpha(x, y, b, bz_min=0.0):

@@ -1,31 +1,35 @@
-// Green's-function field of the half space above a magnetogram (DESIGN.md "Open-box potential field"; semantics:
-// include/ndsm_hip.h, ndsm_hip_green_points): an all-pairs sum of targets times magnetogram pixels.
+// Green's-function sums of the half space above a magnetogram (DESIGN.md "Open-box potential field"; semantics:
+// include/ndsm_hip.h, ndsm_hip_green_points): all-pairs sums of targets times magnetogram pixels.
 //
-//   green_k : the classic all-pairs form.  A block of 256 threads owns 256 targets, one per thread, with X, Y, w and
-//             the three sums in registers.  blockIdx.y is the slice of the pixels (the order of the sum is a function
-//             of npix alone: NS = min(64, ceil(npix / 4096)) slices of len = ceil(npix / NS) pixels).  The slice goes
-//             through LDS in tiles of 256 pixels: thread l stages pixel p = tile + l as xs[p mod nsx], ys[p div nsx]
-//             and q = bz[p] c, and every lane then reads the same address (a broadcast, no bank conflict) pixel after
-//             pixel, so the terms are added left to right.  The three slice sums go to scratch (NS, 3, chunk).
-//   lfff_k  : the same layout for the constant-alpha field (semantics: include/ndsm_hip.h, ndsm_hip_lfff_points): the
-//             pair term of Chiu & Hilton's half-space solution.  sin(alpha w) and cos(alpha w) are per target and stay
-//             in registers with X, Y, w, ww and the sums; a pair costs one sqrt, four divisions and one sincos.
-//   ap_k    : the same layout for the potential field's vector potential ON the plane (semantics: include/ndsm_hip.h,
-//             ndsm_hip_green_ap_points): targets (X, Y), two sums, and a pair term without a square root - one
-//             division.
+//   pairs_k<Term> : the classic all-pairs form.  A block of 256 threads owns 256 targets, one per thread, with X, Y and
+//             the term - what is per target, and the sums - in registers.  blockIdx.y is the slice of the pixels (the
+//             order of the sum is a function of npix alone: NS = min(64, ceil(npix / 4096)) slices of
+//             len = ceil(npix / NS) pixels).  The slice goes through LDS in tiles of 256 pixels: thread l stages pixel
+//             p = tile + l as xs[p mod nsx], ys[p div nsx] and q = bz[p] c, and every lane then reads the same address
+//             (a broadcast, no bank conflict) pixel after pixel, so the terms are added left to right.  The Term::nc
+//             slice sums go to scratch (NS, nc, chunk).
 //   fold_k  : one thread per target adds the slice sums in ascending order, starting from slice 0's, applies the rules
-//             of the plane (w < 0: NaN; w == 0: Bz is the bilinear interpolation of bz; neither for ap_k's two sums)
+//             of the plane (w < 0: NaN; w == 0: Bz is the bilinear interpolation of bz; neither for ApTerm's two sums)
 //             and writes the target's components where its generator says.
 //
-// Three target generators share green_k and lfff_k: a point list (3,npts), the face nodes of a box mesh and all nodes
-// of a box mesh; two more serve ap_k: a point list (2,npts) and the source's own nodes.  Targets are processed in chunks of at most 262144, which keeps the scratch at 384 MiB or less; a target's
-// sums depend on nothing but the target and the source, so the chunking and the generator leave no trace in the bits.
+// The pair terms, each one add(dx, dy, q) in the header's operand order:
+//   GreenTerm : the potential field, three sums; a pair costs one sqrt and one division.
+//   LfffTerm  : the constant-alpha field (ndsm_hip_lfff_points), Chiu & Hilton's half-space solution, three sums.
+//             sin(alpha w) and cos(alpha w) are per target; a pair costs one sqrt, four divisions and one sincos.
+//   ApTerm    : the potential field's vector potential ON the plane (ndsm_hip_green_ap_points): targets (X, Y), two
+//             sums, no square root - one division.
+//
+// Three target generators serve the two field terms: a point list (3,npts), the face nodes of a box mesh and all nodes
+// of a box mesh; two more serve ApTerm: a point list (2,npts) and the source's own nodes.  Targets are processed in
+// chunks of at most 262144, which keeps the scratch at 384 MiB or less; a target's sums depend on nothing but the
+// target and the source, so the chunking and the generator leave no trace in the bits.
 //
 // Plain C++ under -ffp-contract=off with IEEE division and sqrt: the operand order of the header is the bits, and
 // tests/green_model.py restates it.
 #include "common.hpp"
 
 #include <cmath>
+#include <cstdio>
 
 namespace {
 
@@ -129,114 +133,69 @@ __device__ __forceinline__ void target_of(const Targets &g, i64 t, double &X, do
   stride = (size_t)plane * (size_t)g.nz;
 }
 
-// part[(s * 3 + c) * cnt + (t - t0)]: slice s's sum of component c for the targets t0 .. t0 + cnt - 1
-__global__ __launch_bounds__(kBlock) void green_k(Source s, Targets g, i64 t0, i64 cnt, double *__restrict__ part) {
-  __shared__ double lx[kBlock], ly[kBlock], lq[kBlock];
-  const int l = threadIdx.x;
-  const i64 lt = (i64)blockIdx.x * kBlock + l;
-  const bool live = lt < cnt;
-  double X = 0.0, Y = 0.0, Z = 0.0;
-  if (live) {
-    size_t at, stride;
-    target_of(g, t0 + lt, X, Y, Z, at, stride);
-  }
-  const double w = Z - s.zs, ww = w * w;
-  double ax = 0.0, ay = 0.0, az = 0.0;
-  const i64 p0 = (i64)blockIdx.y * s.len;
-  const i64 p1 = p0 + s.len < s.npix ? p0 + s.len : s.npix;
-  for (i64 tile = p0; tile < p1; tile += kBlock) {
-    const i64 p = tile + l;
-    if (p < p1) {
-      const i64 j = p / s.nsx;
-      lx[l] = s.xs[p - j * s.nsx];
-      ly[l] = s.ys[j];
-      lq[l] = s.bz[p] * s.c;
+// The pair terms.  Term(w, alpha) sets up what is per target (w = Z - zs), add(dx, dy, q) adds one pixel's term to the
+// sums a[0 .. nc - 1]: q = bz c of the pixel, (dx, dy) from the pixel to the target.
+struct GreenTerm {
+  static constexpr int nc = 3;
+  double w, ww, a[nc];
+  __device__ __forceinline__ GreenTerm(double w_, double) : w(w_), ww(w_ * w_), a{0.0, 0.0, 0.0} {}
+  __device__ __forceinline__ void add(double dx, double dy, double q) {
+    const double r2 = (dx * dx + dy * dy) + ww;
+    if (r2 > 0.0) {
+      const double t = q / (r2 * sqrt(r2));
+      a[0] = a[0] + dx * t;
+      a[1] = a[1] + dy * t;
+      a[2] = a[2] + w * t;
     }
-    __syncthreads();
-    const int m = p1 - tile < kBlock ? (int)(p1 - tile) : kBlock;
-    for (int n = 0; n < m; ++n) {
-      const double dx = X - lx[n], dy = Y - ly[n];
-      const double r2 = (dx * dx + dy * dy) + ww;
-      if (r2 > 0.0) {
-        const double t = lq[n] / (r2 * sqrt(r2));
-        ax = ax + dx * t;
-        ay = ay + dy * t;
-        az = az + w * t;
-      }
-    }
-    __syncthreads();
   }
-  if (live) {
-    double *o = part + (size_t)blockIdx.y * 3 * (size_t)cnt + (size_t)lt;
-    o[0] = ax;
-    o[(size_t)cnt] = ay;
-    o[2 * (size_t)cnt] = az;
-  }
-}
+};
 
-// the same sum with the pair term of the constant-alpha field; green_k above is left as it is, and so are its bits
-__global__ __launch_bounds__(kBlock) void lfff_k(Source s, double alpha, Targets g, i64 t0, i64 cnt,
-                                                 double *__restrict__ part) {
-  __shared__ double lx[kBlock], ly[kBlock], lq[kBlock];
-  const int l = threadIdx.x;
-  const i64 lt = (i64)blockIdx.x * kBlock + l;
-  const bool live = lt < cnt;
-  double X = 0.0, Y = 0.0, Z = 0.0;
-  if (live) {
-    size_t at, stride;
-    target_of(g, t0 + lt, X, Y, Z, at, stride);
-  }
-  const double w = Z - s.zs, ww = w * w;
-  const double aw = alpha * w;
-  const double sz = sin(aw), cz = cos(aw);
-  double ax = 0.0, ay = 0.0, az = 0.0;
-  const i64 p0 = (i64)blockIdx.y * s.len;
-  const i64 p1 = p0 + s.len < s.npix ? p0 + s.len : s.npix;
-  for (i64 tile = p0; tile < p1; tile += kBlock) {
-    const i64 p = tile + l;
-    if (p < p1) {
-      const i64 j = p / s.nsx;
-      lx[l] = s.xs[p - j * s.nsx];
-      ly[l] = s.ys[j];
-      lq[l] = s.bz[p] * s.c;
-    }
-    __syncthreads();
-    const int m = p1 - tile < kBlock ? (int)(p1 - tile) : kBlock;
-    for (int n = 0; n < m; ++n) {
-      const double dx = X - lx[n], dy = Y - ly[n];
-      const double R2 = dx * dx + dy * dy;
-      const double r2 = R2 + ww;
-      if (r2 > 0.0) {
-        const double q = lq[n];
-        const double r = sqrt(r2);
-        const double t = q / (r2 * r);
-        const double ar = alpha * r;
-        double sr, cr;
-        sincos(ar, &sr, &cr);
-        ax = ax + (dx * t) * cr;
-        ay = ay + (dy * t) * cr;
-        az = az + (w * t) * (cr + ar * sr);
-        if (R2 > 0.0) {
-          const double u = alpha * (q / R2);
-          const double e = sz - (ww / r2) * sr;
-          const double f = (w / r) * cr - cz;
-          ax = ax + u * (dx * e + dy * f);
-          ay = ay + u * (dy * e - dx * f);
-        }
+struct LfffTerm {
+  static constexpr int nc = 3;
+  double w, ww, alpha, sz, cz, a[nc];
+  __device__ __forceinline__ LfffTerm(double w_, double alpha_)
+      : w(w_), ww(w_ * w_), alpha(alpha_), sz(sin(alpha_ * w_)), cz(cos(alpha_ * w_)), a{0.0, 0.0, 0.0} {}
+  __device__ __forceinline__ void add(double dx, double dy, double q) {
+    const double R2 = dx * dx + dy * dy;
+    const double r2 = R2 + ww;
+    if (r2 > 0.0) {
+      const double r = sqrt(r2);
+      const double t = q / (r2 * r);
+      const double ar = alpha * r;
+      double sr, cr;
+      sincos(ar, &sr, &cr);
+      a[0] = a[0] + (dx * t) * cr;
+      a[1] = a[1] + (dy * t) * cr;
+      a[2] = a[2] + (w * t) * (cr + ar * sr);
+      if (R2 > 0.0) {
+        const double u = alpha * (q / R2);
+        const double e = sz - (ww / r2) * sr;
+        const double f = (w / r) * cr - cz;
+        a[0] = a[0] + u * (dx * e + dy * f);
+        a[1] = a[1] + u * (dy * e - dx * f);
       }
     }
-    __syncthreads();
   }
-  if (live) {
-    double *o = part + (size_t)blockIdx.y * 3 * (size_t)cnt + (size_t)lt;
-    o[0] = ax;
-    o[(size_t)cnt] = ay;
-    o[2 * (size_t)cnt] = az;
-  }
-}
+};
 
-// the plane's vector potential: part[(s * 2 + c) * cnt + (t - t0)], two sums per target and slice
-__global__ __launch_bounds__(kBlock) void ap_k(Source s, Targets g, i64 t0, i64 cnt, double *__restrict__ part) {
+struct ApTerm {
+  static constexpr int nc = 2;
+  double a[nc];
+  __device__ __forceinline__ ApTerm(double, double) : a{0.0, 0.0} {}
+  __device__ __forceinline__ void add(double dx, double dy, double q) {
+    const double r2 = dx * dx + dy * dy;
+    if (r2 > 0.0) {
+      const double t = q / r2;
+      a[0] = a[0] + (-dy) * t;
+      a[1] = a[1] + dx * t;
+    }
+  }
+};
+
+// part[(s * nc + c) * cnt + (t - t0)]: slice s's sum of component c for the targets t0 .. t0 + cnt - 1
+template <class Term>
+__global__ __launch_bounds__(kBlock) void pairs_k(Source s, double alpha, Targets g, i64 t0, i64 cnt,
+                                                  double *__restrict__ part) {
   __shared__ double lx[kBlock], ly[kBlock], lq[kBlock];
   const int l = threadIdx.x;
   const i64 lt = (i64)blockIdx.x * kBlock + l;
@@ -246,7 +205,7 @@ __global__ __launch_bounds__(kBlock) void ap_k(Source s, Targets g, i64 t0, i64 
     size_t at, stride;
     target_of(g, t0 + lt, X, Y, Z, at, stride);
   }
-  double ax = 0.0, ay = 0.0;
+  Term term(Z - s.zs, alpha);
   const i64 p0 = (i64)blockIdx.y * s.len;
   const i64 p1 = p0 + s.len < s.npix ? p0 + s.len : s.npix;
   for (i64 tile = p0; tile < p1; tile += kBlock) {
@@ -259,21 +218,13 @@ __global__ __launch_bounds__(kBlock) void ap_k(Source s, Targets g, i64 t0, i64 
     }
     __syncthreads();
     const int m = p1 - tile < kBlock ? (int)(p1 - tile) : kBlock;
-    for (int n = 0; n < m; ++n) {
-      const double dx = X - lx[n], dy = Y - ly[n];
-      const double r2 = dx * dx + dy * dy;
-      if (r2 > 0.0) {
-        const double t = lq[n] / r2;
-        ax = ax + (-dy) * t;
-        ay = ay + dx * t;
-      }
-    }
+    for (int n = 0; n < m; ++n) term.add(X - lx[n], Y - ly[n], lq[n]);
     __syncthreads();
   }
   if (live) {
-    double *o = part + (size_t)blockIdx.y * 2 * (size_t)cnt + (size_t)lt;
-    o[0] = ax;
-    o[(size_t)cnt] = ay;
+    double *o = part + (size_t)blockIdx.y * Term::nc * (size_t)cnt + (size_t)lt;
+#pragma unroll
+    for (int c = 0; c < Term::nc; ++c) o[(size_t)c * (size_t)cnt] = term.a[c];
   }
 }
 
@@ -358,10 +309,10 @@ double own_bytes(const int32_t *nsrc2, const int32_t *n3, double ntargets) {
 }
 
 // the shared driver: mesh vectors up, then chunk after chunk the all-pairs launch and the fold.  alpha NULL: the
-// potential field (green_k); else the constant-alpha field (lfff_k).  g.nc == 2: the plane's vector potential (ap_k)
+// potential field (GreenTerm); else the constant-alpha field (LfffTerm).  g.nc == 2: the plane's vector potential
+// (ApTerm)
 int run(const int32_t *nsrc2, const double *h_xs, const double *h_ys, double zs, const double *bz, const double *alpha,
-        Targets g,
-        const int32_t *n3, const double *h_x, const double *h_y, const double *h_z, double *out) {
+        Targets g, const int32_t *n3, const double *h_x, const double *h_y, const double *h_z, double *out) {
   Source s;
   s.nsx = nsrc2[0];
   s.nsy = nsrc2[1];
@@ -395,22 +346,67 @@ int run(const int32_t *nsrc2, const double *h_xs, const double *h_ys, double zs,
     if (rc == 0) rc = ndsmk_h2d(m + n3[0] + n3[1], h_z, 8 * (size_t)n3[2]);
   }
   double *part = d + nmesh;
+  const auto pairs = g.nc == ApTerm::nc ? pairs_k<ApTerm> : alpha ? pairs_k<LfffTerm> : pairs_k<GreenTerm>;
   for (i64 t0 = 0; t0 < g.count && rc == 0; t0 += chunk) {
     const i64 cnt = g.count - t0 < chunk ? g.count - t0 : chunk;
     const unsigned nb = (unsigned)((cnt + kBlock - 1) / kBlock);
-    if (g.nc == 2)
-      hipLaunchKernelGGL(ap_k, dim3(nb, (unsigned)s.nslices), dim3(kBlock), 0, ndsm::stream(), s, g, t0, cnt, part);
-    else if (alpha)
-      hipLaunchKernelGGL(lfff_k, dim3(nb, (unsigned)s.nslices), dim3(kBlock), 0, ndsm::stream(), s, *alpha, g, t0, cnt,
-                         part);
-    else
-      hipLaunchKernelGGL(green_k, dim3(nb, (unsigned)s.nslices), dim3(kBlock), 0, ndsm::stream(), s, g, t0, cnt, part);
+    hipLaunchKernelGGL(pairs, dim3(nb, (unsigned)s.nslices), dim3(kBlock), 0, ndsm::stream(), s, alpha ? *alpha : 0.0,
+                       g, t0, cnt, part);
     hipLaunchKernelGGL(fold_k, dim3(nb), dim3(kBlock), 0, ndsm::stream(), s, g, t0, cnt, part, out);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) rc = ndsm::fail((int)e, hipGetErrorString(e), __FILE__, __LINE__);
   }
   const int rf = ndsmk_free(buf);       // (drains the stream first)
   return rc != 0 ? rc : rf;
+}
+
+// 9004 with the entry's name, what it asks of its arguments and, for an entry that takes one, the finite alpha
+int bad_value(const char *name, const char *needs, const double *alpha) {
+  char msg[256];
+  std::snprintf(msg, sizeof(msg), "%s: %s%s", name, needs, alpha ? ", and a finite alpha" : "");
+  return ndsmk_note_error(NDSMK_EVALUE, msg);
+}
+
+// the point-list entries: gen GEN_POINTS (nc 3) or GEN_POINTS2 (nc 2); alpha NULL or the constant alpha
+int points_entry(const char *name, int gen, int nc, const int32_t *nsrc2, const double *h_xs, const double *h_ys,
+                 double zs, const double *bz, const double *alpha, int npts, const double *pts, double *out) {
+  NDSM_REQUIRE_READY();
+  NDSM_CHECK_ARG(nsrc2 && h_xs && h_ys && bz);
+  if (!source_ok(nsrc2, h_xs, h_ys) || npts < 0 || (alpha && !std::isfinite(*alpha)))
+    return bad_value(name, "at least 2 source nodes per axis, spacings > 0 and npts >= 0", alpha);
+  if (npts == 0) return 0;
+  NDSM_CHECK_ARG(pts && out);
+  Targets g = {};
+  g.gen = gen;
+  g.nc = nc;
+  g.count = npts;
+  g.pts = pts;
+  return run(nsrc2, h_xs, h_ys, zs, bz, alpha, g, nullptr, nullptr, nullptr, nullptr, out);
+}
+
+// the box entries: which = 0 the face nodes (GEN_FACES), which = 1 all nodes (GEN_VOLUME); alpha as above
+int box_entry(const char *name, const int32_t *nsrc2, const double *h_xs, const double *h_ys, double zs,
+              const double *bz, const double *alpha, const int32_t *n3, const double *h_x, const double *h_y,
+              const double *h_z, int which, double *B) {
+  NDSM_REQUIRE_READY();
+  NDSM_CHECK_ARG(nsrc2 && h_xs && h_ys && bz && n3 && h_x && h_y && h_z && B);
+  if (!source_ok(nsrc2, h_xs, h_ys) || (which != 0 && which != 1) || n3[0] < 2 || n3[1] < 2 || n3[2] < 2 ||
+      !(h_z[0] >= zs) || (alpha && !std::isfinite(*alpha)))
+    return bad_value(name, "at least 2 source nodes per axis, spacings > 0, which 0 or 1, at least 2 box nodes per "
+                           "axis and z[0] >= zs", alpha);
+  if (box_targets(n3, which) > kMaxTargets) {
+    char msg[96];
+    std::snprintf(msg, sizeof(msg), "%s: more targets than any device holds", name);
+    return ndsmk_note_error(NDSMK_ENODEV, msg);
+  }
+  Targets g = {};
+  g.gen = which == 0 ? GEN_FACES : GEN_VOLUME;
+  g.nc = 3;
+  g.count = (i64)box_targets(n3, which);      // (exact: whole numbers below 2^53)
+  g.nx = n3[0];
+  g.ny = n3[1];
+  g.nz = n3[2];
+  return run(nsrc2, h_xs, h_ys, zs, bz, alpha, g, n3, h_x, h_y, h_z, B);
 }
 
 }  // namespace
@@ -436,18 +432,7 @@ extern "C" int ndsmk_green_fits(const int32_t *nsrc2, const int32_t *n3, int whi
 // Returns when B is complete.
 extern "C" int ndsmk_green_points(const int32_t *nsrc2, const double *h_xs, const double *h_ys, double zs,
                                   const double *bz, int npts, const double *pts, double *B) {
-  NDSM_REQUIRE_READY();
-  NDSM_CHECK_ARG(nsrc2 && h_xs && h_ys && bz);
-  if (!source_ok(nsrc2, h_xs, h_ys) || npts < 0)
-    return ndsmk_note_error(NDSMK_EVALUE, "green_points: at least 2 source nodes per axis, spacings > 0 and npts >= 0");
-  if (npts == 0) return 0;
-  NDSM_CHECK_ARG(pts && B);
-  Targets g = {};
-  g.gen = GEN_POINTS;
-  g.nc = 3;
-  g.count = npts;
-  g.pts = pts;
-  return run(nsrc2, h_xs, h_ys, zs, bz, nullptr, g, nullptr, nullptr, nullptr, nullptr, B);
+  return points_entry("green_points", GEN_POINTS, 3, nsrc2, h_xs, h_ys, zs, bz, nullptr, npts, pts, B);
 }
 
 // B (nx,ny,nz,3): which = 0 the nodes with an index at either end of an axis (every other node keeps what it holds),
@@ -455,63 +440,21 @@ extern "C" int ndsmk_green_points(const int32_t *nsrc2, const double *h_xs, cons
 extern "C" int ndsmk_green_box(const int32_t *nsrc2, const double *h_xs, const double *h_ys, double zs,
                                const double *bz, const int32_t *n3, const double *h_x, const double *h_y,
                                const double *h_z, int which, double *B) {
-  NDSM_REQUIRE_READY();
-  NDSM_CHECK_ARG(nsrc2 && h_xs && h_ys && bz && n3 && h_x && h_y && h_z && B);
-  if (!source_ok(nsrc2, h_xs, h_ys) || (which != 0 && which != 1) || n3[0] < 2 || n3[1] < 2 || n3[2] < 2 ||
-      !(h_z[0] >= zs))
-    return ndsmk_note_error(NDSMK_EVALUE, "green_box: at least 2 source nodes per axis, spacings > 0, which 0 or 1, "
-                                          "at least 2 box nodes per axis and z[0] >= zs");
-  if (box_targets(n3, which) > kMaxTargets)
-    return ndsmk_note_error(NDSMK_ENODEV, "green_box: more targets than any device holds");
-  Targets g = {};
-  g.gen = which == 0 ? GEN_FACES : GEN_VOLUME;
-  g.nc = 3;
-  g.count = (i64)box_targets(n3, which);      // (exact: whole numbers below 2^53)
-  g.nx = n3[0];
-  g.ny = n3[1];
-  g.nz = n3[2];
-  return run(nsrc2, h_xs, h_ys, zs, bz, nullptr, g, n3, h_x, h_y, h_z, B);
+  return box_entry("green_box", nsrc2, h_xs, h_ys, zs, bz, nullptr, n3, h_x, h_y, h_z, which, B);
 }
 
 // The constant-alpha field (semantics: include/ndsm_hip.h, ndsm_hip_lfff_points): the arguments of ndsmk_green_points
 // and alpha, a finite double.  alpha = 0 gives the bits of ndsmk_green_points for a finite bz.
 extern "C" int ndsmk_lfff_points(const int32_t *nsrc2, const double *h_xs, const double *h_ys, double zs,
                                  const double *bz, double alpha, int npts, const double *pts, double *B) {
-  NDSM_REQUIRE_READY();
-  NDSM_CHECK_ARG(nsrc2 && h_xs && h_ys && bz);
-  if (!source_ok(nsrc2, h_xs, h_ys) || npts < 0 || !std::isfinite(alpha))
-    return ndsmk_note_error(NDSMK_EVALUE, "lfff_points: at least 2 source nodes per axis, spacings > 0, npts >= 0 and "
-                                          "a finite alpha");
-  if (npts == 0) return 0;
-  NDSM_CHECK_ARG(pts && B);
-  Targets g = {};
-  g.gen = GEN_POINTS;
-  g.nc = 3;
-  g.count = npts;
-  g.pts = pts;
-  return run(nsrc2, h_xs, h_ys, zs, bz, &alpha, g, nullptr, nullptr, nullptr, nullptr, B);
+  return points_entry("lfff_points", GEN_POINTS, 3, nsrc2, h_xs, h_ys, zs, bz, &alpha, npts, pts, B);
 }
 
 // the arguments of ndsmk_green_box and alpha
 extern "C" int ndsmk_lfff_box(const int32_t *nsrc2, const double *h_xs, const double *h_ys, double zs,
                               const double *bz, double alpha, const int32_t *n3, const double *h_x, const double *h_y,
                               const double *h_z, int which, double *B) {
-  NDSM_REQUIRE_READY();
-  NDSM_CHECK_ARG(nsrc2 && h_xs && h_ys && bz && n3 && h_x && h_y && h_z && B);
-  if (!source_ok(nsrc2, h_xs, h_ys) || (which != 0 && which != 1) || n3[0] < 2 || n3[1] < 2 || n3[2] < 2 ||
-      !(h_z[0] >= zs) || !std::isfinite(alpha))
-    return ndsmk_note_error(NDSMK_EVALUE, "lfff_box: at least 2 source nodes per axis, spacings > 0, which 0 or 1, "
-                                          "at least 2 box nodes per axis, z[0] >= zs and a finite alpha");
-  if (box_targets(n3, which) > kMaxTargets)
-    return ndsmk_note_error(NDSMK_ENODEV, "lfff_box: more targets than any device holds");
-  Targets g = {};
-  g.gen = which == 0 ? GEN_FACES : GEN_VOLUME;
-  g.nc = 3;
-  g.count = (i64)box_targets(n3, which);      // (exact: whole numbers below 2^53)
-  g.nx = n3[0];
-  g.ny = n3[1];
-  g.nz = n3[2];
-  return run(nsrc2, h_xs, h_ys, zs, bz, &alpha, g, n3, h_x, h_y, h_z, B);
+  return box_entry("lfff_box", nsrc2, h_xs, h_ys, zs, bz, &alpha, n3, h_x, h_y, h_z, which, B);
 }
 
 // The potential field's vector potential on the plane of the magnetogram (semantics: include/ndsm_hip.h,
@@ -519,18 +462,7 @@ extern "C" int ndsmk_lfff_box(const int32_t *nsrc2, const double *h_xs, const do
 // ndsmk_green_points'.
 extern "C" int ndsmk_green_ap_points(const int32_t *nsrc2, const double *h_xs, const double *h_ys, const double *bz,
                                      int npts, const double *pts, double *Ap) {
-  NDSM_REQUIRE_READY();
-  NDSM_CHECK_ARG(nsrc2 && h_xs && h_ys && bz);
-  if (!source_ok(nsrc2, h_xs, h_ys) || npts < 0)
-    return ndsmk_note_error(NDSMK_EVALUE, "green_ap_points: at least 2 source nodes per axis, spacings > 0 and npts >= 0");
-  if (npts == 0) return 0;
-  NDSM_CHECK_ARG(pts && Ap);
-  Targets g = {};
-  g.gen = GEN_POINTS2;
-  g.nc = 2;
-  g.count = npts;
-  g.pts = pts;
-  return run(nsrc2, h_xs, h_ys, 0.0, bz, nullptr, g, nullptr, nullptr, nullptr, nullptr, Ap);
+  return points_entry("green_ap_points", GEN_POINTS2, 2, nsrc2, h_xs, h_ys, 0.0, bz, nullptr, npts, pts, Ap);
 }
 
 // the same on the source's own nodes: Ap (nsx,nsy,2)

@@ -172,6 +172,39 @@ def test_ap_bitwise(hip, n):
             same([ap_raw(hip, xs, ys, bz, device, off)], [want_off], "%s points off the nodes, device %s" % (n, device))
 
 
+CHUNK = 262144                             # targets per launch (kChunk of csrc/green.hip)
+
+
+# 3x2: one slice, every target against the model.  70x63: two slices; the model on the targets from CHUNK - 256 to the
+# end and on every 1024th before them - a target's sums depend on nothing but the target and the source, so the subset
+# loses nothing, and the full model would take half a minute
+@pytest.mark.parametrize("n", [(3, 2), (70, 63)], ids=IDS)
+def test_ap_points_past_one_chunk(hip, n):
+    """262144 + 300 distinct points through the two-sum path: a second launch whose targets start at 262144, whose count
+    (300) is below the first one's and no multiple of the block of 256, and whose slice sums reuse the first launch's
+    scratch with two components per slice.  All targets differ, so a target written from the other launch's sums, or
+    to the other launch's place, shows"""
+    xs, ys = fm.mesh2(n, (0.1, 0.13))
+    bz = fm.white_noise(n, 43, 1)[0]
+    assert len(fm.slices_of(n[0] * n[1])) == (2 if n == (70, 63) else 1)
+    m = CHUNK + 300
+    rng = np.random.default_rng(44)
+    P = np.stack([rng.uniform(xs[0] - 0.2, xs[-1] + 0.2, m), rng.uniform(ys[0] - 0.2, ys[-1] + 0.2, m)], axis=1)
+    X, Y = np.meshgrid(xs, ys)
+    P[CHUNK - 3:CHUNK + 3] = np.stack([X.ravel(), Y.ravel()], axis=1)[:6]    # source nodes, both sides of the boundary
+    assert len(np.unique(P, axis=0)) == m
+    if n == (3, 2):
+        pick = np.arange(m)
+    else:
+        pick = np.concatenate([np.arange(0, CHUNK - 256, 1024), np.arange(CHUNK - 256, m)])
+    want = fm.green_ap_numpy(xs, ys, bz, P[pick])
+    assert np.isfinite(want).all() and not np.array_equal(want[:300], want[-300:])
+    for device in (False, True):
+        got = ap_raw(hip, xs, ys, bz, device, P)
+        assert got.shape == (m, 2)
+        same([got[pick]], [want], "%s points past one chunk, device %s" % (n, device))
+
+
 @pytest.mark.parametrize("n", AP_SHAPES, ids=IDS)
 def test_flux_bitwise(hip, n):
     xs, ys = fm.mesh2(n, (0.1, 0.13))

@@ -1,5 +1,6 @@
-"""GPU tests of the constant-alpha force-free entries (lfff_k in csrc/green.hip; semantics: include/ndsm_hip.h, "Linear
-force-free field") against the Green's-function entries and against their numpy model (tests/lfff_model.py).
+"""GPU tests of the constant-alpha force-free entries (pairs_k<LfffTerm> in csrc/green.hip; semantics:
+include/ndsm_hip.h, "Linear force-free field") against the Green's-function entries and against their numpy
+model (tests/lfff_model.py).
 
 alpha = 0: equal bits with ndsm_hip_green_points / ndsm_hip_green_box.  alpha != 0: the device's sin and cos are not
 numpy's, so the comparison with the model is a cap and not bit for bit.  With M the model's per-component scale (per

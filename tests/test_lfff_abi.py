@@ -41,7 +41,11 @@ def test_lfff_entries_declared_exported_and_bound(lib):
     for name in ("ndsmk_lfff_points", "ndsmk_lfff_box"):
         assert name in kernels and name not in open(HEADER).read()
     hip = open(os.path.join(ROOT, "ndsm_amd", "csrc", "green.hip")).read()
-    assert "void lfff_k(" in hip and "void green_k(" in hip and "sincos(" in hip
+    # one all-pairs kernel over three pair terms, and the fold: no other __global__ function
+    assert re.findall(r"__global__[^;{]*?void\s+(\w+)\s*\(", hip) == ["pairs_k", "fold_k"]
+    assert "template <class Term>\n__global__" in hip
+    assert sorted(re.findall(r"^struct (\w+Term) \{", hip, re.M)) == ["ApTerm", "GreenTerm", "LfffTerm"]
+    assert all("pairs_k<%s>" % term in hip for term in ("ApTerm", "GreenTerm", "LfffTerm")) and "sincos(" in hip
     text = open(HEADER).read()
     for phrase in ("Linear force-free field", "Chiu & Hilton", "sz = sin(alpha w)", "u = alpha (q / R2)",
                    "e = sz - (ww / r2) sr", "f = (w / r) cr - cz", "A hazard", "not unique", "For finite bz only"):

@@ -1496,6 +1496,101 @@ int ndsm_hip_flow_flux(const int nsrc[2], const double *xs, const double *ys, co
 int ndsm_hip_flow_flux_device(const int nsrc[2], const double *xs, const double *ys, const double *dB,
                               const double *dV, const double *dAp, double *ddens, double out[8]);
 
+/* ---- Flux partitioning and connectivity (DESIGN.md "Flux partitioning and connectivity") ---------------------------
+ * The nulls, spines and fans, separators, Q and the bald patches are the BOUNDARIES of the flux domains of a field.
+ * These entries say what the domains are and how much flux each holds, the question of magnetic charge topology
+ * (Barnes, Longcope & Leka 2005; Longcope 2005): the magnetogram falls into flux patches, and some amount of flux links
+ * patch a to patch b.  fp64 + - * / only, in the operand order written here, no contraction: a numpy restatement in the
+ * same order gives the same bits.
+ *
+ * The keyed sum.  Every sum below is grouped by a key that the data decide - a patch, a pair of patches.  The terms of
+ * one key are taken in ascending pixel index; call the q-th of them rank q.  Lane l of 64 adds the ranks l, l + 64, ...
+ * in that order, from 0.0.  Then v[l] = v[l] + v[l + d] for l < d, d = 32, 16, ... 1.  The sum is v[0].  A key with one
+ * term adds only the tree's zeros to it, which leaves it unchanged except that a lone -0.0 becomes +0.0.  The same bits
+ * on every run and from both entries: the terms of a key are brought together by a stable sort of (key, pixel), whose
+ * result is unique, and nothing is added atomically.
+ *
+ * ndsm_hip_partition: no handle, a plane entry like the flow entries.
+ *   nsrc, xs, ys  a uniform mesh with nsx, nsy >= 2; hx = xs[1] - xs[0], hy = ys[1] - ys[0] as the flow entries form
+ *                 them, both > 0.  The mesh vectors are on the HOST in both forms.
+ *   bz            (nsx,nsy), pixel p = i + nsx j; at most 2^31 - 1 pixels
+ *   thr           >= 0, finite
+ *   max_patches   >= 0 (int64): the capacity of the record arrays; 0 counts only (no record array is looked at)
+ *   counts        int64[2], a HOST array in both forms: (pixels in, patches K), exact whatever the capacity
+ *   label         int32 (nsx,nsy), always fully written
+ *   records       of the first min(K, max_patches) patches: root int64, sign int32, npix int64, flux, sx, sy doubles
+ * Semantics:
+ *   in          pixel p is IN iff fabs(bz) > thr.  A NaN is not in.  Its sign is bz > 0.
+ *   pointer     consider p itself and those of its 8 neighbours that lie inside the magnetogram, are in and have p's
+ *               sign; there is no padding and no wrap.  ptr(p) is the candidate with the greatest |bz|; equal values go
+ *               to the smallest pixel index.  So (|bz|, -index) strictly increases along pointers, there are no
+ *               cycles, and plateaus drain to one pixel.
+ *   root        the fixed point reached from p.  It is unique whatever way it is found.
+ *   numbering   patches are k = 1 .. K in ascending root index.  label(p) = k, and 0 for pixels not in.
+ *   weights     w(p) = wx(i) wy(j), the trapezoid weights of ndsm_hip_flow_flux: hx inside, 0.5 hx on both end rows,
+ *               likewise wy.  f(p) = bz(p) w(p).
+ *   table       of patch k: root; sign +1 or -1; npix; flux = sum f; sx = sum f xs[i] and sy = sum f ys[j] (the
+ *               centroid is the quotient (sx / flux, sy / flux), ndsm_amd's Patches.centroid).  Every sum is a keyed
+ *               sum over the patch's pixels.
+ *   Infinities  +Inf and -Inf are in and are peaks like any other.  There is no special rule: a field with Inf in it
+ *               is the caller's to mask, as in the dips entry.
+ * Returns 0, or >= 9001 errors, in this order: 9001 without a GPU, whatever the arguments; 9001 from the memory screen
+ * as soon as the shapes can be read (the arrays and 50 bytes of scratch a pixel against the device's memory); 9002 a
+ * NULL nsrc, xs, ys, bz, counts or label, or with max_patches > 0 a NULL record array; 9004 fewer than 2 nodes on an
+ * axis, more than 2^31 - 1 pixels, a spacing that is not > 0, a thr that is not finite and >= 0, max_patches < 0.  On
+ * every failure counts is cleared.  The host form also clears its outputs - the max_patches rows of its records and,
+ * once the shape has passed its checks, label.  The device form leaves them. */
+/* HOST arrays */
+int ndsm_hip_partition(const int nsrc[2], const double *xs, const double *ys, const double *bz, double thr,
+                       int64_t max_patches, int64_t *counts, int32_t *label, int64_t *root, int32_t *sign,
+                       int64_t *npix, double *flux, double *sx, double *sy);
+/* the same with bz, label and the six record arrays DEVICE arrays of the library's GPU (counts stays on the host) */
+int ndsm_hip_partition_device(const int nsrc[2], const double *xs, const double *ys, const double *dbz, double thr,
+                              int64_t max_patches, int64_t *counts, int32_t *dlabel, int64_t *droot, int32_t *dsign,
+                              int64_t *dnpix, double *dflux, double *dsx, double *dsy);
+
+/* ndsm_hip_vecpot_connect: on a handle, since it traces through the volume.
+ *   B             (nx,ny,nz,3) on the handle's mesh
+ *   label, K      label int32 (nx,ny) on the lower face and K >= 0.  A label outside 1 .. K counts as 0, both for the
+ *                 seed and at the destination, so every key is bounded whatever the caller passes.
+ *   step, max_steps  as in ndsm_hip_vecpot_trace
+ *   max_pairs     >= 0 (int64): the capacity of the pair arrays; 0 counts only
+ *   counts        int64[2], a HOST array in both forms: (lines traced, distinct pairs M)
+ *   per pixel     on (nx,ny): dest int32, ends (3,npix), length, status int32
+ *   pairs         pa, pc int32, nlines int64, pflux double
+ * Semantics:
+ *   line of p   the seed is (x_i, y_j, lo_z) from the handle's mesh.  sgn = +1 if B_z(node) > 0 and -1 if < 0: the sign
+ *               comes from the field that is traced, not from the label.  No line is traced if label(p) == 0 (after
+ *               the 1 .. K rule), if B_z is 0 or NaN there, or if the seed is not inside the trace entry's box [lo, hi]
+ *               (ndsm_hip_vecpot_trace answers NDSM_HIP_TRACE_OUTSIDE for it too); then dest = NDSM_HIP_CONNECT_NONE
+ *               (-9), end = seed, length = 0 and status = NDSM_HIP_TRACE_OUTSIDE.  Otherwise one lane walks the trace
+ *               entry's loop with that per-lane sgn: ends, length and status are BIT FOR BIT what
+ *               ndsm_hip_vecpot_trace returns for that seed with direction sgn and G = NULL.
+ *   class c     of the destination.  If status is ZLO, c is the label (after the 1 .. K rule) of the nearest pixel,
+ *               i' = clamp((int)floor((x - lo_x) / h_x + 0.5), 0, nx - 1), likewise j'.  Otherwise c = -status, one of
+ *               -1 .. -4, -6, -7, -8.  dest(p) = c.  c = a, a line that comes back to its own patch, is a pair like
+ *               any other.
+ *   pairs       the key is (a, c) with a = label(p).  Records come in ascending a, then ascending c.  nlines is the
+ *               number of lines with that key; pflux is the keyed sum of fabs(B_z(p)) w(p), with w the trapezoid
+ *               weight of the plane (h_x, h_y the handle's spacings).  The matrix is ONE-SIDED on purpose: Psi(a -> b)
+ *               is counted from a's feet and Psi(b -> a) from b's (ndsm_amd's connectivity_matrix offers the
+ *               symmetric mean).
+ *   capacity    counts is exact whatever max_pairs; the first max_pairs records in key order are written and the call
+ *               still returns 0 when there are more.
+ * Returns 0, or >= 9001 errors: 9001 without a GPU whatever the arguments; 9002 a NULL handle, B, label, counts or
+ * per-pixel array, or with max_pairs > 0 a NULL pair array; 9004 K < 0, max_pairs < 0, a step that is not > 0 and finite,
+ * max_steps < 1.  On every failure counts is cleared; on a failure past the handle's check the host entry also clears
+ * its per-pixel arrays and the max_pairs slots of its pair arrays, the device entry leaves its device arrays. */
+#define NDSM_HIP_CONNECT_NONE (-9)
+/* HOST arrays */
+int ndsm_hip_vecpot_connect(void *h, const double *B, const int32_t *label, int K, double step, int max_steps,
+                            int64_t max_pairs, int64_t *counts, int32_t *dest, double *ends, double *length,
+                            int32_t *status, int32_t *pa, int32_t *pc, int64_t *nlines, double *pflux);
+/* the same on DEVICE arrays of the library's GPU (B, label and the eight output arrays; counts stays on the host) */
+int ndsm_hip_vecpot_connect_device(void *h, const double *dB, const int32_t *dlabel, int K, double step, int max_steps,
+                                   int64_t max_pairs, int64_t *counts, int32_t *ddest, double *dends, double *dlength,
+                                   int32_t *dstatus, int32_t *dpa, int32_t *dpc, int64_t *dnlines, double *dpflux);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,8 @@ from ._lib import (load_library, lib_path, MGSolver, VecPot, World, slab_plan, p
                    measurement_weight, force_free_optimize_obs, resample_weighted, force_free_obs_cascade,
                    green_field_points, magnetogram_field, potential_open, lfff_field_points,
                    linear_force_free_field, best_alpha, Dips, find_dips, bald_patches, Flow, Fluxes, flow_fit,
-                   plane_vector_potential, plane_vector_potential_points, boundary_fluxes)
+                   plane_vector_potential, plane_vector_potential_points, boundary_fluxes, Patches,
+                   partition_magnetogram, Connectivity, find_connectivity, connectivity_matrix)
 
 __all__ = ["vector_potential", "vector_potential_slab", "get_lib_path", "load_library", "lib_path", "MGSolver", "VecPot", "poisson_solve",
            "NdsmHipError", "Helicity", "vector_potential_field", "relative_helicity", "Projection", "solenoidal_projection",
@@ -31,4 +32,5 @@ __all__ = ["vector_potential", "vector_potential_slab", "get_lib_path", "load_li
            "measurement_weight", "force_free_optimize_obs", "resample_weighted", "force_free_obs_cascade",
            "green_field_points", "magnetogram_field", "potential_open", "lfff_field_points",
            "linear_force_free_field", "best_alpha", "Dips", "find_dips", "bald_patches", "Flow", "Fluxes", "flow_fit",
-           "plane_vector_potential", "plane_vector_potential_points", "boundary_fluxes"]
+           "plane_vector_potential", "plane_vector_potential_points", "boundary_fluxes", "Patches",
+           "partition_magnetogram", "Connectivity", "find_connectivity", "connectivity_matrix"]

@@ -169,6 +169,13 @@ def load_library(path=None):
     L.ndsm_hip_green_ap_plane_device.argtypes = _pm + [ctypes.c_void_p] * 2
     L.ndsm_hip_flow_flux.argtypes = _pm + [ctypes.c_void_p] * 4 + [_dp]
     L.ndsm_hip_flow_flux_device.argtypes = _pm + [ctypes.c_void_p] * 4 + [_dp]
+    _pt = _pm + [ctypes.c_void_p, ctypes.c_double, ctypes.c_int64] + [ctypes.c_void_p] * 8
+    L.ndsm_hip_partition.argtypes = _pt
+    L.ndsm_hip_partition_device.argtypes = _pt
+    _cn = ([ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int64] +
+           [ctypes.c_void_p] * 9)
+    L.ndsm_hip_vecpot_connect.argtypes = _cn
+    L.ndsm_hip_vecpot_connect_device.argtypes = _cn
     _sk = ([ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_int, ctypes.c_void_p] +
            [ctypes.c_double] * 3 + [ctypes.c_int, ctypes.c_int, ctypes.c_int64] + [ctypes.c_void_p] * 13)
     L.ndsm_hip_vecpot_skeleton.argtypes = _sk
@@ -1187,6 +1194,75 @@ class VecPot:
         else:
             n, (counts, out) = _with_capacity(run, max_dips, count_only=True)
         return _dips_tuple([a[:n] for a in out], counts, int(self.nshape4[0]), int(self.nshape4[1]))
+
+    def connectivity(self, b, label=None, K=None, thr=0.0, step=0.5, max_steps=None, max_pairs=None, device=False):
+        """The connectivity fluxes between the flux patches of the lower face of b (3,nz,ny,nx), on the device
+        (semantics: include/ndsm_hip.h, ndsm_hip_vecpot_connect): one field line from every labelled pixel, followed
+        along b where b_z > 0 there and against it where b_z < 0, the class of the place where it ends - the patch
+        of the nearest pixel when it comes back to the face, else minus its TRACE_* status - and per (patch, class)
+        pair the number of lines and the flux |b_z| w at their feet.  label (ny,nx; integers, e.g.
+        partition_magnetogram()'s) with K the largest label that counts (None: label.max()); label=None partitions
+        b_z of the lower face with thr (thr must be 0 with a label) on the device (ndsm_hip_partition_device), and the
+        label map goes into the connect call without crossing PCIe in between.  step, max_steps as trace()'s.  max_pairs: the capacity of
+        the first call, repeated once when there are more pairs (None: a counting call, then one of the exact size;
+        0: count only).  Returns a Connectivity tuple: dest (ny,nx; int32, CONNECT_NONE where no line starts), ends
+        (ny,nx,3), length, status (ny,nx), pa, pc, nlines, pflux (n; in ascending (pa, pc)), ntraced, npairs (exact
+        whatever the capacity), label (ny,nx; the map that was used), K.  device=True: the arrays are staged in
+        device memory and the device-resident entry point runs."""
+        _, step, max_steps = self._trace_args(step, max_steps, "forward")
+        thr, max_pairs = _thr_arg(thr), _capacity_arg("max_pairs", max_pairs)
+        nx, ny = int(self.nshape4[0]), int(self.nshape4[1])
+        npix = nx * ny
+        if label is None:
+            if K is not None:
+                raise ValueError("K is the partition's to find when label is None")
+            if len(self.x) < 2 or len(self.y) < 2 or not (self.x[1] - self.x[0] > 0.0 and self.y[1] - self.y[0] > 0.0):
+                raise ValueError("the partition needs at least 2 nodes per axis and spacings > 0")
+            lab = None
+        else:
+            if thr != 0.0:
+                raise ValueError("thr is the partition's, which does not run when a label is given")
+            lab = np.asarray(label)
+            if lab.shape != (ny, nx) or lab.dtype.kind not in "iu":
+                raise ValueError(f"label of shape {lab.shape} and type {lab.dtype}, integers of shape {(ny, nx)} are "
+                                 "needed")
+            if K is None:
+                K = max(int(lab.max()), 0)
+            if isinstance(K, bool) or int(K) != K or not 0 <= K <= PATCHES_MAX:
+                raise ValueError(f"K must be an integer in 0 .. {PATCHES_MAX}, not {K!r}")
+            K = int(K)
+            lab = np.clip(lab, -1, PATCHES_MAX).astype(np.int32).reshape(-1).copy()     # (outside 1 .. K stays outside)
+        B = self._field_arg(b, "connectivity")
+        L = self.L
+        ns2 = np.array([nx, ny], dtype=np.intc)
+
+        def run(cap):
+            counts, pcounts = np.zeros(2, dtype=np.int64), np.zeros(2, dtype=np.int64)
+            m = max(cap, 1)
+            out = [np.zeros(npix, dtype=np.int32), np.zeros(3 * npix), np.zeros(npix), np.zeros(npix, dtype=np.int32)]
+            pairs = [np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int64), np.zeros(m)]
+            if lab is not None:
+                self._entry("ndsm_hip_vecpot_connect", [B, lab, K, step, max_steps, cap, counts.ctypes.data, *out, *pairs],
+                            device)
+                return int(counts[1]), (counts, out, pairs, lab, K)
+            own = np.zeros(npix, dtype=np.int32)
+
+            def both(dB, dlab, *dout):
+                rc = L.ndsm_hip_partition_device(ns2.ctypes.data_as(_ip), _d(self.x), _d(self.y),
+                                                 ctypes.c_void_p(dB.value + 16 * (B.size // 3)), thr, 0,
+                                                 pcounts.ctypes.data, dlab, None, None, None, None, None, None)
+                if rc != 0:
+                    return rc
+                return L.ndsm_hip_vecpot_connect_device(self.h, dB, dlab, int(pcounts[1]), step, max_steps, cap,
+                                                        counts.ctypes.data, *dout)
+            _check(_staged(L, [B, own, *out, *pairs], both), "ndsm_hip_partition_device + ndsm_hip_vecpot_connect_device",
+                   L)
+            return int(counts[1]), (counts, out, pairs, own, int(pcounts[1]))
+        if max_pairs is None:
+            n, (counts, out, pairs, used, k) = _with_capacity(run, 0)
+        else:
+            n, (counts, out, pairs, used, k) = _with_capacity(run, max_pairs, count_only=True)
+        return _connect_tuple(counts, out, pairs, n, used, k, ny, nx)
 
     def bald_patch_lines(self, b, dips, lift=1e-3, **paths_options):
         """The field lines that generate the bald-patch separatrix surface of b: the records of `dips` (a Dips tuple
@@ -2407,6 +2483,112 @@ def boundary_fluxes(xs, ys, b, v, ap=None, status=None, device=False, lib=None):
         _check(_staged(L, [B, V, A, D], both), "ndsm_hip_green_ap_plane_device + ndsm_hip_flow_flux_device", L)
     return Fluxes(D.reshape(4, len(qy), len(qx)), tuple(float(x) for x in out[0:3]), tuple(float(x) for x in out[3:6]),
                   (float(out[6]), float(out[7])))
+
+
+Patches = collections.namedtuple("Patches", ["label", "root", "sign", "npix", "flux", "sx", "sy", "centroid", "nin", "K"])
+Connectivity = collections.namedtuple("Connectivity", ["dest", "ends", "length", "status", "pa", "pc", "nlines", "pflux",
+                                                       "ntraced", "npairs", "label", "K"])
+CONNECT_NONE = -9                  # dest of a pixel from which no line is traced
+PATCHES_MAX = 2 ** 31 - 1          # no more patches than pixels, and those fit a C int
+
+
+def _capacity_arg(name, v):
+    """a capacity (None, or a whole number in 0 .. PATCHES_MAX) as None or int; ValueError otherwise"""
+    if v is None:
+        return None
+    if (isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or
+            int(v) != v or not 0 <= v <= PATCHES_MAX):
+        raise ValueError(f"{name} must be None or an integer in 0 .. {PATCHES_MAX}, not {v!r}")
+    return int(v)
+
+
+def _thr_arg(thr):
+    """thr as a finite float >= 0; ValueError for what the library would answer with 9004"""
+    try:
+        t = float(thr)
+    except (TypeError, ValueError):
+        raise ValueError(f"thr must be a finite number >= 0, not {thr!r}") from None
+    if not (np.isfinite(t) and t >= 0.0):
+        raise ValueError(f"thr must be a finite number >= 0, not {thr!r}")
+    return t
+
+
+def partition_magnetogram(xs, ys, bz, thr=0.0, max_patches=None, device=False, lib=None):
+    """The flux patches of the magnetogram bz (nsy,nsx) on the uniform mesh xs, ys, on the device (semantics:
+    include/ndsm_hip.h, ndsm_hip_partition): a pixel is in where |bz| > thr; every pixel in points to the strongest
+    pixel of its sign among itself and its 8 neighbours (equal values: the smallest index), and the pixels that reach
+    the same peak form a patch.  Patches are numbered 1 .. K in ascending peak index.  max_patches: the capacity of the
+    first call; when more are found the call is repeated once with that number (None: a counting call, then one call
+    of the exact size; 0: count only, no table).  Returns Patches(label (nsy,nsx; int32, 0: not in), root (n; int64,
+    the peak's pixel i + nsx j), sign (n; +1 / -1), npix (n), flux, sx, sy (n; the trapezoid sums of bz, bz x and bz y
+    over the patch, with the same bits on every run), centroid (n,2) = (sx / flux, sy / flux), nin (the pixels in),
+    K (the patches, exact whatever the capacity)).  device=True: the arrays are staged in device memory and the
+    device-resident entry point runs."""
+    ns2, qx, qy = _plane_mesh(xs, ys, 2)
+    thr, max_patches = _thr_arg(thr), _capacity_arg("max_patches", max_patches)
+    S = _plane_field(bz, 0, qx, qy, "bz")
+    L = lib or load_library()
+    head = (ns2.ctypes.data_as(_ip), _d(qx), _d(qy))
+
+    def run(cap):
+        counts = np.zeros(2, dtype=np.int64)
+        m = max(cap, 1)
+        label = np.zeros(S.size, dtype=np.int32)
+        rec = [np.zeros(m, dtype=np.int64), np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int64), np.zeros(m),
+               np.zeros(m), np.zeros(m)]
+        if not device:
+            _check(L.ndsm_hip_partition(*head, S.ctypes.data, thr, cap, counts.ctypes.data, label.ctypes.data,
+                                        *[a.ctypes.data for a in rec]), "ndsm_hip_partition", L)
+        else:
+            _check(_staged(L, [S, label, *rec], lambda dS, dl, *dr: L.ndsm_hip_partition_device(
+                *head, dS, thr, cap, counts.ctypes.data, dl, *dr)), "ndsm_hip_partition_device", L)
+        return int(counts[1]), (counts, label, rec)
+    if max_patches is None:
+        n, (counts, label, rec) = _with_capacity(run, 0)
+    else:
+        n, (counts, label, rec) = _with_capacity(run, max_patches, count_only=True)
+    root, sign, npix, flux, sx, sy = [a[:n] for a in rec]
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        centroid = np.stack([sx / flux, sy / flux], axis=1)
+    return Patches(label.reshape(len(qy), len(qx)), root, sign, npix, flux, sx, sy, centroid, int(counts[0]),
+                   int(counts[1]))
+
+
+def _connect_tuple(counts, out, pairs, n, label, K, ny, nx):
+    dest, ends, length, status = out
+    return Connectivity(dest.reshape(ny, nx), ends.reshape(ny, nx, 3), length.reshape(ny, nx), status.reshape(ny, nx),
+                        *[a[:n] for a in pairs], int(counts[0]), int(counts[1]), label.reshape(ny, nx), int(K))
+
+
+def connectivity_matrix(conn, K=None, symmetric=False):
+    """The connectivity fluxes of a Connectivity tuple as a dense (K, K + 1) array: entry (a - 1, c - 1) is the flux
+    Psi(a -> c) at the feet in patch a of the lines that end in patch c, and the last column holds everything of
+    patch a that did not land on a patch (an open class, or an unlabelled pixel).  K None: conn.K.  The matrix is
+    one-sided, Psi(a -> b) counted from a's feet and Psi(b -> a) from b's; symmetric=True replaces both by their mean
+    (the last column stays)."""
+    K = conn.K if K is None else K
+    if isinstance(K, bool) or int(K) != K or K < 0:
+        raise ValueError(f"K must be an integer >= 0, not {K!r}")
+    K = int(K)
+    M = np.zeros((K, K + 1))
+    for a, c, f in zip(conn.pa, conn.pc, conn.pflux):
+        if 1 <= a <= K:
+            M[a - 1, c - 1 if 1 <= c <= K else K] += f
+    if symmetric:
+        M[:, :K] = 0.5 * (M[:, :K] + M[:, :K].T)
+    return M
+
+
+def find_connectivity(x, y, z, b, label=None, K=None, thr=0.0, step=0.5, max_steps=None, max_pairs=None, lib=None):
+    """The patch connectivity of b (3,nz,ny,nx): one-shot form of VecPot.connectivity (returns its Connectivity tuple).
+    Raises NdsmHipError on device / runtime failures (>= 9001)."""
+    _thr_arg(thr)
+    _capacity_arg("max_pairs", max_pairs)
+    V = _grid_handle(x, y, z, b, 0, lib)
+    try:
+        return V.connectivity(b, label=label, K=K, thr=thr, step=step, max_steps=max_steps, max_pairs=max_pairs)
+    finally:
+        V.close()
 
 
 def potential_open(x, y, z, bz, xs=None, ys=None, zs=None, a_init=None, niterex_max=10000, ncycles_max=1024,

@@ -387,6 +387,30 @@ int ndsmk_dips(const double *B, const int32_t *n3, const double *lo3, const doub
                int64_t max_dips, int64_t *h_counts3, int64_t *edge, double *pos, double *bpt, double *grad, double *curv,
                int32_t *flag);
 
+/* Flux partitioning of a magnetogram (partition.hip; semantics: include/ndsm_hip.h, ndsm_hip_partition).  bz (nsx,nsy)
+ * and label (nsx,nsy; int32) DEVICE arrays, h_xs, h_ys the mesh vectors on the HOST.  h_counts2 (HOST, int64): the pixels
+ * in and the patches K, exact whatever max_patches.  The first min(K, max_patches) rows of the table in ascending root
+ * go into the DEVICE arrays root (int64), sign (int32), npix (int64), flux, sx, sy (doubles); with max_patches == 0 they
+ * are not looked at and nothing is sorted.  NDSMK_EVALUE for fewer than 2 nodes on an axis, a spacing that is not > 0, a
+ * thr that is not finite and >= 0, max_patches < 0.  Blocks for the two counts and, with records, for the copies of the
+ * mesh vectors.  ndsmk_partition_fits: 0, or NDSMK_ENODEV when caller_bytes plus the scratch of a call (50 bytes a pixel)
+ * pass the device's total memory. */
+int ndsmk_partition_fits(const int32_t *nsrc2, double caller_bytes);
+int ndsmk_partition(const int32_t *nsrc2, const double *h_xs, const double *h_ys, const double *bz, double thr,
+                    int64_t max_patches, int64_t *h_counts2, int32_t *label, int64_t *root, int32_t *sign, int64_t *npix,
+                    double *flux, double *sx, double *sy);
+
+/* Patch connectivity (connect.hip; semantics: include/ndsm_hip.h, ndsm_hip_vecpot_connect).  B (nx,ny,nz,3) and label
+ * (nx,ny; int32) DEVICE arrays; lo3, h_dq3 as ndsmk_trace's, h_x (nx), h_y (ny) the mesh vectors on the HOST: the seeds
+ * are their values.  h_counts2 (HOST, int64): the lines traced and the distinct pairs M, exact whatever max_pairs.  Per
+ * pixel into the DEVICE arrays dest (int32), ends (3 each), length, status (int32); the first min(M, max_pairs) pairs in
+ * ascending (a, c) into pa, pc (int32), nlines (int64), pflux, not looked at with max_pairs == 0.  NDSMK_EVALUE as
+ * ndsmk_trace, and for K < 0 or max_pairs < 0.  Blocks for the two counts; the records are written asynchronously. */
+int ndsmk_connect(const double *B, const int32_t *n3, const double *lo3, const double *h_dq3, const double *h_x,
+                  const double *h_y, const int32_t *label, int K, double step, int max_steps, int64_t max_pairs,
+                  int64_t *h_counts2, int32_t *dest, double *ends, double *length, int32_t *status, int32_t *pa,
+                  int32_t *pc, int64_t *nlines, double *pflux);
+
 /* Field-line paths (paths.hip; semantics: include/ndsm_hip.h, ndsm_hip_vecpot_paths), in two halves with the same
  * leading arguments, which are ndsmk_trace's.  ndsmk_paths_count: ndsmk_trace itself (ends, length, integral, status,
  * nsteps are its outputs), then offsets (nl + 1, int64, DEVICE) = the exclusive sums of the lines' point counts for the

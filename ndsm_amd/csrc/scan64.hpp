@@ -37,7 +37,7 @@ __global__ __launch_bounds__(kScanBlock) void scan64_k(i64 *a, size_t ng) {
 
 // the tail of a counting half: offsets (ng counts, DEVICE) scanned in place, the total offsets[ng] into *h_total
 // (HOST).  Blocks for the total.
-int scan64_total(int64_t *offsets, size_t ng, int64_t *h_total, hipStream_t s) {
+[[maybe_unused]] int scan64_total(int64_t *offsets, size_t ng, int64_t *h_total, hipStream_t s) {
   hipLaunchKernelGGL(scan64_k, dim3(1), dim3(kScanBlock), 0, s, (i64 *)offsets, ng);
   NDSM_LAUNCH_CHECK();
   NDSM_HIP(hipMemcpyAsync(h_total, offsets + ng, sizeof(int64_t), hipMemcpyDeviceToHost, s));

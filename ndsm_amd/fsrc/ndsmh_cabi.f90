@@ -1811,6 +1811,136 @@ contains
     end function
   end function
 
+  ! ---- Flux partitioning of a magnetogram (include/ndsm_hip.h, ndsm_hip_partition) ----
+  ! No handle; the mesh vectors and counts (2, int64) stay on the host in both forms.  bz (nsx,nsy) in; label (nsx,nsy;
+  ! int32) and the first min(K, max_patches) rows of root (int64), sign (int32), npix (int64), flux, sx, sy out.
+  ! HOST arrays
+  function ndsm_hip_partition(nsrc, xs, ys, bz, thr, max_patches, counts, label, root, sign, npix, flux, sx, sy) &
+      bind(c, name="ndsm_hip_partition") result(ierr)
+    type(c_ptr), value :: nsrc, xs, ys, bz, counts, label, root, sign, npix, flux, sx, sy
+    real(c_double), value :: thr
+    integer(c_int64_t), value :: max_patches
+    integer(c_int) :: ierr
+    ierr = partition_entry(nsrc, xs, ys, bz, thr, max_patches, counts, label, [root, sign, npix, flux, sx, sy], .false., &
+                           "ndsm_hip_partition")
+  end function
+
+  ! the same with bz, label and the record arrays DEVICE arrays of the library's GPU
+  function ndsm_hip_partition_device(nsrc, xs, ys, dbz, thr, max_patches, counts, dlabel, droot, dsign, dnpix, dflux, dsx, &
+                                     dsy) bind(c, name="ndsm_hip_partition_device") result(ierr)
+    type(c_ptr), value :: nsrc, xs, ys, dbz, counts, dlabel, droot, dsign, dnpix, dflux, dsx, dsy
+    real(c_double), value :: thr
+    integer(c_int64_t), value :: max_patches
+    integer(c_int) :: ierr
+    ierr = partition_entry(nsrc, xs, ys, dbz, thr, max_patches, counts, dlabel, [droot, dsign, dnpix, dflux, dsx, dsy], &
+                           .true., "ndsm_hip_partition_device")
+  end function
+
+  ! The two entries above.  The host form stages bz, label and the max_patches rows of the records in one allocation
+  ! and copies the outputs back, the device form passes its arrays on.  In this order: 9001 without a GPU; 9001 from
+  ! the memory screen as soon as the shapes can be read; 9002; 9004.  On every failure counts is cleared; the host form
+  ! also clears the max_patches rows of its records and, once the shape has passed its checks, label.
+  function partition_entry(nsrc, xs, ys, bz, thr, max_patches, counts, label, rec, on_device, who) result(ierr)
+    type(c_ptr), intent(in) :: nsrc, xs, ys, bz, counts, label, rec(6)
+    real(c_double), intent(in) :: thr
+    integer(c_int64_t), intent(in) :: max_patches
+    logical, intent(in) :: on_device
+    character(len=*), intent(in) :: who
+    integer(c_int) :: ierr
+    integer, parameter :: width(6) = [8, 4, 8, 8, 8, 8]
+    integer(c_int), pointer :: ns(:)
+    integer(c_int64_t), pointer :: cnt(:)
+    integer(c_int32_t) :: ns2(2)
+    integer(c_int64_t) :: npix, rows
+    integer(c_size_t) :: off(8), at, nb
+    real(c_double) :: total
+    type(c_ptr) :: buf, d(8)
+    integer(c_int) :: rc
+    integer :: i
+    logical :: shape_ok, complete
+    shape_ok = .false.
+    call clear_host([counts], [8], [2_c_int64_t])
+    ierr = ndsmk_init(-1_c_int)
+    if (ierr /= 0) return
+    ! a call the device cannot hold is refused before anything is allocated - as soon as its shapes can be read
+    if (c_associated(nsrc)) then
+      call c_f_pointer(nsrc, ns, [2])
+      ns2 = ns
+      if (all(ns2 >= 1)) then
+        total = product(real(ns2, c_double)) * 12.0_c_double
+        if (max_patches > 0) total = total + 44.0_c_double * real(max_patches, c_double)
+        ierr = ndsmk_partition_fits(ns2, merge(0.0_c_double, total, on_device))
+        if (ierr /= 0) return
+      end if
+    end if
+    ierr = NDSMK_EARG
+    complete = c_associated(nsrc) .and. c_associated(xs) .and. c_associated(ys) .and. c_associated(bz) .and. &
+               c_associated(counts) .and. c_associated(label)
+    if (max_patches > 0) then
+      do i = 1, 6
+        complete = complete .and. c_associated(rec(i))
+      end do
+    end if
+    if (.not. complete) then
+      call clear_outputs()
+      return
+    end if
+    ierr = green_source_ok(ns, xs, ys)
+    if (ierr == 0 .and. (.not. (thr >= 0.0_c_double .and. thr <= huge(thr)) .or. max_patches < 0)) ierr = NDSMK_EVALUE
+    if (ierr == 0 .and. product(int(ns2, c_int64_t)) > int(huge(0_c_int32_t), c_int64_t)) ierr = NDSMK_EVALUE
+    if (ierr /= 0) then
+      ierr = ndsmk_note_error(NDSMK_EVALUE, "partition: at least 2 nodes per axis, at most 2^31 - 1 pixels, "// &
+                              "spacings > 0, a finite thr >= 0 and max_patches >= 0"//c_null_char)
+      call clear_outputs()
+      return
+    end if
+    shape_ok = .true.
+    npix = product(int(ns2, c_int64_t))
+    call c_f_pointer(counts, cnt, [2])
+    if (on_device) then
+      rc = ndsmk_partition(ns2, xs, ys, bz, thr, max_patches, cnt, label, rec(1), rec(2), rec(3), rec(4), rec(5), rec(6))
+    else
+      ! bz, label, then the records, each on a multiple of 8 bytes
+      off(1) = 0
+      off(2) = int(8 * npix, c_size_t)
+      at = off(2) + int((4 * npix + 7) / 8 * 8, c_size_t)
+      do i = 1, 6
+        off(2 + i) = at
+        at = at + int((width(i) * min(max_patches, npix) + 7) / 8 * 8, c_size_t)     ! (K <= npix)
+      end do
+      buf = c_null_ptr
+      rc = ndsmk_alloc(buf, at)
+      if (rc == 0) then
+        do i = 1, 8
+          d(i) = dptr_offset(buf, off(i))
+        end do
+        rc = ndsmk_h2d(d(1), bz, int(8 * npix, c_size_t))
+        if (rc == 0) rc = ndsmk_partition(ns2, xs, ys, d(1), thr, max_patches, cnt, d(2), d(3), d(4), d(5), d(6), d(7), &
+                                          d(8))
+        if (rc == 0) rc = ndsmk_d2h(label, d(2), int(4 * npix, c_size_t))
+        rows = 0
+        if (rc == 0) rows = min(cnt(2), max_patches)
+        do i = 1, 6
+          nb = int(width(i) * rows, c_size_t)
+          if (rc == 0 .and. nb > 0) rc = ndsmk_d2h(rec(i), d(2 + i), nb)
+        end do
+        i = ndsmk_free(buf)
+        if (rc == 0) rc = int(i, c_int)
+      end if
+    end if
+    if (rc == 0) rc = ndsmk_sync()
+    ierr = reported(who, rc)
+    if (ierr /= 0) call clear_outputs()
+  contains
+    subroutine clear_outputs()
+      call clear_host([counts], [8], [2_c_int64_t])
+      if (on_device) return
+      if (shape_ok) call clear_host([label], [4], [product(int(ns2, c_int64_t))])
+      if (max_patches <= 0 .or. max_patches > huge(0_c_int64_t) / 8) return
+      call clear_host(rec, width, [max_patches, max_patches, max_patches, max_patches, max_patches, max_patches])
+    end subroutine
+  end function
+
   ! The open-box potential field: ndsm_hip_green_box_device (which = 0) on the handle's mesh into the device B, then
   ! ndsm_hip_vecpot_solve_device - bit for bit that composition, no field crossing PCIe in between.  A: in the first
   ! guess, out A; B: out (its interior nodes are read by nothing).  HOST arrays (nx,ny,nz,3), bz (nsx,nsy)
@@ -2738,6 +2868,81 @@ contains
       if (max_dips > huge(0_c_int64_t) / 24) return
       call clear_host([edge, pos, bpt, grad, curv, flag], [8, 24, 24, 24, 8, 4], &
                       [max_dips, max_dips, max_dips, max_dips, max_dips, max_dips])
+    end subroutine
+  end function
+
+  ! ---- patch connectivity on the same handle ---------------------------------
+  ! B (nx,ny,nz,3) and label (nx,ny; int32) in, K >= 0 the largest label that counts; step, max_steps as the trace
+  ! entry's; max_pairs >= 0 the capacity of the pair arrays; counts (2, int64, on the HOST in both entries): lines
+  ! traced, distinct pairs.  Out per pixel: dest (int32), ends (3 each), length, status (int32); the first min(counts(2),
+  ! max_pairs) pairs in ascending (a, c): pa, pc (int32), nlines (int64), pflux.  The handle supplies the mesh; no solve
+  ! runs.  Return value: 0, or >= 9001 errors (9002 a NULL handle, B, label, counts or per-pixel array, or with max_pairs
+  ! > 0 a NULL pair array; 9004 K < 0, max_pairs < 0, step not > 0, max_steps < 1).  On every failure counts is cleared,
+  ! and the host entry clears its per-pixel arrays and the max_pairs slots of its pair arrays.
+
+  ! HOST arrays
+  function ndsm_hip_vecpot_connect(handle, B, label, K, step, max_steps, max_pairs, counts, dest, ends, length, status, &
+                                   pa, pc, nlines, pflux) bind(c, name="ndsm_hip_vecpot_connect") result(ierr)
+    type(c_ptr), value :: handle, B, label, counts, dest, ends, length, status, pa, pc, nlines, pflux
+    integer(c_int), value :: K, max_steps
+    real(c_double), value :: step
+    integer(c_int64_t), value :: max_pairs
+    integer(c_int) :: ierr
+    ierr = connect_entry(handle, B, label, K, step, max_steps, max_pairs, counts, [dest, ends, length, status], &
+                         [pa, pc, nlines, pflux], .false., "ndsm_hip_vecpot_connect")
+  end function
+
+  ! the same on DEVICE arrays of the library's GPU (counts stays a host array; no output is touched on the host)
+  function ndsm_hip_vecpot_connect_device(handle, dB, dlabel, K, step, max_steps, max_pairs, counts, ddest, dends, dlength, &
+                                          dstatus, dpa, dpc, dnlines, dpflux) &
+      bind(c, name="ndsm_hip_vecpot_connect_device") result(ierr)
+    type(c_ptr), value :: handle, dB, dlabel, counts, ddest, dends, dlength, dstatus, dpa, dpc, dnlines, dpflux
+    integer(c_int), value :: K, max_steps
+    real(c_double), value :: step
+    integer(c_int64_t), value :: max_pairs
+    integer(c_int) :: ierr
+    ierr = connect_entry(handle, dB, dlabel, K, step, max_steps, max_pairs, counts, [ddest, dends, dlength, dstatus], &
+                         [dpa, dpc, dnlines, dpflux], .true., "ndsm_hip_vecpot_connect_device")
+  end function
+
+  function connect_entry(handle, B, label, K, step, max_steps, max_pairs, counts, pix, pair, on_device, who) result(ierr)
+    type(c_ptr), intent(in) :: handle, B, label, counts, pix(4), pair(4)
+    integer(c_int), intent(in) :: K, max_steps
+    real(c_double), intent(in) :: step
+    integer(c_int64_t), intent(in) :: max_pairs
+    logical, intent(in) :: on_device
+    character(len=*), intent(in) :: who
+    integer(c_int) :: ierr
+    type(vecpot_ctx), pointer :: ctx
+    integer(c_int64_t), pointer :: cnt(:)
+    integer :: i
+    logical :: complete
+    call clear_host([counts], [8], [2_c_int64_t])
+    ierr = live_ctx(handle, ctx)
+    if (ierr /= 0) return
+    ierr = NDSMK_EARG
+    complete = c_associated(B) .and. c_associated(label) .and. c_associated(counts)
+    do i = 1, 4
+      complete = complete .and. c_associated(pix(i)) .and. (max_pairs <= 0 .or. c_associated(pair(i)))
+    end do
+    if (.not. complete) then
+      call clear_outputs()
+      return
+    end if
+    call c_f_pointer(counts, cnt, [2])
+    ierr = reported(who, vecpot_connect(ctx, B, label, K, step, max_steps, max_pairs, cnt, pix(1), pix(2), pix(3), pix(4), &
+                                        pair(1), pair(2), pair(3), pair(4), on_device))
+    if (ierr /= 0) call clear_outputs()
+  contains
+    ! counts, and (host entry) the per-pixel arrays and the max_pairs slots of every pair array
+    subroutine clear_outputs()
+      integer(c_int64_t) :: np
+      call clear_host([counts], [8], [2_c_int64_t])
+      if (on_device) return
+      np = int(ctx%n3(1), c_int64_t) * int(ctx%n3(2), c_int64_t)
+      call clear_host(pix, [4, 24, 8, 4], [np, np, np, np])
+      if (max_pairs <= 0 .or. max_pairs > huge(0_c_int64_t) / 8) return
+      call clear_host(pair, [4, 4, 8, 8], [max_pairs, max_pairs, max_pairs, max_pairs])
     end subroutine
   end function
 

@@ -901,6 +901,36 @@ module ndsmh_iface
       integer(c_int) :: rc
     end function
 
+    ! ---- flux partitioning of a magnetogram (partition.hip) and patch connectivity (connect.hip) ----
+    function ndsmk_partition_fits(nsrc2, caller_bytes) bind(c, name="ndsmk_partition_fits") result(rc)
+      import :: c_int, c_int32_t, c_double
+      integer(c_int32_t), intent(in) :: nsrc2(2)
+      real(c_double), value :: caller_bytes
+      integer(c_int) :: rc
+    end function
+    function ndsmk_partition(nsrc2, h_xs, h_ys, bz, thr, max_patches, counts2, label, root, sign, npix, flux, sx, sy) &
+        bind(c, name="ndsmk_partition") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_int64_t, c_double
+      integer(c_int32_t), intent(in) :: nsrc2(2)
+      type(c_ptr), value :: h_xs, h_ys, bz, label, root, sign, npix, flux, sx, sy
+      real(c_double), value :: thr
+      integer(c_int64_t), value :: max_patches
+      integer(c_int64_t), intent(out) :: counts2(2)
+      integer(c_int) :: rc
+    end function
+    function ndsmk_connect(B, n3, lo3, dq3, h_x, h_y, label, K, step, max_steps, max_pairs, counts2, dest, ends, length, &
+                           status, pa, pc, nlines, pflux) bind(c, name="ndsmk_connect") result(rc)
+      import :: c_ptr, c_int, c_int32_t, c_int64_t, c_double
+      type(c_ptr), value :: B, label, dest, ends, length, status, pa, pc, nlines, pflux
+      integer(c_int32_t), intent(in) :: n3(3)
+      real(c_double), intent(in) :: lo3(3), dq3(3), h_x(*), h_y(*)
+      integer(c_int), value :: K, max_steps
+      real(c_double), value :: step
+      integer(c_int64_t), value :: max_pairs
+      integer(c_int64_t), intent(out) :: counts2(2)
+      integer(c_int) :: rc
+    end function
+
     ! ---- field-line paths (paths.hip): the counting half (blocks for total) and the filling half ----
     function ndsmk_paths_count(B, G, n3, lo3, dq3, nseeds, seeds, step, max_steps, direction, every, max_points, ends, &
                                length, integral, status, nsteps, offsets, total) bind(c, name="ndsmk_paths_count") result(rc)

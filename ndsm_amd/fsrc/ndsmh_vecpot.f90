@@ -36,6 +36,7 @@ module ndsmh_vecpot
   public :: vecpot_optimize_cascade, vecpot_ref, vecpot_optimize_obs, descent_ctl
   public :: vecpot_project, vecpot_devore, vecpot_lines, vecpot_paths, vecpot_nulls, vecpot_skeleton, vecpot_separators
   public :: vecpot_dips
+  public :: vecpot_connect
   public :: VP_POTENTIAL, VP_FIELD, VP_HELICITY, VP_CURRENT, VP_NLFFF
   ! pieces the distributed driver (ndsmh_wvecpot) shares with vecpot_solve
   public :: face_data, face_axis, face_upper, face_t1, face_t2, face_order, face_copy, vecpot_faces, say
@@ -2304,6 +2305,59 @@ contains
     if (rc == 0) rc = fetch(s, rows=int(min(counts(2), max_dips), c_size_t))
     if (rc == 0) rc = ndsmk_sync()
     call unstage(rc, [buf])
+  end function
+
+  ! ------------------------------------------------------------------
+  ! The connectivity entries on a prepared context (semantics in include/ndsm_hip.h, DESIGN.md "Flux partitioning and
+  ! connectivity"): one field line from every labelled pixel of the lower face and the (patch, class) pairs
+  ! (ndsmk_connect).  The context supplies the mesh, its x and y vectors being the seeds; no solve.  pB (nx,ny,nz,3) and
+  ! plabel (nx,ny; int32) in; counts(2) out on the host: lines traced, distinct pairs; per pixel pdest (int32), pends (3
+  ! each), plen, pstat (int32) and the first min(counts(2), max_pairs) pairs ppa, ppc (int32), pnl (int64), ppf out - on
+  ! the HOST (B goes up into the staging array dF(1), the rest through one scratch buffer) or (on_device) in HBM.
+  ! ------------------------------------------------------------------
+  function vecpot_connect(ctx, pB, plabel, K, step, max_steps, max_pairs, counts, pdest, pends, plen, pstat, ppa, ppc, &
+                          pnl, ppf, on_device) result(rc)
+    type(vecpot_ctx), intent(inout), target :: ctx
+    logical, intent(in) :: on_device
+    type(c_ptr), intent(in) :: pB, plabel, pdest, pends, plen, pstat, ppa, ppc, pnl, ppf
+    integer(c_int), intent(in) :: K, max_steps
+    real(wp), intent(in) :: step
+    integer(c_int64_t), intent(in) :: max_pairs
+    integer(c_int64_t), intent(out) :: counts(2)
+    integer(c_int) :: rc
+    real(wp) :: dq(3), lo(3)
+    integer(c_int32_t) :: n3(3)
+    integer(c_size_t) :: np, nm
+    type(c_ptr) :: buf
+    type(slice) :: s(9)
+
+    counts = 0
+    call ctx_mesh(ctx, n3, lo, dq)
+    if (on_device .or. K < 0 .or. max_pairs < 0 .or. .not. (step > 0.0_wp) .or. max_steps < 1) then
+      ! (the argument errors are the kernel entry's to name; nothing is staged for them)
+      rc = ndsmk_connect(pB, n3, lo, dq, ctx%qx, ctx%qy, plabel, K, step, max_steps, max_pairs, counts, pdest, pends, &
+                         plen, pstat, ppa, ppc, pnl, ppf)
+      if (rc == 0) rc = ndsmk_sync()
+      return
+    end if
+    rc = stage_field(ctx, 1, pB); if (rc /= 0) return
+    np = int(n3(1), c_size_t) * int(n3(2), c_size_t)
+    nm = int(min(max_pairs, int(np, c_int64_t)), c_size_t)     ! (no more pairs than lines)
+    s = [slice(plabel, 4, np, GOES_UP), slice(pdest, 4, np, COMES_HOME), slice(pends, 24, np, COMES_HOME), &
+         slice(plen, 8, np, COMES_HOME), slice(pstat, 4, np, COMES_HOME), &
+         slice(ppa, 4, nm, COMES_HOME), slice(ppc, 4, nm, COMES_HOME), slice(pnl, 8, nm, COMES_HOME), &
+         slice(ppf, 8, nm, COMES_HOME)]
+    rc = carve(buf, s)
+    if (rc == 0) then
+      call say("find_connectivity", "Tracing from the lower face and summing the pairs...")
+      rc = ndsmk_connect(ctx%dF(1), n3, lo, dq, ctx%qx, ctx%qy, s(1)%dev, K, step, max_steps, max_pairs, counts, &
+                         s(2)%dev, s(3)%dev, s(4)%dev, s(5)%dev, s(6)%dev, s(7)%dev, s(8)%dev, s(9)%dev)
+    end if
+    if (rc == 0) rc = fetch(s(1:5))
+    if (rc == 0) rc = fetch(s(6:9), rows=int(min(counts(2), max_pairs), c_size_t))
+    if (rc == 0) rc = ndsmk_sync()
+    call unstage(rc, [buf])
+    if (rc /= 0) counts = 0
   end function
 
   ! B.n of face f (1..6) from the host field (extract_bn, :699-743)
